@@ -28,6 +28,8 @@ one 2^21-frame shard -- what each of eight GPUs does between two exchanges --, t
 After the timed region (untimed) the line's `config.parity` is made: the same level re-run on the plain FP64 sweep must give
 the same codebook bit for bit, and the per-frame outputs of the timed kernel are checked against the strict CPU oracle on a
 32 768-frame sample; a mismatch makes the run fail.
+The printed line leaves out documentation strings and the detail of the untimed extras; --report FILE writes the whole
+record.  --dump-outputs DIR saves what the last timed step computed (codebook and level statistics, .npy).
 """
 import argparse
 import json
@@ -519,10 +521,18 @@ def main():
     ap.add_argument("--collective", default="", help="--in-process: rccl | p2p (default: RCCL when every rank has a GPU of "
                     "its own, else the library's peer-to-peer kernel)")
     ap.add_argument("--no-parity", action="store_true", help="skip the untimed parity section (config.parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the level's codebook and its statistics, "
+                         "what a caller of e2vq_learn receives -- as DIR/<name>.npy (float64; rank 0)")
+    ap.add_argument("--report", metavar="FILE", default=None,
+                    help="write the whole record as one JSON line to FILE: the printed line leaves out the documentation "
+                         "strings and the detail of the untimed extras (anchor ladder, robustness table, small-corpus levels)")
     args = ap.parse_args()
     M = args.codebook_size
     if M < 4 or M & (M - 1):
         raise SystemExit("--codebook-size must be a power of two >= 4")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.no_prefilter:
         os.environ["ECOZ2_VQ_PREFILTER"] = "0"
     if args.in_process and "WORLD_SIZE" not in os.environ:
@@ -907,6 +917,36 @@ def quantize_section(e, torch, local, sess, S, M, sym, dmin):
     }
 
 
+def dump_outputs(d, np, sess, st):
+    """What the last timed step handed back: the codebook (reflections, M x (P+1)) and the LevelStats of the level -- or, when
+    --steps ends inside a level, of its last pass, with the codebook that pass swept"""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "codebook.npy"), sess.get_codebook())
+    np.save(os.path.join(d, "level_stats.npy"), np.array([st.M, st.passes, st.DD, st.avg_distortion, st.sigma, st.inertia,
+                                                           st.empty_cells, st.failed_cells], dtype=np.float64))
+
+
+DOC_KEYS = ("what", "note", "levels_note", "caveat")
+
+
+def result_line(out):
+    """The printed line: the record without its documentation strings, the untimed extras of N = 1 (anchor, robustness,
+    small corpus) cut to their scalar figures.  The whole record runs to tens of kB, more than a reader of one result line
+    can be relied on to take (--report FILE writes it)."""
+
+    def nodoc(x):
+        if isinstance(x, dict):
+            return {k: nodoc(v) for k, v in x.items() if k not in DOC_KEYS}
+        return [nodoc(v) for v in x] if isinstance(x, list) else x
+
+    line = nodoc(out)
+    c = line["config"]
+    for k in ("weak_scaling_anchor", "robustness", "small_corpus"):
+        if isinstance(c.get(k), dict):
+            c[k] = {kk: v for kk, v in c[k].items() if not isinstance(v, (dict, list))}
+    return line
+
+
 def run(args, comm):
     import numpy as np
     import torch
@@ -931,6 +971,8 @@ def run(args, comm):
 
     tm = lb.timed(args.steps, args.warmup)
     L, st = tm["L"], tm["st"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, sess, st)
     kernel_ms_total, kernel_passes, pass_kernels_ms_total = tm["kernel_ms_total"], tm["kernel_passes"], tm["pass_kernels_ms_total"]
     prefiltered, fallback_frames = tm["prefiltered"], tm["fallback_frames"]
     launches_before, timed_lds, timed_sweep, timed_plain = tm["launches_before"], tm["timed_lds"], tm["timed_sweep"], tm["timed_plain"]
@@ -1167,7 +1209,10 @@ def run(args, comm):
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(e, np)
             out["config"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
-        print(json.dumps(out), flush=True)
+        if args.report:
+            with open(args.report, "w") as f:
+                f.write(json.dumps(out) + "\n")
+        print(json.dumps(result_line(out)), flush=True)
     if lb is not None:
         lb.close()
     if parity is not None and not parity["ok"]:

@@ -44,16 +44,17 @@ def digest(cmd, path):
     if isinstance(an, dict) and "value" in an:
         print(f"\n  anchor ({an['frames']} frames on one GPU): value {an['value'] / 1e9:.4f} G frames/s, ms_per_step {an['ms_per_step']:.4f}, "
               f"kernel_ms {an['kernel_ms']:.4f}, {an['ksteps_per_pair']:.3f} k-steps per pair")
-        al = an["learn_end_to_end"]
-        print(f"  anchor ladder {al['seconds'] * 1e3:.2f} ms, passes {al['passes_per_level']}; per level kernel ms / step ms per pass: "
-              + ", ".join(f"M={l['M']}: {l['kernel_ms']:.3f} / {l['step_ms']:.3f}" for l in al["levels"]))
+        al = an.get("learn_end_to_end")  # (the printed line carries the anchor's scalars only: bench.py --report has the rest)
+        if al:
+            print(f"  anchor ladder {al['seconds'] * 1e3:.2f} ms, passes {al['passes_per_level']}; per level kernel ms / step ms per pass: "
+                  + ", ".join(f"M={l['M']}: {l['kernel_ms']:.3f} / {l['step_ms']:.3f}" for l in al["levels"]))
     elif an:
         print("\n  anchor " + json.dumps(an)[:300])
     rb = obj(c.get("robustness"))
     if isinstance(rb, dict):
         print(f"\n  robustness (M = {c.get('codebook_size')} level on {rb['frames']} frames; all equal the plain sweep: {rb['all_equal_plain_sweep']}; "
               f"worst product / fastest variant: {rb.get('worst_product_over_fastest')}):")
-        for g in rb["generators"]:
+        for g in rb.get("generators", []):
             if "error" in g:
                 print(f"    {g['generator']:22s} ERROR {g['error']}")
                 continue
@@ -79,8 +80,9 @@ def digest(cmd, path):
     sc = obj(c.get("small_corpus"))
     if isinstance(sc, dict):
         print("\n  small corpus " + json.dumps({k: v for k, v in sc.items() if k != "levels"}))
-        print("  small corpus per level kernel us / step us per pass: "
-              + ", ".join(f"M={l['M']}: {l['kernel_us_per_pass']} / {l['step_us_per_pass']}" for l in sc["levels"]))
+        if "levels" in sc:
+            print("  small corpus per level kernel us / step us per pass: "
+                  + ", ".join(f"M={l['M']}: {l['kernel_us_per_pass']} / {l['step_us_per_pass']}" for l in sc["levels"]))
     cb = d.get("cpu_baseline")
     if cb:
         print(f"\n  cpu_baseline {cb['value'] / 1e6:.2f} M frames/s on {cb['cores']} threads ({cb['kind']}): {cb['sample']}")
