@@ -17,4 +17,4 @@ from .vq import (  # noqa: F401
     vq_show,
     version,
 )
-from . import classify, formats, hmm, synth  # noqa: F401
+from . import classify, formats, hmm, lpc, synth  # noqa: F401

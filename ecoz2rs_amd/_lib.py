@@ -54,6 +54,8 @@ _sig("ecoz2_vq_quantize", C.c_int, C.c_char_p, c_char_pp, C.c_int, C.c_int)
 _sig("ecoz2_vq_show", C.c_int, C.c_char_p, C.c_int, C.c_int)
 _sig("ecoz2_prd_show_file", C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int)
 _sig("ecoz2_vq_classify", C.c_int, c_char_pp, C.c_int, c_char_pp, C.c_int, C.c_int)
+_sig("ecoz2_lpc_signals", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_char_pp, C.c_int, C.c_float, C.c_int)
+_sig("ecoz2_lpca", C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p)
 
 # Part 2: session API
 _sig("e2vq_last_error", C.c_char_p)
@@ -114,6 +116,15 @@ _sig("e2vq_cbook_info", C.c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.P
 _sig("e2vq_cbook_read", C.c_int, C.c_char_p, C.c_void_p, C.c_int)
 _sig("e2vq_cbook_write", C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p)
 _sig("e2vq_seq_write", C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64)
+_sig("e2vq_wav_info", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int))
+_sig("e2vq_wav_read", C.c_int, C.c_char_p, C.c_void_p, C.c_int64)
+_sig("e2vq_lpc_frame_count", C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+     C.POINTER(C.c_int64))
+_sig("e2vq_lpc_analyze", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+     C.c_int64, C.POINTER(C.c_int64), C.c_int)
+_sig("e2vq_lpc_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_lpca_batch", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p)
 _sig("e2vq_synth_frames", C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p)
 _sig("e2vq_synth_frames_kind", C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_void_p)
 

@@ -42,6 +42,8 @@ static int usage()
             "                  (-s|--sequences <files|dirs|tt.csv>... | --predictors <files|dirs|tt.csv>... --codebooks <files|dirs>...\n"
             "                   [--predictors-dir-template <t>])\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
+            "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
+            "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
             "  ecoz2 cversion\n");
     return 2;
 }
@@ -478,6 +480,70 @@ static int hmm_cmd(int argc, char** argv)
     return usage();
 }
 
+// `ecoz2 lpc`: LpcOpts and main_lpc of src/lpc/mod.rs:17-74, 87-143
+static int lpc_cmd(int argc, char** argv)
+{
+    int P = 36, W = 45, O = 15, minpc = 0;
+    float split = 0.f, mintrpt = 5.f;
+    bool verbose = false;
+    std::string tmpl = "data/signals", tt, cls;
+    std::vector<std::string> signals;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        auto num = [&](const char* name) -> long {
+            const char* v = val(name);
+            char* end = nullptr;
+            const long x = strtol(v, &end, 10);
+            if (!*v || *end || x < 0 || x > 1000000) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto real = [&](const char* name) -> float {
+            const char* v = val(name);
+            char* end = nullptr;
+            const float x = strtof(v, &end);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
+        else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
+        else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "-m" || a == "--minpc") minpc = (int)num("-m");
+        else if (a == "-s" || a == "--split") split = real("-s");
+        else if (a == "-X") mintrpt = real("-X");
+        else if (a == "--verbose") verbose = true;
+        else if (a == "--signals-dir-template") tmpl = val("--signals-dir-template");
+        else if (a == "--tt") tt = val("--tt");
+        else if (a == "--class") cls = val("--class");
+        else if (a == "--zrs" || a == "--zrsp") {
+            fprintf(stderr, "%s selects the reference's Rust variants, which write CBOR predictor files; not supported "
+                            "by this build (the default analysis writes the .prd format)\n",
+                    a.c_str());
+            return 2;
+        }
+        else if (a == "--signals") { while (i + 1 < argc && !is_flag(argv[i + 1])) signals.push_back(argv[++i]); }
+        else return usage();
+    }
+    if (signals.empty()) {
+        fprintf(stderr, "--signals <files|dirs|tt.csv>... is required\n");
+        return usage();
+    }
+    if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
+    if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
+    // utl::resolve_files3(&signals, tt, &class, "", signals_dir_template, ".wav") (src/lpc/mod.rs:103-110)
+    std::vector<std::string> files;
+    const bool tt_list = signals.size() == 1 && signals[0].size() > 4 &&
+                         signals[0].compare(signals[0].size() - 4, 4, ".csv") == 0;
+    int rc = tt_list ? e2vq_io::files_from_csv(signals[0], tt, cls, "", ".wav", &tmpl, files)
+                     : e2vq_io::resolve_filenames(signals, ".wav", files);
+    if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+    auto ptrs = cptrs(files);
+    return ecoz2_lpc_signals(P, W, O, minpc, split, ptrs.data(), (int)ptrs.size(), mintrpt, verbose ? 1 : 0) ? 1 : 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc >= 2 && !strcmp(argv[1], "cversion")) {
@@ -486,6 +552,7 @@ int main(int argc, char** argv)
     }
     if (argc >= 3 && !strcmp(argv[1], "seq") && !strcmp(argv[2], "show")) return seq_show(argc - 3, argv + 3);
     if (argc >= 3 && !strcmp(argv[1], "prd") && !strcmp(argv[2], "show")) return prd_show(argc - 3, argv + 3);
+    if (argc >= 2 && !strcmp(argv[1], "lpc")) return lpc_cmd(argc - 2, argv + 2);
     if (argc >= 3 && !strcmp(argv[1], "hmm")) return hmm_cmd(argc - 2, argv + 2);
     if (argc >= 3 && !strcmp(argv[1], "nb")) return seq_model_cmd(true, argc - 2, argv + 2);
     if (argc >= 3 && !strcmp(argv[1], "mm")) return seq_model_cmd(false, argc - 2, argv + 2);

@@ -82,6 +82,24 @@ int ecoz2_vq_classify(const char *const *cb_filenames, int num_codebooks,
  * vector (Levinson recursion of src/lpc/lpca_r_rs.rs:8-43 on its autocorrelation) instead of the r<n>. */
 int ecoz2_prd_show_file(const char *prd_filename, int show_reflections, int from, int to);
 
+/* replaces `fn ecoz2_lpc_signals(prediction_order, window_length_ms, offset_length_ms, minpc, split, sgn_filenames,
+ *           num_signals, mintrpt, verbose)`                    src/ecoz2_lib/mod.rs:77-87 (caller src/lpc/mod.rs:130-140)
+ * LPC analysis of mono 16/24/32-bit integer-PCM .wav files on the GPU: for every signal, frames of W_ms at offsets of O_ms,
+ * mean removal, pre-emphasis, Hamming window, autocorrelation + Levinson-Durbin, gain-normalised autocorrelations
+ * written to data/predictors/<class>/<stem>.prd (class = the name of the .wav's parent directory).  Bit-identical to the
+ * reference's Rust analysis (src/lpc/lpc_rs.rs, lpca_rs.rs:28-75).  A frame whose recursion fails
+ * (e.g. a digitally silent window) is left out of the .prd and counted on stdout.  minpc: a class is processed only with
+ * at least that many signals; split is deprecated and ignored; a signal taking at least mintrpt seconds has its time
+ * reported.  Returns 0 on success. */
+int ecoz2_lpc_signals(int prediction_order, int window_length_ms, int offset_length_ms, int minpc, float split,
+                      const char *const *sgn_filenames, int num_signals, float mintrpt, int verbose);
+
+/* replaces `fn ecoz2_lpca(x, n, p, r, rc, a, pe) -> c_int`   src/ecoz2_lib/lpca_c.rs:7-17
+ * lpca1 of src/lpc/lpca_rs.rs:28-75 on one windowed frame x[0..n), on the host (the same arithmetic as the kernel):
+ * r[0..p] autocorrelation, rc[1..p] reflections, a[0..p] predictor, *pe prediction error.
+ * Returns 0, 1 (r[0] == 0) or 2 (prediction error <= 0); -1 on bad arguments. */
+int ecoz2_lpca(double *x, int n, int p, double *r, double *rc, double *a, double *pe);
+
 /* Knobs the reference has no argument for: environment variables, none of which changes a result.  The one table of them
  * (19) is INTEGRATION.md section 2; the ones a caller of these entry points is likely to set:
  *   ECOZ2_VQ_MAX_CODEBOOK_SIZE  last codebook size trained (default 2048, notes.md:147)
@@ -260,6 +278,27 @@ int e2vq_cbook_info(const char *path, char class_name[96], int *P, int *M);
 int e2vq_cbook_read(const char *path, double *reflections, int capacity_codewords);
 int e2vq_cbook_write(const char *path, const char *class_name, int P, int M, const double *reflections);
 int e2vq_seq_write(const char *path, const char *class_name, int M, const uint16_t *sym, int64_t T);
+
+/* ---- LPC front-end (lpc_host.cpp, lpc_device.hip) ---------------------------------------------- */
+/* header of a .wav (host only): mono 16/24/32-bit integer PCM, anything else fails naming the file and the format */
+int e2vq_wav_info(const char *path, int *sample_rate, int64_t *num_samples, int *bits_per_sample);
+/* its samples as exact int32 values */
+int e2vq_wav_read(const char *path, int32_t *samples, int64_t capacity);
+/* frame geometry of src/lpc/lpc_rs.rs:203-218 (host only): win = W_ms sr / 1000, off = O_ms sr / 1000 (integer division;
+ * off == 0 fails), T frames; *T = -1 when the signal is shorter than one window */
+int e2vq_lpc_frame_count(int64_t num_samples, int sample_rate, int W_ms, int O_ms, int *win, int *off, int64_t *T);
+/* analysis of one signal in host memory on `device`: frames (T x (P+1) doubles, row-major; rows of failed frames are zeros)
+ * and status (T int32: 0 ok, 1 r[0] == 0, 2 prediction error <= 0) to host memory, or to device memory with on_device
+ * (then `frames` is accepted by e2vq_set_frames_device once the failed rows are dropped).  frames == NULL: *T only.
+ * A signal shorter than one window fails.  1 <= P <= 80. */
+int e2vq_lpc_analyze(int device, int P, int W_ms, int O_ms, const int32_t *samples, int64_t num_samples, int sample_rate,
+                     void *frames, int32_t *status, int64_t capacity_frames, int64_t *T, int on_device);
+/* HIP-event time of the analysis kernel of this thread's last e2vq_lpc_analyze (-1: none yet) */
+int e2vq_lpc_last_kernel_ms(float *ms);
+/* batched lpca1 on already-windowed frames x (count x n, row-major, host memory) on `device`: r, rc, a (count x (P+1)),
+ * pe and status (count), the same bits as ecoz2_lpca frame by frame (rc[0] = 0) */
+int e2vq_lpca_batch(int device, int P, const double *x, int n, int64_t count, double *r, double *rc, double *a, double *pe,
+                    int32_t *status);
 
 /* Synthetic gain-normalised autocorrelation frames [first, first+count) of the stream
  * (seed, n_classes): counter-based, so any shard regenerates identical frames. */
