@@ -125,6 +125,8 @@ _sig("e2vq_lpc_analyze", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p
 _sig("e2vq_lpc_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
 _sig("e2vq_lpca_batch", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p)
+_sig("e2vq_lpc_features", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_int)
 _sig("e2vq_synth_frames", C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p)
 _sig("e2vq_synth_frames_kind", C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_void_p)
 

@@ -8,10 +8,13 @@
 #include "../../include/ecoz2_vq.h"
 #include "vq_io.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -32,7 +35,8 @@ static int usage()
             "  ecoz2 vq classify [-r] --codebooks <files|dirs>... --tt <TRAIN|TEST> --predictors <files|dirs|tt.csv>...\n"
             "  ecoz2 vq show [-f <from>] [-t <to>] <codebook>\n"
             "  ecoz2 seq show [-c] [-L] [--full] [--pickle out.pkl -M <M> --tt <TRAIN|TEST> [--class-name c]] <file.seq|tt.csv>...\n"
-            "  ecoz2 prd show [-k] [--from a] [--to b] <file.prd>\n"
+            "  ecoz2 prd show [-k] [--predictors] [--cepstrum <Q>] [-f|--from a] [-t|--to b] [--zrs] [--pickle <out.pkl>]\n"
+            "                 <file.prd|predictor.cbor>\n"
             "  ecoz2 {nb|mm} learn -M <M> [--class-name <class>] <file.seq|dirs|tt.csv>...\n"
             "  ecoz2 {nb|mm} classify -M <M> [-r] --tt <TRAIN|TEST> --models <files|dirs>... --sequences <files|dirs|tt.csv>...\n"
             "  ecoz2 {nb|mm} show --model <file>\n"
@@ -207,24 +211,35 @@ static bool load_seq(const std::string& f, std::string& cls, unsigned& M, std::v
     return true;
 }
 
-// pickle (protocol 2) of a list of lists of ints: what `utl::to_pickle(&list_of_sequences, ..)` exports
-// (/root/reference/src/seq/mod.rs:88-112, src/utl/mod.rs:277-283); loads with Python's pickle.load
-static bool write_pickle(const std::string& path, const std::vector<std::vector<unsigned>>& seqs)
+// pickle (protocol 2) of a list of lists of ints or floats: what `utl::to_pickle(&list, ..)` exports
+// (the reference's src/seq/mod.rs:88-112, src/prd/mod.rs:174-188, src/utl/mod.rs:277-283); loads with Python's pickle.load
+static void pickle_item(FILE* fp, unsigned v)
+{
+    if (v < 256) { fputc('K', fp); fputc((int)v, fp); }                                   // BININT1
+    else if (v < 65536) { fputc('M', fp); fputc(v & 255, fp); fputc(v >> 8, fp); }        // BININT2
+    else { fputc('J', fp); for (int k = 0; k < 4; ++k) fputc((v >> (8 * k)) & 255, fp); } // BININT
+}
+
+static void pickle_item(FILE* fp, double v)
+{
+    uint64_t u;
+    memcpy(&u, &v, 8);
+    fputc('G', fp);  // BINFLOAT: big-endian IEEE double
+    for (int k = 7; k >= 0; --k) fputc((int)((u >> (8 * k)) & 255), fp);
+}
+
+template <typename V>
+static bool write_pickle(const std::string& path, const std::vector<std::vector<V>>& lists)
 {
     FILE* fp = fopen(path.c_str(), "wb");
     if (!fp) return false;
-    auto put_int = [&](unsigned v) {
-        if (v < 256) { fputc('K', fp); fputc((int)v, fp); }                                   // BININT1
-        else if (v < 65536) { fputc('M', fp); fputc(v & 255, fp); fputc(v >> 8, fp); }        // BININT2
-        else { fputc('J', fp); for (int k = 0; k < 4; ++k) fputc((v >> (8 * k)) & 255, fp); } // BININT
-    };
     fputc(0x80, fp); fputc(2, fp);  // PROTO 2
     fputc(']', fp);                 // EMPTY_LIST
     fputc('(', fp);                 // MARK
-    for (const auto& s : seqs) {
+    for (const auto& s : lists) {
         fputc(']', fp);
         fputc('(', fp);
-        for (unsigned v : s) put_int(v);
+        for (const V& v : s) pickle_item(fp, v);
         fputc('e', fp);             // APPENDS
     }
     fputc('e', fp);
@@ -297,22 +312,143 @@ static int seq_show(int argc, char** argv)
     return 0;
 }
 
-// `ecoz2 prd show [-k|--reflections] [-f|--from a] [-t|--to b] <file>` (options: src/prd/mod.rs:30-62; from defaults to 1,
-// to = 0 means P) -> ecoz2_prd_show_file, the symbol the reference binds (src/ecoz2_lib/mod.rs:89-94, src/prd/mod.rs:99)
+// `ecoz2 prd show [--predictors] [-k|--reflections] [--cepstrum Q] [-f|--from a] [-t|--to b] [--zrs] [--pickle FILE]
+// <file>` (options: src/prd/mod.rs:30-62; from defaults to 1, to = 0 means the last column).  Without the new options:
+// ecoz2_prd_show_file, the symbol the reference binds (src/ecoz2_lib/mod.rs:89-94, src/prd/mod.rs:99), unchanged.
+// With any of --predictors, --cepstrum, --pickle or --zrs: prd_show_rs / Predictor::show (src/prd/mod.rs:105-225) on
+// the same frames, the features computed by e2vq_lpc_features; the input may also be a CBOR predictor document.
+
+// Rust's `{:.4e}` (|v| < 0.00001) or `{:.5}` of an f64: exponent without '+' or padding, NaN, inf, -inf
+static void put_rust(double v)
+{
+    if (std::isnan(v)) { fputs("NaN", stdout); return; }
+    if (std::isinf(v)) { fputs(v < 0 ? "-inf" : "inf", stdout); return; }
+    char buf[64];
+    if (fabs(v) < 0.00001) {
+        snprintf(buf, sizeof buf, "%.4e", v);
+        char* e = strchr(buf, 'e');
+        snprintf(e, sizeof buf - (size_t)(e - buf), "e%d", atoi(e + 1));
+    } else {
+        snprintf(buf, sizeof buf, "%.5f", v);
+    }
+    fputs(buf, stdout);
+}
+
+static int device_of_env()
+{
+    const char* v = getenv("ECOZ2_VQ_DEVICE");
+    return v && *v ? atoi(v) : 0;
+}
+
+static bool parse_count(const char* v, long* out)
+{
+    char* end = nullptr;
+    const long x = strtol(v, &end, 10);
+    if (!*v || *end || x < 0 || x > 1000000000L) return false;
+    *out = x;
+    return true;
+}
+
+static int prd_show_rs(const std::string& file, bool predictors, bool refl, long cepstrum, long from, long to,
+                       const std::string& pickle)
+{
+    std::string cls;
+    int P = 0;
+    std::vector<double> r;
+    if (e2vq_io::predictor_load(file.c_str(), cls, P, r)) { printf("%s\n", e2vq_last_error()); return 0; }
+    const int NC = P + 1;
+    const int64_t T = (int64_t)(r.size() / (size_t)NC);
+    printf("# %s\n", file.c_str());
+    if (cepstrum >= 0 && cepstrum <= P) {
+        fflush(stdout);
+        fprintf(stderr, "cepstrum value=%ld must be > prediction order=%d", cepstrum, P);
+        return 0;
+    }
+    const int Q = cepstrum > 0 ? (int)std::min<long>(cepstrum, INT32_MAX) : 0;
+    long to_;
+    const char* name;
+    int width;  // values per vector
+    std::vector<double> feat;
+    std::vector<int32_t> status;
+    std::vector<double> pe;
+    int rc = 0;
+    if (Q > 0) {
+        to_ = to == 0 || to >= Q ? Q - 1 : to;
+        name = "c";
+        width = Q;
+        if (Q > E2VQ_LPC_FEATURES_MAX_Q) {
+            fprintf(stderr, "cepstrum value=%d exceeds the limit of %d\n", Q, E2VQ_LPC_FEATURES_MAX_Q);
+            return 1;
+        }
+        feat.resize((size_t)T * Q);
+        status.resize((size_t)T);
+        pe.resize((size_t)T);
+        rc = e2vq_lpc_features(device_of_env(), P, Q, r.data(), T, status.data(), pe.data(), nullptr,
+                               nullptr, feat.data(), 0);
+    } else {
+        to_ = to == 0 || to > P ? P : to;
+        name = predictors ? "a" : refl ? "k" : "r";
+        width = NC;
+        if (predictors || refl) {
+            feat.resize((size_t)T * NC);
+            rc = e2vq_lpc_features(device_of_env(), P, 0, r.data(), T, nullptr, nullptr,
+                                   refl && !predictors ? feat.data() : nullptr, predictors ? feat.data() : nullptr,
+                                   nullptr, 0);
+        } else {
+            feat.swap(r);
+        }
+    }
+    if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+    for (int64_t t = 0; t < (int64_t)status.size(); ++t)  // get_cepstrum's warnings (src/prd/mod.rs:252-257)
+        if (status[t] != 0) fprintf(stderr, "WARNING: lpca_r: res_lpca = %d, err_pred = %.17g\n", status[t], pe[t]);
+    if (from > to_ + 1) {  // Rust: a slice-index panic
+        fflush(stdout);
+        fprintf(stderr, "range %ld..=%ld out of bounds for vectors of length %d\n", from, to_, width);
+        return 1;
+    }
+    if (!pickle.empty()) {
+        std::vector<std::vector<double>> list((size_t)T);
+        for (int64_t t = 0; t < T; ++t)
+            list[(size_t)t].assign(feat.begin() + t * width + from, feat.begin() + t * width + to_ + 1);
+        if (!write_pickle(pickle, list)) { printf("%s: cannot write\n", pickle.c_str()); return 0; }
+        printf("%lld vectors(s) saved to \"%s\"\n", (long long)T, pickle.c_str());
+        return 0;
+    }
+    printf("# class_name='%s', T=%lld P=%d\n", cls.c_str(), (long long)T, P);
+    for (long i = from; i <= to_; ++i) printf("%s%s%ld", i == from ? "" : ",", name, i);
+    printf("\n");
+    for (int64_t t = 0; t < T; ++t) {
+        const double* v = feat.data() + t * width;
+        for (long i = from; i <= to_; ++i) {
+            if (i > from) fputs(", ", stdout);
+            put_rust(v[i]);
+        }
+        printf("\n");
+    }
+    return 0;
+}
+
 static int prd_show(int argc, char** argv)
 {
-    int from = 1, to = 0, refl = 0;
-    std::string file;
+    long from = 1, to = 0, cepstrum = -1;
+    int refl = 0;
+    bool predictors = false, zrs = false;
+    std::string file, pickle;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
-        if ((a == "--from" || a == "-f") && i + 1 < argc) from = atoi(argv[++i]);
-        else if ((a == "--to" || a == "-t") && i + 1 < argc) to = atoi(argv[++i]);
+        if ((a == "--from" || a == "-f") && i + 1 < argc) { if (!parse_count(argv[++i], &from)) return usage(); }
+        else if ((a == "--to" || a == "-t") && i + 1 < argc) { if (!parse_count(argv[++i], &to)) return usage(); }
         else if (a == "-k" || a == "--reflections") refl = 1;
+        else if (a == "--predictors") predictors = true;
+        else if (a == "--cepstrum" && i + 1 < argc) { if (!parse_count(argv[++i], &cepstrum)) return usage(); }
+        else if (a == "--pickle" && i + 1 < argc) pickle = argv[++i];
+        else if (a == "--zrs") zrs = true;
         else if (!is_flag(argv[i])) file = a;
         else return usage();
     }
     if (file.empty()) return usage();
-    ecoz2_prd_show_file(file.c_str(), refl, from, to);
+    if (predictors || cepstrum >= 0 || !pickle.empty() || zrs) return prd_show_rs(file, predictors, refl, cepstrum, from, to, pickle);
+    ecoz2_prd_show_file(file.c_str(), refl, (int)from, (int)to);
     return 0;
 }
 

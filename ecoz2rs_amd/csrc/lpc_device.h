@@ -32,6 +32,10 @@ int launch_signals(int P, const int32_t* samples, const Frame* tab, int64_t n_en
 // Levinson on already-windowed frames x (nframes x n, row-major): r, rc, a (nframes x (P + 1)), pe, status
 int launch_windowed(int P, const double* x, int n, int64_t nframes, double* r, double* rc, double* a, double* pe,
                     int32_t* status, hipStream_t stream);
+// features of stored LPC vectors (lpc_features.hip): frames T x (P + 1) -> status, pe, rc, a (T x (P + 1)), c (T x Q);
+// a NULL output is neither computed nor stored (c == NULL: no cepstrum); c[0] = log(sqrt(pe)) from the device log.
+int launch_features(int P, int Q, const double* frames, int64_t T, int32_t* status, double* pe, double* rc, double* a,
+                    double* c, hipStream_t stream);
 // true when order P has a lane-per-frame instantiation (else the generic path runs)
 bool lane_path(int P);
 

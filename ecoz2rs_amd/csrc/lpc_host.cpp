@@ -664,3 +664,62 @@ extern "C" int ecoz2_lpc_signals(int P, int W_ms, int O_ms, int minpc, float spl
     fputs(pending.c_str(), stdout);
     return 0;
 }
+
+// ---- e2vq_lpc_features: features of stored LPC vectors (lpc_features.hip) ------------------------------------------
+extern "C" int e2vq_lpc_features(int device, int P, int Q, const double* frames, int64_t T, int32_t* status, double* pe,
+                                 double* rc, double* a, double* c, int on_device)
+{
+    if (P < 1 || P > E2VQ_LPC_MAX_P) return e2vq_set_error("lpc features: prediction order %d out of range [1, %d]", P, E2VQ_LPC_MAX_P);
+    if (Q < 0 || (Q > 0 && Q <= P)) return e2vq_set_error("lpc features: cepstrum length %d must be > prediction order %d", Q, P);
+    if (Q > E2VQ_LPC_FEATURES_MAX_Q)
+        return e2vq_set_error("lpc features: cepstrum length %d exceeds the limit of %d", Q, E2VQ_LPC_FEATURES_MAX_Q);
+    if (!frames || T < 0) return e2vq_set_error("e2vq_lpc_features: bad arguments");
+    if (Q == 0) c = nullptr;
+    if (have_device()) return 1;
+    if (T == 0) return 0;
+    Analyzer an;
+    if (an.init(device, P)) return 1;
+    const int NC = P + 1;
+    if (on_device) {
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        for (auto& x : ev) HIPCHK(hipEventCreate(&x));
+        struct Release {
+            hipEvent_t* e;
+            ~Release() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
+        } release{ev};
+        HIPCHK(hipEventRecord(ev[0], an.st.s));
+        if (e2lpc::launch_features(P, Q, frames, T, status, pe, rc, a, c, an.st.s))
+            return e2vq_set_error("lpc features kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        HIPCHK(hipEventRecord(ev[1], an.st.s));
+        HIPCHK(hipStreamSynchronize(an.st.s));
+        HIPCHK(hipEventElapsedTime(&g_last_kernel_ms, ev[0], ev[1]));
+        return 0;
+    }
+    // host memory: chunks of frames through device buffers; c[0] is then replaced by the C library's log(sqrt(pe))
+    const int64_t CH = std::min<int64_t>(T, (int64_t)1 << 18);
+    const bool need_pe = pe || c;
+    DevMem din, dst, dpe, drc, da, dc;
+    if (din.reserve((size_t)CH * NC * 8) || (status && dst.reserve((size_t)CH * 4)) || (need_pe && dpe.reserve((size_t)CH * 8)) ||
+        (rc && drc.reserve((size_t)CH * NC * 8)) || (a && da.reserve((size_t)CH * NC * 8)) || (c && dc.reserve((size_t)CH * Q * 8)))
+        return 1;
+    std::vector<double> pe_tmp;
+    if (c && !pe) pe_tmp.resize((size_t)CH);
+    for (int64_t t0 = 0; t0 < T; t0 += CH) {
+        const int64_t n = std::min(CH, T - t0);
+        HIPCHK(hipMemcpyAsync(din.p, frames + t0 * NC, (size_t)n * NC * 8, hipMemcpyHostToDevice, an.st.s));
+        if (e2lpc::launch_features(P, Q, din.as<double>(), n, status ? dst.as<int32_t>() : nullptr,
+                                   need_pe ? dpe.as<double>() : nullptr, rc ? drc.as<double>() : nullptr,
+                                   a ? da.as<double>() : nullptr, c ? dc.as<double>() : nullptr, an.st.s))
+            return e2vq_set_error("lpc features kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        double* pe_h = pe ? pe + t0 : pe_tmp.data();
+        if (status) HIPCHK(hipMemcpyAsync(status + t0, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, an.st.s));
+        if (need_pe) HIPCHK(hipMemcpyAsync(pe_h, dpe.p, (size_t)n * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (rc) HIPCHK(hipMemcpyAsync(rc + t0 * NC, drc.p, (size_t)n * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (a) HIPCHK(hipMemcpyAsync(a + t0 * NC, da.p, (size_t)n * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (c) HIPCHK(hipMemcpyAsync(c + t0 * Q, dc.p, (size_t)n * Q * 8, hipMemcpyDeviceToHost, an.st.s));
+        HIPCHK(hipStreamSynchronize(an.st.s));
+        if (c)
+            for (int64_t t = 0; t < n; ++t) c[(t0 + t) * Q] = log(sqrt(pe_h[t]));
+    }
+    return 0;
+}

@@ -457,6 +457,44 @@ static int seq_open(const char* path, FILE** fp, char class_name[96], uint32_t* 
     return 0;
 }
 
+int e2vq_io::predictor_load(const char* path, std::string& class_name, int& P, std::vector<double>& vectors)
+{
+    FILE* f = fopen(path, "rb");
+    if (!f) return e2vq_set_error("%s: %s", path, strerror(errno));
+    const int b0 = fgetc(f);
+    fclose(f);
+    if (b0 == EOF) return e2vq_set_error("%s: empty file", path);
+    if ((b0 >> 5) != 5) {  // not a CBOR map: the binary .prd
+        char cls[96];
+        int64_t T;
+        if (e2vq_prd_info(path, cls, &P, &T)) return 1;
+        class_name = cls;
+        vectors.assign((size_t)T * (P + 1), 0.0);
+        return T > 0 ? prd_read_range(path, P, 0, T, vectors.data()) : 0;
+    }
+    CborVal doc;
+    if (parse_cbor(path, doc)) return 1;
+    const CborVal *c = doc.get("class_name"), *p = doc.get("prediction_order"), *v = doc.get("vectors");
+    if (!c || c->kind != CborVal::TEXT || !p || p->kind != CborVal::UINT || p->u < 1 || p->u > 80 || !v ||
+        v->kind != CborVal::ARRAY)
+        return e2vq_set_error("%s: not a predictor document", path);
+    class_name = c->s;
+    P = (int)p->u;
+    vectors.clear();
+    vectors.reserve(v->items.size() * (size_t)(P + 1));
+    for (const CborVal& row : v->items) {
+        if (row.kind != CborVal::ARRAY || row.items.size() != (size_t)(P + 1))
+            return e2vq_set_error("%s: predictor vector of %zu values, expected %d", path,
+                                  row.kind == CborVal::ARRAY ? row.items.size() : (size_t)0, P + 1);
+        for (const CborVal& x : row.items) {
+            double d;
+            if (!x.number(&d)) return e2vq_set_error("%s: predictor vector with a non-number", path);
+            vectors.push_back(d);
+        }
+    }
+    return 0;
+}
+
 extern "C" int e2vq_seq_info(const char* path, char class_name[96], int* M, int64_t* T)
 {
     FILE* f = nullptr;

@@ -27,5 +27,9 @@ int seq_create(const char* path, const char* class_name, int M, int64_t T);
 int seq_write_range(const char* path, int64_t t0, const uint16_t* sym, int64_t n);
 // Levinson-Durbin on the host (src/lpc/lpca_r_rs.rs:8-43): status 0 / 1 (r0 == 0) / 2 (prediction error <= 0)
 int lpca_r_host(int P, const double* r, double* rc, double* a);
+// a predictor file of either format, told apart by its first byte: the binary .prd (a text header) or the reference's
+// CBOR `Predictor` document {class_name, prediction_order, vectors} (src/prd/mod.rs:128-133, written by utl::save_ser;
+// any well-formed encoding, short floats included).  vectors: row-major T x (P + 1)
+int predictor_load(const char* path, std::string& class_name, int& P, std::vector<double>& vectors);
 int io_threads();  // reader threads per rank / worker
 }  // namespace e2vq_io

@@ -98,3 +98,68 @@ def lpca_batch(x, p, device=0):
     check(lib.e2vq_lpca_batch(int(device), int(p), x.ctypes.data, n, count, r.ctypes.data, rc.ctypes.data, a.ctypes.data,
                               pe.ctypes.data, st.ctypes.data))
     return st, pe, r, rc, a
+
+
+FEATURES = ("status", "pe", "rc", "a", "c")
+MAX_Q = 1024  # E2VQ_LPC_FEATURES_MAX_Q
+
+
+def features(frames, q=0, device=0, want=FEATURES):
+    """LPC features of stored vectors r (T, P+1) float64 -> dict of the outputs named in ``want``:
+    status (T,) int32, pe (T,), rc and a (T, P+1), c (T, q) (only when q > 0; P < q <= MAX_Q).
+
+    lpca_r (src/lpc/lpca_r_rs.rs) and lpca_get_cepstrum (src/lpc/lpca_cepstrum_rs.rs) of the reference, bit for bit
+    (DESIGN.md 8.1).  status 1 (r[0] == 0) rows are zeros; status 2 rows keep what the recursion left; every row gets a
+    cepstrum.  A numpy array in gives numpy arrays out (c[0] = the C library's log(sqrt(pe))); a CUDA/HIP torch tensor
+    gives tensors on its device, with no host copy (c[0] from the device log, within 1 ulp of the host's)."""
+    want = tuple(want)
+    if q == 0 and want == FEATURES:  # the default: everything there is
+        want = FEATURES[:-1]
+    bad = [w for w in want if w not in FEATURES]
+    if bad:
+        raise ValueError(f"want: names among {FEATURES}, not {bad}")
+    if "c" in want and q == 0:
+        raise ValueError("want 'c' needs q > 0")
+    is_torch = type(frames).__module__.startswith("torch")
+    if is_torch:
+        import torch
+
+        if not frames.is_cuda or frames.dtype != torch.float64 or frames.dim() != 2:
+            raise TypeError("frames: a 2-D torch.float64 tensor on a CUDA/HIP device, or a numpy array")
+        fr = frames.contiguous()
+        dev = fr.device
+        T, NC = fr.shape
+        out = {}
+        for w in want:
+            if w == "status":
+                out[w] = torch.empty(T, dtype=torch.int32, device=dev)
+            elif w == "pe":
+                out[w] = torch.empty(T, dtype=torch.float64, device=dev)
+            elif w == "c":
+                out[w] = torch.empty((T, q), dtype=torch.float64, device=dev)
+            else:
+                out[w] = torch.empty((T, NC), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda w: out[w].data_ptr() if w in out and T > 0 else None  # noqa: E731
+        check(lib.e2vq_lpc_features(dev.index if dev.index is not None else int(device), NC - 1, int(q),
+                                    fr.data_ptr() if T > 0 else 1, T, ptr("status"), ptr("pe"), ptr("rc"), ptr("a"),
+                                    ptr("c"), 1))
+        return out
+    fr = np.ascontiguousarray(frames, dtype=np.float64)
+    if fr.ndim != 2:
+        raise TypeError("frames: a (T, P+1) array")
+    T, NC = fr.shape
+    out = {}
+    for w in want:
+        if w == "status":
+            out[w] = np.zeros(T, dtype=np.int32)
+        elif w == "pe":
+            out[w] = np.zeros(T)
+        elif w == "c":
+            out[w] = np.zeros((T, q))
+        else:
+            out[w] = np.zeros((T, NC))
+    ptr = lambda w: out[w].ctypes.data if w in out else None  # noqa: E731
+    check(lib.e2vq_lpc_features(int(device), NC - 1, int(q), fr.ctypes.data, T, ptr("status"), ptr("pe"), ptr("rc"),
+                                ptr("a"), ptr("c"), 0))
+    return out

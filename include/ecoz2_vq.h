@@ -293,12 +293,21 @@ int e2vq_lpc_frame_count(int64_t num_samples, int sample_rate, int W_ms, int O_m
  * A signal shorter than one window fails.  1 <= P <= 80. */
 int e2vq_lpc_analyze(int device, int P, int W_ms, int O_ms, const int32_t *samples, int64_t num_samples, int sample_rate,
                      void *frames, int32_t *status, int64_t capacity_frames, int64_t *T, int on_device);
-/* HIP-event time of the analysis kernel of this thread's last e2vq_lpc_analyze (-1: none yet) */
+/* HIP-event time of the kernel of this thread's last e2vq_lpc_analyze or device-resident e2vq_lpc_features (-1: none yet) */
 int e2vq_lpc_last_kernel_ms(float *ms);
 /* batched lpca1 on already-windowed frames x (count x n, row-major, host memory) on `device`: r, rc, a (count x (P+1)),
  * pe and status (count), the same bits as ecoz2_lpca frame by frame (rc[0] = 0) */
 int e2vq_lpca_batch(int device, int P, const double *x, int n, int64_t count, double *r, double *rc, double *a, double *pe,
                     int32_t *status);
+/* LPC vectors (T x (P+1), row-major) -> status, pe, rc, a (T x (P+1)), c (T x Q); any output may be NULL;
+ * Q == 0: no cepstrum, else P < Q <= E2VQ_LPC_FEATURES_MAX_Q.  on_device: `frames` and every output are device pointers on
+ * `device` (c[0] from the device log), else host pointers (c[0] = log(sqrt(pe)) of the C library).
+ * lpca_r (src/lpc/lpca_r_rs.rs) and lpca_get_cepstrum (src/lpc/lpca_cepstrum_rs.rs) of the reference, bit for bit: status
+ * 0 / 1 (r[0] == 0: nothing written, pe = 0) / 2 (prediction error <= 0: rc and a as the recursion left them); rc[0] = 0;
+ * frames with status != 0 still get the cepstrum of their partial a and pe.  1 <= P <= 80. */
+#define E2VQ_LPC_FEATURES_MAX_Q 1024
+int e2vq_lpc_features(int device, int P, int Q, const double *frames, int64_t T, int32_t *status, double *pe, double *rc,
+                      double *a, double *c, int on_device);
 
 /* Synthetic gain-normalised autocorrelation frames [first, first+count) of the stream
  * (seed, n_classes): counter-based, so any shard regenerates identical frames. */
