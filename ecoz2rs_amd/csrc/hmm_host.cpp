@@ -8,6 +8,7 @@
 // own -- the reference's C bodies are absent -- written down in oracle/hmm_oracle.h and DESIGN.md.
 #include "../../include/ecoz2_classify.h"
 #include "../../include/ecoz2_vq.h"
+#include "hip_host.h"
 #include "hmm_device.h"
 #include "host_util.h"
 #include "vq_io.h"
@@ -28,24 +29,12 @@
 #include <thread>
 #include <vector>
 
+using namespace e2hip;
 using namespace e2host;
 using e2hmm::ModelDev;
 typedef long long i64;
 
-#define HIPCHK(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return e2vq_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 namespace {
-
-int env_device()
-{
-    const char* v = getenv("ECOZ2_VQ_DEVICE");
-    return v && *v ? atoi(v) : 0;
-}
 
 // ECOZ2_VQ_GPUS = N: sequences (or predictor files) are dealt in contiguous shares to N workers, worker w on device
 // (ECOZ2_VQ_DEVICE + w) % device count -- workers beyond the device count share devices, which is how the 1-GPU tests run
@@ -55,79 +44,6 @@ int env_workers()
     const int n = v && *v ? atoi(v) : 1;
     return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
-void share_of(int total, int workers, int w, int* lo, int* hi)
-{
-    const int base = total / workers, rem = total % workers;
-    *lo = w * base + std::min(w, rem);
-    *hi = *lo + base + (w < rem ? 1 : 0);
-}
-int device_of_worker(int w)
-{
-    int n = 1;
-    (void)hipGetDeviceCount(&n);
-    const char* v = getenv("ECOZ2_VQ_DEVICE");
-    return ((v && *v ? atoi(v) : 0) + w) % std::max(n, 1);
-}
-// runs fn(w) for w = 0 .. workers - 1, worker 0 on the calling thread; the first failing worker's message is kept
-template <typename Fn>
-int run_workers(int workers, Fn fn)
-{
-    std::vector<int> rcs((size_t)workers, 0);
-    std::vector<std::string> errs((size_t)workers);
-    std::vector<std::thread> th;
-    auto body = [&](int w) {
-        rcs[(size_t)w] = fn(w);
-        if (rcs[(size_t)w]) errs[(size_t)w] = e2vq_last_error();
-    };
-    for (int w = 1; w < workers; ++w) th.emplace_back(body, w);
-    body(0);
-    for (auto& t : th) t.join();
-    for (int w = 0; w < workers; ++w)
-        if (rcs[(size_t)w]) return w == 0 ? rcs[0] : e2vq_set_error("%s", errs[(size_t)w].c_str());
-    return 0;
-}
-
-int require_device(int device)
-{
-    int n = 0;
-    const hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return e2vq_set_error("no HIP device available (%s); this library has no CPU path",
-                              e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    if (device < 0 || device >= n) return e2vq_set_error("device %d not in [0, %d)", device, n);
-    HIPCHK(hipSetDevice(device));
-    return 0;
-}
-
-// device buffer released on scope exit
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t count)
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        HIPCHK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-        return 0;
-    }
-    int upload(const T* src, size_t count, hipStream_t st)
-    {
-        if (alloc(count)) return 1;
-        if (count) HIPCHK(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-};
-
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-    int create()
-    {
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        return 0;
-    }
-};
 
 // ---- generator: ecoz2_set_random_seed (oracle: e2h_set_random_seed / splitmix64) ---------------------------
 uint64_t g_rng = 0x9E3779B97F4A7C15ull;
@@ -274,8 +190,8 @@ int load_sequences(const char* const* files, unsigned n, SeqSet& ss)
 
 // ---- device-side model set ----------------------------------------------------------------------------------------
 struct DevModels {
-    DevBuf<double> params;   // all pi | A | B, model after model
-    DevBuf<ModelDev> table;
+    DeviceBuffer<double> params;   // all pi | A | B, model after model
+    DeviceBuffer<ModelDev> table;
     std::vector<ModelDev> host;
     int maxN = 0;
     int upload(const std::vector<const Hmm*>& ms, hipStream_t st)
@@ -296,7 +212,7 @@ struct DevModels {
         host.clear();
         maxN = 0;
         for (size_t k = 0; k < ms.size(); ++k) {
-            const double* base = params.p + at[k];
+            const double* base = params.get() + at[k];
             host.push_back(ModelDev{ms[k]->N, ms[k]->M, base, base + ms[k]->N, base + ms[k]->N + (size_t)ms[k]->N * ms[k]->N});
             maxN = std::max(maxN, ms[k]->N);
         }
@@ -315,20 +231,20 @@ int score_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym,
     const int K = (int)ms.size();
     DevModels dm;
     if (dm.upload(ms, st)) return 1;
-    DevBuf<double> d_mant;
-    DevBuf<i64> d_exp;
-    DevBuf<int> d_st;
+    DeviceBuffer<double> d_mant;
+    DeviceBuffer<i64> d_exp;
+    DeviceBuffer<int> d_st;
     const size_t n = (size_t)S * K;
-    if (d_mant.alloc(n) || d_exp.alloc(n) || d_st.alloc(n)) return 1;
-    e2hmm::launch_score(dm.table.p, K, dm.maxN, d_sym, d_offs, S, d_mant.p, d_exp.p, d_st.p, st);
+    if (d_mant.reserve(n) || d_exp.reserve(n) || d_st.reserve(n)) return 1;
+    e2hmm::launch_score(dm.table.get(), K, dm.maxN, d_sym, d_offs, S, d_mant.get(), d_exp.get(), d_st.get(), st);
     HIPCHK(hipGetLastError());
     std::vector<double> mant(n);
     std::vector<i64> ex(n);
     std::vector<int> stat(n);
     if (n) {
-        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.p, n * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.p, n * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(stat.data(), d_st.p, n * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_st.get(), n * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     log_probs.resize(n);
@@ -344,9 +260,9 @@ struct Trainer {
     int N, M, S;
     i64 total;
     hipStream_t st;
-    DevBuf<double> d_params, d_alpha, d_c, d_mant;
-    DevBuf<i64> d_acc, d_exp, d_scratch;
-    DevBuf<int> d_status;
+    DeviceBuffer<double> d_params, d_alpha, d_c, d_mant;
+    DeviceBuffer<i64> d_acc, d_exp, d_scratch;
+    DeviceBuffer<int> d_status;
     std::vector<double> mant;
     std::vector<i64> ex;
     std::vector<int> stat;
@@ -363,12 +279,12 @@ struct Trainer {
         flat.insert(flat.end(), h.B.begin(), h.B.end());
         if (d_params.upload(flat.data(), flat.size(), st)) return 1;
         HIPCHK(hipStreamSynchronize(st));
-        double* base = d_params.p;
+        double* base = d_params.get();
         md = ModelDev{N, M, base, base + N, base + N + (size_t)N * N};
-        if (d_alpha.alloc((size_t)total * N) || d_c.alloc((size_t)total) || d_acc.alloc((size_t)W) || d_mant.alloc((size_t)S) ||
-            d_exp.alloc((size_t)S) || d_status.alloc((size_t)S))
+        if (d_alpha.reserve((size_t)total * N) || d_c.reserve((size_t)total) || d_acc.reserve((size_t)W) || d_mant.reserve((size_t)S) ||
+            d_exp.reserve((size_t)S) || d_status.reserve((size_t)S))
             return 1;
-        if (e2hmm::fb_scratch_words(N) > 0 && d_scratch.alloc((size_t)e2hmm::fb_scratch_words(N))) return 1;
+        if (e2hmm::fb_scratch_words(N) > 0 && d_scratch.reserve((size_t)e2hmm::fb_scratch_words(N))) return 1;
         mant.resize((size_t)S);
         ex.resize((size_t)S);
         stat.resize((size_t)S);
@@ -378,22 +294,22 @@ struct Trainer {
     // acc_out (optional): the count words copied to the host (several workers: summed there and handed back)
     int estep_counts(const unsigned short* d_sym, const i64* d_offs, std::vector<i64>* acc_out = nullptr)
     {
-        HIPCHK(hipMemsetAsync(d_acc.p, 0, (size_t)W * 8, st));
-        e2hmm::launch_fb(md, d_sym, d_offs, S, d_alpha.p, d_c.p, d_acc.p, d_mant.p, d_exp.p, d_status.p, st, d_scratch.p);
+        HIPCHK(hipMemsetAsync(d_acc.get(), 0, (size_t)W * 8, st));
+        e2hmm::launch_fb(md, d_sym, d_offs, S, d_alpha.get(), d_c.get(), d_acc.get(), d_mant.get(), d_exp.get(), d_status.get(), st, d_scratch.get());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(stat.data(), d_status.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
         if (acc_out) {
             acc_out->resize((size_t)W);
-            HIPCHK(hipMemcpyAsync(acc_out->data(), d_acc.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(acc_out->data(), d_acc.get(), (size_t)W * 8, hipMemcpyDeviceToHost, st));
         }
         HIPCHK(hipStreamSynchronize(st));
         return 0;
     }
     int acc_upload(const std::vector<i64>& acc)
     {
-        HIPCHK(hipMemcpyAsync(d_acc.p, acc.data(), (size_t)W * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_acc.get(), acc.data(), (size_t)W * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
         return 0;
     }
@@ -415,15 +331,15 @@ struct Trainer {
     }
     int mstep(double epsilon)
     {
-        double* base = d_params.p;
-        e2hmm::launch_reestimate(N, M, d_acc.p, epsilon, base, base + N, base + N + (size_t)N * N, st);
+        double* base = d_params.get();
+        e2hmm::launch_reestimate(N, M, d_acc.get(), epsilon, base, base + N, base + N + (size_t)N * N, st);
         HIPCHK(hipGetLastError());
         return 0;
     }
     int download(Hmm& h)
     {
         std::vector<double> flat(h.pi.size() + h.A.size() + h.B.size());
-        HIPCHK(hipMemcpyAsync(flat.data(), d_params.p, flat.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(flat.data(), d_params.get(), flat.size() * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         std::copy(flat.begin(), flat.begin() + h.pi.size(), h.pi.begin());
         std::copy(flat.begin() + h.pi.size(), flat.begin() + h.pi.size() + h.A.size(), h.A.begin());
@@ -444,25 +360,28 @@ int train_sharded(Hmm& h, const SeqSet& ss, double epsilon, double val_auto, int
                   hmm_learn_callback_t callback, std::vector<double>& hist, bool verbose, int workers)
 {
     struct Worker {
-        int device = 0, s0 = 0, s1 = 0;
-        Stream st;
-        DevBuf<unsigned short> d_sym;
-        DevBuf<i64> d_offs;
+        int device = 0;
+        i64 s0 = 0, s1 = 0;
+        DeviceBuffer<unsigned short> d_sym;
+        DeviceBuffer<i64> d_offs;
         Trainer tr;
         std::vector<i64> acc;
+        Stream st;  // (after the buffers: see Stream)
     };
+    const int ndev = device_count();
+    if (!ndev) return 1;
     std::vector<Worker> ws((size_t)workers);
     if (run_workers(workers, [&](int w) -> int {
             Worker& k = ws[(size_t)w];
-            k.device = device_of_worker(w);
-            share_of(ss.S(), workers, w, &k.s0, &k.s1);
+            k.device = worker_device(env_device(), w, ndev);
+            split_range(ss.S(), workers, w, &k.s0, &k.s1);
             if (require_device(k.device) || k.st.create()) return 1;
             const i64 a = ss.offs[(size_t)k.s0], b = ss.offs[(size_t)k.s1];
             std::vector<i64> offs;
-            for (int i = k.s0; i <= k.s1; ++i) offs.push_back(ss.offs[(size_t)i] - a);
+            for (i64 i = k.s0; i <= k.s1; ++i) offs.push_back(ss.offs[(size_t)i] - a);
             if (k.d_sym.upload(ss.sym.data() + a, (size_t)(b - a), k.st.s) || k.d_offs.upload(offs.data(), offs.size(), k.st.s)) return 1;
             HIPCHK(hipStreamSynchronize(k.st.s));  // (`offs` is a local)
-            return k.tr.setup(h, k.s1 - k.s0, b - a, k.st.s);
+            return k.tr.setup(h, (int)(k.s1 - k.s0), b - a, k.st.s);
         }))
         return 1;
     static char var[] = "sum_log_prob";
@@ -475,7 +394,7 @@ int train_sharded(Hmm& h, const SeqSet& ss, double epsilon, double val_auto, int
         if (run_workers(workers, [&](int w) -> int {
                 Worker& k = ws[(size_t)w];
                 HIPCHK(hipSetDevice(k.device));
-                return k.tr.estep_counts(k.d_sym.p, k.d_offs.p, &k.acc);
+                return k.tr.estep_counts(k.d_sym.get(), k.d_offs.get(), &k.acc);
             }))
             return 1;
         total.assign(ws[0].acc.size(), 0);
@@ -520,12 +439,12 @@ int train(Hmm& h, const SeqSet& ss, double epsilon, double val_auto, int max_ite
 {
     const int workers = std::min(env_workers(), std::max(1, ss.S()));
     if (workers > 1) return train_sharded(h, ss, epsilon, val_auto, max_iterations, callback, hist, verbose, workers);
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<i64> d_offs;
+    Trainer tr;
     Stream st;
     if (st.create()) return 1;
-    DevBuf<unsigned short> d_sym;
-    DevBuf<i64> d_offs;
     if (d_sym.upload(ss.sym.data(), ss.sym.size(), st.s) || d_offs.upload(ss.offs.data(), ss.offs.size(), st.s)) return 1;
-    Trainer tr;
     if (tr.setup(h, ss.S(), (i64)ss.sym.size(), st.s)) return 1;
     static char var[] = "sum_log_prob";
     int it = 0;
@@ -535,7 +454,7 @@ int train(Hmm& h, const SeqSet& ss, double epsilon, double val_auto, int max_ite
         if ((max_iterations >= 0 && it >= max_iterations) || it >= MAX_ESTEPS) break;
         double L;
         i64 used, skipped;
-        if (tr.estep(d_sym.p, d_offs.p, &L, &used, &skipped)) return 1;
+        if (tr.estep(d_sym.get(), d_offs.get(), &L, &used, &skipped)) return 1;
         hist.push_back(L);
         if (verbose)
             printf("  it=%d  sum log(P) = %.10g%s\n", it, L,
@@ -686,23 +605,24 @@ extern "C" int ecoz2_hmm_classify(const char* const* model_filenames, unsigned n
     for (const Hmm& h : models) ms.push_back(&h);
     // ECOZ2_VQ_GPUS workers, each scoring a contiguous share of the sequences under every model (independent: the
     // scores are the single worker's bit for bit)
-    const int workers = std::min(env_workers(), std::max(1, ss.S()));
+    const int workers = std::min(env_workers(), std::max(1, ss.S())), ndev = device_count();
+    if (!ndev) return 1;
     const size_t K = ms.size();
     std::vector<double> lp((size_t)ss.S() * K);
     if (run_workers(workers, [&](int w) -> int {
-            int s0, s1;
-            share_of(ss.S(), workers, w, &s0, &s1);
-            if (require_device(device_of_worker(w))) return 1;
-            Stream st;
-            if (st.create()) return 1;
+            i64 s0, s1;
+            split_range(ss.S(), workers, w, &s0, &s1);
+            if (require_device(worker_device(env_device(), w, ndev))) return 1;
             const i64 a = ss.offs[(size_t)s0], b = ss.offs[(size_t)s1];
             std::vector<i64> offs;
-            for (int i = s0; i <= s1; ++i) offs.push_back(ss.offs[(size_t)i] - a);
-            DevBuf<unsigned short> d_sym;
-            DevBuf<i64> d_offs;
+            for (i64 i = s0; i <= s1; ++i) offs.push_back(ss.offs[(size_t)i] - a);
+            DeviceBuffer<unsigned short> d_sym;
+            DeviceBuffer<i64> d_offs;
+            Stream st;
+            if (st.create()) return 1;
             if (d_sym.upload(ss.sym.data() + a, (size_t)(b - a), st.s) || d_offs.upload(offs.data(), offs.size(), st.s)) return 1;
             std::vector<double> part;
-            if (score_device(ms, d_sym.p, d_offs.p, s1 - s0, st.s, part)) return 1;
+            if (score_device(ms, d_sym.get(), d_offs.get(), (int)(s1 - s0), st.s, part)) return 1;
             std::copy(part.begin(), part.end(), lp.begin() + (ptrdiff_t)((size_t)s0 * K));
             return 0;
         }))
@@ -821,7 +741,8 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
     std::vector<double> lp((size_t)S * num_models, -INFINITY);
     std::atomic<int> next_unit{0};
     std::atomic<bool> failed{false};
-    const int workers = std::min(env_workers(), std::max(1, (int)units.size()));
+    const int workers = std::min(env_workers(), std::max(1, (int)units.size())), ndev = device_count();
+    if (!ndev) return 1;
     const int NC = P + 1;
     if (run_workers(workers, [&](int w) -> int {
             // (any way out of this worker but the last line stops the others at their next unit)
@@ -833,8 +754,20 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                     if (!ok) f.store(true);
                 }
             } fail_guard{failed};
-            const int dev = workers == 1 ? device : device_of_worker(w);
+            const int dev = workers == 1 ? device : worker_device(device, w, ndev);
             if (require_device(dev)) return 1;
+            struct Slot {
+                PinnedBuffer<double> h_frames, h_mant;
+                PinnedBuffer<i64> h_offs, h_exp;
+                PinnedBuffer<int> h_st;
+                DeviceBuffer<double> d_frames, d_mant;
+                DeviceBuffer<unsigned short> d_sym;
+                DeviceBuffer<i64> d_offs, d_exp;
+                DeviceBuffer<int> d_st;
+                Event done;
+                int unit = -1;
+            } slots[2];
+            std::vector<DevModels> dms(groups.size());
             Stream st;
             if (st.create()) return 1;
             // one quantize session per codebook (its codeword images are built once), all on the worker's stream
@@ -846,7 +779,6 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                         if (s) e2vq_session_destroy(s);
                 }
             } sessions;
-            std::vector<DevModels> dms(groups.size());
             for (size_t g = 0; g < groups.size(); ++g) {
                 e2vq_session* vq = nullptr;
                 if (e2vq_session_create(dev, P, &vq)) return 1;
@@ -855,44 +787,20 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                 if (e2vq_set_codebook(vq, cbs[(size_t)groups[g].cb].refl.data(), cbs[(size_t)groups[g].cb].M)) return 1;
                 if (dms[g].upload(groups[g].ms, st.s)) return 1;
             }
-            struct Slot {
-                double* h_frames = nullptr;
-                i64* h_offs = nullptr;
-                double* h_mant = nullptr;
-                i64* h_exp = nullptr;
-                int* h_st = nullptr;
-                DevBuf<double> d_frames, d_mant;
-                DevBuf<unsigned short> d_sym;
-                DevBuf<i64> d_offs, d_exp;
-                DevBuf<int> d_st;
-                hipEvent_t done = nullptr;
-                int unit = -1;
-                ~Slot()
-                {
-                    for (void* p : {(void*)h_frames, (void*)h_offs, (void*)h_mant, (void*)h_exp, (void*)h_st})
-                        if (p) (void)hipHostFree(p);
-                    if (done) (void)hipEventDestroy(done);
-                }
-            } slots[2];
             const size_t res_cap = (size_t)max_files * num_models;
             const size_t sym_cap = (size_t)std::max<i64>(CHUNK, max_T) + 64;
             // (the staging slots hold a unit's frames: never more than the whole corpus has)
             const i64 STAGE = std::max<i64>(64, std::min<i64>(CHUNK, offs[(size_t)S]));
-            for (Slot& q : slots) {
-                HIPCHK(hipHostMalloc((void**)&q.h_frames, (size_t)STAGE * NC * 8, hipHostMallocDefault));
-                HIPCHK(hipHostMalloc((void**)&q.h_offs, (size_t)(max_files + 1) * 8, hipHostMallocDefault));
-                HIPCHK(hipHostMalloc((void**)&q.h_mant, res_cap * 8, hipHostMallocDefault));
-                HIPCHK(hipHostMalloc((void**)&q.h_exp, res_cap * 8, hipHostMallocDefault));
-                HIPCHK(hipHostMalloc((void**)&q.h_st, res_cap * 4, hipHostMallocDefault));
-                if (q.d_frames.alloc((size_t)STAGE * NC) || q.d_sym.alloc(sym_cap) || q.d_offs.alloc((size_t)max_files + 1) ||
-                    q.d_mant.alloc(res_cap) || q.d_exp.alloc(res_cap) || q.d_st.alloc(res_cap))
+            for (Slot& q : slots)
+                if (q.h_frames.reserve((size_t)STAGE * NC) || q.h_offs.reserve((size_t)max_files + 1) || q.h_mant.reserve(res_cap) ||
+                    q.h_exp.reserve(res_cap) || q.h_st.reserve(res_cap) || q.d_frames.reserve((size_t)STAGE * NC) ||
+                    q.d_sym.reserve(sym_cap) || q.d_offs.reserve((size_t)max_files + 1) || q.d_mant.reserve(res_cap) ||
+                    q.d_exp.reserve(res_cap) || q.d_st.reserve(res_cap) || q.done.create(hipEventDisableTiming))
                     return 1;
-                HIPCHK(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-            }
             // results of the unit in flight in a slot -> lp (layout on the device: group after group, [sequence][model of the group])
             auto harvest = [&](Slot& q) -> int {
                 if (q.unit < 0) return 0;
-                HIPCHK(hipEventSynchronize(q.done));
+                HIPCHK(hipEventSynchronize(q.done.e));
                 const Unit& u = units[(size_t)q.unit];
                 const int Su = u.f1 - u.f0;
                 size_t base = 0;
@@ -902,7 +810,7 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                         for (size_t j = 0; j < K; ++j) {
                             const size_t o = base + (size_t)sq * K + j;
                             lp[(size_t)(u.f0 + sq) * num_models + gr.idx[j]] =
-                                q.h_st[o] == 0 ? log_prob(q.h_mant[o], q.h_exp[o]) : -INFINITY;
+                                q.h_st.get()[o] == 0 ? log_prob(q.h_mant.get()[o], q.h_exp.get()[o]) : -INFINITY;
                         }
                     base += (size_t)Su * K;
                 }
@@ -912,8 +820,8 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
             auto score_groups = [&](Slot& q, int Su, size_t g0, size_t g1, size_t base) -> int {  // groups [g0, g1) on q.d_sym
                 for (size_t g = g0; g < g1; ++g) {
                     const int K = (int)groups[g].idx.size();
-                    e2hmm::launch_score(dms[g].table.p, K, dms[g].maxN, q.d_sym.p, q.d_offs.p, Su, q.d_mant.p + base,
-                                        q.d_exp.p + base, q.d_st.p + base, st.s);
+                    e2hmm::launch_score(dms[g].table.get(), K, dms[g].maxN, q.d_sym.get(), q.d_offs.get(), Su, q.d_mant.get() + base,
+                                        q.d_exp.get() + base, q.d_st.get() + base, st.s);
                     HIPCHK(hipGetLastError());
                     base += (size_t)Su * K;
                 }
@@ -929,8 +837,8 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                 const Unit& u = units[(size_t)ui];
                 const int Su = u.f1 - u.f0;
                 const i64 n_fr = offs[(size_t)u.f1] - offs[(size_t)u.f0];
-                for (int f = u.f0; f <= u.f1; ++f) q.h_offs[f - u.f0] = offs[(size_t)f] - offs[(size_t)u.f0];
-                HIPCHK(hipMemcpyAsync(q.d_offs.p, q.h_offs, (size_t)(Su + 1) * 8, hipMemcpyHostToDevice, st.s));
+                for (int f = u.f0; f <= u.f1; ++f) q.h_offs.get()[f - u.f0] = offs[(size_t)f] - offs[(size_t)u.f0];
+                HIPCHK(hipMemcpyAsync(q.d_offs.get(), q.h_offs.get(), (size_t)(Su + 1) * 8, hipMemcpyHostToDevice, st.s));
                 size_t n_res = 0;
                 for (const Group& gr : groups) n_res += (size_t)Su * gr.idx.size();
                 if (n_fr <= CHUNK) {
@@ -938,15 +846,15 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                         const i64 T = offs[(size_t)f + 1] - offs[(size_t)f];
                         bool fin = true;
                         if (T > 0 && e2vq_io::prd_read_range_mt(files[(size_t)f].c_str(), P, 0, T,
-                                                                q.h_frames + (size_t)(offs[(size_t)f] - offs[(size_t)u.f0]) * NC,
+                                                                q.h_frames.get() + (size_t)(offs[(size_t)f] - offs[(size_t)u.f0]) * NC,
                                                                 e2vq_io::io_threads(), &fin))
                             return 1;
                         if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", files[(size_t)f].c_str());
                     }
-                    if (n_fr > 0) HIPCHK(hipMemcpyAsync(q.d_frames.p, q.h_frames, (size_t)n_fr * NC * 8, hipMemcpyHostToDevice, st.s));
+                    if (n_fr > 0) HIPCHK(hipMemcpyAsync(q.d_frames.get(), q.h_frames.get(), (size_t)n_fr * NC * 8, hipMemcpyHostToDevice, st.s));
                     size_t base = 0;
                     for (size_t g = 0; g < groups.size(); ++g) {
-                        if (n_fr > 0 && e2vq_quantize_device(sessions.v[g], q.d_frames.p, n_fr, q.d_sym.p, nullptr)) return 1;
+                        if (n_fr > 0 && e2vq_quantize_device(sessions.v[g], q.d_frames.get(), n_fr, q.d_sym.get(), nullptr)) return 1;
                         if (score_groups(q, Su, g, g + 1, base)) return 1;
                         base += (size_t)Su * groups[g].idx.size();
                     }
@@ -959,22 +867,22 @@ extern "C" int ecoz2_hmm_classify_predictors(const char* const* model_filenames,
                             const i64 n = std::min(CHUNK, n_fr - t0);
                             bool fin = true;
                             HIPCHK(hipStreamSynchronize(st.s));  // (the previous piece has left the staging buffer)
-                            if (e2vq_io::prd_read_range_mt(files[(size_t)u.f0].c_str(), P, t0, n, q.h_frames, e2vq_io::io_threads(), &fin))
+                            if (e2vq_io::prd_read_range_mt(files[(size_t)u.f0].c_str(), P, t0, n, q.h_frames.get(), e2vq_io::io_threads(), &fin))
                                 return 1;
                             if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", files[(size_t)u.f0].c_str());
-                            HIPCHK(hipMemcpyAsync(q.d_frames.p, q.h_frames, (size_t)n * NC * 8, hipMemcpyHostToDevice, st.s));
-                            if (e2vq_quantize_device(sessions.v[g], q.d_frames.p, n, q.d_sym.p + t0, nullptr)) return 1;
+                            HIPCHK(hipMemcpyAsync(q.d_frames.get(), q.h_frames.get(), (size_t)n * NC * 8, hipMemcpyHostToDevice, st.s));
+                            if (e2vq_quantize_device(sessions.v[g], q.d_frames.get(), n, q.d_sym.get() + t0, nullptr)) return 1;
                         }
                         if (score_groups(q, Su, g, g + 1, base)) return 1;
                         base += (size_t)Su * groups[g].idx.size();
                     }
                 }
                 if (n_res) {
-                    HIPCHK(hipMemcpyAsync(q.h_mant, q.d_mant.p, n_res * 8, hipMemcpyDeviceToHost, st.s));
-                    HIPCHK(hipMemcpyAsync(q.h_exp, q.d_exp.p, n_res * 8, hipMemcpyDeviceToHost, st.s));
-                    HIPCHK(hipMemcpyAsync(q.h_st, q.d_st.p, n_res * 4, hipMemcpyDeviceToHost, st.s));
+                    HIPCHK(hipMemcpyAsync(q.h_mant.get(), q.d_mant.get(), n_res * 8, hipMemcpyDeviceToHost, st.s));
+                    HIPCHK(hipMemcpyAsync(q.h_exp.get(), q.d_exp.get(), n_res * 8, hipMemcpyDeviceToHost, st.s));
+                    HIPCHK(hipMemcpyAsync(q.h_st.get(), q.d_st.get(), n_res * 4, hipMemcpyDeviceToHost, st.s));
                 }
-                HIPCHK(hipEventRecord(q.done, st.s));
+                HIPCHK(hipEventRecord(q.done.e, st.s));
                 q.unit = ui;
             }
             for (int k = 0; k < 2; ++k)
@@ -1100,15 +1008,15 @@ extern "C" int e2vq_hmm_score(int device, int K, const int* Ns, int M, const dou
         if (model_from_arrays(Ns[k], M, pis[k], As[k], Bs[k], models[(size_t)k])) return 1;
         ms.push_back(&models[(size_t)k]);
     }
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<i64> d_offs;
     Stream st;
     if (st.create()) return 1;
-    DevBuf<unsigned short> d_sym;
-    DevBuf<i64> d_offs;
     if (d_sym.upload(sym, (size_t)offs[S], st.s) || d_offs.upload((const i64*)offs, (size_t)S + 1, st.s)) return 1;
     std::vector<double> lp, mt;
     std::vector<i64> ex;
     std::vector<int> stt;
-    if (score_device(ms, d_sym.p, d_offs.p, S, st.s, lp, &mt, &ex, &stt)) return 1;
+    if (score_device(ms, d_sym.get(), d_offs.get(), S, st.s, lp, &mt, &ex, &stt)) return 1;
     const size_t n = (size_t)S * K;
     for (size_t i = 0; i < n; ++i) {
         if (mant) mant[i] = mt[i];
@@ -1130,16 +1038,16 @@ extern "C" int e2vq_hmm_estep(int device, int N, int M, const double* pi, const 
     if (require_device(device)) return 1;
     Hmm h;
     if (model_from_arrays(N, M, pi, A, B, h)) return 1;
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<i64> d_offs;
+    Trainer tr;
     Stream st;
     if (st.create()) return 1;
-    DevBuf<unsigned short> d_sym;
-    DevBuf<i64> d_offs;
     if (d_sym.upload(sym, (size_t)offs[S], st.s) || d_offs.upload((const i64*)offs, (size_t)S + 1, st.s)) return 1;
-    Trainer tr;
     if (tr.setup(h, S, offs[S], st.s)) return 1;
     double L;
-    if (tr.estep(d_sym.p, d_offs.p, &L, nullptr, nullptr)) return 1;
-    HIPCHK(hipMemcpy(acc, tr.d_acc.p, (size_t)tr.W * 8, hipMemcpyDeviceToHost));
+    if (tr.estep(d_sym.get(), d_offs.get(), &L, nullptr, nullptr)) return 1;
+    HIPCHK(hipMemcpy(acc, tr.d_acc.get(), (size_t)tr.W * 8, hipMemcpyDeviceToHost));
     for (int s = 0; s < S; ++s) {
         if (mant) mant[s] = tr.mant[(size_t)s];
         if (exp2) exp2[s] = tr.ex[(size_t)s];

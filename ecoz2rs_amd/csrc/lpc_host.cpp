@@ -19,6 +19,8 @@
 #include <thread>
 #include <vector>
 
+using namespace e2hip;
+
 namespace {
 
 // ---- WAV ---------------------------------------------------------------------------------------------------------
@@ -175,55 +177,6 @@ void hamming(int win, double* h)
     for (int n = 0; n < win; ++n) h[n] = 0.54 - 0.46 * cos(((double)(n * 2) * M_PI) / (double)(win - 1));
 }
 
-int have_device()
-{
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-        return e2vq_set_error("no HIP device available (%s); this library has no CPU path",
-                              e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    return 0;
-}
-
-struct DevMem {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    int reserve(size_t b)
-    {
-        if (b <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        HIPCHK(hipMalloc(&p, b));
-        bytes = b;
-        return 0;
-    }
-    template <typename T> T* as() const { return (T*)p; }
-};
-
-struct PinnedMem {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~PinnedMem() { if (p) (void)hipHostFree(p); }
-    int reserve(size_t b)
-    {
-        if (b <= bytes) return 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        HIPCHK(hipHostMalloc(&p, b, hipHostMallocDefault));
-        bytes = b;
-        return 0;
-    }
-    template <typename T> T* as() const { return (T*)p; }
-};
-
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() { if (s) (void)hipStreamDestroy(s); }
-};
-
 // One batch of signals analysed by one launch: samples concatenated, a frame table in waves of 64 with the same window
 // per wave, one Hamming table per window length.
 struct BatchSignal {
@@ -262,21 +215,18 @@ struct Batch {
 // device analysis of one batch whose samples are in h_samples (host, pinned or not); results to out/status (host)
 struct Analyzer {
     int device = 0, P = 0;
+    DeviceBuffer<int32_t> d_samples, d_status;
+    DeviceBuffer<e2lpc::Frame> d_tab;
+    DeviceBuffer<double> d_h, d_out;
+    KernelTimer* timer = nullptr;  // optional: recorded around the kernel
     Stream st;
-    DevMem d_samples, d_tab, d_h, d_out, d_status;
-    hipEvent_t after_copies = nullptr, after_kernel = nullptr;  // optional: recorded around the kernel
 
     int init(int dev, int p)
     {
-        if (have_device()) return 1;
-        int ndev = 0;
-        HIPCHK(hipGetDeviceCount(&ndev));
-        if (dev < 0 || dev >= ndev) return e2vq_set_error("device %d not in [0, %d)", dev, ndev);
+        if (require_device(dev)) return 1;
         device = dev;
         P = p;
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
-        return 0;
+        return st.create();
     }
     // enqueue: copies in, kernel; results stay on the device (d_out / d_status)
     int launch(Batch& b, const int32_t* h_samples)
@@ -291,23 +241,20 @@ struct Analyzer {
                     return e2vq_set_error("lpc: order %d runs the generic path, whose window limit is %d samples (got %d)",
                                           P, e2lpc::kGenericMaxWin, s.win);
         HIPCHK(hipSetDevice(device));
-        if (d_samples.reserve((size_t)std::max<int64_t>(b.samples, 1) * 4) || d_tab.reserve((size_t)E * sizeof(e2lpc::Frame)) ||
-            d_h.reserve(b.h.size() * 8) || d_out.reserve((size_t)E * NC * 8) || d_status.reserve((size_t)E * 4))
+        if (d_samples.reserve((size_t)std::max<int64_t>(b.samples, 1)) || d_tab.reserve((size_t)E) || d_h.reserve(b.h.size()) ||
+            d_out.reserve((size_t)E * NC) || d_status.reserve((size_t)E))
             return 1;
-        HIPCHK(hipMemcpyAsync(d_samples.p, h_samples, (size_t)b.samples * 4, hipMemcpyHostToDevice, st.s));
-        HIPCHK(hipMemcpyAsync(d_tab.p, b.tab.data(), (size_t)E * sizeof(e2lpc::Frame), hipMemcpyHostToDevice, st.s));
-        HIPCHK(hipMemcpyAsync(d_h.p, b.h.data(), b.h.size() * 8, hipMemcpyHostToDevice, st.s));
-        if (after_copies) HIPCHK(hipEventRecord(after_copies, st.s));
-        if (e2lpc::launch_signals(P, d_samples.as<int32_t>(), d_tab.as<e2lpc::Frame>(), E, d_h.as<double>(),
-                                  d_out.as<double>(), d_status.as<int32_t>(), st.s))
+        HIPCHK(hipMemcpyAsync(d_samples.get(), h_samples, (size_t)b.samples * 4, hipMemcpyHostToDevice, st.s));
+        HIPCHK(hipMemcpyAsync(d_tab.get(), b.tab.data(), (size_t)E * sizeof(e2lpc::Frame), hipMemcpyHostToDevice, st.s));
+        HIPCHK(hipMemcpyAsync(d_h.get(), b.h.data(), b.h.size() * 8, hipMemcpyHostToDevice, st.s));
+        if (timer) HIPCHK(hipEventRecord(timer->start.e, st.s));
+        if (e2lpc::launch_signals(P, d_samples.get(), d_tab.get(), E, d_h.get(), d_out.get(), d_status.get(), st.s))
             return e2vq_set_error("lpc kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-        if (after_kernel) HIPCHK(hipEventRecord(after_kernel, st.s));
+        if (timer) HIPCHK(hipEventRecord(timer->stop.e, st.s));
         // the host tables must stay alive until the copies are done: the caller synchronises before reusing them
         return 0;
     }
 };
-
-int env_device() { return e2vq_env_int("ECOZ2_VQ_DEVICE", 0); }
 
 std::string class_of(const std::string& path)
 {
@@ -430,22 +377,16 @@ extern "C" int e2vq_lpc_analyze(int device, int P, int W_ms, int O_ms, const int
     if (an.init(device, P)) return 1;
     Batch b;
     b.add(num_samples, win, off, T);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    for (auto& x : ev) HIPCHK(hipEventCreate(&x));
-    struct Release {
-        hipEvent_t* e;
-        ~Release() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } release{ev};
-    an.after_copies = ev[0];
-    an.after_kernel = ev[1];
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    an.timer = &timer;
     if (an.launch(b, samples)) return 1;
     const int NC = P + 1;
     const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    HIPCHK(hipMemcpyAsync(frames, an.d_out.p, (size_t)T * NC * 8, k, an.st.s));
-    HIPCHK(hipMemcpyAsync(status, an.d_status.p, (size_t)T * 4, k, an.st.s));
+    HIPCHK(hipMemcpyAsync(frames, an.d_out.get(), (size_t)T * NC * 8, k, an.st.s));
+    HIPCHK(hipMemcpyAsync(status, an.d_status.get(), (size_t)T * 4, k, an.st.s));
     HIPCHK(hipStreamSynchronize(an.st.s));
-    HIPCHK(hipEventElapsedTime(&g_last_kernel_ms, ev[0], ev[1]));
-    return 0;
+    return timer.elapsed_ms(&g_last_kernel_ms);
 }
 
 extern "C" int e2vq_lpca_batch(int device, int P, const double* x, int n, int64_t count, double* r, double* rc, double* a,
@@ -456,24 +397,24 @@ extern "C" int e2vq_lpca_batch(int device, int P, const double* x, int n, int64_
     if (!e2lpc::lane_path(P) && n > e2lpc::kGenericMaxWin)
         return e2vq_set_error("e2vq_lpca_batch: order %d runs the generic path, whose frame limit is %d samples", P,
                               e2lpc::kGenericMaxWin);
-    if (have_device()) return 1;
+    if (!device_count()) return 1;
     if (count == 0) return 0;
+    DeviceBuffer<double> dx, dr, drc, da, dpe;
+    DeviceBuffer<int32_t> dst;
     Analyzer an;
     if (an.init(device, P)) return 1;
     const int NC = P + 1;
-    DevMem dx, dr, drc, da, dpe, dst;
-    if (dx.reserve((size_t)count * n * 8) || dr.reserve((size_t)count * NC * 8) || drc.reserve((size_t)count * NC * 8) ||
-        da.reserve((size_t)count * NC * 8) || dpe.reserve((size_t)count * 8) || dst.reserve((size_t)count * 4))
+    if (dx.reserve((size_t)count * n) || dr.reserve((size_t)count * NC) || drc.reserve((size_t)count * NC) ||
+        da.reserve((size_t)count * NC) || dpe.reserve((size_t)count) || dst.reserve((size_t)count))
         return 1;
-    HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)count * n * 8, hipMemcpyHostToDevice, an.st.s));
-    if (e2lpc::launch_windowed(P, dx.as<double>(), n, count, dr.as<double>(), drc.as<double>(), da.as<double>(),
-                               dpe.as<double>(), dst.as<int32_t>(), an.st.s))
+    HIPCHK(hipMemcpyAsync(dx.get(), x, (size_t)count * n * 8, hipMemcpyHostToDevice, an.st.s));
+    if (e2lpc::launch_windowed(P, dx.get(), n, count, dr.get(), drc.get(), da.get(), dpe.get(), dst.get(), an.st.s))
         return e2vq_set_error("lpca kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(hipMemcpyAsync(r, dr.p, (size_t)count * NC * 8, hipMemcpyDeviceToHost, an.st.s));
-    HIPCHK(hipMemcpyAsync(rc, drc.p, (size_t)count * NC * 8, hipMemcpyDeviceToHost, an.st.s));
-    HIPCHK(hipMemcpyAsync(a, da.p, (size_t)count * NC * 8, hipMemcpyDeviceToHost, an.st.s));
-    HIPCHK(hipMemcpyAsync(pe, dpe.p, (size_t)count * 8, hipMemcpyDeviceToHost, an.st.s));
-    HIPCHK(hipMemcpyAsync(status, dst.p, (size_t)count * 4, hipMemcpyDeviceToHost, an.st.s));
+    HIPCHK(hipMemcpyAsync(r, dr.get(), (size_t)count * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+    HIPCHK(hipMemcpyAsync(rc, drc.get(), (size_t)count * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+    HIPCHK(hipMemcpyAsync(a, da.get(), (size_t)count * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+    HIPCHK(hipMemcpyAsync(pe, dpe.get(), (size_t)count * 8, hipMemcpyDeviceToHost, an.st.s));
+    HIPCHK(hipMemcpyAsync(status, dst.get(), (size_t)count * 4, hipMemcpyDeviceToHost, an.st.s));
     HIPCHK(hipStreamSynchronize(an.st.s));
     return 0;
 }
@@ -525,7 +466,7 @@ extern "C" int ecoz2_lpc_signals(int P, int W_ms, int O_ms, int minpc, float spl
     if (P < 1 || P > E2VQ_LPC_MAX_P) return e2vq_set_error("lpc: prediction order %d out of range [1, %d]", P, E2VQ_LPC_MAX_P);
     if (n < 0 || (n > 0 && !sgn_filenames)) return e2vq_set_error("ecoz2_lpc_signals: bad arguments");
     if (W_ms <= 0 || O_ms <= 0) return e2vq_set_error("lpc: window %d ms / offset %d ms", W_ms, O_ms);
-    if (have_device()) return 1;
+    if (!device_count()) return 1;
     if (split != 0.f) printf("NOTE: split (%g) is deprecated and ignored; all predictors go to data/predictors\n", (double)split);
 
     // classes: the name of each signal's parent directory (notes.md:73-79)
@@ -588,11 +529,12 @@ extern "C" int ecoz2_lpc_signals(int P, int W_ms, int O_ms, int minpc, float spl
         return s;
     };
 
-    Analyzer an;
+    PinnedBuffer<int32_t> stage[2];
+    PinnedBuffer<double> h_out;
+    std::vector<int32_t> h_status;
+    Analyzer an;  // (after the buffers its stream copies into: see Stream)
     if (an.init(env_device(), P)) return 1;
     const int NC = P + 1;
-    PinnedMem stage[2], h_out;
-    std::vector<int32_t> h_status;
     std::vector<double> keep;
     const int threads = e2vq_io::io_threads();
     using clock = std::chrono::steady_clock;
@@ -603,26 +545,23 @@ extern "C" int ecoz2_lpc_signals(int P, int W_ms, int O_ms, int minpc, float spl
     int rrc = 0;
     auto read_into = [&](size_t k) {
         t_read[k] = clock::now();
-        rrc = read_batch(jobs, cut[k], cut[k + 1], stage[k & 1].as<int32_t>(), threads, rerr);
+        rrc = read_batch(jobs, cut[k], cut[k + 1], stage[k & 1].get(), threads, rerr);
     };
-    if (stage[0].reserve((size_t)batch_samples(0) * 4)) return 1;
+    if (stage[0].reserve((size_t)batch_samples(0))) return 1;
     read_into(0);
     if (rrc) return e2vq_set_error("%s", rerr.c_str());
     for (size_t k = 0; k < nb; ++k) {
         Batch b;
         for (size_t i = cut[k]; i < cut[k + 1]; ++i) b.add(jobs[i].w.N, jobs[i].win, jobs[i].off, jobs[i].T);
-        if (an.launch(b, stage[k & 1].as<int32_t>())) return 1;
+        if (an.launch(b, stage[k & 1].get())) return 1;
         const int64_t E = (int64_t)b.tab.size();
-        if (h_out.reserve((size_t)E * NC * 8)) return 1;
+        if (h_out.reserve((size_t)E * NC)) return 1;
         h_status.resize((size_t)E);
-        HIPCHK(hipMemcpyAsync(h_out.p, an.d_out.p, (size_t)E * NC * 8, hipMemcpyDeviceToHost, an.st.s));
-        HIPCHK(hipMemcpyAsync(h_status.data(), an.d_status.p, (size_t)E * 4, hipMemcpyDeviceToHost, an.st.s));
+        HIPCHK(hipMemcpyAsync(h_out.get(), an.d_out.get(), (size_t)E * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+        HIPCHK(hipMemcpyAsync(h_status.data(), an.d_status.get(), (size_t)E * 4, hipMemcpyDeviceToHost, an.st.s));
         std::thread reader;
         if (k + 1 < nb) {
-            if (stage[(k + 1) & 1].reserve((size_t)batch_samples(k + 1) * 4)) {
-                (void)hipStreamSynchronize(an.st.s);
-                return 1;
-            }
+            if (stage[(k + 1) & 1].reserve((size_t)batch_samples(k + 1))) return 1;
             reader = std::thread(read_into, k + 1);
         }
         const hipError_t se = hipStreamSynchronize(an.st.s);
@@ -634,7 +573,7 @@ extern "C" int ecoz2_lpc_signals(int P, int W_ms, int O_ms, int minpc, float spl
             printf("  %s\n", j.path.c_str());
             printf("lpa_on_signal: P=%d numSamples=%lld sampleRate=%d winSize=%d offset=%d T=%lld\n", P, (long long)j.w.N,
                    j.w.sample_rate, j.win, j.off, (long long)j.T);
-            const double* rows = h_out.as<double>() + (size_t)s.first_entry * NC;
+            const double* rows = h_out.get() + (size_t)s.first_entry * NC;
             const int32_t* sts = h_status.data() + s.first_entry;
             int64_t good = 0;
             for (int64_t t = 0; t < j.T; ++t) good += sts[t] == 0;
@@ -675,48 +614,43 @@ extern "C" int e2vq_lpc_features(int device, int P, int Q, const double* frames,
         return e2vq_set_error("lpc features: cepstrum length %d exceeds the limit of %d", Q, E2VQ_LPC_FEATURES_MAX_Q);
     if (!frames || T < 0) return e2vq_set_error("e2vq_lpc_features: bad arguments");
     if (Q == 0) c = nullptr;
-    if (have_device()) return 1;
+    if (!device_count()) return 1;
     if (T == 0) return 0;
+    DeviceBuffer<double> din, dpe, drc, da, dc;
+    DeviceBuffer<int32_t> dst;
     Analyzer an;
     if (an.init(device, P)) return 1;
     const int NC = P + 1;
     if (on_device) {
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        for (auto& x : ev) HIPCHK(hipEventCreate(&x));
-        struct Release {
-            hipEvent_t* e;
-            ~Release() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
-        } release{ev};
-        HIPCHK(hipEventRecord(ev[0], an.st.s));
+        KernelTimer timer;
+        if (timer.create()) return 1;
+        HIPCHK(hipEventRecord(timer.start.e, an.st.s));
         if (e2lpc::launch_features(P, Q, frames, T, status, pe, rc, a, c, an.st.s))
             return e2vq_set_error("lpc features kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-        HIPCHK(hipEventRecord(ev[1], an.st.s));
+        HIPCHK(hipEventRecord(timer.stop.e, an.st.s));
         HIPCHK(hipStreamSynchronize(an.st.s));
-        HIPCHK(hipEventElapsedTime(&g_last_kernel_ms, ev[0], ev[1]));
-        return 0;
+        return timer.elapsed_ms(&g_last_kernel_ms);
     }
     // host memory: chunks of frames through device buffers; c[0] is then replaced by the C library's log(sqrt(pe))
     const int64_t CH = std::min<int64_t>(T, (int64_t)1 << 18);
     const bool need_pe = pe || c;
-    DevMem din, dst, dpe, drc, da, dc;
-    if (din.reserve((size_t)CH * NC * 8) || (status && dst.reserve((size_t)CH * 4)) || (need_pe && dpe.reserve((size_t)CH * 8)) ||
-        (rc && drc.reserve((size_t)CH * NC * 8)) || (a && da.reserve((size_t)CH * NC * 8)) || (c && dc.reserve((size_t)CH * Q * 8)))
+    if (din.reserve((size_t)CH * NC) || (status && dst.reserve((size_t)CH)) || (need_pe && dpe.reserve((size_t)CH)) ||
+        (rc && drc.reserve((size_t)CH * NC)) || (a && da.reserve((size_t)CH * NC)) || (c && dc.reserve((size_t)CH * Q)))
         return 1;
     std::vector<double> pe_tmp;
     if (c && !pe) pe_tmp.resize((size_t)CH);
     for (int64_t t0 = 0; t0 < T; t0 += CH) {
         const int64_t n = std::min(CH, T - t0);
-        HIPCHK(hipMemcpyAsync(din.p, frames + t0 * NC, (size_t)n * NC * 8, hipMemcpyHostToDevice, an.st.s));
-        if (e2lpc::launch_features(P, Q, din.as<double>(), n, status ? dst.as<int32_t>() : nullptr,
-                                   need_pe ? dpe.as<double>() : nullptr, rc ? drc.as<double>() : nullptr,
-                                   a ? da.as<double>() : nullptr, c ? dc.as<double>() : nullptr, an.st.s))
+        HIPCHK(hipMemcpyAsync(din.get(), frames + t0 * NC, (size_t)n * NC * 8, hipMemcpyHostToDevice, an.st.s));
+        if (e2lpc::launch_features(P, Q, din.get(), n, status ? dst.get() : nullptr, need_pe ? dpe.get() : nullptr,
+                                   rc ? drc.get() : nullptr, a ? da.get() : nullptr, c ? dc.get() : nullptr, an.st.s))
             return e2vq_set_error("lpc features kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
         double* pe_h = pe ? pe + t0 : pe_tmp.data();
-        if (status) HIPCHK(hipMemcpyAsync(status + t0, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, an.st.s));
-        if (need_pe) HIPCHK(hipMemcpyAsync(pe_h, dpe.p, (size_t)n * 8, hipMemcpyDeviceToHost, an.st.s));
-        if (rc) HIPCHK(hipMemcpyAsync(rc + t0 * NC, drc.p, (size_t)n * NC * 8, hipMemcpyDeviceToHost, an.st.s));
-        if (a) HIPCHK(hipMemcpyAsync(a + t0 * NC, da.p, (size_t)n * NC * 8, hipMemcpyDeviceToHost, an.st.s));
-        if (c) HIPCHK(hipMemcpyAsync(c + t0 * Q, dc.p, (size_t)n * Q * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (status) HIPCHK(hipMemcpyAsync(status + t0, dst.get(), (size_t)n * 4, hipMemcpyDeviceToHost, an.st.s));
+        if (need_pe) HIPCHK(hipMemcpyAsync(pe_h, dpe.get(), (size_t)n * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (rc) HIPCHK(hipMemcpyAsync(rc + t0 * NC, drc.get(), (size_t)n * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (a) HIPCHK(hipMemcpyAsync(a + t0 * NC, da.get(), (size_t)n * NC * 8, hipMemcpyDeviceToHost, an.st.s));
+        if (c) HIPCHK(hipMemcpyAsync(c + t0 * Q, dc.get(), (size_t)n * Q * 8, hipMemcpyDeviceToHost, an.st.s));
         HIPCHK(hipStreamSynchronize(an.st.s));
         if (c)
             for (int64_t t = 0; t < n; ++t) c[(t0 + t) * Q] = log(sqrt(pe_h[t]));

@@ -2,6 +2,8 @@
 // sequences / reports out, on top of the session API.
 #include "vq_group.h"
 
+using namespace e2hip;
+
 // ==========================================================================================
 // Part 1: the reference's entry points
 // ==========================================================================================
@@ -92,6 +94,26 @@ PinnedPool& pinned_pool()
     static PinnedPool* pool = new PinnedPool();  // (never destroyed: see above)
     return *pool;
 }
+// a pool buffer held for one scope: back to the pool when the lease ends
+struct PinnedLease {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinnedLease() = default;
+    PinnedLease(const PinnedLease&) = delete;
+    PinnedLease& operator=(const PinnedLease&) = delete;
+    ~PinnedLease() { pinned_pool().release(p, bytes); }
+    bool acquire(size_t want) { return (p = pinned_pool().acquire(want, &bytes)) != nullptr; }
+    template <typename T>
+    T* as() const { return (T*)p; }
+};
+// a session destroyed with its scope
+struct Session {
+    e2vq_session* s = nullptr;
+    Session() = default;
+    Session(const Session&) = delete;
+    Session& operator=(const Session&) = delete;
+    ~Session() { e2vq_session_destroy(s); }
+};
 }  // namespace
 
 static int scan_predictors(const char* const* files, int n, int P_expected, PrdSet& ps)
@@ -124,23 +146,6 @@ static int upload_predictors(e2vq_session* s, const PrdSet& ps, i64 lo, i64 hi)
     const i64 T = hi - lo;
     if (T < 1) return e2vq_set_error("empty training shard");
     HIPCHK(hipSetDevice(s->device));
-    struct Res {
-        double* d = nullptr;
-        double* h[2] = {nullptr, nullptr};
-        size_t hb[2] = {0, 0};
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        hipStream_t st = nullptr;
-        ~Res()
-        {
-            if (st) (void)hipStreamSynchronize(st);  // (no copy still reads a staging buffer that goes back to the pool)
-            if (d) (void)hipFree(d);
-            for (int k = 0; k < 2; ++k) {
-                pinned_pool().release(h[k], hb[k]);
-                if (ev[k]) (void)hipEventDestroy(ev[k]);
-            }
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } r;
     static const bool timing = getenv("ECOZ2_VQ_TIMING") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tl = now();
@@ -151,36 +156,41 @@ static int upload_predictors(e2vq_session* s, const PrdSet& ps, i64 lo, i64 hi)
         tl = t1;
     };
     const i64 CH = std::min<i64>(T, 1 << 18);  // 78 MB of predictor vectors per chunk at P = 36
-    HIPCHK(hipMalloc(&r.d, (size_t)((T + 63) / 64 * 64) * NC * 8 + 16));  // (whole blocks + 16 bytes: the session may keep the buffer)
-    HIPCHK(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
+    // (the buffers and events before the stream that uses them: see Stream)
+    DeviceBuffer<double> d;
+    PinnedLease h[2];
+    Event ev[2];
+    Stream st;
+    if (d.reserve((size_t)((T + 63) / 64 * 64) * NC + 2)) return 1;  // (whole blocks + 16 bytes: the session may keep the buffer)
+    if (st.create()) return 1;
     for (int k = 0; k < 2; ++k) {
-        r.h[k] = (double*)pinned_pool().acquire((size_t)CH * NC * 8, &r.hb[k]);
-        if (!r.h[k]) return e2vq_set_error("no pinned memory for the upload staging (%zu bytes)", (size_t)CH * NC * 8);
-        HIPCHK(hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
+        if (!h[k].acquire((size_t)CH * NC * 8))
+            return e2vq_set_error("no pinned memory for the upload staging (%zu bytes)", (size_t)CH * NC * 8);
+        if (ev[k].create(hipEventDisableTiming)) return 1;
     }
     lap("allocations");
     int file = (int)(std::upper_bound(ps.first.begin(), ps.first.end(), lo) - ps.first.begin()) - 1;
     int k = 0;
     for (i64 t0 = lo; t0 < hi; t0 += CH, k ^= 1) {
         const i64 n = std::min(CH, hi - t0);
-        HIPCHK(hipEventSynchronize(r.ev[k]));  // (never recorded: returns at once) the copy out of this buffer is done
+        HIPCHK(hipEventSynchronize(ev[k].e));  // (never recorded: returns at once) the copy out of this buffer is done
         for (i64 got = 0; got < n;) {          // a chunk may span several files
             while (ps.first[(size_t)file + 1] <= t0 + got) ++file;
             const i64 in_file = t0 + got - ps.first[(size_t)file];
             const i64 take = std::min(n - got, ps.first[(size_t)file + 1] - (t0 + got));
-            if (e2vq_io::prd_read_range_mt(ps.files[file], ps.P, in_file, take, r.h[k] + (size_t)got * NC,
+            if (e2vq_io::prd_read_range_mt(ps.files[file], ps.P, in_file, take, h[k].as<double>() + (size_t)got * NC,
                                            e2vq_io::io_threads()))
                 return 1;
             got += take;
         }
-        HIPCHK(hipMemcpyAsync(r.d + (size_t)(t0 - lo) * NC, r.h[k], (size_t)n * NC * 8, hipMemcpyHostToDevice, r.st));
-        HIPCHK(hipEventRecord(r.ev[k], r.st));
+        HIPCHK(hipMemcpyAsync(d.get() + (size_t)(t0 - lo) * NC, h[k].as<double>(), (size_t)n * NC * 8, hipMemcpyHostToDevice, st.s));
+        HIPCHK(hipEventRecord(ev[k].e, st.s));
     }
-    HIPCHK(hipStreamSynchronize(r.st));
+    HIPCHK(hipStreamSynchronize(st.s));
     lap("read + H2D");
     bool adopted = false;
-    const int rc = e2vq_set_frames_device_impl(s, r.d, T, &adopted);  // (synchronises: the row-major copy can go, unless the session kept it)
-    if (adopted) r.d = nullptr;
+    const int rc = e2vq_set_frames_device_impl(s, d.get(), T, &adopted);  // (synchronises: the row-major copy can go, unless the session kept it)
+    if (adopted) (void)d.release();
     lap("re-layout + images");
     return rc;
 }
@@ -238,9 +248,9 @@ static int learn_common(int P, double eps, const char* class_name, const double*
     if (scan_predictors(files, n, P, ps)) return 1;
     const i64 T = ps.T;
     printf("Codebook generation:\n\n%lld training vectors (ε=%g)\n", (long long)T, eps);
-    const int ndev = e2vq_device_count();
-    if (ndev < 1) return e2vq_set_error("no HIP device available; this library has no CPU path");
-    const int dev0 = e2vq_env_int("ECOZ2_VQ_DEVICE", 0);
+    const int ndev = device_count();
+    if (!ndev) return 1;
+    const int dev0 = env_device();
     int world = e2vq_env_int("ECOZ2_VQ_GPUS", 1);
     if (world < 1) world = 1;
     if ((i64)world > T) world = (int)T;  // every rank needs at least one training vector
@@ -256,7 +266,7 @@ static int learn_common(int P, double eps, const char* class_name, const double*
     printf("sharding over %d rank(s) on %d device(s)\n", world, ndev);
     if (world > e2vq::E2VQ_MAX_LOCAL_RANKS) return e2vq_set_error("ECOZ2_VQ_GPUS=%d exceeds %d in-process ranks", world, e2vq::E2VQ_MAX_LOCAL_RANKS);
     std::vector<int> devs((size_t)world);
-    for (int r = 0; r < world; ++r) devs[(size_t)r] = (dev0 + r) % ndev;
+    for (int r = 0; r < world; ++r) devs[(size_t)r] = worker_device(dev0, r, ndev);
     struct Closer {  // (events and communicators go with the group on every return path)
         E2Group* g;
         ~Closer() { e2g_destroy(g); }
@@ -269,38 +279,21 @@ static int learn_common(int P, double eps, const char* class_name, const double*
         ctx[(size_t)r].rank = r;
         e2g_hook(G.g, r, &ctx[(size_t)r].fn, &ctx[(size_t)r].user, &ctx[(size_t)r].force);
     }
-    std::vector<int> rcs((size_t)world, 0);
-    std::vector<std::thread> th;
-    auto shard = [&](int r, i64* lo, i64* hi) {
-        const i64 base = T / world, rem = T % world;
-        *lo = r * base + std::min<i64>(r, rem);
-        *hi = *lo + base + (r < rem ? 1 : 0);
-    };
-    for (int r = 1; r < world; ++r) {
-        th.emplace_back([&, r]() {
-            i64 lo, hi;
-            shard(r, &lo, &hi);
-            rcs[r] = learn_rank(e2g_device(G.g, r), eps, class_name, base_refl, base_M, ps, lo, hi, &ctx[r], world, nullptr, nullptr);
-        });
-    }
-    {  // rank 0 runs on the calling thread: files, messages and the callback come from here
+    // rank 0 runs on the calling thread: files, messages and the callback come from here
+    const int rc = run_workers(world, [&](int r) {
         i64 lo, hi;
-        shard(0, &lo, &hi);
-        rcs[0] = learn_rank(e2g_device(G.g, 0), eps, class_name, base_refl, base_M, ps, lo, hi, &ctx[0], world, target, cb);
-    }
-    for (auto& t : th) t.join();
+        split_range(T, world, r, &lo, &hi);
+        return learn_rank(e2g_device(G.g, r), eps, class_name, base_refl, base_M, ps, lo, hi, &ctx[(size_t)r], world,
+                          r == 0 ? target : nullptr, r == 0 ? cb : nullptr);
+    });
     if (use_rccl && !getenv("ECOZ2_VQ_QUIET")) {
         long calls = 0, bytes = 0;
         e2g_rccl_traffic(G.g, 0, &calls, &bytes);
         printf("collective: rank 0 made %ld ncclAllReduce call(s), %ld bytes\n", calls, bytes);
     }
-    for (int rc : rcs)
-        if (rc) {
-            // the message of the rank that failed FIRST (the others only report the broken barrier)
-            if (!e2g_first_error(G.g).empty()) snprintf(e2vq_err_buf(), 1024, "%s", e2g_first_error(G.g).c_str());
-            return rc;
-        }
-    return 0;
+    // the message of the rank that failed FIRST (the others only report the broken barrier)
+    if (rc && !e2g_first_error(G.g).empty()) snprintf(e2vq_err_buf(), 1024, "%s", e2g_first_error(G.g).c_str());
+    return rc;
 }
 
 extern "C" int ecoz2_vq_learn(int prediction_order, double epsilon, const char* codebook_class_name,
@@ -383,7 +376,7 @@ struct QSlot {
     double* d_frames = nullptr;
     unsigned short* d_sym = nullptr;
     double* d_dmin = nullptr;
-    hipEvent_t done = nullptr;
+    Event done;
     int unit = -1;  // index of the unit in flight, -1 = free
 };
 
@@ -430,97 +423,97 @@ int quantize_worker(int device, QShared& sh, const double* refl)
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = now();
     const int NC = sh.P + 1;
-    e2vq_session* s = nullptr;
-    if (e2vq_session_create(device, sh.P, &s)) return 1;
-    hipStream_t st = nullptr;
-    QSlot slots[2];
-    char* h_block = nullptr;
-    char* d_block = nullptr;
-    int rc = e2vq_set_codebook(s, refl, sh.M);
-    if (!rc && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) rc = e2vq_set_error("stream creation failed");
-    if (!rc) rc = e2vq_set_stream(s, (void*)st);
-    // one pinned and one device allocation, carved into the two slots (frames | distortions | symbols, 256-byte aligned)
-    const size_t fb = ((size_t)sh.chunk * NC * 8 + 255) & ~(size_t)255, db = ((size_t)sh.chunk * 8 + 255) & ~(size_t)255,
-                 sb = ((size_t)sh.chunk * 2 + 64 + 255) & ~(size_t)255, slot_bytes = fb + db + sb;
-    size_t h_block_bytes = 0;
-    if (!rc && !(h_block = (char*)pinned_pool().acquire(2 * slot_bytes, &h_block_bytes)))
-        rc = e2vq_set_error("no pinned memory for the quantize staging (%zu bytes)", 2 * slot_bytes);
-    if (!rc && hipMalloc((void**)&d_block, 2 * slot_bytes) != hipSuccess)
-        rc = e2vq_set_error("no device memory for the quantize staging (%zu bytes)", 2 * slot_bytes);
-    for (int k = 0; k < 2 && !rc; ++k) {
-        QSlot& q = slots[k];
-        q.h_frames = (double*)(h_block + k * slot_bytes);
-        q.h_dmin = (double*)(h_block + k * slot_bytes + fb);
-        q.h_sym = (uint16_t*)(h_block + k * slot_bytes + fb + db);
-        q.d_frames = (double*)(d_block + k * slot_bytes);
-        q.d_dmin = (double*)(d_block + k * slot_bytes + fb);
-        q.d_sym = (unsigned short*)(d_block + k * slot_bytes + fb + db);
-        if (hipEventCreateWithFlags(&q.done, hipEventDisableTiming) != hipSuccess) rc = e2vq_set_error("event creation failed");
-    }
-    const double t_setup = now();
-    auto finish = [&](QSlot& q) -> int {  // results of the unit in flight in q: distortion sums + .seq files
-        if (q.unit < 0) return 0;
-        HIPCHK(hipEventSynchronize(q.done));
-        const QUnit& u = sh.units[(size_t)q.unit];
-        q.unit = -1;
-        for (const QSegment& g : u.segs) {
-            QFileResult& r = sh.results[(size_t)g.file];
-            if (g.whole) {
-                double e = 0.0;
-                for (i64 t = 0; t < g.n; ++t) e += q.h_dmin[g.off + t] - 1.0;
-                r.e = e;
-                if (e2vq_seq_write(r.seq_path.c_str(), r.cls.c_str(), sh.M, q.h_sym + g.off, g.n)) return 1;
-            } else {
-                quantize_fold(r, g.t0, q.h_dmin + g.off, g.n);
-                if (e2vq_io::seq_write_range(r.tmp_path.c_str(), g.t0, q.h_sym + g.off, g.n)) return 1;
+    double t_setup, t_work;
+    int rc, done_units = 0;
+    {
+        // The staging and the events come before the stream: the stream is drained before the pinned block goes back to
+        // the pool, where another worker may take it.  The session comes after it: destroyed before its stream.
+        PinnedLease h_block;
+        DeviceBuffer<char> d_block;
+        QSlot slots[2];
+        Stream st;
+        Session vq;
+        auto setup = [&]() -> int {
+            if (e2vq_session_create(device, sh.P, &vq.s) || e2vq_set_codebook(vq.s, refl, sh.M) || st.create() ||
+                e2vq_set_stream(vq.s, (void*)st.s))
+                return 1;
+            // one pinned and one device allocation, carved into the two slots (frames | distortions | symbols, 256-byte aligned)
+            const size_t fb = ((size_t)sh.chunk * NC * 8 + 255) & ~(size_t)255, db = ((size_t)sh.chunk * 8 + 255) & ~(size_t)255,
+                         sb = ((size_t)sh.chunk * 2 + 64 + 255) & ~(size_t)255, slot_bytes = fb + db + sb;
+            if (!h_block.acquire(2 * slot_bytes))
+                return e2vq_set_error("no pinned memory for the quantize staging (%zu bytes)", 2 * slot_bytes);
+            if (d_block.reserve(2 * slot_bytes))
+                return e2vq_set_error("no device memory for the quantize staging (%zu bytes)", 2 * slot_bytes);
+            for (int k = 0; k < 2; ++k) {
+                QSlot& q = slots[k];
+                char* h = h_block.as<char>() + k * slot_bytes;
+                char* d = d_block.get() + k * slot_bytes;
+                q.h_frames = (double*)h;
+                q.h_dmin = (double*)(h + fb);
+                q.h_sym = (uint16_t*)(h + fb + db);
+                q.d_frames = (double*)d;
+                q.d_dmin = (double*)(d + fb);
+                q.d_sym = (unsigned short*)(d + fb + db);
+                if (q.done.create(hipEventDisableTiming)) return 1;
             }
-        }
-        return 0;
-    };
-    int k = 0, done_units = 0;
-    while (!rc && !sh.failed.load()) {
-        const int ui = sh.next.fetch_add(1);
-        if (ui >= (int)sh.units.size()) break;
-        QSlot& q = slots[k & 1];
-        ++k;
-        rc = finish(q);
-        if (rc) break;
-        const QUnit& u = sh.units[(size_t)ui];
-        bool finite = true;
-        for (const QSegment& g : u.segs) {
-            if (g.n < 1) continue;
-            bool fin = true;
-            rc = e2vq_io::prd_read_range_mt(sh.files[g.file], sh.P, g.t0, g.n, q.h_frames + (size_t)g.off * NC,
-                                            e2vq_io::io_threads(), &fin);
-            if (rc) break;
-            if (!fin) {
-                rc = e2vq_set_error("%s: contains NaN or infinite values", sh.files[g.file]);
-                finite = false;
-                break;
+            return 0;
+        };
+        auto finish = [&](QSlot& q) -> int {  // results of the unit in flight in q: distortion sums + .seq files
+            if (q.unit < 0) return 0;
+            HIPCHK(hipEventSynchronize(q.done.e));
+            const QUnit& u = sh.units[(size_t)q.unit];
+            q.unit = -1;
+            for (const QSegment& g : u.segs) {
+                QFileResult& r = sh.results[(size_t)g.file];
+                if (g.whole) {
+                    double e = 0.0;
+                    for (i64 t = 0; t < g.n; ++t) e += q.h_dmin[g.off + t] - 1.0;
+                    r.e = e;
+                    if (e2vq_seq_write(r.seq_path.c_str(), r.cls.c_str(), sh.M, q.h_sym + g.off, g.n)) return 1;
+                } else {
+                    quantize_fold(r, g.t0, q.h_dmin + g.off, g.n);
+                    if (e2vq_io::seq_write_range(r.tmp_path.c_str(), g.t0, q.h_sym + g.off, g.n)) return 1;
+                }
             }
-        }
-        if (rc || !finite) break;
-        q.unit = ui;
-        if (u.n > 0) {
-            hipError_t e = hipMemcpyAsync(q.d_frames, q.h_frames, (size_t)u.n * NC * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) rc = e2vq_quantize_device(s, q.d_frames, u.n, q.d_sym, q.d_dmin);
-            if (e == hipSuccess && !rc) e = hipMemcpyAsync(q.h_sym, q.d_sym, (size_t)u.n * 2, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && !rc) e = hipMemcpyAsync(q.h_dmin, q.d_dmin, (size_t)u.n * 8, hipMemcpyDeviceToHost, st);
-            if (e != hipSuccess) rc = e2vq_set_error("quantize: copy failed: %s", hipGetErrorString(e));
-        }
-        if (!rc && hipEventRecord(q.done, st) != hipSuccess) rc = e2vq_set_error("event record failed");
-        ++done_units;
+            return 0;
+        };
+        auto work = [&]() -> int {
+            int k = 0;
+            while (!sh.failed.load()) {
+                const int ui = sh.next.fetch_add(1);
+                if (ui >= (int)sh.units.size()) break;
+                QSlot& q = slots[k & 1];
+                ++k;
+                if (finish(q)) return 1;
+                const QUnit& u = sh.units[(size_t)ui];
+                for (const QSegment& g : u.segs) {
+                    if (g.n < 1) continue;
+                    bool fin = true;
+                    if (e2vq_io::prd_read_range_mt(sh.files[g.file], sh.P, g.t0, g.n, q.h_frames + (size_t)g.off * NC,
+                                                   e2vq_io::io_threads(), &fin))
+                        return 1;
+                    if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", sh.files[g.file]);
+                }
+                q.unit = ui;
+                if (u.n > 0) {
+                    HIPCHK(hipMemcpyAsync(q.d_frames, q.h_frames, (size_t)u.n * NC * 8, hipMemcpyHostToDevice, st.s));
+                    if (e2vq_quantize_device(vq.s, q.d_frames, u.n, q.d_sym, q.d_dmin)) return 1;
+                    HIPCHK(hipMemcpyAsync(q.h_sym, q.d_sym, (size_t)u.n * 2, hipMemcpyDeviceToHost, st.s));
+                    HIPCHK(hipMemcpyAsync(q.h_dmin, q.d_dmin, (size_t)u.n * 8, hipMemcpyDeviceToHost, st.s));
+                }
+                HIPCHK(hipEventRecord(q.done.e, st.s));
+                ++done_units;
+            }
+            for (int j = 0; j < 2; ++j)
+                if (finish(slots[(k + j) & 1])) return 1;  // oldest first
+            return 0;
+        };
+        rc = setup();
+        t_setup = now();
+        if (!rc) rc = work();
+        if (rc) sh.failed.store(true);
+        t_work = now();
     }
-    for (int j = 0; j < 2 && !rc; ++j) rc = finish(slots[(k + j) & 1]);  // oldest first
-    if (rc) sh.failed.store(true);
-    if (st) (void)hipStreamSynchronize(st);
-    const double t_work = now();
-    for (QSlot& q : slots)
-        if (q.done) (void)hipEventDestroy(q.done);
-    pinned_pool().release(h_block, h_block_bytes);  // (the stream was synchronised above)
-    if (d_block) (void)hipFree(d_block);
-    e2vq_session_destroy(s);
-    if (st) (void)hipStreamDestroy(st);
     if (timing)
         fprintf(stderr, "[ecoz2 vq quantize, device %d] setup %.1f ms, %d unit(s) %.1f ms, teardown %.1f ms\n", device,
                 (t_setup - t_start) * 1e3, done_units, (t_work - t_setup) * 1e3, (now() - t_work) * 1e3);
@@ -541,9 +534,9 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
     if (e2vq_cbook_info(nom_raas, cb_cls, &P, &M)) return 1;
     std::vector<double> refl((size_t)M * (P + 1));
     if (e2vq_cbook_read(nom_raas, refl.data(), M)) return 1;
-    const int ndev = e2vq_device_count();
-    if (ndev < 1) return e2vq_set_error("no HIP device available; this library has no CPU path");
-    const int dev0 = e2vq_env_int("ECOZ2_VQ_DEVICE", 0);
+    const int ndev = device_count();
+    if (!ndev) return 1;
+    const int dev0 = env_device();
     const char* root = e2vq_env_str("ECOZ2_VQ_OUT_ROOT", ".");
     QShared sh(num_predictors);
     // split files are written to <seq>.tmp and renamed at the end: whatever way this call ends short of that, the .tmp files
@@ -612,21 +605,7 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
         const int distinct = std::min(W, ndev);
         if (W > distinct) W = std::max(distinct, std::min(W, num_predictors / 256));
     }
-    std::vector<int> rcs((size_t)W, 0);
-    std::vector<std::string> errs((size_t)W);
-    std::vector<std::thread> th;
-    auto run = [&](int w) {
-        rcs[(size_t)w] = quantize_worker((dev0 + w) % ndev, sh, refl.data());
-        if (rcs[(size_t)w]) errs[(size_t)w] = e2vq_err_buf();
-    };
-    for (int w = 1; w < W; ++w) th.emplace_back(run, w);
-    run(0);
-    for (auto& t : th) t.join();
-    for (int w = 0; w < W; ++w)
-        if (rcs[(size_t)w]) {
-            if (w > 0) snprintf(e2vq_err_buf(), 1024, "%s", errs[(size_t)w].c_str());
-            return rcs[(size_t)w];
-        }
+    if (run_workers(W, [&](int w) { return quantize_worker(worker_device(dev0, w, ndev), sh, refl.data()); })) return 1;
     for (QFileResult& r : sh.results)
         if (!r.tmp_path.empty()) {
             if (rename(r.tmp_path.c_str(), r.seq_path.c_str()) != 0)
@@ -709,59 +688,44 @@ extern "C" int ecoz2_vq_classify(const char* const* cb_filenames, int num_codebo
         }
         flush();
     }
-    e2vq_session* s = nullptr;
-    const int device = e2vq_env_int("ECOZ2_VQ_DEVICE", 0);
-    if (e2vq_session_create(device, P, &s)) return 1;
     // sums of (dmin - 1) per (file, codebook), in frame order (units are processed in order, frames within a unit too)
     std::vector<double> esum((size_t)num_predictors * num_codebooks, 0.0);
-    int rc = 0;
-    hipStream_t st = nullptr;
-    double *h_frames = nullptr, *h_dmin = nullptr, *d_frames = nullptr, *d_dmin = nullptr;
-    unsigned short* d_sym = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) rc = e2vq_set_error("stream creation failed");
-    if (!rc) rc = e2vq_set_stream(s, (void*)st);
-    size_t h_frames_bytes = 0, h_dmin_bytes = 0;
-    if (!rc && (!(h_frames = (double*)pinned_pool().acquire((size_t)chunk * NC * 8, &h_frames_bytes)) ||
-                !(h_dmin = (double*)pinned_pool().acquire((size_t)chunk * 8, &h_dmin_bytes)) ||
-                hipMalloc((void**)&d_frames, (size_t)chunk * NC * 8) != hipSuccess || hipMalloc((void**)&d_dmin, (size_t)chunk * 8) != hipSuccess ||
-                hipMalloc((void**)&d_sym, (size_t)chunk * 2 + 64) != hipSuccess))
-        rc = e2vq_set_error("no memory for the classify staging (%lld frames per unit)", (long long)chunk);
-    for (size_t u = 0; u < units.size() && !rc; ++u) {
-        const QUnit& un = units[u];
-        if (un.n < 1) continue;
-        for (const QSegment& g : un.segs) {
-            if (g.n < 1) continue;
-            bool fin = true;
-            rc = e2vq_io::prd_read_range_mt(prd_filenames[g.file], P, g.t0, g.n, h_frames + (size_t)g.off * NC, e2vq_io::io_threads(), &fin);
-            if (!rc && !fin) rc = e2vq_set_error("%s: contains NaN or infinite values", prd_filenames[g.file]);
-            if (rc) break;
-        }
-        if (rc) break;
-        if (hipMemcpyAsync(d_frames, h_frames, (size_t)un.n * NC * 8, hipMemcpyHostToDevice, st) != hipSuccess)
-            rc = e2vq_set_error("upload of the predictor vectors failed");
-        for (int i = 0; i < num_codebooks && !rc; ++i) {
-            rc = e2vq_set_codebook(s, cbs[i].refl.data(), cbs[i].M);
-            if (!rc) rc = e2vq_quantize_device(s, d_frames, un.n, d_sym, d_dmin);
-            if (!rc && hipMemcpyAsync(h_dmin, d_dmin, (size_t)un.n * 8, hipMemcpyDeviceToHost, st) != hipSuccess)
-                rc = e2vq_set_error("download of the distortions failed");
-            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = e2vq_set_error("classify: device work failed");
-            if (rc) break;
+    {
+        // (staging before the stream, session after it: as in quantize_worker)
+        PinnedLease h_frames, h_dmin;
+        DeviceBuffer<double> d_frames, d_dmin;
+        DeviceBuffer<unsigned short> d_sym;
+        Stream st;
+        Session vq;
+        if (e2vq_session_create(env_device(), P, &vq.s) || st.create() || e2vq_set_stream(vq.s, (void*)st.s)) return 1;
+        if (!h_frames.acquire((size_t)chunk * NC * 8) || !h_dmin.acquire((size_t)chunk * 8) || d_frames.reserve((size_t)chunk * NC) ||
+            d_dmin.reserve((size_t)chunk) || d_sym.reserve((size_t)chunk + 32))
+            return e2vq_set_error("no memory for the classify staging (%lld frames per unit)", (long long)chunk);
+        for (const QUnit& un : units) {
+            if (un.n < 1) continue;
             for (const QSegment& g : un.segs) {
-                double e = esum[(size_t)g.file * num_codebooks + i];
-                for (i64 t = 0; t < g.n; ++t) e += h_dmin[g.off + t] - 1.0;
-                esum[(size_t)g.file * num_codebooks + i] = e;
+                if (g.n < 1) continue;
+                bool fin = true;
+                if (e2vq_io::prd_read_range_mt(prd_filenames[g.file], P, g.t0, g.n, h_frames.as<double>() + (size_t)g.off * NC,
+                                               e2vq_io::io_threads(), &fin))
+                    return 1;
+                if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", prd_filenames[g.file]);
+            }
+            HIPCHK(hipMemcpyAsync(d_frames.get(), h_frames.as<double>(), (size_t)un.n * NC * 8, hipMemcpyHostToDevice, st.s));
+            for (int i = 0; i < num_codebooks; ++i) {
+                if (e2vq_set_codebook(vq.s, cbs[i].refl.data(), cbs[i].M) ||
+                    e2vq_quantize_device(vq.s, d_frames.get(), un.n, d_sym.get(), d_dmin.get()))
+                    return 1;
+                HIPCHK(hipMemcpyAsync(h_dmin.as<double>(), d_dmin.get(), (size_t)un.n * 8, hipMemcpyDeviceToHost, st.s));
+                HIPCHK(hipStreamSynchronize(st.s));
+                for (const QSegment& g : un.segs) {
+                    double e = esum[(size_t)g.file * num_codebooks + i];
+                    for (i64 t = 0; t < g.n; ++t) e += h_dmin.as<double>()[g.off + t] - 1.0;
+                    esum[(size_t)g.file * num_codebooks + i] = e;
+                }
             }
         }
     }
-    if (st) (void)hipStreamSynchronize(st);
-    pinned_pool().release(h_frames, h_frames_bytes);
-    pinned_pool().release(h_dmin, h_dmin_bytes);
-    if (d_frames) (void)hipFree(d_frames);
-    if (d_dmin) (void)hipFree(d_dmin);
-    if (d_sym) (void)hipFree(d_sym);
-    e2vq_session_destroy(s);
-    if (st) (void)hipStreamDestroy(st);
-    if (rc) return rc;
     std::vector<double> score((size_t)num_predictors * num_codebooks, 0.0);
     for (int k = 0; k < num_predictors; ++k)
         for (int i = 0; i < num_codebooks; ++i)

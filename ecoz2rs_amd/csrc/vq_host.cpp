@@ -170,13 +170,7 @@ extern "C" int e2vq_session_create(int device, int prediction_order, e2vq_sessio
     *out = nullptr;
     if (prediction_order < 1 || prediction_order > E2VQ_MAX_P)
         return e2vq_set_error("prediction order %d out of range [1, %d]", prediction_order, E2VQ_MAX_P);
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-        return e2vq_set_error("no HIP device available (%s); this library has no CPU path",
-                              e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    if (device < 0 || device >= ndev) return e2vq_set_error("device %d not in [0, %d)", device, ndev);
-    HIPCHK(hipSetDevice(device));
+    if (e2hip::require_device(device)) return 1;
     e2vq_session* s = new e2vq_session();
     s->device = device;
     s->P = prediction_order;

@@ -1,11 +1,12 @@
 // vq_session.h -- what the host translation units of libecoz2vq.so share (internal; the C-ABI is include/ecoz2_vq.h):
-// the session object, error plumbing, and the few internal functions that cross files.
+// the session object and the few internal functions that cross files (error plumbing and HIP handles: hip_host.h).
 //   vq_host.cpp   session life cycle, training set, codebook, save / restore, the LBG ladder, quantize on resident data
 //   vq_pass.cpp   one LBG iteration: the pass (kernel choice and launches), statistics, the speculative update
 //   vq_group.cpp  the in-process group: peer-to-peer exchange, RCCL loaded with dlopen
 //   vq_entry.cpp  the reference's entry points: file readers, upload, ecoz2_vq_learn / quantize / classify / show
 #pragma once
 #include "../../include/ecoz2_vq.h"
+#include "hip_host.h"
 #include "vq_device.h"
 #include "vq_fixed.h"
 #include "vq_io.h"
@@ -34,17 +35,6 @@ using e2vq::DevScalars;
 #define E2VQ_MAX_PASSES 1000  // safety cap per codebook size (same in the oracle)
 typedef long long i64;
 typedef unsigned long long u64;
-
-// errors: the message of the calling thread (e2vq_last_error); e2vq_set_error returns 1
-char* e2vq_err_buf();                 // 1024 bytes, thread-local
-int e2vq_set_error(const char* fmt, ...);
-
-#define HIPCHK(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return e2vq_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 struct e2vq_session {
     int device = 0, P = 0, NC = 0, FB = 64, RS = 0, NPAD = 0;
@@ -246,6 +236,5 @@ bool e2vq_use_prefilter(const e2vq_session* s, int mode);                       
 int e2vq_fold_pending_timing(e2vq_session* s);                                       // vq_pass.cpp
 int e2vq_pass_stats_impl(e2vq_session* s, e2vq_level_stats* out, bool wait_failed);  // vq_pass.cpp
 int e2vq_resolve_failed_cells(e2vq_session* s);                                      // vq_pass.cpp
-int e2vq_env_int(const char* name, int dflt);                                        // vq_entry.cpp
-const char* e2vq_env_str(const char* name, const char* dflt);
+const char* e2vq_env_str(const char* name, const char* dflt);                          // vq_entry.cpp
 

@@ -688,6 +688,16 @@ def test_quantize_workers_give_identical_seq_files(tmp_path, monkeypatch, capfd,
         total += acc
         assert f"{files[i]}: 'c{i % 3}' T={b - a} avg distortion={(acc / (b - a) if b > a else 0.0):g} ->" in out
     assert f"total: 8 predictor file(s), 30000 vectors, M={M}, avg distortion={total / 30000:g}" in out
+    if chunk:  # a split file whose last unit is not finite: the call fails, its .seq.tmp goes, nothing is moved into place
+        seqs = {p: p.read_bytes() for p in tmp_path.rglob("*.seq")}
+        bad = frames[:9000].copy()
+        bad[8500, 5] = np.nan
+        fb = tmp_path / "data" / "predictors" / "x" / "bad_long.prd"
+        e.formats.write_prd(str(fb), "x", bad)
+        with pytest.raises(e.Ecoz2Error, match="NaN or infinite"):
+            e.vq_quantize(str(cb), files + [str(fb)])
+        assert not list(tmp_path.rglob("*.seq.tmp"))
+        assert {p: p.read_bytes() for p in tmp_path.rglob("*.seq")} == seqs
     # non-finite input is refused (the file entry points check it; the sweep's argmin assumes finite data)
     bad = frames[:10].copy()
     bad[3, 5] = np.nan
