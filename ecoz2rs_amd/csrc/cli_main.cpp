@@ -35,6 +35,7 @@ static int usage()
             "  ecoz2 vq classify [-r] --codebooks <files|dirs>... --tt <TRAIN|TEST> --predictors <files|dirs|tt.csv>...\n"
             "  ecoz2 vq show [-f <from>] [-t <to>] <codebook>\n"
             "  ecoz2 seq show [-c] [-L] [--full] [--pickle out.pkl -M <M> --tt <TRAIN|TEST> [--class-name c]] <file.seq|tt.csv>...\n"
+            "  ecoz2 seq show [-P] [-Q] --hmm <model> [-c] [-L] [--full] <file.seq>...\n"
             "  ecoz2 prd show [-k] [--predictors] [--cepstrum <Q>] [-f|--from a] [-t|--to b] [--zrs] [--pickle <out.pkl>]\n"
             "                 <file.prd|predictor.cbor>\n"
             "  ecoz2 {nb|mm} learn -M <M> [--class-name <class>] <file.seq|dirs|tt.csv>...\n"
@@ -247,10 +248,11 @@ static bool write_pickle(const std::string& path, const std::vector<std::vector<
     return fclose(fp) == 0;
 }
 
+// With -P (forward ln P) or -Q (Viterbi path and its ln P*) under --hmm <model>: e2vq_seq_show_files, on the GPU
 static int seq_show(int argc, char** argv)
 {
-    bool no_sequence = false, only_length = false, full = false;
-    std::string pickle, cls_filter, tt;
+    bool no_sequence = false, only_length = false, full = false, with_prob = false, gen_q_opt = false;
+    std::string pickle, cls_filter, tt, hmm;
     int codebook_size = -1;
     std::vector<std::string> files;
     for (int i = 0; i < argc; ++i) {
@@ -258,6 +260,9 @@ static int seq_show(int argc, char** argv)
         if (a == "-c") no_sequence = true;
         else if (a == "-L") only_length = true;
         else if (a == "--full") full = true;
+        else if (a == "-P") with_prob = true;
+        else if (a == "-Q") gen_q_opt = true;
+        else if (a == "--hmm" && i + 1 < argc) hmm = argv[++i];
         else if (a == "--pickle" && i + 1 < argc) pickle = argv[++i];
         else if (a == "--class-name" && i + 1 < argc) cls_filter = argv[++i];
         else if (a == "--tt" && i + 1 < argc) tt = argv[++i];
@@ -266,6 +271,22 @@ static int seq_show(int argc, char** argv)
         else return usage();
     }
     if (files.empty()) return usage();
+    if (with_prob || gen_q_opt) {
+        if (!pickle.empty()) {
+            fprintf(stderr, "-P / -Q cannot be combined with --pickle\n");
+            return 2;
+        }
+        if (hmm.empty()) {
+            fprintf(stderr, "-P / -Q need a model: --hmm <file.hmm>\n");
+            return 2;
+        }
+        auto ps = cptrs(files);
+        if (e2vq_seq_show_files(with_prob, gen_q_opt, no_sequence, hmm.c_str(), ps.data(), (int)ps.size(), full, only_length)) {
+            printf("%s\n", e2vq_last_error());
+            return 1;
+        }
+        return 0;
+    }
     if (!pickle.empty()) {  // src/seq/mod.rs:88-118
         if (codebook_size < 0 || tt.empty()) {
             printf("--codebook-size and --tt required when --pickle given\n");

@@ -34,4 +34,15 @@ long long fb_scratch_words(int N);
 void launch_reestimate(int N, int M, const long long* acc, double epsilon, double* pi, double* A, double* B,
                        hipStream_t st);
 
+// Viterbi decoding (hmm_viterbi.hip) of S sequences under one model given as logarithms (lm.pi / lm.A / lm.B hold
+// lpi, lA, lB; -inf where the probability is 0).  Out at [s]: logp = ln P*, status (0 ok, 1 logp = -inf, 2 symbol >= M),
+// and with psi: qlast[s] = q_{T-1} and psi_t[j] (u16) at psi[(offs[s] - psi0 + t) * N + j], t >= 1.  psi null: neither
+// (the kernels without the path).  offs: S+1 symbol offsets.
+void launch_viterbi(const ModelDev& lm, const unsigned short* sym, const long long* offs, int S, long long psi0,
+                    unsigned short* psi, double* logp, int* qlast, int* status, hipStream_t st);
+// the path of each of the S sequences from psi / qlast / status of launch_viterbi (a launch of its own, on the same
+// stream): path[offs[s] + t] = q_t, every entry 0xFFFF when status is 2
+void launch_backtrack(int N, const long long* offs, int S, long long psi0, const unsigned short* psi, const int* qlast,
+                      const int* status, unsigned short* path, hipStream_t st);
+
 }  // namespace e2hmm

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <map>
 #include <string>
 #include <thread>
@@ -347,6 +348,105 @@ struct Trainer {
         return 0;
     }
 };
+
+// ---- Viterbi ---------------------------------------------------------------------------------------
+// lpi | lA | lB: the C library's log of every parameter, log 0 = -inf.  A negative, NaN or infinite parameter is refused
+// (no +inf can then enter a sum, so no NaN can arise on the device).
+int log_model(const Hmm& h, std::vector<double>& flat)
+{
+    flat.clear();
+    flat.reserve(h.pi.size() + h.A.size() + h.B.size());
+    const std::vector<double>* parts[3] = {&h.pi, &h.A, &h.B};
+    const char* names[3] = {"pi", "A", "B"};
+    for (int k = 0; k < 3; ++k)
+        for (size_t i = 0; i < parts[k]->size(); ++i) {
+            const double x = (*parts[k])[i];
+            if (!(x >= 0.0) || !std::isfinite(x))
+                return e2vq_set_error("HMM parameter %s[%zu] = %g: not a finite non-negative number", names[k], i, x);
+            flat.push_back(x == 0.0 ? -INFINITY : log(x));
+        }
+    return 0;
+}
+
+// psi bytes per launch: whole sequences up to ECOZ2_HMM_VITERBI_CHUNK_BYTES (default 256 MiB); a longer sequence alone
+i64 viterbi_chunk_bytes()
+{
+    const char* v = getenv("ECOZ2_HMM_VITERBI_CHUNK_BYTES");
+    const i64 b = v && *v ? atoll(v) : (i64)256 << 20;
+    return std::max<i64>(b, 1);
+}
+
+// Viterbi of S device-resident sequences (hoffs: the S+1 offsets on the host, to cut the launches) under the model
+// whose logarithms `lflat` holds; path (may be null: no psi, no backtrack) receives hoffs[S] states
+int viterbi_device(int N, int M, const std::vector<double>& lflat, const unsigned short* d_sym, const i64* d_offs,
+                   const i64* hoffs, int S, hipStream_t st, uint16_t* path, double* logp, int* status)
+{
+    DeviceBuffer<double> d_model, d_logp;
+    DeviceBuffer<int> d_status, d_qlast;
+    DeviceBuffer<unsigned short> d_psi, d_path;
+    if (d_model.upload(lflat.data(), lflat.size(), st)) return 1;
+    HIPCHK(hipStreamSynchronize(st));  // (`lflat` may go)
+    const double* base = d_model.get();
+    const ModelDev lm{N, M, base, base + N, base + N + (size_t)N * N};
+    if (d_logp.reserve((size_t)S) || d_status.reserve((size_t)S)) return 1;
+    if (!path) {
+        e2hmm::launch_viterbi(lm, d_sym, d_offs, S, 0, nullptr, d_logp.get(), nullptr, d_status.get(), st);
+        HIPCHK(hipGetLastError());
+    } else {
+        const i64 budget = viterbi_chunk_bytes(), row = 2 * (i64)N;
+        std::vector<std::pair<int, int>> chunks;
+        i64 max_syms = 0;
+        for (int s0 = 0; s0 < S;) {
+            int s1 = s0 + 1;
+            while (s1 < S && (hoffs[s1 + 1] - hoffs[s0]) * row <= budget) ++s1;
+            chunks.emplace_back(s0, s1);
+            max_syms = std::max(max_syms, hoffs[s1] - hoffs[s0]);
+            s0 = s1;
+        }
+        if (d_psi.reserve((size_t)max_syms * N) || d_path.reserve((size_t)hoffs[S]) || d_qlast.reserve((size_t)S)) return 1;
+        // (one stream: a chunk's forward pass writes psi only after the previous chunk's backtrack has read it)
+        for (const auto& c : chunks) {
+            const int s0 = c.first, n = c.second - c.first;
+            e2hmm::launch_viterbi(lm, d_sym, d_offs + s0, n, hoffs[s0], d_psi.get(), d_logp.get() + s0, d_qlast.get() + s0,
+                                  d_status.get() + s0, st);
+            HIPCHK(hipGetLastError());
+            e2hmm::launch_backtrack(N, d_offs + s0, n, hoffs[s0], d_psi.get(), d_qlast.get() + s0, d_status.get() + s0,
+                                    d_path.get(), st);
+            HIPCHK(hipGetLastError());
+        }
+        if (hoffs[S] > 0) HIPCHK(hipMemcpyAsync(path, d_path.get(), (size_t)hoffs[S] * 2, hipMemcpyDeviceToHost, st));
+    }
+    if (S > 0) {
+        HIPCHK(hipMemcpyAsync(logp, d_logp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(status, d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// S + 1 offsets that start at 0 and never decrease (the kernels index the symbols with them)
+int check_offsets(const int64_t* offs, int S)
+{
+    if (S < 0 || !offs) return e2vq_set_error("bad sequence count %d or offsets", S);
+    if (offs[0] != 0) return e2vq_set_error("offs[0] = %lld, expected 0", (long long)offs[0]);
+    for (int s = 0; s < S; ++s)
+        if (offs[s + 1] < offs[s]) return e2vq_set_error("offs[%d] = %lld < offs[%d] = %lld", s + 1, (long long)offs[s + 1], s, (long long)offs[s]);
+    return 0;
+}
+
+// values of one sequence as `seq show` prints its symbols: all of them when `full` or L <= 30, else the first 10,
+// ", ..., " and the last 10
+template <typename V>
+void print_abbreviated(const V* v, size_t len, bool full)
+{
+    if (full || len <= 30) {
+        for (size_t t = 0; t < len; ++t) printf("%s%u", t ? ", " : "", (unsigned)v[t]);
+    } else {
+        for (size_t t = 0; t < 10; ++t) printf("%s%u", t ? ", " : "", (unsigned)v[t]);
+        printf(", ..., ");
+        for (size_t t = len - 10; t < len; ++t) printf("%s%u", t > len - 10 ? ", " : "", (unsigned)v[t]);
+    }
+}
 
 typedef void (*hmm_learn_callback_t)(char* variable, double value);
 constexpr int MAX_ESTEPS = 1000;  // safety cap, same in the oracle (val_auto <= 0 with no iteration limit would never stop)
@@ -939,6 +1039,112 @@ extern "C" int ecoz2_hmm_show(const char* hmm_filename, const char* format)
     return 0;
 }
 
+// `seq show [-P] [-Q] --hmm <model>` (the reference's commented `ecoz2_seq_show_files`, src/ecoz2_lib/mod.rs:169-177,
+// with --full and -L of `seq show` on top).  Every file is loaded first; the sequences whose M is the model's then go
+// through one forward scoring call (with_prob) and one Viterbi call (gen_q_opt), and the report follows, file by file.
+extern "C" int e2vq_seq_show_files(int with_prob, int gen_q_opt, int no_sequence, const char* hmm_filename,
+                                   const char* const* sequence_filenames, int num_sequences, int full, int only_length)
+{
+    FlushStdout flush_on_return;
+    if (num_sequences < 0 || (num_sequences > 0 && !sequence_filenames)) return e2vq_set_error("e2vq_seq_show_files: bad arguments");
+    const bool model = with_prob || gen_q_opt;
+    Hmm h;
+    std::vector<double> lflat;
+    if (model) {
+        if (!hmm_filename || !*hmm_filename) return e2vq_set_error("-P / -Q need a model (--hmm)");
+        if (hmm_load(hmm_filename, h)) return 1;
+        if (log_model(h, lflat)) return 1;
+        if (require_device(env_device())) return 1;
+    }
+    struct File {
+        bool ok = false;
+        std::string cls;
+        int M = 0;
+        std::vector<uint16_t> sym;
+        int batch = -1;  // index among the sequences decoded / scored
+    };
+    std::vector<File> fs((size_t)num_sequences);
+    std::vector<uint16_t> sym;
+    std::vector<i64> offs(1, 0);
+    for (int i = 0; i < num_sequences; ++i) {
+        File& f = fs[(size_t)i];
+        char cls[96];
+        int64_t T;
+        if (e2vq_seq_info(sequence_filenames[i], cls, &f.M, &T)) continue;
+        f.sym.resize((size_t)T);
+        if (T > 0 && e2vq_seq_read(sequence_filenames[i], f.sym.data(), T)) continue;
+        f.ok = true;
+        f.cls = cls;
+        if (model && f.M == h.M) {
+            f.batch = (int)offs.size() - 1;
+            sym.insert(sym.end(), f.sym.begin(), f.sym.end());
+            offs.push_back((i64)sym.size());
+        }
+    }
+    const int S = (int)offs.size() - 1;
+    std::vector<double> lp, vlp((size_t)S);
+    std::vector<int> vst((size_t)S);
+    std::vector<uint16_t> path(sym.size());
+    if (model && S > 0) {
+        DeviceBuffer<unsigned short> d_sym;
+        DeviceBuffer<i64> d_offs;
+        Stream st;
+        if (st.create()) return 1;
+        if (d_sym.upload(sym.data(), sym.size(), st.s) || d_offs.upload(offs.data(), offs.size(), st.s)) return 1;
+        if (with_prob && score_device({&h}, d_sym.get(), d_offs.get(), S, st.s, lp)) return 1;
+        if (gen_q_opt && viterbi_device(h.N, h.M, lflat, d_sym.get(), d_offs.get(), offs.data(), S, st.s, path.data(), vlp.data(), vst.data()))
+            return 1;
+    }
+    for (int i = 0; i < num_sequences; ++i) {
+        const File& f = fs[(size_t)i];
+        if (!f.ok) {
+            printf("%s: Not a sequence\n", sequence_filenames[i]);
+            continue;
+        }
+        const size_t len = f.sym.size();
+        if (!no_sequence) {
+            if (only_length) {
+                printf("%zu\n", len);
+            } else {
+                printf("<%s(M=%d,L=%zu): ", f.cls.c_str(), f.M, len);
+                print_abbreviated(f.sym.data(), len, full != 0);
+                printf(">\n");
+            }
+        }
+        if (!model) continue;
+        if (f.batch < 0) {
+            printf("  codebook size M=%d differs from the model's M=%d: no log_prob, no q_opt\n", f.M, h.M);
+            continue;
+        }
+        const size_t b = (size_t)f.batch;
+        if (with_prob) printf("  log_prob = %.17g\n", lp[b]);
+        if (gen_q_opt) {
+            if (vst[b] != 2) {
+                printf("  q_opt = ");
+                print_abbreviated(path.data() + offs[b], len, full != 0);
+                printf("\n");
+            }
+            printf("  q_opt_log_prob = %.17g\n", vlp[b]);
+        }
+        for (size_t t = 0; t < len; ++t)
+            if ((int)f.sym[t] >= h.M) {
+                printf("  note: symbol %u at t = %zu is outside the model's alphabet (M = %d)\n", (unsigned)f.sym[t], t, h.M);
+                break;
+            }
+    }
+    return 0;
+}
+
+// fn ecoz2_seq_show_files(with_prob, gen_q_opt, show_sequence, hmm_filename, sequence_filenames, num_sequences)
+//                                                      src/ecoz2_lib/mod.rs:169-177 (commented out in the reference)
+// The third argument is the reference caller's `no_sequence` (its wrapper, :518-523, passes it there), not the
+// declaration's `show_sequence`: nonzero leaves the symbol line out.
+extern "C" int ecoz2_seq_show_files(int with_prob, int gen_q_opt, int no_sequence, const char* hmm_filename,
+                                    const char* const* sequence_filenames, int num_sequences)
+{
+    return e2vq_seq_show_files(with_prob, gen_q_opt, no_sequence, hmm_filename, sequence_filenames, num_sequences, 0, 0);
+}
+
 // ==========================================================================================
 // array-level entry points (tests, bench, Python mirror): same kernels, no files
 // ==========================================================================================
@@ -1078,4 +1284,22 @@ extern "C" int e2vq_hmm_train(int device, int N, int M, double* pi, double* A, d
     for (size_t i = 0; i < hist.size() && (int)i < cap; ++i) sum_log_prob[i] = hist[i];
     if (num_esteps) *num_esteps = (int)hist.size();
     return 0;
+}
+
+// Viterbi decoding of S host sequences under one model: ln P*, status and (path non-null) Q*
+extern "C" int e2vq_hmm_viterbi(int device, int N, int M, const double* pi, const double* A, const double* B,
+                                const uint16_t* sym, const int64_t* offs, int S, uint16_t* path, double* log_prob,
+                                int* status)
+{
+    Hmm h;
+    std::vector<double> lflat;
+    if (model_from_arrays(N, M, pi, A, B, h) || log_model(h, lflat) || check_offsets(offs, S)) return 1;
+    if (!log_prob || !status) return e2vq_set_error("e2vq_hmm_viterbi: log_prob and status are required");
+    if (require_device(device)) return 1;
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<i64> d_offs;
+    Stream st;
+    if (st.create()) return 1;
+    if (d_sym.upload(sym, (size_t)offs[S], st.s) || d_offs.upload((const i64*)offs, (size_t)S + 1, st.s)) return 1;
+    return viterbi_device(N, M, lflat, d_sym.get(), d_offs.get(), (const i64*)offs, S, st.s, path, log_prob, status);
 }

@@ -37,6 +37,10 @@ _sig("e2vq_hmm_score", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _
 _sig("e2vq_hmm_acc_words", C.c_int64, C.c_int, C.c_int)
 _sig("e2vq_hmm_estep", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("ecoz2_seq_show_files", C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, c_char_pp, C.c_int)
+_sig("e2vq_seq_show_files", C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int)
+_sig("e2vq_hmm_viterbi", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("e2vq_hmm_train", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int))
 
@@ -81,6 +85,13 @@ def hmm_classify_predictors(model_filenames, cb_filenames, prd_filenames, show_r
 def hmm_show(hmm_filename, format="%Lg "):
     """ecoz2_lib::hmm_show (src/ecoz2_lib/mod.rs:481-494)"""
     check(lib.ecoz2_hmm_show(str(hmm_filename).encode(), format.encode()))
+
+
+def seq_show_files(with_prob, gen_q_opt, no_sequence, hmm_filename, seq_filenames):
+    """the reference's commented-out ecoz2_lib::seq_show_files (src/ecoz2_lib/mod.rs:496-528): `seq show -P / -Q`"""
+    files, _k = _strs(seq_filenames)
+    check(lib.ecoz2_seq_show_files(int(bool(with_prob)), int(bool(gen_q_opt)), int(bool(no_sequence)),
+                                   str(hmm_filename).encode() if hmm_filename else b"", files, len(seq_filenames)))
 
 
 # ---- array level ----------------------------------------------------------------------------------------------
@@ -148,3 +159,16 @@ def train(pi, A, B, seqs, epsilon=1e-5, val_auto=0.3, max_iterations=-1, device=
                              S, float(epsilon), float(val_auto), int(max_iterations), hist.ctypes.data, len(hist),
                              C.byref(n)))
     return pi, A, B, list(hist[:n.value])
+
+
+def viterbi(pi, A, B, seqs, device=0, want_path=True):
+    """most likely state sequences: dict(path=[uint16 arrays] or None, log_prob=(S,), status=(S,))"""
+    pi, A, B = (np.ascontiguousarray(x, dtype=np.float64) for x in (pi, A, B))
+    N, M, S = len(pi), B.shape[1], len(seqs)
+    sym, offs = _pack(seqs)
+    lp, st = np.zeros(S), np.zeros(S, dtype=np.int32)
+    path = np.zeros(max(int(offs[-1]), 1), dtype=np.uint16) if want_path else None
+    check(lib.e2vq_hmm_viterbi(device, N, M, pi.ctypes.data, A.ctypes.data, B.ctypes.data, sym.ctypes.data, offs.ctypes.data,
+                               S, path.ctypes.data if want_path else None, lp.ctypes.data, st.ctypes.data))
+    paths = [path[offs[s]:offs[s + 1]].copy() for s in range(S)] if want_path else None
+    return dict(path=paths, log_prob=lp, status=st)

@@ -117,6 +117,22 @@ int ecoz2_hmm_classify_predictors(const char *const *model_filenames, unsigned n
  * format: one printf floating-point conversion per value, default "%Lg " (src/hmm/mod.rs:153-154) */
 int ecoz2_hmm_show(const char *hmm_filename, const char *format);
 
+/* replaces the reference's commented-out `fn ecoz2_seq_show_files(with_prob, gen_q_opt, show_sequence, hmm_filename,
+ *           sequence_filenames, num_sequences)`                         src/ecoz2_lib/mod.rs:169-177
+ * `seq show -P / -Q --hmm`.  The third argument follows the reference's only caller (src/ecoz2_lib/mod.rs:518-523),
+ * which passes `no_sequence` there: nonzero leaves out the symbol line of each file.  Per file, in argument order:
+ * what `seq show` prints for it (unless no_sequence); with_prob: "  log_prob = %.17g", the forward ln P(O | model);
+ * gen_q_opt: "  q_opt = <states>" (abbreviated as the symbol line) and "  q_opt_log_prob = %.17g", ln P* of the
+ * Viterbi path.  A symbol >= M prints -inf, no q_opt line and a note naming the symbol; a file
+ * whose M is not the model's gets one line saying so instead.  All files are loaded first, then decoded (and scored)
+ * in one batched call each. */
+int ecoz2_seq_show_files(int with_prob, int gen_q_opt, int no_sequence, const char *hmm_filename,
+                         const char *const *sequence_filenames, int num_sequences);
+/* the same with the `seq show` flags the reference's signature lacks: full (every symbol and state, `--full`) and
+ * only_length (the length instead of the symbol line, `-L`); ecoz2_seq_show_files is this with both 0 */
+int e2vq_seq_show_files(int with_prob, int gen_q_opt, int no_sequence, const char *hmm_filename,
+                        const char *const *sequence_filenames, int num_sequences, int full, int only_length);
+
 /* ---- array-level entry points over the same kernels (tests, Python mirror) ---------------------------------- */
 /* initial model of `hmm learn -t`: 0 random, 1 uniform, 2 cascade-2, 3 cascade-3 (random B); uses the generator
  * seeded by ecoz2_set_random_seed.  pi[N], A[N*N], B[N*M]; N <= 512. */
@@ -138,6 +154,14 @@ int e2vq_hmm_estep(int device, int N, int M, const double *pi, const double *A, 
 int e2vq_hmm_train(int device, int N, int M, double *pi, double *A, double *B, const uint16_t *sym,
                    const int64_t *offs, int S, double epsilon, double val_auto, int max_iterations,
                    double *sum_log_prob, int cap, int *num_esteps);
+
+/* Viterbi decoding of S sequences under one model: logarithms of the parameters taken on the host
+ * (log 0 = -inf; a negative, NaN or infinite parameter is refused), maximisation on the GPU.  log_prob[s] = ln P*,
+ * status[s]: 0 ok, 1 ln P* = -inf (the model cannot emit the sequence; the path is still written), 2 a symbol >= M
+ * (ln P* = -inf, every path entry 0xFFFF).  path (may be NULL): offs[S] entries, q_t of sequence s at offs[s] + t.
+ * ECOZ2_HMM_VITERBI_CHUNK_BYTES bounds the per-launch back-pointer table (default 256 MiB, whole sequences). */
+int e2vq_hmm_viterbi(int device, int N, int M, const double *pi, const double *A, const double *B, const uint16_t *sym,
+                     const int64_t *offs, int S, uint16_t *path, double *log_prob, int *status);
 
 #ifdef __cplusplus
 }
