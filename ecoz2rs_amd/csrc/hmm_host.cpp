@@ -1207,13 +1207,13 @@ extern "C" int e2vq_hmm_score(int device, int K, const int* Ns, int M, const dou
                               int64_t* exp2, int* status, double* log_probs)
 {
     if (K < 1 || S < 0) return e2vq_set_error("e2vq_hmm_score: bad arguments");
-    if (require_device(device)) return 1;
     std::vector<Hmm> models((size_t)K);
     std::vector<const Hmm*> ms;
     for (int k = 0; k < K; ++k) {
         if (model_from_arrays(Ns[k], M, pis[k], As[k], Bs[k], models[(size_t)k])) return 1;
         ms.push_back(&models[(size_t)k]);
     }
+    if (check_offsets(offs, S) || require_device(device)) return 1;
     DeviceBuffer<unsigned short> d_sym;
     DeviceBuffer<i64> d_offs;
     Stream st;
@@ -1241,9 +1241,8 @@ extern "C" int e2vq_hmm_estep(int device, int N, int M, const double* pi, const 
                               const uint16_t* sym, const int64_t* offs, int S, int64_t* acc, double* mant, int64_t* exp2,
                               int* status)
 {
-    if (require_device(device)) return 1;
     Hmm h;
-    if (model_from_arrays(N, M, pi, A, B, h)) return 1;
+    if (model_from_arrays(N, M, pi, A, B, h) || check_offsets(offs, S) || require_device(device)) return 1;
     DeviceBuffer<unsigned short> d_sym;
     DeviceBuffer<i64> d_offs;
     Trainer tr;
@@ -1267,9 +1266,8 @@ extern "C" int e2vq_hmm_train(int device, int N, int M, double* pi, double* A, d
                               const int64_t* offs, int S, double epsilon, double val_auto, int max_iterations,
                               double* sum_log_prob, int cap, int* num_esteps)
 {
-    if (require_device(device)) return 1;
     Hmm h;
-    if (model_from_arrays(N, M, pi, A, B, h)) return 1;
+    if (model_from_arrays(N, M, pi, A, B, h) || check_offsets(offs, S) || require_device(device)) return 1;
     SeqSet ss;
     ss.M = M;
     ss.sym.assign(sym, sym + offs[S]);
