@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <set>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -43,6 +44,8 @@ static int usage()
             "  ecoz2 {nb|mm} show --model <file>\n"
             "  ecoz2 hmm learn [-N 5] -M <M> [-t 3] [-I -1] [-e 1e-05] [-a 0.3] [-s <seed>] [--ser] [--class-name c]\n"
             "                  --sequences <file.seq|dirs|tt.csv>...\n"
+            "  ecoz2 hmm learn --all-classes [-N 5] -M <M> [-t 3] [-I -1] [-e 1e-05] [-a 0.3] [-s <seed>]\n"
+            "                  --sequences <file.seq|dirs|tt.csv>...   (one model per class, trained together)\n"
             "  ecoz2 hmm classify [-r] [-c|--c12n <out.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST> -M <M> [--class-name c]\n"
             "                  (-s|--sequences <files|dirs|tt.csv>... | --predictors <files|dirs|tt.csv>... --codebooks <files|dirs>...\n"
             "                   [--predictors-dir-template <t>])\n"
@@ -547,7 +550,7 @@ static int hmm_cmd(int argc, char** argv)
     int N = 5, M = -1, type = 3, max_iterations = -1;
     double epsilon = 1e-05, val_auto = 0.3;
     long seed = -1;
-    bool ser = false, ranked = false;
+    bool ser = false, ranked = false, all_classes = false;
     std::string cls, tt, c12n, hmm, format = "%Lg ", tmpl = "data/predictors";
     std::vector<std::string> sequences, models, predictors, codebooks;
     for (int i = 1; i < argc; ++i) {
@@ -565,6 +568,7 @@ static int hmm_cmd(int argc, char** argv)
         else if (a == "-a") val_auto = atof(val("-a"));
         else if (cmd == "learn" && (a == "-s" || a == "--seed")) seed = atol(val("-s"));
         else if (a == "--ser") ser = true;
+        else if (cmd == "learn" && a == "--all-classes") all_classes = true;
         else if (a == "--class-name") cls = val("--class-name");
         else if (a == "-r" || a == "--show-ranked") ranked = true;
         else if (a == "-c" || a == "--c12n") c12n = val("--c12n");
@@ -587,6 +591,33 @@ static int hmm_cmd(int argc, char** argv)
     }
     if (M < 1) return usage();
     const std::string subdir = "sequences/M" + std::to_string(M);
+    if (cmd == "learn" && all_classes) {  // every class of the TRAIN rows / given files at once
+        if (!cls.empty()) {
+            fprintf(stderr, "--all-classes and --class-name exclude each other\n");
+            return usage();
+        }
+        std::vector<std::string> seq_files;
+        int rc = is_csv_list(sequences) ? e2vq_io::files_from_csv(sequences[0], "TRAIN", "", subdir, ".seq", nullptr, seq_files)
+                                        : e2vq_io::resolve_filenames(sequences, ".seq", seq_files);
+        if (rc || seq_files.empty()) { printf("%s\n", rc ? e2vq_last_error() : "No sequences given"); return 0; }
+        std::set<std::string> classes;
+        for (const std::string& f : seq_files) {
+            char c[96];
+            int m;
+            int64_t T;
+            if (e2vq_seq_info(f.c_str(), c, &m, &T)) { printf("%s\n", e2vq_last_error()); return 0; }
+            classes.insert(c);
+        }
+        printf("ECOZ2 C version: %s\n", ecoz2_version());
+        printf("sequences: %zu\n", seq_files.size());
+        printf("classes: %zu\n", classes.size());
+        printf("val_auto = %g\n", val_auto);
+        ecoz2_set_random_seed(seed);
+        auto ps = cptrs(seq_files);
+        if (e2vq_hmm_learn_classes(N, type, ps.data(), (unsigned)ps.size(), epsilon, val_auto, max_iterations, hmm_callback))
+            printf("%s\n", e2vq_last_error());
+        return 0;
+    }
     if (cmd == "learn") {  // main_hmm_learn, src/hmm/mod.rs:172-217
         std::vector<std::string> seq_files;
         int rc = is_csv_list(sequences) ? e2vq_io::files_from_csv(sequences[0], "TRAIN", cls, subdir, ".seq", nullptr, seq_files)

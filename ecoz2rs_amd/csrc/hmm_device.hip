@@ -4,6 +4,8 @@
 //                 added to exact fixed-point accumulators (int64 limb sums: order-free, hence deterministic and
 //                 shardable across GPUs with an integer all-reduce, like the VQ cell sums)
 //   k_hmm_reestimate / k_hmm_adjustb   M-step
+//   k_hmm_fb_classes / k_hmm_reestimate_classes / k_hmm_adjustb_classes   the same E- and M-step over a batch of
+//                 models of one (N, M), each trained on its own sequences (hmm learn --all-classes)
 // Arithmetic: IEEE f64 multiply / fma / add / divide in the order oracle/hmm_oracle.h defines -- the kernels are
 // bit-exact against the oracle.  No transcendental runs on the device: P(O) leaves as (mantissa, exponent) and the
 // host takes the logarithm.
@@ -144,11 +146,13 @@ __device__ __forceinline__ void acc_local(i64 (&cell)[2], double x)
 //               E-step for 600 k symbols at N = 5, all of it same-address contention)
 //   gamma -> AD, BD, PI : per-lane registers over the wave's sequences, one global atomic per lane at the end
 //   gamma -> BN[j][o_t] : global atomics (N x M words: spread out)
-__global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb(ModelDev md, const unsigned short* __restrict__ sym,
-                                                           const i64* __restrict__ offs, int S,
-                                                           double* __restrict__ alpha_buf, double* __restrict__ c_buf,
-                                                           i64* __restrict__ acc, double* __restrict__ mant,
-                                                           i64* __restrict__ exp2, int* __restrict__ status)
+// The body is shared by k_hmm_fb (one model, sequences [0, S), workgroup wg of nwg) and k_hmm_fb_classes (a batch of
+// models, the sequences [s_lo, s_hi) of one of them): one text, so one arithmetic and the same counts, bit for bit.
+__device__ __forceinline__ void fb_wave_body(const ModelDev& md, const unsigned short* __restrict__ sym,
+                                             const i64* __restrict__ offs, int s_lo, int s_hi, int wg, int nwg,
+                                             double* __restrict__ alpha_buf, double* __restrict__ c_buf,
+                                             i64* __restrict__ acc, double* __restrict__ mant, i64* __restrict__ exp2,
+                                             int* __restrict__ status)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int N = md.N, M = md.M;
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb(ModelDev md, const uns
     const double pij = act ? md.pi[lane] : 0.0;
     i64 ad[2] = {0, 0}, bd[2] = {0, 0}, pic[2] = {0, 0};
     int used = 0, skipped = 0;
-    for (int s = blockIdx.x * FB_WAVES + wib; s < S; s += gridDim.x * FB_WAVES) {
+    for (int s = s_lo + wg * FB_WAVES + wib; s < s_hi; s += nwg * FB_WAVES) {
         const i64 base = offs[s];
         const i64 T = offs[s + 1] - base;
         double* alpha = alpha_buf + (size_t)base * N;
@@ -275,6 +279,33 @@ __global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb(ModelDev md, const uns
         const i64 v = ANs[x];
         if (v != 0) atomicAdd((u64*)&AN[x], (u64)v);
     }
+}
+
+__global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb(ModelDev md, const unsigned short* __restrict__ sym,
+                                                           const i64* __restrict__ offs, int S,
+                                                           double* __restrict__ alpha_buf, double* __restrict__ c_buf,
+                                                           i64* __restrict__ acc, double* __restrict__ mant,
+                                                           i64* __restrict__ exp2, int* __restrict__ status)
+{
+    fb_wave_body(md, sym, offs, 0, S, (int)blockIdx.x, (int)gridDim.x, alpha_buf, c_buf, acc, mant, exp2, status);
+}
+
+// Class-batched E-step: K models of one (N <= 64, M), each with its own sequences.  blocks[3 g .. 3 g + 2]
+// = (class k, index of this workgroup among the class's, workgroup count of the class): a workgroup works for one class
+// only -- stages its A, zeroes its own AN table, strides over the class's sequences [cls_s[k], cls_s[k + 1]) and flushes
+// into acc + k W.  offs / mant / exp2 / status are indexed over the whole batch.
+__global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb_classes(const ModelDev* __restrict__ models,
+                                                                   const int* __restrict__ blocks,
+                                                                   const int* __restrict__ cls_s,
+                                                                   const unsigned short* __restrict__ sym,
+                                                                   const i64* __restrict__ offs,
+                                                                   double* __restrict__ alpha_buf, double* __restrict__ c_buf,
+                                                                   i64* __restrict__ acc, i64 W, double* __restrict__ mant,
+                                                                   i64* __restrict__ exp2, int* __restrict__ status)
+{
+    const int k = blocks[3 * blockIdx.x], wg = blocks[3 * blockIdx.x + 1], nwg = blocks[3 * blockIdx.x + 2];
+    const ModelDev md = models[k];
+    fb_wave_body(md, sym, offs, cls_s[k], cls_s[k + 1], wg, nwg, alpha_buf, c_buf, acc + (size_t)k * W, mant, exp2, status);
 }
 
 // ---- more than 64 states: one workgroup per sequence, thread j = state j -------------------------------------------
@@ -485,9 +516,9 @@ __global__ void k_hmm_fb_wg(ModelDev md, const unsigned short* __restrict__ sym,
     }
 }
 
-// M-step: one thread per parameter
-__global__ void k_hmm_reestimate(int N, int M, const i64* __restrict__ acc, double* __restrict__ pi,
-                                 double* __restrict__ A, double* __restrict__ B)
+// M-step: one thread per parameter (x = the parameter's index in pi | A | B)
+__device__ __forceinline__ void reestimate_one(int N, int M, const i64* __restrict__ acc, double* __restrict__ pi,
+                                               double* __restrict__ A, double* __restrict__ B, i64 x)
 {
     const i64* PI = acc;
     const i64* AN = PI + 2 * N;
@@ -495,7 +526,6 @@ __global__ void k_hmm_reestimate(int N, int M, const i64* __restrict__ acc, doub
     const i64* BN = AD + 2 * N;
     const i64* BD = BN + 2 * (i64)N * M;
     const i64 used = BD[2 * N];
-    const i64 x = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (x < N) {
         if (used > 0) pi[x] = e2vq::unfix(PI[2 * x], PI[2 * x + 1], ACC_SHIFT) / (double)used;
     } else if (x < N + (i64)N * N) {
@@ -511,12 +541,15 @@ __global__ void k_hmm_reestimate(int N, int M, const i64* __restrict__ acc, doub
     }
 }
 
-// hmm_adjustb: floor at epsilon, then divide the row by its sequential sum (one thread per state; M <= 65536)
-__global__ void k_hmm_adjustb(int N, int M, double epsilon, double* __restrict__ B)
+__global__ void k_hmm_reestimate(int N, int M, const i64* __restrict__ acc, double* __restrict__ pi,
+                                 double* __restrict__ A, double* __restrict__ B)
 {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    double* row = B + (size_t)j * M;
+    reestimate_one(N, M, acc, pi, A, B, (i64)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// hmm_adjustb: floor at epsilon, then divide the row by its sequential sum (one thread per state; M <= 65536)
+__device__ __forceinline__ void adjustb_row(int M, double epsilon, double* __restrict__ row)
+{
     double s = 0.0;
     for (int k = 0; k < M; ++k) {
         double v = row[k];
@@ -527,6 +560,32 @@ __global__ void k_hmm_adjustb(int N, int M, double epsilon, double* __restrict__
         s = s + v;
     }
     for (int k = 0; k < M; ++k) row[k] = row[k] / s;
+}
+
+__global__ void k_hmm_adjustb(int N, int M, double epsilon, double* __restrict__ B)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    adjustb_row(M, epsilon, B + (size_t)j * M);
+}
+
+// Class-batched M-step: grid.y runs over the list `active` of class indices; class k's counts at acc + k W, its
+// parameters pi | A | B at params + k P (P = N + N^2 + N M)
+__global__ void k_hmm_reestimate_classes(int N, int M, const int* __restrict__ active, const i64* __restrict__ acc, i64 W,
+                                         double* __restrict__ params, i64 P)
+{
+    const int k = active[blockIdx.y];
+    double* pi = params + (size_t)k * P;
+    reestimate_one(N, M, acc + (size_t)k * W, pi, pi + N, pi + N + (size_t)N * N, (i64)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ void k_hmm_adjustb_classes(int N, int M, double epsilon, const int* __restrict__ active, double* __restrict__ params,
+                                      i64 P)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const int k = active[blockIdx.y];
+    adjustb_row(M, epsilon, params + (size_t)k * P + N + (size_t)N * N + (size_t)j * M);
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------
@@ -589,6 +648,39 @@ void launch_reestimate(int N, int M, const i64* acc, double epsilon, double* pi,
     const i64 total = (i64)N + (i64)N * N + (i64)N * M;
     hipLaunchKernelGGL(k_hmm_reestimate, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, N, M, acc, pi, A, B);
     if (epsilon > 0.0) hipLaunchKernelGGL(k_hmm_adjustb, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, N, M, epsilon, B);
+}
+
+int fb_class_workgroups(int S)
+{
+    const int b = (S + FB_WAVES - 1) / FB_WAVES;
+    return b < 1 ? 1 : (b < 2048 ? b : 2048);
+}
+
+void launch_fb_classes(const ModelDev* models, int N, const int* blocks, int nblocks, const int* cls_s,
+                       const unsigned short* sym, const i64* offs, double* alpha_buf, double* c_buf, i64* acc, i64 W,
+                       double* mant, i64* exp2, int* status, hipStream_t st)
+{
+    if (nblocks < 1) return;
+    const size_t lds = (size_t)N * N * (2 * 8 + 16);  // as launch_fb
+    if (hipFuncSetAttribute((const void*)k_hmm_fb_classes, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        fprintf(stderr, "ecoz2vq: the device refuses 160 KB of dynamic LDS for the E-step kernel (N = %d needs %zu bytes)\n", N, lds);
+    hipLaunchKernelGGL(k_hmm_fb_classes, dim3((unsigned)nblocks), dim3(64 * FB_WAVES), lds, st, models, blocks, cls_s, sym, offs,
+                       alpha_buf, c_buf, acc, W, mant, exp2, status);
+}
+
+void launch_reestimate_classes(int N, int M, const int* active, int n_active, const i64* acc, i64 W, double epsilon,
+                               double* params, i64 P, hipStream_t st)
+{
+    const i64 total = (i64)N + (i64)N * N + (i64)N * M;
+    // grid.y carries the classes: at most 65535 per launch, more in further launches
+    for (int k0 = 0; k0 < n_active; k0 += 65535) {
+        const int kn = n_active - k0 < 65535 ? n_active - k0 : 65535;
+        hipLaunchKernelGGL(k_hmm_reestimate_classes, dim3((unsigned)((total + 255) / 256), (unsigned)kn), dim3(256), 0, st, N, M,
+                           active + k0, acc, W, params, P);
+        if (epsilon > 0.0)
+            hipLaunchKernelGGL(k_hmm_adjustb_classes, dim3((unsigned)((N + 63) / 64), (unsigned)kn), dim3(64), 0, st, N, M, epsilon,
+                               active + k0, params, P);
+    }
 }
 
 }  // namespace e2hmm

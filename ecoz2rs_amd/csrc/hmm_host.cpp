@@ -451,6 +451,13 @@ void print_abbreviated(const V* v, size_t len, bool full)
 typedef void (*hmm_learn_callback_t)(char* variable, double value);
 constexpr int MAX_ESTEPS = 1000;  // safety cap, same in the oracle (val_auto <= 0 with no iteration limit would never stop)
 
+// the report line of one E-step of hmm learn
+void print_iteration(int it, double L, i64 skipped)
+{
+    printf("  it=%d  sum log(P) = %.10g%s\n", it, L,
+           skipped ? (" (" + std::to_string(skipped) + " sequence(s) the model cannot emit were skipped)").c_str() : "");
+}
+
 // the training loop of oracle/hmm_oracle.h (e2h_learn): returns the number of E-steps through *n_esteps
 // The same loop with the sequences dealt to `workers` devices (independent sequences; the expected counts
 // are exact int64 limb sums, so their sum over the workers -- taken on the host here: acc_words(N, M) words, 50 KB at
@@ -510,9 +517,7 @@ int train_sharded(Hmm& h, const SeqSet& ss, double epsilon, double val_auto, int
             }
         }
         hist.push_back(L);
-        if (verbose)
-            printf("  it=%d  sum log(P) = %.10g%s\n", it, L,
-                   skipped ? (" (" + std::to_string(skipped) + " sequence(s) the model cannot emit were skipped)").c_str() : "");
+        if (verbose) print_iteration(it, L, skipped);
         if (callback) callback(var, L);
         if (it > 0 && L - Lprev <= val_auto) {
             ++it;
@@ -556,9 +561,7 @@ int train(Hmm& h, const SeqSet& ss, double epsilon, double val_auto, int max_ite
         i64 used, skipped;
         if (tr.estep(d_sym.get(), d_offs.get(), &L, &used, &skipped)) return 1;
         hist.push_back(L);
-        if (verbose)
-            printf("  it=%d  sum log(P) = %.10g%s\n", it, L,
-                   skipped ? (" (" + std::to_string(skipped) + " sequence(s) the model cannot emit were skipped)").c_str() : "");
+        if (verbose) print_iteration(it, L, skipped);
         if (callback) callback(var, L);
         if (it > 0 && L - Lprev <= val_auto) {
             ++it;
@@ -576,6 +579,215 @@ std::string fmt_g(double v)
     char b[64];
     snprintf(b, sizeof b, "%g", v);
     return b;
+}
+
+// data/hmms/N<N>__M<M>_t<type>__a<val_auto>[_I<max_iterations>]/<class>.hmm (CHANGELOG.md:460) and the training measure per
+// iteration beside it as <class>.csv (CHANGELOG.md:288 "generates csv with hmm training measure"); *path: the model's file
+int save_learned(const Hmm& h, int model_type, double val_auto, int max_iterations, const std::vector<double>& hist,
+                 std::string* path)
+{
+    std::string dir = std::string(out_root()) + "/data/hmms/N" + std::to_string(h.N) + "__M" + std::to_string(h.M) + "_t" +
+                      std::to_string(model_type) + "__a" + fmt_g(val_auto);
+    if (max_iterations >= 0) dir += "_I" + std::to_string(max_iterations);
+    *path = dir + "/" + h.class_name + ".hmm";
+    if (hmm_save(*path, h)) return 1;
+    std::string csv = "# class=" + h.class_name + " N=" + std::to_string(h.N) + " M=" + std::to_string(h.M) + "\nI,sum_log_prob\n";
+    for (size_t i = 0; i < hist.size(); ++i) {
+        char b[64];
+        snprintf(b, sizeof b, "%zu,%.17g\n", i, hist[i]);
+        csv += b;
+    }
+    return write_file(dir + "/" + h.class_name + ".csv", std::vector<unsigned char>(csv.begin(), csv.end()));
+}
+
+// ---- every class at once ------------------------------------------------------------------------------
+// One class of a class-batched training: its sequences in list order and its model, trained exactly as `train` trains
+// it alone -- same kernels' arithmetic, same sequential sum of L on the host, same stopping rule.
+struct ClassJob {
+    Hmm h;                          // in: the initial model; out: the trained one
+    const uint16_t* sym = nullptr;  // the class's concatenated symbols (host)
+    std::vector<i64> offs;          // S_k + 1, from 0
+    std::vector<double> hist;       // out: sum ln P per E-step
+    std::vector<i64> skipped;       // out: sequences skipped per E-step
+    int S() const { return (int)offs.size() - 1; }
+    i64 T() const { return offs.back(); }
+};
+
+// device bytes a class takes in a batch: alpha^ and c over its symbols, and its accumulators
+i64 class_batch_bytes(const ClassJob& c) { return (c.T() * ((i64)c.h.N + 1) + e2hmm::acc_words(c.h.N, c.h.M)) * 8; }
+
+// ECOZ2_HMM_LEARN_BATCH_BYTES: the budget of one batch for class_batch_bytes (default 4 GiB)
+i64 learn_batch_bytes()
+{
+    const char* v = getenv("ECOZ2_HMM_LEARN_BATCH_BYTES");
+    const i64 b = v && *v ? atoll(v) : (i64)4 << 30;
+    return std::max<i64>(b, 1);
+}
+
+// K classes of one (N, M) trained together on the current device: per iteration one E-step over every active class's
+// sequences (N <= 64: one k_hmm_fb_classes launch; above: launch_fb once per active class), one copy of the
+// per-sequence P(O) back, the per-class L summed on the host in sequence order, and one batched M-step over the classes
+// that go on.  A class that stops leaves the launches; its parameters on the device are not touched again.
+int train_batch(ClassJob* const* jobs, int K, double epsilon, double val_auto, int max_iterations)
+{
+    const int N = jobs[0]->h.N, M = jobs[0]->h.M;
+    const i64 W = e2hmm::acc_words(N, M), P = (i64)N + (i64)N * N + (i64)N * M;
+    std::vector<i64> offs(1, 0);
+    std::vector<int> cls_s(1, 0);
+    int max_blocks = 0;
+    for (int k = 0; k < K; ++k) {
+        const ClassJob& c = *jobs[k];
+        const i64 base = offs.back();
+        for (int q = 1; q <= c.S(); ++q) offs.push_back(base + c.offs[(size_t)q]);
+        cls_s.push_back(cls_s.back() + c.S());
+        max_blocks += e2hmm::fb_class_workgroups(c.S());
+    }
+    const int S = cls_s.back();
+    const i64 total = offs.back();
+    std::vector<double> flat((size_t)(K * P));
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = jobs[k]->h;
+        double* q = flat.data() + (size_t)k * P;
+        std::copy(h.pi.begin(), h.pi.end(), q);
+        std::copy(h.A.begin(), h.A.end(), q + N);
+        std::copy(h.B.begin(), h.B.end(), q + N + (size_t)N * N);
+    }
+    DeviceBuffer<double> d_params, d_alpha, d_c, d_mant;
+    DeviceBuffer<i64> d_acc, d_exp, d_offs, d_scratch;
+    DeviceBuffer<int> d_status, d_blocks, d_active, d_cls;
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<ModelDev> d_models;
+    Stream st;  // (after the buffers: see Stream)
+    if (st.create()) return 1;
+    if (d_sym.reserve((size_t)total) || d_params.upload(flat.data(), flat.size(), st.s) || d_offs.upload(offs.data(), offs.size(), st.s) ||
+        d_cls.upload(cls_s.data(), cls_s.size(), st.s) || d_alpha.reserve((size_t)(total * N)) || d_c.reserve((size_t)total) ||
+        d_acc.reserve((size_t)(K * W)) || d_mant.reserve((size_t)S) || d_exp.reserve((size_t)S) || d_status.reserve((size_t)S) ||
+        d_blocks.reserve((size_t)max_blocks * 3) || d_active.reserve((size_t)K))
+        return 1;
+    if (e2hmm::fb_scratch_words(N) > 0 && d_scratch.reserve((size_t)e2hmm::fb_scratch_words(N))) return 1;
+    for (int k = 0; k < K; ++k)
+        if (jobs[k]->T() > 0)
+            HIPCHK(hipMemcpyAsync(d_sym.get() + offs[(size_t)cls_s[k]], jobs[k]->sym, (size_t)jobs[k]->T() * 2, hipMemcpyHostToDevice, st.s));
+    std::vector<ModelDev> models;
+    for (int k = 0; k < K; ++k) {
+        const double* q = d_params.get() + (size_t)k * P;
+        models.push_back(ModelDev{N, M, q, q + N, q + N + (size_t)N * N});
+    }
+    if (d_models.upload(models.data(), models.size(), st.s)) return 1;
+    HIPCHK(hipStreamSynchronize(st.s));  // (`flat`, `offs`, `cls_s`, `models` are locals; the copies are done)
+    std::vector<double> mant((size_t)S);
+    std::vector<i64> ex((size_t)S);
+    std::vector<int> stat((size_t)S), blocks, estep_list, mstep_list;
+    std::vector<char> active((size_t)K, 1);
+    std::vector<double> Lprev((size_t)K, 0.0);
+    for (int k = 0; k < K; ++k) {
+        jobs[k]->hist.clear();
+        jobs[k]->skipped.clear();
+    }
+    // (host vectors copied to the device below are rewritten only after the stream synchronisation that follows the copy)
+    for (int it = 0;; ++it) {
+        if ((max_iterations >= 0 && it >= max_iterations) || it >= MAX_ESTEPS) break;
+        estep_list.clear();
+        for (int k = 0; k < K; ++k)
+            if (active[(size_t)k]) estep_list.push_back(k);
+        if (estep_list.empty()) break;
+        HIPCHK(hipMemsetAsync(d_acc.get(), 0, (size_t)(K * W) * 8, st.s));
+        if (N <= e2hmm::WAVE_N) {
+            blocks.clear();
+            for (int k : estep_list) {
+                const int nb = e2hmm::fb_class_workgroups(cls_s[(size_t)k + 1] - cls_s[(size_t)k]);
+                for (int b = 0; b < nb; ++b) blocks.insert(blocks.end(), {k, b, nb});
+            }
+            HIPCHK(hipMemcpyAsync(d_blocks.get(), blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice, st.s));
+            e2hmm::launch_fb_classes(d_models.get(), N, d_blocks.get(), (int)(blocks.size() / 3), d_cls.get(), d_sym.get(), d_offs.get(),
+                                     d_alpha.get(), d_c.get(), d_acc.get(), W, d_mant.get(), d_exp.get(), d_status.get(), st.s);
+            HIPCHK(hipGetLastError());
+        } else {
+            for (int k : estep_list) {
+                const int s0 = cls_s[(size_t)k];
+                e2hmm::launch_fb(models[(size_t)k], d_sym.get(), d_offs.get() + s0, cls_s[(size_t)k + 1] - s0, d_alpha.get(), d_c.get(),
+                                 d_acc.get() + (size_t)k * W, d_mant.get() + s0, d_exp.get() + s0, d_status.get() + s0, st.s, d_scratch.get());
+                HIPCHK(hipGetLastError());
+            }
+        }
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipStreamSynchronize(st.s));
+        mstep_list.clear();
+        for (int k : estep_list) {
+            double L = 0.0;
+            i64 skipped = 0;
+            for (int s = cls_s[(size_t)k]; s < cls_s[(size_t)k + 1]; ++s) {
+                if (stat[(size_t)s] == 0)
+                    L = L + log_prob(mant[(size_t)s], ex[(size_t)s]);
+                else
+                    ++skipped;
+            }
+            jobs[k]->hist.push_back(L);
+            jobs[k]->skipped.push_back(skipped);
+            if (it > 0 && L - Lprev[(size_t)k] <= val_auto) {
+                active[(size_t)k] = 0;
+            } else {
+                mstep_list.push_back(k);
+                Lprev[(size_t)k] = L;
+            }
+        }
+        if (!mstep_list.empty()) {
+            HIPCHK(hipMemcpyAsync(d_active.get(), mstep_list.data(), mstep_list.size() * 4, hipMemcpyHostToDevice, st.s));
+            e2hmm::launch_reestimate_classes(N, M, d_active.get(), (int)mstep_list.size(), d_acc.get(), W, epsilon, d_params.get(), P, st.s);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    HIPCHK(hipMemcpyAsync(flat.data(), d_params.get(), flat.size() * 8, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    for (int k = 0; k < K; ++k) {
+        Hmm& h = jobs[k]->h;
+        const double* q = flat.data() + (size_t)k * P;
+        std::copy(q, q + N, h.pi.begin());
+        std::copy(q + N, q + N + (size_t)N * N, h.A.begin());
+        std::copy(q + N + (size_t)N * N, q + P, h.B.begin());
+    }
+    return 0;
+}
+
+// every job (one N and M for all): dealt to `workers` workers in contiguous ranges balanced by symbol count, worker w on
+// device (dev0 + w) % device count; each worker packs its classes greedily, in order, into batches of at most
+// learn_batch_bytes() (a larger class alone) and trains them one after the other.  Classes are independent, so neither
+// the dealing nor the batching changes a bit of any result.
+int train_classes(std::vector<ClassJob>& jobs, double epsilon, double val_auto, int max_iterations, int workers, int dev0)
+{
+    const int K = (int)jobs.size();
+    workers = std::max(1, std::min(workers, K));
+    const int ndev = device_count();
+    if (!ndev) return 1;
+    std::vector<i64> prefix(1, 0);
+    for (const ClassJob& c : jobs) prefix.push_back(prefix.back() + c.T());
+    std::vector<int> bound((size_t)workers + 1, K);
+    bound[0] = 0;
+    for (int w = 1; w < workers; ++w) {
+        int c = bound[(size_t)w - 1];
+        while (c < K && prefix[(size_t)c] * workers < prefix[(size_t)K] * w) ++c;
+        bound[(size_t)w] = c;
+    }
+    const i64 budget = learn_batch_bytes();
+    return run_workers(workers, [&](int w) -> int {
+        const int lo = bound[(size_t)w], hi = bound[(size_t)w + 1];
+        if (lo >= hi) return 0;
+        if (require_device(worker_device(dev0, w, ndev))) return 1;
+        for (int c0 = lo; c0 < hi;) {
+            std::vector<ClassJob*> batch{&jobs[(size_t)c0]};
+            i64 bytes = class_batch_bytes(jobs[(size_t)c0]);
+            int c1 = c0 + 1;
+            while (c1 < hi && bytes + class_batch_bytes(jobs[(size_t)c1]) <= budget) {
+                bytes += class_batch_bytes(jobs[(size_t)c1]);
+                batch.push_back(&jobs[(size_t)c1++]);
+            }
+            if (train_batch(batch.data(), (int)batch.size(), epsilon, val_auto, max_iterations)) return 1;
+            c0 = c1;
+        }
+        return 0;
+    });
 }
 
 // classification report shared by ecoz2_hmm_classify / ecoz2_hmm_classify_predictors
@@ -670,21 +882,70 @@ extern "C" int ecoz2_hmm_learn(int N, int model_type, const char* const* sequenc
     printf("  epsilon=%g  val_auto=%g  max_iterations=%d\n", hmm_epsilon, val_auto, max_iterations);
     std::vector<double> hist;
     if (train(h, ss, hmm_epsilon, val_auto, max_iterations, callback, hist, getenv("ECOZ2_VQ_QUIET") == nullptr)) return 1;
-    // data/hmms/N<N>__M<M>_t<type>__a<val_auto>[_I<max_iterations>]/<class>.hmm   (CHANGELOG.md:460)
-    std::string dir = std::string(out_root()) + "/data/hmms/N" + std::to_string(N) + "__M" + std::to_string(ss.M) + "_t" +
-                      std::to_string(model_type) + "__a" + fmt_g(val_auto);
-    if (max_iterations >= 0) dir += "_I" + std::to_string(max_iterations);
-    const std::string path = dir + "/" + h.class_name + ".hmm";
-    if (hmm_save(path, h)) return 1;
-    // the training measure per iteration (CHANGELOG.md:288 "generates csv with hmm training measure")
-    std::string csv = "# class=" + h.class_name + " N=" + std::to_string(N) + " M=" + std::to_string(ss.M) + "\nI,sum_log_prob\n";
-    for (size_t i = 0; i < hist.size(); ++i) {
-        char b[64];
-        snprintf(b, sizeof b, "%zu,%.17g\n", i, hist[i]);
-        csv += b;
-    }
-    if (write_file(dir + "/" + h.class_name + ".csv", std::vector<unsigned char>(csv.begin(), csv.end()))) return 1;
+    std::string path;
+    if (save_learned(h, model_type, val_auto, max_iterations, hist, &path)) return 1;
     printf("%zu E-step(s); model saved: %s\n", hist.size(), path.c_str());
+    return 0;
+}
+
+// `hmm learn --all-classes`: one model per class name found in the sequences' headers, classes in byte
+// order of their names, each class's files in list order.  Every class starts from the generator state of entry (a
+// seeded single call's draw) and gets byte for byte what ecoz2_hmm_learn writes and prints for its files alone; all the
+// checks run before any HIP call, and files are written only once every class has trained.
+extern "C" int e2vq_hmm_learn_classes(int N, int model_type, const char* const* sequence_filenames, unsigned num_sequences,
+                                      double hmm_epsilon, double val_auto, int max_iterations, hmm_learn_callback_t callback)
+{
+    FlushStdout flush_on_return;
+    if (!sequence_filenames || num_sequences < 1) return e2vq_set_error("e2vq_hmm_learn_classes: no sequences");
+    if (N < 1 || N > e2hmm::MAX_N) return e2vq_set_error("number of states %d not in [1, %d]", N, e2hmm::MAX_N);
+    if (model_type < 0 || model_type > 3) return e2vq_set_error("model type %d not in 0..3", model_type);
+    SeqSet ss;
+    if (load_sequences(sequence_filenames, num_sequences, ss)) return 1;
+    for (uint16_t v : ss.sym)
+        if ((int)v >= ss.M) return e2vq_set_error("symbol %u outside the codebook size %d", v, ss.M);
+    std::map<std::string, std::vector<int>> by_class;  // (std::string's order is the bytes', as strcmp's)
+    for (int i = 0; i < ss.S(); ++i) by_class[ss.classes[(size_t)i]].push_back(i);
+    // each class's symbols contiguous, in list order
+    std::vector<std::vector<uint16_t>> syms;
+    std::vector<ClassJob> jobs;
+    std::vector<i64> max_T;
+    const uint64_t rng0 = g_rng;
+    for (const auto& kv : by_class) {
+        ClassJob c;
+        std::vector<uint16_t> sy;
+        c.offs.assign(1, 0);
+        i64 mt = 0;
+        for (int i : kv.second) {
+            const i64 a = ss.offs[(size_t)i], b = ss.offs[(size_t)i + 1];
+            sy.insert(sy.end(), ss.sym.begin() + a, ss.sym.begin() + b);
+            c.offs.push_back((i64)sy.size());
+            mt = std::max(mt, b - a);
+        }
+        c.h.class_name = kv.first;
+        c.h.resize(N, ss.M);
+        g_rng = rng0;  // the draw a fresh seeded call would make; after the last class: where that call leaves it
+        if (hmm_init(c.h, model_type)) return 1;
+        syms.push_back(std::move(sy));
+        jobs.push_back(std::move(c));
+        max_T.push_back(mt);
+    }
+    for (size_t k = 0; k < jobs.size(); ++k) jobs[k].sym = syms[k].data();
+    if (train_classes(jobs, hmm_epsilon, val_auto, max_iterations, env_workers(), env_device())) return 1;
+    const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
+    static char var[] = "sum_log_prob";
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        const ClassJob& c = jobs[k];
+        printf("\nHMM learn: class '%s'  N=%d M=%d type=%d  #sequences = %d  max_T=%lld\n", c.h.class_name.c_str(), N, ss.M,
+               model_type, c.S(), (long long)max_T[k]);
+        printf("  epsilon=%g  val_auto=%g  max_iterations=%d\n", hmm_epsilon, val_auto, max_iterations);
+        for (size_t i = 0; i < c.hist.size(); ++i) {
+            if (verbose) print_iteration((int)i, c.hist[i], c.skipped[i]);
+            if (callback) callback(var, c.hist[i]);
+        }
+        std::string path;
+        if (save_learned(c.h, model_type, val_auto, max_iterations, c.hist, &path)) return 1;
+        printf("%zu E-step(s); model saved: %s\n", c.hist.size(), path.c_str());
+    }
     return 0;
 }
 
@@ -1281,6 +1542,45 @@ extern "C" int e2vq_hmm_train(int device, int N, int M, double* pi, double* A, d
     memcpy(B, h.B.data(), h.B.size() * 8);
     for (size_t i = 0; i < hist.size() && (int)i < cap; ++i) sum_log_prob[i] = hist[i];
     if (num_esteps) *num_esteps = (int)hist.size();
+    return 0;
+}
+
+// whole training of K classes on arrays, in place: class k = sequences [class_offs[k], class_offs[k + 1]),
+// model k at pi + k N, A + k N^2, B + k N M; its measure at sum_log_prob + k cap, its E-step count at num_esteps[k].
+// Class k's result is e2vq_hmm_train's on its slice, bit for bit.
+extern "C" int e2vq_hmm_train_classes(int device, int N, int M, int K, double* pi, double* A, double* B, const uint16_t* sym,
+                                      const int64_t* offs, int S, const int64_t* class_offs, double epsilon, double val_auto,
+                                      int max_iterations, double* sum_log_prob, int cap, int* num_esteps)
+{
+    if (K < 1 || !pi || !A || !B || !class_offs || cap < 0 || (cap > 0 && !sum_log_prob))
+        return e2vq_set_error("e2vq_hmm_train_classes: bad arguments (K = %d)", K);
+    if (N < 1 || N > e2hmm::MAX_N || M < 1 || M > 65536) return e2vq_set_error("HMM with N=%d M=%d out of range", N, M);
+    if (check_offsets(offs, S)) return 1;
+    if (class_offs[0] != 0 || class_offs[K] != S)
+        return e2vq_set_error("class_offs must run from 0 to S = %d (got %lld .. %lld)", S, (long long)class_offs[0], (long long)class_offs[K]);
+    for (int k = 0; k < K; ++k)
+        if (class_offs[k + 1] <= class_offs[k])
+            return e2vq_set_error("class_offs not strictly increasing at class %d (%lld, %lld)", k, (long long)class_offs[k],
+                                  (long long)class_offs[k + 1]);
+    const size_t NN = (size_t)N * N, NM = (size_t)N * M;
+    std::vector<ClassJob> jobs((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        ClassJob& c = jobs[(size_t)k];
+        if (model_from_arrays(N, M, pi + (size_t)k * N, A + (size_t)k * NN, B + (size_t)k * NM, c.h)) return 1;
+        const i64 s0 = class_offs[k], s1 = class_offs[k + 1];
+        c.sym = sym + offs[s0];
+        for (i64 s = s0; s <= s1; ++s) c.offs.push_back(offs[s] - offs[s0]);
+    }
+    if (require_device(device)) return 1;
+    if (train_classes(jobs, epsilon, val_auto, max_iterations, 1, device)) return 1;
+    for (int k = 0; k < K; ++k) {
+        const ClassJob& c = jobs[(size_t)k];
+        memcpy(pi + (size_t)k * N, c.h.pi.data(), c.h.pi.size() * 8);
+        memcpy(A + (size_t)k * NN, c.h.A.data(), c.h.A.size() * 8);
+        memcpy(B + (size_t)k * NM, c.h.B.data(), c.h.B.size() * 8);
+        for (size_t i = 0; i < c.hist.size() && (int)i < cap; ++i) sum_log_prob[(size_t)k * cap + i] = c.hist[i];
+        if (num_esteps) num_esteps[k] = (int)c.hist.size();
+    }
     return 0;
 }
 

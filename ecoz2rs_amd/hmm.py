@@ -43,6 +43,10 @@ _sig("e2vq_hmm_viterbi", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_voi
      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("e2vq_hmm_train", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int))
+_sig("e2vq_hmm_learn_classes", C.c_int, C.c_int, C.c_int, c_char_pp, C.c_uint, C.c_double, C.c_double, C.c_int,
+     HMM_LEARN_CALLBACK)
+_sig("e2vq_hmm_train_classes", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p)
 
 
 def _strs(items):
@@ -61,6 +65,15 @@ def hmm_learn(n, model_type, sequence_filenames, hmm_epsilon, val_auto, max_iter
     cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
     check(lib.ecoz2_hmm_learn(int(n), int(model_type), files, len(sequence_filenames), float(hmm_epsilon),
                               float(val_auto), int(max_iterations), int(bool(use_par)), cb))
+
+
+def hmm_learn_classes(n, model_type, sequence_filenames, hmm_epsilon, val_auto, max_iterations, callback=None):
+    """`hmm learn --all-classes`: one model per class of the sequences, all trained together; per class
+    the files and output of hmm_learn on that class's files after the same set_random_seed"""
+    files, _k = _strs(sequence_filenames)
+    cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
+    check(lib.e2vq_hmm_learn_classes(int(n), int(model_type), files, len(sequence_filenames), float(hmm_epsilon),
+                                     float(val_auto), int(max_iterations), cb))
 
 
 def hmm_classify_sequences(model_filenames, sequence_filenames, show_ranked=False, classification_filename=None):
@@ -159,6 +172,28 @@ def train(pi, A, B, seqs, epsilon=1e-5, val_auto=0.3, max_iterations=-1, device=
                              S, float(epsilon), float(val_auto), int(max_iterations), hist.ctypes.data, len(hist),
                              C.byref(n)))
     return pi, A, B, list(hist[:n.value])
+
+
+def train_classes(models, class_seqs, epsilon=1e-5, val_auto=0.3, max_iterations=-1, device=0):
+    """Baum-Welch of K classes in one batched training: models = [(pi, A, B)] sharing N and M,
+    class_seqs = [[uint16 arrays] per class] -> [(pi, A, B, [sum_log_prob per E-step])], each as `train` on its class"""
+    K = len(models)
+    if K != len(class_seqs):
+        raise ValueError(f"{K} models for {len(class_seqs)} classes")
+    N, M = len(models[0][0]), np.asarray(models[0][2]).shape[1]
+    pi = np.ascontiguousarray(np.stack([np.asarray(m[0], dtype=np.float64) for m in models]))
+    A = np.ascontiguousarray(np.stack([np.asarray(m[1], dtype=np.float64) for m in models]))
+    B = np.ascontiguousarray(np.stack([np.asarray(m[2], dtype=np.float64) for m in models]))
+    seqs = [s for cs in class_seqs for s in cs]
+    sym, offs = _pack(seqs)
+    class_offs = np.zeros(len(class_seqs) + 1, dtype=np.int64)
+    class_offs[1:] = np.cumsum([len(cs) for cs in class_seqs])
+    cap = 4096
+    hist, n = np.zeros((K, cap)), np.zeros(K, dtype=np.int32)
+    check(lib.e2vq_hmm_train_classes(device, N, M, K, pi.ctypes.data, A.ctypes.data, B.ctypes.data, sym.ctypes.data,
+                                     offs.ctypes.data, len(seqs), class_offs.ctypes.data, float(epsilon), float(val_auto),
+                                     int(max_iterations), hist.ctypes.data, cap, n.ctypes.data))
+    return [(pi[k].copy(), A[k].copy(), B[k].copy(), list(hist[k, :n[k]])) for k in range(K)]
 
 
 def viterbi(pi, A, B, seqs, device=0, want_path=True):

@@ -155,6 +155,31 @@ int e2vq_hmm_train(int device, int N, int M, double *pi, double *A, double *B, c
                    const int64_t *offs, int S, double epsilon, double val_auto, int max_iterations,
                    double *sum_log_prob, int cap, int *num_esteps);
 
+/* ---- every class's HMM in one batched training -------------------------------------------------
+ * `hmm learn --all-classes`: one model per class name of the sequences' headers, classes in byte order of their names
+ * (strcmp), each class's sequences in list order.  For every class c, ecoz2_set_random_seed(s) followed by this call
+ * writes and prints byte for byte what ecoz2_set_random_seed(s); ecoz2_hmm_learn(N, model_type, <c's files in list
+ * order>, ...) would: every class starts from the generator state of entry, and the generator is left where that single
+ * call leaves it.  (With a seed < 0 all classes therefore share one time-based draw.)  A class stops as the single loop
+ * does; the classes train together -- one E-step launch and one M-step launch per iteration over the classes still
+ * going.  Stdout: the single call's block per class, in class order, after all training; the callback gets the classes'
+ * ("sum_log_prob", L) class after class.  An empty list, N outside [1, 512], a model type outside 0..3, differing M or a
+ * symbol >= M return 1 before any HIP call; no file is written unless every class trained.
+ * ECOZ2_HMM_LEARN_BATCH_BYTES (default 4 GiB): the device bytes one batch of classes may take for alpha^, c and the
+ * accumulators ((T_k (N + 1) + e2vq_hmm_acc_words(N, M)) * 8 per class); classes are packed in order, greedily, a larger
+ * class alone.  ECOZ2_VQ_GPUS = W: whole classes dealt to W workers in contiguous ranges balanced by symbol count.
+ * Neither changes a byte of the output. */
+int e2vq_hmm_learn_classes(int N, int model_type, const char *const *sequence_filenames, unsigned num_sequences,
+                           double hmm_epsilon, double val_auto, int max_iterations,
+                           void (*callback)(char *variable, double value));
+/* the same training on arrays, in place: K classes, class k = sequences [class_offs[k], class_offs[k + 1]) (class_offs:
+ * K + 1 entries, strictly increasing from 0 to S), model k at pi + k N, A + k N^2, B + k N M; its measure per E-step at
+ * sum_log_prob[k cap ..], its E-step count at num_esteps[k].  Class k's result equals e2vq_hmm_train on its slice, bit
+ * for bit.  One device; ECOZ2_HMM_LEARN_BATCH_BYTES applies. */
+int e2vq_hmm_train_classes(int device, int N, int M, int K, double *pi, double *A, double *B, const uint16_t *sym,
+                           const int64_t *offs, int S, const int64_t *class_offs, double epsilon, double val_auto,
+                           int max_iterations, double *sum_log_prob, int cap, int *num_esteps);
+
 /* Viterbi decoding of S sequences under one model: logarithms of the parameters taken on the host
  * (log 0 = -inf; a negative, NaN or infinite parameter is refused), maximisation on the GPU.  log_prob[s] = ln P*,
  * status[s]: 0 ok, 1 ln P* = -inf (the model cannot emit the sequence; the path is still written), 2 a symbol >= M
