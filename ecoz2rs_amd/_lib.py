@@ -58,6 +58,11 @@ _sig("ecoz2_lpc_signals", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float
 _sig("ecoz2_lpca", C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p)
 
 # Part 2: session API
+# Part 2: every class's codebook in one batched training (vq_classes.cpp)
+_sig("e2vq_vq_learn_classes", C.c_int, C.c_int, C.c_double, c_char_pp, C.c_int, C.c_void_p, LEARN_CALLBACK)
+_sig("e2vq_vq_train_classes", C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+     C.POINTER(LevelStatsC), C.c_int, C.c_void_p)
+
 _sig("e2vq_last_error", C.c_char_p)
 _sig("e2vq_device_count", C.c_int)
 _sig("e2vq_session_create", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p))

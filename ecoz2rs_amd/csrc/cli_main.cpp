@@ -31,6 +31,8 @@ static int usage()
             "usage:\n"
             "  ecoz2 vq learn [-B <codebook>] [-P <P>] [-e <eps>] [--class-name <class>] [--exp-key <k>]\n"
             "                 --predictors <files|dirs|tt.csv>...\n"
+            "  ecoz2 vq learn --all-classes -P <P> [-e <eps>] --predictors <files|dirs|tt.csv>...   (one codebook per class,\n"
+            "                 trained together)\n"
             "  ecoz2 vq quantize --codebook <cbook> --predictors <files|dirs|tt.csv>...\n"
             "                 [--predictors-dir-template <t>] [--tt <TRAIN|TEST>] [--class-name <class>] [-s]\n"
             "  ecoz2 vq classify [-r] --codebooks <files|dirs>... --tt <TRAIN|TEST> --predictors <files|dirs|tt.csv>...\n"
@@ -71,13 +73,15 @@ static int vq_learn(int argc, char** argv)
     int P = -1;
     double eps = 0.05;
     std::vector<std::string> predictors;
+    bool all_classes = false;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
             if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
             return argv[++i];
         };
-        if (a == "-B" || a == "--base-codebook") base = val("-B");
+        if (a == "--all-classes") all_classes = true;
+        else if (a == "-B" || a == "--base-codebook") base = val("-B");
         else if (a == "-P" || a == "--prediction-order") P = atoi(val("-P"));
         else if (a == "-e" || a == "--epsilon") eps = atof(val("-e"));
         else if (a == "--class-name") cls = val("--class-name");
@@ -85,6 +89,33 @@ static int vq_learn(int argc, char** argv)
         else if (a == "--predictors") { while (i + 1 < argc && !is_flag(argv[i + 1])) predictors.push_back(argv[++i]); }
         else if (!is_flag(argv[i])) predictors.push_back(a);
         else return usage();
+    }
+    if (all_classes) {  // every class of the TRAIN rows / given files at once
+        if (!cls.empty() || !base.empty()) {
+            fprintf(stderr, "--all-classes excludes --class-name and -B\n");
+            return usage();
+        }
+        if (P < 0) return usage();
+        std::vector<std::string> files;
+        const bool tt_list = predictors.size() == 1 && predictors[0].size() > 4 &&
+                             predictors[0].compare(predictors[0].size() - 4, 4, ".csv") == 0;
+        int rc = tt_list ? e2vq_io::files_from_csv(predictors[0], "TRAIN", "", "predictors", ".prd", nullptr, files)
+                         : e2vq_io::resolve_filenames(predictors, ".prd", files);
+        if (!rc && files.empty()) { printf("No predictors given\n"); return 0; }
+        if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+        std::set<std::string> classes;
+        for (const std::string& f : files) {
+            char c[96];
+            int p;
+            int64_t T;
+            if (e2vq_prd_info(f.c_str(), c, &p, &T)) { printf("%s\n", e2vq_last_error()); return 0; }
+            classes.insert(c);
+        }
+        printf("predictor files: %zu\n", files.size());
+        printf("classes: %zu\n", classes.size());
+        auto ptrs = cptrs(files);
+        if (e2vq_vq_learn_classes(P, eps, ptrs.data(), (int)ptrs.size(), nullptr, callback)) printf("%s\n", e2vq_last_error());
+        return 0;
     }
     if (!base.empty() && P >= 0) {  // src/vq/mod.rs:161-163
         printf("Only one of base codebook or prediction order expected\n");

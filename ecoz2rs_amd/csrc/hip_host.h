@@ -52,6 +52,13 @@ inline int require_device(int device)
 
 // ECOZ2_VQ_DEVICE: the device of a single-device call, the first device of a sharded one
 inline int env_device() { return e2vq_env_int("ECOZ2_VQ_DEVICE", 0); }
+// ECOZ2_VQ_GPUS = N: sequences, predictor files or classes are dealt in contiguous shares to N workers, worker w on device
+// (ECOZ2_VQ_DEVICE + w) % device count -- workers beyond the device count share devices, which is how the 1-GPU tests run
+inline int env_workers()
+{
+    const int n = e2vq_env_int("ECOZ2_VQ_GPUS", 1);
+    return n < 1 ? 1 : (n > 64 ? 64 : n);
+}
 
 // worker w of a sharded call runs on device (dev0 + w) % ndev: workers beyond the device count share devices
 inline int worker_device(int dev0, int w, int ndev) { return (dev0 + w) % ndev; }

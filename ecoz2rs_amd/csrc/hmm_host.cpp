@@ -37,15 +37,6 @@ typedef long long i64;
 
 namespace {
 
-// ECOZ2_VQ_GPUS = N: sequences (or predictor files) are dealt in contiguous shares to N workers, worker w on device
-// (ECOZ2_VQ_DEVICE + w) % device count -- workers beyond the device count share devices, which is how the 1-GPU tests run
-int env_workers()
-{
-    const char* v = getenv("ECOZ2_VQ_GPUS");
-    const int n = v && *v ? atoi(v) : 1;
-    return n < 1 ? 1 : (n > 64 ? 64 : n);
-}
-
 // ---- generator: ecoz2_set_random_seed (oracle: e2h_set_random_seed / splitmix64) ---------------------------
 uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 

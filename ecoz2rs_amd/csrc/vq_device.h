@@ -36,6 +36,21 @@ void launch_global_sums(const double* blk, long nblocks, int NC, int FB, const D
 int launch_pass(int NC, int mode, const double* blk, long T, long nblocks, const double* cbq, const double* cbm,
                 int M, const DevScalars* sc, const unsigned long long* l1max_bits, unsigned short* sym, double* dmin,
                 long long* rows, hipStream_t s);
+// Class-batched plain sweep (vq_classes.cpp): one workgroup per entry, a run of whole 64-frame blocks of one class.
+// first_block: the run's first block in the concatenated image (every class starts on a block); frames: the class's frames
+// from that block on (the body stops at the class's end); blocks: the run's length; cls: the class (its codebook, scalars,
+// L1 maximum and rows at cls times the strides).
+struct PassClassEntry {
+    long first_block;
+    long frames;
+    int blocks;
+    int cls;
+};
+int pass_classes_mode(int NC, int M);  // the accumulate mode of the batched sweep at codebook size M (1, 5 or 2)
+// 0: launched; 1: no MFMA sweep for this order.  cbm / sc / l1max_bits / rows: class k's at k * the stride (sc, l1max: k)
+int launch_pass_classes(int NC, const double* blk, const PassClassEntry* table, int nentries, const double* cbm, long cbm_stride,
+                        int M, const DevScalars* sc, const unsigned long long* l1max_bits, long long* rows, long rows_stride,
+                        hipStream_t s);
 // prediction orders with a prefiltered sweep (NC = P + 1): the usual LPC orders 12, 16, ..., 40
 #ifndef E2VQ_PRE_NC_LIST
 #define E2VQ_PRE_NC_LIST(X) X(13) X(17) X(21) X(25) X(29) X(33) X(37) X(41)
@@ -197,5 +212,22 @@ void launch_init_codebook(const long long* stats, int NC, const DevScalars* sc, 
 void launch_grow(const double* old_refl, int M, int NC, double* new_refl, hipStream_t s, const struct ZeroList* zero = nullptr);
 void launch_codebook_prepare(const double* reflections, int M, int NC, double* cbq, unsigned long long* l1max_bits,
                              double* cbm, hipStream_t s);
+
+// the tail of a class-batched pass (vq_update.hip): grid.y over the `nact` classes listed in `act` (device), class k's
+// arrays at k times the stride; lstats: 8 words per class; the level record: 8 words per listed class, in list order --
+// the six statistics words, the within-cell sum (double bits), the L1 maximum's bits
+constexpr int LEVEL_RECORD_WORDS = 8;
+void launch_zero_rows_classes(long long* rows, long stride, int M, int NC, const int* act, int nact, hipStream_t s);
+void launch_rows_stats_classes(const long long* rows, long rows_stride, int M, int NC, const DevScalars* sc, double* S, long S_stride,
+                               double* within, long within_stride, long long* lstats, const int* act, int nact, hipStream_t s);
+void launch_centroids_classes(const long long* rows, long rows_stride, const double* S, long S_stride, int M, int NC,
+                              const double* refl_in, double* refl_out, long refl_stride, long long* lstats, const int* act, int nact,
+                              hipStream_t s);
+void launch_level_record_classes(long long* lstats, unsigned long long* l1max_bits, const double* within, long within_stride, int M,
+                                 long long* out, const int* act, int nact, hipStream_t s);
+void launch_codebook_prepare_classes(const double* reflections, long refl_stride, int M, int NC, double* cbq, long cbq_stride,
+                                     unsigned long long* l1max_bits, double* cbm, long cbm_stride, double* commit_to, const int* act,
+                                     int nact, hipStream_t s);
+void launch_grow_classes(const double* old_refl, int M, int NC, double* new_refl, long refl_stride, int K, hipStream_t s);
 
 }  // namespace e2vq

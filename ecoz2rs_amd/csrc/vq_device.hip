@@ -214,17 +214,19 @@ __global__ void k_blockify_mfma(const double* __restrict__ aos, long T, int NC, 
 // for data on which the list is LONG (tens of per cent of the frames: distortions that are small differences of large terms
 // certify poorly): the short-list kernel loads every codeword tile for 16 frames and ran at 0.6 of the plain
 // sweep's rate per frame there.
-template <int NC, int MODE, int TPBM, int SRC = 0>
-__global__ __launch_bounds__(TPBM, 2) void k_pass_mfma(const double* __restrict__ blk, long T, long nblocks,
-                                                       const double* __restrict__ cbm, int MT, int M,
-                                                       const DevScalars* __restrict__ sc,
-                                                       const u64* __restrict__ l1max_bits,
-                                                       unsigned short* __restrict__ sym, double* __restrict__ dmin,
-                                                       i64* __restrict__ rows, int stagger,
-                                                       const int* __restrict__ fb_list = nullptr,
-                                                       const int* __restrict__ fb_count = nullptr,
-                                                       unsigned short* __restrict__ prev_sym = nullptr, int incr = 0,
-                                                       int list_rowmajor = 0, unsigned short* cells_out = nullptr)
+// The body is shared by k_pass_mfma (one training set: wg / nwg are the workgroup's index and the grid size) and
+// k_pass_mfma_classes (one entry of a class table per workgroup: the pointers are the entry's class's, wg = 0, nwg = 1).
+template <int NC, int MODE, int TPBM, int SRC>
+__device__ __forceinline__ void pass_mfma_body(const double* __restrict__ blk, long T, long nblocks,
+                                               const double* __restrict__ cbm, int MT, int M,
+                                               const DevScalars* __restrict__ sc,
+                                               const u64* __restrict__ l1max_bits,
+                                               unsigned short* __restrict__ sym, double* __restrict__ dmin,
+                                               i64* __restrict__ rows, int stagger,
+                                               const int* __restrict__ fb_list,
+                                               const int* __restrict__ fb_count,
+                                               unsigned short* __restrict__ prev_sym, int incr,
+                                               int list_rowmajor, unsigned short* cells_out, long wg, long nwg)
 {
     constexpr bool AOS = SRC == 1;
     constexpr bool LIST = SRC == 2 || SRC == 3;
@@ -258,8 +260,8 @@ __global__ __launch_bounds__(TPBM, 2) void k_pass_mfma(const double* __restrict_
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, j = lane & 15;
     const int wib = threadIdx.x >> 6;
-    const long wave = SPLIT > 1 ? (long)blockIdx.x : (long)blockIdx.x * (TPBM >> 6) + wib;
-    const long nwaves = SPLIT > 1 ? (long)gridDim.x : (long)gridDim.x * (TPBM >> 6);
+    const long wave = SPLIT > 1 ? wg : wg * (TPBM >> 6) + wib;
+    const long nwaves = SPLIT > 1 ? nwg : nwg * (TPBM >> 6);
 
     int sh_r = 0, sh_d = 0, sh_d2 = 0;
     if constexpr (MODE != 0) {
@@ -287,7 +289,7 @@ __global__ __launch_bounds__(TPBM, 2) void k_pass_mfma(const double* __restrict_
     // block period turns the bursts into a steady stream; partners differ by half a period.
     if constexpr (MODE != 0 && TPBM == 512) {
         if (nblocks >= 4 * nwaves && stagger && MT >= 16) {
-            int phase = (((int)blockIdx.x + 4 * (wib & 3)) & 7) + 8 * (wib >> 2);  // 0..15 of 16
+            int phase = (((int)wg + 4 * (wib & 3)) & 7) + 8 * (wib >> 2);  // 0..15 of 16
             if (stagger == 2) phase >>= 1;                                            // half amplitude
             if (stagger == 3) phase = 8 * (wib >> 2);                                 // partners only
             const int naps = (phase * (MT * NSM * 4 * 64 / 16)) >> 13;  // s_sleep(127) ~ 8k cycles
@@ -542,6 +544,40 @@ __global__ __launch_bounds__(TPBM, 2) void k_pass_mfma(const double* __restrict_
         atomicAdd(&g_mfma_stamps[9], 1ull);
     }
 #endif
+}
+
+template <int NC, int MODE, int TPBM, int SRC = 0>
+__global__ __launch_bounds__(TPBM, 2) void k_pass_mfma(const double* __restrict__ blk, long T, long nblocks,
+                                                       const double* __restrict__ cbm, int MT, int M,
+                                                       const DevScalars* __restrict__ sc,
+                                                       const u64* __restrict__ l1max_bits,
+                                                       unsigned short* __restrict__ sym, double* __restrict__ dmin,
+                                                       i64* __restrict__ rows, int stagger,
+                                                       const int* __restrict__ fb_list = nullptr,
+                                                       const int* __restrict__ fb_count = nullptr,
+                                                       unsigned short* __restrict__ prev_sym = nullptr, int incr = 0,
+                                                       int list_rowmajor = 0, unsigned short* cells_out = nullptr)
+{
+    pass_mfma_body<NC, MODE, TPBM, SRC>(blk, T, nblocks, cbm, MT, M, sc, l1max_bits, sym, dmin, rows, stagger, fb_list, fb_count,
+                                        prev_sym, incr, list_rowmajor, cells_out, (long)blockIdx.x, (long)gridDim.x);
+}
+
+// The plain accumulating sweep of many training sets at once (vq_classes.cpp): workgroup w takes entry w of
+// the table -- a run of whole 64-frame blocks of one class, never two -- and runs k_pass_mfma's body over it with that
+// class's frames, codebook, scalars and rows.  The class's frames start on a block boundary of the concatenated image;
+// `T` of the entry counts the class's frames from the entry's first block on, so the class's last block is cut where the
+// class ends.  The LDS table of modes 1 and 5 is flushed into the entry's class's rows.
+template <int NC, int MODE, int TPBM>
+__global__ __launch_bounds__(TPBM, 2) void k_pass_mfma_classes(const double* __restrict__ blk, const PassClassEntry* __restrict__ table,
+                                                               const double* __restrict__ cbm, long cbm_stride, int MT, int M,
+                                                               const DevScalars* __restrict__ sc, const u64* __restrict__ l1max_bits,
+                                                               i64* __restrict__ rows, long rows_stride)
+{
+    const PassClassEntry e = table[blockIdx.x];
+    const int k = e.cls;
+    pass_mfma_body<NC, MODE, TPBM, 0>(blk + e.first_block * (long)(NC * 64), e.frames, e.blocks, cbm + k * cbm_stride, MT, M, sc + k,
+                                      l1max_bits + k, nullptr, nullptr, rows + k * rows_stride, 0, nullptr, nullptr, nullptr, 0, 0,
+                                      nullptr, 0, 1);
 }
 
 
@@ -879,6 +915,7 @@ static inline int grid_for(long work_items, int per_block, int cap)
     X(62) X(63) X(64) X(65) X(66) X(67) X(68) X(69) X(70) X(71) X(72) X(73) X(74) X(75) X(76) X(77) X(78) X(79) X(80) X(81)
 #endif
 bool uses_mfma(int NC) { return NC >= 5 && NC <= 81; }
+static constexpr bool mfma_is_wide_nc(int NC) { return NC > 41 && NC <= 81; }
 bool mfma_is_wide(int NC) { return NC > 41 && NC <= 81; }
 int mfma_hybrid_cells(int NC) { return mfma_hyb_cells(NC); }
 
@@ -1001,6 +1038,66 @@ static int launch_pass_mfma_wide(int mode, const double* blk, long T, long nbloc
                            l1max_bits, sym, dmin, rows, 0);
     }
     return 0;
+}
+
+// the class-batched plain sweep: the mode e2vq_pass_mode picks for one training set at this M (the small-M kernel's levels run
+// on mode 1 here), the wide orders in launch_pass_mfma_wide's accumulating shape
+template <int NC>
+static int launch_pass_mfma_classes(const double* blk, const PassClassEntry* table, int nentries, const double* cbm, long cbm_stride,
+                                    int M, const DevScalars* sc, const u64* l1max_bits, i64* rows, long rows_stride, hipStream_t s)
+{
+    constexpr int RS = (2 * NC + 5 + 7) & ~7;
+    constexpr int IMG = 2 * NC + 5 + IMG_STRIDE_PAD;
+    const int MT = (M + 15) / 16;
+    const size_t images = (size_t)8 * 16 * IMG * 4;
+    const int mode = pass_classes_mode(NC, M);
+    if (mode == 1) {
+        if constexpr (!mfma_is_wide_nc(NC)) {
+            (void)hipFuncSetAttribute((const void*)k_pass_mfma_classes<NC, 1, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      E2VQ_LDS_BYTES);
+            hipLaunchKernelGGL((k_pass_mfma_classes<NC, 1, 512>), dim3(nentries), dim3(512), (size_t)M * RS * 8 + images, s, blk, table,
+                               cbm, cbm_stride, MT, M, sc, l1max_bits, rows, rows_stride);
+        }
+    } else if (mode == 5) {
+        if constexpr (!mfma_is_wide_nc(NC)) {
+            (void)hipFuncSetAttribute((const void*)k_pass_mfma_classes<NC, 5, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      E2VQ_LDS_BYTES);
+            hipLaunchKernelGGL((k_pass_mfma_classes<NC, 5, 512>), dim3(nentries), dim3(512),
+                               (size_t)mfma_hyb_cells(NC) * RS * 8 + images, s, blk, table, cbm, cbm_stride, MT, M, sc, l1max_bits,
+                               rows, rows_stride);
+        }
+    } else {
+        (void)hipFuncSetAttribute((const void*)k_pass_mfma_classes<NC, 2, 512>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  E2VQ_LDS_BYTES);
+        hipLaunchKernelGGL((k_pass_mfma_classes<NC, 2, 512>), dim3(nentries), dim3(512), images, s, blk, table, cbm, cbm_stride, MT,
+                           M, sc, l1max_bits, rows, rows_stride);
+    }
+    return 0;
+}
+
+int pass_classes_mode(int NC, int M)
+{
+    if (mfma_is_wide(NC)) return 2;
+    const long RS = row_stride(NC);
+    const long images = 8L * 16 * (2 * NC + 5 + 3) * 4;  // (e2vq_pass_mode's rule)
+    if ((long)M * RS * 8 + images + 2048 <= E2VQ_LDS_BYTES && M <= 128) return 1;
+    if (M <= 4 * mfma_hyb_cells(NC)) return 5;
+    return 2;
+}
+
+int launch_pass_classes(int NC, const double* blk, const PassClassEntry* table, int nentries, const double* cbm, long cbm_stride,
+                        int M, const DevScalars* sc, const u64* l1max_bits, i64* rows, long rows_stride, hipStream_t s)
+{
+    if (nentries < 1) return 0;
+    switch (NC) {
+#define X(N) \
+    case N: return launch_pass_mfma_classes<N>(blk, table, nentries, cbm, cbm_stride, M, sc, l1max_bits, rows, rows_stride, s);
+        E2VQ_MFMA_NC_LIST(X)
+        E2VQ_MFMA_WIDE_NC_LIST(X)
+#undef X
+        default: break;
+    }
+    return 1;  // (orders without an MFMA sweep train through the single-class path)
 }
 
 int launch_pass(int NC, int mode, const double* blk, long T, long nblocks, const double* cbq, const double* cbm,

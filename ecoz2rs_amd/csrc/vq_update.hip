@@ -35,11 +35,11 @@ __device__ __forceinline__ i64 wave_sum_i64(i64 v)
 // per-level statistics from the (all-reduced) rows
 // ------------------------------------------------------------------------------------------
 // lstats (i64): [0] dist_hi [1] dist_lo [2] dist2_hi [3] dist2_lo [4] empty cells [5] failed cells
-__global__ void k_rows_stats(const i64* __restrict__ rows, int M, int NC, const DevScalars* __restrict__ sc,
-                             double* __restrict__ S, double* __restrict__ within, i64* __restrict__ lstats)
+__device__ __forceinline__ void rows_stats_cell(const i64* __restrict__ rows, int M, int NC, const DevScalars* __restrict__ sc,
+                                                double* __restrict__ S, double* __restrict__ within, i64* __restrict__ lstats,
+                                                int m)
 {
     const int RS = (2 * NC + 5 + 7) & ~7;
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
     const i64* row = rows + (long)m * RS;
     const int sh_r = sc->sh_r;
@@ -60,6 +60,12 @@ __global__ void k_rows_stats(const i64* __restrict__ rows, int M, int NC, const 
         ss += s * s;
     }
     within[m] = ss / (double)cnt;
+}
+
+__global__ void k_rows_stats(const i64* __restrict__ rows, int M, int NC, const DevScalars* __restrict__ sc,
+                             double* __restrict__ S, double* __restrict__ within, i64* __restrict__ lstats)
+{
+    rows_stats_cell(rows, M, NC, sc, S, within, lstats, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // Per-thread arrays live in LDS as columns (element i of thread t at [i*64 + t]): dynamic indexing without
@@ -97,15 +103,14 @@ __device__ int lpca_r(int P, Col r, Col rc, Col a)
 
 // K3: cell sums -> reflections.  Non-empty cells whose recursion succeeds get new reflections, every other
 // cell keeps its codeword (refl_out may alias refl_in, or be a shadow buffer for the speculative update).
-__global__ void k_centroids(const i64* __restrict__ rows, const double* __restrict__ S, int M, int NC,
-                            const double* refl_in, double* refl_out, i64* __restrict__ lstats)
+__device__ __forceinline__ void centroid_cell(const i64* __restrict__ rows, const double* __restrict__ S, int M, int NC,
+                                              const double* refl_in, double* refl_out, i64* __restrict__ lstats, int m)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* base = (double*)smem;
     const int W = blockDim.x;
     const Col r{base + threadIdx.x, W}, rc{base + NC * W + threadIdx.x, W}, a{base + 2 * NC * W + threadIdx.x, W};
     const int RS = (2 * NC + 5 + 7) & ~7;
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
     const int P = NC - 1;
     double* dst = refl_out + (long)m * NC;
@@ -124,6 +129,12 @@ __global__ void k_centroids(const i64* __restrict__ rows, const double* __restri
     } else if (dst != src) {
         for (int n = 0; n < NC; ++n) dst[n] = src[n];
     }
+}
+
+__global__ void k_centroids(const i64* __restrict__ rows, const double* __restrict__ S, int M, int NC,
+                            const double* refl_in, double* refl_out, i64* __restrict__ lstats)
+{
+    centroid_cell(rows, S, M, NC, refl_in, refl_out, lstats, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 
@@ -438,12 +449,8 @@ __global__ void k_finish_q(const i64* __restrict__ stats, int NC, DevScalars* __
 // K4a: M -> 2M split, in place from the top (new[2i] = old[i]*0.99, new[2i+1] = old[i]*1.01)
 // (+ up to two small blocks of words zeroed on the way -- the L1 maximum and the limb-image scalars that the kernels behind it
 // accumulate into with atomicMax: a memset each, with its own gap in the queue, otherwise)
-__global__ void k_grow(const double* __restrict__ old_refl, int M, int NC, double* __restrict__ new_refl, ZeroList z)
+__device__ __forceinline__ void grow_element(const double* __restrict__ old_refl, int M, int NC, double* __restrict__ new_refl, int i)
 {
-    if (blockIdx.x == 0)
-        for (int k = 0; k < 3; ++k)
-            for (int j = threadIdx.x; j < z.words[k]; j += blockDim.x) ((unsigned int*)z.p[k])[j] = 0u;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M * NC) return;
     const int m = i / NC, n = i - m * NC;
     const double v = old_refl[i];
@@ -451,12 +458,19 @@ __global__ void k_grow(const double* __restrict__ old_refl, int M, int NC, doubl
     new_refl[(long)(2 * m + 1) * NC + n] = n == 0 ? 0.0 : v * 1.01;
 }
 
+__global__ void k_grow(const double* __restrict__ old_refl, int M, int NC, double* __restrict__ new_refl, ZeroList z)
+{
+    if (blockIdx.x == 0)
+        for (int k = 0; k < 3; ++k)
+            for (int j = threadIdx.x; j < z.words[k]; j += blockDim.x) ((unsigned int*)z.p[k])[j] = 0u;
+    grow_element(old_refl, M, NC, new_refl, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // K4b: reflections -> predictor (step-up) -> raas -> pre-doubled padded codeword rows; L1 max
-__global__ void k_codebook_prepare(const double* __restrict__ reflections, int M, int NC, double* __restrict__ cbq,
-                                   u64* __restrict__ l1max_bits, double* __restrict__ cbm, int MT)
+__device__ __forceinline__ void codebook_prepare_cell(const double* __restrict__ reflections, int M, int NC, double* __restrict__ cbq,
+                                                      u64* __restrict__ l1max_bits, double* __restrict__ cbm, int MT, int m)
 {
     const int NPAD = (NC + 7) & ~7;
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const Col a{(double*)smem + threadIdx.x, (int)blockDim.x};
     const bool real = m < M;
@@ -496,6 +510,12 @@ __global__ void k_codebook_prepare(const double* __restrict__ reflections, int M
         cbm[(long)MT * NP * 128 + (long)(m >> 4) * 16 + (jm & 3) * 4 + (jm >> 2)] = lastc;
     }
     if (real) atomicMax(l1max_bits, (u64)__double_as_longlong(l1));
+}
+
+__global__ void k_codebook_prepare(const double* __restrict__ reflections, int M, int NC, double* __restrict__ cbq,
+                                   u64* __restrict__ l1max_bits, double* __restrict__ cbm, int MT)
+{
+    codebook_prepare_cell(reflections, M, NC, cbq, l1max_bits, cbm, MT, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ---- the first pass after a split, seeded (round 3) -----------------------------------------------------------------------
@@ -709,6 +729,128 @@ void launch_codebook_prepare(const double* reflections, int M, int NC, double* c
     const int tpb = small_tpb(NC);
     hipLaunchKernelGGL(k_codebook_prepare, dim3((n + tpb - 1) / tpb), dim3(tpb), (size_t)NC * tpb * 8, s, reflections, M, NC,
                        cbq, l1max_bits, cbm, MT);
+}
+
+// ---- the tail of a class-batched pass (vq_classes.cpp) ---------------------------------------------------
+// grid.y: the position in the list `act` of the classes the launch serves; class k = act[blockIdx.y] has its arrays at k
+// times the strides (in elements).  Each kernel runs the per-cell (per-element) body of its single-set kernel, so the
+// level statistics and the codebooks are the same arithmetic.
+
+__global__ __launch_bounds__(256) void k_zero_rows_classes(i64* __restrict__ rows, long stride, long words, const int* __restrict__ act)
+{
+    ulonglong2* r2 = (ulonglong2*)(rows + act[blockIdx.y] * stride);  // (stride and words: multiples of 8)
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < words / 2; i += (long)gridDim.x * 256) r2[i] = make_ulonglong2(0ull, 0ull);
+}
+
+__global__ void k_rows_stats_classes(const i64* __restrict__ rows, long rows_stride, int M, int NC, const DevScalars* __restrict__ sc,
+                                     double* __restrict__ S, long S_stride, double* __restrict__ within, long within_stride,
+                                     i64* __restrict__ lstats, const int* __restrict__ act)
+{
+    const int k = act[blockIdx.y];
+    rows_stats_cell(rows + k * rows_stride, M, NC, sc + k, S + k * S_stride, within + k * within_stride, lstats + 8L * k,
+                    blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ void k_centroids_classes(const i64* __restrict__ rows, long rows_stride, const double* __restrict__ S, long S_stride, int M,
+                                    int NC, const double* refl_in, double* refl_out, long refl_stride, i64* __restrict__ lstats,
+                                    const int* __restrict__ act)
+{
+    const int k = act[blockIdx.y];
+    centroid_cell(rows + k * rows_stride, S + k * S_stride, M, NC, refl_in + k * refl_stride, refl_out + k * refl_stride,
+                  lstats + 8L * k, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// One workgroup per class: the class's level record -- the six statistics words, the sum of the within-cell terms in cell
+// order from +0.0 (e2vq_pass_stats' loop on the host), the L1 maximum of the codebook the pass ran on -- then the statistics
+// words and that L1 maximum zeroed for the next pass / the next codebook's preparation.
+__global__ __launch_bounds__(256) void k_level_record_classes(i64* __restrict__ lstats, u64* __restrict__ l1max_bits,
+                                                             const double* __restrict__ within, long within_stride, int M,
+                                                             i64* __restrict__ out, const int* __restrict__ act)
+{
+    constexpr int CH = 4096;
+    __shared__ double w[CH];
+    const int k = act[blockIdx.y];
+    const double* wk = within + k * within_stride;
+    double acc = 0.0;
+    for (int m0 = 0; m0 < M; m0 += CH) {
+        const int n = M - m0 < CH ? M - m0 : CH;
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += 256) w[i] = wk[m0 + i];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < n; ++i) acc += w[i];
+    }
+    if (threadIdx.x == 0) {
+        i64* o = out + (long)LEVEL_RECORD_WORDS * blockIdx.y;
+        for (int i = 0; i < 6; ++i) {
+            o[i] = lstats[8L * k + i];
+            lstats[8L * k + i] = 0;
+        }
+        o[6] = __double_as_longlong(acc);
+        o[7] = (i64)l1max_bits[k];
+        l1max_bits[k] = 0;
+    }
+}
+
+// commit_to (optional): the prepared reflections are also copied there (the update a class keeps)
+__global__ void k_codebook_prepare_classes(const double* __restrict__ reflections, long refl_stride, int M, int NC,
+                                           double* __restrict__ cbq, long cbq_stride, u64* __restrict__ l1max_bits,
+                                           double* __restrict__ cbm, long cbm_stride, int MT, double* __restrict__ commit_to,
+                                           const int* __restrict__ act)
+{
+    const int k = act[blockIdx.y];
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (commit_to && m < M)
+        for (int n = 0; n < NC; ++n) commit_to[k * refl_stride + (long)m * NC + n] = reflections[k * refl_stride + (long)m * NC + n];
+    codebook_prepare_cell(reflections + k * refl_stride, M, NC, cbq + k * cbq_stride, l1max_bits + k, cbm + k * cbm_stride, MT, m);
+}
+
+__global__ void k_grow_classes(const double* __restrict__ old_refl, int M, int NC, double* __restrict__ new_refl, long refl_stride)
+{
+    const long k = blockIdx.y;
+    grow_element(old_refl + k * refl_stride, M, NC, new_refl + k * refl_stride, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+void launch_zero_rows_classes(i64* rows, long stride, int M, int NC, const int* act, int nact, hipStream_t s)
+{
+    const long words = (long)M * row_stride(NC);
+    hipLaunchKernelGGL(k_zero_rows_classes, dim3(grid_for(words / 2, 256, 64), nact), dim3(256), 0, s, rows, stride, words, act);
+}
+
+void launch_rows_stats_classes(const i64* rows, long rows_stride, int M, int NC, const DevScalars* sc, double* S, long S_stride,
+                               double* within, long within_stride, i64* lstats, const int* act, int nact, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_rows_stats_classes, dim3((M + 63) / 64, nact), dim3(64), 0, s, rows, rows_stride, M, NC, sc, S, S_stride,
+                       within, within_stride, lstats, act);
+}
+
+void launch_centroids_classes(const i64* rows, long rows_stride, const double* S, long S_stride, int M, int NC, const double* refl_in,
+                              double* refl_out, long refl_stride, i64* lstats, const int* act, int nact, hipStream_t s)
+{
+    const int tpb = small_tpb(NC);
+    hipLaunchKernelGGL(k_centroids_classes, dim3((M + tpb - 1) / tpb, nact), dim3(tpb), (size_t)3 * NC * tpb * 8, s, rows, rows_stride,
+                       S, S_stride, M, NC, refl_in, refl_out, refl_stride, lstats, act);
+}
+
+void launch_level_record_classes(i64* lstats, u64* l1max_bits, const double* within, long within_stride, int M, i64* out,
+                                 const int* act, int nact, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_level_record_classes, dim3(1, nact), dim3(256), 0, s, lstats, l1max_bits, within, within_stride, M, out, act);
+}
+
+void launch_codebook_prepare_classes(const double* reflections, long refl_stride, int M, int NC, double* cbq, long cbq_stride,
+                                     u64* l1max_bits, double* cbm, long cbm_stride, double* commit_to, const int* act, int nact,
+                                     hipStream_t s)
+{
+    const int MT = (M + 15) / 16;
+    const int tpb = small_tpb(NC);
+    hipLaunchKernelGGL(k_codebook_prepare_classes, dim3((16 * MT + tpb - 1) / tpb, nact), dim3(tpb), (size_t)NC * tpb * 8, s,
+                       reflections, refl_stride, M, NC, cbq, cbq_stride, l1max_bits, cbm, cbm_stride, MT, commit_to, act);
+}
+
+void launch_grow_classes(const double* old_refl, int M, int NC, double* new_refl, long refl_stride, int K, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_grow_classes, dim3((M * NC + 255) / 256, K), dim3(256), 0, s, old_refl, M, NC, new_refl, refl_stride);
 }
 
 }  // namespace e2vq

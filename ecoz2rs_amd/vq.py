@@ -50,6 +50,41 @@ def vq_learn(base_codebook_opt, prediction_order_opt, epsilon, codebook_class_na
     check(rc)
 
 
+def vq_learn_classes(prediction_order, epsilon, predictor_filenames, callback=None):
+    """`vq learn --all-classes`: one codebook per class of the .prd headers, all trained together; per
+    class the files, stdout block and callbacks of ecoz2_vq_learn on that class's files alone.  ``callback(M,
+    avg_distortion, sigma, inertia)`` gets the levels class after class, in class order."""
+    files, _keep = _to_vec_of_ptr_const_c_char(predictor_filenames)
+    cb = LEARN_CALLBACK((lambda _t, m, a, s, i: callback(m, a, s, i)) if callback else (lambda *_a: None))
+    check(lib.e2vq_vq_learn_classes(int(prediction_order), float(epsilon), files, len(predictor_filenames), None, cb))
+
+
+def train_codebooks(frames_per_class, P, eps, max_M, device=0):
+    """Whole LBG ladders of K classes in one batched training: frames_per_class = [T_k x (P+1) float64
+    arrays] -> [(codebook (M x (P+1) reflections), [LevelStats])] per class, bit for bit what
+    ``VqSession(P).set_frames(f); prepare(); init_codebook(); learn(eps, max_M)`` gives for that class.  max_M: a power
+    of two."""
+    K = len(frames_per_class)
+    NC = int(P) + 1
+    arrs = [np.ascontiguousarray(np.asarray(f, dtype=np.float64).reshape(-1, NC)) for f in frames_per_class]
+    offs = np.zeros(K + 1, dtype=np.int64)
+    for k, a in enumerate(arrs):
+        offs[k + 1] = offs[k] + a.shape[0]
+    frames = np.ascontiguousarray(np.concatenate(arrs) if K else np.zeros((0, NC)))
+    max_levels = max(int(max_M).bit_length(), 1)
+    cbs = np.zeros((max(K, 1), max(int(max_M), 1), NC), dtype=np.float64)
+    levels = (LevelStatsC * (max(K, 1) * max_levels))()
+    nlev = np.zeros(max(K, 1), dtype=np.int32)
+    check(lib.e2vq_vq_train_classes(int(device), int(P), K, frames.ctypes.data, offs.ctypes.data, float(eps), int(max_M),
+                                    cbs.ctypes.data, levels, max_levels, nlev.ctypes.data))
+    out = []
+    for k in range(K):
+        lv = [LevelStats.from_c(levels[k * max_levels + i]) for i in range(min(int(nlev[k]), max_levels))]
+        M = lv[-1].M if lv else 1
+        out.append((cbs[k, :M].copy(), lv))
+    return out
+
+
 def vq_quantize(nom_raas, predictor_filenames, show_filenames=False):
     """ecoz2_lib::vq_quantize (src/ecoz2_lib/mod.rs:325-342)."""
     print(f"nom_raas = {nom_raas}")

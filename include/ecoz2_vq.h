@@ -101,7 +101,7 @@ int ecoz2_lpc_signals(int prediction_order, int window_length_ms, int offset_len
 int ecoz2_lpca(double *x, int n, int p, double *r, double *rc, double *a, double *pe);
 
 /* Knobs the reference has no argument for: environment variables, none of which changes a result.  The one table of them
- * (19) is INTEGRATION.md section 2; the ones a caller of these entry points is likely to set:
+ * (21) is INTEGRATION.md section 2; the ones a caller of these entry points is likely to set:
  *   ECOZ2_VQ_MAX_CODEBOOK_SIZE  last codebook size trained (default 2048, notes.md:147)
  *   ECOZ2_VQ_OUT_ROOT           prefix for the data/... outputs (default ".")
  *   ECOZ2_VQ_DEVICE             HIP device ordinal (default 0)
@@ -109,7 +109,8 @@ int ecoz2_lpca(double *x, int n, int p, double *r, double *rc, double *a, double
  *                               vq quantize: deal the files to this many workers (no collective; same .seq files)
  *   ECOZ2_VQ_COLLECTIVE         rccl | p2p: the in-process exchange of ECOZ2_VQ_GPUS > 1 (default: RCCL -- librccl.so is
  *                               loaded with dlopen -- when every rank has a device of its own, else the peer-to-peer kernel)
- *   ECOZ2_VQ_QUIET              no progress lines on stderr                                   */
+ *   ECOZ2_VQ_QUIET              no progress lines on stderr
+ *   ECOZ2_VQ_LEARN_BATCH_BYTES, ECOZ2_VQ_LEARN_CLASSES_SOLO_FRAMES   e2vq_vq_learn_classes (Part 2)              */
 
 /* ========================================================================================
  * Part 2 -- session API (resident training set, one session per GPU / per rank)
@@ -269,6 +270,32 @@ int e2vq_quantize_device(e2vq_session *s, const void *device_frames, int64_t T, 
 int e2vq_synchronize(e2vq_session *s);
 /* average distortion sum_t (dmin_t - 1) / T of frames against the session's codebook (frame order, plain f64 sum) */
 int e2vq_avg_distortion_host(e2vq_session *s, const double *frames, int64_t T, double *avg);
+
+/* ---- every class's codebook in one batched training (vq_classes.cpp) --------------------------------
+ * `vq learn --all-classes`: one codebook per class name found in the .prd headers (e2vq_prd_info), classes in byte order
+ * of their names (strcmp), each class's files in list order (its frame order).  For every class c this writes and prints
+ * byte for byte what ecoz2_vq_learn(P, eps, c, <c's files in list order>, n_c, target, cb) would under the same
+ * ECOZ2_VQ_OUT_ROOT, ECOZ2_VQ_MAX_CODEBOOK_SIZE and ECOZ2_VQ_QUIET: the .cbook of every level and the .rpt, the stdout
+ * block from "Codebook generation:" through the last pass line, and the callbacks -- written and printed class by class
+ * once every class has trained.  Orders with an MFMA sweep (P <= 80) train together: per pass one launch of each kernel
+ * over the classes still active at this level (the plain FP64 sweep and the per-cell tail of the single path, the same
+ * arithmetic), one copy of their statistics back, one synchronisation.  An empty list, an unreadable file, a file of
+ * another order than P, a class without vectors or more than 2^31 - 65 frames in all return 1 before any HIP call.
+ *   ECOZ2_VQ_GPUS = W                   whole classes dealt to W workers in contiguous class ranges balanced by frame
+ *                                       count, worker w on device (ECOZ2_VQ_DEVICE + w) % device count; no collective
+ *   ECOZ2_VQ_LEARN_BATCH_BYTES          device bytes of one batch (frames, rows, codebooks and their images; default
+ *                                       4 GiB): classes packed greedily in class order, a larger class alone
+ *   ECOZ2_VQ_LEARN_CLASSES_SOLO_FRAMES  a class with more frames (default 524288) trains alone through the session path,
+ *                                       where its prefiltered sweeps win; so do all classes of orders above 80
+ * None of them changes a byte of the output. */
+int e2vq_vq_learn_classes(int P, double eps, const char *const *prd_files, int n, void *target, ecoz2_vq_learn_callback_t cb);
+/* the same on arrays: class k = frames [class_offs[k], class_offs[k+1]) of the T x (P+1) row-major `frames`, class_offs
+ * strictly increasing from 0 to T; max_M a power of two.  Out: class k's last codebook at codebooks + k max_M (P+1) (max_M
+ * codewords), its level records at levels + k max_levels (up to max_levels), their number at num_levels[k].  Bit for bit
+ * what a session ladder of the class's frames alone gives (e2vq_set_frames_host, e2vq_prepare, e2vq_init_codebook,
+ * e2vq_learn(eps, max_M)).  Bad arguments return 1 before any HIP call. */
+int e2vq_vq_train_classes(int device, int P, int K, const double *frames, const int64_t *class_offs, double eps, int max_M,
+                          double *codebooks, e2vq_level_stats *levels, int max_levels, int *num_levels);
 
 /* ---- files (.prd / .cbook / .seq) and synthetic data ------------------------------------- */
 int e2vq_prd_info(const char *path, char class_name[96], int *P, int64_t *T);
