@@ -1,7 +1,8 @@
 """`vq learn --all-classes`, CPU side: the argument checks of e2vq_vq_learn_classes /
 e2vq_vq_train_classes run before any HIP call (so they answer the same with or without a device) and write no file; the
 CLI refuses --all-classes with --class-name or -B; the class-batched kernels are in the gfx950 build without scratch or
-spilled registers.  The GPU parity tests are in test_gpu_vq_learn_classes.py."""
+spilled registers, and at every order class of the sweep no worse than the single-set sweep.  The GPU parity tests are in
+test_gpu_vq_learn_classes.py and test_gpu_vq_learn_classes_shapes.py."""
 import os
 import re
 import subprocess
@@ -209,3 +210,40 @@ def test_batched_sweep_keeps_the_single_set_register_budget(asm, nc, mode):
     single = _one(metas, rf"11k_pass_mfmaILi{nc}ELi{mode}ELi512ELi0E")
     assert batched["vgpr"] <= 256 and _waves_per_simd(batched["vgpr"]) == _waves_per_simd(single["vgpr"]) == 2, (batched, single)
     assert batched["vgpr"] <= single["vgpr"] + 8, (batched, single)
+
+
+# every order class of the sweep: NC = 5 (REM 1, the trailing VALU fma), 8 (REM 4), 41 (the last narrow order), 42 and 81 (the
+# first and the last wide order)
+WIDE_FLAGS = [f for f in FLAGS if not f.startswith("-DE2VQ_")] + [
+    "-DE2VQ_PRE_NC_LIST(X)=X(41)", "-DE2VQ_MFMA_NC_LIST(X)=X(5) X(8) X(41)", "-DE2VQ_MFMA_WIDE_NC_LIST(X)=X(42) X(81)"]
+ORDER_CLASSES = [(5, 1), (5, 5), (5, 2), (8, 1), (8, 5), (8, 2), (41, 1), (41, 5), (41, 2), (42, 2), (81, 2)]
+
+
+@pytest.fixture(scope="module")
+def asm_orders(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not installed")
+    path = str(tmp_path_factory.mktemp("isa_orders") / "vq_device.s")
+    subprocess.run([HIPCC, *WIDE_FLAGS, "-o", path, os.path.join(CSRC, "vq_device.hip")], check=True, stdout=subprocess.DEVNULL,
+                   stderr=subprocess.DEVNULL, timeout=900)
+    return _metas(open(path).read())
+
+
+def test_order_classes_are_all_instantiated(asm_orders):
+    got = {tuple(int(x) for x in m.groups()) for n in asm_orders for m in [re.search(r"k_pass_mfma_classesILi(\d+)ELi(\d+)ELi512E", n)]
+           if m}
+    assert got == set(ORDER_CLASSES)
+
+
+@pytest.mark.parametrize("nc,mode", ORDER_CLASSES)
+def test_batched_sweep_is_no_worse_than_the_single_set_sweep(asm_orders, nc, mode):
+    """k_pass_mfma_classes<NC, MODE> against k_pass_mfma<NC, MODE, 512, 0> at every order class: the same occupancy, no more
+    spilled registers, no more scratch.  At NC = 41 mode 1 (P = 40, M <= 128) both spill today -- the largest narrow order
+    fills the 256 registers of two waves per SIMD with four frame tiles of 11 k-steps plus the prefetched next block -- so
+    the batched kernel is held to the single-set kernel's figures there and to none elsewhere."""
+    batched = _one(asm_orders, rf"k_pass_mfma_classesILi{nc}ELi{mode}ELi512E")
+    single = _one(asm_orders, rf"11k_pass_mfmaILi{nc}ELi{mode}ELi512ELi0E")
+    assert batched["vgpr"] <= 256 and _waves_per_simd(batched["vgpr"]) == _waves_per_simd(single["vgpr"]), (batched, single)
+    assert batched["spill"] <= single["spill"] and batched["scratch"] <= single["scratch"], (batched, single)
+    if (nc, mode) != (41, 1):
+        assert batched["scratch"] == 0 and batched["spill"] == 0, batched
