@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <climits>
 #include <set>
 #include <cmath>
 #include <string>
@@ -48,6 +49,8 @@ static int usage()
             "                  --sequences <file.seq|dirs|tt.csv>...\n"
             "  ecoz2 hmm learn --all-classes [-N 5] -M <M> [-t 3] [-I -1] [-e 1e-05] [-a 0.3] [-s <seed>]\n"
             "                  --sequences <file.seq|dirs|tt.csv>...   (one model per class, trained together)\n"
+            "  ecoz2 hmm learn --grid -N <n1,n2,...> -M <m1,m2,...> [-t 3] [-I -1] [-e 1e-05] [-a 0.3] [-s <seed>]\n"
+            "                  --sequences <file.seq|dirs|tt.csv>...   (one model per N, M and class, trained together)\n"
             "  ecoz2 hmm classify [-r] [-c|--c12n <out.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST> -M <M> [--class-name c]\n"
             "                  (-s|--sequences <files|dirs|tt.csv>... | --predictors <files|dirs|tt.csv>... --codebooks <files|dirs>...\n"
             "                   [--predictors-dir-template <t>])\n"
@@ -574,6 +577,89 @@ static int seq_model_cmd(bool nb, int argc, char** argv)
 // `ecoz2 hmm {learn,classify,show}`: option structs and mains of /root/reference/src/hmm/mod.rs:40-291
 static void hmm_callback(char*, double) {}  // the reference's Rust callback is a no-op too (src/hmm/mod.rs:205-207)
 
+// "a,b,c" -> integers; false unless every item is a whole decimal integer
+static bool int_list(const std::string& text, std::vector<int>& out)
+{
+    out.clear();
+    size_t at = 0;
+    for (;;) {
+        const size_t end = std::min(text.find(',', at), text.size());
+        const std::string item = text.substr(at, end - at);
+        char* stop = nullptr;
+        const long v = strtol(item.c_str(), &stop, 10);
+        if (item.empty() || *stop != 0 || v < INT_MIN || v > INT_MAX) return false;
+        out.push_back((int)v);
+        if (end == text.size()) return true;
+        at = end + 1;
+    }
+}
+
+// `hmm learn --grid -N <n1,...> -M <m1,...>`: one model per (N, M, class) in one training.  With a
+// tt.csv each M takes the TRAIN rows under sequences/M<m>; every file's header M must be listed and every listed M must
+// have a file.
+static int hmm_learn_grid(const std::string& n_arg, const std::string& m_arg, const std::string& cls, int type, int max_iterations,
+                          double epsilon, double val_auto, long seed, const std::vector<std::string>& sequences)
+{
+    if (!cls.empty()) {
+        fprintf(stderr, "--grid and --class-name exclude each other\n");
+        return usage();
+    }
+    std::vector<int> ns, ms;
+    if (!int_list(n_arg, ns) || !int_list(m_arg, ms)) {
+        fprintf(stderr, "--grid needs -N <n1,n2,...> and -M <m1,m2,...>: comma-separated integers\n");
+        return usage();
+    }
+    std::sort(ns.begin(), ns.end());
+    std::sort(ms.begin(), ms.end());
+    for (size_t i = 0; i < ms.size(); ++i)
+        if (ms[i] < 1 || (i > 0 && ms[i] == ms[i - 1])) {
+            fprintf(stderr, "-M %d: %s\n", ms[i], ms[i] < 1 ? "not a codebook size" : "given more than once");
+            return usage();
+        }
+    std::vector<std::string> seq_files;
+    int rc = 0;
+    if (is_csv_list(sequences)) {
+        for (int m : ms) {
+            std::vector<std::string> f;
+            rc = e2vq_io::files_from_csv(sequences[0], "TRAIN", "", "sequences/M" + std::to_string(m), ".seq", nullptr, f);
+            if (rc) break;
+            seq_files.insert(seq_files.end(), f.begin(), f.end());
+        }
+    } else {
+        rc = e2vq_io::resolve_filenames(sequences, ".seq", seq_files);
+    }
+    if (rc || seq_files.empty()) { printf("%s\n", rc ? e2vq_last_error() : "No sequences given"); return 0; }
+    std::set<std::string> classes;
+    std::set<int> seen_M;
+    for (const std::string& f : seq_files) {
+        char c[96];
+        int m;
+        int64_t T;
+        if (e2vq_seq_info(f.c_str(), c, &m, &T)) { printf("%s\n", e2vq_last_error()); return 0; }
+        if (!std::binary_search(ms.begin(), ms.end(), m)) { printf("%s: codebook size %d is not in the -M list\n", f.c_str(), m); return 0; }
+        classes.insert(c);
+        seen_M.insert(m);
+    }
+    for (int m : ms)
+        if (!seen_M.count(m)) { printf("no sequence with codebook size %d among the given ones\n", m); return 0; }
+    auto joined = [](const std::vector<int>& v) {
+        std::string s;
+        for (int x : v) s += (s.empty() ? "" : ",") + std::to_string(x);
+        return s;
+    };
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("sequences: %zu\n", seq_files.size());
+    printf("classes: %zu\n", classes.size());
+    printf("grid: N=%s M=%s\n", joined(ns).c_str(), joined(ms).c_str());
+    printf("val_auto = %g\n", val_auto);
+    ecoz2_set_random_seed(seed);
+    auto ps = cptrs(seq_files);
+    if (e2vq_hmm_learn_grid(ns.data(), (int)ns.size(), type, ps.data(), (unsigned)ps.size(), epsilon, val_auto, max_iterations,
+                            hmm_callback))
+        printf("%s\n", e2vq_last_error());
+    return 0;
+}
+
 static int hmm_cmd(int argc, char** argv)
 {
     if (argc < 1) return usage();
@@ -581,8 +667,8 @@ static int hmm_cmd(int argc, char** argv)
     int N = 5, M = -1, type = 3, max_iterations = -1;
     double epsilon = 1e-05, val_auto = 0.3;
     long seed = -1;
-    bool ser = false, ranked = false, all_classes = false;
-    std::string cls, tt, c12n, hmm, format = "%Lg ", tmpl = "data/predictors";
+    bool ser = false, ranked = false, all_classes = false, grid = false;
+    std::string cls, tt, c12n, hmm, format = "%Lg ", tmpl = "data/predictors", n_arg, m_arg;
     std::vector<std::string> sequences, models, predictors, codebooks;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -591,8 +677,8 @@ static int hmm_cmd(int argc, char** argv)
             return argv[++i];
         };
         auto many = [&](std::vector<std::string>& v) { while (i + 1 < argc && !is_flag(argv[i + 1])) v.push_back(argv[++i]); };
-        if (a == "-N" || a == "--num-states") N = atoi(val("-N"));
-        else if (a == "-M" || a == "--codebook-size") M = atoi(val("-M"));
+        if (a == "-N" || a == "--num-states") N = atoi((n_arg = val("-N")).c_str());
+        else if (a == "-M" || a == "--codebook-size") M = atoi((m_arg = val("-M")).c_str());
         else if (a == "-t") type = atoi(val("-t"));
         else if (a == "-I" || a == "--max-iterations") max_iterations = atoi(val("-I"));
         else if (a == "-e") epsilon = atof(val("-e"));
@@ -600,6 +686,7 @@ static int hmm_cmd(int argc, char** argv)
         else if (cmd == "learn" && (a == "-s" || a == "--seed")) seed = atol(val("-s"));
         else if (a == "--ser") ser = true;
         else if (cmd == "learn" && a == "--all-classes") all_classes = true;
+        else if (cmd == "learn" && a == "--grid") grid = true;
         else if (a == "--class-name") cls = val("--class-name");
         else if (a == "-r" || a == "--show-ranked") ranked = true;
         else if (a == "-c" || a == "--c12n") c12n = val("--c12n");
@@ -620,6 +707,8 @@ static int hmm_cmd(int argc, char** argv)
         if (ecoz2_hmm_show(hmm.c_str(), format.c_str())) printf("%s\n", e2vq_last_error());
         return 0;
     }
+    if (cmd == "learn" && grid) return hmm_learn_grid(n_arg.empty() ? "5" : n_arg, m_arg, cls, type, max_iterations, epsilon,
+                                                      val_auto, seed, sequences);
     if (M < 1) return usage();
     const std::string subdir = "sequences/M" + std::to_string(M);
     if (cmd == "learn" && all_classes) {  // every class of the TRAIN rows / given files at once

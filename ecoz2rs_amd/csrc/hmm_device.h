@@ -45,6 +45,26 @@ void launch_fb_classes(const ModelDev* models, int N, const int* blocks, int nbl
 void launch_reestimate_classes(int N, int M, const int* active, int n_active, const long long* acc, long long W,
                                double epsilon, double* params, long long P, hipStream_t st);
 
+// One model of a grid batch: its own (N, M) in md, the sequences [s_lo, s_hi) of the batch's offs
+// (other models may train on the same ones), and where its own slices of the batch's buffers start.
+struct GridModelDev {
+    ModelDev md;
+    int s_lo, s_hi;
+    long long alpha_at;  // alpha^ of sequence s_lo's first symbol at alpha_buf + alpha_at (T_k N_k words in all)
+    long long c_at;      // c at c_buf + c_at (T_k words)
+    long long res_at;    // mant / exp2 / status of sequence s_lo at index res_at (S_k slots)
+    long long acc_at;    // acc_words(N, M) count words at acc + acc_at
+    long long param_at;  // pi | A | B at params + param_at (md's pointers, writable)
+};
+// Grid-batched E-step of the models of ONE N <= WAVE_N (LDS is sized by it): nblocks workgroups, blocks[3 g .. 3 g + 2] =
+// (model, workgroup index within the model, workgroup count of the model; fb_class_workgroups(S_k) of them)
+void launch_fb_grid(const GridModelDev* models, int N, const int* blocks, int nblocks, const unsigned short* sym,
+                    const long long* offs, double* alpha_buf, double* c_buf, long long* acc, double* mant, long long* exp2,
+                    int* status, hipStream_t st);
+// Grid-batched M-step of the n_active models listed in `active`; max_P / max_N: the largest N + N^2 + N M and N among them
+void launch_reestimate_grid(const GridModelDev* models, const int* active, int n_active, long long max_P, int max_N,
+                            const long long* acc, double epsilon, double* params, hipStream_t st);
+
 // Viterbi decoding (hmm_viterbi.hip) of S sequences under one model given as logarithms (lm.pi / lm.A / lm.B hold
 // lpi, lA, lB; -inf where the probability is 0).  Out at [s]: logp = ln P*, status (0 ok, 1 logp = -inf, 2 symbol >= M),
 // and with psi: qlast[s] = q_{T-1} and psi_t[j] (u16) at psi[(offs[s] - psi0 + t) * N + j], t >= 1.  psi null: neither

@@ -6,6 +6,8 @@
 //   k_hmm_reestimate / k_hmm_adjustb   M-step
 //   k_hmm_fb_classes / k_hmm_reestimate_classes / k_hmm_adjustb_classes   the same E- and M-step over a batch of
 //                 models of one (N, M), each trained on its own sequences (hmm learn --all-classes)
+//   k_hmm_fb_grid / k_hmm_reestimate_grid / k_hmm_adjustb_grid   the same over a batch of models of any (N, M), sequences
+//                 shared between them (hmm learn --grid)
 // Arithmetic: IEEE f64 multiply / fma / add / divide in the order oracle/hmm_oracle.h defines -- the kernels are
 // bit-exact against the oracle.  No transcendental runs on the device: P(O) leaves as (mantissa, exponent) and the
 // host takes the logarithm.
@@ -308,6 +310,24 @@ __global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb_classes(const ModelDev
     fb_wave_body(md, sym, offs, cls_s[k], cls_s[k + 1], wg, nwg, alpha_buf, c_buf, acc + (size_t)k * W, mant, exp2, status);
 }
 
+// Grid-batched E-step: models of one N <= 64 (one launch per distinct N), each with its own M,
+// sequences, alpha^ / c / result slices and accumulators.  The body gets pointers rebased for the model, so that its
+// own indexing (alpha^ at offs[s] N, c at offs[s], results at s) lands in the model's slices: the same text as above.
+__global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb_grid(const GridModelDev* __restrict__ models,
+                                                                const int* __restrict__ blocks,
+                                                                const unsigned short* __restrict__ sym,
+                                                                const i64* __restrict__ offs,
+                                                                double* __restrict__ alpha_buf, double* __restrict__ c_buf,
+                                                                i64* __restrict__ acc, double* __restrict__ mant,
+                                                                i64* __restrict__ exp2, int* __restrict__ status)
+{
+    const int k = blocks[3 * blockIdx.x], wg = blocks[3 * blockIdx.x + 1], nwg = blocks[3 * blockIdx.x + 2];
+    const GridModelDev g = models[k];
+    const i64 o = offs[g.s_lo], r = g.res_at - g.s_lo;
+    fb_wave_body(g.md, sym, offs, g.s_lo, g.s_hi, wg, nwg, alpha_buf + (g.alpha_at - o * g.md.N), c_buf + (g.c_at - o),
+                 acc + g.acc_at, mant + r, exp2 + r, status + r);
+}
+
 // ---- more than 64 states: one workgroup per sequence, thread j = state j -------------------------------------------
 // LDS: xs[N] (the values the next sum runs over), ys[N].  grid: (S, models of this launch) for scoring.
 // LDSA (round 4, the E-step kernel k_hmm_fb_wg at N <= WG_LDS_N = 141): the transition matrix is staged in LDS with an odd
@@ -588,6 +608,29 @@ __global__ void k_hmm_adjustb_classes(int N, int M, double epsilon, const int* _
     adjustb_row(M, epsilon, params + (size_t)k * P + N + (size_t)N * N + (size_t)j * M);
 }
 
+// Grid-batched M-step: grid.y runs over the list `active` of model indices, each model with its own (N, M); grid.x
+// covers the largest of them, and the threads beyond a model's own extent return
+__global__ void k_hmm_reestimate_grid(const GridModelDev* __restrict__ models, const int* __restrict__ active,
+                                      const i64* __restrict__ acc, double* __restrict__ params)
+{
+    const GridModelDev& g = models[active[blockIdx.y]];
+    const int N = g.md.N, M = g.md.M;
+    const i64 x = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= (i64)N + (i64)N * N + (i64)N * M) return;
+    double* pi = params + g.param_at;
+    reestimate_one(N, M, acc + g.acc_at, pi, pi + N, pi + N + (size_t)N * N, x);
+}
+
+__global__ void k_hmm_adjustb_grid(const GridModelDev* __restrict__ models, const int* __restrict__ active, double epsilon,
+                                   double* __restrict__ params)
+{
+    const GridModelDev& g = models[active[blockIdx.y]];
+    const int N = g.md.N, M = g.md.M;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    adjustb_row(M, epsilon, params + g.param_at + N + (size_t)N * N + (size_t)j * M);
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------
 i64 acc_words(int N, int M) { return 2 * ((i64)N + (i64)N * N + N + (i64)N * M + N) + 2; }
 
@@ -680,6 +723,32 @@ void launch_reestimate_classes(int N, int M, const int* active, int n_active, co
         if (epsilon > 0.0)
             hipLaunchKernelGGL(k_hmm_adjustb_classes, dim3((unsigned)((N + 63) / 64), (unsigned)kn), dim3(64), 0, st, N, M, epsilon,
                                active + k0, params, P);
+    }
+}
+
+void launch_fb_grid(const GridModelDev* models, int N, const int* blocks, int nblocks, const unsigned short* sym,
+                    const i64* offs, double* alpha_buf, double* c_buf, i64* acc, double* mant, i64* exp2, int* status,
+                    hipStream_t st)
+{
+    if (nblocks < 1) return;
+    const size_t lds = (size_t)N * N * (2 * 8 + 16);  // as launch_fb
+    if (hipFuncSetAttribute((const void*)k_hmm_fb_grid, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        fprintf(stderr, "ecoz2vq: the device refuses 160 KB of dynamic LDS for the E-step kernel (N = %d needs %zu bytes)\n", N, lds);
+    hipLaunchKernelGGL(k_hmm_fb_grid, dim3((unsigned)nblocks), dim3(64 * FB_WAVES), lds, st, models, blocks, sym, offs, alpha_buf,
+                       c_buf, acc, mant, exp2, status);
+}
+
+void launch_reestimate_grid(const GridModelDev* models, const int* active, int n_active, i64 max_P, int max_N, const i64* acc,
+                            double epsilon, double* params, hipStream_t st)
+{
+    // grid.y carries the models: at most 65535 per launch, more in further launches
+    for (int k0 = 0; k0 < n_active; k0 += 65535) {
+        const int kn = n_active - k0 < 65535 ? n_active - k0 : 65535;
+        hipLaunchKernelGGL(k_hmm_reestimate_grid, dim3((unsigned)((max_P + 255) / 256), (unsigned)kn), dim3(256), 0, st, models,
+                           active + k0, acc, params);
+        if (epsilon > 0.0)
+            hipLaunchKernelGGL(k_hmm_adjustb_grid, dim3((unsigned)((max_N + 63) / 64), (unsigned)kn), dim3(64), 0, st, models,
+                               active + k0, epsilon, params);
     }
 }
 

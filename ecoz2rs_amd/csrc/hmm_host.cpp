@@ -156,11 +156,13 @@ struct SeqSet {
     std::vector<std::string> files, classes;
     std::vector<uint16_t> sym;  // concatenated
     std::vector<i64> offs;      // S + 1
-    int M = -1;                 // codebook size (all equal)
+    int M = -1;                 // codebook size (all equal, unless loaded with mixed_M)
+    std::vector<int> Ms;        // each file's codebook size
     int S() const { return (int)files.size(); }
 };
 
-int load_sequences(const char* const* files, unsigned n, SeqSet& ss)
+// mixed_M: files of different codebook sizes are accepted (ss.M is then the first file's)
+int load_sequences(const char* const* files, unsigned n, SeqSet& ss, bool mixed_M = false)
 {
     ss.offs.assign(1, 0);
     for (unsigned i = 0; i < n; ++i) {
@@ -169,12 +171,14 @@ int load_sequences(const char* const* files, unsigned n, SeqSet& ss)
         int64_t T;
         if (e2vq_seq_info(files[i], cls, &M, &T)) return 1;
         if (ss.M < 0) ss.M = M;
-        if (M != ss.M) return e2vq_set_error("%s: codebook size %d differs from the first sequence's %d", files[i], M, ss.M);
+        if (M != ss.M && !mixed_M)
+            return e2vq_set_error("%s: codebook size %d differs from the first sequence's %d", files[i], M, ss.M);
         const size_t at = ss.sym.size();
         ss.sym.resize(at + (size_t)T);
         if (T > 0 && e2vq_seq_read(files[i], ss.sym.data() + at, T)) return 1;
         ss.files.push_back(files[i]);
         ss.classes.push_back(cls);
+        ss.Ms.push_back(M);
         ss.offs.push_back((i64)ss.sym.size());
     }
     return 0;
@@ -781,6 +785,258 @@ int train_classes(std::vector<ClassJob>& jobs, double epsilon, double val_auto, 
     });
 }
 
+// ---- a grid of (N, M) points at once --------------------------------------------------------------------
+// The sequences a grid's models train on: host symbols and S + 1 offsets from 0.  Each model trains on a range of them;
+// the models of different N of one class and M share theirs.
+struct SeqStore {
+    const uint16_t* sym = nullptr;
+    const i64* offs = nullptr;
+};
+
+// One model of a grid, trained exactly as `train` trains it alone on the store's sequences [s_lo, s_hi)
+struct GridJob {
+    Hmm h;                     // in: the initial model; out: the trained one
+    int s_lo = 0, s_hi = 0;    // its sequences (s_lo < s_hi)
+    std::vector<double> hist;  // out: sum ln P per E-step
+    std::vector<i64> skipped;  // out: sequences skipped per E-step
+    int S() const { return s_hi - s_lo; }
+};
+
+i64 grid_T(const GridJob& j, const SeqStore& ss) { return ss.offs[j.s_hi] - ss.offs[j.s_lo]; }
+
+// device bytes a model takes in a grid batch besides its symbols: alpha^ and c over its symbols, and its accumulators
+i64 grid_model_bytes(const GridJob& j, const SeqStore& ss)
+{
+    return (grid_T(j, ss) * ((i64)j.h.N + 1) + e2hmm::acc_words(j.h.N, j.h.M)) * 8;
+}
+
+// K models of any (N, M) trained together on the current device.  The models' sequence ranges are merged into disjoint
+// runs and uploaded once.  Per iteration: one memset of the accumulators, one k_hmm_fb_grid launch per distinct N <= 64
+// and one launch_fb per active model above, one copy of the per-sequence P(O) of every model back, one sync, each model's
+// L summed on the host in sequence order, and one M-step launch pair over the models that go on.  A model that stops
+// leaves the launches; its parameters on the device are not touched again.
+int train_grid_batch(GridJob* const* jobs, int K, const SeqStore& ss, double epsilon, double val_auto, int max_iterations)
+{
+    std::vector<std::pair<int, int>> runs;
+    for (int k = 0; k < K; ++k) runs.emplace_back(jobs[k]->s_lo, jobs[k]->s_hi);
+    std::sort(runs.begin(), runs.end());
+    std::vector<std::pair<int, int>> merged;
+    for (const auto& r : runs) {
+        if (!merged.empty() && r.first <= merged.back().second)
+            merged.back().second = std::max(merged.back().second, r.second);
+        else
+            merged.push_back(r);
+    }
+    std::vector<i64> offs(1, 0);  // the batch's sequences: the runs one after the other
+    std::vector<int> run_at;      // batch index of each run's first sequence
+    for (const auto& r : merged) {
+        run_at.push_back((int)offs.size() - 1);
+        for (int s = r.first; s < r.second; ++s) offs.push_back(offs.back() + (ss.offs[s + 1] - ss.offs[s]));
+    }
+    auto local = [&](int s) {  // batch index of the store's sequence s
+        size_t q = 0;
+        while (q + 1 < merged.size() && merged[q + 1].first <= s) ++q;
+        return run_at[q] + (s - merged[q].first);
+    };
+    std::vector<e2hmm::GridModelDev> g((size_t)K);
+    i64 n_alpha = 0, n_c = 0, n_acc = 0, n_par = 0;
+    int n_res = 0, max_blocks = 0, big_N = 0;
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = jobs[k]->h;
+        e2hmm::GridModelDev& m = g[(size_t)k];
+        m.s_lo = local(jobs[k]->s_lo);
+        m.s_hi = m.s_lo + jobs[k]->S();
+        const i64 T = offs[(size_t)m.s_hi] - offs[(size_t)m.s_lo];
+        m.alpha_at = n_alpha;
+        n_alpha += T * h.N;
+        m.c_at = n_c;
+        n_c += T;
+        m.res_at = n_res;
+        n_res += jobs[k]->S();
+        m.acc_at = n_acc;
+        n_acc += e2hmm::acc_words(h.N, h.M);
+        m.param_at = n_par;
+        n_par += (i64)h.N + (i64)h.N * h.N + (i64)h.N * h.M;
+        if (h.N <= e2hmm::WAVE_N)
+            max_blocks += e2hmm::fb_class_workgroups(jobs[k]->S());
+        else
+            big_N = std::max(big_N, h.N);
+    }
+    std::vector<double> flat((size_t)n_par);
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = jobs[k]->h;
+        double* q = flat.data() + g[(size_t)k].param_at;
+        std::copy(h.pi.begin(), h.pi.end(), q);
+        std::copy(h.A.begin(), h.A.end(), q + h.N);
+        std::copy(h.B.begin(), h.B.end(), q + h.N + (size_t)h.N * h.N);
+    }
+    DeviceBuffer<double> d_params, d_alpha, d_c, d_mant;
+    DeviceBuffer<i64> d_acc, d_exp, d_offs, d_scratch;
+    DeviceBuffer<int> d_status, d_blocks, d_active;
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<e2hmm::GridModelDev> d_models;
+    Stream st;  // (after the buffers: see Stream)
+    if (st.create()) return 1;
+    if (d_sym.reserve((size_t)offs.back()) || d_params.upload(flat.data(), flat.size(), st.s) ||
+        d_offs.upload(offs.data(), offs.size(), st.s) || d_alpha.reserve((size_t)n_alpha) || d_c.reserve((size_t)n_c) ||
+        d_acc.reserve((size_t)n_acc) || d_mant.reserve((size_t)n_res) || d_exp.reserve((size_t)n_res) ||
+        d_status.reserve((size_t)n_res) || d_blocks.reserve((size_t)max_blocks * 3) || d_active.reserve((size_t)K))
+        return 1;
+    if (big_N && d_scratch.reserve((size_t)e2hmm::fb_scratch_words(big_N))) return 1;
+    for (size_t q = 0; q < merged.size(); ++q) {
+        const i64 a = ss.offs[merged[q].first], b = ss.offs[merged[q].second];
+        if (b > a)
+            HIPCHK(hipMemcpyAsync(d_sym.get() + offs[(size_t)run_at[q]], ss.sym + a, (size_t)(b - a) * 2, hipMemcpyHostToDevice, st.s));
+    }
+    for (int k = 0; k < K; ++k) {
+        e2hmm::GridModelDev& m = g[(size_t)k];
+        const double* q = d_params.get() + m.param_at;
+        const int N = jobs[k]->h.N, M = jobs[k]->h.M;
+        m.md = ModelDev{N, M, q, q + N, q + N + (size_t)N * N};
+    }
+    if (d_models.upload(g.data(), g.size(), st.s)) return 1;
+    HIPCHK(hipStreamSynchronize(st.s));  // (`flat`, `offs`, `g` are locals; the copies are done)
+    std::vector<double> mant((size_t)n_res);
+    std::vector<i64> ex((size_t)n_res);
+    std::vector<int> stat((size_t)n_res), blocks, estep_list, mstep_list;
+    std::map<int, std::vector<int>> by_N;  // the active models of each N <= 64
+    std::vector<char> active((size_t)K, 1);
+    std::vector<double> Lprev((size_t)K, 0.0);
+    for (int k = 0; k < K; ++k) {
+        jobs[k]->hist.clear();
+        jobs[k]->skipped.clear();
+    }
+    // (host vectors copied to the device below are rewritten only after the stream synchronisation that follows the copy)
+    for (int it = 0;; ++it) {
+        if ((max_iterations >= 0 && it >= max_iterations) || it >= MAX_ESTEPS) break;
+        estep_list.clear();
+        for (int k = 0; k < K; ++k)
+            if (active[(size_t)k]) estep_list.push_back(k);
+        if (estep_list.empty()) break;
+        HIPCHK(hipMemsetAsync(d_acc.get(), 0, (size_t)n_acc * 8, st.s));
+        by_N.clear();
+        for (int k : estep_list)
+            if (g[(size_t)k].md.N <= e2hmm::WAVE_N) by_N[g[(size_t)k].md.N].push_back(k);
+        if (!by_N.empty()) {
+            blocks.clear();
+            for (const auto& kv : by_N)
+                for (int k : kv.second) {
+                    const int nb = e2hmm::fb_class_workgroups(jobs[k]->S());
+                    for (int b = 0; b < nb; ++b) blocks.insert(blocks.end(), {k, b, nb});
+                }
+            HIPCHK(hipMemcpyAsync(d_blocks.get(), blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice, st.s));
+            int at = 0;  // one launch per N: each sized by its own LDS (4 N^2 words a workgroup)
+            for (const auto& kv : by_N) {
+                int nb = 0;
+                for (int k : kv.second) nb += e2hmm::fb_class_workgroups(jobs[k]->S());
+                e2hmm::launch_fb_grid(d_models.get(), kv.first, d_blocks.get() + 3 * at, nb, d_sym.get(), d_offs.get(), d_alpha.get(),
+                                      d_c.get(), d_acc.get(), d_mant.get(), d_exp.get(), d_status.get(), st.s);
+                HIPCHK(hipGetLastError());
+                at += nb;
+            }
+        }
+        for (int k : estep_list) {
+            const e2hmm::GridModelDev& m = g[(size_t)k];
+            if (m.md.N <= e2hmm::WAVE_N) continue;
+            const i64 o = offs[(size_t)m.s_lo];
+            e2hmm::launch_fb(m.md, d_sym.get(), d_offs.get() + m.s_lo, jobs[k]->S(), d_alpha.get() + (m.alpha_at - o * m.md.N),
+                             d_c.get() + (m.c_at - o), d_acc.get() + m.acc_at, d_mant.get() + m.res_at, d_exp.get() + m.res_at,
+                             d_status.get() + m.res_at, st.s, d_scratch.get());
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), (size_t)n_res * 8, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), (size_t)n_res * 8, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_status.get(), (size_t)n_res * 4, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipStreamSynchronize(st.s));
+        mstep_list.clear();
+        i64 max_P = 0;
+        int max_N = 0;
+        for (int k : estep_list) {
+            const e2hmm::GridModelDev& m = g[(size_t)k];
+            double L = 0.0;
+            i64 skipped = 0;
+            for (i64 r = m.res_at; r < m.res_at + jobs[k]->S(); ++r) {
+                if (stat[(size_t)r] == 0)
+                    L = L + log_prob(mant[(size_t)r], ex[(size_t)r]);
+                else
+                    ++skipped;
+            }
+            jobs[k]->hist.push_back(L);
+            jobs[k]->skipped.push_back(skipped);
+            if (it > 0 && L - Lprev[(size_t)k] <= val_auto) {
+                active[(size_t)k] = 0;
+            } else {
+                mstep_list.push_back(k);
+                Lprev[(size_t)k] = L;
+                max_P = std::max(max_P, (i64)m.md.N + (i64)m.md.N * m.md.N + (i64)m.md.N * m.md.M);
+                max_N = std::max(max_N, m.md.N);
+            }
+        }
+        if (!mstep_list.empty()) {
+            HIPCHK(hipMemcpyAsync(d_active.get(), mstep_list.data(), mstep_list.size() * 4, hipMemcpyHostToDevice, st.s));
+            e2hmm::launch_reestimate_grid(d_models.get(), d_active.get(), (int)mstep_list.size(), max_P, max_N, d_acc.get(), epsilon,
+                                          d_params.get(), st.s);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    HIPCHK(hipMemcpyAsync(flat.data(), d_params.get(), flat.size() * 8, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    for (int k = 0; k < K; ++k) {
+        Hmm& h = jobs[k]->h;
+        const double* q = flat.data() + g[(size_t)k].param_at;
+        std::copy(q, q + h.N, h.pi.begin());
+        std::copy(q + h.N, q + h.N + (size_t)h.N * h.N, h.A.begin());
+        std::copy(q + h.N + (size_t)h.N * h.N, q + h.N + (size_t)h.N * h.N + (size_t)h.N * h.M, h.B.begin());
+    }
+    return 0;
+}
+
+// every model of a grid: dealt to `workers` workers in contiguous ranges of the grid order balanced by grid_model_bytes,
+// worker w on device (dev0 + w) % device count; each worker packs its models greedily, in order, into batches of at most
+// learn_batch_bytes() (a larger model alone), counting a sequence range's symbols once per batch, and trains them one
+// batch after the other.  Models are independent, so neither the dealing nor the batching changes a bit of any result.
+int train_grid(std::vector<GridJob>& jobs, const SeqStore& ss, double epsilon, double val_auto, int max_iterations, int workers,
+               int dev0)
+{
+    const int K = (int)jobs.size();
+    workers = std::max(1, std::min(workers, K));
+    const int ndev = device_count();
+    if (!ndev) return 1;
+    std::vector<i64> prefix(1, 0);
+    for (const GridJob& j : jobs) prefix.push_back(prefix.back() + grid_model_bytes(j, ss));
+    std::vector<int> bound((size_t)workers + 1, K);
+    bound[0] = 0;
+    for (int w = 1; w < workers; ++w) {
+        int c = bound[(size_t)w - 1];
+        while (c < K && prefix[(size_t)c] * workers < prefix[(size_t)K] * w) ++c;
+        bound[(size_t)w] = c;
+    }
+    const i64 budget = learn_batch_bytes();
+    return run_workers(workers, [&](int w) -> int {
+        const int lo = bound[(size_t)w], hi = bound[(size_t)w + 1];
+        if (lo >= hi) return 0;
+        if (require_device(worker_device(dev0, w, ndev))) return 1;
+        for (int c0 = lo; c0 < hi;) {
+            std::vector<GridJob*> batch;
+            std::vector<std::pair<int, int>> ranges;  // (the sequence ranges whose symbols the batch already counts)
+            i64 bytes = 0;
+            int c1 = c0;
+            while (c1 < hi) {
+                const GridJob& j = jobs[(size_t)c1];
+                const bool seen = std::find(ranges.begin(), ranges.end(), std::make_pair(j.s_lo, j.s_hi)) != ranges.end();
+                const i64 more = grid_model_bytes(j, ss) + (seen ? 0 : grid_T(j, ss) * 2);
+                if (c1 > c0 && bytes + more > budget) break;
+                bytes += more;
+                if (!seen) ranges.emplace_back(j.s_lo, j.s_hi);
+                batch.push_back(&jobs[(size_t)c1++]);
+            }
+            if (train_grid_batch(batch.data(), (int)batch.size(), ss, epsilon, val_auto, max_iterations)) return 1;
+            c0 = c1;
+        }
+        return 0;
+    });
+}
+
 // classification report shared by ecoz2_hmm_classify / ecoz2_hmm_classify_predictors
 int classify_report(const std::vector<Hmm>& models, const std::vector<std::string>& case_files,
                     const std::vector<std::string>& case_classes, const std::vector<double>& log_probs, int M,
@@ -936,6 +1192,94 @@ extern "C" int e2vq_hmm_learn_classes(int N, int model_type, const char* const* 
         std::string path;
         if (save_learned(c.h, model_type, val_auto, max_iterations, c.hist, &path)) return 1;
         printf("%zu E-step(s); model saved: %s\n", c.hist.size(), path.c_str());
+    }
+    return 0;
+}
+
+// `hmm learn --grid`: one model per grid point (N, M, class) -- the N given, ascending; the M of the
+// sequences' headers, ascending; the classes present at that M in byte order of their names -- each trained on the files
+// of its class and M in list order, all models in one batched training.  Every model starts from the generator state of
+// entry and gets byte for byte what e2vq_hmm_learn_classes(N, ...) of the files of that M writes and prints for its class;
+// the generator is left where a seeded single call for the last model leaves it.  All the checks run before any HIP call,
+// and files are written only once every model has trained.
+extern "C" int e2vq_hmm_learn_grid(const int* Ns, int num_N, int model_type, const char* const* sequence_filenames,
+                                   unsigned num_sequences, double hmm_epsilon, double val_auto, int max_iterations,
+                                   hmm_learn_callback_t callback)
+{
+    FlushStdout flush_on_return;
+    if (!sequence_filenames || num_sequences < 1) return e2vq_set_error("e2vq_hmm_learn_grid: no sequences");
+    if (!Ns || num_N < 1) return e2vq_set_error("e2vq_hmm_learn_grid: no number of states given");
+    std::vector<int> n_list(Ns, Ns + num_N);
+    std::sort(n_list.begin(), n_list.end());
+    for (size_t i = 0; i < n_list.size(); ++i) {
+        if (n_list[i] < 1 || n_list[i] > e2hmm::MAX_N) return e2vq_set_error("number of states %d not in [1, %d]", n_list[i], e2hmm::MAX_N);
+        if (i > 0 && n_list[i] == n_list[i - 1]) return e2vq_set_error("number of states %d given more than once", n_list[i]);
+    }
+    if (model_type < 0 || model_type > 3) return e2vq_set_error("model type %d not in 0..3", model_type);
+    SeqSet ss;
+    if (load_sequences(sequence_filenames, num_sequences, ss, /*mixed_M=*/true)) return 1;
+    for (int i = 0; i < ss.S(); ++i)
+        for (i64 t = ss.offs[(size_t)i]; t < ss.offs[(size_t)i + 1]; ++t)
+            if ((int)ss.sym[(size_t)t] >= ss.Ms[(size_t)i])
+                return e2vq_set_error("%s: symbol %u outside the codebook size %d", ss.files[(size_t)i].c_str(), ss.sym[(size_t)t],
+                                      ss.Ms[(size_t)i]);
+    // (std::map: M ascending; std::string's order is the bytes', as strcmp's)
+    std::map<int, std::map<std::string, std::vector<int>>> by_M;
+    for (int i = 0; i < ss.S(); ++i) by_M[ss.Ms[(size_t)i]][ss.classes[(size_t)i]].push_back(i);
+    // the store: each (M, class)'s symbols contiguous, in list order, groups in grid order
+    struct Group {
+        std::string name;
+        int M, s_lo, s_hi;
+        i64 max_T;
+    };
+    std::vector<uint16_t> sym;
+    std::vector<i64> offs(1, 0);
+    std::vector<Group> groups;
+    for (const auto& mv : by_M)
+        for (const auto& kv : mv.second) {
+            Group gr{kv.first, mv.first, (int)offs.size() - 1, 0, 0};
+            for (int i : kv.second) {
+                const i64 a = ss.offs[(size_t)i], b = ss.offs[(size_t)i + 1];
+                sym.insert(sym.end(), ss.sym.begin() + a, ss.sym.begin() + b);
+                offs.push_back((i64)sym.size());
+                gr.max_T = std::max(gr.max_T, b - a);
+            }
+            gr.s_hi = (int)offs.size() - 1;
+            groups.push_back(gr);
+        }
+    std::vector<GridJob> jobs;
+    std::vector<const Group*> job_group;
+    const uint64_t rng0 = g_rng;
+    for (int N : n_list)
+        for (const Group& gr : groups) {
+            GridJob j;
+            j.h.class_name = gr.name;
+            j.h.resize(N, gr.M);
+            j.s_lo = gr.s_lo;
+            j.s_hi = gr.s_hi;
+            g_rng = rng0;  // the draw a fresh seeded call would make; after the last model: where that call leaves it
+            if (hmm_init(j.h, model_type)) return 1;
+            jobs.push_back(std::move(j));
+            job_group.push_back(&gr);
+        }
+    SeqStore store;
+    store.sym = sym.data();
+    store.offs = offs.data();
+    if (train_grid(jobs, store, hmm_epsilon, val_auto, max_iterations, env_workers(), env_device())) return 1;
+    const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
+    static char var[] = "sum_log_prob";
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        const GridJob& j = jobs[k];
+        printf("\nHMM learn: class '%s'  N=%d M=%d type=%d  #sequences = %d  max_T=%lld\n", j.h.class_name.c_str(), j.h.N, j.h.M,
+               model_type, j.S(), (long long)job_group[k]->max_T);
+        printf("  epsilon=%g  val_auto=%g  max_iterations=%d\n", hmm_epsilon, val_auto, max_iterations);
+        for (size_t i = 0; i < j.hist.size(); ++i) {
+            if (verbose) print_iteration((int)i, j.hist[i], j.skipped[i]);
+            if (callback) callback(var, j.hist[i]);
+        }
+        std::string path;
+        if (save_learned(j.h, model_type, val_auto, max_iterations, j.hist, &path)) return 1;
+        printf("%zu E-step(s); model saved: %s\n", j.hist.size(), path.c_str());
     }
     return 0;
 }
@@ -1571,6 +1915,61 @@ extern "C" int e2vq_hmm_train_classes(int device, int N, int M, int K, double* p
         memcpy(B + (size_t)k * NM, c.h.B.data(), c.h.B.size() * 8);
         for (size_t i = 0; i < c.hist.size() && (int)i < cap; ++i) sum_log_prob[(size_t)k * cap + i] = c.hist[i];
         if (num_esteps) num_esteps[k] = (int)c.hist.size();
+    }
+    return 0;
+}
+
+// whole training of K models of any (N, M) on arrays, in place: model k has Ns[k] states and Ms[k]
+// symbols, trains on the sequences [seq_lo[k], seq_hi[k]) (ranges may overlap), its pi | A | B at params + param_offs[k]
+// (blocks may not overlap); its measure at sum_log_prob + k cap, its E-step count at num_esteps[k].  Model k's result is
+// e2vq_hmm_train's on its slice, bit for bit.
+extern "C" int e2vq_hmm_train_grid(int device, int K, const int* Ns, const int* Ms, double* params, const int64_t* param_offs,
+                                   const uint16_t* sym, const int64_t* offs, int S, const int64_t* seq_lo, const int64_t* seq_hi,
+                                   double epsilon, double val_auto, int max_iterations, double* sum_log_prob, int cap,
+                                   int* num_esteps)
+{
+    if (K < 1 || !Ns || !Ms || !params || !param_offs || !seq_lo || !seq_hi || cap < 0 || (cap > 0 && !sum_log_prob))
+        return e2vq_set_error("e2vq_hmm_train_grid: bad arguments (K = %d)", K);
+    if (check_offsets(offs, S)) return 1;
+    std::vector<std::pair<i64, i64>> blocks;  // (offset, end) of each model's parameters
+    for (int k = 0; k < K; ++k) {
+        const int N = Ns[k], M = Ms[k];
+        if (N < 1 || N > e2hmm::MAX_N || M < 1 || M > 65536) return e2vq_set_error("model %d: HMM with N=%d M=%d out of range", k, N, M);
+        if (seq_lo[k] < 0 || seq_lo[k] >= seq_hi[k] || seq_hi[k] > S)
+            return e2vq_set_error("model %d: sequence range [%lld, %lld) not a non-empty part of [0, %d)", k, (long long)seq_lo[k],
+                                  (long long)seq_hi[k], S);
+        if (param_offs[k] < 0) return e2vq_set_error("model %d: parameter offset %lld < 0", k, (long long)param_offs[k]);
+        blocks.emplace_back(param_offs[k], param_offs[k] + (i64)N + (i64)N * N + (i64)N * M);
+        for (i64 t = offs[seq_lo[k]]; t < offs[seq_hi[k]]; ++t)
+            if ((int)sym[t] >= M) return e2vq_set_error("model %d: symbol %u outside the codebook size %d", k, sym[t], M);
+    }
+    std::sort(blocks.begin(), blocks.end());
+    for (size_t i = 1; i < blocks.size(); ++i)
+        if (blocks[i].first < blocks[i - 1].second)
+            return e2vq_set_error("parameter blocks overlap: [%lld, %lld) and [%lld, %lld)", (long long)blocks[i - 1].first,
+                                  (long long)blocks[i - 1].second, (long long)blocks[i].first, (long long)blocks[i].second);
+    std::vector<GridJob> jobs((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        GridJob& j = jobs[(size_t)k];
+        const int N = Ns[k];
+        const double* q = params + param_offs[k];
+        if (model_from_arrays(N, Ms[k], q, q + N, q + N + (size_t)N * N, j.h)) return 1;
+        j.s_lo = (int)seq_lo[k];
+        j.s_hi = (int)seq_hi[k];
+    }
+    if (require_device(device)) return 1;
+    SeqStore store;
+    store.sym = sym;
+    store.offs = (const i64*)offs;
+    if (train_grid(jobs, store, epsilon, val_auto, max_iterations, 1, device)) return 1;
+    for (int k = 0; k < K; ++k) {
+        const GridJob& j = jobs[(size_t)k];
+        double* q = params + param_offs[k];
+        memcpy(q, j.h.pi.data(), j.h.pi.size() * 8);
+        memcpy(q + j.h.N, j.h.A.data(), j.h.A.size() * 8);
+        memcpy(q + j.h.N + j.h.A.size(), j.h.B.data(), j.h.B.size() * 8);
+        for (size_t i = 0; i < j.hist.size() && (int)i < cap; ++i) sum_log_prob[(size_t)k * cap + i] = j.hist[i];
+        if (num_esteps) num_esteps[k] = (int)j.hist.size();
     }
     return 0;
 }

@@ -47,6 +47,10 @@ _sig("e2vq_hmm_learn_classes", C.c_int, C.c_int, C.c_int, c_char_pp, C.c_uint, C
      HMM_LEARN_CALLBACK)
 _sig("e2vq_hmm_train_classes", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p)
+_sig("e2vq_hmm_learn_grid", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, c_char_pp, C.c_uint, C.c_double, C.c_double,
+     C.c_int, HMM_LEARN_CALLBACK)
+_sig("e2vq_hmm_train_grid", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p)
 
 
 def _strs(items):
@@ -74,6 +78,17 @@ def hmm_learn_classes(n, model_type, sequence_filenames, hmm_epsilon, val_auto, 
     cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
     check(lib.e2vq_hmm_learn_classes(int(n), int(model_type), files, len(sequence_filenames), float(hmm_epsilon),
                                      float(val_auto), int(max_iterations), cb))
+
+
+def hmm_learn_grid(ns, model_type, sequence_filenames, hmm_epsilon, val_auto, max_iterations, callback=None):
+    """`hmm learn --grid`: one model per (N in ns, M of the files, class at that M), all trained
+    together; per grid point the files and output of hmm_learn_classes(N, ...) on the files of that M, for that class,
+    after the same set_random_seed"""
+    ns = [int(n) for n in ns]
+    files, _k = _strs(sequence_filenames)
+    cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
+    check(lib.e2vq_hmm_learn_grid((C.c_int * max(len(ns), 1))(*ns), len(ns), int(model_type), files, len(sequence_filenames),
+                                  float(hmm_epsilon), float(val_auto), int(max_iterations), cb))
 
 
 def hmm_classify_sequences(model_filenames, sequence_filenames, show_ranked=False, classification_filename=None):
@@ -194,6 +209,37 @@ def train_classes(models, class_seqs, epsilon=1e-5, val_auto=0.3, max_iterations
                                      offs.ctypes.data, len(seqs), class_offs.ctypes.data, float(epsilon), float(val_auto),
                                      int(max_iterations), hist.ctypes.data, cap, n.ctypes.data))
     return [(pi[k].copy(), A[k].copy(), B[k].copy(), list(hist[k, :n[k]])) for k in range(K)]
+
+
+def train_grid(models, seqs, ranges, epsilon=1e-5, val_auto=0.3, max_iterations=-1, device=0):
+    """Baum-Welch of K models of any (N, M) in one batched training: models = [(pi, A, B)],
+    seqs = [uint16 arrays] shared by all, ranges = [(lo, hi)] the sequences seqs[lo:hi] model k trains on (ranges may
+    overlap) -> [(pi, A, B, [sum_log_prob per E-step])], each as `train` on its slice"""
+    K = len(models)
+    if K != len(ranges):
+        raise ValueError(f"{K} models for {len(ranges)} sequence ranges")
+    ms = [tuple(np.asarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = np.array([len(m[0]) for m in ms], dtype=np.int32)
+    Ms = np.array([m[2].shape[1] if m[2].ndim == 2 else 0 for m in ms], dtype=np.int32)
+    sizes = [m[0].size + m[1].size + m[2].size for m in ms]
+    param_offs = np.zeros(K, dtype=np.int64)
+    param_offs[1:] = np.cumsum(sizes)[:-1]
+    params = np.ascontiguousarray(np.concatenate([np.concatenate([x.ravel() for x in m]) for m in ms]))
+    sym, offs = _pack(seqs)
+    lo = np.array([r[0] for r in ranges], dtype=np.int64)
+    hi = np.array([r[1] for r in ranges], dtype=np.int64)
+    cap = 4096
+    hist, n = np.zeros((K, cap)), np.zeros(K, dtype=np.int32)
+    check(lib.e2vq_hmm_train_grid(device, K, Ns.ctypes.data, Ms.ctypes.data, params.ctypes.data, param_offs.ctypes.data,
+                                  sym.ctypes.data, offs.ctypes.data, len(seqs), lo.ctypes.data, hi.ctypes.data,
+                                  float(epsilon), float(val_auto), int(max_iterations), hist.ctypes.data, cap,
+                                  n.ctypes.data))
+    out = []
+    for k, (N, M, o) in enumerate(zip(Ns, Ms, param_offs)):
+        p = params[o:o + sizes[k]]
+        out.append((p[:N].copy(), p[N:N + N * N].reshape(N, N).copy(), p[N + N * N:].reshape(N, M).copy(),
+                    list(hist[k, :n[k]])))
+    return out
 
 
 def viterbi(pi, A, B, seqs, device=0, want_path=True):

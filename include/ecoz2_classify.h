@@ -180,6 +180,32 @@ int e2vq_hmm_train_classes(int device, int N, int M, int K, double *pi, double *
                            const int64_t *offs, int S, const int64_t *class_offs, double epsilon, double val_auto,
                            int max_iterations, double *sum_log_prob, int cap, int *num_esteps);
 
+/* ---- a grid of (N, M) points in one batched training -------------------------------------------
+ * `hmm learn --grid`: one model per grid point (n, m, c) of Ns x {the M values of the sequences' headers} x {the classes
+ * present at that M}; N ascending, M ascending, classes in strcmp order; model (n, m, c) trains on the files of class c
+ * and codebook size m in list order.  For every grid point, ecoz2_set_random_seed(s) followed by this call writes and
+ * prints byte for byte what ecoz2_set_random_seed(s); e2vq_hmm_learn_classes(n, model_type, <the files of M = m>, ...)
+ * writes and prints for class c (.hmm, .csv, stdout block, callback values): every model starts from the generator state
+ * of entry, and the generator is left where a seeded single call for the last model leaves it.  Stdout: the blocks in
+ * grid order, after all training.  An empty list, an empty or duplicated N, N outside [1, 512], a model type outside 0..3
+ * or a symbol >= its file's M return 1 before any HIP call, and no file is written unless every model trained.
+ * ECOZ2_HMM_LEARN_BATCH_BYTES packs models greedily in grid order, a model counting (T_k (N_k + 1) + W_k) * 8 bytes
+ * (W_k = e2vq_hmm_acc_words(N_k, M_k)) and the symbols of a (class, M) counted once per batch; ECOZ2_VQ_GPUS deals whole
+ * models to devices.  Neither changes a byte of the output. */
+int e2vq_hmm_learn_grid(const int *Ns, int num_N, int model_type, const char *const *sequence_filenames,
+                        unsigned num_sequences, double hmm_epsilon, double val_auto, int max_iterations,
+                        void (*callback)(char *variable, double value));
+/* the same training on arrays, in place: K models, model k with Ns[k] states and Ms[k] symbols, trained on the sequences
+ * [seq_lo[k], seq_hi[k]) of offs (non-empty; ranges of different models may overlap, the symbols go to the device once),
+ * its pi | A | B (Ns[k] + Ns[k]^2 + Ns[k] Ms[k] doubles) at params + param_offs[k] (blocks may not overlap); its measure
+ * per E-step at sum_log_prob[k cap ..], its E-step count at num_esteps[k].  Model k's result equals e2vq_hmm_train on its
+ * slice, bit for bit.  Bad ranges, overlapping parameter blocks and symbols >= M_k are refused before the device.  One
+ * device; ECOZ2_HMM_LEARN_BATCH_BYTES applies. */
+int e2vq_hmm_train_grid(int device, int K, const int *Ns, const int *Ms, double *params, const int64_t *param_offs,
+                        const uint16_t *sym, const int64_t *offs, int S, const int64_t *seq_lo, const int64_t *seq_hi,
+                        double epsilon, double val_auto, int max_iterations, double *sum_log_prob, int cap,
+                        int *num_esteps);
+
 /* Viterbi decoding of S sequences under one model: logarithms of the parameters taken on the host
  * (log 0 = -inf; a negative, NaN or infinite parameter is refused), maximisation on the GPU.  log_prob[s] = ln P*,
  * status[s]: 0 ok, 1 ln P* = -inf (the model cannot emit the sequence; the path is still written), 2 a symbol >= M
