@@ -10,9 +10,11 @@ from ._lib import lib, lib_path, Ecoz2Error, check  # noqa: F401
 from .vq import (  # noqa: F401
     VqGroup,
     VqSession,
+    CodebookSet,
     LevelStats,
     vq_learn,
     vq_quantize,
+    vq_quantize_codebooks,
     vq_classify,
     vq_show,
     version,

@@ -113,6 +113,14 @@ _sig("e2vq_learn", C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_char_p, C.c_cha
 _sig("e2vq_quantize_host", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 _sig("e2vq_quantize_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 _sig("e2vq_synchronize", C.c_int, C.c_void_p)
+# Part 2: a resident set of codebooks and the one-pass quantize over it (vq_cbset.cpp)
+_sig("e2vq_cbset_create", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p))
+_sig("e2vq_cbset_destroy", None, C.c_void_p)
+_sig("e2vq_cbset_set_stream", C.c_int, C.c_void_p, C.c_void_p)
+_sig("e2vq_cbset_quantize_device", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64)
+_sig("e2vq_cbset_quantize_host", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
+_sig("e2vq_cbset_launch_counts", C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_sig("e2vq_vq_quantize_codebooks", C.c_int, c_char_pp, C.c_int, c_char_pp, C.c_int, C.c_int)
 _sig("e2vq_avg_distortion_host", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double))
 _sig("e2vq_prd_info", C.c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int64))
 _sig("e2vq_prd_read", C.c_int, C.c_char_p, C.c_void_p, C.c_int64)

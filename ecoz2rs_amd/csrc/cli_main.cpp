@@ -36,6 +36,8 @@ static int usage()
             "                 trained together)\n"
             "  ecoz2 vq quantize --codebook <cbook> --predictors <files|dirs|tt.csv>...\n"
             "                 [--predictors-dir-template <t>] [--tt <TRAIN|TEST>] [--class-name <class>] [-s]\n"
+            "  ecoz2 vq quantize --codebooks <files|dirs>... --predictors <files|dirs|tt.csv>...   (every codebook in one pass,\n"
+            "                 [--tt <TRAIN|TEST>] [--class-name <class>] [-s]                      ascending M)\n"
             "  ecoz2 vq classify [-r] --codebooks <files|dirs>... --tt <TRAIN|TEST> --predictors <files|dirs|tt.csv>...\n"
             "  ecoz2 vq show [-f <from>] [-t <to>] <codebook>\n"
             "  ecoz2 seq show [-c] [-L] [--full] [--pickle out.pkl -M <M> --tt <TRAIN|TEST> [--class-name c]] <file.seq|tt.csv>...\n"
@@ -147,7 +149,7 @@ static int vq_quantize(int argc, char** argv)
 {
     std::string codebook, tmpl = "data/predictors", tt, cls;
     bool show = false;
-    std::vector<std::string> predictors;
+    std::vector<std::string> predictors, codebooks;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -155,6 +157,7 @@ static int vq_quantize(int argc, char** argv)
             return argv[++i];
         };
         if (a == "--codebook") codebook = val("--codebook");
+        else if (a == "--codebooks") { while (i + 1 < argc && !is_flag(argv[i + 1])) codebooks.push_back(argv[++i]); }
         else if (a == "--predictors-dir-template") tmpl = val("--predictors-dir-template");
         else if (a == "--tt") tt = val("--tt");
         else if (a == "--class-name") cls = val("--class-name");
@@ -163,16 +166,26 @@ static int vq_quantize(int argc, char** argv)
         else if (!is_flag(argv[i])) predictors.push_back(a);
         else return usage();
     }
-    if (codebook.empty() || predictors.empty()) return usage();
-    std::vector<std::string> files;
+    if (codebook.empty() == codebooks.empty() || predictors.empty()) return usage();  // (one of --codebook / --codebooks)
+    std::vector<std::string> files, cbs;
+    if (!codebooks.empty()) {
+        e2vq_io::resolve_filenames(codebooks, ".cbook", cbs);
+        if (cbs.empty()) { printf("No codebooks given\n"); return 0; }
+    }
     const bool tt_list = predictors.size() == 1 && predictors[0].size() > 4 &&
                          predictors[0].compare(predictors[0].size() - 4, 4, ".csv") == 0;
     int rc = tt_list ? e2vq_io::files_from_csv(predictors[0], tt, cls, "", ".prd", &tmpl, files)
                      : e2vq_io::resolve_filenames(predictors, ".prd", files);
     if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
     printf("number of predictor files: %zu\n", files.size());  // src/vq/mod.rs:211
-    printf("nom_raas = %s\n", codebook.c_str());               // src/ecoz2_lib/mod.rs:326
     auto ptrs = cptrs(files);
+    if (!cbs.empty()) {
+        for (const std::string& c : cbs) printf("nom_raas = %s\n", c.c_str());
+        auto pc = cptrs(cbs);
+        e2vq_vq_quantize_codebooks(pc.data(), (int)pc.size(), ptrs.data(), (int)ptrs.size(), show ? 1 : 0);
+        return 0;
+    }
+    printf("nom_raas = %s\n", codebook.c_str());               // src/ecoz2_lib/mod.rs:326
     ecoz2_vq_quantize(codebook.c_str(), ptrs.data(), (int)ptrs.size(), show ? 1 : 0);
     return 0;
 }

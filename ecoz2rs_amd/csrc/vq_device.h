@@ -51,6 +51,16 @@ int pass_classes_mode(int NC, int M);  // the accumulate mode of the batched swe
 int launch_pass_classes(int NC, const double* blk, const PassClassEntry* table, int nentries, const double* cbm, long cbm_stride,
                         int M, const DevScalars* sc, const unsigned long long* l1max_bits, long long* rows, long rows_stride,
                         hipStream_t s);
+// One pass over row-major frames for a set of codebooks (vq_cbset.cpp): every wave fetches its frames once
+// and walks the table; entry e's symbols go to sym + slot * sym_stride, its distortions to dmin + slot * dmin_stride (dmin
+// may be null); 16-byte aligned frames.  0: launched; 1: the order has no narrow MFMA sweep.
+struct QuantizeSetEntry {
+    const double* cbm;  // MFMA tile image of the codebook (codewords beyond M: copies of codeword 0)
+    int MT, M;          // codeword tiles of 16, codebook size
+    int slot, pad;
+};
+int launch_quantize_set(int NC, const double* aos, long T, long nblocks, const QuantizeSetEntry* table, int nentries,
+                        unsigned short* sym, long sym_stride, double* dmin, long dmin_stride, hipStream_t s);
 // prediction orders with a prefiltered sweep (NC = P + 1): the usual LPC orders 12, 16, ..., 40
 #ifndef E2VQ_PRE_NC_LIST
 #define E2VQ_PRE_NC_LIST(X) X(13) X(17) X(21) X(25) X(29) X(33) X(37) X(41)

@@ -226,9 +226,14 @@ __device__ __forceinline__ void pass_mfma_body(const double* __restrict__ blk, l
                                                const int* __restrict__ fb_list,
                                                const int* __restrict__ fb_count,
                                                unsigned short* __restrict__ prev_sym, int incr,
-                                               int list_rowmajor, unsigned short* cells_out, long wg, long nwg)
+                                               int list_rowmajor, unsigned short* cells_out, long wg, long nwg,
+                                               const QuantizeSetEntry* __restrict__ set_table = nullptr, int set_entries = 0,
+                                               long sym_stride = 0, long dmin_stride = 0)
 {
-    constexpr bool AOS = SRC == 1;
+    // SRC = 4 (k_quantize_set): SRC 1 for a SET of codebooks -- the block's operands stay in registers while the sweep, the
+    // combine and the outputs below run once per entry of set_table (its image, and its outputs at slot * the strides)
+    constexpr bool SET = SRC == 4;
+    constexpr bool AOS = SRC == 1 || SET;
     constexpr bool LIST = SRC == 2 || SRC == 3;
     // frame tiles (of 16) per wave: the fallback list is short, so its waves take one tile each -- four times as
     // many waves, each a quarter of the latency of a full 64-frame sweep.  Prediction orders 41 .. 80 (round 4): two
@@ -320,16 +325,19 @@ __device__ __forceinline__ void pass_mfma_body(const double* __restrict__ blk, l
             double* stage = (double*)smem + wib * (NC * 64);  // this wave's 64 rows
             const long remaining = (T - b * 64) * NC;         // doubles left in the payload from this block on
             constexpr int CHUNKS = NC * 64 / 2;               // 16-B chunks per block
+            // ... from this lane's chunk of the first round on: one 32-bit value compared with constants per round (64-bit
+            // bounds per chunk cost the P = 36 kernel 23 spilled registers)
+            const int left = (int)(remaining < NC * 64 ? remaining : NC * 64) - 2 * lane;
 #pragma unroll
             for (int c0 = 0; c0 < CHUNKS; c0 += 64) {
-                const int c = c0 + lane;
-                if (c < CHUNKS) {
+                if (c0 + 64 <= CHUNKS || c0 + lane < CHUNKS) {
+                    const int o = 2 * (c0 + lane);
                     double2 v = make_double2(0.0, 0.0);
-                    if (2 * c + 1 < remaining)
-                        v = *(const double2*)(fb + 2 * c);
-                    else if (2 * c < remaining)
-                        v.x = fb[2 * c];
-                    *(double2*)(stage + 2 * c) = v;
+                    if (left > 2 * c0 + 1)
+                        v = *(const double2*)(fb + o);
+                    else if (left > 2 * c0)
+                        v.x = fb[o];
+                    *(double2*)(stage + o) = v;
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -373,6 +381,22 @@ __device__ __forceinline__ void pass_mfma_body(const double* __restrict__ blk, l
             load_block_frames<NC>(blk, b, lane, Bf);
         }
 
+        [[maybe_unused]] int set_e = 0;
+        [[maybe_unused]] unsigned short* const sym0 = sym;
+        [[maybe_unused]] double* const dmin0 = dmin;
+        // SET: everything from this label to the `goto` below runs once PER ENTRY of the table on the same block.  It may
+        // read but must not change b, T, nblocks, the operands Bf (never written after the fetch above) and the wave's
+        // staging region in LDS (not touched again before the next block's fetch), and it must not contain a workgroup
+        // barrier (the waves of a workgroup walk the table at their own pace).  Only cbm, MT, sym and dmin differ between
+        // entries; best / code / idx are re-initialised by the sweep.  Code added in between becomes per-codebook work.
+        // (-DE2VQ_MFMA_STAMP: stamps 0 and 1 then count once per entry.)
+    [[maybe_unused]] next_codebook:
+        if constexpr (SET) {
+            cbm = set_table[set_e].cbm;
+            MT = set_table[set_e].MT;
+            sym = sym0 + set_table[set_e].slot * sym_stride;
+            dmin = dmin0 ? dmin0 + set_table[set_e].slot * dmin_stride : nullptr;
+        }
         E2VQ_MSTAMP(0)  // frames into registers (prefetched: a copy; else the load is issued here and waited for in the sweep)
         // ---- sweep: 16 codewords x 16 frames per MFMA, k ascending = canonical chain -------
         double best[4];
@@ -494,6 +518,11 @@ __device__ __forceinline__ void pass_mfma_body(const double* __restrict__ blk, l
             }
         }
 
+        if constexpr (SET) {
+            if (++set_e < set_entries) goto next_codebook;
+            sym = sym0;
+            dmin = dmin0;
+        }
         E2VQ_MSTAMP(2)  // combine, prefetch request, outputs
         // ---- accumulate: int32 row images [frame][2n+limb | count, d, d2] -> exact 64-bit adds ----
         if constexpr (MODE == 2 && LIST) {
@@ -578,6 +607,21 @@ __global__ __launch_bounds__(TPBM, 2) void k_pass_mfma_classes(const double* __r
     pass_mfma_body<NC, MODE, TPBM, 0>(blk + e.first_block * (long)(NC * 64), e.frames, e.blocks, cbm + k * cbm_stride, MT, M, sc + k,
                                       l1max_bits + k, nullptr, nullptr, rows + k * rows_stride, 0, nullptr, nullptr, nullptr, 0, 0,
                                       nullptr, 0, 1);
+}
+
+
+// One pass over row-major frames for a SET of codebooks (vq quantize --codebooks): assignment only.
+// k_pass_mfma's row-major body in its set mode (SRC 4): a wave stages each of its 64-frame blocks through LDS once, keeps
+// the operands in registers and walks the set's table -- per entry the body's tile loop and argmin, then that codebook's
+// symbols and distortions at slot * the stride.  The frames are fetched once whatever the set's size.
+template <int NC>
+__global__ __launch_bounds__(256, 2) void k_quantize_set(const double* __restrict__ aos, long T, long nblocks,
+                                                         const QuantizeSetEntry* __restrict__ table, int nentries,
+                                                         unsigned short* __restrict__ sym, long sym_stride,
+                                                         double* __restrict__ dmin, long dmin_stride)
+{
+    pass_mfma_body<NC, 0, 256, 4>(aos, T, nblocks, nullptr, 0, 0, nullptr, nullptr, sym, dmin, nullptr, 0, nullptr, nullptr, nullptr, 0,
+                                  0, nullptr, (long)blockIdx.x, (long)gridDim.x, table, nentries, sym_stride, dmin_stride);
 }
 
 
@@ -1098,6 +1142,25 @@ int launch_pass_classes(int NC, const double* blk, const PassClassEntry* table, 
         default: break;
     }
     return 1;  // (orders without an MFMA sweep train through the single-class path)
+}
+
+int launch_quantize_set(int NC, const double* aos, long T, long nblocks, const QuantizeSetEntry* table, int nentries,
+                        unsigned short* sym, long sym_stride, double* dmin, long dmin_stride, hipStream_t s)
+{
+    if (nentries < 1) return 0;
+    const int grid = grid_for(nblocks, 4, 512);
+    switch (NC) {
+#define X(N)                                                                                                                  \
+    case N:                                                                                                                   \
+        (void)hipFuncSetAttribute((const void*)k_quantize_set<N>, hipFuncAttributeMaxDynamicSharedMemorySize, E2VQ_LDS_BYTES); \
+        hipLaunchKernelGGL((k_quantize_set<N>), dim3(grid), dim3(256), (size_t)4 * N * 64 * 8, s, aos, T, nblocks, table,     \
+                           nentries, sym, sym_stride, dmin, dmin_stride);                                                     \
+        return 0;
+        E2VQ_MFMA_NC_LIST(X)
+#undef X
+        default: break;
+    }
+    return 1;  // (no narrow MFMA sweep for this order: the caller sweeps codebook after codebook)
 }
 
 int launch_pass(int NC, int mode, const double* blk, long T, long nblocks, const double* cbq, const double* cbm,

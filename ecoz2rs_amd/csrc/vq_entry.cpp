@@ -106,6 +106,14 @@ struct PinnedLease {
     template <typename T>
     T* as() const { return (T*)p; }
 };
+// a codebook set destroyed with its scope
+struct CodebookSet {
+    e2vq_cbset* set = nullptr;
+    CodebookSet() = default;
+    CodebookSet(const CodebookSet&) = delete;
+    CodebookSet& operator=(const CodebookSet&) = delete;
+    ~CodebookSet() { e2vq_cbset_destroy(set); }
+};
 // a session destroyed with its scope
 struct Session {
     e2vq_session* s = nullptr;
@@ -348,6 +356,9 @@ namespace {
 // writes overlap.  Every worker allocates ONE pinned and ONE device block (2 slots x CHUNK frames), whatever the file
 // sizes: round 2's whole-file slots cost 370 MB of pinned memory per slot at 1.25 M frames, and four workers sharing a
 // device took 0.82 s where one took 0.23.
+// K codebooks (e2vq_vq_quantize_codebooks; ecoz2_vq_quantize is K = 1): a worker holds the whole set, a unit is read and
+// uploaded once and swept by e2vq_cbset_quantize_device; a slot has room for K rows of symbols and distortions, and every
+// (codebook, file) pair has its own result record and .seq.
 struct QSegment {
     int file;
     i64 t0, n;    // frames [t0, t0 + n) of the file
@@ -371,8 +382,8 @@ struct QFileResult {
 
 struct QSlot {
     double* h_frames = nullptr;
-    uint16_t* h_sym = nullptr;
-    double* h_dmin = nullptr;
+    uint16_t* h_sym = nullptr;  // K rows of QShared::sym_stride symbols
+    double* h_dmin = nullptr;   // K rows of QShared::dmin_stride distortions
     double* d_frames = nullptr;
     unsigned short* d_sym = nullptr;
     double* d_dmin = nullptr;
@@ -382,14 +393,19 @@ struct QSlot {
 
 struct QShared {
     const char* const* files;
-    int P, M;
+    int nfiles, P;
+    std::vector<int> Ms;                       // the codebooks' sizes, ascending
+    std::vector<const double*> refl;           // their reflections
     const char* root;
     i64 chunk;
+    i64 sym_stride = 0, dmin_stride = 0;       // elements between two codebooks' rows of a slot
     std::vector<QUnit> units;
-    std::vector<QFileResult> results;
+    std::vector<QFileResult> results;          // [codebook][file]
     std::atomic<int> next{0};
     std::atomic<bool> failed{false};
-    QShared(int nfiles) : results((size_t)nfiles) {}
+    QShared(int K, int nfiles) : nfiles(nfiles), Ms((size_t)K), refl((size_t)K), results((size_t)K * nfiles) {}
+    int K() const { return (int)Ms.size(); }
+    QFileResult& result(int k, int file) { return results[(size_t)k * nfiles + file]; }
 };
 
 // folds the distortions of frames [t0, t0 + n) of a file into its sum, in frame order
@@ -417,29 +433,30 @@ void quantize_fold(QFileResult& r, i64 t0, const double* dmin, i64 n)
     r.e = e;
 }
 
-int quantize_worker(int device, QShared& sh, const double* refl)
+int quantize_worker(int device, QShared& sh)
 {
     static const bool timing = getenv("ECOZ2_VQ_TIMING") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_start = now();
-    const int NC = sh.P + 1;
+    const int NC = sh.P + 1, K = sh.K();
     double t_setup, t_work;
     int rc, done_units = 0;
     {
         // The staging and the events come before the stream: the stream is drained before the pinned block goes back to
-        // the pool, where another worker may take it.  The session comes after it: destroyed before its stream.
+        // the pool, where another worker may take it.  The codebook set comes after it: destroyed before its stream.
         PinnedLease h_block;
         DeviceBuffer<char> d_block;
         QSlot slots[2];
         Stream st;
-        Session vq;
+        CodebookSet vq;
         auto setup = [&]() -> int {
-            if (e2vq_session_create(device, sh.P, &vq.s) || e2vq_set_codebook(vq.s, refl, sh.M) || st.create() ||
-                e2vq_set_stream(vq.s, (void*)st.s))
+            if (e2vq_cbset_create(device, sh.P, K, sh.Ms.data(), sh.refl.data(), &vq.set) || st.create() ||
+                e2vq_cbset_set_stream(vq.set, (void*)st.s))
                 return 1;
-            // one pinned and one device allocation, carved into the two slots (frames | distortions | symbols, 256-byte aligned)
+            // one pinned and one device allocation, carved into the two slots (frames | K rows of distortions | K rows of
+            // symbols, 256-byte aligned)
             const size_t fb = ((size_t)sh.chunk * NC * 8 + 255) & ~(size_t)255, db = ((size_t)sh.chunk * 8 + 255) & ~(size_t)255,
-                         sb = ((size_t)sh.chunk * 2 + 64 + 255) & ~(size_t)255, slot_bytes = fb + db + sb;
+                         sb = ((size_t)sh.chunk * 2 + 64 + 255) & ~(size_t)255, slot_bytes = fb + K * (db + sb);
             if (!h_block.acquire(2 * slot_bytes))
                 return e2vq_set_error("no pinned memory for the quantize staging (%zu bytes)", 2 * slot_bytes);
             if (d_block.reserve(2 * slot_bytes))
@@ -450,10 +467,10 @@ int quantize_worker(int device, QShared& sh, const double* refl)
                 char* d = d_block.get() + k * slot_bytes;
                 q.h_frames = (double*)h;
                 q.h_dmin = (double*)(h + fb);
-                q.h_sym = (uint16_t*)(h + fb + db);
+                q.h_sym = (uint16_t*)(h + fb + K * db);
                 q.d_frames = (double*)d;
                 q.d_dmin = (double*)(d + fb);
-                q.d_sym = (unsigned short*)(d + fb + db);
+                q.d_sym = (unsigned short*)(d + fb + K * db);
                 if (q.done.create(hipEventDisableTiming)) return 1;
             }
             return 0;
@@ -463,16 +480,20 @@ int quantize_worker(int device, QShared& sh, const double* refl)
             HIPCHK(hipEventSynchronize(q.done.e));
             const QUnit& u = sh.units[(size_t)q.unit];
             q.unit = -1;
-            for (const QSegment& g : u.segs) {
-                QFileResult& r = sh.results[(size_t)g.file];
-                if (g.whole) {
-                    double e = 0.0;
-                    for (i64 t = 0; t < g.n; ++t) e += q.h_dmin[g.off + t] - 1.0;
-                    r.e = e;
-                    if (e2vq_seq_write(r.seq_path.c_str(), r.cls.c_str(), sh.M, q.h_sym + g.off, g.n)) return 1;
-                } else {
-                    quantize_fold(r, g.t0, q.h_dmin + g.off, g.n);
-                    if (e2vq_io::seq_write_range(r.tmp_path.c_str(), g.t0, q.h_sym + g.off, g.n)) return 1;
+            for (int k = 0; k < K; ++k) {
+                const uint16_t* sym = q.h_sym + k * sh.sym_stride;
+                const double* dmin = q.h_dmin + k * sh.dmin_stride;
+                for (const QSegment& g : u.segs) {
+                    QFileResult& r = sh.result(k, g.file);
+                    if (g.whole) {
+                        double e = 0.0;
+                        for (i64 t = 0; t < g.n; ++t) e += dmin[g.off + t] - 1.0;
+                        r.e = e;
+                        if (e2vq_seq_write(r.seq_path.c_str(), r.cls.c_str(), sh.Ms[(size_t)k], sym + g.off, g.n)) return 1;
+                    } else {
+                        quantize_fold(r, g.t0, dmin + g.off, g.n);
+                        if (e2vq_io::seq_write_range(r.tmp_path.c_str(), g.t0, sym + g.off, g.n)) return 1;
+                    }
                 }
             }
             return 0;
@@ -497,9 +518,13 @@ int quantize_worker(int device, QShared& sh, const double* refl)
                 q.unit = ui;
                 if (u.n > 0) {
                     HIPCHK(hipMemcpyAsync(q.d_frames, q.h_frames, (size_t)u.n * NC * 8, hipMemcpyHostToDevice, st.s));
-                    if (e2vq_quantize_device(vq.s, q.d_frames, u.n, q.d_sym, q.d_dmin)) return 1;
-                    HIPCHK(hipMemcpyAsync(q.h_sym, q.d_sym, (size_t)u.n * 2, hipMemcpyDeviceToHost, st.s));
-                    HIPCHK(hipMemcpyAsync(q.h_dmin, q.d_dmin, (size_t)u.n * 8, hipMemcpyDeviceToHost, st.s));
+                    if (e2vq_cbset_quantize_device(vq.set, q.d_frames, u.n, q.d_sym, sh.sym_stride, q.d_dmin, sh.dmin_stride)) return 1;
+                    for (int c = 0; c < K; ++c) {
+                        HIPCHK(hipMemcpyAsync(q.h_sym + c * sh.sym_stride, q.d_sym + c * sh.sym_stride, (size_t)u.n * 2,
+                                              hipMemcpyDeviceToHost, st.s));
+                        HIPCHK(hipMemcpyAsync(q.h_dmin + c * sh.dmin_stride, q.d_dmin + c * sh.dmin_stride, (size_t)u.n * 8,
+                                              hipMemcpyDeviceToHost, st.s));
+                    }
                 }
                 HIPCHK(hipEventRecord(q.done.e, st.s));
                 ++done_units;
@@ -522,25 +547,14 @@ int quantize_worker(int device, QShared& sh, const double* refl)
 
 }  // namespace
 
-// ECOZ2_VQ_GPUS = N workers (one session + host thread each; ranks beyond the device count share devices).  Frames are
-// independent, so there is no collective; every .seq, and the totals (per file in frame order, files in list order, on
-// the calling thread), are the same for any N.  ECOZ2_VQ_QUANTIZE_CHUNK: frames per unit (default 2^17 = 39 MB at P = 36).
-extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predictor_filenames, int num_predictors,
-                                 int show_filenames)
+// every .prd against the codebooks of `sh` (ascending M): plan, workers, renames, report.  The headers of all files are read
+// before the first HIP call and before anything is created under the out root.
+static int quantize_files(QShared& sh, const char* const* predictor_filenames, int num_predictors, int show_filenames)
 {
-    if (!nom_raas || !predictor_filenames || num_predictors < 0) return e2vq_set_error("ecoz2_vq_quantize: bad arguments");
-    char cb_cls[96];
-    int P, M;
-    if (e2vq_cbook_info(nom_raas, cb_cls, &P, &M)) return 1;
-    std::vector<double> refl((size_t)M * (P + 1));
-    if (e2vq_cbook_read(nom_raas, refl.data(), M)) return 1;
-    const int ndev = device_count();
-    if (!ndev) return 1;
-    const int dev0 = env_device();
+    const int K = sh.K(), P = sh.P;
     const char* root = e2vq_env_str("ECOZ2_VQ_OUT_ROOT", ".");
-    QShared sh(num_predictors);
     // split files are written to <seq>.tmp and renamed at the end: whatever way this call ends short of that, the .tmp files
-    // it has created so far go away (a later file's bad header, a failed worker, a failed rename)
+    // it has created so far go away (a failed worker, a failed rename)
     struct TmpGuard {
         QShared& sh;
         bool keep = false;
@@ -552,11 +566,30 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
         }
     } tmp_guard{sh};
     sh.files = predictor_filenames;
-    sh.P = P;
-    sh.M = M;
     sh.root = root;
     sh.chunk = std::max(1024, e2vq_env_int("ECOZ2_VQ_QUANTIZE_CHUNK", 1 << 17));
-    // plan: headers of every file, then units of at most `chunk` frames
+    sh.dmin_stride = (i64)((((size_t)sh.chunk * 8 + 255) & ~(size_t)255) / 8);
+    sh.sym_stride = (i64)((((size_t)sh.chunk * 2 + 64 + 255) & ~(size_t)255) / 2);
+    for (int i = 0; i < num_predictors; ++i) {
+        char cls[96];
+        int p;
+        int64_t T;
+        if (e2vq_prd_info(predictor_filenames[i], cls, &p, &T)) return 1;
+        if (p != P) return e2vq_set_error("%s: prediction order %d differs from the codebook's %d", predictor_filenames[i], p, P);
+        for (int k = 0; k < K; ++k) {
+            QFileResult& r = sh.result(k, i);
+            r.T = T;
+            r.cls = cls;
+            char path[4096];
+            snprintf(path, sizeof path, "%s/data/sequences/M%d/%s/%s.seq", root, sh.Ms[(size_t)k], cls,
+                     e2vq_io::basename_noext(predictor_filenames[i]).c_str());
+            r.seq_path = path;
+        }
+    }
+    const int ndev = device_count();
+    if (!ndev) return 1;
+    const int dev0 = env_device();
+    // plan: units of at most `chunk` frames
     {
         QUnit cur;
         auto flush = [&] {
@@ -564,18 +597,7 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
             cur = QUnit();
         };
         for (int i = 0; i < num_predictors; ++i) {
-            char cls[96];
-            int p;
-            int64_t T;
-            if (e2vq_prd_info(predictor_filenames[i], cls, &p, &T)) return 1;
-            if (p != P) return e2vq_set_error("%s: prediction order %d differs from the codebook's %d", predictor_filenames[i], p, P);
-            QFileResult& r = sh.results[(size_t)i];
-            r.T = T;
-            r.cls = cls;
-            char path[4096];
-            snprintf(path, sizeof path, "%s/data/sequences/M%d/%s/%s.seq", root, M, cls,
-                     e2vq_io::basename_noext(predictor_filenames[i]).c_str());
-            r.seq_path = path;
+            const i64 T = sh.result(0, i).T;
             if (T <= sh.chunk) {
                 if (cur.n + T > sh.chunk) flush();
                 cur.segs.push_back(QSegment{i, 0, T, cur.n, true});
@@ -584,8 +606,11 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
                 flush();
                 // (not at the final path: a run that fails later must not leave a well-formed .seq of zeros behind, nor
                 // overwrite an earlier good one)
-                r.tmp_path = r.seq_path + ".tmp";
-                if (e2vq_io::seq_create(r.tmp_path.c_str(), cls, M, T)) return 1;
+                for (int k = 0; k < K; ++k) {
+                    QFileResult& r = sh.result(k, i);
+                    r.tmp_path = r.seq_path + ".tmp";
+                    if (e2vq_io::seq_create(r.tmp_path.c_str(), r.cls.c_str(), sh.Ms[(size_t)k], T)) return 1;
+                }
                 for (i64 t0 = 0; t0 < T; t0 += sh.chunk) {
                     const i64 n = std::min<i64>(sh.chunk, T - t0);
                     cur.segs.push_back(QSegment{i, t0, n, 0, false});
@@ -605,7 +630,7 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
         const int distinct = std::min(W, ndev);
         if (W > distinct) W = std::max(distinct, std::min(W, num_predictors / 256));
     }
-    if (run_workers(W, [&](int w) { return quantize_worker(worker_device(dev0, w, ndev), sh, refl.data()); })) return 1;
+    if (run_workers(W, [&](int w) { return quantize_worker(worker_device(dev0, w, ndev), sh); })) return 1;
     for (QFileResult& r : sh.results)
         if (!r.tmp_path.empty()) {
             if (rename(r.tmp_path.c_str(), r.seq_path.c_str()) != 0)
@@ -613,19 +638,80 @@ extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predic
             r.tmp_path.clear();  // (in place: no longer the guard's business)
         }
     tmp_guard.keep = true;
-    double total_e = 0.0;
-    i64 total_T = 0;
-    for (int i = 0; i < num_predictors; ++i) {
-        const QFileResult& r = sh.results[(size_t)i];
-        total_e += r.e;
-        total_T += r.T;
-        if (show_filenames)
-            printf("%s: '%s' T=%lld avg distortion=%g -> %s\n", predictor_filenames[i], r.cls.c_str(), (long long)r.T,
-                   r.T ? r.e / (double)r.T : 0.0, r.seq_path.c_str());
+    for (int k = 0; k < K; ++k) {
+        double total_e = 0.0;
+        i64 total_T = 0;
+        for (int i = 0; i < num_predictors; ++i) {
+            const QFileResult& r = sh.result(k, i);
+            total_e += r.e;
+            total_T += r.T;
+            if (show_filenames)
+                printf("%s: '%s' T=%lld avg distortion=%g -> %s\n", predictor_filenames[i], r.cls.c_str(), (long long)r.T,
+                       r.T ? r.e / (double)r.T : 0.0, r.seq_path.c_str());
+        }
+        printf("total: %d predictor file(s), %lld vectors, M=%d, avg distortion=%g\n", num_predictors, (long long)total_T,
+               sh.Ms[(size_t)k], total_T ? total_e / (double)total_T : 0.0);
     }
-    printf("total: %d predictor file(s), %lld vectors, M=%d, avg distortion=%g\n", num_predictors, (long long)total_T, M,
-           total_T ? total_e / (double)total_T : 0.0);
     return 0;
+}
+
+// ECOZ2_VQ_GPUS = N workers (one codebook set + host thread each; ranks beyond the device count share devices).  Frames are
+// independent, so there is no collective; every .seq, and the totals (per file in frame order, files in list order, on
+// the calling thread), are the same for any N.  ECOZ2_VQ_QUANTIZE_CHUNK: frames per unit (default 2^17 = 39 MB at P = 36).
+extern "C" int ecoz2_vq_quantize(const char* nom_raas, const char* const* predictor_filenames, int num_predictors,
+                                 int show_filenames)
+{
+    if (!nom_raas || !predictor_filenames || num_predictors < 0) return e2vq_set_error("ecoz2_vq_quantize: bad arguments");
+    char cb_cls[96];
+    int P, M;
+    if (e2vq_cbook_info(nom_raas, cb_cls, &P, &M)) return 1;
+    std::vector<double> refl((size_t)M * (P + 1));
+    if (e2vq_cbook_read(nom_raas, refl.data(), M)) return 1;
+    QShared sh(1, num_predictors);
+    sh.P = P;
+    sh.Ms[0] = M;
+    sh.refl[0] = refl.data();
+    return quantize_files(sh, predictor_filenames, num_predictors, show_filenames);
+}
+
+// `vq quantize --codebooks`: the same over a set of codebooks of one order, in ascending M (include/ecoz2_vq.h)
+extern "C" int e2vq_vq_quantize_codebooks(const char* const* cb_filenames, int num_codebooks,
+                                          const char* const* predictor_filenames, int num_predictors, int show_filenames)
+{
+    if (!cb_filenames || !predictor_filenames || num_predictors < 0) return e2vq_set_error("e2vq_vq_quantize_codebooks: bad arguments");
+    if (num_codebooks < 1) return e2vq_set_error("e2vq_vq_quantize_codebooks: no codebooks");
+    if (num_codebooks > 64) return e2vq_set_error("e2vq_vq_quantize_codebooks: %d codebooks, at most 64 per call", num_codebooks);
+    struct Cb {
+        const char* file;
+        int M;
+        std::vector<double> refl;
+    };
+    std::vector<Cb> cbs((size_t)num_codebooks);
+    int P = -1;
+    for (int k = 0; k < num_codebooks; ++k) {
+        Cb& c = cbs[(size_t)k];
+        c.file = cb_filenames[k];
+        char cls[96];
+        int p;
+        if (!c.file) return e2vq_set_error("e2vq_vq_quantize_codebooks: bad arguments");
+        if (e2vq_cbook_info(c.file, cls, &p, &c.M)) return 1;
+        if (P < 0) P = p;
+        if (p != P) return e2vq_set_error("%s: prediction order %d differs from %s's %d", c.file, p, cb_filenames[0], P);
+        c.refl.resize((size_t)c.M * (P + 1));
+        if (e2vq_cbook_read(c.file, c.refl.data(), c.M)) return 1;
+    }
+    std::stable_sort(cbs.begin(), cbs.end(), [](const Cb& a, const Cb& b) { return a.M < b.M; });
+    for (int k = 1; k < num_codebooks; ++k)
+        if (cbs[(size_t)k].M == cbs[(size_t)k - 1].M)
+            return e2vq_set_error("%s and %s: two codebooks of M=%d would write the same sequences", cbs[(size_t)k - 1].file,
+                                  cbs[(size_t)k].file, cbs[(size_t)k].M);
+    QShared sh(num_codebooks, num_predictors);
+    sh.P = P;
+    for (int k = 0; k < num_codebooks; ++k) {
+        sh.Ms[(size_t)k] = cbs[(size_t)k].M;
+        sh.refl[(size_t)k] = cbs[(size_t)k].refl.data();
+    }
+    return quantize_files(sh, predictor_filenames, num_predictors, show_filenames);
 }
 
 extern "C" int ecoz2_vq_classify(const char* const* cb_filenames, int num_codebooks, const char* const* prd_filenames,

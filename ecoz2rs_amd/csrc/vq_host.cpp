@@ -819,6 +819,12 @@ static int ensure_qblk(e2vq_session* s, i64 T)
     return 0;
 }
 
+// the route e2vq_quantize_device takes for the session's codebook: the prefiltered sweep + FP64 fallback, or a plain sweep
+bool e2vq_quantize_is_prefiltered(const e2vq_session* s)
+{
+    return s->pre_enabled && s->M >= s->pre_min_M_quant && e2vq::prefilter_supports(s->NC, s->M);
+}
+
 extern "C" int e2vq_quantize_device(e2vq_session* s, const void* device_frames, int64_t T, void* device_sym,
                                     void* device_dmin)
 {
@@ -827,7 +833,7 @@ extern "C" int e2vq_quantize_device(e2vq_session* s, const void* device_frames, 
     if (T > (int64_t)INT32_MAX - 64) return e2vq_set_error("%lld frames per quantize call exceed 2^31 - 65 (split the call)", (long long)T);
     HIPCHK(hipSetDevice(s->device));
     const i64 nb = (T + s->FB - 1) / s->FB;
-    if (s->pre_enabled && s->M >= s->pre_min_M_quant && e2vq::prefilter_supports(s->NC, s->M)) {
+    if (e2vq_quantize_is_prefiltered(s)) {
         // prefiltered sweep.  Fused (every prefiltered order): the assignment-only kernel builds the f16 limb images of its frames from the
         // row-major payload itself and keeps the FP64 frames in LDS for the exact evaluation -- every frame is read once.
         // Otherwise one preparation pass over the payload writes the limb image and the tolerance terms first.  Either

@@ -4,6 +4,7 @@
 //   vq_pass.cpp   one LBG iteration: the pass (kernel choice and launches), statistics, the speculative update
 //   vq_group.cpp  the in-process group: peer-to-peer exchange, RCCL loaded with dlopen
 //   vq_entry.cpp  the reference's entry points: file readers, upload, ecoz2_vq_learn / quantize / classify / show
+//   vq_cbset.cpp  a resident set of codebooks and the one-pass quantize over it
 #pragma once
 #include "../../include/ecoz2_vq.h"
 #include "hip_host.h"
@@ -236,5 +237,6 @@ bool e2vq_use_prefilter(const e2vq_session* s, int mode);                       
 int e2vq_fold_pending_timing(e2vq_session* s);                                       // vq_pass.cpp
 int e2vq_pass_stats_impl(e2vq_session* s, e2vq_level_stats* out, bool wait_failed);  // vq_pass.cpp
 int e2vq_resolve_failed_cells(e2vq_session* s);                                      // vq_pass.cpp
+bool e2vq_quantize_is_prefiltered(const e2vq_session* s);                             // vq_host.cpp
 const char* e2vq_env_str(const char* name, const char* dflt);                          // vq_entry.cpp
 

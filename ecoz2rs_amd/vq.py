@@ -92,6 +92,14 @@ def vq_quantize(nom_raas, predictor_filenames, show_filenames=False):
     check(lib.ecoz2_vq_quantize(str(nom_raas).encode(), files, len(predictor_filenames), int(show_filenames)))
 
 
+def vq_quantize_codebooks(cb_filenames, predictor_filenames, show_filenames=False):
+    """`vq quantize --codebooks`: every .prd against every codebook, each file read and uploaded once; per
+    codebook, in ascending M, the .seq files and stdout block of ``vq_quantize`` with that codebook."""
+    cbs, _k1 = _to_vec_of_ptr_const_c_char(cb_filenames)
+    files, _k2 = _to_vec_of_ptr_const_c_char(predictor_filenames)
+    check(lib.e2vq_vq_quantize_codebooks(cbs, len(cb_filenames), files, len(predictor_filenames), int(show_filenames)))
+
+
 def vq_classify(cb_filenames, prd_filenames, show_ranked=False):
     """ecoz2_lib::vq_classify (src/ecoz2_lib/mod.rs:344-358)."""
     cbs, _k1 = _to_vec_of_ptr_const_c_char(cb_filenames)
@@ -394,3 +402,56 @@ class VqSession:
 
     def quantize_device(self, device_frames, T, device_sym, device_dmin=None):
         check(lib.e2vq_quantize_device(self._h, _ptr(device_frames), int(T), _ptr(device_sym), _ptr(device_dmin)))
+
+
+class CodebookSet:
+    """K codebooks of one prediction order resident on one GPU, quantized over in one pass (include/ecoz2_vq.h:
+    e2vq_cbset_*).  codebooks: K arrays of (M_k, P+1) reflections."""
+
+    def __init__(self, prediction_order, codebooks, device=0):
+        self._h = C.c_void_p()  # (first: close() runs from __del__ whatever fails below)
+        self.P = int(prediction_order)
+        self._cbs = [np.ascontiguousarray(c, dtype=np.float64) for c in codebooks]
+        assert all(c.ndim == 2 and c.shape[1] == self.P + 1 for c in self._cbs)
+        self.K = len(self._cbs)
+        self.Ms = [c.shape[0] for c in self._cbs]
+        ms = (C.c_int * max(self.K, 1))(*self.Ms)
+        ptrs = (C.c_void_p * max(self.K, 1))(*[c.ctypes.data for c in self._cbs])
+        check(lib.e2vq_cbset_create(int(device), self.P, self.K, ms, ptrs, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib.e2vq_cbset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_stream(self, hip_stream):
+        check(lib.e2vq_cbset_set_stream(self._h, C.c_void_p(hip_stream) if hip_stream else None))
+
+    def quantize(self, frames, want_dmin=True):
+        """(T, P+1) float64 numpy frames -> (K, T) uint16 symbols [, (K, T) float64 minimum distortions]"""
+        a = np.ascontiguousarray(frames, dtype=np.float64)
+        assert a.ndim == 2 and a.shape[1] == self.P + 1
+        sym = np.empty((self.K, a.shape[0]), dtype=np.uint16)
+        dmin = np.empty((self.K, a.shape[0]), dtype=np.float64) if want_dmin else None
+        check(lib.e2vq_cbset_quantize_host(self._h, a.ctypes.data, a.shape[0], sym.ctypes.data,
+                                           dmin.ctypes.data if want_dmin else None))
+        return (sym, dmin) if want_dmin else sym
+
+    def quantize_device(self, device_frames, T, device_sym, sym_stride, device_dmin=None, dmin_stride=0):
+        """Device pointers or tensors; codebook k's symbols at device_sym + k * sym_stride elements.  Enqueued on the set's stream."""
+        check(lib.e2vq_cbset_quantize_device(self._h, _ptr(device_frames), int(T), _ptr(device_sym), int(sym_stride),
+                                             _ptr(device_dmin), int(dmin_stride)))
+
+    def launch_counts(self):
+        """(launches of k_quantize_set, per-codebook sweeps made on the set's behalf) so far"""
+        a, b = C.c_int64(), C.c_int64()
+        check(lib.e2vq_cbset_launch_counts(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value

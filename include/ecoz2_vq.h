@@ -271,6 +271,37 @@ int e2vq_synchronize(e2vq_session *s);
 /* average distortion sum_t (dmin_t - 1) / T of frames against the session's codebook (frame order, plain f64 sum) */
 int e2vq_avg_distortion_host(e2vq_session *s, const double *frames, int64_t T, double *avg);
 
+/* ---- a resident set of codebooks and the one-pass quantize over it (vq_cbset.cpp) ---------------------
+ * K codebooks (reflections, Ms[k] x (P+1) row-major) of one order on one device; 1 <= K <= 64, 1 <= Ms[k] <= 65536.  The
+ * set keeps per codebook what a session builds from e2vq_set_codebook and e2vq_quantize_device (codewords, MFMA tile image,
+ * the prefiltered sweep's limb image and scales), built once.  Bad arguments return 1 before any HIP call. */
+typedef struct e2vq_cbset e2vq_cbset;
+int  e2vq_cbset_create(int device, int prediction_order, int K, const int *Ms, const double *const *reflections,
+                       e2vq_cbset **out);
+void e2vq_cbset_destroy(e2vq_cbset *set);
+int  e2vq_cbset_set_stream(e2vq_cbset *set, void *hip_stream);
+/* T row-major frames on the device -> symbols of codebook k at device_sym + k * sym_stride (uint16 elements), distortions
+ * at device_dmin + k * dmin_stride (doubles; device_dmin may be NULL); strides >= T.  T <= 2^31 - 65.  Enqueued on the
+ * set's stream.  Codebook k's outputs are bit for bit those of e2vq_quantize_device of a session holding codebook k.
+ * Orders P = 4 .. 40 with 16-byte aligned frames: one launch of k_quantize_set sweeps every codebook that a session would
+ * sweep plainly (the frames are fetched once); a codebook a session sweeps prefiltered (P = 12, 16 .. 40, M >= 256) keeps
+ * that path; other orders and 8-byte aligned frames run the session's sweep per codebook. */
+int  e2vq_cbset_quantize_device(e2vq_cbset *set, const void *device_frames, int64_t T, void *device_sym,
+                                int64_t sym_stride, void *device_dmin, int64_t dmin_stride);
+int  e2vq_cbset_quantize_host(e2vq_cbset *set, const double *frames, int64_t T, uint16_t *sym, double *dmin); /* K x T */
+/* launches so far: of k_quantize_set, and of the per-codebook sweeps (prefiltered or plain) made on the set's behalf */
+int  e2vq_cbset_launch_counts(e2vq_cbset *set, int64_t *set_launches, int64_t *single_launches);
+
+/* `vq quantize --codebooks`: every .prd against every codebook, each file read and uploaded once.  Codebooks are processed
+ * and reported in ascending M whatever the argument order; for every codebook this writes and prints byte for byte what
+ * ecoz2_vq_quantize(<that codebook>, <the same files>, n, show_filenames) would under the same ECOZ2_VQ_OUT_ROOT (the
+ * data/sequences/M<M>/<class>/<name>.seq files, the per-file lines, the `total:` line), the stdout blocks after all work.
+ * An empty list or more than 64 codebooks, an unreadable codebook or predictor file, codebooks of differing P, two
+ * codebooks of one M and a predictor file of another order return 1 before any HIP call.  ECOZ2_VQ_GPUS,
+ * ECOZ2_VQ_QUANTIZE_CHUNK and ECOZ2_VQ_DEVICE as for ecoz2_vq_quantize (every worker holds the whole set). */
+int  e2vq_vq_quantize_codebooks(const char *const *cb_filenames, int num_codebooks,
+                                const char *const *predictor_filenames, int num_predictors, int show_filenames);
+
 /* ---- every class's codebook in one batched training (vq_classes.cpp) --------------------------------
  * `vq learn --all-classes`: one codebook per class name found in the .prd headers (e2vq_prd_info), classes in byte order
  * of their names (strcmp), each class's files in list order (its frame order).  For every class c this writes and prints
