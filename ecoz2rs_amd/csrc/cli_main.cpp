@@ -56,6 +56,9 @@ static int usage()
             "  ecoz2 hmm classify [-r] [-c|--c12n <out.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST> -M <M> [--class-name c]\n"
             "                  (-s|--sequences <files|dirs|tt.csv>... | --predictors <files|dirs|tt.csv>... --codebooks <files|dirs>...\n"
             "                   [--predictors-dir-template <t>])\n"
+            "  ecoz2 hmm classify --grid [-r] [-c|--c12n <dir>] [--summary <file.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST>\n"
+            "                  [-M <m1,m2,...>] -s|--sequences <files|dirs|tt.csv>...   (every (N, M) of the models, scored together;\n"
+            "                  a tt.csv needs -M)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -673,6 +676,80 @@ static int hmm_learn_grid(const std::string& n_arg, const std::string& m_arg, co
     return 0;
 }
 
+// `hmm classify --grid`: every (N, M) point of the given models classified in one batched scoring.
+// With a tt.csv each M of -M takes the --tt rows under sequences/M<m>; with directories or files -M, if given, filters
+// both the models and the sequences by their headers.
+static int hmm_classify_grid(const std::string& m_arg, const std::string& cls, const std::string& tt, bool ranked,
+                             const std::string& c12n_dir, const std::string& summary, const std::vector<std::string>& models,
+                             const std::vector<std::string>& sequences, const std::vector<std::string>& predictors,
+                             const std::vector<std::string>& codebooks)
+{
+    const char* excluded = !cls.empty() ? "--class-name" : !predictors.empty() ? "--predictors" : !codebooks.empty() ? "--codebooks" : nullptr;
+    if (excluded) {
+        fprintf(stderr, "--grid and %s exclude each other\n", excluded);
+        return usage();
+    }
+    if (models.empty() || tt.empty() || sequences.empty()) return usage();
+    std::vector<int> ms;
+    if (!m_arg.empty() && !int_list(m_arg, ms)) {
+        fprintf(stderr, "--grid takes -M <m1,m2,...>: comma-separated integers\n");
+        return usage();
+    }
+    const bool csv = is_csv_list(sequences);
+    if (csv && ms.empty()) {
+        fprintf(stderr, "--grid with a tt.csv needs -M <m1,m2,...>\n");
+        return usage();
+    }
+    std::sort(ms.begin(), ms.end());
+    for (size_t i = 0; i < ms.size(); ++i)
+        if (ms[i] < 1 || (i > 0 && ms[i] == ms[i - 1])) {
+            fprintf(stderr, "-M %d: %s\n", ms[i], ms[i] < 1 ? "not a codebook size" : "given more than once");
+            return usage();
+        }
+    std::vector<std::string> found_models, hmm_files, found_seqs, seq_files;
+    e2vq_io::resolve_filenames(models, ".hmm", found_models);
+    int rc = 0;
+    if (csv) {
+        for (int m : ms) {
+            std::vector<std::string> f;
+            rc = e2vq_io::files_from_csv(sequences[0], tt, "", "sequences/M" + std::to_string(m), ".seq", nullptr, f);
+            if (rc) break;
+            found_seqs.insert(found_seqs.end(), f.begin(), f.end());
+        }
+    } else {
+        rc = e2vq_io::resolve_filenames(sequences, ".seq", found_seqs);
+    }
+    if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+    auto listed = [&](int m) { return ms.empty() || std::binary_search(ms.begin(), ms.end(), m); };
+    std::set<std::pair<int, int>> points;
+    for (const std::string& f : found_models) {
+        char c[96];
+        int n, m;
+        if (e2vq_hmm_info(f.c_str(), c, &n, &m)) { printf("%s\n", e2vq_last_error()); return 0; }
+        if (!listed(m)) continue;
+        hmm_files.push_back(f);
+        points.insert({n, m});
+    }
+    for (const std::string& f : found_seqs) {
+        char c[96];
+        int m;
+        int64_t T;
+        if (e2vq_seq_info(f.c_str(), c, &m, &T)) { printf("%s\n", e2vq_last_error()); return 0; }
+        if (listed(m)) seq_files.push_back(f);
+    }
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    if (seq_files.empty()) { printf("No sequences given\n"); return 0; }
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("number of HMM models: %zu  number of sequences: %zu\n", hmm_files.size(), seq_files.size());
+    printf("grid points: %zu\n", points.size());
+    printf("show_ranked = %s\n", ranked ? "true" : "false");
+    auto pm = cptrs(hmm_files), ps = cptrs(seq_files);
+    if (e2vq_hmm_classify_grid(pm.data(), (unsigned)pm.size(), ps.data(), (unsigned)ps.size(), ranked, c12n_dir.empty() ? nullptr : c12n_dir.c_str(),
+                               summary.empty() ? nullptr : summary.c_str()))
+        printf("%s\n", e2vq_last_error());
+    return 0;
+}
+
 static int hmm_cmd(int argc, char** argv)
 {
     if (argc < 1) return usage();
@@ -681,7 +758,7 @@ static int hmm_cmd(int argc, char** argv)
     double epsilon = 1e-05, val_auto = 0.3;
     long seed = -1;
     bool ser = false, ranked = false, all_classes = false, grid = false;
-    std::string cls, tt, c12n, hmm, format = "%Lg ", tmpl = "data/predictors", n_arg, m_arg;
+    std::string cls, tt, c12n, hmm, format = "%Lg ", tmpl = "data/predictors", n_arg, m_arg, summary;
     std::vector<std::string> sequences, models, predictors, codebooks;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -699,7 +776,8 @@ static int hmm_cmd(int argc, char** argv)
         else if (cmd == "learn" && (a == "-s" || a == "--seed")) seed = atol(val("-s"));
         else if (a == "--ser") ser = true;
         else if (cmd == "learn" && a == "--all-classes") all_classes = true;
-        else if (cmd == "learn" && a == "--grid") grid = true;
+        else if ((cmd == "learn" || cmd == "classify") && a == "--grid") grid = true;
+        else if (cmd == "classify" && a == "--summary") summary = val("--summary");
         else if (a == "--class-name") cls = val("--class-name");
         else if (a == "-r" || a == "--show-ranked") ranked = true;
         else if (a == "-c" || a == "--c12n") c12n = val("--c12n");
@@ -722,6 +800,7 @@ static int hmm_cmd(int argc, char** argv)
     }
     if (cmd == "learn" && grid) return hmm_learn_grid(n_arg.empty() ? "5" : n_arg, m_arg, cls, type, max_iterations, epsilon,
                                                       val_auto, seed, sequences);
+    if (cmd == "classify" && grid) return hmm_classify_grid(m_arg, cls, tt, ranked, c12n, summary, models, sequences, predictors, codebooks);
     if (M < 1) return usage();
     const std::string subdir = "sequences/M" + std::to_string(M);
     if (cmd == "learn" && all_classes) {  // every class of the TRAIN rows / given files at once

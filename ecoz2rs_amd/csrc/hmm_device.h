@@ -23,6 +23,27 @@ long long acc_words(int N, int M);
 // 1 the model cannot emit the sequence, 2 symbol outside the model's alphabet.  offs: S+1 symbol offsets.
 void launch_score(const ModelDev* models, int K, int maxN, const unsigned short* sym, const long long* offs, int S,
                   double* mant, long long* exp2, int* status, hipStream_t st);
+// Grid scoring.  One model of the batch: the result of sequence s of its pack goes to
+// res_at + (s - the pack's s_lo).  One pack: the models [k0, k0 + count) of the table, which share N, M and the
+// sequences [s_lo, s_hi) of the batch's offs; count <= G of its launch.
+struct ScoreModelDev {
+    ModelDev md;
+    long long res_at;
+};
+struct ScorePackDev {
+    int k0, count, s_lo, s_hi;
+};
+// models of N <= WAVE_N states one wave scores together: floor(64 / N) where that is at least 3 (N <= SCORE_PACK_MAX_N),
+// else 1 -- two models to a wave (22 <= N <= 32) measured 1 to 4 % slower than one
+constexpr int SCORE_PACK_MAX_N = 21;
+inline int score_pack_width(int N) { return N <= SCORE_PACK_MAX_N ? WAVE_N / N : 1; }
+// workgroups a pack of S sequences takes in launch_score_grid (4 waves, a sequence each)
+int score_grid_workgroups(int S);
+// Scores the packs of ONE N <= WAVE_N (LDS is sized by it), G models to a wave (1 <= G <= floor(64 / N)): nblocks
+// workgroups, blocks[2 b], blocks[2 b + 1] = (pack, index of the workgroup within the pack).
+void launch_score_grid(const ScoreModelDev* models, const ScorePackDev* packs, int N, int G, const int* blocks, int nblocks,
+                       const unsigned short* sym, const long long* offs, double* mant, long long* exp2, int* status,
+                       hipStream_t st);
 // Baum-Welch E-step of one model over S sequences (expected counts added to acc; per-sequence P(O) and status out).
 // alpha_buf: total_symbols x N doubles, c_buf: total_symbols doubles (scratch).
 // scratch (N > WAVE_N only; may be null otherwise): fb_scratch_words(N) int64 words, contents irrelevant

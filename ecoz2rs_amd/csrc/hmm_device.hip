@@ -1,5 +1,7 @@
 // hmm_device.hip -- HIP kernels (gfx950) of the HMM consumers of the VQ path:
 //   k_hmm_score   scaled forward pass of every (sequence, model) pair: one wavefront per pair, lane = state
+//   k_hmm_score_grid   the same pass over a batch of models of any (N, M): up to floor(64 / N) models of one (N, M) share a
+//                 wave, lane g N + j = state j of model g (hmm classify --grid)
 //   k_hmm_fb      E-step of Baum-Welch: forward, backward and the expected counts of one sequence per wavefront,
 //                 added to exact fixed-point accumulators (int64 limb sums: order-free, hence deterministic and
 //                 shardable across GPUs with an integer all-reduce, like the VQ cell sums)
@@ -116,6 +118,127 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_hmm_score(const ModelDev* 
     // status 1 -- "not used": an empty sequence has no counts to give and must not enter the pi denominator)
     if (lane == 0) {
         const size_t idx = (size_t)s * K + k;
+        mant[idx] = st == 0 ? p : 0.0;
+        exp2[idx] = st == 0 ? E : 0;
+        status[idx] = st;
+    }
+}
+
+// the value of x in lane `src` (its own for every lane: ds_bpermute_b32, two dwords per double)
+__device__ __forceinline__ double lane_read(double x, int src)
+{
+    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
+    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
+    return __hiloint2double(hi, lo);
+}
+
+// Grid scoring (hmm classify --grid): a PACK is up to G = floor(64 / N) models of one N, M and sequence
+// range; one wave scores one sequence under one pack, lane g N + j = state j of the pack's model g (the lanes from G N up,
+// and the segments of a tail pack's missing models, idle).  Every lane performs k_hmm_score's operations in k_hmm_score's
+// order -- the other states' values come from the lanes of its own segment through lane_read instead of the wave-uniform
+// v_readlane -- so the bits are k_hmm_score's.  A of the pack is in LDS interleaved by lane, element (i, lane) at
+// i G N + lane: row i is one contiguous ds_read_b64 per lane.  Status is per segment: a segment that stops keeps its
+// p and E and idles while the others go on; a symbol >= M stops them all (M is the pack's).
+// blocks[2 b], blocks[2 b + 1] = (pack, index of the block of SCORE_WAVES sequences within the pack's range).
+// G = 1 (N > 21, where fewer than three models fit a wave): one model per wave, k_hmm_score's layout and its v_readlane
+// sums, driven by the tables.
+__global__ __launch_bounds__(64 * SCORE_WAVES) void k_hmm_score_grid(const ScoreModelDev* __restrict__ models,
+                                                                      const ScorePackDev* __restrict__ packs, int N, int G,
+                                                                      const int* __restrict__ blocks,
+                                                                      const unsigned short* __restrict__ sym,
+                                                                      const i64* __restrict__ offs,
+                                                                      double* __restrict__ mant, i64* __restrict__ exp2,
+                                                                      int* __restrict__ status)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double* As = (double*)smem;  // [N][G N]
+    const ScorePackDev pk = packs[blocks[2 * blockIdx.x]];
+    const int GN = G * N;
+    for (int x = threadIdx.x; x < N * GN; x += blockDim.x) {
+        const int i = x / GN, l = x - i * GN, g = l / N;
+        As[x] = g < pk.count ? models[pk.k0 + g].md.A[i * N + (l - g * N)] : 0.0;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int s = pk.s_lo + blocks[2 * blockIdx.x + 1] * SCORE_WAVES + wib;
+    if (s >= pk.s_hi) return;
+    const int g = lane / N;
+    const bool act = g < G && g < pk.count;
+    const int seg = act ? g * N : 0, j = act ? lane - seg : 0;
+    const ScoreModelDev mine = models[pk.k0 + (act ? g : 0)];
+    const int M = mine.md.M;  // (the pack's)
+    const i64 base = offs[s];
+    const i64 T = offs[s + 1] - base;
+    const double pij = act ? mine.md.pi[j] : 0.0;
+    const double* Brow = mine.md.B + (size_t)j * M;
+    const double* Acol = As + (act ? lane : 0);
+    double al = 0.0, p = 0.5;
+    i64 E = 1;
+    int st = act ? 0 : 3;  // (3: no model in this segment)
+    for (i64 t0 = 0; t0 < T && __any(st == 0); t0 += 64) {
+        const int n = (int)((T - t0) < 64 ? (T - t0) : 64);
+        const int mysym = lane < n ? (int)sym[base + t0 + lane] : 0;
+        int o = __builtin_amdgcn_readlane(mysym, 0);
+        double b = (act && o < M) ? Brow[o] : 0.0;
+        for (int q = 0; q < n; ++q) {
+            const double bq = b;
+            const int oq = o;
+            if (q + 1 < n) {  // next step's emission probability is requested before this step's chain runs
+                o = __builtin_amdgcn_readlane(mysym, q + 1);
+                b = (act && o < M) ? Brow[o] : 0.0;
+            }
+            if (oq >= M) {  // symbol outside the pack's alphabet: every segment still going stops
+                if (st == 0) st = 2;
+                break;
+            }
+            double nx;
+            if (t0 + q == 0) {
+                nx = pij * bq;
+            } else {
+                // (four reads in flight ahead of the chain: the compiler does not unroll a loop of cross-lane reads)
+                double acc = 0.0;
+                int i = 0;
+                if (G == 1)  // one segment: its lanes' values are wave-uniform reads, as in k_hmm_score (no LDS-path latency)
+                    for (; i < N; ++i) acc = fma(bcast(al, i), Acol[i * GN], acc);
+                for (; i + 4 <= N; i += 4) {
+                    const double x0 = lane_read(al, seg + i), x1 = lane_read(al, seg + i + 1);
+                    const double x2 = lane_read(al, seg + i + 2), x3 = lane_read(al, seg + i + 3);
+                    const double a0 = Acol[i * GN], a1 = Acol[(i + 1) * GN], a2 = Acol[(i + 2) * GN], a3 = Acol[(i + 3) * GN];
+                    acc = fma(x0, a0, acc);
+                    acc = fma(x1, a1, acc);
+                    acc = fma(x2, a2, acc);
+                    acc = fma(x3, a3, acc);
+                }
+                for (; i < N; ++i) acc = fma(lane_read(al, seg + i), Acol[i * GN], acc);
+                nx = acc * bq;
+            }
+            if (!act) nx = 0.0;
+            double c = 0.0;
+            int i = 0;
+            if (G == 1)
+                for (; i < N; ++i) c = c + bcast(nx, i);
+            for (; i + 4 <= N; i += 4) {
+                const double x0 = lane_read(nx, seg + i), x1 = lane_read(nx, seg + i + 1);
+                const double x2 = lane_read(nx, seg + i + 2), x3 = lane_read(nx, seg + i + 3);
+                c = c + x0;
+                c = c + x1;
+                c = c + x2;
+                c = c + x3;
+            }
+            for (; i < N; ++i) c = c + lane_read(nx, seg + i);
+            if (st == 0) {
+                if (!(c > 0.0)) {
+                    st = 1;
+                } else {
+                    al = nx / c;
+                    scale_step(c, p, E);
+                }
+            }
+            if (!__any(st == 0)) break;
+        }
+    }
+    if (act && j == 0) {
+        const i64 idx = mine.res_at + (s - pk.s_lo);
         mant[idx] = st == 0 ? p : 0.0;
         exp2[idx] = st == 0 ? E : 0;
         status[idx] = st;
@@ -658,6 +781,16 @@ void launch_score(const ModelDev* models, int K, int maxN, const unsigned short*
         hipLaunchKernelGGL(k_hmm_score, grid, dim3(64 * SCORE_WAVES), (size_t)maxN * maxN * 8, st, models, K, k0, sym, offs, S,
                            mant, exp2, status);
     }
+}
+
+int score_grid_workgroups(int S) { return (S + SCORE_WAVES - 1) / SCORE_WAVES; }
+
+void launch_score_grid(const ScoreModelDev* models, const ScorePackDev* packs, int N, int G, const int* blocks, int nblocks,
+                       const unsigned short* sym, const i64* offs, double* mant, i64* exp2, int* status, hipStream_t st)
+{
+    if (nblocks < 1 || N < 1 || N > WAVE_N || G < 1 || G * N > WAVE_N) return;
+    hipLaunchKernelGGL(k_hmm_score_grid, dim3((unsigned)nblocks), dim3(64 * SCORE_WAVES), (size_t)N * G * N * 8, st, models, packs,
+                       N, G, blocks, sym, offs, mant, exp2, status);
 }
 
 void launch_fb(const ModelDev& md, const unsigned short* sym, const i64* offs, int S, double* alpha_buf, double* c_buf,

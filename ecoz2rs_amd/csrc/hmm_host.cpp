@@ -1038,9 +1038,16 @@ int train_grid(std::vector<GridJob>& jobs, const SeqStore& ss, double epsilon, d
 }
 
 // classification report shared by ecoz2_hmm_classify / ecoz2_hmm_classify_predictors
+// what a report says in figures (hmm classify --grid sums them up): the cases that had a model of their class, and
+// C12nResults::last_accuracy / last_avg_accuracy
+struct ReportFigures {
+    size_t classified = 0;
+    float accuracy = 0.f, avg_accuracy = 0.f;
+};
+
 int classify_report(const std::vector<Hmm>& models, const std::vector<std::string>& case_files,
                     const std::vector<std::string>& case_classes, const std::vector<double>& log_probs, int M,
-                    bool show_ranked, const char* c12n_filename)
+                    bool show_ranked, const char* c12n_filename, ReportFigures* figures = nullptr)
 {
     const size_t K = models.size();
     std::vector<std::string> names;
@@ -1067,6 +1074,7 @@ int classify_report(const std::vector<Hmm>& models, const std::vector<std::strin
     }
     printf("\n");
     if (c12n.report_results(names, "", /*c_report=*/true)) return 1;
+    if (figures) *figures = ReportFigures{classified, c12n.last_accuracy, c12n.last_avg_accuracy};
     if (c12n_filename && *c12n_filename) {
         std::string doc = "# num_models=" + std::to_string(K) + "  M=" + std::to_string(M) + "  num_seqs=" + std::to_string(classified) +
                           "\nseq_filename,seq_class_name,correct,rank\n" + csv;
@@ -1081,6 +1089,171 @@ int load_models(const char* const* files, unsigned n, std::vector<Hmm>& models)
     models.resize(n);
     for (unsigned i = 0; i < n; ++i)
         if (hmm_load(files[i], models[i])) return 1;
+    return 0;
+}
+
+// ---- scoring at every point of a grid at once -------------------------------------------------------------
+// One model of a grid scoring: scored exactly as k_hmm_score scores it on the store's sequences [s_lo, s_hi); out[s - s_lo]
+struct ScoreJob {
+    const Hmm* h = nullptr;
+    int s_lo = 0, s_hi = 0;
+    double* log_prob = nullptr;  // ln P, -inf unless the status is 0
+    double* mant = nullptr;      // (the three below may be null)
+    int64_t* exp2 = nullptr;
+    int* status = nullptr;
+    int S() const { return s_hi - s_lo; }
+};
+
+// models to a wave: score_pack_width(N), the widths that measured faster than one model per wave (DESIGN.md 4.8.4's
+// table).  ECOZ2_HMM_SCORE_PACK=0 scores one model per wave at every N, =1 packs floor(64 / N) at every N <= 32 (the
+// benchmark's other arms; the bits are the same)
+int score_pack_width_in_use(int N)
+{
+    const char* v = getenv("ECOZ2_HMM_SCORE_PACK");
+    if (v && *v) return atoi(v) == 0 || N > 32 ? 1 : e2hmm::WAVE_N / N;
+    return e2hmm::score_pack_width(N);
+}
+
+// K jobs of any (N, M) scored together on the current device.  The jobs' sequence ranges are merged into disjoint runs
+// and uploaded once.  Consecutive jobs of one (N, M, range) form groups: for N <= 64 a group is cut into packs of
+// score_pack_width_in_use(N) models, and all packs of one N go into one k_hmm_score_grid launch; a group of N > 64 goes
+// through launch_score (k_hmm_score_wg).  Every launch is enqueued before the one copy back and synchronisation.
+int score_grid_batch(const ScoreJob* jobs, int K, const SeqStore& ss)
+{
+    std::vector<std::pair<int, int>> runs;
+    for (int k = 0; k < K; ++k) runs.emplace_back(jobs[k].s_lo, jobs[k].s_hi);
+    std::sort(runs.begin(), runs.end());
+    std::vector<std::pair<int, int>> merged;
+    for (const auto& r : runs) {
+        if (!merged.empty() && r.first <= merged.back().second)
+            merged.back().second = std::max(merged.back().second, r.second);
+        else
+            merged.push_back(r);
+    }
+    std::vector<i64> offs(1, 0);  // the batch's sequences: the runs one after the other
+    std::vector<int> run_at;      // batch index of each run's first sequence
+    for (const auto& r : merged) {
+        run_at.push_back((int)offs.size() - 1);
+        for (int s = r.first; s < r.second; ++s) offs.push_back(offs.back() + (ss.offs[s + 1] - ss.offs[s]));
+    }
+    auto local = [&](int s) {  // batch index of the store's sequence s
+        const auto it = std::upper_bound(merged.begin(), merged.end(), std::make_pair(s, INT32_MAX));
+        const size_t q = (size_t)(it - merged.begin()) - 1;
+        return run_at[q] + (s - merged[q].first);
+    };
+    // parameters, model table, result slots
+    std::vector<e2hmm::ScoreModelDev> table((size_t)K);
+    std::vector<i64> param_at((size_t)K), res_at((size_t)K), res_stride((size_t)K, 1);
+    i64 n_par = 0, n_res = 0;
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = *jobs[k].h;
+        param_at[(size_t)k] = n_par;
+        n_par += (i64)h.N + (i64)h.N * h.N + (i64)h.N * h.M;
+    }
+    struct Big {  // a group of N > 64: the models [k0, k0 + count) through launch_score, results at [s * count + i]
+        int k0, count, s_lo, S;
+        i64 base;
+    };
+    std::vector<Big> bigs;
+    std::vector<e2hmm::ScorePackDev> packs;
+    std::map<int, std::vector<int>> blocks_by_N;  // N <= 64 -> (pack, workgroup) pairs
+    std::map<int, int> width_of_N;
+    for (int k0 = 0; k0 < K;) {
+        const ScoreJob& a = jobs[k0];
+        int k1 = k0 + 1;
+        while (k1 < K && jobs[k1].h->N == a.h->N && jobs[k1].h->M == a.h->M && jobs[k1].s_lo == a.s_lo && jobs[k1].s_hi == a.s_hi) ++k1;
+        const int N = a.h->N, S = a.S(), lo = local(a.s_lo);
+        if (N > e2hmm::WAVE_N) {
+            bigs.push_back(Big{k0, k1 - k0, lo, S, n_res});
+            for (int k = k0; k < k1; ++k) {
+                res_at[(size_t)k] = n_res + (k - k0);
+                res_stride[(size_t)k] = k1 - k0;
+            }
+            n_res += (i64)S * (k1 - k0);
+        } else {
+            const int G = width_of_N.emplace(N, score_pack_width_in_use(N)).first->second;
+            std::vector<int>& blocks = blocks_by_N[N];
+            for (int p0 = k0; p0 < k1; p0 += G) {
+                const int count = std::min(G, k1 - p0);
+                for (int b = 0; b < e2hmm::score_grid_workgroups(S); ++b) blocks.insert(blocks.end(), {(int)packs.size(), b});
+                packs.push_back(e2hmm::ScorePackDev{p0, count, lo, lo + S});
+                for (int k = p0; k < p0 + count; ++k) {
+                    res_at[(size_t)k] = n_res;
+                    n_res += S;
+                }
+            }
+        }
+        k0 = k1;
+    }
+    std::vector<double> flat((size_t)n_par);
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = *jobs[k].h;
+        double* q = flat.data() + param_at[(size_t)k];
+        std::copy(h.pi.begin(), h.pi.end(), q);
+        std::copy(h.A.begin(), h.A.end(), q + h.N);
+        std::copy(h.B.begin(), h.B.end(), q + h.N + (size_t)h.N * h.N);
+    }
+    std::vector<int> blocks;
+    for (const auto& kv : blocks_by_N) blocks.insert(blocks.end(), kv.second.begin(), kv.second.end());
+    DeviceBuffer<double> d_params, d_mant;
+    DeviceBuffer<i64> d_exp, d_offs;
+    DeviceBuffer<int> d_status, d_blocks;
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<e2hmm::ScoreModelDev> d_table;
+    DeviceBuffer<e2hmm::ScorePackDev> d_packs;
+    DeviceBuffer<ModelDev> d_big;
+    Stream st;  // (after the buffers: see Stream)
+    if (st.create()) return 1;
+    if (d_sym.reserve((size_t)offs.back()) || d_params.upload(flat.data(), flat.size(), st.s) || d_offs.upload(offs.data(), offs.size(), st.s) ||
+        d_mant.reserve((size_t)n_res) || d_exp.reserve((size_t)n_res) || d_status.reserve((size_t)n_res) ||
+        d_blocks.upload(blocks.data(), blocks.size(), st.s) || d_packs.upload(packs.data(), packs.size(), st.s))
+        return 1;
+    for (size_t q = 0; q < merged.size(); ++q) {
+        const i64 a = ss.offs[merged[q].first], b = ss.offs[merged[q].second];
+        if (b > a)
+            HIPCHK(hipMemcpyAsync(d_sym.get() + offs[(size_t)run_at[q]], ss.sym + a, (size_t)(b - a) * 2, hipMemcpyHostToDevice, st.s));
+    }
+    std::vector<ModelDev> big_table;
+    for (int k = 0; k < K; ++k) {
+        const double* q = d_params.get() + param_at[(size_t)k];
+        const int N = jobs[k].h->N, M = jobs[k].h->M;
+        table[(size_t)k] = e2hmm::ScoreModelDev{ModelDev{N, M, q, q + N, q + N + (size_t)N * N}, res_at[(size_t)k]};
+        big_table.push_back(table[(size_t)k].md);
+    }
+    if (d_table.upload(table.data(), table.size(), st.s)) return 1;
+    if (!bigs.empty() && d_big.upload(big_table.data(), big_table.size(), st.s)) return 1;
+    int at = 0;  // one launch per N: each sized by its own LDS (N^2 G doubles a workgroup)
+    for (const auto& kv : blocks_by_N) {
+        const int nb = (int)(kv.second.size() / 2);
+        e2hmm::launch_score_grid(d_table.get(), d_packs.get(), kv.first, width_of_N[kv.first], d_blocks.get() + 2 * at, nb, d_sym.get(),
+                                 d_offs.get(), d_mant.get(), d_exp.get(), d_status.get(), st.s);
+        HIPCHK(hipGetLastError());
+        at += nb;
+    }
+    for (const Big& g : bigs) {
+        e2hmm::launch_score(d_big.get() + g.k0, g.count, jobs[g.k0].h->N, d_sym.get(), d_offs.get() + g.s_lo, g.S, d_mant.get() + g.base,
+                            d_exp.get() + g.base, d_status.get() + g.base, st.s);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<double> mant((size_t)n_res);
+    std::vector<i64> ex((size_t)n_res);
+    std::vector<int> stat((size_t)n_res);
+    if (n_res) {
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), (size_t)n_res * 8, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), (size_t)n_res * 8, hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_status.get(), (size_t)n_res * 4, hipMemcpyDeviceToHost, st.s));
+    }
+    HIPCHK(hipStreamSynchronize(st.s));  // (the one synchronisation; the host vectors above are locals)
+    for (int k = 0; k < K; ++k) {
+        const ScoreJob& j = jobs[k];
+        for (int q = 0; q < j.S(); ++q) {
+            const size_t r = (size_t)(res_at[(size_t)k] + q * res_stride[(size_t)k]);
+            j.log_prob[q] = stat[r] == 0 ? log_prob(mant[r], ex[r]) : -INFINITY;
+            if (j.mant) j.mant[q] = mant[r];
+            if (j.exp2) j.exp2[q] = ex[r];
+            if (j.status) j.status[q] = stat[r];
+        }
+    }
     return 0;
 }
 
@@ -1325,6 +1498,139 @@ extern "C" int ecoz2_hmm_classify(const char* const* model_filenames, unsigned n
         return 1;
     return classify_report(models, ss.files, ss.classes, lp, ss.M < 0 ? models[0].M : ss.M, show_ranked != 0,
                            classification_filename);
+}
+
+// `hmm classify --grid`: a grid point is an (N, M) for which a model is given -- N ascending, then M
+// ascending; its models are the given .hmm files of that header in list order, its sequences the given .seq files of
+// that M in list order.  Every sequence is scored under every model of every point in one batch; then each point gets
+// the line "grid point: N=<n> M=<m>" followed byte for byte by what ecoz2_hmm_classify prints for its lists (and, with
+// classification_dir, that call's CSV as <dir>/N<n>__M<m>.csv), and a summary block (and CSV) closes the output.  All the
+// checks run before any HIP call, and files are written only once everything is scored.
+extern "C" int e2vq_hmm_classify_grid(const char* const* model_filenames, unsigned num_models,
+                                      const char* const* sequence_filenames, unsigned num_sequences, int show_ranked,
+                                      const char* classification_dir, const char* summary_filename)
+{
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("e2vq_hmm_classify_grid: no models");
+    if (!sequence_filenames || num_sequences < 1) return e2vq_set_error("e2vq_hmm_classify_grid: no sequences");
+    std::vector<Hmm> models;
+    if (load_models(model_filenames, num_models, models)) return 1;
+    SeqSet ss;
+    if (load_sequences(sequence_filenames, num_sequences, ss, /*mixed_M=*/true)) return 1;
+    std::map<std::pair<int, int>, std::vector<int>> by_point;  // (std::map: N ascending, then M ascending)
+    for (int k = 0; k < (int)models.size(); ++k) by_point[{models[(size_t)k].N, models[(size_t)k].M}].push_back(k);
+    std::map<int, std::vector<int>> by_M;
+    for (int i = 0; i < ss.S(); ++i) by_M[ss.Ms[(size_t)i]].push_back(i);
+    for (const auto& pv : by_point) {
+        const int N = pv.first.first, M = pv.first.second;
+        for (size_t a = 0; a < pv.second.size(); ++a)
+            for (size_t b = a + 1; b < pv.second.size(); ++b)
+                if (models[(size_t)pv.second[a]].class_name == models[(size_t)pv.second[b]].class_name)
+                    return e2vq_set_error("grid point N=%d M=%d: class '%s' has more than one model (%s, %s)", N, M,
+                                          models[(size_t)pv.second[a]].class_name.c_str(), model_filenames[pv.second[a]],
+                                          model_filenames[pv.second[b]]);
+        if (!by_M.count(M)) return e2vq_set_error("grid point N=%d M=%d: no sequence with codebook size %d among the given ones", N, M, M);
+    }
+    for (const auto& mv : by_M) {
+        bool found = false;
+        for (const auto& pv : by_point) found = found || pv.first.second == mv.first;
+        if (!found)
+            return e2vq_set_error("%s: no model with codebook size %d among the given ones", ss.files[(size_t)mv.second[0]].c_str(), mv.first);
+    }
+    // the store: each M's sequences contiguous, in list order
+    struct MRange {
+        int s_lo = 0, s_hi = 0;
+    };
+    std::vector<uint16_t> sym;
+    std::vector<i64> offs(1, 0);
+    std::map<int, MRange> range_of_M;
+    for (const auto& mv : by_M) {
+        MRange r;
+        r.s_lo = (int)offs.size() - 1;
+        for (int i : mv.second) {
+            sym.insert(sym.end(), ss.sym.begin() + ss.offs[(size_t)i], ss.sym.begin() + ss.offs[(size_t)i + 1]);
+            offs.push_back((i64)sym.size());
+        }
+        r.s_hi = (int)offs.size() - 1;
+        range_of_M[mv.first] = r;
+    }
+    SeqStore store;
+    store.sym = sym.data();
+    store.offs = offs.data();
+    // model k's ln P of its point's sequences, in the point's sequence order
+    std::vector<std::vector<double>> lp(models.size());
+    std::vector<ScoreJob> jobs;
+    for (const auto& pv : by_point)
+        for (int k : pv.second) {
+            const MRange r = range_of_M[pv.first.second];
+            lp[(size_t)k].assign((size_t)(r.s_hi - r.s_lo), 0.0);
+            ScoreJob j;
+            j.h = &models[(size_t)k];
+            j.s_lo = r.s_lo;
+            j.s_hi = r.s_hi;
+            j.log_prob = lp[(size_t)k].data();
+            jobs.push_back(j);
+        }
+    // ECOZ2_VQ_GPUS workers, each scoring a contiguous share of every point's sequences (independent: the scores are
+    // the single worker's bit for bit)
+    int max_S = 1;
+    for (const auto& mv : by_M) max_S = std::max(max_S, (int)mv.second.size());
+    const int workers = std::min(env_workers(), max_S), ndev = device_count();
+    if (!ndev) return 1;
+    if (run_workers(workers, [&](int w) -> int {
+            std::vector<ScoreJob> mine;
+            for (const ScoreJob& j : jobs) {
+                i64 a, b;
+                split_range(j.S(), workers, w, &a, &b);
+                if (a >= b) continue;
+                ScoreJob q = j;
+                q.s_lo = j.s_lo + (int)a;
+                q.s_hi = j.s_lo + (int)b;
+                q.log_prob = j.log_prob + a;
+                mine.push_back(q);
+            }
+            if (mine.empty()) return 0;
+            if (require_device(worker_device(env_device(), w, ndev))) return 1;
+            return score_grid_batch(mine.data(), (int)mine.size(), store);
+        }))
+        return 1;
+    std::string summary = "N,M,models,sequences,accuracy,avg_accuracy\n";
+    std::vector<std::string> lines;
+    for (const auto& pv : by_point) {
+        const int N = pv.first.first, M = pv.first.second;
+        const std::vector<int>& seq_ids = by_M[M];
+        const size_t K = pv.second.size(), S = seq_ids.size();
+        std::vector<Hmm> point_models;
+        std::vector<std::string> files, classes;
+        std::vector<double> point_lp(S * K);
+        for (size_t k = 0; k < K; ++k) {
+            point_models.push_back(models[(size_t)pv.second[k]]);
+            for (size_t s = 0; s < S; ++s) point_lp[s * K + k] = lp[(size_t)pv.second[k]][s];
+        }
+        for (int i : seq_ids) {
+            files.push_back(ss.files[(size_t)i]);
+            classes.push_back(ss.classes[(size_t)i]);
+        }
+        printf("grid point: N=%d M=%d\n", N, M);
+        std::string csv;
+        if (classification_dir && *classification_dir)
+            csv = std::string(classification_dir) + "/N" + std::to_string(N) + "__M" + std::to_string(M) + ".csv";
+        ReportFigures fig;
+        if (classify_report(point_models, files, classes, point_lp, M, show_ranked != 0, csv.empty() ? nullptr : csv.c_str(), &fig)) return 1;
+        char b[160];
+        snprintf(b, sizeof b, "  N=%-4d M=%-5d models=%-4zu sequences=%-6zu accuracy=%.2f avg_accuracy=%.2f\n", N, M, K, fig.classified,
+                 (double)fig.accuracy, (double)fig.avg_accuracy);
+        lines.push_back(b);
+        snprintf(b, sizeof b, "%d,%d,%zu,%zu,%.9g,%.9g\n", N, M, K, fig.classified, (double)fig.accuracy, (double)fig.avg_accuracy);
+        summary += b;
+    }
+    printf("\ngrid summary: %zu point(s)\n", lines.size());
+    for (const std::string& l : lines) printf("%s", l.c_str());
+    if (summary_filename && *summary_filename) {
+        if (write_file(summary_filename, std::vector<unsigned char>(summary.begin(), summary.end()))) return 1;
+        printf("%s saved\n", summary_filename);
+    }
+    return 0;
 }
 
 // fn ecoz2_hmm_classify_predictors(model_filenames, num_models: c_uint, cb_filenames, num_codebooks: c_int,
@@ -1827,6 +2133,57 @@ extern "C" int e2vq_hmm_score(int device, int K, const int* Ns, int M, const dou
         if (log_probs) log_probs[i] = lp[i];
     }
     return 0;
+}
+
+// scaled forward scores of K models of any (N, M) in one batch: model k has Ns[k] states and Ms[k]
+// symbols, its pi | A | B at params + param_offs[k], and scores the sequences [seq_lo[k], seq_hi[k]) (ranges may overlap;
+// the symbols go to the device once); the result of sequence s at out_offs[k] + (s - seq_lo[k]) of mant / exp2 / status /
+// log_probs (output ranges may not overlap).  Each result is e2vq_hmm_score's for that pair, bit for bit.  A symbol >= M_k
+// is not refused: it scores status 2.
+extern "C" int e2vq_hmm_score_grid(int device, int K, const int* Ns, const int* Ms, const double* params, const int64_t* param_offs,
+                                   const uint16_t* sym, const int64_t* offs, int S, const int64_t* seq_lo, const int64_t* seq_hi,
+                                   const int64_t* out_offs, double* mant, int64_t* exp2, int* status, double* log_probs)
+{
+    if (K < 1 || !Ns || !Ms || !params || !param_offs || !seq_lo || !seq_hi || !out_offs)
+        return e2vq_set_error("e2vq_hmm_score_grid: bad arguments (K = %d)", K);
+    if (!log_probs) return e2vq_set_error("e2vq_hmm_score_grid: log_probs is required");
+    if (check_offsets(offs, S)) return 1;
+    std::vector<std::pair<i64, i64>> outs;  // (offset, end) of each model's results
+    for (int k = 0; k < K; ++k) {
+        const int N = Ns[k], M = Ms[k];
+        if (N < 1 || N > e2hmm::MAX_N || M < 1 || M > 65536) return e2vq_set_error("model %d: HMM with N=%d M=%d out of range", k, N, M);
+        if (seq_lo[k] < 0 || seq_lo[k] >= seq_hi[k] || seq_hi[k] > S)
+            return e2vq_set_error("model %d: sequence range [%lld, %lld) not a non-empty part of [0, %d)", k, (long long)seq_lo[k],
+                                  (long long)seq_hi[k], S);
+        if (param_offs[k] < 0) return e2vq_set_error("model %d: parameter offset %lld < 0", k, (long long)param_offs[k]);
+        if (out_offs[k] < 0) return e2vq_set_error("model %d: output offset %lld < 0", k, (long long)out_offs[k]);
+        outs.emplace_back(out_offs[k], out_offs[k] + (seq_hi[k] - seq_lo[k]));
+    }
+    std::sort(outs.begin(), outs.end());
+    for (size_t i = 1; i < outs.size(); ++i)
+        if (outs[i].first < outs[i - 1].second)
+            return e2vq_set_error("output ranges overlap: [%lld, %lld) and [%lld, %lld)", (long long)outs[i - 1].first,
+                                  (long long)outs[i - 1].second, (long long)outs[i].first, (long long)outs[i].second);
+    std::vector<Hmm> models((size_t)K);
+    std::vector<ScoreJob> jobs((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        const int N = Ns[k];
+        const double* q = params + param_offs[k];
+        if (model_from_arrays(N, Ms[k], q, q + N, q + N + (size_t)N * N, models[(size_t)k])) return 1;
+        ScoreJob& j = jobs[(size_t)k];
+        j.h = &models[(size_t)k];
+        j.s_lo = (int)seq_lo[k];
+        j.s_hi = (int)seq_hi[k];
+        j.log_prob = log_probs + out_offs[k];
+        j.mant = mant ? mant + out_offs[k] : nullptr;
+        j.exp2 = exp2 ? exp2 + out_offs[k] : nullptr;
+        j.status = status ? status + out_offs[k] : nullptr;
+    }
+    if (require_device(device)) return 1;
+    SeqStore store;
+    store.sym = sym;
+    store.offs = (const i64*)offs;
+    return score_grid_batch(jobs.data(), K, store);
 }
 
 extern "C" int64_t e2vq_hmm_acc_words(int N, int M) { return e2hmm::acc_words(N, M); }

@@ -51,6 +51,9 @@ _sig("e2vq_hmm_learn_grid", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, c_cha
      C.c_int, HMM_LEARN_CALLBACK)
 _sig("e2vq_hmm_train_grid", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p)
+_sig("e2vq_hmm_classify_grid", C.c_int, c_char_pp, C.c_uint, c_char_pp, C.c_uint, C.c_int, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_score_grid", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 def _strs(items):
@@ -97,6 +100,18 @@ def hmm_classify_sequences(model_filenames, sequence_filenames, show_ranked=Fals
     s, _k2 = _strs(sequence_filenames)
     check(lib.ecoz2_hmm_classify(m, len(model_filenames), s, len(sequence_filenames), int(show_ranked),
                                  str(classification_filename).encode() if classification_filename else None))
+
+
+def hmm_classify_grid(model_filenames, sequence_filenames, show_ranked=False, classification_dir=None,
+                      summary_filename=None):
+    """`hmm classify --grid` (DESIGN.md 4.8.4): every (N, M) point of the given models classified in one batched scoring;
+    per point the report (and CSV, as <classification_dir>/N<n>__M<m>.csv) of hmm_classify_sequences on that point's
+    models and sequences, then the summary of the sweep (and its CSV)"""
+    m, _k1 = _strs(model_filenames)
+    s, _k2 = _strs(sequence_filenames)
+    check(lib.e2vq_hmm_classify_grid(m, len(model_filenames), s, len(sequence_filenames), int(show_ranked),
+                                     str(classification_dir).encode() if classification_dir else None,
+                                     str(summary_filename).encode() if summary_filename else None))
 
 
 def hmm_classify_predictors(model_filenames, cb_filenames, prd_filenames, show_ranked=False,
@@ -163,6 +178,35 @@ def score(models, seqs, device=0):
     check(lib.e2vq_hmm_score(device, K, Ns, ms[0][2].shape[1], ptr(0), ptr(1), ptr(2), sym.ctypes.data, offs.ctypes.data,
                              S, mant.ctypes.data, ex.ctypes.data, st.ctypes.data, lp.ctypes.data))
     return dict(mant=mant, exp2=ex, status=st, log_prob=lp)
+
+
+def score_grid(models, seqs, ranges, device=0):
+    """scores of K models of any (N, M) in one batch: models = [(pi, A, B)], seqs = [uint16 arrays]
+    shared by all, ranges = [(lo, hi)] the sequences seqs[lo:hi] model k scores (ranges may overlap) -> per model a dict
+    of (hi - lo,) arrays mant / exp2 / status / log_prob, each as `score` of that model on its slice"""
+    K = len(models)
+    if K != len(ranges):
+        raise ValueError(f"{K} models for {len(ranges)} sequence ranges")
+    ms = [tuple(np.asarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = np.array([len(m[0]) for m in ms], dtype=np.int32)
+    Ms = np.array([m[2].shape[1] if m[2].ndim == 2 else 0 for m in ms], dtype=np.int32)
+    sizes = [m[0].size + m[1].size + m[2].size for m in ms]
+    param_offs = np.zeros(K, dtype=np.int64)
+    param_offs[1:] = np.cumsum(sizes)[:-1]
+    params = np.ascontiguousarray(np.concatenate([np.concatenate([x.ravel() for x in m]) for m in ms]))
+    sym, offs = _pack(seqs)
+    lo = np.array([r[0] for r in ranges], dtype=np.int64)
+    hi = np.array([r[1] for r in ranges], dtype=np.int64)
+    out_offs = np.zeros(K, dtype=np.int64)
+    out_offs[1:] = np.cumsum(np.maximum(hi - lo, 0))[:-1]
+    n = max(int(np.maximum(hi - lo, 0).sum()), 1)
+    mant, ex = np.zeros(n), np.zeros(n, dtype=np.int64)
+    st, lp = np.zeros(n, dtype=np.int32), np.zeros(n)
+    check(lib.e2vq_hmm_score_grid(device, K, Ns.ctypes.data, Ms.ctypes.data, params.ctypes.data, param_offs.ctypes.data,
+                                  sym.ctypes.data, offs.ctypes.data, len(seqs), lo.ctypes.data, hi.ctypes.data,
+                                  out_offs.ctypes.data, mant.ctypes.data, ex.ctypes.data, st.ctypes.data, lp.ctypes.data))
+    return [dict(mant=mant[o:o + h - l].copy(), exp2=ex[o:o + h - l].copy(), status=st[o:o + h - l].copy(),
+                 log_prob=lp[o:o + h - l].copy()) for o, l, h in zip(out_offs, lo, hi)]
 
 
 def estep(pi, A, B, seqs, device=0):

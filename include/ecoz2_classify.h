@@ -206,6 +206,33 @@ int e2vq_hmm_train_grid(int device, int K, const int *Ns, const int *Ms, double 
                         double epsilon, double val_auto, int max_iterations, double *sum_log_prob, int cap,
                         int *num_esteps);
 
+/* ---- classification at every (N, M) point of a sweep in one batched scoring -----------------------
+ * `hmm classify --grid`: a grid point is an (N, M) for which at least one model is given; points in order of N, then M.
+ * A point's models are the given .hmm files with that header, in list order; its sequences the given .seq files with
+ * header M, in list order.  Every sequence is scored under every model of every point in one batch (k_hmm_score_grid:
+ * floor(64 / N) models of a point to a wave for N <= 21); each score is ecoz2_hmm_classify's bit for bit.  Stdout:
+ * per point the line "grid point: N=<n> M=<m>" followed byte for byte by what ecoz2_hmm_classify(<the point's models>,
+ * <the point's sequences>, show_ranked, <dir>/N<n>__M<m>.csv) prints, then a block "grid summary: <points> point(s)"
+ * with one line per point: N, M, models, sequences classified, accuracy and avg_accuracy (%.2f).  classification_dir
+ * (may be NULL): each point's CSV as <dir>/N<n>__M<m>.csv, the bytes ecoz2_hmm_classify writes.  summary_filename (may
+ * be NULL): a CSV "N,M,models,sequences,accuracy,avg_accuracy" with one row per point (%.9g for the two floats).
+ * An empty model or sequence list, a class name that occurs twice among a point's models, a point with no sequence of its
+ * M and a sequence whose M no model has return 1 before any HIP call, and no file is written.  ECOZ2_VQ_GPUS = W deals
+ * each point's sequences to W workers in contiguous shares; it changes no byte. */
+int e2vq_hmm_classify_grid(const char *const *model_filenames, unsigned num_models,
+                           const char *const *sequence_filenames, unsigned num_sequences, int show_ranked,
+                           const char *classification_dir, const char *summary_filename);
+/* the same scoring on arrays: K models, model k with Ns[k] states and Ms[k] symbols, its pi | A | B at
+ * params + param_offs[k], scored on the sequences [seq_lo[k], seq_hi[k]) of offs (non-empty; ranges may overlap, the
+ * symbols go to the device once).  The result of sequence s under model k is at index out_offs[k] + (s - seq_lo[k]) of
+ * mant / exp2 / status (each may be NULL) and log_probs; the output ranges may not overlap.  Consecutive models of equal
+ * (N, M, range) are scored together.  Each result equals e2vq_hmm_score's for that pair, bit for bit.  K < 1, an N or M
+ * out of range, a bad sequence range and overlapping output ranges are refused before the device; a symbol >= M_k is
+ * not: it scores status 2. */
+int e2vq_hmm_score_grid(int device, int K, const int *Ns, const int *Ms, const double *params, const int64_t *param_offs,
+                        const uint16_t *sym, const int64_t *offs, int S, const int64_t *seq_lo, const int64_t *seq_hi,
+                        const int64_t *out_offs, double *mant, int64_t *exp2, int *status, double *log_probs);
+
 /* Viterbi decoding of S sequences under one model: logarithms of the parameters taken on the host
  * (log 0 = -inf; a negative, NaN or infinite parameter is refused), maximisation on the GPU.  log_prob[s] = ln P*,
  * status[s]: 0 ok, 1 ln P* = -inf (the model cannot emit the sequence; the path is still written), 2 a symbol >= M
