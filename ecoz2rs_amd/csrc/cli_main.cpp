@@ -59,6 +59,10 @@ static int usage()
             "  ecoz2 hmm classify --grid [-r] [-c|--c12n <dir>] [--summary <file.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST>\n"
             "                  [-M <m1,m2,...>] -s|--sequences <files|dirs|tt.csv>...   (every (N, M) of the models, scored together;\n"
             "                  a tt.csv needs -M)\n"
+            "  ecoz2 hmm scan -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15] --window <frames>\n"
+            "                  [--hop <frames>] [--min-margin <x>] [-c <csv dir|file.csv>]\n"
+            "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
+            "                  (where in each recording every class occurs: the models over sliding windows; --hop defaults to --window)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -750,10 +754,77 @@ static int hmm_classify_grid(const std::string& m_arg, const std::string& cls, c
     return 0;
 }
 
+// `hmm scan`: the trained models over sliding windows of whole recordings
+static int hmm_scan_cmd(int argc, char** argv)
+{
+    int P = 36, W = 45, O = 15;
+    long long window = 0, hop = 0;
+    double min_margin = 0.0;
+    std::string codebook, csv;
+    std::vector<std::string> models, signals, predictors, sequences;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        auto num = [&](const char* name) -> long long {
+            const char* v = val(name);
+            char* end = nullptr;
+            const long long x = strtoll(v, &end, 10);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto many = [&](std::vector<std::string>& v) { while (i + 1 < argc && !is_flag(argv[i + 1])) v.push_back(argv[++i]); };
+        if (a == "-m" || a == "--models") many(models);
+        else if (a == "--codebook") codebook = val("--codebook");
+        else if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
+        else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
+        else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "--window") window = num("--window");
+        else if (a == "--hop") hop = num("--hop");
+        else if (a == "--min-margin") min_margin = atof(val("--min-margin"));
+        else if (a == "-c" || a == "--csv") csv = val("-c");
+        else if (a == "--signals") many(signals);
+        else if (a == "--predictors") many(predictors);
+        else if (a == "-s" || a == "--sequences") many(sequences);
+        else return usage();
+    }
+    if (models.empty()) { fprintf(stderr, "hmm scan: --models <files|dirs>... is required\n"); return usage(); }
+    if ((int)!signals.empty() + (int)!predictors.empty() + (int)!sequences.empty() != 1) {
+        fprintf(stderr, "hmm scan: exactly one of --signals, --predictors and --sequences is required\n");
+        return usage();
+    }
+    if (window < 1) { fprintf(stderr, "hmm scan: --window <frames> is required and at least 1\n"); return 2; }
+    if (hop == 0) hop = window;
+    if (hop < 1) { fprintf(stderr, "hmm scan: --hop %lld: at least 1\n", hop); return 2; }
+    if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
+    if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
+    if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm scan: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    std::vector<std::string> hmm_files, inputs;
+    e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    const int rc = !signals.empty() ? e2vq_io::resolve_filenames(signals, ".wav", inputs)
+                   : !predictors.empty() ? e2vq_io::resolve_filenames(predictors, ".prd", inputs)
+                                         : e2vq_io::resolve_filenames(sequences, ".seq", inputs);
+    if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+    if (inputs.empty()) { printf("No inputs given\n"); return 0; }
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
+    auto pm = cptrs(hmm_files), pi = cptrs(inputs);
+    if (e2vq_hmm_scan_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(), (int)pi.size(), P,
+                            W, O, window, hop, min_margin, csv.empty() ? nullptr : csv.c_str())) {
+        printf("%s\n", e2vq_last_error());
+        return 1;
+    }
+    return 0;
+}
+
 static int hmm_cmd(int argc, char** argv)
 {
     if (argc < 1) return usage();
     const std::string cmd = argv[0];
+    if (cmd == "scan") return hmm_scan_cmd(argc - 1, argv + 1);
     int N = 5, M = -1, type = 3, max_iterations = -1;
     double epsilon = 1e-05, val_auto = 0.3;
     long seed = -1;

@@ -44,6 +44,31 @@ int score_grid_workgroups(int S);
 void launch_score_grid(const ScoreModelDev* models, const ScorePackDev* packs, int N, int G, const int* blocks, int nblocks,
                        const unsigned short* sym, const long long* offs, double* mant, long long* exp2, int* status,
                        hipStream_t st);
+// Window scan (hmm_scan.hip).  One window: `len` symbols of stream `stream` from its frame `first` on.
+// One run: the windows [w0, w0 + count) of the table -- of one stream, starting in non-decreasing order, the last one
+// ending last -- which one workgroup scores from one staged copy of the symbols they cover.
+struct ScanWin {
+    int stream, len;
+    long long first;
+};
+struct ScanRun {
+    int w0, count;
+};
+constexpr int SCAN_SPAN_CAP = 8192;  // symbols of a run staged in LDS (16 KB next to at most 32 KB of A)
+int scan_waves();                    // waves of a k_hmm_scan workgroup: each takes G windows of the run at a time
+// Scores every window of the runs under the nk models models[ks[0 .. nk)] of ONE N <= WAVE_N, G windows to a wave
+// (1 <= G <= floor(64 / N)); results at [w * K + k] as launch_score's.  span_lds <= SCAN_SPAN_CAP: the longest span among the
+// runs, all of which are staged; 0: none is (the symbols are read from global memory).  offs: the streams' S + 1 symbol offsets.
+void launch_scan(const ModelDev* models, const int* ks, int nk, int K, int N, int G, const ScanWin* wins, const ScanRun* runs,
+                 int nruns, int span_lds, const unsigned short* sym, const long long* offs, double* mant, long long* exp2,
+                 int* status, hipStream_t st);
+// the same for models of more than WAVE_N states (maxN: the largest among them): a workgroup per (window, model)
+void launch_scan_wg(const ModelDev* models, const int* ks, int nk, int K, int maxN, const ScanWin* wins, long long W,
+                    const unsigned short* sym, const long long* offs, double* mant, long long* exp2, int* status, hipStream_t st);
+// best and second-best model of each of the W windows from the W x K results: top[2 w], top[2 w + 1] (second -1 when K = 1),
+// their P at tmant / texp[2 w], [2 w + 1] (0, 0 where the status is not 0); ties as `hmm classify` ranks them
+void launch_scan_top2(const double* mant, const long long* exp2, const int* status, long long W, int K, int* top, double* tmant,
+                      long long* texp, hipStream_t st);
 // Baum-Welch E-step of one model over S sequences (expected counts added to acc; per-sequence P(O) and status out).
 // alpha_buf: total_symbols x N doubles, c_buf: total_symbols doubles (scratch).
 // scratch (N > WAVE_N only; may be null otherwise): fb_scratch_words(N) int64 words, contents irrelevant

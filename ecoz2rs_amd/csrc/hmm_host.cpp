@@ -1257,6 +1257,197 @@ int score_grid_batch(const ScoreJob* jobs, int K, const SeqStore& ss)
     return 0;
 }
 
+// ---- hmm scan: the trained models over the windows of whole recordings ------------------------------------
+// windows of `window` frames every `hop` frames: stream s of T_s symbols has (T_s - window) / hop + 1 of them when
+// T_s >= window, else none (a trailing incomplete window is dropped); win_offs: S + 1 entries
+void scan_window_offsets(const i64* offs, int S, i64 window, i64 hop, i64* win_offs)
+{
+    win_offs[0] = 0;
+    for (int s = 0; s < S; ++s) {
+        const i64 T = offs[s + 1] - offs[s];
+        win_offs[s + 1] = win_offs[s] + (T >= window ? (T - window) / hop + 1 : 0);
+    }
+}
+
+int scan_check_geometry(const char* who, i64 window, i64 hop)
+{
+    if (window < 1) return e2vq_set_error("%s: window of %lld frames (at least 1)", who, (long long)window);
+    if (window > (1 << 30)) return e2vq_set_error("%s: window of %lld frames (at most 2^30)", who, (long long)window);
+    if (hop < 1) return e2vq_set_error("%s: hop of %lld frames (at least 1)", who, (long long)hop);
+    return 0;
+}
+
+// windows to a wave: floor(64 / N) where that is at least 3 (N <= SCAN_PACK_MAX_N), else one -- two windows to a wave measured
+// between 1.4 % faster (N = 22) and 3 % slower (N = 28, 32) than one (DESIGN.md 4.8.5's table).
+// ECOZ2_HMM_SCAN_PACK=0 scores one window per wave at every N, =1 packs floor(64 / N) at every N <= 32 (the other arms of
+// tools/hmm_scan_bench.py and of the tests; the bits are the same)
+constexpr int SCAN_PACK_MAX_N = 21;
+int scan_pack_width_in_use(int N)
+{
+    const char* v = getenv("ECOZ2_HMM_SCAN_PACK");
+    if (v && *v) return atoi(v) == 0 || N > 32 ? 1 : e2hmm::WAVE_N / N;
+    return N <= SCAN_PACK_MAX_N ? e2hmm::WAVE_N / N : 1;
+}
+
+// rounds of (waves x G) windows a k_hmm_scan workgroup takes from one staging of A and the symbols
+// (ECOZ2_HMM_SCAN_ROUNDS, 1 .. 64; changes no bit)
+int scan_rounds()
+{
+    const int r = e2vq_env_int("ECOZ2_HMM_SCAN_ROUNDS", 4);
+    return r < 1 ? 1 : (r > 64 ? 64 : r);
+}
+
+thread_local float g_scan_kernel_ms = -1.f;  // e2vq_hmm_scan_last_kernel_ms
+
+struct ScanOut {  // any may be null; matrices W x K, the others W
+    double* mant = nullptr;
+    int64_t* exp2 = nullptr;
+    int* status = nullptr;
+    double* log_probs = nullptr;
+    int* best = nullptr;
+    double* best_log_prob = nullptr;
+    int* second = nullptr;
+    double* second_log_prob = nullptr;
+    bool matrix() const { return mant || exp2 || status || log_probs; }
+    bool top() const { return best || best_log_prob || second || second_log_prob; }
+};
+
+// Scores every window of the S device-resident streams (h_offs: their S + 1 offsets, on the host) under the models, on the
+// current device and the stream st.  Models of one N <= 64 go into one k_hmm_scan launch over runs of at most
+// waves x G x rounds windows whose span fits the staging area; models of more states through k_hmm_scan_wg; then
+// k_scan_top2.  One copy back: two results per window, and the W x K matrix only when `out` asks for it.
+int scan_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* h_offs, int S, i64 window, i64 hop,
+                hipStream_t st, const ScanOut& out)
+{
+    const int K = (int)ms.size();
+    std::vector<i64> win_offs((size_t)S + 1);
+    scan_window_offsets(h_offs, S, window, hop, win_offs.data());
+    const i64 W = win_offs[(size_t)S];
+    if (W == 0) return 0;
+    if (W > (i64)INT32_MAX - 64 || W * K > ((i64)1 << 40)) return e2vq_set_error("hmm scan: %lld windows x %d models", (long long)W, K);
+    std::vector<e2hmm::ScanWin> wins((size_t)W);
+    for (int s = 0; s < S; ++s)
+        for (i64 i = 0, n = win_offs[(size_t)s + 1] - win_offs[(size_t)s]; i < n; ++i)
+            wins[(size_t)(win_offs[(size_t)s] + i)] = e2hmm::ScanWin{s, (int)window, i * hop};
+    // runs of at most `cap` windows, stream by stream
+    auto make_runs = [&](i64 cap, std::vector<e2hmm::ScanRun>& runs) {
+        for (int s = 0; s < S; ++s)
+            for (i64 w = win_offs[(size_t)s]; w < win_offs[(size_t)s + 1]; w += cap)
+                runs.push_back(e2hmm::ScanRun{(int)w, (int)std::min<i64>(cap, win_offs[(size_t)s + 1] - w)});
+    };
+    std::map<int, std::vector<int>> by_N;  // models of N <= 64 states, by N
+    std::vector<int> big;                  // the others
+    int big_N = 0;
+    for (int k = 0; k < K; ++k) {
+        if (ms[(size_t)k]->N > e2hmm::WAVE_N) {
+            big.push_back(k);
+            big_N = std::max(big_N, ms[(size_t)k]->N);
+        } else {
+            by_N[ms[(size_t)k]->N].push_back(k);
+        }
+    }
+    struct Launch {
+        int N, G, span_lds, ks_at, nk, runs_at, nruns;
+    };
+    std::vector<Launch> launches;
+    std::vector<int> ks;
+    std::vector<e2hmm::ScanRun> runs;
+    const int rounds = scan_rounds();
+    for (const auto& kv : by_N) {
+        const int N = kv.first, G = scan_pack_width_in_use(N);
+        i64 cap = (i64)e2hmm::scan_waves() * G * rounds;
+        // (a window longer than the staging area is read from global memory; shorter ones: as many as fit)
+        if (window <= e2hmm::SCAN_SPAN_CAP) cap = std::min<i64>(cap, (e2hmm::SCAN_SPAN_CAP - window) / hop + 1);
+        const i64 span = (std::min<i64>(cap, W) - 1) * hop + window;
+        Launch l{N, G, (int)(span <= e2hmm::SCAN_SPAN_CAP ? span : 0), (int)ks.size(), (int)kv.second.size(), (int)runs.size(), 0};
+        ks.insert(ks.end(), kv.second.begin(), kv.second.end());
+        make_runs(cap, runs);
+        l.nruns = (int)runs.size() - l.runs_at;
+        launches.push_back(l);
+    }
+    const int big_at = (int)ks.size();
+    ks.insert(ks.end(), big.begin(), big.end());
+
+    DevModels dm;
+    if (dm.upload(ms, st)) return 1;
+    DeviceBuffer<e2hmm::ScanWin> d_wins;
+    DeviceBuffer<e2hmm::ScanRun> d_runs;
+    DeviceBuffer<int> d_ks, d_st, d_top;
+    DeviceBuffer<i64> d_offs, d_exp, d_texp;
+    DeviceBuffer<double> d_mant, d_tmant;
+    const size_t n = (size_t)W * K;
+    if (d_wins.upload(wins.data(), wins.size(), st) || d_runs.upload(runs.data(), runs.size(), st) ||
+        d_ks.upload(ks.data(), ks.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) || d_mant.reserve(n) || d_exp.reserve(n) ||
+        d_st.reserve(n) || d_top.reserve((size_t)2 * W) || d_tmant.reserve((size_t)2 * W) || d_texp.reserve((size_t)2 * W))
+        return 1;
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    for (const Launch& l : launches) {
+        e2hmm::launch_scan(dm.table.get(), d_ks.get() + l.ks_at, l.nk, K, l.N, l.G, d_wins.get(), d_runs.get() + l.runs_at, l.nruns,
+                           l.span_lds, d_sym, d_offs.get(), d_mant.get(), d_exp.get(), d_st.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    if (!big.empty()) {
+        e2hmm::launch_scan_wg(dm.table.get(), d_ks.get() + big_at, (int)big.size(), K, big_N, d_wins.get(), W, d_sym, d_offs.get(),
+                              d_mant.get(), d_exp.get(), d_st.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    e2hmm::launch_scan_top2(d_mant.get(), d_exp.get(), d_st.get(), W, K, d_top.get(), d_tmant.get(), d_texp.get(), st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    std::vector<int> top, stat;
+    std::vector<double> tmant, mant;
+    std::vector<i64> texp, ex;
+    if (out.top()) {
+        top.resize((size_t)2 * W);
+        tmant.resize((size_t)2 * W);
+        texp.resize((size_t)2 * W);
+        HIPCHK(hipMemcpyAsync(top.data(), d_top.get(), top.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(tmant.data(), d_tmant.get(), tmant.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(texp.data(), d_texp.get(), texp.size() * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (out.matrix()) {
+        mant.resize(n);
+        ex.resize(n);
+        stat.resize(n);
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_st.get(), n * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_scan_kernel_ms)) return 1;
+    if (out.top())
+        for (i64 w = 0; w < W; ++w) {
+            const size_t a = (size_t)2 * w, b = a + 1;
+            if (out.best) out.best[w] = top[a];
+            if (out.second) out.second[w] = top[b];
+            if (out.best_log_prob) out.best_log_prob[w] = log_prob(tmant[a], texp[a]);
+            if (out.second_log_prob) out.second_log_prob[w] = log_prob(tmant[b], texp[b]);
+        }
+    if (out.matrix())
+        for (size_t i = 0; i < n; ++i) {
+            if (out.mant) out.mant[i] = mant[i];
+            if (out.exp2) out.exp2[i] = ex[i];
+            if (out.status) out.status[i] = stat[i];
+            if (out.log_probs) out.log_probs[i] = stat[i] == 0 ? log_prob(mant[i], ex[i]) : -INFINITY;
+        }
+    return 0;
+}
+
+std::string fmt_17g(double v)
+{
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+bool ends_with(const std::string& s, const char* ext)
+{
+    const size_t n = strlen(ext);
+    return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
+}
+
 }  // namespace
 
 // ==========================================================================================
@@ -2347,4 +2538,269 @@ extern "C" int e2vq_hmm_viterbi(int device, int N, int M, const double* pi, cons
     if (st.create()) return 1;
     if (d_sym.upload(sym, (size_t)offs[S], st.s) || d_offs.upload((const i64*)offs, (size_t)S + 1, st.s)) return 1;
     return viterbi_device(N, M, lflat, d_sym.get(), d_offs.get(), (const i64*)offs, S, st.s, path, log_prob, status);
+}
+
+// ---- hmm scan -----------------------------------------------------------------------------------------
+// window count of every stream (host only): win_offs[S + 1]
+extern "C" int e2vq_hmm_scan_windows(const int64_t* offs, int S, int64_t window_frames, int64_t hop_frames, int64_t* win_offs)
+{
+    if (scan_check_geometry("e2vq_hmm_scan_windows", window_frames, hop_frames)) return 1;
+    if (!win_offs) return e2vq_set_error("e2vq_hmm_scan_windows: bad arguments");
+    if (check_offsets(offs, S)) return 1;
+    scan_window_offsets((const i64*)offs, S, window_frames, hop_frames, (i64*)win_offs);
+    return 0;
+}
+
+extern "C" int e2vq_hmm_scan_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_scan_last_kernel_ms: bad arguments");
+    *ms = g_scan_kernel_ms;
+    return 0;
+}
+
+// every window of S streams under K models sharing M: each result is e2vq_hmm_score's for the window's symbols, bit for bit
+extern "C" int e2vq_hmm_scan(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                             const double* const* Bs, const void* sym, const int64_t* offs, int S, int64_t window_frames,
+                             int64_t hop_frames, int64_t* win_offs, double* mant, int64_t* exp2, int* status, double* log_probs,
+                             int* best, double* best_log_prob, int* second, double* second_log_prob, int sym_on_device)
+{
+    if (scan_check_geometry("e2vq_hmm_scan", window_frames, hop_frames)) return 1;
+    if (K < 1) return e2vq_set_error("e2vq_hmm_scan: %d models (at least 1)", K);
+    if (!Ns || !pis || !As || !Bs || S < 0 || (!sym && S > 0 && offs && offs[S] > 0)) return e2vq_set_error("e2vq_hmm_scan: bad arguments");
+    for (int k = 0; k < K; ++k)
+        if (Ns[k] < 1 || Ns[k] > e2hmm::MAX_N)
+            return e2vq_set_error("e2vq_hmm_scan: model %d has N=%d states (1 .. %d)", k, Ns[k], e2hmm::MAX_N);
+    std::vector<Hmm> models((size_t)K);
+    std::vector<const Hmm*> ms;
+    for (int k = 0; k < K; ++k) {
+        if (model_from_arrays(Ns[k], M, pis[k], As[k], Bs[k], models[(size_t)k])) return 1;
+        ms.push_back(&models[(size_t)k]);
+    }
+    if (check_offsets(offs, S)) return 1;
+    std::vector<i64> wo((size_t)S + 1);
+    scan_window_offsets((const i64*)offs, S, window_frames, hop_frames, wo.data());
+    if (win_offs) memcpy(win_offs, wo.data(), wo.size() * 8);
+    if (require_device(device)) return 1;
+    DeviceBuffer<unsigned short> d_sym;
+    Stream st;
+    if (st.create()) return 1;
+    if (!sym_on_device && d_sym.upload((const unsigned short*)sym, (size_t)offs[S], st.s)) return 1;
+    ScanOut out;
+    out.mant = mant, out.exp2 = exp2, out.status = status, out.log_probs = log_probs;
+    out.best = best, out.best_log_prob = best_log_prob, out.second = second, out.second_log_prob = second_log_prob;
+    return scan_device(ms, sym_on_device ? (const unsigned short*)sym : d_sym.get(), (const i64*)offs, S, window_frames, hop_frames,
+                       st.s, out);
+}
+
+// CSV and stdout block of one scanned input from its two results per window (host only)
+extern "C" int e2vq_hmm_scan_report(const char* name, int64_t T, int K, const char* const* class_names, int64_t W,
+                                    int64_t window_frames, int64_t hop_frames, int W_ms, int O_ms, const int* best,
+                                    const double* best_log_prob, const int* second, const double* second_log_prob,
+                                    double min_margin, const char* csv_filename)
+{
+    FlushStdout flush_on_return;
+    if (!name || K < 1 || !class_names || W < 0 || (W > 0 && (!best || !best_log_prob || !second || !second_log_prob)))
+        return e2vq_set_error("e2vq_hmm_scan_report: bad arguments");
+    if (scan_check_geometry("e2vq_hmm_scan_report", window_frames, hop_frames)) return 1;
+    for (int64_t w = 0; w < W; ++w)
+        if (best[w] < 0 || best[w] >= K || second[w] < -1 || second[w] >= K)
+            return e2vq_set_error("e2vq_hmm_scan_report: window %lld names a model outside [0, %d)", (long long)w, K);
+    auto begin_s = [&](int64_t w) { return (double)(w * hop_frames * O_ms) / 1000.0; };
+    // (the end of the analysis window of the window's last frame)
+    auto end_s = [&](int64_t w) { return (double)((w * hop_frames + window_frames - 1) * O_ms + W_ms) / 1000.0; };
+    if (csv_filename && *csv_filename) {
+        std::string doc = "window,begin_frame,end_frame,begin_s,end_s,class,log_prob,second_class,second_log_prob\n";
+        for (int64_t w = 0; w < W; ++w) {
+            const bool has1 = best_log_prob[w] > -INFINITY, has2 = second[w] >= 0 && second_log_prob[w] > -INFINITY;
+            doc += std::to_string(w) + "," + std::to_string(w * hop_frames) + "," + std::to_string(w * hop_frames + window_frames) + "," +
+                   fmt_17g(begin_s(w)) + "," + fmt_17g(end_s(w)) + "," + (has1 ? class_names[best[w]] : "") + "," +
+                   fmt_17g(best_log_prob[w]) + "," + (has2 ? class_names[second[w]] : "") + "," +
+                   fmt_17g(second[w] >= 0 ? second_log_prob[w] : -INFINITY) + "\n";
+        }
+        if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
+    }
+    printf("%s: T=%lld  windows=%lld  (window %lld frames, hop %lld)\n", name, (long long)T, (long long)W, (long long)window_frames,
+           (long long)hop_frames);
+    std::vector<int64_t> won((size_t)K, 0);
+    int64_t none = 0;
+    for (int64_t w = 0; w < W; ++w) {
+        if (best_log_prob[w] > -INFINITY) ++won[(size_t)best[w]];
+        else ++none;
+    }
+    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)won[(size_t)k]);
+    if (none) printf("  (no model can emit the window): %lld\n", (long long)none);
+    printf("  runs (margin >= %g):\n", min_margin);
+    // maximal runs of consecutive windows won by one class with margin >= min_margin (a window no model can emit wins nothing)
+    auto winner = [&](int64_t w) -> int {
+        if (!(best_log_prob[w] > -INFINITY)) return -1;
+        const double second_lp = second[w] >= 0 ? second_log_prob[w] : -INFINITY;
+        return best_log_prob[w] - second_lp >= min_margin ? best[w] : -1;
+    };
+    for (int64_t w = 0; w < W;) {
+        const int c = winner(w);
+        int64_t e = w + 1;
+        while (e < W && winner(e) == c) ++e;
+        if (c >= 0) printf("    %.3f - %.3f %s\n", begin_s(w), end_s(e - 1), class_names[c]);
+        w = e;
+    }
+    if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
+    return 0;
+}
+
+// `hmm scan`: every input (.wav: lpc -> quantize -> scan; .prd: quantize -> scan; .seq: scan) under the models
+extern "C" int e2vq_hmm_scan_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                   const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                   int64_t window_frames, int64_t hop_frames, double min_margin, const char* csv_dir_or_file)
+{
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("e2vq_hmm_scan_files: no models");
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("e2vq_hmm_scan_files: no inputs");
+    if (scan_check_geometry("e2vq_hmm_scan_files", window_frames, hop_frames)) return 1;
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("e2vq_hmm_scan_files: window %d ms / offset %d ms", W_ms, O_ms);
+    std::vector<Hmm> models;
+    if (load_models(model_filenames, num_models, models)) return 1;
+    const int M = models[0].M;
+    std::vector<const Hmm*> ms;
+    std::vector<const char*> names;
+    for (unsigned k = 0; k < num_models; ++k) {
+        if (models[k].M != M)
+            return e2vq_set_error("%s: model has M=%d but %s has M=%d", model_filenames[k], models[k].M, model_filenames[0], M);
+        ms.push_back(&models[k]);
+        names.push_back(models[k].class_name.c_str());
+    }
+    const bool have_cb = cb_filename && *cb_filename;
+    int cbP = 0, cbM = 0;
+    std::vector<double> refl;
+    if (have_cb) {
+        char cls[96];
+        if (e2vq_cbook_info(cb_filename, cls, &cbP, &cbM)) return 1;
+        if (cbM != M) return e2vq_set_error("%s: codebook has M=%d but the models have M=%d", cb_filename, cbM, M);
+    }
+    struct Input {
+        std::string path, csv;
+        int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
+        int sample_rate = 0;
+        int64_t samples = 0, T = 0;
+    };
+    std::vector<Input> inputs((size_t)num_inputs);
+    const std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
+    const bool csv_is_file = num_inputs == 1 && ends_with(csv, ".csv");
+    bool need_cb = false;
+    for (int f = 0; f < num_inputs; ++f) {
+        Input& in = inputs[(size_t)f];
+        if (!input_filenames[f]) return e2vq_set_error("e2vq_hmm_scan_files: NULL file name");
+        in.path = input_filenames[f];
+        char cls[96];
+        if (ends_with(in.path, ".seq")) {
+            in.kind = 2;
+            int m;
+            if (e2vq_seq_info(in.path.c_str(), cls, &m, &in.T)) return 1;
+            if (m != M) return e2vq_set_error("%s: codebook size %d differs from the models' %d", in.path.c_str(), m, M);
+        } else if (ends_with(in.path, ".prd")) {
+            in.kind = 1;
+            int p;
+            if (e2vq_prd_info(in.path.c_str(), cls, &p, &in.T)) return 1;
+            if (have_cb && p != cbP)
+                return e2vq_set_error("%s: prediction order %d differs from the codebook's %d", in.path.c_str(), p, cbP);
+            need_cb = true;
+        } else if (ends_with(in.path, ".wav")) {
+            in.kind = 0;
+            if (e2vq_wav_info(in.path.c_str(), &in.sample_rate, &in.samples, nullptr)) return 1;
+            if (have_cb && P != cbP) return e2vq_set_error("%s: prediction order -P %d differs from the codebook's %d", in.path.c_str(), P, cbP);
+            int win, off;
+            if (e2vq_lpc_frame_count(in.samples, in.sample_rate, W_ms, O_ms, &win, &off, &in.T)) return 1;
+            if (in.T < 0) return e2vq_set_error("%s: signal too short (%lld samples, window %d)", in.path.c_str(), (long long)in.samples, win);
+            need_cb = true;
+        } else {
+            return e2vq_set_error("%s: not a .wav, .prd or .seq file", in.path.c_str());
+        }
+        if (!csv.empty()) in.csv = csv_is_file ? csv : csv + "/" + e2vq_io::basename_noext(in.path.c_str()) + ".csv";
+        for (int g = 0; g < f && !in.csv.empty(); ++g)
+            if (inputs[(size_t)g].csv == in.csv) return e2vq_set_error("%s and %s would both write %s", inputs[(size_t)g].path.c_str(), in.path.c_str(), in.csv.c_str());
+    }
+    if (need_cb && !have_cb) return e2vq_set_error("e2vq_hmm_scan_files: signals and predictors need a codebook");
+    if (need_cb) {
+        refl.resize((size_t)cbM * (cbP + 1));
+        if (e2vq_cbook_read(cb_filename, refl.data(), cbM)) return 1;
+    }
+    // ---- the device from here on --------------------------------------------------------------------------------
+    const int device = env_device();
+    if (require_device(device)) return 1;
+    DeviceBuffer<double> d_frames;
+    DeviceBuffer<int32_t> d_status;
+    DeviceBuffer<unsigned short> d_sym;
+    Stream st;
+    if (st.create()) return 1;
+    struct Session {
+        e2vq_session* s = nullptr;
+        ~Session()
+        {
+            if (s) e2vq_session_destroy(s);
+        }
+    } vq;
+    if (need_cb) {
+        if (e2vq_session_create(device, cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, refl.data(), cbM))
+            return 1;
+    }
+    const int NC = cbP + 1;
+    for (Input& in : inputs) {
+        int64_t T = in.T;
+        std::vector<uint16_t> h_sym;
+        std::vector<double> h_frames;
+        if (in.kind == 2) {
+            h_sym.resize((size_t)std::max<int64_t>(T, 1));
+            if (T > 0 && e2vq_seq_read(in.path.c_str(), h_sym.data(), T)) return 1;
+            if (d_sym.upload(h_sym.data(), (size_t)T, st.s)) return 1;
+        } else {
+            if (d_frames.reserve((size_t)std::max<int64_t>(T, 1) * NC) || d_sym.reserve((size_t)T + 64)) return 1;
+            if (in.kind == 1) {
+                h_frames.resize((size_t)std::max<int64_t>(T, 1) * NC);
+                bool fin = true;
+                if (T > 0 && e2vq_io::prd_read_range_mt(in.path.c_str(), cbP, 0, T, h_frames.data(), e2vq_io::io_threads(), &fin)) return 1;
+                if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", in.path.c_str());
+                if (T > 0) HIPCHK(hipMemcpyAsync(d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st.s));
+            } else {
+                std::vector<int32_t> samples((size_t)std::max<int64_t>(in.samples, 1));
+                if (e2vq_wav_read(in.path.c_str(), samples.data(), in.samples)) return 1;
+                if (d_status.reserve((size_t)std::max<int64_t>(T, 1))) return 1;
+                int64_t T2 = 0;
+                if (T > 0 && e2vq_lpc_analyze(device, P, W_ms, O_ms, samples.data(), in.samples, in.sample_rate, d_frames.get(),
+                                              d_status.get(), T, &T2, 1))
+                    return 1;
+                std::vector<int32_t> fst((size_t)T);
+                if (T > 0) HIPCHK(hipMemcpyAsync(fst.data(), d_status.get(), (size_t)T * 4, hipMemcpyDeviceToHost, st.s));
+                HIPCHK(hipStreamSynchronize(st.s));
+                int64_t good = 0;
+                for (int64_t t = 0; t < T; ++t) good += fst[(size_t)t] == 0;
+                if (good != T) {
+                    // frames whose Levinson recursion failed are left out, as `ecoz2 lpc` leaves them out of the .prd: the rest
+                    // makes one round trip through the host (the only place where the frames leave the device)
+                    h_frames.resize((size_t)T * NC);
+                    HIPCHK(hipMemcpy(h_frames.data(), d_frames.get(), (size_t)T * NC * 8, hipMemcpyDeviceToHost));
+                    int64_t o = 0;
+                    for (int64_t t = 0; t < T; ++t)
+                        if (fst[(size_t)t] == 0) memmove(h_frames.data() + (size_t)(o++) * NC, h_frames.data() + (size_t)t * NC, (size_t)NC * 8);
+                    printf("%s: %lld frames left out: Levinson status != 0 (later frame times are early by their offsets)\n",
+                           in.path.c_str(), (long long)(T - good));
+                    T = good;
+                    if (T > 0) HIPCHK(hipMemcpyAsync(d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st.s));
+                }
+            }
+            if (T > 0 && e2vq_quantize_device(vq.s, d_frames.get(), T, d_sym.get(), nullptr)) return 1;
+        }
+        const i64 offs[2] = {0, T};
+        i64 wo[2];
+        scan_window_offsets(offs, 1, window_frames, hop_frames, wo);
+        const size_t W = (size_t)wo[1];
+        std::vector<int> best(W), second(W);
+        std::vector<double> lp1(W), lp2(W);
+        ScanOut out;
+        out.best = best.data(), out.best_log_prob = lp1.data(), out.second = second.data(), out.second_log_prob = lp2.data();
+        if (scan_device(ms, d_sym.get(), offs, 1, window_frames, hop_frames, st.s, out)) return 1;
+        HIPCHK(hipStreamSynchronize(st.s));  // (the host buffers of this input are locals)
+        if (e2vq_hmm_scan_report(in.path.c_str(), T, (int)num_models, names.data(), (int64_t)W, window_frames, hop_frames, W_ms, O_ms,
+                                 best.data(), lp1.data(), second.data(), lp2.data(), min_margin, in.csv.empty() ? nullptr : in.csv.c_str()))
+            return 1;
+    }
+    return 0;
 }

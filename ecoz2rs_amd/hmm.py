@@ -54,6 +54,15 @@ _sig("e2vq_hmm_train_grid", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C
 _sig("e2vq_hmm_classify_grid", C.c_int, c_char_pp, C.c_uint, c_char_pp, C.c_uint, C.c_int, C.c_char_p, C.c_char_p)
 _sig("e2vq_hmm_score_grid", C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("e2vq_hmm_scan_windows", C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p)
+_sig("e2vq_hmm_scan", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_scan_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_scan_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_int64, C.c_int64, C.c_double, C.c_char_p)
+_sig("e2vq_hmm_scan_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_char_p)
 
 
 def _strs(items):
@@ -297,3 +306,70 @@ def viterbi(pi, A, B, seqs, device=0, want_path=True):
                                S, path.ctypes.data if want_path else None, lp.ctypes.data, st.ctypes.data))
     paths = [path[offs[s]:offs[s + 1]].copy() for s in range(S)] if want_path else None
     return dict(path=paths, log_prob=lp, status=st)
+
+
+def scan_windows(offs, window, hop=None):
+    """window offsets of `scan` (host only): stream s has (T_s - window) // hop + 1 windows when T_s >= window, else none"""
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    win_offs = np.zeros(len(offs), dtype=np.int64)
+    check(lib.e2vq_hmm_scan_windows(offs.ctypes.data, len(offs) - 1, int(window), int(window if hop is None else hop),
+                                    win_offs.ctypes.data))
+    return win_offs
+
+
+def scan(models, sym, offs, window, hop=None, device=0, matrix=True):
+    """the models over sliding windows of whole symbol streams: models = [(pi, A, B)] sharing M; sym =
+    the concatenated uint16 symbols of the streams -- a numpy array, or a device tensor (torch, dtype uint16 or int16, on
+    `device`) as lpc.features takes frames --, offs = their S + 1 offsets; windows of `window` symbols every `hop` (default:
+    window).  -> dict: win_offs (S + 1), best / second (W,) model indices with best_log_prob / second_log_prob, and with
+    `matrix` the (W, K) arrays mant / exp2 / status / log_prob, each entry what `score` gives for that window's symbols"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    S = len(offs) - 1
+    hop = window if hop is None else hop
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    win_offs = np.zeros(S + 1, dtype=np.int64)
+    if int(window) >= 1 and int(hop) >= 1 and K >= 1:
+        win_offs = scan_windows(offs, window, hop)
+    W = int(win_offs[-1])
+    best, second = np.zeros(W, dtype=np.int32), np.zeros(W, dtype=np.int32)
+    lp1, lp2 = np.zeros(W), np.zeros(W)
+    out = dict(win_offs=win_offs, best=best, best_log_prob=lp1, second=second, second_log_prob=lp2)
+    mat = [None] * 4
+    if matrix:
+        n = max(K, 0)
+        out.update(mant=np.zeros((W, n)), exp2=np.zeros((W, n), dtype=np.int64), status=np.zeros((W, n), dtype=np.int32),
+                   log_prob=np.zeros((W, n)))
+        mat = [out[k].ctypes.data for k in ("mant", "exp2", "status", "log_prob")]
+    check(lib.e2vq_hmm_scan(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, int(window), int(hop),
+                            win_offs.ctypes.data, *mat, best.ctypes.data, lp1.ctypes.data, second.ctypes.data,
+                            lp2.ctypes.data, int(on_device)))
+    return out
+
+
+def scan_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_scan_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def scan_files(model_filenames, input_filenames, window, hop=None, codebook=None, P=36, W_ms=45, O_ms=15, min_margin=0.0,
+               csv=None):
+    """`hmm scan`: every input (.wav, .prd or .seq) under the models over sliding windows; per input a
+    block on stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the windows"""
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    check(lib.e2vq_hmm_scan_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                  len(input_filenames), int(P), int(W_ms), int(O_ms), int(window),
+                                  int(window if hop is None else hop), float(min_margin), str(csv).encode() if csv else None))

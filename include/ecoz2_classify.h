@@ -233,6 +233,47 @@ int e2vq_hmm_score_grid(int device, int K, const int *Ns, const int *Ms, const d
                         const uint16_t *sym, const int64_t *offs, int S, const int64_t *seq_lo, const int64_t *seq_hi,
                         const int64_t *out_offs, double *mant, int64_t *exp2, int *status, double *log_probs);
 
+/* ---- the trained models over whole recordings -------------------------------------------------------
+ * `hmm scan`: windows of window_frames symbols every hop_frames symbols over each of S streams (concatenated u16 symbols +
+ * S+1 offsets).  Stream s of T_s symbols has W_s = (T_s - L) / H + 1 windows when T_s >= L, else none: a trailing incomplete
+ * window is dropped; window i starts at frame i H.  win_offs (S+1 entries, may be NULL): the windows of stream s are
+ * [win_offs[s], win_offs[s+1]).  Outputs, each may be NULL: the matrix at [w*K + k] in the layout of e2vq_hmm_score (mant,
+ * exp2, status, ln P) -- every value bit for bit what e2vq_hmm_score returns for that window's symbols passed as a sequence
+ * of its own, a symbol >= M scoring status 2 in exactly the windows that contain it -- and per window the best and the
+ * second-best model with their ln P, ranked as `hmm classify` ranks (by P = mant 2^exp2; among equal scores the model given
+ * later first; second = -1 and -inf when K = 1).  Without the matrix outputs only the two results per window leave the
+ * device.  The symbols are staged once per run of overlapping windows (k_hmm_scan), never materialised per window.
+ * sym_on_device: `sym` is a device pointer on `device` (offs stays a host pointer).
+ * L < 1, H < 1, K < 1 and an N outside [1, 512] are refused before any HIP call.
+ * By default floor(64 / N) windows share a wave for N <= 21.  ECOZ2_HMM_SCAN_PACK = 0 / 1: one window per wave / floor(64 / N) windows per wave (N <= 32) whatever N; the bits are the
+ * same.  e2vq_hmm_scan_windows: the window arithmetic alone (host only). */
+int e2vq_hmm_scan_windows(const int64_t *offs, int S, int64_t window_frames, int64_t hop_frames, int64_t *win_offs);
+int e2vq_hmm_scan(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                  const double *const *Bs, const void *sym, const int64_t *offs, int S, int64_t window_frames,
+                  int64_t hop_frames, int64_t *win_offs, double *mant, int64_t *exp2, int *status, double *log_probs,
+                  int *best, double *best_log_prob, int *second, double *second_log_prob, int sym_on_device);
+/* HIP-event time of the kernels (scan + top-2) of this thread's last scan (-1: none yet) */
+int e2vq_hmm_scan_last_kernel_ms(float *ms);
+/* The file form.  Each input is a .wav (lpc with P, W_ms, O_ms -> quantize with the codebook -> scan), a .prd (quantize ->
+ * scan) or a .seq (scan; no codebook needed); each is read and uploaded once, and frames and symbols stay on the device
+ * between the stages (DESIGN.md 4.8.5 names the one exception).  Per input a block on stdout (name, T, windows; windows won
+ * per class; the maximal runs of consecutive windows won by one class with margin ln P1 - ln P2 >= min_margin as
+ * "begin_s - end_s class") and, with csv_dir_or_file, a CSV -- <dir>/<input's base name>.csv, or the named file when there
+ * is one input and the name ends in .csv -- with the header
+ *   window,begin_frame,end_frame,begin_s,end_s,class,log_prob,second_class,second_log_prob
+ * end_frame is exclusive; begin_s = begin_frame O_ms / 1000; end_s = ((end_frame - 1) O_ms + W_ms) / 1000, the end of the
+ * last frame's analysis window (.prd and .seq inputs: the W_ms / O_ms given); floats as %.17g; a class is empty where no
+ * model can emit the window.  No models, no inputs, L < 1, H < 1, models of differing M, a codebook whose M differs from
+ * the models' or whose P differs from a .prd's or from P (signals), a .seq of another M, signals or predictors without a
+ * codebook and two inputs of one CSV name return 1 before any HIP call, and no file is written. */
+int e2vq_hmm_scan_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                        const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms, int64_t window_frames,
+                        int64_t hop_frames, double min_margin, const char *csv_dir_or_file);
+/* CSV and stdout block of one scanned input from its two results per window (host only; what e2vq_hmm_scan_files calls) */
+int e2vq_hmm_scan_report(const char *name, int64_t T, int K, const char *const *class_names, int64_t W, int64_t window_frames,
+                         int64_t hop_frames, int W_ms, int O_ms, const int *best, const double *best_log_prob, const int *second,
+                         const double *second_log_prob, double min_margin, const char *csv_filename);
+
 /* Viterbi decoding of S sequences under one model: logarithms of the parameters taken on the host
  * (log 0 = -inf; a negative, NaN or infinite parameter is refused), maximisation on the GPU.  log_prob[s] = ln P*,
  * status[s]: 0 ok, 1 ln P* = -inf (the model cannot emit the sequence; the path is still written), 2 a symbol >= M
