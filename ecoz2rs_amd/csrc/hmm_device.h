@@ -79,20 +79,12 @@ long long fb_scratch_words(int N);
 // M-step (+ epsilon restriction on B when epsilon > 0), in place
 void launch_reestimate(int N, int M, const long long* acc, double epsilon, double* pi, double* A, double* B,
                        hipStream_t st);
-// workgroups of class k in launch_fb_classes: ceil(S_k / 4 waves), at least 1, at most 2048 (as launch_fb's grid)
+// workgroups of a model with S sequences in launch_fb_grid: ceil(S / 4 waves), at least 1, at most 2048 (as launch_fb's grid)
 int fb_class_workgroups(int S);
-// Class-batched E-step (N <= WAVE_N): models[k] of one (N, M); nblocks workgroups, blocks[3 g .. 3 g + 2] =
-// (class, workgroup index within the class, workgroup count of the class); class k owns the sequences
-// [cls_s[k], cls_s[k + 1]) of offs and the W = acc_words(N, M) words at acc + k W.  mant / exp2 / status over the batch.
-void launch_fb_classes(const ModelDev* models, int N, const int* blocks, int nblocks, const int* cls_s,
-                       const unsigned short* sym, const long long* offs, double* alpha_buf, double* c_buf, long long* acc,
-                       long long W, double* mant, long long* exp2, int* status, hipStream_t st);
-// Class-batched M-step of the n_active classes listed in `active`: counts at acc + k W, pi | A | B at params + k P
-void launch_reestimate_classes(int N, int M, const int* active, int n_active, const long long* acc, long long W,
-                               double epsilon, double* params, long long P, hipStream_t st);
 
-// One model of a grid batch: its own (N, M) in md, the sequences [s_lo, s_hi) of the batch's offs
-// (other models may train on the same ones), and where its own slices of the batch's buffers start.
+// One model of a training batch (the classes of `hmm learn --all-classes`, 4.8.2, are the batch of one
+// (N, M) with disjoint sequences): its own (N, M) in md, the sequences [s_lo, s_hi) of the batch's offs (other models may
+// train on the same ones), and where its own slices of the batch's buffers start.
 struct GridModelDev {
     ModelDev md;
     int s_lo, s_hi;

@@ -6,10 +6,9 @@
 //                 added to exact fixed-point accumulators (int64 limb sums: order-free, hence deterministic and
 //                 shardable across GPUs with an integer all-reduce, like the VQ cell sums)
 //   k_hmm_reestimate / k_hmm_adjustb   M-step
-//   k_hmm_fb_classes / k_hmm_reestimate_classes / k_hmm_adjustb_classes   the same E- and M-step over a batch of
-//                 models of one (N, M), each trained on its own sequences (hmm learn --all-classes)
-//   k_hmm_fb_grid / k_hmm_reestimate_grid / k_hmm_adjustb_grid   the same over a batch of models of any (N, M), sequences
-//                 shared between them (hmm learn --grid)
+//   k_hmm_fb_grid / k_hmm_reestimate_grid / k_hmm_adjustb_grid   the same E- and M-step over a batch of models of any
+//                 (N, M), each trained on its own range of the batch's sequences, which models may share (hmm learn --grid,
+//                 DESIGN.md 4.8.3; hmm learn --all-classes, 4.8.2, is the batch of one (N, M) and disjoint ranges)
 // Arithmetic: IEEE f64 multiply / fma / add / divide in the order oracle/hmm_oracle.h defines -- the kernels are
 // bit-exact against the oracle.  No transcendental runs on the device: P(O) leaves as (mantissa, exponent) and the
 // host takes the logarithm.
@@ -271,7 +270,7 @@ __device__ __forceinline__ void acc_local(i64 (&cell)[2], double x)
 //               E-step for 600 k symbols at N = 5, all of it same-address contention)
 //   gamma -> AD, BD, PI : per-lane registers over the wave's sequences, one global atomic per lane at the end
 //   gamma -> BN[j][o_t] : global atomics (N x M words: spread out)
-// The body is shared by k_hmm_fb (one model, sequences [0, S), workgroup wg of nwg) and k_hmm_fb_classes (a batch of
+// The body is shared by k_hmm_fb (one model, sequences [0, S), workgroup wg of nwg) and k_hmm_fb_grid (a batch of
 // models, the sequences [s_lo, s_hi) of one of them): one text, so one arithmetic and the same counts, bit for bit.
 __device__ __forceinline__ void fb_wave_body(const ModelDev& md, const unsigned short* __restrict__ sym,
                                              const i64* __restrict__ offs, int s_lo, int s_hi, int wg, int nwg,
@@ -415,27 +414,12 @@ __global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb(ModelDev md, const uns
     fb_wave_body(md, sym, offs, 0, S, (int)blockIdx.x, (int)gridDim.x, alpha_buf, c_buf, acc, mant, exp2, status);
 }
 
-// Class-batched E-step: K models of one (N <= 64, M), each with its own sequences.  blocks[3 g .. 3 g + 2]
-// = (class k, index of this workgroup among the class's, workgroup count of the class): a workgroup works for one class
-// only -- stages its A, zeroes its own AN table, strides over the class's sequences [cls_s[k], cls_s[k + 1]) and flushes
-// into acc + k W.  offs / mant / exp2 / status are indexed over the whole batch.
-__global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb_classes(const ModelDev* __restrict__ models,
-                                                                   const int* __restrict__ blocks,
-                                                                   const int* __restrict__ cls_s,
-                                                                   const unsigned short* __restrict__ sym,
-                                                                   const i64* __restrict__ offs,
-                                                                   double* __restrict__ alpha_buf, double* __restrict__ c_buf,
-                                                                   i64* __restrict__ acc, i64 W, double* __restrict__ mant,
-                                                                   i64* __restrict__ exp2, int* __restrict__ status)
-{
-    const int k = blocks[3 * blockIdx.x], wg = blocks[3 * blockIdx.x + 1], nwg = blocks[3 * blockIdx.x + 2];
-    const ModelDev md = models[k];
-    fb_wave_body(md, sym, offs, cls_s[k], cls_s[k + 1], wg, nwg, alpha_buf, c_buf, acc + (size_t)k * W, mant, exp2, status);
-}
-
 // Grid-batched E-step: models of one N <= 64 (one launch per distinct N), each with its own M,
-// sequences, alpha^ / c / result slices and accumulators.  The body gets pointers rebased for the model, so that its
-// own indexing (alpha^ at offs[s] N, c at offs[s], results at s) lands in the model's slices: the same text as above.
+// sequences, alpha^ / c / result slices and accumulators.  blocks[3 g .. 3 g + 2] = (model k, index of this workgroup
+// among the model's, workgroup count of the model): a workgroup works for one model only -- stages its A, zeroes its own
+// AN table, strides over the model's sequences and flushes into the model's accumulators.  The body gets pointers rebased
+// for the model, so that its own indexing (alpha^ at offs[s] N, c at offs[s], results at s) lands in the model's slices:
+// the same text as above.
 __global__ __launch_bounds__(64 * FB_WAVES) void k_hmm_fb_grid(const GridModelDev* __restrict__ models,
                                                                 const int* __restrict__ blocks,
                                                                 const unsigned short* __restrict__ sym,
@@ -712,25 +696,6 @@ __global__ void k_hmm_adjustb(int N, int M, double epsilon, double* __restrict__
     adjustb_row(M, epsilon, B + (size_t)j * M);
 }
 
-// Class-batched M-step: grid.y runs over the list `active` of class indices; class k's counts at acc + k W, its
-// parameters pi | A | B at params + k P (P = N + N^2 + N M)
-__global__ void k_hmm_reestimate_classes(int N, int M, const int* __restrict__ active, const i64* __restrict__ acc, i64 W,
-                                         double* __restrict__ params, i64 P)
-{
-    const int k = active[blockIdx.y];
-    double* pi = params + (size_t)k * P;
-    reestimate_one(N, M, acc + (size_t)k * W, pi, pi + N, pi + N + (size_t)N * N, (i64)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-__global__ void k_hmm_adjustb_classes(int N, int M, double epsilon, const int* __restrict__ active, double* __restrict__ params,
-                                      i64 P)
-{
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const int k = active[blockIdx.y];
-    adjustb_row(M, epsilon, params + (size_t)k * P + N + (size_t)N * N + (size_t)j * M);
-}
-
 // Grid-batched M-step: grid.y runs over the list `active` of model indices, each model with its own (N, M); grid.x
 // covers the largest of them, and the threads beyond a model's own extent return
 __global__ void k_hmm_reestimate_grid(const GridModelDev* __restrict__ models, const int* __restrict__ active,
@@ -830,33 +795,6 @@ int fb_class_workgroups(int S)
 {
     const int b = (S + FB_WAVES - 1) / FB_WAVES;
     return b < 1 ? 1 : (b < 2048 ? b : 2048);
-}
-
-void launch_fb_classes(const ModelDev* models, int N, const int* blocks, int nblocks, const int* cls_s,
-                       const unsigned short* sym, const i64* offs, double* alpha_buf, double* c_buf, i64* acc, i64 W,
-                       double* mant, i64* exp2, int* status, hipStream_t st)
-{
-    if (nblocks < 1) return;
-    const size_t lds = (size_t)N * N * (2 * 8 + 16);  // as launch_fb
-    if (hipFuncSetAttribute((const void*)k_hmm_fb_classes, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        fprintf(stderr, "ecoz2vq: the device refuses 160 KB of dynamic LDS for the E-step kernel (N = %d needs %zu bytes)\n", N, lds);
-    hipLaunchKernelGGL(k_hmm_fb_classes, dim3((unsigned)nblocks), dim3(64 * FB_WAVES), lds, st, models, blocks, cls_s, sym, offs,
-                       alpha_buf, c_buf, acc, W, mant, exp2, status);
-}
-
-void launch_reestimate_classes(int N, int M, const int* active, int n_active, const i64* acc, i64 W, double epsilon,
-                               double* params, i64 P, hipStream_t st)
-{
-    const i64 total = (i64)N + (i64)N * N + (i64)N * M;
-    // grid.y carries the classes: at most 65535 per launch, more in further launches
-    for (int k0 = 0; k0 < n_active; k0 += 65535) {
-        const int kn = n_active - k0 < 65535 ? n_active - k0 : 65535;
-        hipLaunchKernelGGL(k_hmm_reestimate_classes, dim3((unsigned)((total + 255) / 256), (unsigned)kn), dim3(256), 0, st, N, M,
-                           active + k0, acc, W, params, P);
-        if (epsilon > 0.0)
-            hipLaunchKernelGGL(k_hmm_adjustb_classes, dim3((unsigned)((N + 63) / 64), (unsigned)kn), dim3(64), 0, st, N, M, epsilon,
-                               active + k0, params, P);
-    }
 }
 
 void launch_fb_grid(const GridModelDev* models, int N, const int* blocks, int nblocks, const unsigned short* sym,

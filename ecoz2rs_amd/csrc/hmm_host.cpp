@@ -61,6 +61,20 @@ struct Hmm {
         A.assign((size_t)n * n, 0.0);
         B.assign((size_t)n * m, 0.0);
     }
+    // pi | A | B as one flat block of params() doubles: how every device parameter buffer holds a model
+    size_t params() const { return pi.size() + A.size() + B.size(); }
+    void pack(double* q) const
+    {
+        std::copy(pi.begin(), pi.end(), q);
+        std::copy(A.begin(), A.end(), q + pi.size());
+        std::copy(B.begin(), B.end(), q + pi.size() + A.size());
+    }
+    void unpack(const double* q)
+    {
+        std::copy(q, q + pi.size(), pi.begin());
+        std::copy(q + pi.size(), q + pi.size() + A.size(), A.begin());
+        std::copy(q + pi.size() + A.size(), q + params(), B.begin());
+    }
 };
 
 // uniform draws in (0, 1] divided by their sequential sum
@@ -193,16 +207,13 @@ struct DevModels {
     int upload(const std::vector<const Hmm*>& ms, hipStream_t st)
     {
         size_t total = 0;
-        for (const Hmm* h : ms) total += h->pi.size() + h->A.size() + h->B.size();
-        std::vector<double> flat;
-        flat.reserve(total);
         std::vector<size_t> at;
         for (const Hmm* h : ms) {
-            at.push_back(flat.size());
-            flat.insert(flat.end(), h->pi.begin(), h->pi.end());
-            flat.insert(flat.end(), h->A.begin(), h->A.end());
-            flat.insert(flat.end(), h->B.begin(), h->B.end());
+            at.push_back(total);
+            total += h->params();
         }
+        std::vector<double> flat(total);
+        for (size_t k = 0; k < ms.size(); ++k) ms[k]->pack(flat.data() + at[k]);
         if (params.upload(flat.data(), flat.size(), st)) return 1;
         HIPCHK(hipStreamSynchronize(st));  // `flat` is a local
         host.clear();
@@ -269,10 +280,8 @@ struct Trainer {
     {
         N = h.N; M = h.M; S = S_; total = total_; st = st_;
         W = e2hmm::acc_words(N, M);
-        std::vector<double> flat;
-        flat.insert(flat.end(), h.pi.begin(), h.pi.end());
-        flat.insert(flat.end(), h.A.begin(), h.A.end());
-        flat.insert(flat.end(), h.B.begin(), h.B.end());
+        std::vector<double> flat(h.params());
+        h.pack(flat.data());
         if (d_params.upload(flat.data(), flat.size(), st)) return 1;
         HIPCHK(hipStreamSynchronize(st));
         double* base = d_params.get();
@@ -334,12 +343,10 @@ struct Trainer {
     }
     int download(Hmm& h)
     {
-        std::vector<double> flat(h.pi.size() + h.A.size() + h.B.size());
+        std::vector<double> flat(h.params());
         HIPCHK(hipMemcpyAsync(flat.data(), d_params.get(), flat.size() * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        std::copy(flat.begin(), flat.begin() + h.pi.size(), h.pi.begin());
-        std::copy(flat.begin() + h.pi.size(), flat.begin() + h.pi.size() + h.A.size(), h.A.begin());
-        std::copy(flat.begin() + h.pi.size() + h.A.size(), flat.end(), h.B.begin());
+        h.unpack(flat.data());
         return 0;
     }
 };
@@ -595,23 +602,7 @@ int save_learned(const Hmm& h, int model_type, double val_auto, int max_iteratio
     return write_file(dir + "/" + h.class_name + ".csv", std::vector<unsigned char>(csv.begin(), csv.end()));
 }
 
-// ---- every class at once ------------------------------------------------------------------------------
-// One class of a class-batched training: its sequences in list order and its model, trained exactly as `train` trains
-// it alone -- same kernels' arithmetic, same sequential sum of L on the host, same stopping rule.
-struct ClassJob {
-    Hmm h;                          // in: the initial model; out: the trained one
-    const uint16_t* sym = nullptr;  // the class's concatenated symbols (host)
-    std::vector<i64> offs;          // S_k + 1, from 0
-    std::vector<double> hist;       // out: sum ln P per E-step
-    std::vector<i64> skipped;       // out: sequences skipped per E-step
-    int S() const { return (int)offs.size() - 1; }
-    i64 T() const { return offs.back(); }
-};
-
-// device bytes a class takes in a batch: alpha^ and c over its symbols, and its accumulators
-i64 class_batch_bytes(const ClassJob& c) { return (c.T() * ((i64)c.h.N + 1) + e2hmm::acc_words(c.h.N, c.h.M)) * 8; }
-
-// ECOZ2_HMM_LEARN_BATCH_BYTES: the budget of one batch for class_batch_bytes (default 4 GiB)
+// ECOZ2_HMM_LEARN_BATCH_BYTES: the budget of one training batch (default 4 GiB)
 i64 learn_batch_bytes()
 {
     const char* v = getenv("ECOZ2_HMM_LEARN_BATCH_BYTES");
@@ -619,178 +610,54 @@ i64 learn_batch_bytes()
     return std::max<i64>(b, 1);
 }
 
-// K classes of one (N, M) trained together on the current device: per iteration one E-step over every active class's
-// sequences (N <= 64: one k_hmm_fb_classes launch; above: launch_fb once per active class), one copy of the
-// per-sequence P(O) back, the per-class L summed on the host in sequence order, and one batched M-step over the classes
-// that go on.  A class that stops leaves the launches; its parameters on the device are not touched again.
-int train_batch(ClassJob* const* jobs, int K, double epsilon, double val_auto, int max_iterations)
-{
-    const int N = jobs[0]->h.N, M = jobs[0]->h.M;
-    const i64 W = e2hmm::acc_words(N, M), P = (i64)N + (i64)N * N + (i64)N * M;
-    std::vector<i64> offs(1, 0);
-    std::vector<int> cls_s(1, 0);
-    int max_blocks = 0;
-    for (int k = 0; k < K; ++k) {
-        const ClassJob& c = *jobs[k];
-        const i64 base = offs.back();
-        for (int q = 1; q <= c.S(); ++q) offs.push_back(base + c.offs[(size_t)q]);
-        cls_s.push_back(cls_s.back() + c.S());
-        max_blocks += e2hmm::fb_class_workgroups(c.S());
-    }
-    const int S = cls_s.back();
-    const i64 total = offs.back();
-    std::vector<double> flat((size_t)(K * P));
-    for (int k = 0; k < K; ++k) {
-        const Hmm& h = jobs[k]->h;
-        double* q = flat.data() + (size_t)k * P;
-        std::copy(h.pi.begin(), h.pi.end(), q);
-        std::copy(h.A.begin(), h.A.end(), q + N);
-        std::copy(h.B.begin(), h.B.end(), q + N + (size_t)N * N);
-    }
-    DeviceBuffer<double> d_params, d_alpha, d_c, d_mant;
-    DeviceBuffer<i64> d_acc, d_exp, d_offs, d_scratch;
-    DeviceBuffer<int> d_status, d_blocks, d_active, d_cls;
-    DeviceBuffer<unsigned short> d_sym;
-    DeviceBuffer<ModelDev> d_models;
-    Stream st;  // (after the buffers: see Stream)
-    if (st.create()) return 1;
-    if (d_sym.reserve((size_t)total) || d_params.upload(flat.data(), flat.size(), st.s) || d_offs.upload(offs.data(), offs.size(), st.s) ||
-        d_cls.upload(cls_s.data(), cls_s.size(), st.s) || d_alpha.reserve((size_t)(total * N)) || d_c.reserve((size_t)total) ||
-        d_acc.reserve((size_t)(K * W)) || d_mant.reserve((size_t)S) || d_exp.reserve((size_t)S) || d_status.reserve((size_t)S) ||
-        d_blocks.reserve((size_t)max_blocks * 3) || d_active.reserve((size_t)K))
-        return 1;
-    if (e2hmm::fb_scratch_words(N) > 0 && d_scratch.reserve((size_t)e2hmm::fb_scratch_words(N))) return 1;
-    for (int k = 0; k < K; ++k)
-        if (jobs[k]->T() > 0)
-            HIPCHK(hipMemcpyAsync(d_sym.get() + offs[(size_t)cls_s[k]], jobs[k]->sym, (size_t)jobs[k]->T() * 2, hipMemcpyHostToDevice, st.s));
-    std::vector<ModelDev> models;
-    for (int k = 0; k < K; ++k) {
-        const double* q = d_params.get() + (size_t)k * P;
-        models.push_back(ModelDev{N, M, q, q + N, q + N + (size_t)N * N});
-    }
-    if (d_models.upload(models.data(), models.size(), st.s)) return 1;
-    HIPCHK(hipStreamSynchronize(st.s));  // (`flat`, `offs`, `cls_s`, `models` are locals; the copies are done)
-    std::vector<double> mant((size_t)S);
-    std::vector<i64> ex((size_t)S);
-    std::vector<int> stat((size_t)S), blocks, estep_list, mstep_list;
-    std::vector<char> active((size_t)K, 1);
-    std::vector<double> Lprev((size_t)K, 0.0);
-    for (int k = 0; k < K; ++k) {
-        jobs[k]->hist.clear();
-        jobs[k]->skipped.clear();
-    }
-    // (host vectors copied to the device below are rewritten only after the stream synchronisation that follows the copy)
-    for (int it = 0;; ++it) {
-        if ((max_iterations >= 0 && it >= max_iterations) || it >= MAX_ESTEPS) break;
-        estep_list.clear();
-        for (int k = 0; k < K; ++k)
-            if (active[(size_t)k]) estep_list.push_back(k);
-        if (estep_list.empty()) break;
-        HIPCHK(hipMemsetAsync(d_acc.get(), 0, (size_t)(K * W) * 8, st.s));
-        if (N <= e2hmm::WAVE_N) {
-            blocks.clear();
-            for (int k : estep_list) {
-                const int nb = e2hmm::fb_class_workgroups(cls_s[(size_t)k + 1] - cls_s[(size_t)k]);
-                for (int b = 0; b < nb; ++b) blocks.insert(blocks.end(), {k, b, nb});
-            }
-            HIPCHK(hipMemcpyAsync(d_blocks.get(), blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice, st.s));
-            e2hmm::launch_fb_classes(d_models.get(), N, d_blocks.get(), (int)(blocks.size() / 3), d_cls.get(), d_sym.get(), d_offs.get(),
-                                     d_alpha.get(), d_c.get(), d_acc.get(), W, d_mant.get(), d_exp.get(), d_status.get(), st.s);
-            HIPCHK(hipGetLastError());
-        } else {
-            for (int k : estep_list) {
-                const int s0 = cls_s[(size_t)k];
-                e2hmm::launch_fb(models[(size_t)k], d_sym.get(), d_offs.get() + s0, cls_s[(size_t)k + 1] - s0, d_alpha.get(), d_c.get(),
-                                 d_acc.get() + (size_t)k * W, d_mant.get() + s0, d_exp.get() + s0, d_status.get() + s0, st.s, d_scratch.get());
-                HIPCHK(hipGetLastError());
-            }
-        }
-        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st.s));
-        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st.s));
-        HIPCHK(hipMemcpyAsync(stat.data(), d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st.s));
-        HIPCHK(hipStreamSynchronize(st.s));
-        mstep_list.clear();
-        for (int k : estep_list) {
-            double L = 0.0;
-            i64 skipped = 0;
-            for (int s = cls_s[(size_t)k]; s < cls_s[(size_t)k + 1]; ++s) {
-                if (stat[(size_t)s] == 0)
-                    L = L + log_prob(mant[(size_t)s], ex[(size_t)s]);
-                else
-                    ++skipped;
-            }
-            jobs[k]->hist.push_back(L);
-            jobs[k]->skipped.push_back(skipped);
-            if (it > 0 && L - Lprev[(size_t)k] <= val_auto) {
-                active[(size_t)k] = 0;
-            } else {
-                mstep_list.push_back(k);
-                Lprev[(size_t)k] = L;
-            }
-        }
-        if (!mstep_list.empty()) {
-            HIPCHK(hipMemcpyAsync(d_active.get(), mstep_list.data(), mstep_list.size() * 4, hipMemcpyHostToDevice, st.s));
-            e2hmm::launch_reestimate_classes(N, M, d_active.get(), (int)mstep_list.size(), d_acc.get(), W, epsilon, d_params.get(), P, st.s);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    HIPCHK(hipMemcpyAsync(flat.data(), d_params.get(), flat.size() * 8, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipStreamSynchronize(st.s));
-    for (int k = 0; k < K; ++k) {
-        Hmm& h = jobs[k]->h;
-        const double* q = flat.data() + (size_t)k * P;
-        std::copy(q, q + N, h.pi.begin());
-        std::copy(q + N, q + N + (size_t)N * N, h.A.begin());
-        std::copy(q + N + (size_t)N * N, q + P, h.B.begin());
-    }
-    return 0;
-}
-
-// every job (one N and M for all): dealt to `workers` workers in contiguous ranges balanced by symbol count, worker w on
-// device (dev0 + w) % device count; each worker packs its classes greedily, in order, into batches of at most
-// learn_batch_bytes() (a larger class alone) and trains them one after the other.  Classes are independent, so neither
-// the dealing nor the batching changes a bit of any result.
-int train_classes(std::vector<ClassJob>& jobs, double epsilon, double val_auto, int max_iterations, int workers, int dev0)
-{
-    const int K = (int)jobs.size();
-    workers = std::max(1, std::min(workers, K));
-    const int ndev = device_count();
-    if (!ndev) return 1;
-    std::vector<i64> prefix(1, 0);
-    for (const ClassJob& c : jobs) prefix.push_back(prefix.back() + c.T());
-    std::vector<int> bound((size_t)workers + 1, K);
-    bound[0] = 0;
-    for (int w = 1; w < workers; ++w) {
-        int c = bound[(size_t)w - 1];
-        while (c < K && prefix[(size_t)c] * workers < prefix[(size_t)K] * w) ++c;
-        bound[(size_t)w] = c;
-    }
-    const i64 budget = learn_batch_bytes();
-    return run_workers(workers, [&](int w) -> int {
-        const int lo = bound[(size_t)w], hi = bound[(size_t)w + 1];
-        if (lo >= hi) return 0;
-        if (require_device(worker_device(dev0, w, ndev))) return 1;
-        for (int c0 = lo; c0 < hi;) {
-            std::vector<ClassJob*> batch{&jobs[(size_t)c0]};
-            i64 bytes = class_batch_bytes(jobs[(size_t)c0]);
-            int c1 = c0 + 1;
-            while (c1 < hi && bytes + class_batch_bytes(jobs[(size_t)c1]) <= budget) {
-                bytes += class_batch_bytes(jobs[(size_t)c1]);
-                batch.push_back(&jobs[(size_t)c1++]);
-            }
-            if (train_batch(batch.data(), (int)batch.size(), epsilon, val_auto, max_iterations)) return 1;
-            c0 = c1;
-        }
-        return 0;
-    });
-}
-
-// ---- a grid of (N, M) points at once --------------------------------------------------------------------
-// The sequences a grid's models train on: host symbols and S + 1 offsets from 0.  Each model trains on a range of them;
-// the models of different N of one class and M share theirs.
+// ---- many models at once: a grid of (N, M) points, or every class of one (N, M) ------------------
+// The sequences a batch's models train on: host symbols and S + 1 offsets from 0.  Each model trains on a range of them;
+// the models of different N of one class and M share theirs, the classes of `--all-classes` have disjoint ones.
 struct SeqStore {
     const uint16_t* sym = nullptr;
     const i64* offs = nullptr;
+};
+
+// The sequences of one batch (of trainings or of scorings): the jobs' ranges [s_lo, s_hi) of the store merged into
+// disjoint runs that follow one another, so that a sequence goes to the device once however many jobs use it.
+struct BatchSeqs {
+    std::vector<std::pair<int, int>> merged;  // the runs, as ranges of the store, ascending
+    std::vector<int> run_at;                  // batch index of each run's first sequence
+    std::vector<i64> offs;                    // the batch's sequences: their symbol offsets, from 0
+    BatchSeqs(std::vector<std::pair<int, int>> ranges, const SeqStore& ss) : offs(1, 0)
+    {
+        std::sort(ranges.begin(), ranges.end());
+        for (const auto& r : ranges) {
+            if (!merged.empty() && r.first <= merged.back().second)
+                merged.back().second = std::max(merged.back().second, r.second);
+            else
+                merged.push_back(r);
+        }
+        for (const auto& r : merged) {
+            run_at.push_back((int)offs.size() - 1);
+            for (int s = r.first; s < r.second; ++s) offs.push_back(offs.back() + (ss.offs[s + 1] - ss.offs[s]));
+        }
+    }
+    int local(int s) const  // batch index of the store's sequence s (one of a range given)
+    {
+        const auto it = std::upper_bound(merged.begin(), merged.end(), std::make_pair(s, INT32_MAX));
+        const size_t q = (size_t)(it - merged.begin()) - 1;
+        return run_at[q] + (s - merged[q].first);
+    }
+    // d_sym: offs.back() symbols.  A run goes up in pieces of 128 KB: the store is pageable caller memory, and a copy of
+    // megabytes from it makes the runtime pin the pages first, at a cost that varies from call to call; pieces of this
+    // size go through the runtime's staging buffer instead (docs/HISTORY.md, "one batched HMM trainer")
+    int upload_symbols(const SeqStore& ss, unsigned short* d_sym, hipStream_t st) const
+    {
+        constexpr i64 PIECE = 65536;
+        for (size_t q = 0; q < merged.size(); ++q) {
+            const i64 a = ss.offs[merged[q].first], b = ss.offs[merged[q].second];
+            for (i64 c = a; c < b; c += PIECE)
+                HIPCHK(hipMemcpyAsync(d_sym + offs[(size_t)run_at[q]] + (c - a), ss.sym + c, (size_t)std::min(PIECE, b - c) * 2,
+                                      hipMemcpyHostToDevice, st));
+        }
+        return 0;
+    }
 };
 
 // One model of a grid, trained exactly as `train` trains it alone on the store's sequences [s_lo, s_hi)
@@ -817,34 +684,17 @@ i64 grid_model_bytes(const GridJob& j, const SeqStore& ss)
 // leaves the launches; its parameters on the device are not touched again.
 int train_grid_batch(GridJob* const* jobs, int K, const SeqStore& ss, double epsilon, double val_auto, int max_iterations)
 {
-    std::vector<std::pair<int, int>> runs;
-    for (int k = 0; k < K; ++k) runs.emplace_back(jobs[k]->s_lo, jobs[k]->s_hi);
-    std::sort(runs.begin(), runs.end());
-    std::vector<std::pair<int, int>> merged;
-    for (const auto& r : runs) {
-        if (!merged.empty() && r.first <= merged.back().second)
-            merged.back().second = std::max(merged.back().second, r.second);
-        else
-            merged.push_back(r);
-    }
-    std::vector<i64> offs(1, 0);  // the batch's sequences: the runs one after the other
-    std::vector<int> run_at;      // batch index of each run's first sequence
-    for (const auto& r : merged) {
-        run_at.push_back((int)offs.size() - 1);
-        for (int s = r.first; s < r.second; ++s) offs.push_back(offs.back() + (ss.offs[s + 1] - ss.offs[s]));
-    }
-    auto local = [&](int s) {  // batch index of the store's sequence s
-        size_t q = 0;
-        while (q + 1 < merged.size() && merged[q + 1].first <= s) ++q;
-        return run_at[q] + (s - merged[q].first);
-    };
+    std::vector<std::pair<int, int>> ranges;
+    for (int k = 0; k < K; ++k) ranges.emplace_back(jobs[k]->s_lo, jobs[k]->s_hi);
+    const BatchSeqs seqs(std::move(ranges), ss);
+    const std::vector<i64>& offs = seqs.offs;
     std::vector<e2hmm::GridModelDev> g((size_t)K);
     i64 n_alpha = 0, n_c = 0, n_acc = 0, n_par = 0;
     int n_res = 0, max_blocks = 0, big_N = 0;
     for (int k = 0; k < K; ++k) {
         const Hmm& h = jobs[k]->h;
         e2hmm::GridModelDev& m = g[(size_t)k];
-        m.s_lo = local(jobs[k]->s_lo);
+        m.s_lo = seqs.local(jobs[k]->s_lo);
         m.s_hi = m.s_lo + jobs[k]->S();
         const i64 T = offs[(size_t)m.s_hi] - offs[(size_t)m.s_lo];
         m.alpha_at = n_alpha;
@@ -856,20 +706,14 @@ int train_grid_batch(GridJob* const* jobs, int K, const SeqStore& ss, double eps
         m.acc_at = n_acc;
         n_acc += e2hmm::acc_words(h.N, h.M);
         m.param_at = n_par;
-        n_par += (i64)h.N + (i64)h.N * h.N + (i64)h.N * h.M;
+        n_par += (i64)h.params();
         if (h.N <= e2hmm::WAVE_N)
             max_blocks += e2hmm::fb_class_workgroups(jobs[k]->S());
         else
             big_N = std::max(big_N, h.N);
     }
     std::vector<double> flat((size_t)n_par);
-    for (int k = 0; k < K; ++k) {
-        const Hmm& h = jobs[k]->h;
-        double* q = flat.data() + g[(size_t)k].param_at;
-        std::copy(h.pi.begin(), h.pi.end(), q);
-        std::copy(h.A.begin(), h.A.end(), q + h.N);
-        std::copy(h.B.begin(), h.B.end(), q + h.N + (size_t)h.N * h.N);
-    }
+    for (int k = 0; k < K; ++k) jobs[k]->h.pack(flat.data() + g[(size_t)k].param_at);
     DeviceBuffer<double> d_params, d_alpha, d_c, d_mant;
     DeviceBuffer<i64> d_acc, d_exp, d_offs, d_scratch;
     DeviceBuffer<int> d_status, d_blocks, d_active;
@@ -883,11 +727,7 @@ int train_grid_batch(GridJob* const* jobs, int K, const SeqStore& ss, double eps
         d_status.reserve((size_t)n_res) || d_blocks.reserve((size_t)max_blocks * 3) || d_active.reserve((size_t)K))
         return 1;
     if (big_N && d_scratch.reserve((size_t)e2hmm::fb_scratch_words(big_N))) return 1;
-    for (size_t q = 0; q < merged.size(); ++q) {
-        const i64 a = ss.offs[merged[q].first], b = ss.offs[merged[q].second];
-        if (b > a)
-            HIPCHK(hipMemcpyAsync(d_sym.get() + offs[(size_t)run_at[q]], ss.sym + a, (size_t)(b - a) * 2, hipMemcpyHostToDevice, st.s));
-    }
+    if (seqs.upload_symbols(ss, d_sym.get(), st.s)) return 1;
     for (int k = 0; k < K; ++k) {
         e2hmm::GridModelDev& m = g[(size_t)k];
         const double* q = d_params.get() + m.param_at;
@@ -968,7 +808,7 @@ int train_grid_batch(GridJob* const* jobs, int K, const SeqStore& ss, double eps
             } else {
                 mstep_list.push_back(k);
                 Lprev[(size_t)k] = L;
-                max_P = std::max(max_P, (i64)m.md.N + (i64)m.md.N * m.md.N + (i64)m.md.N * m.md.M);
+                max_P = std::max(max_P, (i64)jobs[k]->h.params());
                 max_N = std::max(max_N, m.md.N);
             }
         }
@@ -981,13 +821,7 @@ int train_grid_batch(GridJob* const* jobs, int K, const SeqStore& ss, double eps
     }
     HIPCHK(hipMemcpyAsync(flat.data(), d_params.get(), flat.size() * 8, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
-    for (int k = 0; k < K; ++k) {
-        Hmm& h = jobs[k]->h;
-        const double* q = flat.data() + g[(size_t)k].param_at;
-        std::copy(q, q + h.N, h.pi.begin());
-        std::copy(q + h.N, q + h.N + (size_t)h.N * h.N, h.A.begin());
-        std::copy(q + h.N + (size_t)h.N * h.N, q + h.N + (size_t)h.N * h.N + (size_t)h.N * h.M, h.B.begin());
-    }
+    for (int k = 0; k < K; ++k) jobs[k]->h.unpack(flat.data() + g[(size_t)k].param_at);
     return 0;
 }
 
@@ -1035,6 +869,76 @@ int train_grid(std::vector<GridJob>& jobs, const SeqStore& ss, double epsilon, d
         }
         return 0;
     });
+}
+
+// What `hmm learn --all-classes` and `hmm learn --grid` do once their checks have passed: one model per (N, M, class)
+// -- the N of n_list in its order; the M of the sequences' headers, ascending; the classes present at that M in byte
+// order of their names -- each trained on the files of its class and M in list order, all models in one batched
+// training.  Every model starts from the generator state of entry (the draw a fresh seeded call would make; after the
+// last model the generator is where that call leaves it) and gets byte for byte what ecoz2_hmm_learn writes and prints
+// for its files alone; files are written only once every model has trained.
+int learn_models(const SeqSet& ss, const std::vector<int>& n_list, int model_type, double hmm_epsilon, double val_auto,
+                 int max_iterations, hmm_learn_callback_t callback)
+{
+    // (std::map: M ascending; std::string's order is the bytes', as strcmp's)
+    std::map<int, std::map<std::string, std::vector<int>>> by_M;
+    for (int i = 0; i < ss.S(); ++i) by_M[ss.Ms[(size_t)i]][ss.classes[(size_t)i]].push_back(i);
+    // the store: each (M, class)'s symbols contiguous, in list order, groups in grid order
+    struct Group {
+        std::string name;
+        int M, s_lo, s_hi;
+        i64 max_T;
+    };
+    std::vector<uint16_t> sym;
+    std::vector<i64> offs(1, 0);
+    std::vector<Group> groups;
+    for (const auto& mv : by_M)
+        for (const auto& kv : mv.second) {
+            Group gr{kv.first, mv.first, (int)offs.size() - 1, 0, 0};
+            for (int i : kv.second) {
+                const i64 a = ss.offs[(size_t)i], b = ss.offs[(size_t)i + 1];
+                sym.insert(sym.end(), ss.sym.begin() + a, ss.sym.begin() + b);
+                offs.push_back((i64)sym.size());
+                gr.max_T = std::max(gr.max_T, b - a);
+            }
+            gr.s_hi = (int)offs.size() - 1;
+            groups.push_back(gr);
+        }
+    std::vector<GridJob> jobs;
+    std::vector<const Group*> job_group;
+    const uint64_t rng0 = g_rng;
+    for (int N : n_list)
+        for (const Group& gr : groups) {
+            GridJob j;
+            j.h.class_name = gr.name;
+            j.h.resize(N, gr.M);
+            j.s_lo = gr.s_lo;
+            j.s_hi = gr.s_hi;
+            g_rng = rng0;
+            if (hmm_init(j.h, model_type)) return 1;
+            jobs.push_back(std::move(j));
+            job_group.push_back(&gr);
+        }
+    SeqStore store;
+    store.sym = sym.data();
+    store.offs = offs.data();
+    if (train_grid(jobs, store, hmm_epsilon, val_auto, max_iterations, env_workers(), env_device())) return 1;
+    const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
+    static char var[] = "sum_log_prob";
+    for (size_t k = 0; k < jobs.size(); ++k) {
+        const GridJob& j = jobs[k];
+        printf("\nHMM learn: class '%s'  N=%d M=%d type=%d  #sequences = %d  max_T=%lld\n", j.h.class_name.c_str(), j.h.N, j.h.M,
+               model_type, j.S(), (long long)job_group[k]->max_T);
+        printf("  epsilon=%g  val_auto=%g  max_iterations=%d\n", hmm_epsilon, val_auto, max_iterations);
+        for (size_t i = 0; i < j.hist.size(); ++i) {
+            if (verbose) print_iteration((int)i, j.hist[i], j.skipped[i]);
+            if (callback) callback(var, j.hist[i]);
+        }
+        std::string path;
+        if (save_learned(j.h, model_type, val_auto, max_iterations, j.hist, &path)) return 1;
+        printf("%zu E-step(s); model saved: %s\n", j.hist.size(), path.c_str());
+    }
+    return 0;
 }
 
 // classification report shared by ecoz2_hmm_classify / ecoz2_hmm_classify_predictors
@@ -1120,35 +1024,17 @@ int score_pack_width_in_use(int N)
 // through launch_score (k_hmm_score_wg).  Every launch is enqueued before the one copy back and synchronisation.
 int score_grid_batch(const ScoreJob* jobs, int K, const SeqStore& ss)
 {
-    std::vector<std::pair<int, int>> runs;
-    for (int k = 0; k < K; ++k) runs.emplace_back(jobs[k].s_lo, jobs[k].s_hi);
-    std::sort(runs.begin(), runs.end());
-    std::vector<std::pair<int, int>> merged;
-    for (const auto& r : runs) {
-        if (!merged.empty() && r.first <= merged.back().second)
-            merged.back().second = std::max(merged.back().second, r.second);
-        else
-            merged.push_back(r);
-    }
-    std::vector<i64> offs(1, 0);  // the batch's sequences: the runs one after the other
-    std::vector<int> run_at;      // batch index of each run's first sequence
-    for (const auto& r : merged) {
-        run_at.push_back((int)offs.size() - 1);
-        for (int s = r.first; s < r.second; ++s) offs.push_back(offs.back() + (ss.offs[s + 1] - ss.offs[s]));
-    }
-    auto local = [&](int s) {  // batch index of the store's sequence s
-        const auto it = std::upper_bound(merged.begin(), merged.end(), std::make_pair(s, INT32_MAX));
-        const size_t q = (size_t)(it - merged.begin()) - 1;
-        return run_at[q] + (s - merged[q].first);
-    };
+    std::vector<std::pair<int, int>> ranges;
+    for (int k = 0; k < K; ++k) ranges.emplace_back(jobs[k].s_lo, jobs[k].s_hi);
+    const BatchSeqs seqs(std::move(ranges), ss);
+    const std::vector<i64>& offs = seqs.offs;
     // parameters, model table, result slots
     std::vector<e2hmm::ScoreModelDev> table((size_t)K);
     std::vector<i64> param_at((size_t)K), res_at((size_t)K), res_stride((size_t)K, 1);
     i64 n_par = 0, n_res = 0;
     for (int k = 0; k < K; ++k) {
-        const Hmm& h = *jobs[k].h;
         param_at[(size_t)k] = n_par;
-        n_par += (i64)h.N + (i64)h.N * h.N + (i64)h.N * h.M;
+        n_par += (i64)jobs[k].h->params();
     }
     struct Big {  // a group of N > 64: the models [k0, k0 + count) through launch_score, results at [s * count + i]
         int k0, count, s_lo, S;
@@ -1162,7 +1048,7 @@ int score_grid_batch(const ScoreJob* jobs, int K, const SeqStore& ss)
         const ScoreJob& a = jobs[k0];
         int k1 = k0 + 1;
         while (k1 < K && jobs[k1].h->N == a.h->N && jobs[k1].h->M == a.h->M && jobs[k1].s_lo == a.s_lo && jobs[k1].s_hi == a.s_hi) ++k1;
-        const int N = a.h->N, S = a.S(), lo = local(a.s_lo);
+        const int N = a.h->N, S = a.S(), lo = seqs.local(a.s_lo);
         if (N > e2hmm::WAVE_N) {
             bigs.push_back(Big{k0, k1 - k0, lo, S, n_res});
             for (int k = k0; k < k1; ++k) {
@@ -1186,13 +1072,7 @@ int score_grid_batch(const ScoreJob* jobs, int K, const SeqStore& ss)
         k0 = k1;
     }
     std::vector<double> flat((size_t)n_par);
-    for (int k = 0; k < K; ++k) {
-        const Hmm& h = *jobs[k].h;
-        double* q = flat.data() + param_at[(size_t)k];
-        std::copy(h.pi.begin(), h.pi.end(), q);
-        std::copy(h.A.begin(), h.A.end(), q + h.N);
-        std::copy(h.B.begin(), h.B.end(), q + h.N + (size_t)h.N * h.N);
-    }
+    for (int k = 0; k < K; ++k) jobs[k].h->pack(flat.data() + param_at[(size_t)k]);
     std::vector<int> blocks;
     for (const auto& kv : blocks_by_N) blocks.insert(blocks.end(), kv.second.begin(), kv.second.end());
     DeviceBuffer<double> d_params, d_mant;
@@ -1208,11 +1088,7 @@ int score_grid_batch(const ScoreJob* jobs, int K, const SeqStore& ss)
         d_mant.reserve((size_t)n_res) || d_exp.reserve((size_t)n_res) || d_status.reserve((size_t)n_res) ||
         d_blocks.upload(blocks.data(), blocks.size(), st.s) || d_packs.upload(packs.data(), packs.size(), st.s))
         return 1;
-    for (size_t q = 0; q < merged.size(); ++q) {
-        const i64 a = ss.offs[merged[q].first], b = ss.offs[merged[q].second];
-        if (b > a)
-            HIPCHK(hipMemcpyAsync(d_sym.get() + offs[(size_t)run_at[q]], ss.sym + a, (size_t)(b - a) * 2, hipMemcpyHostToDevice, st.s));
-    }
+    if (seqs.upload_symbols(ss, d_sym.get(), st.s)) return 1;
     std::vector<ModelDev> big_table;
     for (int k = 0; k < K; ++k) {
         const double* q = d_params.get() + param_at[(size_t)k];
@@ -1499,10 +1375,8 @@ extern "C" int ecoz2_hmm_learn(int N, int model_type, const char* const* sequenc
     return 0;
 }
 
-// `hmm learn --all-classes`: one model per class name found in the sequences' headers, classes in byte
-// order of their names, each class's files in list order.  Every class starts from the generator state of entry (a
-// seeded single call's draw) and gets byte for byte what ecoz2_hmm_learn writes and prints for its files alone; all the
-// checks run before any HIP call, and files are written only once every class has trained.
+// `hmm learn --all-classes`: learn_models over one N, after this entry point's own checks (all before
+// any HIP call).  Unlike the grid, sequences of different codebook sizes are refused.
 extern "C" int e2vq_hmm_learn_classes(int N, int model_type, const char* const* sequence_filenames, unsigned num_sequences,
                                       double hmm_epsilon, double val_auto, int max_iterations, hmm_learn_callback_t callback)
 {
@@ -1514,58 +1388,11 @@ extern "C" int e2vq_hmm_learn_classes(int N, int model_type, const char* const* 
     if (load_sequences(sequence_filenames, num_sequences, ss)) return 1;
     for (uint16_t v : ss.sym)
         if ((int)v >= ss.M) return e2vq_set_error("symbol %u outside the codebook size %d", v, ss.M);
-    std::map<std::string, std::vector<int>> by_class;  // (std::string's order is the bytes', as strcmp's)
-    for (int i = 0; i < ss.S(); ++i) by_class[ss.classes[(size_t)i]].push_back(i);
-    // each class's symbols contiguous, in list order
-    std::vector<std::vector<uint16_t>> syms;
-    std::vector<ClassJob> jobs;
-    std::vector<i64> max_T;
-    const uint64_t rng0 = g_rng;
-    for (const auto& kv : by_class) {
-        ClassJob c;
-        std::vector<uint16_t> sy;
-        c.offs.assign(1, 0);
-        i64 mt = 0;
-        for (int i : kv.second) {
-            const i64 a = ss.offs[(size_t)i], b = ss.offs[(size_t)i + 1];
-            sy.insert(sy.end(), ss.sym.begin() + a, ss.sym.begin() + b);
-            c.offs.push_back((i64)sy.size());
-            mt = std::max(mt, b - a);
-        }
-        c.h.class_name = kv.first;
-        c.h.resize(N, ss.M);
-        g_rng = rng0;  // the draw a fresh seeded call would make; after the last class: where that call leaves it
-        if (hmm_init(c.h, model_type)) return 1;
-        syms.push_back(std::move(sy));
-        jobs.push_back(std::move(c));
-        max_T.push_back(mt);
-    }
-    for (size_t k = 0; k < jobs.size(); ++k) jobs[k].sym = syms[k].data();
-    if (train_classes(jobs, hmm_epsilon, val_auto, max_iterations, env_workers(), env_device())) return 1;
-    const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
-    static char var[] = "sum_log_prob";
-    for (size_t k = 0; k < jobs.size(); ++k) {
-        const ClassJob& c = jobs[k];
-        printf("\nHMM learn: class '%s'  N=%d M=%d type=%d  #sequences = %d  max_T=%lld\n", c.h.class_name.c_str(), N, ss.M,
-               model_type, c.S(), (long long)max_T[k]);
-        printf("  epsilon=%g  val_auto=%g  max_iterations=%d\n", hmm_epsilon, val_auto, max_iterations);
-        for (size_t i = 0; i < c.hist.size(); ++i) {
-            if (verbose) print_iteration((int)i, c.hist[i], c.skipped[i]);
-            if (callback) callback(var, c.hist[i]);
-        }
-        std::string path;
-        if (save_learned(c.h, model_type, val_auto, max_iterations, c.hist, &path)) return 1;
-        printf("%zu E-step(s); model saved: %s\n", c.hist.size(), path.c_str());
-    }
-    return 0;
+    return learn_models(ss, {N}, model_type, hmm_epsilon, val_auto, max_iterations, callback);
 }
 
-// `hmm learn --grid`: one model per grid point (N, M, class) -- the N given, ascending; the M of the
-// sequences' headers, ascending; the classes present at that M in byte order of their names -- each trained on the files
-// of its class and M in list order, all models in one batched training.  Every model starts from the generator state of
-// entry and gets byte for byte what e2vq_hmm_learn_classes(N, ...) of the files of that M writes and prints for its class;
-// the generator is left where a seeded single call for the last model leaves it.  All the checks run before any HIP call,
-// and files are written only once every model has trained.
+// `hmm learn --grid`: learn_models over the N given, ascending, after this entry point's own checks
+// (all before any HIP call).  Each model gets what e2vq_hmm_learn_classes(N, ...) of the files of its M gives its class.
 extern "C" int e2vq_hmm_learn_grid(const int* Ns, int num_N, int model_type, const char* const* sequence_filenames,
                                    unsigned num_sequences, double hmm_epsilon, double val_auto, int max_iterations,
                                    hmm_learn_callback_t callback)
@@ -1587,65 +1414,7 @@ extern "C" int e2vq_hmm_learn_grid(const int* Ns, int num_N, int model_type, con
             if ((int)ss.sym[(size_t)t] >= ss.Ms[(size_t)i])
                 return e2vq_set_error("%s: symbol %u outside the codebook size %d", ss.files[(size_t)i].c_str(), ss.sym[(size_t)t],
                                       ss.Ms[(size_t)i]);
-    // (std::map: M ascending; std::string's order is the bytes', as strcmp's)
-    std::map<int, std::map<std::string, std::vector<int>>> by_M;
-    for (int i = 0; i < ss.S(); ++i) by_M[ss.Ms[(size_t)i]][ss.classes[(size_t)i]].push_back(i);
-    // the store: each (M, class)'s symbols contiguous, in list order, groups in grid order
-    struct Group {
-        std::string name;
-        int M, s_lo, s_hi;
-        i64 max_T;
-    };
-    std::vector<uint16_t> sym;
-    std::vector<i64> offs(1, 0);
-    std::vector<Group> groups;
-    for (const auto& mv : by_M)
-        for (const auto& kv : mv.second) {
-            Group gr{kv.first, mv.first, (int)offs.size() - 1, 0, 0};
-            for (int i : kv.second) {
-                const i64 a = ss.offs[(size_t)i], b = ss.offs[(size_t)i + 1];
-                sym.insert(sym.end(), ss.sym.begin() + a, ss.sym.begin() + b);
-                offs.push_back((i64)sym.size());
-                gr.max_T = std::max(gr.max_T, b - a);
-            }
-            gr.s_hi = (int)offs.size() - 1;
-            groups.push_back(gr);
-        }
-    std::vector<GridJob> jobs;
-    std::vector<const Group*> job_group;
-    const uint64_t rng0 = g_rng;
-    for (int N : n_list)
-        for (const Group& gr : groups) {
-            GridJob j;
-            j.h.class_name = gr.name;
-            j.h.resize(N, gr.M);
-            j.s_lo = gr.s_lo;
-            j.s_hi = gr.s_hi;
-            g_rng = rng0;  // the draw a fresh seeded call would make; after the last model: where that call leaves it
-            if (hmm_init(j.h, model_type)) return 1;
-            jobs.push_back(std::move(j));
-            job_group.push_back(&gr);
-        }
-    SeqStore store;
-    store.sym = sym.data();
-    store.offs = offs.data();
-    if (train_grid(jobs, store, hmm_epsilon, val_auto, max_iterations, env_workers(), env_device())) return 1;
-    const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
-    static char var[] = "sum_log_prob";
-    for (size_t k = 0; k < jobs.size(); ++k) {
-        const GridJob& j = jobs[k];
-        printf("\nHMM learn: class '%s'  N=%d M=%d type=%d  #sequences = %d  max_T=%lld\n", j.h.class_name.c_str(), j.h.N, j.h.M,
-               model_type, j.S(), (long long)job_group[k]->max_T);
-        printf("  epsilon=%g  val_auto=%g  max_iterations=%d\n", hmm_epsilon, val_auto, max_iterations);
-        for (size_t i = 0; i < j.hist.size(); ++i) {
-            if (verbose) print_iteration((int)i, j.hist[i], j.skipped[i]);
-            if (callback) callback(var, j.hist[i]);
-        }
-        std::string path;
-        if (save_learned(j.h, model_type, val_auto, max_iterations, j.hist, &path)) return 1;
-        printf("%zu E-step(s); model saved: %s\n", j.hist.size(), path.c_str());
-    }
-    return 0;
+    return learn_models(ss, n_list, model_type, hmm_epsilon, val_auto, max_iterations, callback);
 }
 
 // fn ecoz2_hmm_classify(model_filenames, num_models, sequence_filenames, num_sequences, show_ranked,
@@ -2430,7 +2199,8 @@ extern "C" int e2vq_hmm_train(int device, int N, int M, double* pi, double* A, d
 
 // whole training of K classes on arrays, in place: class k = sequences [class_offs[k], class_offs[k + 1]),
 // model k at pi + k N, A + k N^2, B + k N M; its measure at sum_log_prob + k cap, its E-step count at num_esteps[k].
-// Class k's result is e2vq_hmm_train's on its slice, bit for bit.
+// Class k's result is e2vq_hmm_train's on its slice, bit for bit.  It is e2vq_hmm_train_grid's batch with one (N, M) for
+// every model and ranges that do not overlap.
 extern "C" int e2vq_hmm_train_classes(int device, int N, int M, int K, double* pi, double* A, double* B, const uint16_t* sym,
                                       const int64_t* offs, int S, const int64_t* class_offs, double epsilon, double val_auto,
                                       int max_iterations, double* sum_log_prob, int cap, int* num_esteps)
@@ -2446,18 +2216,20 @@ extern "C" int e2vq_hmm_train_classes(int device, int N, int M, int K, double* p
             return e2vq_set_error("class_offs not strictly increasing at class %d (%lld, %lld)", k, (long long)class_offs[k],
                                   (long long)class_offs[k + 1]);
     const size_t NN = (size_t)N * N, NM = (size_t)N * M;
-    std::vector<ClassJob> jobs((size_t)K);
+    std::vector<GridJob> jobs((size_t)K);
     for (int k = 0; k < K; ++k) {
-        ClassJob& c = jobs[(size_t)k];
+        GridJob& c = jobs[(size_t)k];
         if (model_from_arrays(N, M, pi + (size_t)k * N, A + (size_t)k * NN, B + (size_t)k * NM, c.h)) return 1;
-        const i64 s0 = class_offs[k], s1 = class_offs[k + 1];
-        c.sym = sym + offs[s0];
-        for (i64 s = s0; s <= s1; ++s) c.offs.push_back(offs[s] - offs[s0]);
+        c.s_lo = (int)class_offs[k];
+        c.s_hi = (int)class_offs[k + 1];
     }
     if (require_device(device)) return 1;
-    if (train_classes(jobs, epsilon, val_auto, max_iterations, 1, device)) return 1;
+    SeqStore store;
+    store.sym = sym;
+    store.offs = (const i64*)offs;
+    if (train_grid(jobs, store, epsilon, val_auto, max_iterations, 1, device)) return 1;
     for (int k = 0; k < K; ++k) {
-        const ClassJob& c = jobs[(size_t)k];
+        const GridJob& c = jobs[(size_t)k];
         memcpy(pi + (size_t)k * N, c.h.pi.data(), c.h.pi.size() * 8);
         memcpy(A + (size_t)k * NN, c.h.A.data(), c.h.A.size() * 8);
         memcpy(B + (size_t)k * NM, c.h.B.data(), c.h.B.size() * 8);
@@ -2512,10 +2284,7 @@ extern "C" int e2vq_hmm_train_grid(int device, int K, const int* Ns, const int* 
     if (train_grid(jobs, store, epsilon, val_auto, max_iterations, 1, device)) return 1;
     for (int k = 0; k < K; ++k) {
         const GridJob& j = jobs[(size_t)k];
-        double* q = params + param_offs[k];
-        memcpy(q, j.h.pi.data(), j.h.pi.size() * 8);
-        memcpy(q + j.h.N, j.h.A.data(), j.h.A.size() * 8);
-        memcpy(q + j.h.N + j.h.A.size(), j.h.B.data(), j.h.B.size() * 8);
+        j.h.pack(params + param_offs[k]);
         for (size_t i = 0; i < j.hist.size() && (int)i < cap; ++i) sum_log_prob[(size_t)k * cap + i] = j.hist[i];
         if (num_esteps) num_esteps[k] = (int)j.hist.size();
     }

@@ -165,10 +165,10 @@ int e2vq_hmm_train(int device, int N, int M, double *pi, double *A, double *B, c
  * going.  Stdout: the single call's block per class, in class order, after all training; the callback gets the classes'
  * ("sum_log_prob", L) class after class.  An empty list, N outside [1, 512], a model type outside 0..3, differing M or a
  * symbol >= M return 1 before any HIP call; no file is written unless every class trained.
- * ECOZ2_HMM_LEARN_BATCH_BYTES (default 4 GiB): the device bytes one batch of classes may take for alpha^, c and the
- * accumulators ((T_k (N + 1) + e2vq_hmm_acc_words(N, M)) * 8 per class); classes are packed in order, greedily, a larger
- * class alone.  ECOZ2_VQ_GPUS = W: whole classes dealt to W workers in contiguous ranges balanced by symbol count.
- * Neither changes a byte of the output. */
+ * The classes are the grid batch below with one (N, M): ECOZ2_HMM_LEARN_BATCH_BYTES (default 4 GiB) is the device bytes
+ * one batch of classes may take for alpha^, c and the accumulators ((T_k (N + 1) + e2vq_hmm_acc_words(N, M)) * 8 per class)
+ * and its symbols (2 T_k); classes are packed in order, greedily, a larger class alone.  ECOZ2_VQ_GPUS = W: whole classes
+ * dealt to W workers in contiguous ranges balanced by those bytes.  Neither changes a byte of the output. */
 int e2vq_hmm_learn_classes(int N, int model_type, const char *const *sequence_filenames, unsigned num_sequences,
                            double hmm_epsilon, double val_auto, int max_iterations,
                            void (*callback)(char *variable, double value));

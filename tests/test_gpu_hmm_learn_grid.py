@@ -2,7 +2,10 @@
 single training's, bit for bit -- on arrays (e2vq_hmm_train_grid against e2vq_hmm_train and the oracle, across both
 E-step paths, overlapping sequence ranges and models that stop at different iterations), on files (e2vq_hmm_learn_grid
 against a loop of seeded e2vq_hmm_learn_classes calls, one per (N, M): .hmm, .csv, stdout, callbacks, the generator state
-after the call), for any ECOZ2_VQ_GPUS and ECOZ2_HMM_LEARN_BATCH_BYTES, and through the CLI."""
+after the call), for any ECOZ2_VQ_GPUS and ECOZ2_HMM_LEARN_BATCH_BYTES, and through the CLI.
+e2vq_hmm_learn_classes runs on the same batched trainer as the grid, so the file comparisons show that one grid call
+equals many one-(N, M) calls of it, not that either is right: the independent reference is the single-class training
+(the array tests here, and test_gpu_hmm_learn_classes.py against seeded ecoz2_hmm_learn loops)."""
 import os
 import subprocess
 

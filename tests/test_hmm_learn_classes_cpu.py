@@ -1,20 +1,12 @@
 """`hmm learn --all-classes`, CPU side: the argument checks of e2vq_hmm_learn_classes /
-e2vq_hmm_train_classes run before any HIP call (so they answer the same with or without a device) and write no file;
-the class-batched kernels are in the gfx950 build without scratch or spilled registers.  The GPU parity tests are in
-test_gpu_hmm_learn_classes.py."""
-import os
-import re
-import subprocess
-
+e2vq_hmm_train_classes run before any HIP call (so they answer the same with or without a device) and write no file.
+The classes train as the one-(N, M) case of the grid batch, whose kernels test_hmm_learn_grid_cpu.py guards.  The GPU
+parity tests are in test_gpu_hmm_learn_classes.py."""
 import numpy as np
 import pytest
 
 import ecoz2rs_amd as e
 from ecoz2rs_amd import hmm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ecoz2rs_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _err():
@@ -108,34 +100,3 @@ def test_train_classes_refuses_before_the_device(kw, needle):
 def test_python_train_classes_checks_the_class_count():
     with pytest.raises(ValueError):
         hmm.train_classes([(np.ones(2) / 2, np.ones((2, 2)) / 2, np.ones((2, 4)) / 4)], [[], []])
-
-
-# ---- ISA guard (style of test_isa_guards.py) ---------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def asm(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = str(tmp_path_factory.mktemp("isa") / "hmm_device.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-x", "hip",
-                    "--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, "hmm_device.hip")], check=True,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
-    return open(out).read()
-
-
-def _meta(text, pattern):
-    metas = [(m.group(1), m.group(2)) for m in re.finditer(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S)
-             if re.search(pattern, m.group(1))]
-    assert len(metas) == 1, f"{pattern}: {[n for n, _ in metas]}"
-    g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", metas[0][1]).group(1))
-    return dict(vgpr=g("vgpr_count"), spill=g("vgpr_spill_count"), scratch=g("private_segment_fixed_size"))
-
-
-@pytest.mark.parametrize("kernel", ["k_hmm_fb_classes", "k_hmm_reestimate_classes", "k_hmm_adjustb_classes"])
-def test_batched_kernels_have_no_scratch_and_no_spill(asm, kernel):
-    m = _meta(asm, kernel)
-    assert m["scratch"] == 0 and m["spill"] == 0, m
-
-
-def test_batched_estep_keeps_the_single_class_register_budget(asm):
-    """the class-batched E-step runs k_hmm_fb's body: it must not need more registers (occupancy of the 4-wave groups)"""
-    assert _meta(asm, r"k_hmm_fb_classes")["vgpr"] <= _meta(asm, r"8k_hmm_fbENS")["vgpr"]

@@ -4,8 +4,8 @@ JSON record (optionally also written to --out).
 For each N (default 5, 64, 70): K = 20 classes, each with its own random model (e2vq_hmm_init type 3) with M = 1024 and
 S = 200 sequences of T = 300 symbols drawn around a class-specific ramp.  Every training runs exactly --iters E-steps
 (val_auto = -inf, max_iterations = --iters):
-  batched  e2vq_hmm_train_classes over the K classes: per iteration one k_hmm_fb_classes launch (N <= 64; above, one
-           k_hmm_fb_wg launch per class), one copy back, one k_hmm_reestimate_classes / k_hmm_adjustb_classes
+  batched  e2vq_hmm_train_classes over the K classes (the grid batch of one (N, M)): per iteration one k_hmm_fb_grid launch
+           (N <= 64; above, one k_hmm_fb_wg launch per class), one copy back, one k_hmm_reestimate_grid / k_hmm_adjustb_grid
   loop     e2vq_hmm_train once per class, one class after the other, in the same warm process
 Wall times: --warmup + --reps calls of each in a plain run (no tracer), the median of the timed calls.  Kernel times: a
 `rocprofv3 --kernel-trace` run of its own (the same calls); every k_hmm_* launch of a call is summed, the warm-up calls
