@@ -114,4 +114,37 @@ void launch_viterbi(const ModelDev& lm, const unsigned short* sym, const long lo
 void launch_backtrack(int N, const long long* offs, int S, long long psi0, const unsigned short* psi, const int* qlast,
                       const int* status, unsigned short* path, hipStream_t st);
 
+// Joint Viterbi over all class models (hmm_segment.hip).  The classes are packed in class order into
+// wave-slots of 64 lanes, class k on N_k consecutive lanes of one slot; the composite index of (k, j) is sum_{k' < k} N_k' + j.
+constexpr int SEG_MAX_N = 64;               // states of one class: a class never straddles a wave
+constexpr int SEG_MAX_SUM_N = 4096;         // states of all classes
+constexpr int SEG_MAX_WAVES = 16;           // waves of a workgroup: up to here a wave per slot (the resident body)
+constexpr size_t SEG_LDS_BYTES = 160 * 1024;  // lA of all classes lives in LDS when it fits next to the rest
+struct SegLaneDev {  // one lane of one slot; a lane without a state: cls = -1, j = N = a_at = 0, seg = its own lane
+    int cls, j, N;
+    int seg;   // the lane of state 0 of the class
+    int comp;  // composite index
+    int a_at;  // lA of the class at this many doubles into the lA area
+};
+struct SegPlanDev {
+    int K, M, sumN, slots;
+    int a_words;                      // sum_k N_k^2
+    const SegLaneDev* lanes;          // [slots][64]
+    const int* slot_info;             // [slots][2]: the largest N of the slot, 1 when the slot holds one class
+    const double* params;             // lpi of every class (sumN) | lA of every class (a_words) | lB (sumN rows of M)
+    const unsigned short* comp_cls;   // [sumN]: composite index -> class
+    const int* cls_comp0;             // [K]: class -> composite index of its state 0
+};
+// S streams (a workgroup each) from offs[0] on; psi ((frames of the launch) x sumN u16) and gsel (frames of the launch) are
+// indexed relative to psi0 = the first stream's offset, gbest by the absolute frame; logp / qlast (composite index of
+// q_{T-1}) / status at [s].  looped: the body that takes any number of slots.  Returns 1 when the shape cannot be launched.
+int launch_segment(const SegPlanDev& pl, bool looped, const unsigned short* sym, const long long* offs, int S, long long psi0,
+                   double ln_switch, unsigned short* psi, int* gsel, double* gbest, double* logp, int* qlast, int* status,
+                   hipStream_t st);
+// cls / state / entered of each of the S streams (absolute frames) from what launch_segment left; a stream of status 2
+// gets 0xFFFF, 0xFFFF, 0 and gbest = -inf from its frame 1 on
+void launch_segment_backtrack(const SegPlanDev& pl, const long long* offs, int S, long long psi0, const unsigned short* psi,
+                              const int* gsel, const int* qlast, const int* status, unsigned short* cls, unsigned short* state,
+                              unsigned char* entered, double* gbest, hipStream_t st);
+
 }  // namespace e2hmm

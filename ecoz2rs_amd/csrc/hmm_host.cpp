@@ -1324,6 +1324,164 @@ bool ends_with(const std::string& s, const char* ext)
     return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
 }
 
+// ---- hmm segment: one Viterbi pass through the class loop of all models ------------------------------------
+thread_local float g_segment_kernel_ms = -1.f;  // e2vq_hmm_segment_last_kernel_ms
+
+// psi and g bytes per launch: whole streams up to ECOZ2_HMM_SEGMENT_CHUNK_BYTES (default 256 MiB); a longer stream alone
+i64 segment_chunk_bytes()
+{
+    const char* v = getenv("ECOZ2_HMM_SEGMENT_CHUNK_BYTES");
+    const i64 b = v && *v ? atoll(v) : (i64)256 << 20;
+    return std::max<i64>(b, 1);
+}
+
+int segment_check_shape(const char* who, int K, const int* Ns)
+{
+    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
+    i64 sum = 0;
+    for (int k = 0; k < K; ++k) {
+        if (Ns[k] < 1 || Ns[k] > e2hmm::SEG_MAX_N)
+            return e2vq_set_error("%s: model %d has N=%d states (1 .. %d)", who, k, Ns[k], e2hmm::SEG_MAX_N);
+        sum += Ns[k];
+    }
+    if (sum > e2hmm::SEG_MAX_SUM_N)
+        return e2vq_set_error("%s: %lld states in all models (at most %d)", who, (long long)sum, e2hmm::SEG_MAX_SUM_N);
+    return 0;
+}
+
+int segment_check_switch(const char* who, double ln_switch)
+{
+    if (std::isnan(ln_switch) || ln_switch > 0.0)
+        return e2vq_set_error("%s: ln_switch = %g: the logarithm of a price, at most 0 (-inf forbids a new segment)", who, ln_switch);
+    return 0;
+}
+
+struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered, gbest; per stream: log_prob, status
+    uint16_t* cls = nullptr;
+    uint16_t* state = nullptr;
+    uint8_t* entered = nullptr;
+    double* gbest = nullptr;
+    double* log_prob = nullptr;
+    int* status = nullptr;
+};
+
+// The joint Viterbi of S device-resident streams (h_offs: their S + 1 offsets, on the host) under the class loop of the
+// models (already checked by segment_check_shape; all of one M; lflats: log_model of each), on the current device and the
+// stream st.
+int segment_device(const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats, const unsigned short* d_sym, const i64* h_offs, int S, double ln_switch,
+                   hipStream_t st, const SegOut& out)
+{
+    const int K = (int)ms.size(), M = ms[0]->M;
+    // logarithms: lpi of every class | lA of every class | lB of every class
+    int sumN = 0, a_words = 0;
+    std::vector<int> comp0((size_t)K), a_at((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        comp0[(size_t)k] = sumN;
+        a_at[(size_t)k] = a_words;
+        sumN += ms[(size_t)k]->N;
+        a_words += ms[(size_t)k]->N * ms[(size_t)k]->N;
+    }
+    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M);
+    for (int k = 0; k < K; ++k) {
+        const std::vector<double>& lflat = lflats[(size_t)k];
+        const size_t N = (size_t)ms[(size_t)k]->N;
+        std::copy(lflat.begin(), lflat.begin() + N, params.begin() + comp0[(size_t)k]);
+        std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + a_at[(size_t)k]);
+        std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + a_words + (size_t)comp0[(size_t)k] * M);
+    }
+    // the packing: class after class, a class that does not fit the current slot opens the next
+    std::vector<e2hmm::SegLaneDev> lanes;
+    std::vector<int> slot_info;
+    std::vector<uint16_t> comp_cls((size_t)sumN);
+    int fill = 64;  // lanes taken of the current slot (64: none is open)
+    for (int k = 0; k < K; ++k) {
+        const int N = ms[(size_t)k]->N;
+        if (fill + N > 64) {
+            const int l0 = (int)lanes.size();
+            lanes.resize((size_t)l0 + 64);
+            for (int l = 0; l < 64; ++l) lanes[(size_t)(l0 + l)] = e2hmm::SegLaneDev{-1, 0, 0, l, 0, 0};
+            slot_info.push_back(0);
+            slot_info.push_back(0);
+            fill = 0;
+        }
+        const size_t l0 = lanes.size() - 64;
+        for (int j = 0; j < N; ++j) {
+            lanes[l0 + (size_t)(fill + j)] = e2hmm::SegLaneDev{k, j, N, fill, comp0[(size_t)k] + j, a_at[(size_t)k]};
+            comp_cls[(size_t)(comp0[(size_t)k] + j)] = (uint16_t)k;
+        }
+        int* info = &slot_info[slot_info.size() - 2];
+        info[0] = std::max(info[0], N);
+        info[1] = fill == 0 ? 1 : 0;  // (a second class in the slot clears it)
+        fill += N;
+    }
+    const int slots = (int)(lanes.size() / 64);
+    // the body: resident where the packing fits a workgroup's waves, unless ECOZ2_HMM_SEGMENT_BODY=looped
+    const char* body = getenv("ECOZ2_HMM_SEGMENT_BODY");
+    if (body && *body && strcmp(body, "resident") != 0 && strcmp(body, "looped") != 0)
+        return e2vq_set_error("ECOZ2_HMM_SEGMENT_BODY=%s: resident or looped", body);
+    const bool looped = slots > e2hmm::SEG_MAX_WAVES || (body && strcmp(body, "looped") == 0);
+
+    DeviceBuffer<double> d_params, d_logp, d_gbest;
+    DeviceBuffer<e2hmm::SegLaneDev> d_lanes;
+    DeviceBuffer<int> d_info, d_comp0, d_status, d_qlast, d_gsel;
+    DeviceBuffer<unsigned short> d_comp_cls, d_psi, d_cls, d_state;
+    DeviceBuffer<unsigned char> d_entered;
+    DeviceBuffer<i64> d_offs;
+    const i64 frames = h_offs[S];
+    if (d_params.upload(params.data(), params.size(), st) || d_lanes.upload(lanes.data(), lanes.size(), st) ||
+        d_info.upload(slot_info.data(), slot_info.size(), st) || d_comp0.upload(comp0.data(), comp0.size(), st) ||
+        d_comp_cls.upload(comp_cls.data(), comp_cls.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) ||
+        d_logp.reserve((size_t)S) || d_status.reserve((size_t)S) || d_qlast.reserve((size_t)S) || d_gbest.reserve((size_t)frames) ||
+        d_cls.reserve((size_t)frames) || d_state.reserve((size_t)frames) || d_entered.reserve((size_t)frames))
+        return 1;
+    const e2hmm::SegPlanDev pl{K, M, sumN, slots, a_words, d_lanes.get(), d_info.get(), d_params.get(), d_comp_cls.get(), d_comp0.get()};
+    // launches of whole streams whose psi (2 sumN bytes a frame) and g (4 bytes a frame) stay within the budget
+    const i64 budget = segment_chunk_bytes(), row = 2 * (i64)sumN + 4;
+    std::vector<std::pair<int, int>> chunks;
+    i64 max_frames = 0;
+    for (int s0 = 0; s0 < S;) {
+        int s1 = s0 + 1;
+        while (s1 < S && (h_offs[s1 + 1] - h_offs[s0]) * row <= budget) ++s1;
+        chunks.emplace_back(s0, s1);
+        max_frames = std::max(max_frames, h_offs[s1] - h_offs[s0]);
+        s0 = s1;
+    }
+    if (d_psi.reserve((size_t)max_frames * sumN) || d_gsel.reserve((size_t)max_frames)) {
+        const std::string why = e2vq_last_error();
+        return e2vq_set_error("hmm segment: no room for the back-pointer table of %lld frames x %d states (%lld bytes; "
+                              "ECOZ2_HMM_SEGMENT_CHUNK_BYTES bounds it by whole streams): %s",
+                              (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
+    }
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    // (one stream: a chunk's forward pass writes psi only after the previous chunk's backtrack has read it)
+    for (const auto& c : chunks) {
+        const int s0 = c.first, n = c.second - c.first;
+        if (e2hmm::launch_segment(pl, looped, d_sym, d_offs.get() + s0, n, h_offs[s0], ln_switch, d_psi.get(), d_gsel.get(), d_gbest.get(),
+                                  d_logp.get() + s0, d_qlast.get() + s0, d_status.get() + s0, st))
+            return e2vq_set_error("hmm segment: %d wave-slots of %d states cannot be launched", slots, sumN);
+        HIPCHK(hipGetLastError());
+        e2hmm::launch_segment_backtrack(pl, d_offs.get() + s0, n, h_offs[s0], d_psi.get(), d_gsel.get(), d_qlast.get() + s0,
+                                        d_status.get() + s0, d_cls.get(), d_state.get(), d_entered.get(), d_gbest.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    if (frames > 0) {
+        if (out.cls) HIPCHK(hipMemcpyAsync(out.cls, d_cls.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        if (out.state) HIPCHK(hipMemcpyAsync(out.state, d_state.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        if (out.entered) HIPCHK(hipMemcpyAsync(out.entered, d_entered.get(), (size_t)frames, hipMemcpyDeviceToHost, st));
+        if (out.gbest) HIPCHK(hipMemcpyAsync(out.gbest, d_gbest.get(), (size_t)frames * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (S > 0) {
+        if (out.log_prob) HIPCHK(hipMemcpyAsync(out.log_prob, d_logp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        if (out.status) HIPCHK(hipMemcpyAsync(out.status, d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_segment_kernel_ms)) return 1;
+    return 0;
+}
+
 }  // namespace
 
 // ==========================================================================================
@@ -2416,6 +2574,143 @@ extern "C" int e2vq_hmm_scan_report(const char* name, int64_t T, int K, const ch
     return 0;
 }
 
+// ---- input -> device symbols: the stage `hmm scan` and `hmm segment` share ----------------------------------------------------
+struct SymInput {
+    std::string path, csv;
+    int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
+    int sample_rate = 0;
+    int64_t samples = 0, T = 0;
+};
+struct SymInputs {
+    bool have_cb = false, need_cb = false;
+    int cbP = 0, cbM = 0;
+    std::vector<double> refl;
+    std::vector<SymInput> inputs;
+};
+struct SymStage {  // device buffers the inputs of one call reuse; symbols of the current input in d_sym
+    DeviceBuffer<double> d_frames;
+    DeviceBuffer<int32_t> d_status;
+    DeviceBuffer<unsigned short> d_sym;
+};
+struct VqSessionHolder {
+    e2vq_session* s = nullptr;
+    ~VqSessionHolder()
+    {
+        if (s) e2vq_session_destroy(s);
+    }
+};
+
+// the checks of the inputs against the models' M and the codebook, and the codebook itself: host only, no file written
+static int sym_inputs_check(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs,
+                            int P, int W_ms, int O_ms, const char* csv_dir_or_file, SymInputs& si)
+{
+    si.have_cb = cb_filename && *cb_filename;
+    if (si.have_cb) {
+        char cls[96];
+        if (e2vq_cbook_info(cb_filename, cls, &si.cbP, &si.cbM)) return 1;
+        if (si.cbM != M) return e2vq_set_error("%s: codebook has M=%d but the models have M=%d", cb_filename, si.cbM, M);
+    }
+    const bool have_cb = si.have_cb;
+    const int cbP = si.cbP;
+    std::vector<SymInput>& inputs = si.inputs;
+    inputs.assign((size_t)num_inputs, SymInput());
+    const std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
+    const bool csv_is_file = num_inputs == 1 && ends_with(csv, ".csv");
+    for (int f = 0; f < num_inputs; ++f) {
+        SymInput& in = inputs[(size_t)f];
+        if (!input_filenames[f]) return e2vq_set_error("%s: NULL file name", who);
+        in.path = input_filenames[f];
+        char cls[96];
+        if (ends_with(in.path, ".seq")) {
+            in.kind = 2;
+            int m;
+            if (e2vq_seq_info(in.path.c_str(), cls, &m, &in.T)) return 1;
+            if (m != M) return e2vq_set_error("%s: codebook size %d differs from the models' %d", in.path.c_str(), m, M);
+        } else if (ends_with(in.path, ".prd")) {
+            in.kind = 1;
+            int p;
+            if (e2vq_prd_info(in.path.c_str(), cls, &p, &in.T)) return 1;
+            if (have_cb && p != cbP)
+                return e2vq_set_error("%s: prediction order %d differs from the codebook's %d", in.path.c_str(), p, cbP);
+            si.need_cb = true;
+        } else if (ends_with(in.path, ".wav")) {
+            in.kind = 0;
+            if (e2vq_wav_info(in.path.c_str(), &in.sample_rate, &in.samples, nullptr)) return 1;
+            if (have_cb && P != cbP) return e2vq_set_error("%s: prediction order -P %d differs from the codebook's %d", in.path.c_str(), P, cbP);
+            int win, off;
+            if (e2vq_lpc_frame_count(in.samples, in.sample_rate, W_ms, O_ms, &win, &off, &in.T)) return 1;
+            if (in.T < 0) return e2vq_set_error("%s: signal too short (%lld samples, window %d)", in.path.c_str(), (long long)in.samples, win);
+            si.need_cb = true;
+        } else {
+            return e2vq_set_error("%s: not a .wav, .prd or .seq file", in.path.c_str());
+        }
+        if (!csv.empty()) in.csv = csv_is_file ? csv : csv + "/" + e2vq_io::basename_noext(in.path.c_str()) + ".csv";
+        for (int g = 0; g < f && !in.csv.empty(); ++g)
+            if (inputs[(size_t)g].csv == in.csv) return e2vq_set_error("%s and %s would both write %s", inputs[(size_t)g].path.c_str(), in.path.c_str(), in.csv.c_str());
+    }
+    if (si.need_cb && !have_cb) return e2vq_set_error("%s: signals and predictors need a codebook", who);
+    if (si.need_cb) {
+        si.refl.resize((size_t)si.cbM * (cbP + 1));
+        if (e2vq_cbook_read(cb_filename, si.refl.data(), si.cbM)) return 1;
+    }
+    return 0;
+}
+
+// one input to symbols in stg.d_sym (read and uploaded once; frames and symbols stay on the device): *T_out of them
+static int sym_input_to_device(const SymInput& in, const SymInputs& si, SymStage& stg, e2vq_session* vq, int device, int P, int W_ms,
+                               int O_ms, hipStream_t st, int64_t* T_out)
+{
+    const int cbP = si.cbP, NC = cbP + 1;
+    int64_t T = in.T;
+    std::vector<uint16_t> h_sym;
+    std::vector<double> h_frames;
+    if (in.kind == 2) {
+        h_sym.resize((size_t)std::max<int64_t>(T, 1));
+        if (T > 0 && e2vq_seq_read(in.path.c_str(), h_sym.data(), T)) return 1;
+        if (stg.d_sym.upload(h_sym.data(), (size_t)T, st)) return 1;
+        HIPCHK(hipStreamSynchronize(st));  // (`h_sym` is a local)
+    } else {
+        if (stg.d_frames.reserve((size_t)std::max<int64_t>(T, 1) * NC) || stg.d_sym.reserve((size_t)T + 64)) return 1;
+        if (in.kind == 1) {
+            h_frames.resize((size_t)std::max<int64_t>(T, 1) * NC);
+            bool fin = true;
+            if (T > 0 && e2vq_io::prd_read_range_mt(in.path.c_str(), cbP, 0, T, h_frames.data(), e2vq_io::io_threads(), &fin)) return 1;
+            if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", in.path.c_str());
+            if (T > 0) HIPCHK(hipMemcpyAsync(stg.d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st));
+        } else {
+            std::vector<int32_t> samples((size_t)std::max<int64_t>(in.samples, 1));
+            if (e2vq_wav_read(in.path.c_str(), samples.data(), in.samples)) return 1;
+            if (stg.d_status.reserve((size_t)std::max<int64_t>(T, 1))) return 1;
+            int64_t T2 = 0;
+            if (T > 0 && e2vq_lpc_analyze(device, P, W_ms, O_ms, samples.data(), in.samples, in.sample_rate, stg.d_frames.get(),
+                                          stg.d_status.get(), T, &T2, 1))
+                return 1;
+            std::vector<int32_t> fst((size_t)T);
+            if (T > 0) HIPCHK(hipMemcpyAsync(fst.data(), stg.d_status.get(), (size_t)T * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            int64_t good = 0;
+            for (int64_t t = 0; t < T; ++t) good += fst[(size_t)t] == 0;
+            if (good != T) {
+                // frames whose Levinson recursion failed are left out, as `ecoz2 lpc` leaves them out of the .prd: the rest
+                // makes one round trip through the host (the only place where the frames leave the device)
+                h_frames.resize((size_t)T * NC);
+                HIPCHK(hipMemcpy(h_frames.data(), stg.d_frames.get(), (size_t)T * NC * 8, hipMemcpyDeviceToHost));
+                int64_t o = 0;
+                for (int64_t t = 0; t < T; ++t)
+                    if (fst[(size_t)t] == 0) memmove(h_frames.data() + (size_t)(o++) * NC, h_frames.data() + (size_t)t * NC, (size_t)NC * 8);
+                printf("%s: %lld frames left out: Levinson status != 0 (later frame times are early by their offsets)\n",
+                       in.path.c_str(), (long long)(T - good));
+                T = good;
+                if (T > 0) HIPCHK(hipMemcpyAsync(stg.d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st));
+            }
+        }
+        if (T > 0 && e2vq_quantize_device(vq, stg.d_frames.get(), T, stg.d_sym.get(), nullptr)) return 1;
+        HIPCHK(hipStreamSynchronize(st));  // (`h_frames` is a local)
+    }
+    *T_out = T;
+    return 0;
+}
+
 // `hmm scan`: every input (.wav: lpc -> quantize -> scan; .prd: quantize -> scan; .seq: scan) under the models
 extern "C" int e2vq_hmm_scan_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
                                    const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
@@ -2437,126 +2732,24 @@ extern "C" int e2vq_hmm_scan_files(const char* const* model_filenames, unsigned 
         ms.push_back(&models[k]);
         names.push_back(models[k].class_name.c_str());
     }
-    const bool have_cb = cb_filename && *cb_filename;
-    int cbP = 0, cbM = 0;
-    std::vector<double> refl;
-    if (have_cb) {
-        char cls[96];
-        if (e2vq_cbook_info(cb_filename, cls, &cbP, &cbM)) return 1;
-        if (cbM != M) return e2vq_set_error("%s: codebook has M=%d but the models have M=%d", cb_filename, cbM, M);
-    }
-    struct Input {
-        std::string path, csv;
-        int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
-        int sample_rate = 0;
-        int64_t samples = 0, T = 0;
-    };
-    std::vector<Input> inputs((size_t)num_inputs);
-    const std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
-    const bool csv_is_file = num_inputs == 1 && ends_with(csv, ".csv");
-    bool need_cb = false;
-    for (int f = 0; f < num_inputs; ++f) {
-        Input& in = inputs[(size_t)f];
-        if (!input_filenames[f]) return e2vq_set_error("e2vq_hmm_scan_files: NULL file name");
-        in.path = input_filenames[f];
-        char cls[96];
-        if (ends_with(in.path, ".seq")) {
-            in.kind = 2;
-            int m;
-            if (e2vq_seq_info(in.path.c_str(), cls, &m, &in.T)) return 1;
-            if (m != M) return e2vq_set_error("%s: codebook size %d differs from the models' %d", in.path.c_str(), m, M);
-        } else if (ends_with(in.path, ".prd")) {
-            in.kind = 1;
-            int p;
-            if (e2vq_prd_info(in.path.c_str(), cls, &p, &in.T)) return 1;
-            if (have_cb && p != cbP)
-                return e2vq_set_error("%s: prediction order %d differs from the codebook's %d", in.path.c_str(), p, cbP);
-            need_cb = true;
-        } else if (ends_with(in.path, ".wav")) {
-            in.kind = 0;
-            if (e2vq_wav_info(in.path.c_str(), &in.sample_rate, &in.samples, nullptr)) return 1;
-            if (have_cb && P != cbP) return e2vq_set_error("%s: prediction order -P %d differs from the codebook's %d", in.path.c_str(), P, cbP);
-            int win, off;
-            if (e2vq_lpc_frame_count(in.samples, in.sample_rate, W_ms, O_ms, &win, &off, &in.T)) return 1;
-            if (in.T < 0) return e2vq_set_error("%s: signal too short (%lld samples, window %d)", in.path.c_str(), (long long)in.samples, win);
-            need_cb = true;
-        } else {
-            return e2vq_set_error("%s: not a .wav, .prd or .seq file", in.path.c_str());
-        }
-        if (!csv.empty()) in.csv = csv_is_file ? csv : csv + "/" + e2vq_io::basename_noext(in.path.c_str()) + ".csv";
-        for (int g = 0; g < f && !in.csv.empty(); ++g)
-            if (inputs[(size_t)g].csv == in.csv) return e2vq_set_error("%s and %s would both write %s", inputs[(size_t)g].path.c_str(), in.path.c_str(), in.csv.c_str());
-    }
-    if (need_cb && !have_cb) return e2vq_set_error("e2vq_hmm_scan_files: signals and predictors need a codebook");
-    if (need_cb) {
-        refl.resize((size_t)cbM * (cbP + 1));
-        if (e2vq_cbook_read(cb_filename, refl.data(), cbM)) return 1;
-    }
+    SymInputs si;
+    if (sym_inputs_check("e2vq_hmm_scan_files", M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms,
+                         csv_dir_or_file, si))
+        return 1;
     // ---- the device from here on --------------------------------------------------------------------------------
     const int device = env_device();
     if (require_device(device)) return 1;
-    DeviceBuffer<double> d_frames;
-    DeviceBuffer<int32_t> d_status;
-    DeviceBuffer<unsigned short> d_sym;
+    SymStage stg;
     Stream st;
     if (st.create()) return 1;
-    struct Session {
-        e2vq_session* s = nullptr;
-        ~Session()
-        {
-            if (s) e2vq_session_destroy(s);
-        }
-    } vq;
-    if (need_cb) {
-        if (e2vq_session_create(device, cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, refl.data(), cbM))
+    VqSessionHolder vq;
+    if (si.need_cb) {
+        if (e2vq_session_create(device, si.cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, si.refl.data(), si.cbM))
             return 1;
     }
-    const int NC = cbP + 1;
-    for (Input& in : inputs) {
-        int64_t T = in.T;
-        std::vector<uint16_t> h_sym;
-        std::vector<double> h_frames;
-        if (in.kind == 2) {
-            h_sym.resize((size_t)std::max<int64_t>(T, 1));
-            if (T > 0 && e2vq_seq_read(in.path.c_str(), h_sym.data(), T)) return 1;
-            if (d_sym.upload(h_sym.data(), (size_t)T, st.s)) return 1;
-        } else {
-            if (d_frames.reserve((size_t)std::max<int64_t>(T, 1) * NC) || d_sym.reserve((size_t)T + 64)) return 1;
-            if (in.kind == 1) {
-                h_frames.resize((size_t)std::max<int64_t>(T, 1) * NC);
-                bool fin = true;
-                if (T > 0 && e2vq_io::prd_read_range_mt(in.path.c_str(), cbP, 0, T, h_frames.data(), e2vq_io::io_threads(), &fin)) return 1;
-                if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", in.path.c_str());
-                if (T > 0) HIPCHK(hipMemcpyAsync(d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st.s));
-            } else {
-                std::vector<int32_t> samples((size_t)std::max<int64_t>(in.samples, 1));
-                if (e2vq_wav_read(in.path.c_str(), samples.data(), in.samples)) return 1;
-                if (d_status.reserve((size_t)std::max<int64_t>(T, 1))) return 1;
-                int64_t T2 = 0;
-                if (T > 0 && e2vq_lpc_analyze(device, P, W_ms, O_ms, samples.data(), in.samples, in.sample_rate, d_frames.get(),
-                                              d_status.get(), T, &T2, 1))
-                    return 1;
-                std::vector<int32_t> fst((size_t)T);
-                if (T > 0) HIPCHK(hipMemcpyAsync(fst.data(), d_status.get(), (size_t)T * 4, hipMemcpyDeviceToHost, st.s));
-                HIPCHK(hipStreamSynchronize(st.s));
-                int64_t good = 0;
-                for (int64_t t = 0; t < T; ++t) good += fst[(size_t)t] == 0;
-                if (good != T) {
-                    // frames whose Levinson recursion failed are left out, as `ecoz2 lpc` leaves them out of the .prd: the rest
-                    // makes one round trip through the host (the only place where the frames leave the device)
-                    h_frames.resize((size_t)T * NC);
-                    HIPCHK(hipMemcpy(h_frames.data(), d_frames.get(), (size_t)T * NC * 8, hipMemcpyDeviceToHost));
-                    int64_t o = 0;
-                    for (int64_t t = 0; t < T; ++t)
-                        if (fst[(size_t)t] == 0) memmove(h_frames.data() + (size_t)(o++) * NC, h_frames.data() + (size_t)t * NC, (size_t)NC * 8);
-                    printf("%s: %lld frames left out: Levinson status != 0 (later frame times are early by their offsets)\n",
-                           in.path.c_str(), (long long)(T - good));
-                    T = good;
-                    if (T > 0) HIPCHK(hipMemcpyAsync(d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st.s));
-                }
-            }
-            if (T > 0 && e2vq_quantize_device(vq.s, d_frames.get(), T, d_sym.get(), nullptr)) return 1;
-        }
+    for (const SymInput& in : si.inputs) {
+        int64_t T = 0;
+        if (sym_input_to_device(in, si, stg, vq.s, device, P, W_ms, O_ms, st.s, &T)) return 1;
         const i64 offs[2] = {0, T};
         i64 wo[2];
         scan_window_offsets(offs, 1, window_frames, hop_frames, wo);
@@ -2565,10 +2758,153 @@ extern "C" int e2vq_hmm_scan_files(const char* const* model_filenames, unsigned 
         std::vector<double> lp1(W), lp2(W);
         ScanOut out;
         out.best = best.data(), out.best_log_prob = lp1.data(), out.second = second.data(), out.second_log_prob = lp2.data();
-        if (scan_device(ms, d_sym.get(), offs, 1, window_frames, hop_frames, st.s, out)) return 1;
+        if (scan_device(ms, stg.d_sym.get(), offs, 1, window_frames, hop_frames, st.s, out)) return 1;
         HIPCHK(hipStreamSynchronize(st.s));  // (the host buffers of this input are locals)
         if (e2vq_hmm_scan_report(in.path.c_str(), T, (int)num_models, names.data(), (int64_t)W, window_frames, hop_frames, W_ms, O_ms,
                                  best.data(), lp1.data(), second.data(), lp2.data(), min_margin, in.csv.empty() ? nullptr : in.csv.c_str()))
+            return 1;
+    }
+    return 0;
+}
+
+// ---- hmm segment --------------------------------------------------------------------------------------
+extern "C" int e2vq_hmm_segment_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_segment_last_kernel_ms: bad arguments");
+    *ms = g_segment_kernel_ms;
+    return 0;
+}
+
+// the most likely path of each of S streams through the class loop of K models sharing M.  One device.
+extern "C" int e2vq_hmm_segment(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                                const double* const* Bs, const void* sym, const int64_t* offs, int S, double ln_switch,
+                                uint16_t* cls, uint16_t* state, uint8_t* entered, double* gbest, double* log_prob, int* status,
+                                int sym_on_device)
+{
+    if (K < 1) return e2vq_set_error("e2vq_hmm_segment: %d models (at least 1)", K);
+    if (!Ns || !pis || !As || !Bs || S < 0 || (!sym && S > 0 && offs && offs[S] > 0)) return e2vq_set_error("e2vq_hmm_segment: bad arguments");
+    if (segment_check_shape("e2vq_hmm_segment", K, Ns) || segment_check_switch("e2vq_hmm_segment", ln_switch)) return 1;
+    std::vector<Hmm> models((size_t)K);
+    std::vector<const Hmm*> ms;
+    std::vector<std::vector<double>> lflats((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        if (model_from_arrays(Ns[k], M, pis[k], As[k], Bs[k], models[(size_t)k]) || log_model(models[(size_t)k], lflats[(size_t)k])) return 1;
+        ms.push_back(&models[(size_t)k]);
+    }
+    if (check_offsets(offs, S)) return 1;
+    if (require_device(device)) return 1;
+    DeviceBuffer<unsigned short> d_sym;
+    Stream st;
+    if (st.create()) return 1;
+    if (!sym_on_device && d_sym.upload((const unsigned short*)sym, (size_t)offs[S], st.s)) return 1;
+    SegOut out;
+    out.cls = cls, out.state = state, out.entered = entered, out.gbest = gbest, out.log_prob = log_prob, out.status = status;
+    return segment_device(ms, lflats, sym_on_device ? (const unsigned short*)sym : d_sym.get(), (const i64*)offs, S, ln_switch, st.s, out);
+}
+
+// CSV and stdout block of one segmented input from the per-frame outputs (host only)
+extern "C" int e2vq_hmm_segment_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
+                                       const uint16_t* cls, const uint8_t* entered, const double* gbest, double log_prob,
+                                       double ln_switch, const char* csv_filename)
+{
+    FlushStdout flush_on_return;
+    if (!name || K < 1 || !class_names || T < 0 || (T > 0 && (!cls || !entered || !gbest)))
+        return e2vq_set_error("e2vq_hmm_segment_report: bad arguments");
+    if (T > 0 && !entered[0]) return e2vq_set_error("e2vq_hmm_segment_report: frame 0 does not start a segment");
+    for (int64_t t = 0; t < T; ++t)
+        if (cls[t] >= K) return e2vq_set_error("e2vq_hmm_segment_report: frame %lld names a model outside [0, %d)", (long long)t, K);
+    struct Seg {
+        int64_t b, e;
+        double lp;
+    };
+    std::vector<Seg> segs;
+    for (int64_t b = 0; b < T;) {
+        int64_t e = b + 1;
+        while (e < T && !entered[e]) ++e;
+        // (gbest[e] of an entered frame e is the path's own cumulative score at e - 1)
+        const double hi = e == T ? log_prob : gbest[e], lo = b == 0 ? 0.0 : gbest[b] + ln_switch;
+        segs.push_back(Seg{b, e, hi - lo});
+        b = e;
+    }
+    auto begin_s = [&](int64_t b) { return (double)(b * O_ms) / 1000.0; };
+    // (the end of the analysis window of the segment's last frame)
+    auto end_s = [&](int64_t e) { return (double)((e - 1) * O_ms + W_ms) / 1000.0; };
+    if (csv_filename && *csv_filename) {
+        std::string doc = "segment,begin_frame,end_frame,begin_s,end_s,class,log_prob,log_prob_per_frame\n";
+        for (size_t i = 0; i < segs.size(); ++i) {
+            const Seg& g = segs[i];
+            doc += std::to_string(i) + "," + std::to_string(g.b) + "," + std::to_string(g.e) + "," + fmt_17g(begin_s(g.b)) + "," +
+                   fmt_17g(end_s(g.e)) + "," + class_names[cls[g.b]] + "," + fmt_17g(g.lp) + "," + fmt_17g(g.lp / (double)(g.e - g.b)) + "\n";
+        }
+        if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
+    }
+    printf("%s: T=%lld  segments=%zu  (switch penalty %g)\n", name, (long long)T, segs.size(), ln_switch);
+    std::vector<int64_t> frames((size_t)K, 0);
+    for (int64_t t = 0; t < T; ++t) ++frames[cls[t]];
+    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)frames[(size_t)k]);
+    printf("  segments:\n");
+    for (const Seg& g : segs) printf("    %.3f - %.3f %s\n", begin_s(g.b), end_s(g.e), class_names[cls[g.b]]);
+    if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
+    return 0;
+}
+
+// `hmm segment`: every input (.wav: lpc -> quantize -> segment; .prd: quantize -> segment; .seq: segment) under the models
+extern "C" int e2vq_hmm_segment_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                      const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                                      const char* csv_dir_or_file)
+{
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("e2vq_hmm_segment_files: no models");
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("e2vq_hmm_segment_files: no inputs");
+    if (segment_check_switch("e2vq_hmm_segment_files", ln_switch)) return 1;
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("e2vq_hmm_segment_files: window %d ms / offset %d ms", W_ms, O_ms);
+    std::vector<Hmm> models;
+    if (load_models(model_filenames, num_models, models)) return 1;
+    const int M = models[0].M;
+    std::vector<const Hmm*> ms;
+    std::vector<const char*> names;
+    std::vector<int> Ns;
+    for (unsigned k = 0; k < num_models; ++k) {
+        if (models[k].M != M)
+            return e2vq_set_error("%s: model has M=%d but %s has M=%d", model_filenames[k], models[k].M, model_filenames[0], M);
+        ms.push_back(&models[k]);
+        names.push_back(models[k].class_name.c_str());
+        Ns.push_back(models[k].N);
+    }
+    if (segment_check_shape("e2vq_hmm_segment_files", (int)num_models, Ns.data())) return 1;
+    std::vector<std::vector<double>> lflats((size_t)num_models);
+    for (unsigned k = 0; k < num_models; ++k)
+        if (log_model(models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    SymInputs si;
+    if (sym_inputs_check("e2vq_hmm_segment_files", M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, si))
+        return 1;
+    // ---- the device from here on --------------------------------------------------------------------------------
+    const int device = env_device();
+    if (require_device(device)) return 1;
+    SymStage stg;
+    Stream st;
+    if (st.create()) return 1;
+    VqSessionHolder vq;
+    if (si.need_cb) {
+        if (e2vq_session_create(device, si.cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, si.refl.data(), si.cbM))
+            return 1;
+    }
+    for (const SymInput& in : si.inputs) {
+        int64_t T = 0;
+        if (sym_input_to_device(in, si, stg, vq.s, device, P, W_ms, O_ms, st.s, &T)) return 1;
+        const i64 offs[2] = {0, T};
+        const size_t n = (size_t)std::max<int64_t>(T, 1);
+        std::vector<uint16_t> cls(n);
+        std::vector<uint8_t> entered(n);
+        std::vector<double> gbest(n);
+        double lp = 0.0;
+        int status = 0;
+        SegOut out;
+        out.cls = cls.data(), out.entered = entered.data(), out.gbest = gbest.data(), out.log_prob = &lp, out.status = &status;
+        if (segment_device(ms, lflats, stg.d_sym.get(), offs, 1, ln_switch, st.s, out)) return 1;
+        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), M);
+        if (e2vq_hmm_segment_report(in.path.c_str(), T, (int)num_models, names.data(), W_ms, O_ms, cls.data(), entered.data(), gbest.data(),
+                                    lp, ln_switch, in.csv.empty() ? nullptr : in.csv.c_str()))
             return 1;
     }
     return 0;

@@ -64,6 +64,13 @@ _sig("e2vq_hmm_scan_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp,
 _sig("e2vq_hmm_scan_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int64, C.c_int64, C.c_int64, C.c_int,
      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_char_p)
 
+_sig("e2vq_hmm_segment", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_segment_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_segment_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_double, C.c_char_p)
+_sig("e2vq_hmm_segment_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_double, C.c_double, C.c_char_p)
 
 def _strs(items):
     arr = (C.c_char_p * len(items))(*[str(p).encode() for p in items])
@@ -373,3 +380,67 @@ def scan_files(model_filenames, input_filenames, window, hop=None, codebook=None
     check(lib.e2vq_hmm_scan_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                   len(input_filenames), int(P), int(W_ms), int(O_ms), int(window),
                                   int(window if hop is None else hop), float(min_margin), str(csv).encode() if csv else None))
+
+
+def segments_of(cls, entered, gbest, log_prob, ln_switch):
+    """the segments of one stream from its per-frame outputs (host arithmetic): a list of dicts begin, end
+    (exclusive), cls, log_prob -- the segment [b, e) runs from one entered frame to the next"""
+    T = len(cls)
+    starts = [int(t) for t in np.flatnonzero(np.asarray(entered))]
+    out = []
+    for b, e in zip(starts, starts[1:] + [T]):
+        hi = float(log_prob) if e == T else float(gbest[e])
+        lo = 0.0 if b == 0 else float(gbest[b]) + float(ln_switch)
+        with np.errstate(invalid="ignore"):
+            out.append(dict(begin=b, end=e, cls=int(cls[b]), log_prob=float(np.float64(hi) - np.float64(lo))))
+    return out
+
+
+def segment(models, sym, offs, ln_switch, device=0):
+    """the most likely path of whole symbol streams through the class loop of the models: models =
+    [(pi, A, B)] sharing M, each of at most 64 states; sym, offs as `scan` takes them (numpy, or a device tensor);
+    ln_switch <= 0: the log of the price of starting a segment (-inf: never).  -> dict: per frame cls / state (uint16),
+    entered (uint8), gbest; per stream log_prob, status; and segments = per stream the list `segments_of` gives"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    S = len(offs) - 1
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    n = max(int(offs[-1]), 1)
+    cls, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
+    entered, gbest = np.zeros(n, dtype=np.uint8), np.zeros(n)
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_segment(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, float(ln_switch),
+                               cls.ctypes.data, state.ctypes.data, entered.ctypes.data, gbest.ctypes.data, lp.ctypes.data,
+                               st.ctypes.data, int(on_device)))
+    T = int(offs[-1])
+    out = dict(cls=cls[:T], state=state[:T], entered=entered[:T], gbest=gbest[:T], log_prob=lp[:S], status=st[:S])
+    out["segments"] = [segments_of(out["cls"][a:b], out["entered"][a:b], out["gbest"][a:b], lp[s], ln_switch)
+                       for s, (a, b) in enumerate(zip(offs[:-1], offs[1:]))]
+    return out
+
+
+def segment_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_segment_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None):
+    """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
+    stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments"""
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    check(lib.e2vq_hmm_segment_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                     len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                     str(csv).encode() if csv else None))

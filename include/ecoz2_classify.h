@@ -282,6 +282,45 @@ int e2vq_hmm_scan_report(const char *name, int64_t T, int K, const char *const *
 int e2vq_hmm_viterbi(int device, int N, int M, const double *pi, const double *A, const double *B, const uint16_t *sym,
                      const int64_t *offs, int S, uint16_t *path, double *log_prob, int *status);
 
+/* ---- segmentation by joint Viterbi over all class models -----------------------------------------------
+ * `hmm segment`: each of S streams (concatenated u16 symbols + S+1 offsets, the layout of e2vq_hmm_scan) is decoded once
+ * under the class loop of K models sharing M: the models side by side; a path may leave the class it is in at any frame and
+ * enter any class -- the same one included -- through that class's pi, at the price ln_switch <= 0 (the logarithm of the
+ * price of starting a segment; -inf forbids it).  Logarithms of the parameters are taken on the host exactly as
+ * e2vq_hmm_viterbi takes them; the device adds and compares.  With d_0[k][j] = lpi_k[j] + lB_k[j][o_0], and for t >= 1
+ * G_t = max d_{t-1} reached first by g_t in (class, state) order: per state the in-class maximum of e2vq_hmm_viterbi (ties
+ * to the lowest state), then x = (G_t + ln_switch) + lpi_k[j] replaces it when strictly greater (ENTER; a tie stays in the
+ * class), then + lB_k[j][o_t].  ln P* = max d_{T-1}, q_{T-1} the lowest (class, state) reaching it; backwards an ENTER at
+ * t+1 gives q_t = g_{t+1} and marks frame t+1 as the start of a segment; frame 0 always starts one.
+ * Outputs, each may be NULL: per frame (offs[S] entries) cls, state, entered (1: the frame starts a segment) and gbest
+ * (G_t; 0.0 at frame 0 of a stream); per stream log_prob = ln P* and status: 0 ok; 1 ln P* = -inf (the path is still written
+ * by the same rules); 2 a symbol >= M (ln P* = -inf, cls and state 0xFFFF, entered 0, gbest -inf except entry 0).  An empty
+ * stream: status 0, ln P* = 0.0.  The segment [b, e) between two entered frames has class cls[b] and the score
+ * (e == T ? ln P* : gbest[e]) - (b == 0 ? 0.0 : gbest[b] + ln_switch).
+ * K < 1, an N_k outside [1, 64], more than 4096 states in all, a negative, NaN or infinite parameter and an ln_switch that
+ * is NaN or > 0 are refused before any HIP call.  One device: the streams are not dealt over several GPUs.
+ * sym_on_device: `sym` is a device pointer on `device` (offs stays a host pointer).
+ * ECOZ2_HMM_SEGMENT_CHUNK_BYTES bounds the per-launch back-pointer table (default 256 MiB, whole streams; a table that
+ * cannot be allocated is an error).  ECOZ2_HMM_SEGMENT_BODY = resident | looped forces a kernel body where it is possible
+ * (resident needs a packing of at most 16 waves); the bits are the same. */
+int e2vq_hmm_segment(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                     const double *const *Bs, const void *sym, const int64_t *offs, int S, double ln_switch, uint16_t *cls,
+                     uint16_t *state, uint8_t *entered, double *gbest, double *log_prob, int *status, int sym_on_device);
+/* HIP-event time of the kernels (forward + backtrack) of this thread's last segmentation (-1: none yet) */
+int e2vq_hmm_segment_last_kernel_ms(float *ms);
+/* CSV and stdout block of one segmented stream from its per-frame outputs (host only; what e2vq_hmm_segment_files calls).
+ * stdout: name, T, the number of segments; frames per class; one line "begin_s - end_s class" per segment.  CSV header:
+ *   segment,begin_frame,end_frame,begin_s,end_s,class,log_prob,log_prob_per_frame
+ * end_frame is exclusive; begin_s = begin_frame O_ms / 1000, end_s = ((end_frame - 1) O_ms + W_ms) / 1000; floats as %.17g. */
+int e2vq_hmm_segment_report(const char *name, int64_t T, int K, const char *const *class_names, int W_ms, int O_ms,
+                            const uint16_t *cls, const uint8_t *entered, const double *gbest, double log_prob, double ln_switch,
+                            const char *csv_filename);
+/* The file form: inputs, stages and up-front refusals of e2vq_hmm_scan_files without window and hop, plus the limits on
+ * N_k and on the number of states above; per input the block and CSV of e2vq_hmm_segment_report. */
+int e2vq_hmm_segment_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                           const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                           const char *csv_dir_or_file);
+
 #ifdef __cplusplus
 }
 #endif
