@@ -1,4 +1,4 @@
-// hip_host.h -- the host-side HIP plumbing of the entry points (vq_entry.cpp, vq_host.cpp, hmm_host.cpp, lpc_host.cpp):
+// hip_host.h -- the host-side HIP plumbing of the entry points (vq_entry.cpp, vq_host.cpp, the hmm_*.cpp units, lpc_host.cpp):
 // error check, device check, handles that release themselves, and the fan-out over worker threads.  Host code only.
 // Internal.
 #pragma once

@@ -1,0 +1,965 @@
+// hmm_decode.cpp -- decoding on the GPU: Viterbi under one model (`seq show -P / -Q --hmm`, e2vq_hmm_viterbi; DESIGN.md
+// 4.8.1), the models over the windows of whole recordings (`hmm scan`, 4.8.5) and the joint Viterbi through the class
+// loop of all models (`hmm segment`, 4.8.6), with the stage that turns a .wav / .prd / .seq input into device symbols;
+// over the kernels of hmm_viterbi.hip, hmm_scan.hip and hmm_segment.hip.
+#include "hmm_host.h"
+
+#include <functional>
+
+namespace e2hmm_host {
+namespace {
+
+// The launches of a decoder whose table takes `row` bytes a frame: whole sequences [s0, s1) up to the budget of the
+// environment variable `env` (default 256 MiB), a longer sequence alone; *max_frames: the most frames of a launch
+std::vector<std::pair<int, int>> plan_chunks(const char* env, i64 row, const i64* hoffs, int S, i64* max_frames)
+{
+    const i64 budget = env_bytes(env, (i64)256 << 20);
+    std::vector<std::pair<int, int>> chunks;
+    *max_frames = 0;
+    for (int s0 = 0; s0 < S;) {
+        int s1 = s0 + 1;
+        while (s1 < S && (hoffs[s1 + 1] - hoffs[s0]) * row <= budget) ++s1;
+        chunks.emplace_back(s0, s1);
+        *max_frames = std::max(*max_frames, hoffs[s1] - hoffs[s0]);
+        s0 = s1;
+    }
+    return chunks;
+}
+
+// Viterbi of S device-resident sequences (hoffs: the S+1 offsets on the host, to cut the launches) under the model
+// whose logarithms `lflat` holds; path (may be null: no psi, no backtrack) receives hoffs[S] states
+int viterbi_device(int N, int M, const std::vector<double>& lflat, const unsigned short* d_sym, const i64* d_offs,
+                   const i64* hoffs, int S, hipStream_t st, uint16_t* path, double* logp, int* status)
+{
+    DeviceBuffer<double> d_model, d_logp;
+    DeviceBuffer<int> d_status, d_qlast;
+    DeviceBuffer<unsigned short> d_psi, d_path;
+    if (d_model.upload(lflat.data(), lflat.size(), st)) return 1;
+    HIPCHK(hipStreamSynchronize(st));  // (`lflat` may go)
+    const double* base = d_model.get();
+    const ModelDev lm{N, M, base, base + N, base + N + (size_t)N * N};
+    if (d_logp.reserve((size_t)S) || d_status.reserve((size_t)S)) return 1;
+    if (!path) {
+        e2hmm::launch_viterbi(lm, d_sym, d_offs, S, 0, nullptr, d_logp.get(), nullptr, d_status.get(), st);
+        HIPCHK(hipGetLastError());
+    } else {
+        i64 max_syms = 0;  // (psi: 2 N bytes a frame)
+        const auto chunks = plan_chunks("ECOZ2_HMM_VITERBI_CHUNK_BYTES", 2 * (i64)N, hoffs, S, &max_syms);
+        if (d_psi.reserve((size_t)max_syms * N) || d_path.reserve((size_t)hoffs[S]) || d_qlast.reserve((size_t)S)) return 1;
+        // (one stream: a chunk's forward pass writes psi only after the previous chunk's backtrack has read it)
+        for (const auto& c : chunks) {
+            const int s0 = c.first, n = c.second - c.first;
+            e2hmm::launch_viterbi(lm, d_sym, d_offs + s0, n, hoffs[s0], d_psi.get(), d_logp.get() + s0, d_qlast.get() + s0,
+                                  d_status.get() + s0, st);
+            HIPCHK(hipGetLastError());
+            e2hmm::launch_backtrack(N, d_offs + s0, n, hoffs[s0], d_psi.get(), d_qlast.get() + s0, d_status.get() + s0,
+                                    d_path.get(), st);
+            HIPCHK(hipGetLastError());
+        }
+        if (hoffs[S] > 0) HIPCHK(hipMemcpyAsync(path, d_path.get(), (size_t)hoffs[S] * 2, hipMemcpyDeviceToHost, st));
+    }
+    if (S > 0) {
+        HIPCHK(hipMemcpyAsync(logp, d_logp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(status, d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// values of one sequence as `seq show` prints its symbols: all of them when `full` or L <= 30, else the first 10,
+// ", ..., " and the last 10
+template <typename V>
+void print_abbreviated(const V* v, size_t len, bool full)
+{
+    if (full || len <= 30) {
+        for (size_t t = 0; t < len; ++t) printf("%s%u", t ? ", " : "", (unsigned)v[t]);
+    } else {
+        for (size_t t = 0; t < 10; ++t) printf("%s%u", t ? ", " : "", (unsigned)v[t]);
+        printf(", ..., ");
+        for (size_t t = len - 10; t < len; ++t) printf("%s%u", t > len - 10 ? ", " : "", (unsigned)v[t]);
+    }
+}
+
+// ---- hmm scan: the trained models over the windows of whole recordings ------------------------------------
+// windows of `window` frames every `hop` frames: stream s of T_s symbols has (T_s - window) / hop + 1 of them when
+// T_s >= window, else none (a trailing incomplete window is dropped); win_offs: S + 1 entries
+void scan_window_offsets(const i64* offs, int S, i64 window, i64 hop, i64* win_offs)
+{
+    win_offs[0] = 0;
+    for (int s = 0; s < S; ++s) {
+        const i64 T = offs[s + 1] - offs[s];
+        win_offs[s + 1] = win_offs[s] + (T >= window ? (T - window) / hop + 1 : 0);
+    }
+}
+
+int scan_check_geometry(const char* who, i64 window, i64 hop)
+{
+    if (window < 1) return e2vq_set_error("%s: window of %lld frames (at least 1)", who, (long long)window);
+    if (window > (1 << 30)) return e2vq_set_error("%s: window of %lld frames (at most 2^30)", who, (long long)window);
+    if (hop < 1) return e2vq_set_error("%s: hop of %lld frames (at least 1)", who, (long long)hop);
+    return 0;
+}
+
+// windows to a wave: floor(64 / N) where that is at least 3 (N <= SCAN_PACK_MAX_N), else one -- two windows to a wave measured
+// between 1.4 % faster (N = 22) and 3 % slower (N = 28, 32) than one (DESIGN.md 4.8.5's table).
+// ECOZ2_HMM_SCAN_PACK=0 scores one window per wave at every N, =1 packs floor(64 / N) at every N <= 32 (the other arms of
+// tools/hmm_scan_bench.py and of the tests; the bits are the same)
+constexpr int SCAN_PACK_MAX_N = 21;
+int scan_pack_width_in_use(int N)
+{
+    const char* v = getenv("ECOZ2_HMM_SCAN_PACK");
+    if (v && *v) return atoi(v) == 0 || N > 32 ? 1 : e2hmm::WAVE_N / N;
+    return N <= SCAN_PACK_MAX_N ? e2hmm::WAVE_N / N : 1;
+}
+
+// rounds of (waves x G) windows a k_hmm_scan workgroup takes from one staging of A and the symbols
+// (ECOZ2_HMM_SCAN_ROUNDS, 1 .. 64; changes no bit)
+int scan_rounds()
+{
+    const int r = e2vq_env_int("ECOZ2_HMM_SCAN_ROUNDS", 4);
+    return r < 1 ? 1 : (r > 64 ? 64 : r);
+}
+
+thread_local float g_scan_kernel_ms = -1.f;  // e2vq_hmm_scan_last_kernel_ms
+
+struct ScanOut {  // any may be null; matrices W x K, the others W
+    double* mant = nullptr;
+    int64_t* exp2 = nullptr;
+    int* status = nullptr;
+    double* log_probs = nullptr;
+    int* best = nullptr;
+    double* best_log_prob = nullptr;
+    int* second = nullptr;
+    double* second_log_prob = nullptr;
+    bool matrix() const { return mant || exp2 || status || log_probs; }
+    bool top() const { return best || best_log_prob || second || second_log_prob; }
+};
+
+// Scores every window of the S device-resident streams (h_offs: their S + 1 offsets, on the host) under the models, on the
+// current device and the stream st.  Models of one N <= 64 go into one k_hmm_scan launch over runs of at most
+// waves x G x rounds windows whose span fits the staging area; models of more states through k_hmm_scan_wg; then
+// k_scan_top2.  One copy back: two results per window, and the W x K matrix only when `out` asks for it.
+int scan_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* h_offs, int S, i64 window, i64 hop,
+                hipStream_t st, const ScanOut& out)
+{
+    const int K = (int)ms.size();
+    std::vector<i64> win_offs((size_t)S + 1);
+    scan_window_offsets(h_offs, S, window, hop, win_offs.data());
+    const i64 W = win_offs[(size_t)S];
+    if (W == 0) return 0;
+    if (W > (i64)INT32_MAX - 64 || W * K > ((i64)1 << 40)) return e2vq_set_error("hmm scan: %lld windows x %d models", (long long)W, K);
+    std::vector<e2hmm::ScanWin> wins((size_t)W);
+    for (int s = 0; s < S; ++s)
+        for (i64 i = 0, n = win_offs[(size_t)s + 1] - win_offs[(size_t)s]; i < n; ++i)
+            wins[(size_t)(win_offs[(size_t)s] + i)] = e2hmm::ScanWin{s, (int)window, i * hop};
+    // runs of at most `cap` windows, stream by stream
+    auto make_runs = [&](i64 cap, std::vector<e2hmm::ScanRun>& runs) {
+        for (int s = 0; s < S; ++s)
+            for (i64 w = win_offs[(size_t)s]; w < win_offs[(size_t)s + 1]; w += cap)
+                runs.push_back(e2hmm::ScanRun{(int)w, (int)std::min<i64>(cap, win_offs[(size_t)s + 1] - w)});
+    };
+    std::map<int, std::vector<int>> by_N;  // models of N <= 64 states, by N
+    std::vector<int> big;                  // the others
+    int big_N = 0;
+    for (int k = 0; k < K; ++k) {
+        if (ms[(size_t)k]->N > e2hmm::WAVE_N) {
+            big.push_back(k);
+            big_N = std::max(big_N, ms[(size_t)k]->N);
+        } else {
+            by_N[ms[(size_t)k]->N].push_back(k);
+        }
+    }
+    struct Launch {
+        int N, G, span_lds, ks_at, nk, runs_at, nruns;
+    };
+    std::vector<Launch> launches;
+    std::vector<int> ks;
+    std::vector<e2hmm::ScanRun> runs;
+    const int rounds = scan_rounds();
+    for (const auto& kv : by_N) {
+        const int N = kv.first, G = scan_pack_width_in_use(N);
+        i64 cap = (i64)e2hmm::scan_waves() * G * rounds;
+        // (a window longer than the staging area is read from global memory; shorter ones: as many as fit)
+        if (window <= e2hmm::SCAN_SPAN_CAP) cap = std::min<i64>(cap, (e2hmm::SCAN_SPAN_CAP - window) / hop + 1);
+        const i64 span = (std::min<i64>(cap, W) - 1) * hop + window;
+        Launch l{N, G, (int)(span <= e2hmm::SCAN_SPAN_CAP ? span : 0), (int)ks.size(), (int)kv.second.size(), (int)runs.size(), 0};
+        ks.insert(ks.end(), kv.second.begin(), kv.second.end());
+        make_runs(cap, runs);
+        l.nruns = (int)runs.size() - l.runs_at;
+        launches.push_back(l);
+    }
+    const int big_at = (int)ks.size();
+    ks.insert(ks.end(), big.begin(), big.end());
+
+    DevModels dm;
+    if (dm.upload(ms, st)) return 1;
+    DeviceBuffer<e2hmm::ScanWin> d_wins;
+    DeviceBuffer<e2hmm::ScanRun> d_runs;
+    DeviceBuffer<int> d_ks, d_st, d_top;
+    DeviceBuffer<i64> d_offs, d_exp, d_texp;
+    DeviceBuffer<double> d_mant, d_tmant;
+    const size_t n = (size_t)W * K;
+    if (d_wins.upload(wins.data(), wins.size(), st) || d_runs.upload(runs.data(), runs.size(), st) ||
+        d_ks.upload(ks.data(), ks.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) || d_mant.reserve(n) || d_exp.reserve(n) ||
+        d_st.reserve(n) || d_top.reserve((size_t)2 * W) || d_tmant.reserve((size_t)2 * W) || d_texp.reserve((size_t)2 * W))
+        return 1;
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    for (const Launch& l : launches) {
+        e2hmm::launch_scan(dm.table.get(), d_ks.get() + l.ks_at, l.nk, K, l.N, l.G, d_wins.get(), d_runs.get() + l.runs_at, l.nruns,
+                           l.span_lds, d_sym, d_offs.get(), d_mant.get(), d_exp.get(), d_st.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    if (!big.empty()) {
+        e2hmm::launch_scan_wg(dm.table.get(), d_ks.get() + big_at, (int)big.size(), K, big_N, d_wins.get(), W, d_sym, d_offs.get(),
+                              d_mant.get(), d_exp.get(), d_st.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    e2hmm::launch_scan_top2(d_mant.get(), d_exp.get(), d_st.get(), W, K, d_top.get(), d_tmant.get(), d_texp.get(), st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    std::vector<int> top, stat;
+    std::vector<double> tmant, mant;
+    std::vector<i64> texp, ex;
+    if (out.top()) {
+        top.resize((size_t)2 * W);
+        tmant.resize((size_t)2 * W);
+        texp.resize((size_t)2 * W);
+        HIPCHK(hipMemcpyAsync(top.data(), d_top.get(), top.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(tmant.data(), d_tmant.get(), tmant.size() * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(texp.data(), d_texp.get(), texp.size() * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (out.matrix()) {
+        mant.resize(n);
+        ex.resize(n);
+        stat.resize(n);
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_st.get(), n * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_scan_kernel_ms)) return 1;
+    if (out.top())
+        for (i64 w = 0; w < W; ++w) {
+            const size_t a = (size_t)2 * w, b = a + 1;
+            if (out.best) out.best[w] = top[a];
+            if (out.second) out.second[w] = top[b];
+            if (out.best_log_prob) out.best_log_prob[w] = log_prob(tmant[a], texp[a]);
+            if (out.second_log_prob) out.second_log_prob[w] = log_prob(tmant[b], texp[b]);
+        }
+    if (out.matrix())
+        for (size_t i = 0; i < n; ++i) {
+            if (out.mant) out.mant[i] = mant[i];
+            if (out.exp2) out.exp2[i] = ex[i];
+            if (out.status) out.status[i] = stat[i];
+            if (out.log_probs) out.log_probs[i] = stat[i] == 0 ? log_prob(mant[i], ex[i]) : -INFINITY;
+        }
+    return 0;
+}
+
+std::string fmt_17g(double v)
+{
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+bool ends_with(const std::string& s, const char* ext)
+{
+    const size_t n = strlen(ext);
+    return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
+}
+
+// ---- hmm segment: one Viterbi pass through the class loop of all models ------------------------------------
+thread_local float g_segment_kernel_ms = -1.f;  // e2vq_hmm_segment_last_kernel_ms
+
+int segment_check_shape(const char* who, int K, const int* Ns)
+{
+    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
+    i64 sum = 0;
+    for (int k = 0; k < K; ++k) {
+        if (Ns[k] < 1 || Ns[k] > e2hmm::SEG_MAX_N)
+            return e2vq_set_error("%s: model %d has N=%d states (1 .. %d)", who, k, Ns[k], e2hmm::SEG_MAX_N);
+        sum += Ns[k];
+    }
+    if (sum > e2hmm::SEG_MAX_SUM_N)
+        return e2vq_set_error("%s: %lld states in all models (at most %d)", who, (long long)sum, e2hmm::SEG_MAX_SUM_N);
+    return 0;
+}
+
+int segment_check_switch(const char* who, double ln_switch)
+{
+    if (std::isnan(ln_switch) || ln_switch > 0.0)
+        return e2vq_set_error("%s: ln_switch = %g: the logarithm of a price, at most 0 (-inf forbids a new segment)", who, ln_switch);
+    return 0;
+}
+
+struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered, gbest; per stream: log_prob, status
+    uint16_t* cls = nullptr;
+    uint16_t* state = nullptr;
+    uint8_t* entered = nullptr;
+    double* gbest = nullptr;
+    double* log_prob = nullptr;
+    int* status = nullptr;
+};
+
+// The joint Viterbi of S device-resident streams (h_offs: their S + 1 offsets, on the host) under the class loop of the
+// models (already checked by segment_check_shape; all of one M; lflats: log_model of each), on the current device and the
+// stream st.
+int segment_device(const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats, const unsigned short* d_sym, const i64* h_offs, int S, double ln_switch,
+                   hipStream_t st, const SegOut& out)
+{
+    const int K = (int)ms.size(), M = ms[0]->M;
+    // logarithms: lpi of every class | lA of every class | lB of every class
+    int sumN = 0, a_words = 0;
+    std::vector<int> comp0((size_t)K), a_at((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        comp0[(size_t)k] = sumN;
+        a_at[(size_t)k] = a_words;
+        sumN += ms[(size_t)k]->N;
+        a_words += ms[(size_t)k]->N * ms[(size_t)k]->N;
+    }
+    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M);
+    for (int k = 0; k < K; ++k) {
+        const std::vector<double>& lflat = lflats[(size_t)k];
+        const size_t N = (size_t)ms[(size_t)k]->N;
+        std::copy(lflat.begin(), lflat.begin() + N, params.begin() + comp0[(size_t)k]);
+        std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + a_at[(size_t)k]);
+        std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + a_words + (size_t)comp0[(size_t)k] * M);
+    }
+    // the packing: class after class, a class that does not fit the current slot opens the next
+    std::vector<e2hmm::SegLaneDev> lanes;
+    std::vector<int> slot_info;
+    std::vector<uint16_t> comp_cls((size_t)sumN);
+    int fill = 64;  // lanes taken of the current slot (64: none is open)
+    for (int k = 0; k < K; ++k) {
+        const int N = ms[(size_t)k]->N;
+        if (fill + N > 64) {
+            const int l0 = (int)lanes.size();
+            lanes.resize((size_t)l0 + 64);
+            for (int l = 0; l < 64; ++l) lanes[(size_t)(l0 + l)] = e2hmm::SegLaneDev{-1, 0, 0, l, 0, 0};
+            slot_info.push_back(0);
+            slot_info.push_back(0);
+            fill = 0;
+        }
+        const size_t l0 = lanes.size() - 64;
+        for (int j = 0; j < N; ++j) {
+            lanes[l0 + (size_t)(fill + j)] = e2hmm::SegLaneDev{k, j, N, fill, comp0[(size_t)k] + j, a_at[(size_t)k]};
+            comp_cls[(size_t)(comp0[(size_t)k] + j)] = (uint16_t)k;
+        }
+        int* info = &slot_info[slot_info.size() - 2];
+        info[0] = std::max(info[0], N);
+        info[1] = fill == 0 ? 1 : 0;  // (a second class in the slot clears it)
+        fill += N;
+    }
+    const int slots = (int)(lanes.size() / 64);
+    // the body: resident where the packing fits a workgroup's waves, unless ECOZ2_HMM_SEGMENT_BODY=looped
+    const char* body = getenv("ECOZ2_HMM_SEGMENT_BODY");
+    if (body && *body && strcmp(body, "resident") != 0 && strcmp(body, "looped") != 0)
+        return e2vq_set_error("ECOZ2_HMM_SEGMENT_BODY=%s: resident or looped", body);
+    const bool looped = slots > e2hmm::SEG_MAX_WAVES || (body && strcmp(body, "looped") == 0);
+
+    DeviceBuffer<double> d_params, d_logp, d_gbest;
+    DeviceBuffer<e2hmm::SegLaneDev> d_lanes;
+    DeviceBuffer<int> d_info, d_comp0, d_status, d_qlast, d_gsel;
+    DeviceBuffer<unsigned short> d_comp_cls, d_psi, d_cls, d_state;
+    DeviceBuffer<unsigned char> d_entered;
+    DeviceBuffer<i64> d_offs;
+    const i64 frames = h_offs[S];
+    if (d_params.upload(params.data(), params.size(), st) || d_lanes.upload(lanes.data(), lanes.size(), st) ||
+        d_info.upload(slot_info.data(), slot_info.size(), st) || d_comp0.upload(comp0.data(), comp0.size(), st) ||
+        d_comp_cls.upload(comp_cls.data(), comp_cls.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) ||
+        d_logp.reserve((size_t)S) || d_status.reserve((size_t)S) || d_qlast.reserve((size_t)S) || d_gbest.reserve((size_t)frames) ||
+        d_cls.reserve((size_t)frames) || d_state.reserve((size_t)frames) || d_entered.reserve((size_t)frames))
+        return 1;
+    const e2hmm::SegPlanDev pl{K, M, sumN, slots, a_words, d_lanes.get(), d_info.get(), d_params.get(), d_comp_cls.get(), d_comp0.get()};
+    // launches of whole streams whose psi (2 sumN bytes a frame) and g (4 bytes a frame) stay within the budget
+    const i64 row = 2 * (i64)sumN + 4;
+    i64 max_frames = 0;
+    const auto chunks = plan_chunks("ECOZ2_HMM_SEGMENT_CHUNK_BYTES", row, h_offs, S, &max_frames);
+    if (d_psi.reserve((size_t)max_frames * sumN) || d_gsel.reserve((size_t)max_frames)) {
+        const std::string why = e2vq_last_error();
+        return e2vq_set_error("hmm segment: no room for the back-pointer table of %lld frames x %d states (%lld bytes; "
+                              "ECOZ2_HMM_SEGMENT_CHUNK_BYTES bounds it by whole streams): %s",
+                              (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
+    }
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    // (one stream: a chunk's forward pass writes psi only after the previous chunk's backtrack has read it)
+    for (const auto& c : chunks) {
+        const int s0 = c.first, n = c.second - c.first;
+        if (e2hmm::launch_segment(pl, looped, d_sym, d_offs.get() + s0, n, h_offs[s0], ln_switch, d_psi.get(), d_gsel.get(), d_gbest.get(),
+                                  d_logp.get() + s0, d_qlast.get() + s0, d_status.get() + s0, st))
+            return e2vq_set_error("hmm segment: %d wave-slots of %d states cannot be launched", slots, sumN);
+        HIPCHK(hipGetLastError());
+        e2hmm::launch_segment_backtrack(pl, d_offs.get() + s0, n, h_offs[s0], d_psi.get(), d_gsel.get(), d_qlast.get() + s0,
+                                        d_status.get() + s0, d_cls.get(), d_state.get(), d_entered.get(), d_gbest.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    if (frames > 0) {
+        if (out.cls) HIPCHK(hipMemcpyAsync(out.cls, d_cls.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        if (out.state) HIPCHK(hipMemcpyAsync(out.state, d_state.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        if (out.entered) HIPCHK(hipMemcpyAsync(out.entered, d_entered.get(), (size_t)frames, hipMemcpyDeviceToHost, st));
+        if (out.gbest) HIPCHK(hipMemcpyAsync(out.gbest, d_gbest.get(), (size_t)frames * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (S > 0) {
+        if (out.log_prob) HIPCHK(hipMemcpyAsync(out.log_prob, d_logp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        if (out.status) HIPCHK(hipMemcpyAsync(out.status, d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_segment_kernel_ms)) return 1;
+    return 0;
+}
+
+// ---- input -> device symbols: the stage `hmm scan` and `hmm segment` share ----------------------------------------------------
+struct SymInput {
+    std::string path, csv;
+    int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
+    int sample_rate = 0;
+    int64_t samples = 0, T = 0;
+};
+struct SymInputs {
+    bool have_cb = false, need_cb = false;
+    int cbP = 0, cbM = 0;
+    std::vector<double> refl;
+    std::vector<SymInput> inputs;
+};
+struct SymStage {  // device buffers the inputs of one call reuse; symbols of the current input in d_sym
+    DeviceBuffer<double> d_frames;
+    DeviceBuffer<int32_t> d_status;
+    DeviceBuffer<unsigned short> d_sym;
+};
+struct VqSessionHolder {
+    e2vq_session* s = nullptr;
+    ~VqSessionHolder()
+    {
+        if (s) e2vq_session_destroy(s);
+    }
+};
+
+// the checks of the inputs against the models' M and the codebook, and the codebook itself: host only, no file written
+int sym_inputs_check(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs,
+                            int P, int W_ms, int O_ms, const char* csv_dir_or_file, SymInputs& si)
+{
+    si.have_cb = cb_filename && *cb_filename;
+    if (si.have_cb) {
+        char cls[96];
+        if (e2vq_cbook_info(cb_filename, cls, &si.cbP, &si.cbM)) return 1;
+        if (si.cbM != M) return e2vq_set_error("%s: codebook has M=%d but the models have M=%d", cb_filename, si.cbM, M);
+    }
+    const bool have_cb = si.have_cb;
+    const int cbP = si.cbP;
+    std::vector<SymInput>& inputs = si.inputs;
+    inputs.assign((size_t)num_inputs, SymInput());
+    const std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
+    const bool csv_is_file = num_inputs == 1 && ends_with(csv, ".csv");
+    for (int f = 0; f < num_inputs; ++f) {
+        SymInput& in = inputs[(size_t)f];
+        if (!input_filenames[f]) return e2vq_set_error("%s: NULL file name", who);
+        in.path = input_filenames[f];
+        char cls[96];
+        if (ends_with(in.path, ".seq")) {
+            in.kind = 2;
+            int m;
+            if (e2vq_seq_info(in.path.c_str(), cls, &m, &in.T)) return 1;
+            if (m != M) return e2vq_set_error("%s: codebook size %d differs from the models' %d", in.path.c_str(), m, M);
+        } else if (ends_with(in.path, ".prd")) {
+            in.kind = 1;
+            int p;
+            if (e2vq_prd_info(in.path.c_str(), cls, &p, &in.T)) return 1;
+            if (have_cb && p != cbP)
+                return e2vq_set_error("%s: prediction order %d differs from the codebook's %d", in.path.c_str(), p, cbP);
+            si.need_cb = true;
+        } else if (ends_with(in.path, ".wav")) {
+            in.kind = 0;
+            if (e2vq_wav_info(in.path.c_str(), &in.sample_rate, &in.samples, nullptr)) return 1;
+            if (have_cb && P != cbP) return e2vq_set_error("%s: prediction order -P %d differs from the codebook's %d", in.path.c_str(), P, cbP);
+            int win, off;
+            if (e2vq_lpc_frame_count(in.samples, in.sample_rate, W_ms, O_ms, &win, &off, &in.T)) return 1;
+            if (in.T < 0) return e2vq_set_error("%s: signal too short (%lld samples, window %d)", in.path.c_str(), (long long)in.samples, win);
+            si.need_cb = true;
+        } else {
+            return e2vq_set_error("%s: not a .wav, .prd or .seq file", in.path.c_str());
+        }
+        if (!csv.empty()) in.csv = csv_is_file ? csv : csv + "/" + e2vq_io::basename_noext(in.path.c_str()) + ".csv";
+        for (int g = 0; g < f && !in.csv.empty(); ++g)
+            if (inputs[(size_t)g].csv == in.csv) return e2vq_set_error("%s and %s would both write %s", inputs[(size_t)g].path.c_str(), in.path.c_str(), in.csv.c_str());
+    }
+    if (si.need_cb && !have_cb) return e2vq_set_error("%s: signals and predictors need a codebook", who);
+    if (si.need_cb) {
+        si.refl.resize((size_t)si.cbM * (cbP + 1));
+        if (e2vq_cbook_read(cb_filename, si.refl.data(), si.cbM)) return 1;
+    }
+    return 0;
+}
+
+// one input to symbols in stg.d_sym (read and uploaded once; frames and symbols stay on the device): *T_out of them
+int sym_input_to_device(const SymInput& in, const SymInputs& si, SymStage& stg, e2vq_session* vq, int device, int P, int W_ms,
+                               int O_ms, hipStream_t st, int64_t* T_out)
+{
+    const int cbP = si.cbP, NC = cbP + 1;
+    int64_t T = in.T;
+    std::vector<uint16_t> h_sym;
+    std::vector<double> h_frames;
+    if (in.kind == 2) {
+        h_sym.resize((size_t)std::max<int64_t>(T, 1));
+        if (T > 0 && e2vq_seq_read(in.path.c_str(), h_sym.data(), T)) return 1;
+        if (stg.d_sym.upload(h_sym.data(), (size_t)T, st)) return 1;
+        HIPCHK(hipStreamSynchronize(st));  // (`h_sym` is a local)
+    } else {
+        if (stg.d_frames.reserve((size_t)std::max<int64_t>(T, 1) * NC) || stg.d_sym.reserve((size_t)T + 64)) return 1;
+        if (in.kind == 1) {
+            h_frames.resize((size_t)std::max<int64_t>(T, 1) * NC);
+            bool fin = true;
+            if (T > 0 && e2vq_io::prd_read_range_mt(in.path.c_str(), cbP, 0, T, h_frames.data(), e2vq_io::io_threads(), &fin)) return 1;
+            if (!fin) return e2vq_set_error("%s: contains NaN or infinite values", in.path.c_str());
+            if (T > 0) HIPCHK(hipMemcpyAsync(stg.d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st));
+        } else {
+            std::vector<int32_t> samples((size_t)std::max<int64_t>(in.samples, 1));
+            if (e2vq_wav_read(in.path.c_str(), samples.data(), in.samples)) return 1;
+            if (stg.d_status.reserve((size_t)std::max<int64_t>(T, 1))) return 1;
+            int64_t T2 = 0;
+            if (T > 0 && e2vq_lpc_analyze(device, P, W_ms, O_ms, samples.data(), in.samples, in.sample_rate, stg.d_frames.get(),
+                                          stg.d_status.get(), T, &T2, 1))
+                return 1;
+            std::vector<int32_t> fst((size_t)T);
+            if (T > 0) HIPCHK(hipMemcpyAsync(fst.data(), stg.d_status.get(), (size_t)T * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            int64_t good = 0;
+            for (int64_t t = 0; t < T; ++t) good += fst[(size_t)t] == 0;
+            if (good != T) {
+                // frames whose Levinson recursion failed are left out, as `ecoz2 lpc` leaves them out of the .prd: the rest
+                // makes one round trip through the host (the only place where the frames leave the device)
+                h_frames.resize((size_t)T * NC);
+                HIPCHK(hipMemcpy(h_frames.data(), stg.d_frames.get(), (size_t)T * NC * 8, hipMemcpyDeviceToHost));
+                int64_t o = 0;
+                for (int64_t t = 0; t < T; ++t)
+                    if (fst[(size_t)t] == 0) memmove(h_frames.data() + (size_t)(o++) * NC, h_frames.data() + (size_t)t * NC, (size_t)NC * 8);
+                printf("%s: %lld frames left out: Levinson status != 0 (later frame times are early by their offsets)\n",
+                       in.path.c_str(), (long long)(T - good));
+                T = good;
+                if (T > 0) HIPCHK(hipMemcpyAsync(stg.d_frames.get(), h_frames.data(), (size_t)T * NC * 8, hipMemcpyHostToDevice, st));
+            }
+        }
+        if (T > 0 && e2vq_quantize_device(vq, stg.d_frames.get(), T, stg.d_sym.get(), nullptr)) return 1;
+        HIPCHK(hipStreamSynchronize(st));  // (`h_frames` is a local)
+    }
+    *T_out = T;
+    return 0;
+}
+
+// The models of `hmm scan` / `hmm segment`: loaded, all of one M
+struct FilesModels {
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    std::vector<const char*> names;  // the classes'
+    int M = 0;
+    int load(const char* const* files, unsigned n)
+    {
+        if (load_models(files, n, models)) return 1;
+        M = models[0].M;
+        for (unsigned k = 0; k < n; ++k) {
+            if (models[k].M != M) return e2vq_set_error("%s: model has M=%d but %s has M=%d", files[k], models[k].M, files[0], M);
+            ms.push_back(&models[k]);
+            names.push_back(models[k].class_name.c_str());
+        }
+        return 0;
+    }
+};
+
+// What `hmm scan` and `hmm segment` do once the command's own checks have passed (`who`: the entry point): the check of
+// the inputs and the codebook against M, still on the host alone; then one device, stream and quantize session, and
+// for every input its symbols on the device followed by the command's work on them, run(input, T, d_sym, stream).
+int run_on_files(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs, int P, int W_ms,
+                 int O_ms, const char* csv_dir_or_file,
+                 const std::function<int(const SymInput&, int64_t, const unsigned short*, hipStream_t)>& run)
+{
+    SymInputs si;
+    if (sym_inputs_check(who, M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, si)) return 1;
+    // ---- the device from here on --------------------------------------------------------------------------------
+    const int device = env_device();
+    if (require_device(device)) return 1;
+    SymStage stg;
+    Stream st;
+    if (st.create()) return 1;
+    VqSessionHolder vq;
+    if (si.need_cb) {
+        if (e2vq_session_create(device, si.cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, si.refl.data(), si.cbM))
+            return 1;
+    }
+    for (const SymInput& in : si.inputs) {
+        int64_t T = 0;
+        if (sym_input_to_device(in, si, stg, vq.s, device, P, W_ms, O_ms, st.s, &T)) return 1;
+        if (run(in, T, stg.d_sym.get(), st.s)) return 1;
+    }
+    return 0;
+}
+
+}  // namespace
+}  // namespace e2hmm_host
+using namespace e2hmm_host;
+
+// `seq show [-P] [-Q] --hmm <model>` (the reference's commented `ecoz2_seq_show_files`, src/ecoz2_lib/mod.rs:169-177,
+// with --full and -L of `seq show` on top).  Every file is loaded first; the sequences whose M is the model's then go
+// through one forward scoring call (with_prob) and one Viterbi call (gen_q_opt), and the report follows, file by file.
+extern "C" int e2vq_seq_show_files(int with_prob, int gen_q_opt, int no_sequence, const char* hmm_filename,
+                                   const char* const* sequence_filenames, int num_sequences, int full, int only_length)
+{
+    FlushStdout flush_on_return;
+    if (num_sequences < 0 || (num_sequences > 0 && !sequence_filenames)) return e2vq_set_error("e2vq_seq_show_files: bad arguments");
+    const bool model = with_prob || gen_q_opt;
+    Hmm h;
+    std::vector<double> lflat;
+    if (model) {
+        if (!hmm_filename || !*hmm_filename) return e2vq_set_error("-P / -Q need a model (--hmm)");
+        if (hmm_load(hmm_filename, h)) return 1;
+        if (log_model(h, lflat)) return 1;
+        if (require_device(env_device())) return 1;
+    }
+    struct File {
+        bool ok = false;
+        std::string cls;
+        int M = 0;
+        std::vector<uint16_t> sym;
+        int batch = -1;  // index among the sequences decoded / scored
+    };
+    std::vector<File> fs((size_t)num_sequences);
+    std::vector<uint16_t> sym;
+    std::vector<i64> offs(1, 0);
+    for (int i = 0; i < num_sequences; ++i) {
+        File& f = fs[(size_t)i];
+        char cls[96];
+        int64_t T;
+        if (e2vq_seq_info(sequence_filenames[i], cls, &f.M, &T)) continue;
+        f.sym.resize((size_t)T);
+        if (T > 0 && e2vq_seq_read(sequence_filenames[i], f.sym.data(), T)) continue;
+        f.ok = true;
+        f.cls = cls;
+        if (model && f.M == h.M) {
+            f.batch = (int)offs.size() - 1;
+            sym.insert(sym.end(), f.sym.begin(), f.sym.end());
+            offs.push_back((i64)sym.size());
+        }
+    }
+    const int S = (int)offs.size() - 1;
+    Scores lp;
+    std::vector<double> vlp((size_t)S);
+    std::vector<int> vst((size_t)S);
+    std::vector<uint16_t> path(sym.size());
+    if (model && S > 0) {
+        DevSeqs seqs;
+        if (seqs.upload(sym.data(), offs.data(), S)) return 1;
+        if (with_prob && score_device({&h}, seqs.sym, seqs.d_offs.get(), S, seqs.st.s, lp)) return 1;
+        if (gen_q_opt && viterbi_device(h.N, h.M, lflat, seqs.sym, seqs.d_offs.get(), offs.data(), S, seqs.st.s, path.data(), vlp.data(), vst.data()))
+            return 1;
+    }
+    for (int i = 0; i < num_sequences; ++i) {
+        const File& f = fs[(size_t)i];
+        if (!f.ok) {
+            printf("%s: Not a sequence\n", sequence_filenames[i]);
+            continue;
+        }
+        const size_t len = f.sym.size();
+        if (!no_sequence) {
+            if (only_length) {
+                printf("%zu\n", len);
+            } else {
+                printf("<%s(M=%d,L=%zu): ", f.cls.c_str(), f.M, len);
+                print_abbreviated(f.sym.data(), len, full != 0);
+                printf(">\n");
+            }
+        }
+        if (!model) continue;
+        if (f.batch < 0) {
+            printf("  codebook size M=%d differs from the model's M=%d: no log_prob, no q_opt\n", f.M, h.M);
+            continue;
+        }
+        const size_t b = (size_t)f.batch;
+        if (with_prob) printf("  log_prob = %.17g\n", lp.log_prob(b));
+        if (gen_q_opt) {
+            if (vst[b] != 2) {
+                printf("  q_opt = ");
+                print_abbreviated(path.data() + offs[b], len, full != 0);
+                printf("\n");
+            }
+            printf("  q_opt_log_prob = %.17g\n", vlp[b]);
+        }
+        for (size_t t = 0; t < len; ++t)
+            if ((int)f.sym[t] >= h.M) {
+                printf("  note: symbol %u at t = %zu is outside the model's alphabet (M = %d)\n", (unsigned)f.sym[t], t, h.M);
+                break;
+            }
+    }
+    return 0;
+}
+
+// fn ecoz2_seq_show_files(with_prob, gen_q_opt, show_sequence, hmm_filename, sequence_filenames, num_sequences)
+//                                                      src/ecoz2_lib/mod.rs:169-177 (commented out in the reference)
+// The third argument is the reference caller's `no_sequence` (its wrapper, :518-523, passes it there), not the
+// declaration's `show_sequence`: nonzero leaves the symbol line out.
+extern "C" int ecoz2_seq_show_files(int with_prob, int gen_q_opt, int no_sequence, const char* hmm_filename,
+                                    const char* const* sequence_filenames, int num_sequences)
+{
+    return e2vq_seq_show_files(with_prob, gen_q_opt, no_sequence, hmm_filename, sequence_filenames, num_sequences, 0, 0);
+}
+
+// Viterbi decoding of S host sequences under one model: ln P*, status and (path non-null) Q*
+extern "C" int e2vq_hmm_viterbi(int device, int N, int M, const double* pi, const double* A, const double* B,
+                                const uint16_t* sym, const int64_t* offs, int S, uint16_t* path, double* log_prob,
+                                int* status)
+{
+    Hmm h;
+    std::vector<double> lflat;
+    if (model_from_arrays(N, M, pi, A, B, h) || log_model(h, lflat) || check_offsets(offs, S)) return 1;
+    if (!log_prob || !status) return e2vq_set_error("e2vq_hmm_viterbi: log_prob and status are required");
+    if (require_device(device)) return 1;
+    DevSeqs seqs;
+    if (seqs.upload(sym, (const i64*)offs, S)) return 1;
+    return viterbi_device(N, M, lflat, seqs.sym, seqs.d_offs.get(), (const i64*)offs, S, seqs.st.s, path, log_prob, status);
+}
+
+// ---- hmm scan -----------------------------------------------------------------------------------------
+// window count of every stream (host only): win_offs[S + 1]
+extern "C" int e2vq_hmm_scan_windows(const int64_t* offs, int S, int64_t window_frames, int64_t hop_frames, int64_t* win_offs)
+{
+    if (scan_check_geometry("e2vq_hmm_scan_windows", window_frames, hop_frames)) return 1;
+    if (!win_offs) return e2vq_set_error("e2vq_hmm_scan_windows: bad arguments");
+    if (check_offsets(offs, S)) return 1;
+    scan_window_offsets((const i64*)offs, S, window_frames, hop_frames, (i64*)win_offs);
+    return 0;
+}
+
+extern "C" int e2vq_hmm_scan_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_scan_last_kernel_ms: bad arguments");
+    *ms = g_scan_kernel_ms;
+    return 0;
+}
+
+// every window of S streams under K models sharing M: each result is e2vq_hmm_score's for the window's symbols, bit for bit
+extern "C" int e2vq_hmm_scan(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                             const double* const* Bs, const void* sym, const int64_t* offs, int S, int64_t window_frames,
+                             int64_t hop_frames, int64_t* win_offs, double* mant, int64_t* exp2, int* status, double* log_probs,
+                             int* best, double* best_log_prob, int* second, double* second_log_prob, int sym_on_device)
+{
+    if (scan_check_geometry("e2vq_hmm_scan", window_frames, hop_frames)) return 1;
+    if (K < 1) return e2vq_set_error("e2vq_hmm_scan: %d models (at least 1)", K);
+    if (!Ns || !pis || !As || !Bs || S < 0 || (!sym && S > 0 && offs && offs[S] > 0)) return e2vq_set_error("e2vq_hmm_scan: bad arguments");
+    for (int k = 0; k < K; ++k)
+        if (Ns[k] < 1 || Ns[k] > e2hmm::MAX_N)
+            return e2vq_set_error("e2vq_hmm_scan: model %d has N=%d states (1 .. %d)", k, Ns[k], e2hmm::MAX_N);
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms) || check_offsets(offs, S)) return 1;
+    std::vector<i64> wo((size_t)S + 1);
+    scan_window_offsets((const i64*)offs, S, window_frames, hop_frames, wo.data());
+    if (win_offs) memcpy(win_offs, wo.data(), wo.size() * 8);
+    if (require_device(device)) return 1;
+    DevSeqs seqs;
+    if (seqs.symbols(sym, (size_t)offs[S], sym_on_device != 0)) return 1;
+    ScanOut out;
+    out.mant = mant, out.exp2 = exp2, out.status = status, out.log_probs = log_probs;
+    out.best = best, out.best_log_prob = best_log_prob, out.second = second, out.second_log_prob = second_log_prob;
+    return scan_device(ms, seqs.sym, (const i64*)offs, S, window_frames, hop_frames, seqs.st.s, out);
+}
+
+// CSV and stdout block of one scanned input from its two results per window (host only)
+extern "C" int e2vq_hmm_scan_report(const char* name, int64_t T, int K, const char* const* class_names, int64_t W,
+                                    int64_t window_frames, int64_t hop_frames, int W_ms, int O_ms, const int* best,
+                                    const double* best_log_prob, const int* second, const double* second_log_prob,
+                                    double min_margin, const char* csv_filename)
+{
+    FlushStdout flush_on_return;
+    if (!name || K < 1 || !class_names || W < 0 || (W > 0 && (!best || !best_log_prob || !second || !second_log_prob)))
+        return e2vq_set_error("e2vq_hmm_scan_report: bad arguments");
+    if (scan_check_geometry("e2vq_hmm_scan_report", window_frames, hop_frames)) return 1;
+    for (int64_t w = 0; w < W; ++w)
+        if (best[w] < 0 || best[w] >= K || second[w] < -1 || second[w] >= K)
+            return e2vq_set_error("e2vq_hmm_scan_report: window %lld names a model outside [0, %d)", (long long)w, K);
+    auto begin_s = [&](int64_t w) { return (double)(w * hop_frames * O_ms) / 1000.0; };
+    // (the end of the analysis window of the window's last frame)
+    auto end_s = [&](int64_t w) { return (double)((w * hop_frames + window_frames - 1) * O_ms + W_ms) / 1000.0; };
+    if (csv_filename && *csv_filename) {
+        std::string doc = "window,begin_frame,end_frame,begin_s,end_s,class,log_prob,second_class,second_log_prob\n";
+        for (int64_t w = 0; w < W; ++w) {
+            const bool has1 = best_log_prob[w] > -INFINITY, has2 = second[w] >= 0 && second_log_prob[w] > -INFINITY;
+            doc += std::to_string(w) + "," + std::to_string(w * hop_frames) + "," + std::to_string(w * hop_frames + window_frames) + "," +
+                   fmt_17g(begin_s(w)) + "," + fmt_17g(end_s(w)) + "," + (has1 ? class_names[best[w]] : "") + "," +
+                   fmt_17g(best_log_prob[w]) + "," + (has2 ? class_names[second[w]] : "") + "," +
+                   fmt_17g(second[w] >= 0 ? second_log_prob[w] : -INFINITY) + "\n";
+        }
+        if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
+    }
+    printf("%s: T=%lld  windows=%lld  (window %lld frames, hop %lld)\n", name, (long long)T, (long long)W, (long long)window_frames,
+           (long long)hop_frames);
+    std::vector<int64_t> won((size_t)K, 0);
+    int64_t none = 0;
+    for (int64_t w = 0; w < W; ++w) {
+        if (best_log_prob[w] > -INFINITY) ++won[(size_t)best[w]];
+        else ++none;
+    }
+    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)won[(size_t)k]);
+    if (none) printf("  (no model can emit the window): %lld\n", (long long)none);
+    printf("  runs (margin >= %g):\n", min_margin);
+    // maximal runs of consecutive windows won by one class with margin >= min_margin (a window no model can emit wins nothing)
+    auto winner = [&](int64_t w) -> int {
+        if (!(best_log_prob[w] > -INFINITY)) return -1;
+        const double second_lp = second[w] >= 0 ? second_log_prob[w] : -INFINITY;
+        return best_log_prob[w] - second_lp >= min_margin ? best[w] : -1;
+    };
+    for (int64_t w = 0; w < W;) {
+        const int c = winner(w);
+        int64_t e = w + 1;
+        while (e < W && winner(e) == c) ++e;
+        if (c >= 0) printf("    %.3f - %.3f %s\n", begin_s(w), end_s(e - 1), class_names[c]);
+        w = e;
+    }
+    if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
+    return 0;
+}
+
+// `hmm scan`: every input (.wav: lpc -> quantize -> scan; .prd: quantize -> scan; .seq: scan) under the models
+extern "C" int e2vq_hmm_scan_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                   const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                   int64_t window_frames, int64_t hop_frames, double min_margin, const char* csv_dir_or_file)
+{
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("e2vq_hmm_scan_files: no models");
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("e2vq_hmm_scan_files: no inputs");
+    if (scan_check_geometry("e2vq_hmm_scan_files", window_frames, hop_frames)) return 1;
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("e2vq_hmm_scan_files: window %d ms / offset %d ms", W_ms, O_ms);
+    FilesModels fm;
+    if (fm.load(model_filenames, num_models)) return 1;
+    auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
+        const i64 offs[2] = {0, T};
+        i64 wo[2];
+        scan_window_offsets(offs, 1, window_frames, hop_frames, wo);
+        const size_t W = (size_t)wo[1];
+        std::vector<int> best(W), second(W);
+        std::vector<double> lp1(W), lp2(W);
+        ScanOut out;
+        out.best = best.data(), out.best_log_prob = lp1.data(), out.second = second.data(), out.second_log_prob = lp2.data();
+        if (scan_device(fm.ms, d_sym, offs, 1, window_frames, hop_frames, st, out)) return 1;
+        HIPCHK(hipStreamSynchronize(st));  // (the host buffers of this input are locals)
+        return e2vq_hmm_scan_report(in.path.c_str(), T, (int)num_models, fm.names.data(), (int64_t)W, window_frames, hop_frames, W_ms, O_ms,
+                                    best.data(), lp1.data(), second.data(), lp2.data(), min_margin, in.csv.empty() ? nullptr : in.csv.c_str());
+    };
+    return run_on_files("e2vq_hmm_scan_files", fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+}
+
+// ---- hmm segment --------------------------------------------------------------------------------------
+extern "C" int e2vq_hmm_segment_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_segment_last_kernel_ms: bad arguments");
+    *ms = g_segment_kernel_ms;
+    return 0;
+}
+
+// the most likely path of each of S streams through the class loop of K models sharing M.  One device.
+extern "C" int e2vq_hmm_segment(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                                const double* const* Bs, const void* sym, const int64_t* offs, int S, double ln_switch,
+                                uint16_t* cls, uint16_t* state, uint8_t* entered, double* gbest, double* log_prob, int* status,
+                                int sym_on_device)
+{
+    if (K < 1) return e2vq_set_error("e2vq_hmm_segment: %d models (at least 1)", K);
+    if (!Ns || !pis || !As || !Bs || S < 0 || (!sym && S > 0 && offs && offs[S] > 0)) return e2vq_set_error("e2vq_hmm_segment: bad arguments");
+    if (segment_check_shape("e2vq_hmm_segment", K, Ns) || segment_check_switch("e2vq_hmm_segment", ln_switch)) return 1;
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    std::vector<std::vector<double>> lflats((size_t)K);
+    // (segment_check_shape has passed every N, and M is one: the models can fail here only before any logarithm does)
+    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms)) return 1;
+    for (int k = 0; k < K; ++k)
+        if (log_model(models[(size_t)k], lflats[(size_t)k])) return 1;
+    if (check_offsets(offs, S) || require_device(device)) return 1;
+    DevSeqs seqs;
+    if (seqs.symbols(sym, (size_t)offs[S], sym_on_device != 0)) return 1;
+    SegOut out;
+    out.cls = cls, out.state = state, out.entered = entered, out.gbest = gbest, out.log_prob = log_prob, out.status = status;
+    return segment_device(ms, lflats, seqs.sym, (const i64*)offs, S, ln_switch, seqs.st.s, out);
+}
+
+// CSV and stdout block of one segmented input from the per-frame outputs (host only)
+extern "C" int e2vq_hmm_segment_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
+                                       const uint16_t* cls, const uint8_t* entered, const double* gbest, double log_prob,
+                                       double ln_switch, const char* csv_filename)
+{
+    FlushStdout flush_on_return;
+    if (!name || K < 1 || !class_names || T < 0 || (T > 0 && (!cls || !entered || !gbest)))
+        return e2vq_set_error("e2vq_hmm_segment_report: bad arguments");
+    if (T > 0 && !entered[0]) return e2vq_set_error("e2vq_hmm_segment_report: frame 0 does not start a segment");
+    for (int64_t t = 0; t < T; ++t)
+        if (cls[t] >= K) return e2vq_set_error("e2vq_hmm_segment_report: frame %lld names a model outside [0, %d)", (long long)t, K);
+    struct Seg {
+        int64_t b, e;
+        double lp;
+    };
+    std::vector<Seg> segs;
+    for (int64_t b = 0; b < T;) {
+        int64_t e = b + 1;
+        while (e < T && !entered[e]) ++e;
+        // (gbest[e] of an entered frame e is the path's own cumulative score at e - 1)
+        const double hi = e == T ? log_prob : gbest[e], lo = b == 0 ? 0.0 : gbest[b] + ln_switch;
+        segs.push_back(Seg{b, e, hi - lo});
+        b = e;
+    }
+    auto begin_s = [&](int64_t b) { return (double)(b * O_ms) / 1000.0; };
+    // (the end of the analysis window of the segment's last frame)
+    auto end_s = [&](int64_t e) { return (double)((e - 1) * O_ms + W_ms) / 1000.0; };
+    if (csv_filename && *csv_filename) {
+        std::string doc = "segment,begin_frame,end_frame,begin_s,end_s,class,log_prob,log_prob_per_frame\n";
+        for (size_t i = 0; i < segs.size(); ++i) {
+            const Seg& g = segs[i];
+            doc += std::to_string(i) + "," + std::to_string(g.b) + "," + std::to_string(g.e) + "," + fmt_17g(begin_s(g.b)) + "," +
+                   fmt_17g(end_s(g.e)) + "," + class_names[cls[g.b]] + "," + fmt_17g(g.lp) + "," + fmt_17g(g.lp / (double)(g.e - g.b)) + "\n";
+        }
+        if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
+    }
+    printf("%s: T=%lld  segments=%zu  (switch penalty %g)\n", name, (long long)T, segs.size(), ln_switch);
+    std::vector<int64_t> frames((size_t)K, 0);
+    for (int64_t t = 0; t < T; ++t) ++frames[cls[t]];
+    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)frames[(size_t)k]);
+    printf("  segments:\n");
+    for (const Seg& g : segs) printf("    %.3f - %.3f %s\n", begin_s(g.b), end_s(g.e), class_names[cls[g.b]]);
+    if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
+    return 0;
+}
+
+// `hmm segment`: every input (.wav: lpc -> quantize -> segment; .prd: quantize -> segment; .seq: segment) under the models
+extern "C" int e2vq_hmm_segment_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                      const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                                      const char* csv_dir_or_file)
+{
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("e2vq_hmm_segment_files: no models");
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("e2vq_hmm_segment_files: no inputs");
+    if (segment_check_switch("e2vq_hmm_segment_files", ln_switch)) return 1;
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("e2vq_hmm_segment_files: window %d ms / offset %d ms", W_ms, O_ms);
+    FilesModels fm;
+    if (fm.load(model_filenames, num_models)) return 1;
+    std::vector<int> Ns;
+    for (const Hmm& h : fm.models) Ns.push_back(h.N);
+    if (segment_check_shape("e2vq_hmm_segment_files", (int)num_models, Ns.data())) return 1;
+    std::vector<std::vector<double>> lflats((size_t)num_models);
+    for (unsigned k = 0; k < num_models; ++k)
+        if (log_model(fm.models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
+        const i64 offs[2] = {0, T};
+        const size_t n = (size_t)std::max<int64_t>(T, 1);
+        std::vector<uint16_t> cls(n);
+        std::vector<uint8_t> entered(n);
+        std::vector<double> gbest(n);
+        double lp = 0.0;
+        int status = 0;
+        SegOut out;
+        out.cls = cls.data(), out.entered = entered.data(), out.gbest = gbest.data(), out.log_prob = &lp, out.status = &status;
+        if (segment_device(fm.ms, lflats, d_sym, offs, 1, ln_switch, st, out)) return 1;
+        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), fm.M);
+        return e2vq_hmm_segment_report(in.path.c_str(), T, (int)num_models, fm.names.data(), W_ms, O_ms, cls.data(), entered.data(),
+                                       gbest.data(), lp, ln_switch, in.csv.empty() ? nullptr : in.csv.c_str());
+    };
+    return run_on_files("e2vq_hmm_segment_files", fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+}

@@ -1,0 +1,220 @@
+// hmm_host.h -- what the host units of the HMM consumers share (hmm_model.cpp: models, files, sequences; hmm_train.cpp:
+// Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi, scan, segment).
+// The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
+// pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
+// that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
+// Definitions (file layout, generator, scaled Baum-Welch with exact fixed-point sums, stopping rule): this repo's own,
+// written down in oracle/hmm_oracle.h and DESIGN.md.  Internal.
+#pragma once
+#include "../../include/ecoz2_classify.h"
+#include "../../include/ecoz2_vq.h"
+#include "hip_host.h"
+#include "hmm_device.h"
+#include "host_util.h"
+#include "vq_io.h"
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <string>
+#include <vector>
+
+namespace e2hmm_host {
+using namespace e2hip;
+using namespace e2host;
+using e2hmm::ModelDev;
+typedef long long i64;
+
+// ---- model (hmm_model.cpp) -----------------------------------------------------------------------------------------
+extern uint64_t g_rng;  // the generator's state (ecoz2_set_random_seed); hmm_init draws from it
+
+struct Hmm {
+    std::string class_name;
+    int N = 0, M = 0;
+    std::vector<double> pi, A, B;
+    void resize(int n, int m)
+    {
+        N = n;
+        M = m;
+        pi.assign((size_t)n, 0.0);
+        A.assign((size_t)n * n, 0.0);
+        B.assign((size_t)n * m, 0.0);
+    }
+    // pi | A | B as one flat block of params() doubles: how every device parameter buffer holds a model
+    size_t params() const { return pi.size() + A.size() + B.size(); }
+    void pack(double* q) const
+    {
+        std::copy(pi.begin(), pi.end(), q);
+        std::copy(A.begin(), A.end(), q + pi.size());
+        std::copy(B.begin(), B.end(), q + pi.size() + A.size());
+    }
+    void unpack(const double* q)
+    {
+        std::copy(q, q + pi.size(), pi.begin());
+        std::copy(q + pi.size(), q + pi.size() + A.size(), A.begin());
+        std::copy(q + pi.size() + A.size(), q + params(), B.begin());
+    }
+    // the model as the device sees it, its block at `base`
+    ModelDev dev(const double* base) const { return ModelDev{N, M, base, base + N, base + N + (size_t)N * N}; }
+};
+
+// the shapes a model may have
+inline bool shape_ok(int N, int M) { return N >= 1 && N <= e2hmm::MAX_N && M >= 1 && M <= 65536; }
+
+int hmm_init(Hmm& h, int type);
+int hmm_save(const std::string& path, const Hmm& h);
+int hmm_load(const char* path, Hmm& h);
+int load_models(const char* const* files, unsigned n, std::vector<Hmm>& models);
+int log_model(const Hmm& h, std::vector<double>& flat);
+// a model from the caller's arrays and back
+int model_from_arrays(int N, int M, const double* pi, const double* A, const double* B, Hmm& h);
+void model_to_arrays(const Hmm& h, double* pi, double* A, double* B);
+// K models of one M from per-model arrays; ms: pointers to them
+int models_from_arrays(int K, const int* Ns, int M, const double* const* pis, const double* const* As, const double* const* Bs,
+                       std::vector<Hmm>& models, std::vector<const Hmm*>& ms);
+
+// natural log of mant * 2^exp2 (oracle: e2h_log_prob)
+inline double log_prob(double mant, i64 exp2)
+{
+    if (!(mant > 0.0)) return -INFINITY;
+    return log(mant) + (double)exp2 * M_LN2;
+}
+
+// a byte budget from the environment, at least 1
+inline i64 env_bytes(const char* name, i64 dflt)
+{
+    const char* v = getenv(name);
+    return std::max<i64>(v && *v ? atoll(v) : dflt, 1);
+}
+
+// ---- sequences (hmm_model.cpp) -------------------------------------------------------------------------------------
+struct SeqSet {
+    std::vector<std::string> files, classes;
+    std::vector<uint16_t> sym;  // concatenated
+    std::vector<i64> offs;      // S + 1
+    int M = -1;                 // codebook size (all equal, unless loaded with mixed_M)
+    std::vector<int> Ms;        // each file's codebook size
+    int S() const { return (int)files.size(); }
+};
+
+// mixed_M: files of different codebook sizes are accepted (ss.M is then the first file's)
+int load_sequences(const char* const* files, unsigned n, SeqSet& ss, bool mixed_M = false);
+// S + 1 offsets that start at 0 and never decrease (the kernels index the symbols with them)
+int check_offsets(const int64_t* offs, int S);
+
+// Host sequences on the device, and the stream the call works on.  The symbols are uploaded, or the caller's device
+// pointer is adopted; nothing here synchronises.  Declare it after every buffer and host mirror the stream's work
+// touches (a Trainer, a Scores): its Stream then waits before they are released (see Stream).
+struct DevSeqs {
+    DeviceBuffer<unsigned short> d_sym;
+    DeviceBuffer<i64> d_offs;
+    std::vector<i64> h_offs;              // of a slice: its offsets, from 0
+    const unsigned short* sym = nullptr;  // d_sym, or the adopted pointer
+    Stream st;                            // (after the buffers: see Stream)
+    // the stream and n symbols alone (the offsets stay with the caller)
+    int symbols(const void* src, size_t n, bool on_device = false)
+    {
+        if (st.create()) return 1;
+        if (!on_device && d_sym.upload((const unsigned short*)src, n, st.s)) return 1;
+        sym = on_device ? (const unsigned short*)src : d_sym.get();
+        return 0;
+    }
+    // S whole sequences
+    int upload(const uint16_t* src, const i64* offs, int S) { return symbols(src, (size_t)offs[S]) || d_offs.upload(offs, (size_t)S + 1, st.s); }
+    // the sequences [s0, s1) of a set
+    int upload_slice(const SeqSet& ss, i64 s0, i64 s1)
+    {
+        const i64 a = ss.offs[(size_t)s0];
+        for (i64 i = s0; i <= s1; ++i) h_offs.push_back(ss.offs[(size_t)i] - a);
+        return upload(ss.sym.data() + a, h_offs.data(), (int)(s1 - s0));
+    }
+};
+
+// ---- many models at once -------------------------------------------------------------------
+// The sequences a batch's models work on: host symbols and S + 1 offsets from 0.  Each model takes a range of them; the
+// models of different N of one class and M share theirs, the classes of `--all-classes` have disjoint ones.
+struct SeqStore {
+    const uint16_t* sym = nullptr;
+    const i64* offs = nullptr;
+};
+
+// The sequences of one batch (of trainings or of scorings): the jobs' ranges [s_lo, s_hi) of the store merged into
+// disjoint runs that follow one another, so that a sequence goes to the device once however many jobs use it.
+struct BatchSeqs {
+    std::vector<std::pair<int, int>> merged;  // the runs, as ranges of the store, ascending
+    std::vector<int> run_at;                  // batch index of each run's first sequence
+    std::vector<i64> offs;                    // the batch's sequences: their symbol offsets, from 0
+    BatchSeqs(std::vector<std::pair<int, int>> ranges, const SeqStore& ss);
+    int local(int s) const;  // batch index of the store's sequence s (one of a range given)
+    int upload_symbols(const SeqStore& ss, unsigned short* d_sym, hipStream_t st) const;  // d_sym: offs.back() symbols
+};
+
+// the checks the array-level grid entry points make of model k; then: the (offset, end) ranges of `what` do not overlap
+int grid_model_check(int k, int N, int M, i64 seq_lo, i64 seq_hi, int S, i64 param_off);
+int check_disjoint(std::vector<std::pair<i64, i64>> ranges, const char* what);
+
+// ---- scores (hmm_classify.cpp) -----------------------------------------------------------------------------------------
+// P(O) = mant * 2^exp2 and the status of scored sequences: the device slots the kernels fill and their host mirrors
+// (Host: HostVec, or PinnedBuffer where the copy back must not wait for the host).  reserve() makes the device slots
+// only; the host mirrors are made by download(), after the launches, so that a large result set is allocated while the
+// kernels run -- or ahead of time by reserve_host(), which pinned mirrors need.
+template <typename T>
+struct HostVec {
+    std::vector<T> v;
+    int reserve(size_t n) { return v.resize(std::max(n, v.size())), 0; }
+    T* get() { return v.data(); }
+    const T* get() const { return v.data(); }
+};
+template <template <typename> class Host>
+struct ScoresT {
+    DeviceBuffer<double> d_mant;
+    DeviceBuffer<i64> d_exp;
+    DeviceBuffer<int> d_status;
+    Host<double> mant;
+    Host<i64> exp2;
+    Host<int> status;
+    int reserve(size_t n) { return d_mant.reserve(n) || d_exp.reserve(n) || d_status.reserve(n); }
+    int reserve_host(size_t n) { return mant.reserve(n) || exp2.reserve(n) || status.reserve(n); }
+    // enqueues the copy of the first n results to the host mirrors (the caller synchronises)
+    int download(size_t n, hipStream_t st)
+    {
+        if (reserve_host(n)) return 1;
+        if (!n) return 0;
+        HIPCHK(hipMemcpyAsync(mant.get(), d_mant.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(exp2.get(), d_exp.get(), n * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(status.get(), d_status.get(), n * 4, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    bool ok(size_t i) const { return status.get()[i] == 0; }
+    // natural log; -inf when the model cannot emit the sequence or a symbol is outside its alphabet
+    double log_prob(size_t i) const { return ok(i) ? e2hmm_host::log_prob(mant.get()[i], exp2.get()[i]) : -INFINITY; }
+    // result i into the caller's arrays (any may be null)
+    void get(size_t i, double* m, int64_t* e, int* s, double* lp) const
+    {
+        if (m) *m = mant.get()[i];
+        if (e) *e = exp2.get()[i];
+        if (s) *s = status.get()[i];
+        if (lp) *lp = log_prob(i);
+    }
+};
+typedef ScoresT<HostVec> Scores;
+
+struct DevModels {  // a set of models on the device
+    DeviceBuffer<double> params;  // all pi | A | B, model after model
+    DeviceBuffer<ModelDev> table;
+    std::vector<ModelDev> host;
+    int maxN = 0;
+    int upload(const std::vector<const Hmm*>& ms, hipStream_t st);
+};
+
+// scores of S device-resident sequences under K models: sc[s * K + k]
+int score_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* d_offs, int S, hipStream_t st, Scores& sc);
+
+}  // namespace e2hmm_host

@@ -1,4 +1,4 @@
-// host_util.h -- host-side helpers shared by the `.seq` consumers (seq_models.cpp, hmm_host.cpp): Rust-style number
+// host_util.h -- host-side helpers shared by the `.seq` consumers (seq_models.cpp, the hmm_*.cpp units): Rust-style number
 // formatting, small file helpers, and C12nResults, the classification report of /root/reference/src/c12n/mod.rs
 // (which, per its line 5, is a translation of the C report the HMM classifier prints).  Internal.
 #pragma once
