@@ -76,6 +76,38 @@ def levinson(r):
     return status, pe
 
 
+def lpca(w, P):
+    """lpca1 (lpca_rs.rs:28-75) on windowed frames w (T, n) -> (status, pe, r, rc, a) as lpca1 leaves them: a row stops
+    at the step where pe <= 0 first holds (status 2): pe is that non-positive value, rc and a are what the step left,
+    zeros beyond it.  A row with r[0] == 0 (status 1) has pe = 0 and rc, a all zero: the kernels' convention
+    (lpc_levinson.h); host ecoz2_lpca returns before it writes rc and a there.  rc[0] = 0."""
+    r = autocorrelation(np.asarray(w, dtype=np.float64), P)
+    T, NC = r.shape
+    status = np.where(r[:, 0] == 0.0, 1, 0).astype(np.int32)
+    run = status == 0
+    pe = np.where(run, r[:, 0], 0.0)
+    rc = np.zeros((T, NC))
+    a = np.zeros((T, NC))
+    a[run, 0] = 1.0
+    with np.errstate(all="ignore"):
+        for k in range(1, NC):
+            s = np.zeros(T)
+            for i in range(1, k + 1):
+                s = s - a[:, k - i] * r[:, i]
+            akk = s / pe
+            rc[run, k] = akk[run]
+            a[run, k] = akk[run]
+            for i in range(1, (k >> 1) + 1):
+                ai, aj = a[:, i].copy(), a[:, k - i].copy()
+                a[run, i] = (ai + akk * aj)[run]
+                a[run, k - i] = (aj + akk * ai)[run]
+            pe = np.where(run, pe * (1.0 - akk * akk), pe)
+            failed = run & (pe <= 0.0)
+            status[failed] = 2
+            run = run & ~failed
+    return status, pe, r, rc, a
+
+
 def analyze(samples, sample_rate, P=36, W=45, O=15):
     """-> (frames (T, P+1), status (T,)): r / pe for status 0 (lpc_rs.rs:126-131), zero rows otherwise."""
     r = autocorrelation(windowed_frames(samples, sample_rate, W, O), P)

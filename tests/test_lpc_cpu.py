@@ -1,5 +1,6 @@
 """CPU tests of the LPC front-end (`ecoz2 lpc`): the reference's per-frame helper ecoz2_lpca on its own fixture, the
-exported symbols, the WAV reader, the frame count, the CLI's argument errors and the ISA of the NC = 37 kernel."""
+exported symbols, the WAV reader, the frame count, the numpy restatement against ecoz2_lpca at every status, the CLI's
+argument errors and the ISA of the NC = 37 kernel."""
 import os
 import re
 import subprocess
@@ -126,6 +127,70 @@ def test_restatement_matches_lpca_frame_by_frame():
         assert st == status[t]
         if st == 0:
             assert np.array_equal(_bits(r / pe), _bits(frames[t]))
+
+
+# ---- rows that reach every Levinson status through a real autocorrelation (shared with test_gpu_lpc_shapes) --------------
+LANE = (12, 16, 20, 24, 28, 32, 36, 40)  # orders with a lane-per-frame instantiation (E2VQ_LPC_NC_LIST)
+GENERIC = (1, 2, 13, 41, 79, 80)  # block-per-frame path: the smallest orders, just off a lane order, the largest
+# cos(2 pi f k) times 1e-161 and 3e-162: the squares land in the subnormal range, where pe * (1 - akk^2) rounds to <= 0
+# (status 2) for some rows and not for others; times 1e-162 every square underflows to zero (r[0] == 0: status 1).
+# Two orders' worth of exceptions, picked on the CPU with the restatement: at P >= 79 no row scaled by 1e-161 or less
+# keeps status 0 at most frame lengths, and at P = 1, n = 2 no row scaled by 3e-162 or more reaches status 2.
+def subnormal_scales(P):
+    return ((3e-161, 1e-161) if P >= 79 else (3e-162, 2e-162) if P == 1 else (1e-161, 3e-162)) + (1e-162,)
+
+
+def frame_lengths(NC):
+    """Around each phase of the lane kernel's autocorrelation: first NC samples only, no main loop, an empty tail."""
+    return (NC, NC + 1, 2 * NC - 1, 2 * NC, 2 * NC + 1, 2 * NC + 3, 3 * NC, 3 * NC + 7)
+
+
+def subnormal_rows(P, n):
+    f = np.linspace(0.001, 0.45, 200)
+    x = np.cos(2 * np.pi * f[:, None] * np.arange(n)[None, :])
+    return np.concatenate([x * sc for sc in subnormal_scales(P)])
+
+
+def lpca_rows(P, n):
+    """Windowed frames (rows, n): seeded normal rows, two AR rows, a zero row, a row that is zero except for its last
+    sample, and the subnormal-scale rows."""
+    rng = np.random.default_rng(1000 * P + n)
+    last = np.zeros((1, n))
+    last[0, -1] = 0.75
+    ar = [lpc_wavs.ar_source(s, 10, n, 0.6)[None, :] for s in (21, 22)]
+    return np.concatenate([rng.standard_normal((8, n)), *ar, np.zeros((1, n)), last, subnormal_rows(P, n)])
+
+
+@pytest.mark.parametrize("P", LANE + GENERIC)
+def test_restatement_lpca_matches_host_lpca_at_every_status(P):
+    """R.lpca (frozen rows: what lpca1 leaves in pe, rc and a when it stops) against host ecoz2_lpca, row by row on the
+    bits, on the rows the GPU test uses at this order.  The subnormal-scale rows alone give statuses 0, 1 and 2 at every
+    frame length (asserted here on the restatement, before the host is asked).  Status 1: the host returns before it
+    writes rc and a, so only status, pe and r are compared.  These rows give no NaN or infinity in rc or a (pe <= 0 ends
+    the recursion first); the comparison still goes by NaN position.  Signal mode cannot be steered into status 2:
+    integer sinusoids (16- and 32-bit, P up to 80) and unscaled cosines never gave it, so no test tries."""
+    for n in frame_lengths(P + 1):
+        x = lpca_rows(P, n)
+        st, pe, r, rc, a = R.lpca(x, P)
+        assert set(st[-600:]) == {0, 1, 2}, (P, n)
+        assert st[10] == 1 and st[11] == 0 and (st[:10] == 0).all(), (P, n)
+        for t in range(len(x)):
+            st_h, pe_h, r_h, rc_h, a_h = e.lpc.lpca(x[t], P)
+            assert st_h == st[t] and _bits([pe_h]) == _bits(pe[t:t + 1]), (P, n, t)
+            assert np.array_equal(_bits(r_h), _bits(r[t])), (P, n, t)
+            if st_h != 1:
+                for got, ref in ((rc_h, rc[t]), (a_h, a[t])):
+                    nan = np.isnan(ref)
+                    assert np.array_equal(np.isnan(got), nan), (P, n, t)
+                    assert np.array_equal(_bits(got[~nan]), _bits(ref[~nan])), (P, n, t)
+
+
+def test_restatement_lpca_agrees_with_levinson():
+    """On rows that do not fail, the frozen restatement and the one `analyze` uses are the same numbers."""
+    x = lpca_rows(12, 29)
+    st, pe, r, _rc, _a = R.lpca(x, 12)
+    st_l, pe_l = R.levinson(r)
+    assert np.array_equal(st, st_l) and np.array_equal(_bits(pe[st == 0]), _bits(pe_l[st == 0]))
 
 
 def _cli(*args, cwd=None):
