@@ -65,8 +65,10 @@ static int usage()
             "                  (where in each recording every class occurs: the models over sliding windows; --hop defaults to --window)\n"
             "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  --switch-penalty <x <= 0 | -inf> [-c <csv dir|file.csv>]\n"
+            "                  [--posteriors [--frame-posteriors <dir>]]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
-            "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment)\n"
+            "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
+            "                  --posteriors adds each segment's mean and least class posterior, and the per-frame table)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -830,7 +832,8 @@ static int hmm_segment_cmd(int argc, char** argv)
     int P = 36, W = 45, O = 15;
     double ln_switch = 0.0;
     bool have_switch = false;
-    std::string codebook, csv;
+    bool posteriors = false;
+    std::string codebook, csv, frames_dir;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -851,6 +854,8 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
         else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
         else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "--posteriors") posteriors = true;
+        else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
         else if (a == "--switch-penalty") {
             const char* v = val("--switch-penalty");
             char* end = nullptr;
@@ -874,6 +879,7 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    if (!frames_dir.empty() && !posteriors) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
     std::vector<std::string> hmm_files, inputs;
     e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
     if (hmm_files.empty()) { printf("No models given\n"); return 0; }
@@ -885,8 +891,12 @@ static int hmm_segment_cmd(int argc, char** argv)
     printf("ECOZ2 C version: %s\n", ecoz2_version());
     printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
     auto pm = cptrs(hmm_files), pi = cptrs(inputs);
-    if (e2vq_hmm_segment_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(), (int)pi.size(), P,
-                               W, O, ln_switch, csv.empty() ? nullptr : csv.c_str())) {
+    const char* cb = codebook.empty() ? nullptr : codebook.c_str();
+    const char* out = csv.empty() ? nullptr : csv.c_str();
+    const int failed = posteriors ? e2vq_hmm_segment_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+                                                                      ln_switch, out, frames_dir.empty() ? nullptr : frames_dir.c_str())
+                                  : e2vq_hmm_segment_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O, ln_switch, out);
+    if (failed) {
         printf("%s\n", e2vq_last_error());
         return 1;
     }

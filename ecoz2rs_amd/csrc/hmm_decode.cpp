@@ -1,7 +1,8 @@
 // hmm_decode.cpp -- decoding on the GPU: Viterbi under one model (`seq show -P / -Q --hmm`, e2vq_hmm_viterbi; DESIGN.md
-// 4.8.1), the models over the windows of whole recordings (`hmm scan`, 4.8.5) and the joint Viterbi through the class
-// loop of all models (`hmm segment`, 4.8.6), with the stage that turns a .wav / .prd / .seq input into device symbols;
-// over the kernels of hmm_viterbi.hip, hmm_scan.hip and hmm_segment.hip.
+// 4.8.1), the models over the windows of whole recordings (`hmm scan`, 4.8.5), the joint Viterbi through the class
+// loop of all models (`hmm segment`, 4.8.6) and the class posteriors under that loop (`--posteriors`, 4.8.7), with the
+// stage that turns a .wav / .prd / .seq input into device symbols; over the kernels of hmm_viterbi.hip, hmm_scan.hip,
+// hmm_segment.hip and hmm_posterior.hip.
 #include "hmm_host.h"
 
 #include <functional>
@@ -304,6 +305,54 @@ struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered
     int* status = nullptr;
 };
 
+// The packing of the classes into wave-slots of 64 lanes that `hmm segment` and its posteriors share: class after class, a
+// class that does not fit the open slot opens the next.  a_ld(N): the leading dimension of a class's A in the device block
+// (a_at / a_words count N x a_ld(N) words a class).
+struct SegPacking {
+    int sumN = 0, a_words = 0, slots = 0;
+    std::vector<int> comp0, a_at;            // [K]: composite index of state 0, offset of A
+    std::vector<int> slot_info;              // [slots][2]: the largest N of the slot, 1 when the slot holds one class
+    std::vector<e2hmm::SegLaneDev> lanes;    // [slots][64]
+    std::vector<uint16_t> comp_cls;          // [sumN]
+};
+SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int))
+{
+    SegPacking pk;
+    const int K = (int)Ns.size();
+    pk.comp0.resize((size_t)K);
+    pk.a_at.resize((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        pk.comp0[(size_t)k] = pk.sumN;
+        pk.a_at[(size_t)k] = pk.a_words;
+        pk.sumN += Ns[(size_t)k];
+        pk.a_words += Ns[(size_t)k] * a_ld(Ns[(size_t)k]);
+    }
+    pk.comp_cls.resize((size_t)pk.sumN);
+    int fill = 64;  // lanes taken of the current slot (64: none is open)
+    for (int k = 0; k < K; ++k) {
+        const int N = Ns[(size_t)k];
+        if (fill + N > 64) {
+            const int l0 = (int)pk.lanes.size();
+            pk.lanes.resize((size_t)l0 + 64);
+            for (int l = 0; l < 64; ++l) pk.lanes[(size_t)(l0 + l)] = e2hmm::SegLaneDev{-1, 0, 0, l, 0, 0};
+            pk.slot_info.push_back(0);
+            pk.slot_info.push_back(0);
+            fill = 0;
+        }
+        const size_t l0 = pk.lanes.size() - 64;
+        for (int j = 0; j < N; ++j) {
+            pk.lanes[l0 + (size_t)(fill + j)] = e2hmm::SegLaneDev{k, j, N, fill, pk.comp0[(size_t)k] + j, pk.a_at[(size_t)k]};
+            pk.comp_cls[(size_t)(pk.comp0[(size_t)k] + j)] = (uint16_t)k;
+        }
+        int* info = &pk.slot_info[pk.slot_info.size() - 2];
+        info[0] = std::max(info[0], N);
+        info[1] = fill == 0 ? 1 : 0;  // (a second class in the slot clears it)
+        fill += N;
+    }
+    pk.slots = (int)(pk.lanes.size() / 64);
+    return pk;
+}
+
 // The joint Viterbi of S device-resident streams (h_offs: their S + 1 offsets, on the host) under the class loop of the
 // models (already checked by segment_check_shape; all of one M; lflats: log_model of each), on the current device and the
 // stream st.
@@ -311,15 +360,16 @@ int segment_device(const std::vector<const Hmm*>& ms, const std::vector<std::vec
                    hipStream_t st, const SegOut& out)
 {
     const int K = (int)ms.size(), M = ms[0]->M;
+    std::vector<int> Ns;
+    for (const Hmm* h : ms) Ns.push_back(h->N);
+    const SegPacking pk = pack_slots(Ns, [](int N) { return N; });
+    const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
+    const std::vector<int>& comp0 = pk.comp0;
+    const std::vector<int>& a_at = pk.a_at;
+    const std::vector<int>& slot_info = pk.slot_info;
+    const std::vector<e2hmm::SegLaneDev>& lanes = pk.lanes;
+    const std::vector<uint16_t>& comp_cls = pk.comp_cls;
     // logarithms: lpi of every class | lA of every class | lB of every class
-    int sumN = 0, a_words = 0;
-    std::vector<int> comp0((size_t)K), a_at((size_t)K);
-    for (int k = 0; k < K; ++k) {
-        comp0[(size_t)k] = sumN;
-        a_at[(size_t)k] = a_words;
-        sumN += ms[(size_t)k]->N;
-        a_words += ms[(size_t)k]->N * ms[(size_t)k]->N;
-    }
     std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M);
     for (int k = 0; k < K; ++k) {
         const std::vector<double>& lflat = lflats[(size_t)k];
@@ -328,32 +378,6 @@ int segment_device(const std::vector<const Hmm*>& ms, const std::vector<std::vec
         std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + a_at[(size_t)k]);
         std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + a_words + (size_t)comp0[(size_t)k] * M);
     }
-    // the packing: class after class, a class that does not fit the current slot opens the next
-    std::vector<e2hmm::SegLaneDev> lanes;
-    std::vector<int> slot_info;
-    std::vector<uint16_t> comp_cls((size_t)sumN);
-    int fill = 64;  // lanes taken of the current slot (64: none is open)
-    for (int k = 0; k < K; ++k) {
-        const int N = ms[(size_t)k]->N;
-        if (fill + N > 64) {
-            const int l0 = (int)lanes.size();
-            lanes.resize((size_t)l0 + 64);
-            for (int l = 0; l < 64; ++l) lanes[(size_t)(l0 + l)] = e2hmm::SegLaneDev{-1, 0, 0, l, 0, 0};
-            slot_info.push_back(0);
-            slot_info.push_back(0);
-            fill = 0;
-        }
-        const size_t l0 = lanes.size() - 64;
-        for (int j = 0; j < N; ++j) {
-            lanes[l0 + (size_t)(fill + j)] = e2hmm::SegLaneDev{k, j, N, fill, comp0[(size_t)k] + j, a_at[(size_t)k]};
-            comp_cls[(size_t)(comp0[(size_t)k] + j)] = (uint16_t)k;
-        }
-        int* info = &slot_info[slot_info.size() - 2];
-        info[0] = std::max(info[0], N);
-        info[1] = fill == 0 ? 1 : 0;  // (a second class in the slot clears it)
-        fill += N;
-    }
-    const int slots = (int)(lanes.size() / 64);
     // the body: resident where the packing fits a workgroup's waves, unless ECOZ2_HMM_SEGMENT_BODY=looped
     const char* body = getenv("ECOZ2_HMM_SEGMENT_BODY");
     if (body && *body && strcmp(body, "resident") != 0 && strcmp(body, "looped") != 0)
@@ -411,6 +435,118 @@ int segment_device(const std::vector<const Hmm*>& ms, const std::vector<std::vec
     }
     HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
     if (timer.elapsed_ms(&g_segment_kernel_ms)) return 1;
+    return 0;
+}
+
+// ---- hmm segment --posteriors: forward-backward through the same class loop -------------------------------
+thread_local float g_posteriors_kernel_ms = -1.f;  // e2vq_hmm_segment_posteriors_last_kernel_ms
+
+int posteriors_a_ld(int N) { return N | 1; }  // (odd: see hmm_posterior.hip)
+
+// only the resident layout exists: a packing of more than SEG_MAX_WAVES slots is refused (host only)
+int posteriors_check_slots(const char* who, int K, const int* Ns)
+{
+    const int slots = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld).slots;
+    if (slots > e2hmm::SEG_MAX_WAVES)
+        return e2vq_set_error("%s: the classes take %d wave-slots of 64 lanes (at most %d: the posteriors have no looped body)", who,
+                              slots, e2hmm::SEG_MAX_WAVES);
+    return 0;
+}
+
+// log_model's refusal, without the logarithms: a negative, NaN or infinite parameter (then no NaN can arise on the device)
+int posteriors_check_params(const Hmm& h)
+{
+    const std::vector<double>* parts[3] = {&h.pi, &h.A, &h.B};
+    const char* names[3] = {"pi", "A", "B"};
+    for (int k = 0; k < 3; ++k)
+        for (size_t i = 0; i < parts[k]->size(); ++i) {
+            const double x = (*parts[k])[i];
+            if (!(x >= 0.0) || !std::isfinite(x))
+                return e2vq_set_error("HMM parameter %s[%zu] = %g: not a finite non-negative number", names[k], i, x);
+        }
+    return 0;
+}
+
+struct PostOut {  // host arrays, any may be null; post: K doubles a frame; per stream: log_prob, status
+    double* post = nullptr;
+    double* log_prob = nullptr;
+    int* status = nullptr;
+};
+
+// The smoothed class posteriors of S device-resident streams (h_offs: their S + 1 offsets, on the host) under the class
+// loop of the models (already checked by segment_check_shape and posteriors_check_slots; all of one M), on the current
+// device and the stream st.
+int posteriors_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* h_offs, int S, double ln_switch,
+                      hipStream_t st, const PostOut& out)
+{
+    const int K = (int)ms.size(), M = ms[0]->M;
+    std::vector<int> Ns;
+    for (const Hmm* h : ms) Ns.push_back(h->N);
+    const SegPacking pk = pack_slots(Ns, posteriors_a_ld);
+    const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
+    const double sw = exp(ln_switch);  // (-inf: 0.0)
+    // pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class
+    std::vector<double> params((size_t)2 * sumN + (size_t)a_words + (size_t)sumN * M, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = *ms[(size_t)k];
+        const int N = h.N, ld = posteriors_a_ld(N), c0 = pk.comp0[(size_t)k];
+        for (int j = 0; j < N; ++j) {
+            params[(size_t)(c0 + j)] = h.pi[(size_t)j];
+            params[(size_t)(sumN + c0 + j)] = sw * h.pi[(size_t)j];
+            std::copy(h.A.begin() + (size_t)j * N, h.A.begin() + (size_t)(j + 1) * N,
+                      params.begin() + 2 * sumN + pk.a_at[(size_t)k] + (size_t)j * ld);
+        }
+        std::copy(h.B.begin(), h.B.end(), params.begin() + 2 * sumN + a_words + (size_t)c0 * M);
+    }
+    DeviceBuffer<double> d_params, d_mant, d_post, d_ah, d_c;
+    DeviceBuffer<e2hmm::SegLaneDev> d_lanes;
+    DeviceBuffer<int> d_info, d_comp0, d_status;
+    DeviceBuffer<unsigned short> d_comp_cls;
+    DeviceBuffer<i64> d_offs, d_exp;
+    const i64 frames = h_offs[S];
+    if (d_params.upload(params.data(), params.size(), st) || d_lanes.upload(pk.lanes.data(), pk.lanes.size(), st) ||
+        d_info.upload(pk.slot_info.data(), pk.slot_info.size(), st) || d_comp0.upload(pk.comp0.data(), pk.comp0.size(), st) ||
+        d_comp_cls.upload(pk.comp_cls.data(), pk.comp_cls.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) ||
+        d_mant.reserve((size_t)S) || d_exp.reserve((size_t)S) || d_status.reserve((size_t)S) || d_post.reserve((size_t)frames * K))
+        return 1;
+    const e2hmm::SegPlanDev pl{K, M, sumN, slots, a_words, d_lanes.get(), d_info.get(), d_params.get(), d_comp_cls.get(), d_comp0.get()};
+    // launches of whole streams whose ah (8 sumN bytes a frame) and c (8 bytes a frame and wave) stay within the budget
+    const i64 row = 8 * ((i64)sumN + slots);
+    i64 max_frames = 0;
+    const auto chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
+    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * slots)) {
+        const std::string why = e2vq_last_error();
+        return e2vq_set_error("hmm segment --posteriors: no room for the forward table of %lld frames x %d states (%lld bytes; "
+                              "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
+                              (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
+    }
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
+    for (const auto& c : chunks) {
+        const int s0 = c.first, n = c.second - c.first;
+        if (e2hmm::launch_loop_posteriors(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], sw, d_ah.get(), d_c.get(), d_post.get(),
+                                          d_mant.get() + s0, d_exp.get() + s0, d_status.get() + s0, st))
+            return e2vq_set_error("hmm segment --posteriors: %d wave-slots of %d states cannot be launched", slots, sumN);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    std::vector<double> mant((size_t)S);
+    std::vector<i64> ex((size_t)S);
+    std::vector<int> stat((size_t)S);
+    if (frames > 0 && out.post) HIPCHK(hipMemcpyAsync(out.post, d_post.get(), (size_t)frames * K * 8, hipMemcpyDeviceToHost, st));
+    if (S > 0) {
+        HIPCHK(hipMemcpyAsync(mant.data(), d_mant.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ex.data(), d_exp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stat.data(), d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_posteriors_kernel_ms)) return 1;
+    for (int s = 0; s < S; ++s) {
+        if (out.log_prob) out.log_prob[s] = stat[(size_t)s] == 0 ? log_prob(mant[(size_t)s], ex[(size_t)s]) : -INFINITY;
+        if (out.status) out.status[s] = stat[(size_t)s];
+    }
     return 0;
 }
 
@@ -882,20 +1018,22 @@ extern "C" int e2vq_hmm_segment(int device, int K, const int* Ns, int M, const d
     return segment_device(ms, lflats, seqs.sym, (const i64*)offs, S, ln_switch, seqs.st.s, out);
 }
 
-// CSV and stdout block of one segmented input from the per-frame outputs (host only)
-extern "C" int e2vq_hmm_segment_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
-                                       const uint16_t* cls, const uint8_t* entered, const double* gbest, double log_prob,
-                                       double ln_switch, const char* csv_filename)
+namespace {
+
+// CSV and stdout block of one segmented input from the per-frame outputs (host only).  post (T rows of K; may be null: every
+// byte as without it): two more CSV columns and a p= field per segment, and with frames_csv the per-frame table.
+int segment_report(const char* who, const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
+                   const uint16_t* cls, const uint8_t* entered, const double* gbest, double log_prob, double ln_switch,
+                   const double* post, const char* csv_filename, const char* frames_csv)
 {
     FlushStdout flush_on_return;
-    if (!name || K < 1 || !class_names || T < 0 || (T > 0 && (!cls || !entered || !gbest)))
-        return e2vq_set_error("e2vq_hmm_segment_report: bad arguments");
-    if (T > 0 && !entered[0]) return e2vq_set_error("e2vq_hmm_segment_report: frame 0 does not start a segment");
+    if (!name || K < 1 || !class_names || T < 0 || (T > 0 && (!cls || !entered || !gbest))) return e2vq_set_error("%s: bad arguments", who);
+    if (T > 0 && !entered[0]) return e2vq_set_error("%s: frame 0 does not start a segment", who);
     for (int64_t t = 0; t < T; ++t)
-        if (cls[t] >= K) return e2vq_set_error("e2vq_hmm_segment_report: frame %lld names a model outside [0, %d)", (long long)t, K);
+        if (cls[t] >= K) return e2vq_set_error("%s: frame %lld names a model outside [0, %d)", who, (long long)t, K);
     struct Seg {
         int64_t b, e;
-        double lp;
+        double lp, mean, min;
     };
     std::vector<Seg> segs;
     for (int64_t b = 0; b < T;) {
@@ -903,63 +1041,179 @@ extern "C" int e2vq_hmm_segment_report(const char* name, int64_t T, int K, const
         while (e < T && !entered[e]) ++e;
         // (gbest[e] of an entered frame e is the path's own cumulative score at e - 1)
         const double hi = e == T ? log_prob : gbest[e], lo = b == 0 ? 0.0 : gbest[b] + ln_switch;
-        segs.push_back(Seg{b, e, hi - lo});
+        Seg g{b, e, hi - lo, 0.0, 0.0};
+        if (post) {  // the class's posterior over the segment's frames: a serial sum in frame order, then one division
+            const double* col = post + cls[b];
+            double sum = 0.0, least = col[(size_t)b * K];
+            for (int64_t t = b; t < e; ++t) {
+                const double v = col[(size_t)t * K];
+                sum = sum + v;
+                if (v < least) least = v;
+            }
+            g.mean = sum / (double)(e - b);
+            g.min = least;
+        }
+        segs.push_back(g);
         b = e;
     }
     auto begin_s = [&](int64_t b) { return (double)(b * O_ms) / 1000.0; };
     // (the end of the analysis window of the segment's last frame)
     auto end_s = [&](int64_t e) { return (double)((e - 1) * O_ms + W_ms) / 1000.0; };
     if (csv_filename && *csv_filename) {
-        std::string doc = "segment,begin_frame,end_frame,begin_s,end_s,class,log_prob,log_prob_per_frame\n";
+        std::string doc = "segment,begin_frame,end_frame,begin_s,end_s,class,log_prob,log_prob_per_frame";
+        doc += post ? ",posterior,min_posterior\n" : "\n";
         for (size_t i = 0; i < segs.size(); ++i) {
             const Seg& g = segs[i];
             doc += std::to_string(i) + "," + std::to_string(g.b) + "," + std::to_string(g.e) + "," + fmt_17g(begin_s(g.b)) + "," +
-                   fmt_17g(end_s(g.e)) + "," + class_names[cls[g.b]] + "," + fmt_17g(g.lp) + "," + fmt_17g(g.lp / (double)(g.e - g.b)) + "\n";
+                   fmt_17g(end_s(g.e)) + "," + class_names[cls[g.b]] + "," + fmt_17g(g.lp) + "," + fmt_17g(g.lp / (double)(g.e - g.b));
+            if (post) doc += "," + fmt_17g(g.mean) + "," + fmt_17g(g.min);
+            doc += "\n";
         }
         if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
     }
+    const bool frames = post && frames_csv && *frames_csv;
+    if (frames) {
+        std::string doc = "frame,begin_s,class";
+        for (int k = 0; k < K; ++k) doc += std::string(",") + class_names[k];
+        doc += "\n";
+        for (int64_t t = 0; t < T; ++t) {
+            doc += std::to_string(t) + "," + fmt_17g(begin_s(t)) + "," + class_names[cls[t]];
+            for (int k = 0; k < K; ++k) doc += "," + fmt_17g(post[(size_t)t * K + k]);
+            doc += "\n";
+        }
+        if (write_file(frames_csv, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
+    }
     printf("%s: T=%lld  segments=%zu  (switch penalty %g)\n", name, (long long)T, segs.size(), ln_switch);
-    std::vector<int64_t> frames((size_t)K, 0);
-    for (int64_t t = 0; t < T; ++t) ++frames[cls[t]];
-    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)frames[(size_t)k]);
+    std::vector<int64_t> count((size_t)K, 0);
+    for (int64_t t = 0; t < T; ++t) ++count[cls[t]];
+    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)count[(size_t)k]);
     printf("  segments:\n");
-    for (const Seg& g : segs) printf("    %.3f - %.3f %s\n", begin_s(g.b), end_s(g.e), class_names[cls[g.b]]);
+    for (const Seg& g : segs) {
+        printf("    %.3f - %.3f %s", begin_s(g.b), end_s(g.e), class_names[cls[g.b]]);
+        if (post) printf(" p=%.3f", g.mean);
+        printf("\n");
+    }
     if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
+    if (frames) printf("  %s saved\n", frames_csv);
     return 0;
 }
 
-// `hmm segment`: every input (.wav: lpc -> quantize -> segment; .prd: quantize -> segment; .seq: segment) under the models
-extern "C" int e2vq_hmm_segment_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
-                                      const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
-                                      const char* csv_dir_or_file)
+// `hmm segment` with and without --posteriors: every input (.wav: lpc -> quantize -> segment; .prd: quantize -> segment;
+// .seq: segment) under the models.  The symbols of an input are staged once; the posteriors run on the same device buffer.
+int segment_files(const char* who, const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                  const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                  const char* csv_dir_or_file, bool posteriors, const char* frames_dir)
 {
     FlushStdout flush_on_return;
-    if (!model_filenames || num_models < 1) return e2vq_set_error("e2vq_hmm_segment_files: no models");
-    if (!input_filenames || num_inputs < 1) return e2vq_set_error("e2vq_hmm_segment_files: no inputs");
-    if (segment_check_switch("e2vq_hmm_segment_files", ln_switch)) return 1;
-    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("e2vq_hmm_segment_files: window %d ms / offset %d ms", W_ms, O_ms);
+    if (!model_filenames || num_models < 1) return e2vq_set_error("%s: no models", who);
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("%s: no inputs", who);
+    if (segment_check_switch(who, ln_switch)) return 1;
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms);
     FilesModels fm;
     if (fm.load(model_filenames, num_models)) return 1;
     std::vector<int> Ns;
     for (const Hmm& h : fm.models) Ns.push_back(h.N);
-    if (segment_check_shape("e2vq_hmm_segment_files", (int)num_models, Ns.data())) return 1;
+    if (segment_check_shape(who, (int)num_models, Ns.data())) return 1;
+    if (posteriors && posteriors_check_slots(who, (int)num_models, Ns.data())) return 1;
     std::vector<std::vector<double>> lflats((size_t)num_models);
     for (unsigned k = 0; k < num_models; ++k)
         if (log_model(fm.models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    const std::string fdir = posteriors && frames_dir ? frames_dir : "";
+    auto frames_csv = [&](const char* path) { return fdir + "/" + e2vq_io::basename_noext(path) + ".csv"; };
+    for (int f = 0; f < num_inputs && !fdir.empty(); ++f)
+        for (int g = 0; g < f; ++g)
+            if (input_filenames[f] && input_filenames[g] && frames_csv(input_filenames[g]) == frames_csv(input_filenames[f]))
+                return e2vq_set_error("%s and %s would both write %s", input_filenames[g], input_filenames[f], frames_csv(input_filenames[f]).c_str());
+    const int K = (int)num_models;
     auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
         const i64 offs[2] = {0, T};
         const size_t n = (size_t)std::max<int64_t>(T, 1);
         std::vector<uint16_t> cls(n);
         std::vector<uint8_t> entered(n);
-        std::vector<double> gbest(n);
+        std::vector<double> gbest(n), post;
         double lp = 0.0;
         int status = 0;
         SegOut out;
         out.cls = cls.data(), out.entered = entered.data(), out.gbest = gbest.data(), out.log_prob = &lp, out.status = &status;
         if (segment_device(fm.ms, lflats, d_sym, offs, 1, ln_switch, st, out)) return 1;
         if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), fm.M);
-        return e2vq_hmm_segment_report(in.path.c_str(), T, (int)num_models, fm.names.data(), W_ms, O_ms, cls.data(), entered.data(),
-                                       gbest.data(), lp, ln_switch, in.csv.empty() ? nullptr : in.csv.c_str());
+        if (posteriors) {
+            post.resize(n * (size_t)K);
+            PostOut po;
+            po.post = post.data();
+            if (posteriors_device(fm.ms, d_sym, offs, 1, ln_switch, st, po)) return 1;
+        }
+        const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
+        return segment_report(who, in.path.c_str(), T, K, fm.names.data(), W_ms, O_ms, cls.data(), entered.data(), gbest.data(), lp,
+                              ln_switch, posteriors ? post.data() : nullptr, in.csv.empty() ? nullptr : in.csv.c_str(),
+                              fcsv.empty() ? nullptr : fcsv.c_str());
     };
-    return run_on_files("e2vq_hmm_segment_files", fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+    return run_on_files(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+}
+
+}  // namespace
+
+extern "C" int e2vq_hmm_segment_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
+                                       const uint16_t* cls, const uint8_t* entered, const double* gbest, double log_prob,
+                                       double ln_switch, const char* csv_filename)
+{
+    return segment_report("e2vq_hmm_segment_report", name, T, K, class_names, W_ms, O_ms, cls, entered, gbest, log_prob, ln_switch,
+                          nullptr, csv_filename, nullptr);
+}
+
+extern "C" int e2vq_hmm_segment_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                      const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                                      const char* csv_dir_or_file)
+{
+    return segment_files("e2vq_hmm_segment_files", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms,
+                         ln_switch, csv_dir_or_file, false, nullptr);
+}
+
+// ---- hmm segment --posteriors -------------------------------------------------------------------------
+extern "C" int e2vq_hmm_segment_posteriors_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_segment_posteriors_last_kernel_ms: bad arguments");
+    *ms = g_posteriors_kernel_ms;
+    return 0;
+}
+
+// P(class at frame t | the whole stream) of each of S streams under the class loop of K models sharing M.  One device.
+extern "C" int e2vq_hmm_segment_posteriors(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                                           const double* const* Bs, const void* sym, const int64_t* offs, int S, double ln_switch,
+                                           double* post, double* log_prob, int* status, int sym_on_device)
+{
+    const char* who = "e2vq_hmm_segment_posteriors";
+    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
+    if (!Ns || !pis || !As || !Bs || S < 0 || (!sym && S > 0 && offs && offs[S] > 0)) return e2vq_set_error("%s: bad arguments", who);
+    if (segment_check_shape(who, K, Ns) || segment_check_switch(who, ln_switch) || posteriors_check_slots(who, K, Ns)) return 1;
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms)) return 1;
+    for (const Hmm& h : models)
+        if (posteriors_check_params(h)) return 1;
+    if (check_offsets(offs, S) || require_device(device)) return 1;
+    DevSeqs seqs;
+    if (seqs.symbols(sym, (size_t)offs[S], sym_on_device != 0)) return 1;
+    PostOut out;
+    out.post = post, out.log_prob = log_prob, out.status = status;
+    return posteriors_device(ms, seqs.sym, (const i64*)offs, S, ln_switch, seqs.st.s, out);
+}
+
+extern "C" int e2vq_hmm_segment_report_posteriors(const char* name, int64_t T, int K, const char* const* class_names, int W_ms,
+                                                  int O_ms, const uint16_t* cls, const uint8_t* entered, const double* gbest,
+                                                  double log_prob, double ln_switch, const double* post, const char* csv_filename,
+                                                  const char* frames_csv_filename)
+{
+    if (T > 0 && !post) return e2vq_set_error("e2vq_hmm_segment_report_posteriors: bad arguments");
+    const double none = 0.0;  // (T = 0: no row is read)
+    return segment_report("e2vq_hmm_segment_report_posteriors", name, T, K, class_names, W_ms, O_ms, cls, entered, gbest, log_prob,
+                          ln_switch, post ? post : &none, csv_filename, frames_csv_filename);
+}
+
+extern "C" int e2vq_hmm_segment_files_posteriors(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                                 const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                                 double ln_switch, const char* csv_dir_or_file, const char* frames_dir)
+{
+    return segment_files("e2vq_hmm_segment_files_posteriors", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P,
+                         W_ms, O_ms, ln_switch, csv_dir_or_file, true, frames_dir && *frames_dir ? frames_dir : nullptr);
 }

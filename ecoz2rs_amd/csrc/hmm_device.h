@@ -147,4 +147,14 @@ void launch_segment_backtrack(const SegPlanDev& pl, const long long* offs, int S
                               const int* gsel, const int* qlast, const int* status, unsigned short* cls, unsigned short* state,
                               unsigned char* entered, double* gbest, hipStream_t st);
 
+// Smoothed class posteriors under the same class loop (hmm_posterior.hip), on the packing above with at
+// most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | e = sw pi (sumN) | A of every class with the leading dimension
+// N_k | 1 (lanes[].a_at and a_words count these padded words) | B (sumN rows of M).  S streams (a workgroup each) from
+// offs[0] on; the scratch tables ahs ((frames of the launch) x sumN doubles) and cs ((frames of the launch) x slots) are
+// indexed relative to a0 = the first stream's offset, post (K doubles a frame) by the absolute frame; P(O | loop) =
+// mant 2^exp2 and status at [s].  Returns 1 when the shape cannot be launched.
+bool posteriors_a_in_lds(const SegPlanDev& pl);
+int launch_loop_posteriors(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0, double sw,
+                           double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status, hipStream_t st);
+
 }  // namespace e2hmm

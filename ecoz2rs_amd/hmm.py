@@ -71,6 +71,13 @@ _sig("e2vq_hmm_segment_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_
      C.c_double, C.c_char_p)
 _sig("e2vq_hmm_segment_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_double, C.c_double, C.c_char_p)
+_sig("e2vq_hmm_segment_posteriors", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p,
+     C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_segment_posteriors_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_segment_files_posteriors", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_double, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_segment_report_posteriors", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_char_p, C.c_char_p)
 
 def _strs(items):
     arr = (C.c_char_p * len(items))(*[str(p).encode() for p in items])
@@ -436,11 +443,56 @@ def segment_last_kernel_ms():
     return ms.value
 
 
-def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None):
+def segment_posteriors(models, sym, offs, ln_switch, device=0):
+    """P(class at frame t | the whole stream) under the class loop `segment` decodes: arguments as
+    `segment` takes them (sym a numpy array or a device tensor); the classes must pack into at most 16 wave-slots.
+    -> dict: post (sum T_s, K), row offs[s] + t; per stream log_prob = ln P(O | loop) and status (0 ok, 1 the loop cannot
+    emit the stream, 2 a symbol >= M; then the stream's rows are 0.0 and log_prob is -inf)"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    S = len(offs) - 1
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    T = int(offs[-1])
+    post = np.zeros((max(T, 1), max(K, 1)))
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_segment_posteriors(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, float(ln_switch),
+                                          post.ctypes.data, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    return dict(post=post[:T], log_prob=lp[:S], status=st[:S])
+
+
+def segment_posteriors_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_segment_posteriors_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
+                  frame_posteriors=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
-    stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments"""
+    stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
+    segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
+    table for every input"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
+    if frame_posteriors is not None and not posteriors:
+        raise ValueError("frame_posteriors needs posteriors=True")
+    if posteriors:
+        check(lib.e2vq_hmm_segment_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                    len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                    str(csv).encode() if csv else None,
+                                                    str(frame_posteriors).encode() if frame_posteriors is not None else None))
+        return
     check(lib.e2vq_hmm_segment_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                      len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
                                      str(csv).encode() if csv else None))

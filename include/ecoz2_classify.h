@@ -321,6 +321,45 @@ int e2vq_hmm_segment_files(const char *const *model_filenames, unsigned num_mode
                            const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
                            const char *csv_dir_or_file);
 
+/* ---- smoothed class posteriors under the same class loop -----------------------------------------------
+ * `hmm segment --posteriors`: post[t][k] = P(class k at frame t | the whole stream) under the class loop e2vq_hmm_segment
+ * decodes -- the forward-backward companion of its joint Viterbi: at every frame the whole mass may leave its class and
+ * enter any class through that class's pi at the price sw = exp(ln_switch) (the C library's exp on the host; -inf gives 0).
+ * Inputs and refusals are e2vq_hmm_segment's; in addition a packing of more than 16 wave-slots is refused (classes are
+ * packed in class order into slots of 64 lanes, a class that does not fit the open slot opens the next).  The arithmetic is
+ * scaled and linear, every operation one IEEE double operation in a fixed order, no fma (DESIGN.md 4.8.7 states it;
+ * tests/hmm_posterior_restatement.py restates it; the GPU matches it bit for bit):
+ *   x_0[k][j] = pi_k[j] B_k[j][o_0];  x_t[k][j] = (sum_i ah_{t-1}[k][i] A_k[i][j] + sw pi_k[j]) B_k[j][o_t];
+ *   c_t = sum over all states of x_t;  ah_t = x_t / c_t;  P(O | loop) = prod c_t;
+ *   bh_{T-1} = 1;  u = B_k[j][o_{t+1}] bh_{t+1}[k][j] / c_{t+1};  bh_t[k][i] = sum_j A_k[i][j] u[k][j] + sw sum_all pi u;
+ *   post[t][k] = sum_j ah_t[k][j] bh_t[k][j].
+ * Outputs, each may be NULL: post (offs[S] rows of K doubles, row offs[s] + t); per stream log_prob = ln P(O | loop) and
+ * status: 0 ok; 1 the loop cannot emit the stream (the first c_t that is not > 0); 2 a symbol >= M; the first event in frame
+ * order decides.  Status != 0: every post entry of the stream is 0.0 and log_prob is -inf.  An empty stream: status 0,
+ * log_prob 0.0, no rows.  One device.  sym_on_device as in e2vq_hmm_segment.
+ * ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds the per-launch forward table (default 256 MiB, whole streams; a table that cannot
+ * be allocated is an error). */
+int e2vq_hmm_segment_posteriors(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                                const double *const *Bs, const void *sym, const int64_t *offs, int S, double ln_switch,
+                                double *post, double *log_prob, int *status, int sym_on_device);
+/* HIP-event time of the kernels of this thread's last posteriors call (-1: none yet) */
+int e2vq_hmm_segment_posteriors_last_kernel_ms(float *ms);
+/* e2vq_hmm_segment_report with the posteriors of the stream (host only; post: T rows of K).  The CSV gains two trailing
+ * columns, posterior,min_posterior: the mean of post[t][class of the segment] over the segment's frames (a serial sum in
+ * frame order, then one division) and its minimum; each stdout segment line gains " p=%.3f" (the mean).  With
+ * frames_csv_filename (may be NULL) the per-frame table is written: header frame,begin_s,class,<class names...>, one row a
+ * frame with the decoded class and the K posteriors.  Floats as %.17g. */
+int e2vq_hmm_segment_report_posteriors(const char *name, int64_t T, int K, const char *const *class_names, int W_ms, int O_ms,
+                                       const uint16_t *cls, const uint8_t *entered, const double *gbest, double log_prob,
+                                       double ln_switch, const double *post, const char *csv_filename,
+                                       const char *frames_csv_filename);
+/* e2vq_hmm_segment_files with the posteriors: the symbols of an input are staged once, the segmentation and the posteriors
+ * run on the same device buffer, and the report is e2vq_hmm_segment_report_posteriors'.  frames_dir (may be NULL): the
+ * per-frame table of every input goes to <frames_dir>/<input's base name>.csv. */
+int e2vq_hmm_segment_files_posteriors(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                      const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                      double ln_switch, const char *csv_dir_or_file, const char *frames_dir);
+
 #ifdef __cplusplus
 }
 #endif
