@@ -66,9 +66,13 @@ static int usage()
             "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  --switch-penalty <x <= 0 | -inf> [-c <csv dir|file.csv>]\n"
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
+            "                  [--class-transitions <file.csv>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
             "                  --posteriors adds each segment's mean and least class posterior, and the per-frame table)\n"
+            "                  (--class-transitions adds the file's price of every class-to-class succession to the penalty)\n"
+            "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
+            "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -833,7 +837,7 @@ static int hmm_segment_cmd(int argc, char** argv)
     double ln_switch = 0.0;
     bool have_switch = false;
     bool posteriors = false;
-    std::string codebook, csv, frames_dir;
+    std::string codebook, csv, frames_dir, transitions;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -856,6 +860,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
         else if (a == "--posteriors") posteriors = true;
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
+        else if (a == "--class-transitions") transitions = val("--class-transitions");
         else if (a == "--switch-penalty") {
             const char* v = val("--switch-penalty");
             char* end = nullptr;
@@ -880,6 +885,10 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
     if (!frames_dir.empty() && !posteriors) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
+    if (!transitions.empty() && posteriors) {
+        fprintf(stderr, "hmm segment: --class-transitions and --posteriors exclude one another (the posteriors know one price only)\n");
+        return 2;
+    }
     std::vector<std::string> hmm_files, inputs;
     e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
     if (hmm_files.empty()) { printf("No models given\n"); return 0; }
@@ -893,10 +902,50 @@ static int hmm_segment_cmd(int argc, char** argv)
     auto pm = cptrs(hmm_files), pi = cptrs(inputs);
     const char* cb = codebook.empty() ? nullptr : codebook.c_str();
     const char* out = csv.empty() ? nullptr : csv.c_str();
-    const int failed = posteriors ? e2vq_hmm_segment_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+    const int failed = !transitions.empty() ? e2vq_hmm_segment_trans_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+                                                                           ln_switch, transitions.c_str(), out)
+                       : posteriors ? e2vq_hmm_segment_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                       ln_switch, out, frames_dir.empty() ? nullptr : frames_dir.c_str())
                                   : e2vq_hmm_segment_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O, ln_switch, out);
     if (failed) {
+        printf("%s\n", e2vq_last_error());
+        return 1;
+    }
+    return 0;
+}
+
+// `hmm transitions`: the class-to-class prices of `hmm segment --class-transitions` from labelled successions
+static int hmm_transitions_cmd(int argc, char** argv)
+{
+    double alpha = 1.0;
+    std::string out;
+    std::vector<std::string> models, inputs;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-m" || a == "--models") { while (i + 1 < argc && !is_flag(argv[i + 1])) models.push_back(argv[++i]); }
+        else if (a == "--alpha") {
+            const char* v = val("--alpha");
+            char* end = nullptr;
+            alpha = strtod(v, &end);
+            if (!*v || *end) { fprintf(stderr, "--alpha: invalid value '%s'\n", v); exit(2); }
+        }
+        else if (a == "-o" || a == "--output") out = val("-o");
+        else if (is_flag(argv[i])) return usage();
+        else inputs.push_back(a);
+    }
+    if (models.empty()) { fprintf(stderr, "hmm transitions: --models <files|dirs>... is required\n"); return usage(); }
+    if (out.empty()) { fprintf(stderr, "hmm transitions: -o <file.csv> is required\n"); return 2; }
+    if (!(alpha >= 0.0)) { fprintf(stderr, "hmm transitions: --alpha %g: at least 0\n", alpha); return 2; }
+    if (inputs.empty()) { fprintf(stderr, "hmm transitions: no inputs\n"); return 2; }
+    std::vector<std::string> hmm_files;
+    e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    auto pm = cptrs(hmm_files), pi = cptrs(inputs);
+    if (e2vq_hmm_transitions_files(pm.data(), (unsigned)pm.size(), pi.data(), (int)pi.size(), alpha, out.c_str())) {
         printf("%s\n", e2vq_last_error());
         return 1;
     }
@@ -908,6 +957,7 @@ static int hmm_cmd(int argc, char** argv)
     if (argc < 1) return usage();
     const std::string cmd = argv[0];
     if (cmd == "scan") return hmm_scan_cmd(argc - 1, argv + 1);
+    if (cmd == "transitions") return hmm_transitions_cmd(argc - 1, argv + 1);
     if (cmd == "segment") return hmm_segment_cmd(argc - 1, argv + 1);
     int N = 5, M = -1, type = 3, max_iterations = -1;
     double epsilon = 1e-05, val_auto = 0.3;

@@ -2,7 +2,8 @@
 // 4.8.1), the models over the windows of whole recordings (`hmm scan`, 4.8.5), the joint Viterbi through the class
 // loop of all models (`hmm segment`, 4.8.6) and the class posteriors under that loop (`--posteriors`, 4.8.7), with the
 // stage that turns a .wav / .prd / .seq input into device symbols; over the kernels of hmm_viterbi.hip, hmm_scan.hip,
-// hmm_segment.hip and hmm_posterior.hip.
+// hmm_segment.hip and hmm_posterior.hip; and the same loop under a matrix of class-to-class prices (`hmm segment
+// --class-transitions`, 4.8.8, hmm_segment_trans.hip) with the estimator of that matrix (`hmm transitions`).
 #include "hmm_host.h"
 
 #include <functional>
@@ -1021,10 +1022,11 @@ extern "C" int e2vq_hmm_segment(int device, int K, const int* Ns, int M, const d
 namespace {
 
 // CSV and stdout block of one segmented input from the per-frame outputs (host only).  post (T rows of K; may be null: every
-// byte as without it): two more CSV columns and a p= field per segment, and with frames_csv the per-frame table.
+// byte as without it): two more CSV columns and a p= field per segment, and with frames_csv the per-frame table.  lt (K x K;
+// may be null: ln_switch for every pair): the price of the succession that starts a segment (4.8.8; gbest is then exit_score).
 int segment_report(const char* who, const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
                    const uint16_t* cls, const uint8_t* entered, const double* gbest, double log_prob, double ln_switch,
-                   const double* post, const char* csv_filename, const char* frames_csv)
+                   const double* post, const char* csv_filename, const char* frames_csv, const double* lt = nullptr)
 {
     FlushStdout flush_on_return;
     if (!name || K < 1 || !class_names || T < 0 || (T > 0 && (!cls || !entered || !gbest))) return e2vq_set_error("%s: bad arguments", who);
@@ -1040,7 +1042,8 @@ int segment_report(const char* who, const char* name, int64_t T, int K, const ch
         int64_t e = b + 1;
         while (e < T && !entered[e]) ++e;
         // (gbest[e] of an entered frame e is the path's own cumulative score at e - 1)
-        const double hi = e == T ? log_prob : gbest[e], lo = b == 0 ? 0.0 : gbest[b] + ln_switch;
+        const double hi = e == T ? log_prob : gbest[e];
+        const double lo = b == 0 ? 0.0 : gbest[b] + (lt ? lt[(size_t)cls[b - 1] * K + cls[b]] : ln_switch);
         Seg g{b, e, hi - lo, 0.0, 0.0};
         if (post) {  // the class's posterior over the segment's frames: a serial sum in frame order, then one division
             const double* col = post + cls[b];
@@ -1216,4 +1219,412 @@ extern "C" int e2vq_hmm_segment_files_posteriors(const char* const* model_filena
 {
     return segment_files("e2vq_hmm_segment_files_posteriors", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P,
                          W_ms, O_ms, ln_switch, csv_dir_or_file, true, frames_dir && *frames_dir ? frames_dir : nullptr);
+}
+
+// ---- hmm segment --class-transitions ----------------------------------------------------------------------
+namespace {
+
+thread_local float g_segment_trans_kernel_ms = -1.f;  // e2vq_hmm_segment_trans_last_kernel_ms
+
+int trans_check_lt(const char* who, int K, const double* lt)
+{
+    for (int f = 0; f < K; ++f)
+        for (int k = 0; k < K; ++k) {
+            const double v = lt[(size_t)f * K + k];
+            if (std::isnan(v) || v > 0.0)
+                return e2vq_set_error("%s: lt[%d][%d] = %g: the logarithm of a price, at most 0 (-inf forbids the succession)", who, f, k, v);
+        }
+    return 0;
+}
+
+// only the resident layout exists: a packing of more than SEG_MAX_WAVES slots is refused (host only)
+int trans_check_slots(const char* who, int K, const int* Ns)
+{
+    const int slots = pack_slots(std::vector<int>(Ns, Ns + K), [](int N) { return N; }).slots;
+    if (slots > e2hmm::SEG_MAX_WAVES)
+        return e2vq_set_error("%s: the classes take %d wave-slots of 64 lanes (at most %d: the class-transition decoder has no looped body)",
+                              who, slots, e2hmm::SEG_MAX_WAVES);
+    return 0;
+}
+
+// segment_device under the K x K prices lt (row: the class left); out.gbest receives exit_score.  Already checked:
+// segment_check_shape, trans_check_slots, trans_check_lt.
+int segment_trans_device(const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats, const unsigned short* d_sym,
+                         const i64* h_offs, int S, const double* lt, hipStream_t st, const SegOut& out)
+{
+    const int K = (int)ms.size(), M = ms[0]->M;
+    std::vector<int> Ns;
+    for (const Hmm* h : ms) Ns.push_back(h->N);
+    const SegPacking pk = pack_slots(Ns, [](int N) { return N; });
+    const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
+    // logarithms: lpi of every class | lA of every class | lB of every class
+    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M);
+    for (int k = 0; k < K; ++k) {
+        const std::vector<double>& lflat = lflats[(size_t)k];
+        const size_t N = (size_t)ms[(size_t)k]->N;
+        std::copy(lflat.begin(), lflat.begin() + N, params.begin() + pk.comp0[(size_t)k]);
+        std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + pk.a_at[(size_t)k]);
+        std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + a_words + (size_t)pk.comp0[(size_t)k] * M);
+    }
+    std::vector<double> ltT((size_t)K * K);  // a lane of class k walks its sources along consecutive words
+    for (int f = 0; f < K; ++f)
+        for (int k = 0; k < K; ++k) ltT[(size_t)k * K + f] = lt[(size_t)f * K + k];
+
+    DeviceBuffer<double> d_params, d_ltT, d_logp, d_exit, d_Es;
+    DeviceBuffer<e2hmm::SegLaneDev> d_lanes;
+    DeviceBuffer<int> d_info, d_comp0, d_status, d_qlast;
+    DeviceBuffer<unsigned short> d_comp_cls, d_psi, d_src, d_xs, d_cls, d_state;
+    DeviceBuffer<unsigned char> d_entered;
+    DeviceBuffer<i64> d_offs;
+    const i64 frames = h_offs[S];
+    if (d_params.upload(params.data(), params.size(), st) || d_ltT.upload(ltT.data(), ltT.size(), st) ||
+        d_lanes.upload(pk.lanes.data(), pk.lanes.size(), st) || d_info.upload(pk.slot_info.data(), pk.slot_info.size(), st) ||
+        d_comp0.upload(pk.comp0.data(), pk.comp0.size(), st) || d_comp_cls.upload(pk.comp_cls.data(), pk.comp_cls.size(), st) ||
+        d_offs.upload(h_offs, (size_t)S + 1, st) || d_logp.reserve((size_t)S) || d_status.reserve((size_t)S) ||
+        d_qlast.reserve((size_t)S) || d_exit.reserve((size_t)frames) || d_cls.reserve((size_t)frames) ||
+        d_state.reserve((size_t)frames) || d_entered.reserve((size_t)frames))
+        return 1;
+    const e2hmm::SegPlanDev pl{K, M, sumN, slots, a_words, d_lanes.get(), d_info.get(), d_params.get(), d_comp_cls.get(), d_comp0.get()};
+    // launches of whole streams whose tables stay within the budget: psi (2 sumN bytes a frame), src and x (2 K each), E (8 K)
+    const i64 row = 2 * (i64)sumN + 12 * (i64)K;
+    i64 max_frames = 0;
+    const auto chunks = plan_chunks("ECOZ2_HMM_SEGMENT_CHUNK_BYTES", row, h_offs, S, &max_frames);
+    if (d_psi.reserve((size_t)max_frames * sumN) || d_src.reserve((size_t)max_frames * K) || d_xs.reserve((size_t)max_frames * K) ||
+        d_Es.reserve((size_t)max_frames * K)) {
+        const std::string why = e2vq_last_error();
+        return e2vq_set_error("hmm segment --class-transitions: no room for the back-pointer tables of %lld frames x (%d states, %d "
+                              "classes) (%lld bytes; ECOZ2_HMM_SEGMENT_CHUNK_BYTES bounds them by whole streams): %s",
+                              (long long)max_frames, sumN, K, (long long)(max_frames * row), why.c_str());
+    }
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backtrack has read them)
+    for (const auto& c : chunks) {
+        const int s0 = c.first, n = c.second - c.first;
+        if (e2hmm::launch_segment_trans(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_ltT.get(), d_psi.get(), d_src.get(), d_xs.get(),
+                                        d_Es.get(), d_logp.get() + s0, d_qlast.get() + s0, d_status.get() + s0, st))
+            return e2vq_set_error("hmm segment --class-transitions: %d wave-slots of %d states cannot be launched", slots, sumN);
+        HIPCHK(hipGetLastError());
+        e2hmm::launch_segment_trans_backtrack(pl, d_offs.get() + s0, n, h_offs[s0], d_psi.get(), d_src.get(), d_xs.get(), d_Es.get(),
+                                              d_qlast.get() + s0, d_status.get() + s0, d_cls.get(), d_state.get(), d_entered.get(),
+                                              d_exit.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    if (frames > 0) {
+        if (out.cls) HIPCHK(hipMemcpyAsync(out.cls, d_cls.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        if (out.state) HIPCHK(hipMemcpyAsync(out.state, d_state.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        if (out.entered) HIPCHK(hipMemcpyAsync(out.entered, d_entered.get(), (size_t)frames, hipMemcpyDeviceToHost, st));
+        if (out.gbest) HIPCHK(hipMemcpyAsync(out.gbest, d_exit.get(), (size_t)frames * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (S > 0) {
+        if (out.log_prob) HIPCHK(hipMemcpyAsync(out.log_prob, d_logp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        if (out.status) HIPCHK(hipMemcpyAsync(out.status, d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_segment_trans_kernel_ms)) return 1;
+    return 0;
+}
+
+// ---- the transitions file: "class,<name_1>,...,<name_K>", then one line "<from>,v_1,...,v_K" per class ------------------
+std::vector<std::string> split_on(const std::string& s, char sep)
+{
+    std::vector<std::string> out(1);
+    for (char ch : s) {
+        if (ch == sep) out.emplace_back();
+        else out.back() += ch;
+    }
+    return out;
+}
+
+// the lines of a text file without their line ends; a last line without one counts, trailing empty lines do not
+int read_lines(const char* path, std::vector<std::string>& lines)
+{
+    std::vector<unsigned char> bytes;
+    if (read_file(path, bytes)) return 1;
+    lines = split_on(std::string(bytes.begin(), bytes.end()), '\n');
+    for (std::string& l : lines)
+        if (!l.empty() && l.back() == '\r') l.pop_back();
+    while (!lines.empty() && lines.back().empty()) lines.pop_back();
+    return 0;
+}
+
+// the file's matrix in the order of `names` (the models' classes): lt[f * K + k], each value <= 0 or -inf
+int transitions_read(const char* path, int K, const char* const* names, std::vector<double>& lt)
+{
+    std::vector<std::string> lines;
+    if (read_lines(path, lines)) return 1;
+    if (lines.empty()) return e2vq_set_error("%s: empty: no header 'class,<name>,...'", path);
+    auto index_of = [&](const std::string& name) {
+        for (int k = 0; k < K; ++k)
+            if (name == names[k]) return k;
+        return -1;
+    };
+    const std::vector<std::string> head = split_on(lines[0], ',');
+    if (head[0] != "class") return e2vq_set_error("%s:1: the header starts with '%s', not 'class'", path, head[0].c_str());
+    if ((int)head.size() != K + 1) return e2vq_set_error("%s:1: %zu class names for %d models", path, head.size() - 1, K);
+    std::vector<int> col((size_t)K), seen_col((size_t)K, 0), seen_row((size_t)K, 0);
+    for (int c = 0; c < K; ++c) {
+        const int k = index_of(head[(size_t)c + 1]);
+        if (k < 0) return e2vq_set_error("%s:1: '%s' is no model's class", path, head[(size_t)c + 1].c_str());
+        if (seen_col[(size_t)k]++) return e2vq_set_error("%s:1: class '%s' is named twice", path, names[k]);
+        col[(size_t)c] = k;
+    }
+    if ((int)lines.size() != K + 1) return e2vq_set_error("%s:%zu: %zu rows for %d models", path, lines.size(), lines.size() - 1, K);
+    lt.assign((size_t)K * K, 0.0);
+    for (int r = 0; r < K; ++r) {
+        const int line = r + 2;
+        const std::vector<std::string> cells = split_on(lines[(size_t)r + 1], ',');
+        if ((int)cells.size() != K + 1) return e2vq_set_error("%s:%d: %zu fields, not %d", path, line, cells.size(), K + 1);
+        const int f = index_of(cells[0]);
+        if (f < 0) return e2vq_set_error("%s:%d: '%s' is no model's class", path, line, cells[0].c_str());
+        if (seen_row[(size_t)f]++) return e2vq_set_error("%s:%d: class '%s' has a second row", path, line, names[f]);
+        for (int c = 0; c < K; ++c) {
+            const std::string& cell = cells[(size_t)c + 1];
+            char* end = nullptr;
+            const double v = strtod(cell.c_str(), &end);
+            if (cell.empty() || *end) return e2vq_set_error("%s:%d: '%s' is not a number", path, line, cell.c_str());
+            if (std::isnan(v) || v > 0.0)
+                return e2vq_set_error("%s:%d: %s -> %s = %g: the logarithm of a price, at most 0 or -inf", path, line, names[f],
+                                      names[col[(size_t)c]], v);
+            lt[(size_t)f * K + col[(size_t)c]] = v;
+        }
+    }
+    return 0;
+}
+
+int transitions_write(const char* path, int K, const char* const* names, const double* lt)
+{
+    std::string doc = "class";
+    for (int k = 0; k < K; ++k) doc += std::string(",") + names[k];
+    doc += "\n";
+    for (int f = 0; f < K; ++f) {
+        doc += names[f];
+        for (int k = 0; k < K; ++k) doc += "," + fmt_17g(lt[(size_t)f * K + k]);
+        doc += "\n";
+    }
+    return write_file(path, std::vector<unsigned char>(doc.begin(), doc.end()));
+}
+
+int check_names(const char* who, int K, const char* const* names)
+{
+    if (K < 1 || !names) return e2vq_set_error("%s: bad arguments", who);
+    for (int k = 0; k < K; ++k) {
+        if (!names[k] || !*names[k] || strpbrk(names[k], ",\t\r\n")) return e2vq_set_error("%s: class name %d cannot head a column", who, k);
+        for (int g = 0; g < k; ++g)
+            if (strcmp(names[g], names[k]) == 0) return e2vq_set_error("%s: two models of the class '%s'", who, names[k]);
+    }
+    return 0;
+}
+
+// ln((c[f][k] + alpha) / (sum_k' c[f][k'] + alpha K)) from the bigram counts c (K x K)
+int transitions_from_counts(const char* who, int K, const std::vector<int64_t>& c, double alpha, const char* const* names, double* lt)
+{
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return e2vq_set_error("%s: alpha = %g: a finite number, at least 0", who, alpha);
+    for (int f = 0; f < K; ++f) {
+        int64_t n = 0;
+        for (int k = 0; k < K; ++k) n += c[(size_t)f * K + k];
+        const double den = (double)n + alpha * (double)K;
+        if (!(den > 0.0)) {
+            if (names) return e2vq_set_error("%s: nothing follows class '%s' in the inputs: its row is undefined at alpha = 0", who, names[f]);
+            return e2vq_set_error("%s: nothing follows class %d in the inputs: its row is undefined at alpha = 0", who, f);
+        }
+        for (int k = 0; k < K; ++k) {
+            const double num = (double)c[(size_t)f * K + k] + alpha;
+            lt[(size_t)f * K + k] = num > 0.0 ? log(num / den) : -INFINITY;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int e2vq_hmm_segment_trans_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_segment_trans_last_kernel_ms: bad arguments");
+    *ms = g_segment_trans_kernel_ms;
+    return 0;
+}
+
+extern "C" int e2vq_hmm_segment_trans(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                                      const double* const* Bs, const void* sym, const int64_t* offs, int S, const double* lt,
+                                      uint16_t* cls, uint16_t* state, uint8_t* entered, double* exit_score, double* log_prob,
+                                      int* status, int sym_on_device)
+{
+    const char* who = "e2vq_hmm_segment_trans";
+    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
+    if (!Ns || !pis || !As || !Bs || !lt || S < 0 || (!sym && S > 0 && offs && offs[S] > 0)) return e2vq_set_error("%s: bad arguments", who);
+    if (segment_check_shape(who, K, Ns) || trans_check_lt(who, K, lt) || trans_check_slots(who, K, Ns)) return 1;
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    std::vector<std::vector<double>> lflats((size_t)K);
+    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms)) return 1;
+    for (int k = 0; k < K; ++k)
+        if (log_model(models[(size_t)k], lflats[(size_t)k])) return 1;
+    if (check_offsets(offs, S) || require_device(device)) return 1;
+    DevSeqs seqs;
+    if (seqs.symbols(sym, (size_t)offs[S], sym_on_device != 0)) return 1;
+    SegOut out;
+    out.cls = cls, out.state = state, out.entered = entered, out.gbest = exit_score, out.log_prob = log_prob, out.status = status;
+    return segment_trans_device(ms, lflats, seqs.sym, (const i64*)offs, S, lt, seqs.st.s, out);
+}
+
+extern "C" int e2vq_hmm_segment_trans_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,
+                                             const uint16_t* cls, const uint8_t* entered, const double* exit_score, double log_prob,
+                                             double ln_switch, const double* lt, const char* csv_filename)
+{
+    if (!lt) return e2vq_set_error("e2vq_hmm_segment_trans_report: bad arguments");
+    return segment_report("e2vq_hmm_segment_trans_report", name, T, K, class_names, W_ms, O_ms, cls, entered, exit_score, log_prob,
+                          ln_switch, nullptr, csv_filename, nullptr, lt);
+}
+
+extern "C" int e2vq_hmm_transitions_read(const char* filename, int K, const char* const* class_names, double* lt)
+{
+    if (!filename || !lt) return e2vq_set_error("e2vq_hmm_transitions_read: bad arguments");
+    if (check_names("e2vq_hmm_transitions_read", K, class_names)) return 1;
+    std::vector<double> m;
+    if (transitions_read(filename, K, class_names, m)) return 1;
+    std::copy(m.begin(), m.end(), lt);
+    return 0;
+}
+
+extern "C" int e2vq_hmm_transitions_write(const char* filename, int K, const char* const* class_names, const double* lt)
+{
+    if (!filename || !lt) return e2vq_set_error("e2vq_hmm_transitions_write: bad arguments");
+    if (check_names("e2vq_hmm_transitions_write", K, class_names)) return 1;
+    return transitions_write(filename, K, class_names, lt);
+}
+
+extern "C" int e2vq_hmm_segment_trans_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                            const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                            double ln_switch, const char* transitions_csv, const char* csv_dir_or_file)
+{
+    const char* who = "e2vq_hmm_segment_trans_files";
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("%s: no models", who);
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("%s: no inputs", who);
+    if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
+    if (segment_check_switch(who, ln_switch)) return 1;
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms);
+    FilesModels fm;
+    if (fm.load(model_filenames, num_models)) return 1;
+    const int K = (int)num_models;
+    std::vector<int> Ns;
+    for (const Hmm& h : fm.models) Ns.push_back(h.N);
+    if (segment_check_shape(who, K, Ns.data()) || trans_check_slots(who, K, Ns.data())) return 1;
+    if (check_names(who, K, fm.names.data())) return 1;
+    std::vector<double> lt;
+    if (transitions_read(transitions_csv, K, fm.names.data(), lt)) return 1;
+    for (double& v : lt) v = v + ln_switch;  // the effective price
+    std::vector<std::vector<double>> lflats((size_t)num_models);
+    for (unsigned k = 0; k < num_models; ++k)
+        if (log_model(fm.models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
+        const i64 offs[2] = {0, T};
+        const size_t n = (size_t)std::max<int64_t>(T, 1);
+        std::vector<uint16_t> cls(n);
+        std::vector<uint8_t> entered(n);
+        std::vector<double> exit_score(n);
+        double lp = 0.0;
+        int status = 0;
+        SegOut out;
+        out.cls = cls.data(), out.entered = entered.data(), out.gbest = exit_score.data(), out.log_prob = &lp, out.status = &status;
+        if (segment_trans_device(fm.ms, lflats, d_sym, offs, 1, lt.data(), st, out)) return 1;
+        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), fm.M);
+        return segment_report(who, in.path.c_str(), T, K, fm.names.data(), W_ms, O_ms, cls.data(), entered.data(), exit_score.data(), lp,
+                              ln_switch, nullptr, in.csv.empty() ? nullptr : in.csv.c_str(), nullptr, lt.data());
+    };
+    return run_on_files(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+}
+
+// ---- hmm transitions: the matrix from labelled successions (host only) ---------------------------------------------------
+extern "C" int e2vq_hmm_class_transitions(const int32_t* labels, const int64_t* offs, int S, int K, double alpha, double* lt)
+{
+    const char* who = "e2vq_hmm_class_transitions";
+    if (K < 1 || S < 0 || !offs || !lt || (S > 0 && offs[S] > 0 && !labels)) return e2vq_set_error("%s: bad arguments", who);
+    if (check_offsets(offs, S)) return 1;
+    std::vector<int64_t> c((size_t)K * K, 0);
+    for (int s = 0; s < S; ++s)
+        for (int64_t t = offs[s]; t < offs[s + 1]; ++t) {
+            if (labels[t] < 0 || labels[t] >= K) return e2vq_set_error("%s: label %d at %lld is outside [0, %d)", who, labels[t], (long long)t, K);
+            if (t > offs[s]) ++c[(size_t)labels[t - 1] * K + labels[t]];
+        }
+    return transitions_from_counts(who, K, c, alpha, nullptr, lt);
+}
+
+extern "C" int e2vq_hmm_transitions_files(const char* const* model_filenames, unsigned num_models, const char* const* input_filenames,
+                                          int num_inputs, double alpha, const char* out_csv)
+{
+    const char* who = "e2vq_hmm_transitions_files";
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("%s: no models", who);
+    if (!input_filenames || num_inputs < 1) return e2vq_set_error("%s: no inputs", who);
+    if (!out_csv || !*out_csv) return e2vq_set_error("%s: no output file", who);
+    std::vector<std::string> names;
+    for (unsigned k = 0; k < num_models; ++k) {
+        char cls[96];
+        int N, M;
+        if (e2vq_hmm_info(model_filenames[k], cls, &N, &M)) return 1;
+        names.push_back(cls);
+    }
+    const int K = (int)num_models;
+    std::vector<const char*> pn;
+    for (const std::string& s : names) pn.push_back(s.c_str());
+    if (check_names(who, K, pn.data())) return 1;
+    std::vector<int64_t> c((size_t)K * K, 0);
+    int64_t pairs = 0, skipped = 0;
+    for (int i = 0; i < num_inputs; ++i) {
+        const char* path = input_filenames[i];
+        if (!path) return e2vq_set_error("%s: NULL file name", who);
+        std::vector<std::string> lines;
+        if (read_lines(path, lines)) return 1;
+        // the first line that is no '#' comment is the header: a segment CSV (column `class`) or a tab-separated selection table
+        size_t h = 0;
+        while (h < lines.size() && (lines[h].empty() || lines[h][0] == '#')) ++h;
+        if (h == lines.size()) return e2vq_set_error("%s: no header", path);
+        const bool table = lines[h].find('\t') != std::string::npos;
+        const std::vector<std::string> head = split_on(lines[h], table ? '\t' : ',');
+        auto column = [&](const char* name) { return (int)(std::find(head.begin(), head.end(), name) - head.begin()); };
+        const int ncol = (int)head.size();
+        const int c_label = column(table ? "Type" : "class"), c_time = table ? column("Begin Time (s)") : -1;
+        if (c_label == ncol || c_time == ncol)
+            return e2vq_set_error("%s:%zu: neither a segment CSV (column 'class') nor a selection table (tab-separated, 'Begin Time (s)' and 'Type')",
+                                  path, h + 1);
+        std::vector<std::pair<double, std::string>> rows;  // (begin time or row number, label)
+        for (size_t l = h + 1; l < lines.size(); ++l) {
+            if (lines[l].empty() || lines[l][0] == '#') continue;
+            const std::vector<std::string> cells = split_on(lines[l], table ? '\t' : ',');
+            if ((int)cells.size() != ncol) return e2vq_set_error("%s:%zu: %zu fields, not %d", path, l + 1, cells.size(), ncol);
+            double at = (double)rows.size();
+            if (table) {
+                char* end = nullptr;
+                at = strtod(cells[(size_t)c_time].c_str(), &end);
+                if (cells[(size_t)c_time].empty() || *end || std::isnan(at))
+                    return e2vq_set_error("%s:%zu: begin time '%s' is not a number", path, l + 1, cells[(size_t)c_time].c_str());
+            }
+            rows.emplace_back(at, cells[(size_t)c_label]);
+        }
+        std::stable_sort(rows.begin(), rows.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        int prev = -1;  // (a label that is no model's class is left out: its neighbours follow one another)
+        for (const auto& r : rows) {
+            int k = 0;
+            while (k < K && r.second != names[(size_t)k]) ++k;
+            if (k == K) {
+                ++skipped;
+                continue;
+            }
+            if (prev >= 0) {
+                ++c[(size_t)prev * K + k];
+                ++pairs;
+            }
+            prev = k;
+        }
+    }
+    std::vector<double> lt((size_t)K * K);
+    if (transitions_from_counts(who, K, c, alpha, pn.data(), lt.data())) return 1;
+    if (transitions_write(out_csv, K, pn.data(), lt.data())) return 1;
+    printf("%d inputs: %lld successions counted, %lld labels skipped (no model's class)\n", num_inputs, (long long)pairs, (long long)skipped);
+    printf("%s saved (alpha %g, %d classes)\n", out_csv, alpha, K);
+    return 0;
 }

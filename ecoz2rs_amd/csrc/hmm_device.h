@@ -147,6 +147,22 @@ void launch_segment_backtrack(const SegPlanDev& pl, const long long* offs, int S
                               const int* gsel, const int* qlast, const int* status, unsigned short* cls, unsigned short* state,
                               unsigned char* entered, double* gbest, hipStream_t st);
 
+// The same joint Viterbi under a K x K matrix of class-to-class prices (hmm_segment_trans.hip), on the
+// packing above with at most SEG_MAX_WAVES slots; pl.params as launch_segment takes them.  ltT: the K x K prices
+// transposed, ltT[k * K + f] = lt[f][k].  The tables psi (sumN u16 a frame), src and xs (K u16 a frame) and Es (K doubles a
+// frame) are indexed relative to psi0 = the first stream's offset; logp / qlast / status at [s].  Returns 1 when the
+// shape cannot be launched.  segment_trans_layout: whether lA, and then ltT, live in LDS (the instantiation).
+void segment_trans_layout(const SegPlanDev& pl, bool* a_lds, bool* lt_lds);
+int launch_segment_trans(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long psi0,
+                         const double* ltT, unsigned short* psi, unsigned short* src, unsigned short* xs, double* Es, double* logp,
+                         int* qlast, int* status, hipStream_t st);
+// cls / state / entered / exit_score of each of the S streams (absolute frames) from what launch_segment_trans left; a
+// stream of status 2 gets 0xFFFF, 0xFFFF, 0 and exit_score = -inf from its frame 1 on
+void launch_segment_trans_backtrack(const SegPlanDev& pl, const long long* offs, int S, long long psi0, const unsigned short* psi,
+                                    const unsigned short* src, const unsigned short* xs, const double* Es, const int* qlast,
+                                    const int* status, unsigned short* cls, unsigned short* state, unsigned char* entered,
+                                    double* exit_score, hipStream_t st);
+
 // Smoothed class posteriors under the same class loop (hmm_posterior.hip), on the packing above with at
 // most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | e = sw pi (sumN) | A of every class with the leading dimension
 // N_k | 1 (lanes[].a_at and a_words count these padded words) | B (sumN rows of M).  S streams (a workgroup each) from

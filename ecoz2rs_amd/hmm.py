@@ -78,6 +78,18 @@ _sig("e2vq_hmm_segment_files_posteriors", C.c_int, c_char_pp, C.c_uint, C.c_char
      C.c_int, C.c_double, C.c_char_p, C.c_char_p)
 _sig("e2vq_hmm_segment_report_posteriors", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_segment_trans", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p,
+     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_segment_trans_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_segment_trans_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_double, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_segment_trans_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_char_p)
+_sig("e2vq_hmm_transitions_read", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_void_p)
+_sig("e2vq_hmm_transitions_write", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_void_p)
+_sig("e2vq_hmm_class_transitions", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p)
+_sig("e2vq_hmm_transitions_files", C.c_int, c_char_pp, C.c_uint, c_char_pp, C.c_int, C.c_double, C.c_char_p)
+
 
 def _strs(items):
     arr = (C.c_char_p * len(items))(*[str(p).encode() for p in items])
@@ -477,16 +489,116 @@ def segment_posteriors_last_kernel_ms():
     return ms.value
 
 
+def segments_of_trans(cls, entered, exit_score, log_prob, ln_trans):
+    """`segments_of` under the K x K prices ln_trans: the segment that starts at b > 0 paid
+    ln_trans[cls[b - 1]][cls[b]]"""
+    lt = np.asarray(ln_trans, dtype=np.float64)
+    T = len(cls)
+    starts = [int(t) for t in np.flatnonzero(np.asarray(entered))]
+    out = []
+    for b, e in zip(starts, starts[1:] + [T]):
+        hi = np.float64(log_prob if e == T else exit_score[e])
+        with np.errstate(invalid="ignore"):
+            lo = np.float64(0.0) if b == 0 else np.float64(exit_score[b]) + lt[int(cls[b - 1]), int(cls[b])]
+            out.append(dict(begin=b, end=e, cls=int(cls[b]), log_prob=float(hi - lo)))
+    return out
+
+
+def segment_trans(models, sym, offs, ln_trans, device=0):
+    """`segment` under a K x K matrix of class-to-class prices: ln_trans[f][k] <= 0 (or -inf) is the log of
+    the price of leaving class f and entering class k; the classes must pack into at most 16 wave-slots.  -> the dict of
+    `segment` with exit_score in the place of gbest: exit_score[t] = the best score in the class of frame t - 1 at t - 1"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    lt = np.ascontiguousarray(ln_trans, dtype=np.float64)
+    if lt.shape != (K, K):
+        raise ValueError(f"ln_trans has the shape {lt.shape}, not ({K}, {K})")
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    S = len(offs) - 1
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    n = max(int(offs[-1]), 1)
+    cls, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
+    entered, ex = np.zeros(n, dtype=np.uint8), np.zeros(n)
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_segment_trans(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, lt.ctypes.data,
+                                     cls.ctypes.data, state.ctypes.data, entered.ctypes.data, ex.ctypes.data, lp.ctypes.data,
+                                     st.ctypes.data, int(on_device)))
+    T = int(offs[-1])
+    out = dict(cls=cls[:T], state=state[:T], entered=entered[:T], exit_score=ex[:T], log_prob=lp[:S], status=st[:S])
+    out["segments"] = [segments_of_trans(out["cls"][a:b], out["entered"][a:b], out["exit_score"][a:b], lp[s], lt)
+                       for s, (a, b) in enumerate(zip(offs[:-1], offs[1:]))]
+    return out
+
+
+def segment_trans_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_segment_trans_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def class_transitions(label_sequences, K, alpha=1.0):
+    """the K x K prices of `segment_trans` from sequences of class labels in [0, K) (host only): bigrams
+    are counted within each sequence; ln((c[f][k] + alpha) / (sum_k' c[f][k'] + alpha K)), -inf for an unseen pair at alpha = 0"""
+    arrs = [np.ascontiguousarray(s, dtype=np.int32) for s in label_sequences]
+    offs = np.zeros(len(arrs) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([len(a) for a in arrs])
+    labels = np.ascontiguousarray(np.concatenate(arrs)) if arrs and offs[-1] else np.zeros(1, dtype=np.int32)
+    lt = np.zeros((max(int(K), 1), max(int(K), 1)))
+    check(lib.e2vq_hmm_class_transitions(labels.ctypes.data, offs.ctypes.data, len(arrs), int(K), float(alpha), lt.ctypes.data))
+    return lt
+
+
+def read_class_transitions(path, class_names):
+    """the matrix of a transitions file in the order of class_names (the models' classes)"""
+    names, _k = _strs(class_names)
+    lt = np.zeros((max(len(class_names), 1),) * 2)
+    check(lib.e2vq_hmm_transitions_read(str(path).encode(), len(class_names), names, lt.ctypes.data))
+    return lt
+
+
+def write_class_transitions(path, class_names, ln_trans):
+    """the transitions file `hmm segment --class-transitions` reads: header class,<names>, a row per class"""
+    names, _k = _strs(class_names)
+    lt = np.ascontiguousarray(ln_trans, dtype=np.float64)
+    if lt.shape != (len(class_names),) * 2:
+        raise ValueError(f"ln_trans has the shape {lt.shape} for {len(class_names)} classes")
+    check(lib.e2vq_hmm_transitions_write(str(path).encode(), len(class_names), names, lt.ctypes.data))
+
+
+def class_transitions_files(model_filenames, input_filenames, out_csv, alpha=1.0):
+    """`hmm transitions`: the transitions file of the models' classes from segment CSVs or selection tables"""
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    check(lib.e2vq_hmm_transitions_files(m, len(model_filenames), f, len(input_filenames), float(alpha), str(out_csv).encode()))
+
+
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
-                  frame_posteriors=None):
+                  frame_posteriors=None, class_transitions=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
-    table for every input"""
+    table for every input.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     if frame_posteriors is not None and not posteriors:
         raise ValueError("frame_posteriors needs posteriors=True")
+    if class_transitions is not None:
+        if posteriors:
+            raise ValueError("class_transitions and posteriors exclude one another")
+        check(lib.e2vq_hmm_segment_trans_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                               len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                               str(class_transitions).encode(), str(csv).encode() if csv else None))
+        return
     if posteriors:
         check(lib.e2vq_hmm_segment_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                                     len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),

@@ -360,6 +360,52 @@ int e2vq_hmm_segment_files_posteriors(const char *const *model_filenames, unsign
                                       const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
                                       double ln_switch, const char *csv_dir_or_file, const char *frames_dir);
 
+/* ---- the class loop under class-to-class prices ---------------------------------------------------------
+ * `hmm segment --class-transitions`: e2vq_hmm_segment with the one price ln_switch replaced by lt, a row-major K x K
+ * array: lt[f * K + k] is the logarithm of the price of leaving class f and entering class k through pi_k (f = k: a
+ * boundary between two segments of one class).  Every entry is <= 0 or -inf.  Refused before any HIP call: what
+ * e2vq_hmm_segment refuses, an entry that is NaN or > 0, and a packing of more than 16 wave-slots (classes are packed in
+ * class order into slots of 64 lanes, N_k consecutive lanes each, never across a slot; only the resident layout exists).
+ * Per step: E_t[f] = max_i d_{t-1}[f][i] with x_t[f] the lowest state reaching it; base_t[k] = max_f (E_t[f] + lt[f][k])
+ * with src_t[k] the lowest class reaching it; a state (k, j) is entered when base_t[k] + lpi_k[j] is strictly greater
+ * than the best in-class predecessor.  Backwards an ENTER at frame t + 1 in class k gives q_t = (src_{t+1}[k], x_{t+1}[.]).
+ * Outputs as e2vq_hmm_segment's with exit_score in the place of gbest: exit_score[t] = E_t[cls[t-1]] (0.0 at frame 0);
+ * on an entered frame it is the path's own cumulative score at t - 1.  The segment [b, e) scores
+ *   (e == T ? ln P* : exit_score[e]) - (b == 0 ? 0.0 : exit_score[b] + lt[cls[b-1]][cls[b]]).
+ * With every entry equal to ln_switch, d, ln P* and exit_score on entered frames are e2vq_hmm_segment's bit for bit. */
+int e2vq_hmm_segment_trans(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                           const double *const *Bs, const void *sym, const int64_t *offs, int S, const double *lt,
+                           uint16_t *cls, uint16_t *state, uint8_t *entered, double *exit_score, double *log_prob, int *status,
+                           int sym_on_device);
+/* HIP-event time of the kernels (forward + backtrack) of this thread's last such segmentation (-1: none yet) */
+int e2vq_hmm_segment_trans_last_kernel_ms(float *ms);
+/* e2vq_hmm_segment_report with the segment score above (host only): lt is the K x K matrix of effective prices;
+ * ln_switch is printed in the block's first line.  Columns and formats are e2vq_hmm_segment_report's. */
+int e2vq_hmm_segment_trans_report(const char *name, int64_t T, int K, const char *const *class_names, int W_ms, int O_ms,
+                                  const uint16_t *cls, const uint8_t *entered, const double *exit_score, double log_prob,
+                                  double ln_switch, const double *lt, const char *csv_filename);
+/* The transitions file (host only): a header "class,<name_1>,...,<name_K>", then one line "<from>,v_1,...,v_K" per class;
+ * values are %lg or -inf.  The names must be exactly class_names, in any order; _read permutes the matrix to the order
+ * of class_names (lt: K x K).  A missing, extra or repeated name, a wrong field count, or a value that is > 0 or NaN is
+ * refused with the file and line.  _write writes lt in the order of class_names with %.17g. */
+int e2vq_hmm_transitions_read(const char *filename, int K, const char *const *class_names, double *lt);
+int e2vq_hmm_transitions_write(const char *filename, int K, const char *const *class_names, const double *lt);
+/* e2vq_hmm_segment_files under the transitions file: inputs, stages and refusals are e2vq_hmm_segment_files's; the
+ * effective price is lt[f][k] = file[f][k] + ln_switch (one host addition; 0 means "the file alone"). */
+int e2vq_hmm_segment_trans_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                 const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                                 const char *transitions_csv, const char *csv_dir_or_file);
+/* The matrix from labelled successions (host only): class bigrams are counted within each of the S label sequences
+ * (labels in [0, K), offs: S + 1 offsets), and lt[f][k] = ln((c[f][k] + alpha) / (sum_k' c[f][k'] + alpha K)) with the C
+ * library's log; alpha = 0 gives -inf for unseen pairs, and a row without any count is then refused. */
+int e2vq_hmm_class_transitions(const int32_t *labels, const int64_t *offs, int S, int K, double alpha, double *lt);
+/* `hmm transitions`: the same from files, written as a transitions file for the models' classes.  An input is one of this
+ * project's segment CSVs (column `class`; consecutive rows are one succession) or a tab-separated selection table with the
+ * columns `Begin Time (s)` and `Type` and `#` comment lines (rows ordered by begin time); the kind is detected by the
+ * header.  A label that is no model's class is skipped and counted on stdout. */
+int e2vq_hmm_transitions_files(const char *const *model_filenames, unsigned num_models, const char *const *input_filenames,
+                               int num_inputs, double alpha, const char *out_csv);
+
 #ifdef __cplusplus
 }
 #endif
