@@ -67,10 +67,12 @@ static int usage()
             "                  --switch-penalty <x <= 0 | -inf> [-c <csv dir|file.csv>]\n"
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
             "                  [--class-transitions <file.csv>]\n"
+            "                  [--continuous <name>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
             "                  --posteriors adds each segment's mean and least class posterior, and the per-frame table)\n"
             "                  (--class-transitions adds the file's price of every class-to-class succession to the penalty)\n"
+            "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
@@ -837,7 +839,8 @@ static int hmm_segment_cmd(int argc, char** argv)
     double ln_switch = 0.0;
     bool have_switch = false;
     bool posteriors = false;
-    std::string codebook, csv, frames_dir, transitions;
+    bool continuous = false;
+    std::string codebook, csv, frames_dir, transitions, rec_name;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -859,6 +862,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
         else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
         else if (a == "--posteriors") posteriors = true;
+        else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
         else if (a == "--class-transitions") transitions = val("--class-transitions");
         else if (a == "--switch-penalty") {
@@ -889,6 +893,11 @@ static int hmm_segment_cmd(int argc, char** argv)
         fprintf(stderr, "hmm segment: --class-transitions and --posteriors exclude one another (the posteriors know one price only)\n");
         return 2;
     }
+    if (continuous && (posteriors || !transitions.empty())) {
+        fprintf(stderr, "hmm segment: --continuous decodes under the one switch penalty: not with --posteriors or --class-transitions\n");
+        return 2;
+    }
+    if (continuous && rec_name.empty()) { fprintf(stderr, "hmm segment: --continuous <name>: the recording needs a name\n"); return 2; }
     std::vector<std::string> hmm_files, inputs;
     e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
     if (hmm_files.empty()) { printf("No models given\n"); return 0; }
@@ -902,7 +911,9 @@ static int hmm_segment_cmd(int argc, char** argv)
     auto pm = cptrs(hmm_files), pi = cptrs(inputs);
     const char* cb = codebook.empty() ? nullptr : codebook.c_str();
     const char* out = csv.empty() ? nullptr : csv.c_str();
-    const int failed = !transitions.empty() ? e2vq_hmm_segment_trans_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+    const int failed = continuous ? e2vq_hmm_segment_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+                                                                      ln_switch, rec_name.c_str(), out)
+                       : !transitions.empty() ? e2vq_hmm_segment_trans_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                            ln_switch, transitions.c_str(), out)
                        : posteriors ? e2vq_hmm_segment_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                       ln_switch, out, frames_dir.empty() ? nullptr : frames_dir.c_str())

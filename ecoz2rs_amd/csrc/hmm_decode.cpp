@@ -276,6 +276,8 @@ bool ends_with(const std::string& s, const char* ext)
 // ---- hmm segment: one Viterbi pass through the class loop of all models ------------------------------------
 thread_local float g_segment_kernel_ms = -1.f;  // e2vq_hmm_segment_last_kernel_ms
 
+}  // namespace
+
 int segment_check_shape(const char* who, int K, const int* Ns)
 {
     if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
@@ -297,6 +299,8 @@ int segment_check_switch(const char* who, double ln_switch)
     return 0;
 }
 
+namespace {
+
 struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered, gbest; per stream: log_prob, status
     uint16_t* cls = nullptr;
     uint16_t* state = nullptr;
@@ -306,16 +310,8 @@ struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered
     int* status = nullptr;
 };
 
-// The packing of the classes into wave-slots of 64 lanes that `hmm segment` and its posteriors share: class after class, a
-// class that does not fit the open slot opens the next.  a_ld(N): the leading dimension of a class's A in the device block
-// (a_at / a_words count N x a_ld(N) words a class).
-struct SegPacking {
-    int sumN = 0, a_words = 0, slots = 0;
-    std::vector<int> comp0, a_at;            // [K]: composite index of state 0, offset of A
-    std::vector<int> slot_info;              // [slots][2]: the largest N of the slot, 1 when the slot holds one class
-    std::vector<e2hmm::SegLaneDev> lanes;    // [slots][64]
-    std::vector<uint16_t> comp_cls;          // [sumN]
-};
+}  // namespace
+
 SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int))
 {
     SegPacking pk;
@@ -353,6 +349,8 @@ SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int))
     pk.slots = (int)(pk.lanes.size() / 64);
     return pk;
 }
+
+namespace {
 
 // The joint Viterbi of S device-resident streams (h_offs: their S + 1 offsets, on the host) under the class loop of the
 // models (already checked by segment_check_shape; all of one M; lflats: log_model of each), on the current device and the
@@ -551,31 +549,9 @@ int posteriors_device(const std::vector<const Hmm*>& ms, const unsigned short* d
     return 0;
 }
 
-// ---- input -> device symbols: the stage `hmm scan` and `hmm segment` share ----------------------------------------------------
-struct SymInput {
-    std::string path, csv;
-    int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
-    int sample_rate = 0;
-    int64_t samples = 0, T = 0;
-};
-struct SymInputs {
-    bool have_cb = false, need_cb = false;
-    int cbP = 0, cbM = 0;
-    std::vector<double> refl;
-    std::vector<SymInput> inputs;
-};
-struct SymStage {  // device buffers the inputs of one call reuse; symbols of the current input in d_sym
-    DeviceBuffer<double> d_frames;
-    DeviceBuffer<int32_t> d_status;
-    DeviceBuffer<unsigned short> d_sym;
-};
-struct VqSessionHolder {
-    e2vq_session* s = nullptr;
-    ~VqSessionHolder()
-    {
-        if (s) e2vq_session_destroy(s);
-    }
-};
+}  // namespace
+
+// ---- input -> device symbols: the stage `hmm scan` and `hmm segment` share (its structs: hmm_host.h) --------------------------
 
 // the checks of the inputs against the models' M and the codebook, and the codebook itself: host only, no file written
 int sym_inputs_check(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs,
@@ -688,24 +664,7 @@ int sym_input_to_device(const SymInput& in, const SymInputs& si, SymStage& stg, 
     return 0;
 }
 
-// The models of `hmm scan` / `hmm segment`: loaded, all of one M
-struct FilesModels {
-    std::vector<Hmm> models;
-    std::vector<const Hmm*> ms;
-    std::vector<const char*> names;  // the classes'
-    int M = 0;
-    int load(const char* const* files, unsigned n)
-    {
-        if (load_models(files, n, models)) return 1;
-        M = models[0].M;
-        for (unsigned k = 0; k < n; ++k) {
-            if (models[k].M != M) return e2vq_set_error("%s: model has M=%d but %s has M=%d", files[k], models[k].M, files[0], M);
-            ms.push_back(&models[k]);
-            names.push_back(models[k].class_name.c_str());
-        }
-        return 0;
-    }
-};
+namespace {
 
 // What `hmm scan` and `hmm segment` do once the command's own checks have passed (`who`: the entry point): the check of
 // the inputs and the codebook against M, still on the host alone; then one device, stream and quantize session, and

@@ -1,5 +1,6 @@
 // hmm_host.h -- what the host units of the HMM consumers share (hmm_model.cpp: models, files, sequences; hmm_train.cpp:
-// Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi, scan, segment, posteriors).
+// Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi, scan, segment, posteriors;
+// hmm_segment_stream.cpp: the streaming segment decoder).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -216,5 +217,73 @@ struct DevModels {  // a set of models on the device
 
 // scores of S device-resident sequences under K models: sc[s * K + k]
 int score_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* d_offs, int S, hipStream_t st, Scores& sc);
+
+// ---- decoding (hmm_decode.cpp): what the streaming decoder (hmm_segment_stream.cpp) shares with `hmm segment` ---------
+// the shapes and the price the class loop takes (`who`: the entry point named in the message)
+int segment_check_shape(const char* who, int K, const int* Ns);
+int segment_check_switch(const char* who, double ln_switch);
+
+// The packing of the classes into wave-slots of 64 lanes that `hmm segment` and its posteriors share: class after class, a
+// class that does not fit the open slot opens the next.  a_ld(N): the leading dimension of a class's A in the device block
+// (a_at / a_words count N x a_ld(N) words a class).
+struct SegPacking {
+    int sumN = 0, a_words = 0, slots = 0;
+    std::vector<int> comp0, a_at;            // [K]: composite index of state 0, offset of A
+    std::vector<int> slot_info;              // [slots][2]: the largest N of the slot, 1 when the slot holds one class
+    std::vector<e2hmm::SegLaneDev> lanes;    // [slots][64]
+    std::vector<uint16_t> comp_cls;          // [sumN]
+};
+SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int));
+
+// input -> device symbols: the stage `hmm scan` and `hmm segment` share
+struct SymInput {
+    std::string path, csv;
+    int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
+    int sample_rate = 0;
+    int64_t samples = 0, T = 0;
+};
+struct SymInputs {
+    bool have_cb = false, need_cb = false;
+    int cbP = 0, cbM = 0;
+    std::vector<double> refl;
+    std::vector<SymInput> inputs;
+};
+struct SymStage {  // device buffers the inputs of one call reuse; symbols of the current input in d_sym
+    DeviceBuffer<double> d_frames;
+    DeviceBuffer<int32_t> d_status;
+    DeviceBuffer<unsigned short> d_sym;
+};
+struct VqSessionHolder {
+    e2vq_session* s = nullptr;
+    ~VqSessionHolder()
+    {
+        if (s) e2vq_session_destroy(s);
+    }
+};
+// the checks of the inputs against the models' M and the codebook, and the codebook itself: host only, no file written
+int sym_inputs_check(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs, int P,
+                     int W_ms, int O_ms, const char* csv_dir_or_file, SymInputs& si);
+// one input to symbols in stg.d_sym (read and uploaded once; frames and symbols stay on the device): *T_out of them
+int sym_input_to_device(const SymInput& in, const SymInputs& si, SymStage& stg, e2vq_session* vq, int device, int P, int W_ms,
+                        int O_ms, hipStream_t st, int64_t* T_out);
+
+// The models of `hmm scan` / `hmm segment`: loaded, all of one M
+struct FilesModels {
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    std::vector<const char*> names;  // the classes'
+    int M = 0;
+    int load(const char* const* files, unsigned n)
+    {
+        if (load_models(files, n, models)) return 1;
+        M = models[0].M;
+        for (unsigned k = 0; k < n; ++k) {
+            if (models[k].M != M) return e2vq_set_error("%s: model has M=%d but %s has M=%d", files[k], models[k].M, files[0], M);
+            ms.push_back(&models[k]);
+            names.push_back(models[k].class_name.c_str());
+        }
+        return 0;
+    }
+};
 
 }  // namespace e2hmm_host

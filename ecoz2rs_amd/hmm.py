@@ -90,6 +90,18 @@ _sig("e2vq_hmm_transitions_write", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_
 _sig("e2vq_hmm_class_transitions", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p)
 _sig("e2vq_hmm_transitions_files", C.c_int, c_char_pp, C.c_uint, c_char_pp, C.c_int, C.c_double, C.c_char_p)
 
+_sig("e2vq_hmm_segment_stream_open", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_double,
+     C.POINTER(C.c_void_p))
+_sig("e2vq_hmm_segment_stream_feed", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64))
+_sig("e2vq_hmm_segment_stream_flush", C.c_int, C.c_void_p, C.POINTER(C.c_int64))
+_sig("e2vq_hmm_segment_stream_close", C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int64))
+_sig("e2vq_hmm_segment_stream_take", C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_sig("e2vq_hmm_segment_stream_kernel_ms", C.c_int, C.c_void_p, C.POINTER(C.c_float))
+_sig("e2vq_hmm_segment_stream_stats", C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float))
+_sig("e2vq_hmm_segment_stream_free", None, C.c_void_p)
+_sig("e2vq_hmm_segment_continuous_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_double, C.c_char_p, C.c_char_p)
 
 def _strs(items):
     arr = (C.c_char_p * len(items))(*[str(p).encode() for p in items])
@@ -455,6 +467,116 @@ def segment_last_kernel_ms():
     return ms.value
 
 
+class SegmentStream:
+    """`segment` on one stream that arrives piece by piece: a context manager around a decoder session.
+    models, ln_switch as `segment` takes them.  `feed(sym)` (numpy, or a device tensor), `flush()` (the buffered remainder
+    is processed) and `close()` each return a dict of the frames that became final with the call: first (the absolute
+    frame of the first), cls, state, entered, gbest, and segments -- the segments completed since the last call, as
+    `segments_of` gives them with absolute frames: [b, e) is complete once frame e is final and entered, or at close.
+    After `close`, log_prob and status are set.  The block length and the pending budget are read from
+    ECOZ2_HMM_SEGMENT_STREAM_BLOCK and ECOZ2_HMM_SEGMENT_STREAM_PENDING_BYTES when the session is opened, and
+    ECOZ2_HMM_SEGMENT_BODY is honoured as by `segment`."""
+
+    def __init__(self, models, ln_switch, device=0):
+        K = len(models)
+        ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+        Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+        ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+        M = ms[0][2].shape[1] if K else 0
+        self._h = C.c_void_p()
+        self.ln_switch = float(ln_switch)
+        self.final_frames_ = 0
+        self.log_prob = None
+        self.status = None
+        self._open = None  # the segment that is not complete yet: (begin, cls, lo)
+        check(lib.e2vq_hmm_segment_stream_open(device, K, Ns, M, ptr(0), ptr(1), ptr(2), self.ln_switch, C.byref(self._h)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def free(self):
+        if self._h:
+            lib.e2vq_hmm_segment_stream_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = free
+
+    @property
+    def final_frames(self):
+        """frames final so far"""
+        return self.final_frames_
+
+    def _take(self, end_log_prob=None):
+        n = max(self.final_frames_, 1)
+        cls, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
+        entered, gbest = np.zeros(n, dtype=np.uint8), np.zeros(n)
+        first, count = C.c_int64(), C.c_int64()
+        check(lib.e2vq_hmm_segment_stream_take(self._h, n, cls.ctypes.data, state.ctypes.data, entered.ctypes.data, gbest.ctypes.data,
+                                               C.byref(first), C.byref(count)))
+        c, f0 = count.value, first.value
+        out = dict(first=f0, cls=cls[:c], state=state[:c], entered=entered[:c], gbest=gbest[:c], segments=[])
+
+        def complete(end, hi):
+            b, k, lo = self._open
+            with np.errstate(invalid="ignore"):
+                out["segments"].append(dict(begin=b, end=end, cls=k, log_prob=float(np.float64(hi) - np.float64(lo))))
+
+        for i in np.flatnonzero(out["entered"]):
+            t = f0 + int(i)
+            if self._open is not None:
+                complete(t, float(gbest[i]))
+            self._open = (t, int(cls[i]), 0.0 if t == 0 else float(gbest[i]) + self.ln_switch)
+        if end_log_prob is not None and self._open is not None:
+            complete(f0 + c, end_log_prob)
+            self._open = None
+        return out
+
+    def feed(self, sym):
+        on_device = hasattr(sym, "data_ptr")
+        if on_device:
+            if not sym.is_contiguous() or sym.element_size() != 2:
+                raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+            sym_ptr, n = sym.data_ptr(), sym.numel()
+        else:
+            sym = np.ascontiguousarray(sym, dtype=np.uint16)
+            sym_ptr, n = sym.ctypes.data, sym.size
+        fin = C.c_int64()
+        rc = lib.e2vq_hmm_segment_stream_feed(self._h, sym_ptr, n, int(on_device), C.byref(fin))
+        self.final_frames_ = max(self.final_frames_, fin.value)  # (a feed that fails may have processed blocks before it did)
+        check(rc)
+        return self._take()
+
+    def flush(self):
+        fin = C.c_int64()
+        check(lib.e2vq_hmm_segment_stream_flush(self._h, C.byref(fin)))
+        self.final_frames_ = fin.value
+        return self._take()
+
+    def close(self):
+        lp, st, fin = C.c_double(), C.c_int(), C.c_int64()
+        check(lib.e2vq_hmm_segment_stream_close(self._h, C.byref(lp), C.byref(st), C.byref(fin)))
+        self.final_frames_, self.log_prob, self.status = fin.value, lp.value, st.value
+        return self._take(end_log_prob=lp.value if st.value != 2 else None)
+
+    def take(self):
+        """the frames that are final and were not handed out yet (after a feed that failed, for instance)"""
+        return self._take()
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        check(lib.e2vq_hmm_segment_stream_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def stats(self):
+        """dict peak_pending (frames), device_bytes, commit_ms (coalescence and backtrack, part of kernel_ms)"""
+        pk, by, ms = C.c_int64(), C.c_int64(), C.c_float()
+        check(lib.e2vq_hmm_segment_stream_stats(self._h, C.byref(pk), C.byref(by), C.byref(ms)))
+        return dict(peak_pending=pk.value, device_bytes=by.value, commit_ms=ms.value)
+
+
 def segment_posteriors(models, sym, offs, ln_switch, device=0):
     """P(class at frame t | the whole stream) under the class loop `segment` decodes: arguments as
     `segment` takes them (sym a numpy array or a device tensor); the classes must pack into at most 16 wave-slots.
@@ -583,13 +705,22 @@ def class_transitions_files(model_filenames, input_filenames, out_csv, alpha=1.0
 
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
-                  frame_posteriors=None, class_transitions=None):
+                  frame_posteriors=None, class_transitions=None, continuous=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
-    table for every input.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch"""
+    table for every input.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch.  continuous
+    (4.8.9): the name of the one recording whose consecutive pieces the inputs are -- one block, and with `csv` (a directory
+    or a .csv file) one CSV, <csv>/<name>.csv"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
+    if continuous is not None:
+        if posteriors or class_transitions is not None:
+            raise ValueError("continuous excludes posteriors and class_transitions")
+        check(lib.e2vq_hmm_segment_continuous_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                    len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                    str(continuous).encode(), str(csv).encode() if csv else None))
+        return
     if frame_posteriors is not None and not posteriors:
         raise ValueError("frame_posteriors needs posteriors=True")
     if class_transitions is not None:

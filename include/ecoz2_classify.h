@@ -406,6 +406,60 @@ int e2vq_hmm_class_transitions(const int32_t *labels, const int64_t *offs, int S
 int e2vq_hmm_transitions_files(const char *const *model_filenames, unsigned num_models, const char *const *input_filenames,
                                int num_inputs, double alpha, const char *out_csv);
 
+/* ---- the same decode on a stream that arrives piece by piece -------------------------------------------
+ * `hmm segment --continuous`: a session decodes ONE symbol stream of unknown length under the contract of e2vq_hmm_segment
+ * (K models sharing M, one ln_switch; same recursion, ties, G_t, g_t, psi and ENTER) and gives the bits of e2vq_hmm_segment
+ * on the concatenation of everything fed, whatever the feeds' lengths.  Symbols are processed in blocks of exactly B frames
+ * (ECOZ2_HMM_SEGMENT_STREAM_BLOCK, read at open, default 4096; below 1 is refused); fewer than B stay buffered until the
+ * next feed, a flush or close.  A block starts from the d the previous one left; the frame-0 rule holds at the absolute
+ * frame 0 only.
+ * Finality: after the last block of a feed, the paths of all states with d > -inf are followed back in lockstep; up to the
+ * latest frame at which they are all in one state, the frames are final, and they are that path's.  (The state this reaches
+ * just before the first new frame must be where the previous commit ended; otherwise an internal error is returned.)  With
+ * no such state nothing becomes final.  The number of final frames after p processed frames depends on the first p symbols
+ * alone.  close decides the rest from the lowest state reaching max d, as e2vq_hmm_segment does, and yields ln P* and the
+ * status.  Final frames wait in host memory (13 bytes a frame) until e2vq_hmm_segment_stream_take hands them out, in order;
+ * each of its outputs may be NULL.
+ * Status.  The equality with e2vq_hmm_segment is claimed for a stream whose status there is 0.  2, a symbol >= M: the feed
+ * or flush that meets it fails with a message naming the absolute frame, and the session takes no more symbols; close then
+ * reports status 2 and ln P* = -inf, frames already final stay, and every other frame fed is delivered as cls = state =
+ * 0xFFFF, entered 0, gbest -inf.  1, every state dead: nothing more becomes final before close, which backtracks by the
+ * usual rules and reports status 1, ln P* = -inf; the frames of such a stream need not be e2vq_hmm_segment's, because a
+ * path that died later may have left a committed prefix.  Nothing fed: status 0, ln P* = 0.0, no frames.
+ * Memory.  psi and g of the frames that are not final stay on the device in a ring of 2 sum N + 4 bytes a frame, bounded by
+ * ECOZ2_HMM_SEGMENT_STREAM_PENDING_BYTES (default 256 MiB; a budget below two blocks is refused at open).  A feed or flush
+ * whose next block does not fit fails with a message naming the variable and the number of pending frames (with ln_switch =
+ * -inf paths of different classes never meet); the blocks before it stay processed, the rest of that feed is dropped, and
+ * the session can still be closed (B - 1 rows beyond the budget are kept for the remainder at close).  Besides the ring a
+ * session holds the parameters, O(B) staging and 5 bytes a pending frame for the results of a commit: nothing grows with
+ * the stream.  ECOZ2_HMM_SEGMENT_BODY is honoured as by e2vq_hmm_segment.
+ * Refused before any HIP call: what e2vq_hmm_segment refuses, a bad block length, a budget below two blocks.  A NULL
+ * session, and a feed or flush after close or after status 2, are refused.  One thread at a time uses a session. */
+typedef struct e2vq_segment_stream e2vq_segment_stream;
+int e2vq_hmm_segment_stream_open(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                                 const double *const *Bs, double ln_switch, e2vq_segment_stream **out);
+/* n >= 0 symbols (u16; sym_on_device: a device pointer on the session's device); *final_frames: all frames final so far */
+int e2vq_hmm_segment_stream_feed(e2vq_segment_stream *s, const void *sym, int64_t n, int sym_on_device, int64_t *final_frames);
+/* processes the buffered remainder as a short block */
+int e2vq_hmm_segment_stream_flush(e2vq_segment_stream *s, int64_t *final_frames);
+int e2vq_hmm_segment_stream_close(e2vq_segment_stream *s, double *log_prob, int *status, int64_t *final_frames);
+int e2vq_hmm_segment_stream_take(e2vq_segment_stream *s, int64_t max_frames, uint16_t *cls, uint16_t *state, uint8_t *entered,
+                                 double *gbest, int64_t *first_frame, int64_t *count);
+/* HIP-event time of all kernels of the session so far (per feed: first launch to last, the copies between them included) */
+int e2vq_hmm_segment_stream_kernel_ms(e2vq_segment_stream *s, float *ms);
+/* the most frames that were pending at once; the device bytes of the session; the part of kernel_ms spent in coalescence
+ * and backtrack.  Each may be NULL. */
+int e2vq_hmm_segment_stream_stats(e2vq_segment_stream *s, int64_t *peak_pending, int64_t *device_bytes, float *commit_ms);
+void e2vq_hmm_segment_stream_free(e2vq_segment_stream *s);
+/* The file form: the inputs, in the order given, are consecutive pieces of ONE recording called `name`.  Models, inputs and
+ * up-front refusals as e2vq_hmm_segment_files.  Each piece becomes symbols on its own -- a .wav is analysed by itself, so no
+ * LPC window straddles two files -- and is fed to one session; at the end e2vq_hmm_segment_report(name, ...) writes the
+ * block and the CSV (csv_dir_or_file: <dir>/<name>.csv, or the .csv file itself).  Times are frame arithmetic over the
+ * whole run, as if it were one .seq. */
+int e2vq_hmm_segment_continuous_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                      const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                      double ln_switch, const char *name, const char *csv_dir_or_file);
+
 #ifdef __cplusplus
 }
 #endif
