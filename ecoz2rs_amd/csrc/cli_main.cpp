@@ -75,6 +75,11 @@ static int usage()
             "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
+            "  ecoz2 hmm align -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
+            "                  [--switch-penalty <x <= 0>] [--filler <class>] [-c <csv dir|file.csv>] --labels <files>...\n"
+            "                  (--signals <.wav files>... | --predictors <.prd files>... | --sequences <.seq files>...)\n"
+            "                  (each recording aligned to the units its label file names, in their order: a segment .csv or a\n"
+            "                  selection table; --filler: that class's model may stand before, between and after the units)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -963,6 +968,75 @@ static int hmm_transitions_cmd(int argc, char** argv)
     return 0;
 }
 
+// `hmm align`: each recording aligned to the known order of its units under the trained models
+static int hmm_align_cmd(int argc, char** argv)
+{
+    int P = 36, W = 45, O = 15;
+    double ln_switch = 0.0;
+    std::string codebook, csv, filler;
+    std::vector<std::string> models, labels, signals, predictors, sequences;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        auto num = [&](const char* name) -> long long {
+            const char* v = val(name);
+            char* end = nullptr;
+            const long long x = strtoll(v, &end, 10);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto many = [&](std::vector<std::string>& v) { while (i + 1 < argc && !is_flag(argv[i + 1])) v.push_back(argv[++i]); };
+        if (a == "-m" || a == "--models") many(models);
+        else if (a == "--codebook") codebook = val("--codebook");
+        else if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
+        else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
+        else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "--filler") filler = val("--filler");
+        else if (a == "--labels") many(labels);
+        else if (a == "--switch-penalty") {
+            const char* v = val("--switch-penalty");
+            char* end = nullptr;
+            ln_switch = strtod(v, &end);
+            if (!*v || *end) { fprintf(stderr, "--switch-penalty: invalid value '%s'\n", v); exit(2); }
+        }
+        else if (a == "-c" || a == "--csv") csv = val("-c");
+        else if (a == "--signals") many(signals);
+        else if (a == "--predictors") many(predictors);
+        else if (a == "-s" || a == "--sequences") many(sequences);
+        else return usage();
+    }
+    if (models.empty()) { fprintf(stderr, "hmm align: --models <files|dirs>... is required\n"); return usage(); }
+    if ((int)!signals.empty() + (int)!predictors.empty() + (int)!sequences.empty() != 1) {
+        fprintf(stderr, "hmm align: exactly one of --signals, --predictors and --sequences is required\n");
+        return usage();
+    }
+    if (!(ln_switch <= 0.0) || std::isinf(ln_switch)) { fprintf(stderr, "hmm align: --switch-penalty %g: finite and at most 0\n", ln_switch); return 2; }
+    if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
+    if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
+    if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm align: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    // (the inputs are taken as given, not resolved from directories: input i goes with label file i)
+    const std::vector<std::string>& inputs = !signals.empty() ? signals : !predictors.empty() ? predictors : sequences;
+    if (labels.size() != inputs.size()) {
+        fprintf(stderr, "hmm align: %zu label files for %zu inputs (--labels names one per input, in the inputs' order)\n", labels.size(), inputs.size());
+        return 2;
+    }
+    std::vector<std::string> hmm_files;
+    e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
+    auto pm = cptrs(hmm_files), pi = cptrs(inputs), pl = cptrs(labels);
+    if (e2vq_hmm_align_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(), pl.data(),
+                             (int)pi.size(), P, W, O, ln_switch, filler.empty() ? nullptr : filler.c_str(), csv.empty() ? nullptr : csv.c_str())) {
+        printf("%s\n", e2vq_last_error());
+        return 1;
+    }
+    return 0;
+}
+
 static int hmm_cmd(int argc, char** argv)
 {
     if (argc < 1) return usage();
@@ -970,6 +1044,7 @@ static int hmm_cmd(int argc, char** argv)
     if (cmd == "scan") return hmm_scan_cmd(argc - 1, argv + 1);
     if (cmd == "transitions") return hmm_transitions_cmd(argc - 1, argv + 1);
     if (cmd == "segment") return hmm_segment_cmd(argc - 1, argv + 1);
+    if (cmd == "align") return hmm_align_cmd(argc - 1, argv + 1);
     int N = 5, M = -1, type = 3, max_iterations = -1;
     double epsilon = 1e-05, val_auto = 0.3;
     long seed = -1;

@@ -1,0 +1,441 @@
+// hmm_align.cpp -- forced alignment on the GPU (`hmm align`, e2vq_hmm_align): the most likely path of a
+// symbol stream through the units of its transcript, in their order, over the kernels of hmm_align.hip.  The host checks
+// the transcripts and packs each stream's units into wave-slots (all before any HIP call), cuts the launches by the table
+// budget, replays the decoded path for its per-frame score, and writes the reports.
+#include "hmm_host.h"
+
+namespace e2hmm_host {
+namespace {
+
+thread_local float g_align_kernel_ms = -1.f;  // e2vq_hmm_align_last_kernel_ms
+
+constexpr int ALIGN_MAX_L = 65535;
+
+struct AlignOut {  // host arrays, any may be null; per frame: unit, state, entered, score; per unit: begin, end; per stream: the rest
+    uint16_t* unit = nullptr;
+    uint16_t* state = nullptr;
+    uint8_t* entered = nullptr;
+    double* score = nullptr;
+    int64_t* begin = nullptr;
+    int64_t* end = nullptr;
+    double* log_prob = nullptr;
+    int* status = nullptr;
+};
+
+// What the host decides about a call before the device is touched: the packing of every stream's units, the device tables
+// that describe it, and the launches (consecutive streams of one body whose tables and LDS fit together).
+struct AlignPlan {
+    std::vector<e2hmm::AlignStreamDev> streams;  // tab_at: relative to the first stream of its launch
+    std::vector<e2hmm::AlignLaneDev> lanes;
+    std::vector<int> slot_info, unit_comp0;
+    std::vector<uint16_t> comp_unit;
+    struct Launch {
+        int s0, s1, waves, max_L, max_sumN;
+        bool looped;
+        i64 bytes;
+    };
+    std::vector<Launch> launches;
+    i64 max_bytes = 0;
+};
+
+// may unit l hold frame 0 / the last frame (opt: the stream's flags, or null)
+bool unit_is_initial(int l, const uint8_t* opt) { return l == 0 || (l == 1 && opt && opt[0]); }
+bool unit_is_final(int l, int L, const uint8_t* opt) { return l == L - 1 || (l == L - 2 && opt && opt[L - 1]); }
+
+// the checks of the transcripts and the price, the packing and the launches: host only (`who`: the entry point named in
+// the messages)
+int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
+               const uint8_t* optional, double ln_switch, AlignPlan& ap)
+{
+    if (segment_check_switch(who, ln_switch)) return 1;
+    if (std::isinf(ln_switch)) return e2vq_set_error("%s: ln_switch = %g: a finite price (every unit has to be entered)", who, ln_switch);
+    if (unit_offs[0] != 0) return e2vq_set_error("%s: unit_offs[0] = %lld, not 0", who, (long long)unit_offs[0]);
+    const char* body = getenv("ECOZ2_HMM_ALIGN_BODY");
+    if (body && *body && strcmp(body, "resident") != 0 && strcmp(body, "looped") != 0)
+        return e2vq_set_error("ECOZ2_HMM_ALIGN_BODY=%s: resident or looped", body);
+    const bool force_looped = body && strcmp(body, "looped") == 0;
+    const i64 budget = env_bytes("ECOZ2_HMM_ALIGN_TABLE_BYTES", (i64)4 << 30);
+    std::vector<int> cls_comp0((size_t)K), cls_a_at((size_t)K);
+    int a_words = 0;
+    for (int k = 0, c = 0; k < K; ++k) {
+        cls_comp0[(size_t)k] = c;
+        cls_a_at[(size_t)k] = a_words;
+        c += Ns[k];
+        a_words += Ns[k] * Ns[k];
+    }
+    std::vector<bool> looped((size_t)S);
+    std::vector<i64> bytes((size_t)S);
+    ap.streams.resize((size_t)S);
+    for (int s = 0; s < S; ++s) {
+        const i64 u0 = unit_offs[s], L64 = unit_offs[s + 1] - u0;
+        if (L64 < 0) return e2vq_set_error("%s: unit_offs decrease at stream %d", who, s);
+        if (L64 < 1) return e2vq_set_error("%s: stream %d has an empty transcript", who, s);
+        if (L64 > ALIGN_MAX_L) return e2vq_set_error("%s: stream %d has %lld units (at most %d)", who, s, (long long)L64, ALIGN_MAX_L);
+        const int L = (int)L64;
+        const int32_t* u = units + u0;
+        const uint8_t* opt = optional ? optional + u0 : nullptr;
+        std::vector<int> uN((size_t)L);
+        i64 sumN = 0;
+        bool mandatory = false;
+        for (int l = 0; l < L; ++l) {
+            if (u[l] < 0 || u[l] >= K) return e2vq_set_error("%s: stream %d, unit %d names the class %d outside [0, %d)", who, s, l, u[l], K);
+            if (opt && opt[l] && l > 0 && opt[l - 1])
+                return e2vq_set_error("%s: stream %d, units %d and %d are both optional (a path may pass over one unit only)", who, s, l - 1, l);
+            mandatory = mandatory || !(opt && opt[l]);
+            uN[(size_t)l] = Ns[u[l]];
+            sumN += Ns[u[l]];
+        }
+        if (!mandatory) return e2vq_set_error("%s: stream %d: every unit of the transcript is optional", who, s);
+        if (!e2hmm::align_fits_lds(L, (int)sumN, false))
+            return e2vq_set_error("%s: stream %d: %d units of sum N = %lld states do not fit in LDS (%zu of %zu bytes)", who, s, L,
+                                  (long long)sumN, e2hmm::align_lds_bytes(L, (int)sumN, 0, false, false), e2hmm::SEG_LDS_BYTES);
+        const SegPacking pk = pack_slots(uN, [](int N) { return N; });
+        looped[(size_t)s] = force_looped || pk.slots > e2hmm::SEG_MAX_WAVES;
+        if (looped[(size_t)s] && !e2hmm::align_fits_lds(L, pk.sumN, true))
+            return e2vq_set_error("%s: stream %d: %d units of sum N = %d states in %d wave-slots do not fit in LDS (%zu of %zu bytes)", who,
+                                  s, L, pk.sumN, pk.slots, e2hmm::align_lds_bytes(L, pk.sumN, 0, true, false), e2hmm::SEG_LDS_BYTES);
+        const i64 T = offs[s + 1] - offs[s];
+        bytes[(size_t)s] = T * ((i64)pk.sumN + L);
+        if (bytes[(size_t)s] > budget)
+            return e2vq_set_error("%s: stream %d: the back-pointers of %lld frames x (%d states + %d units) take %lld bytes: more than "
+                                  "ECOZ2_HMM_ALIGN_TABLE_BYTES=%lld",
+                                  who, s, (long long)T, pk.sumN, L, (long long)bytes[(size_t)s], (long long)budget);
+        e2hmm::AlignStreamDev& sd = ap.streams[(size_t)s];
+        sd.lane_at = (i64)ap.lanes.size();
+        sd.tab_at = 0;
+        sd.unit_at = u0;
+        sd.comp_at = (i64)ap.comp_unit.size();
+        sd.slots = pk.slots, sd.L = L, sd.sumN = pk.sumN, sd.pad = 0;
+        for (const e2hmm::SegLaneDev& sl : pk.lanes) {
+            e2hmm::AlignLaneDev al{-1, 0, 0, sl.seg, 0, 0, 0, 0};
+            if (sl.cls >= 0) {
+                const int l = sl.cls, k = u[l];
+                const int flags = (unit_is_initial(l, opt) ? e2hmm::ALIGN_INIT : 0) | (l >= 1 ? e2hmm::ALIGN_PRED : 0) |
+                                  (l >= 2 && opt && opt[l - 1] ? e2hmm::ALIGN_SKIP : 0) | (unit_is_final(l, L, opt) ? e2hmm::ALIGN_FINAL : 0);
+                al = e2hmm::AlignLaneDev{l, sl.j, sl.N, sl.seg, sl.comp, cls_comp0[(size_t)k] + sl.j, cls_a_at[(size_t)k], flags};
+            }
+            ap.lanes.push_back(al);
+        }
+        ap.slot_info.insert(ap.slot_info.end(), pk.slot_info.begin(), pk.slot_info.end());
+        ap.unit_comp0.insert(ap.unit_comp0.end(), pk.comp0.begin(), pk.comp0.end());
+        ap.comp_unit.insert(ap.comp_unit.end(), pk.comp_cls.begin(), pk.comp_cls.end());
+    }
+    // the launches: consecutive streams of one body whose tables stay within the budget and whose largest L and sum N fit LDS
+    for (int s0 = 0; s0 < S;) {
+        AlignPlan::Launch g{s0, s0, 0, 0, 0, looped[(size_t)s0], 0};
+        int slots = 0;
+        while (g.s1 < S) {
+            const e2hmm::AlignStreamDev& sd = ap.streams[(size_t)g.s1];
+            const int mL = std::max(g.max_L, sd.L), mN = std::max(g.max_sumN, sd.sumN);
+            if (g.s1 > s0 && (looped[(size_t)g.s1] != g.looped || g.bytes + bytes[(size_t)g.s1] > budget || !e2hmm::align_fits_lds(mL, mN, g.looped)))
+                break;
+            ap.streams[(size_t)g.s1].tab_at = g.bytes;
+            g.bytes += bytes[(size_t)g.s1];
+            g.max_L = mL, g.max_sumN = mN;
+            slots = std::max(slots, sd.slots);
+            ++g.s1;
+        }
+        g.waves = std::min(slots, e2hmm::SEG_MAX_WAVES);
+        ap.max_bytes = std::max(ap.max_bytes, g.bytes);
+        ap.launches.push_back(g);
+        s0 = g.s1;
+    }
+    return 0;
+}
+
+// the path's own cumulative score, frame by frame, from the decoded path: one addition per term in the device's order
+void align_replay(const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats, const uint16_t* sym, i64 T,
+                  const int32_t* units, const uint8_t* opt, double ln_switch, const uint16_t* unit, const uint16_t* state,
+                  const uint8_t* entered, double* score)
+{
+    const int M = ms[0]->M;
+    for (i64 t = 0; t < T; ++t) {
+        const int l = unit[t], j = state[t], k = units[l];
+        const size_t N = (size_t)ms[(size_t)k]->N;
+        const double* lf = lflats[(size_t)k].data();
+        const double lpi = lf[j], lB = lf[N + N * N + (size_t)j * M + sym[t]];
+        if (t == 0) score[0] = unit_is_initial(l, opt) ? lpi + lB : -INFINITY;
+        else if (entered[t]) score[t] = ((score[t - 1] + ln_switch) + lpi) + lB;
+        else score[t] = (score[t - 1] + lf[N + (size_t)state[t - 1] * N + j]) + lB;
+    }
+}
+
+// The alignment of S device-resident streams (h_offs: their S + 1 offsets, on the host) to their transcripts under the
+// models (all of one M; lflats: log_model of each), as planned by align_plan, on the current device and the stream st.
+int align_device(const char* who, const AlignPlan& ap, const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats,
+                 const unsigned short* d_sym, const i64* h_offs, int S, const int32_t* units, const i64* unit_offs,
+                 const uint8_t* optional, double ln_switch, hipStream_t st, const AlignOut& out)
+{
+    const int K = (int)ms.size(), M = ms[0]->M;
+    int sumN = 0, a_words = 0;
+    for (const Hmm* h : ms) sumN += h->N, a_words += h->N * h->N;
+    // logarithms: lpi of every class | lA of every class | lB of every class
+    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M);
+    for (int k = 0, c = 0, a = 0; k < K; ++k) {
+        const std::vector<double>& lflat = lflats[(size_t)k];
+        const size_t N = (size_t)ms[(size_t)k]->N;
+        std::copy(lflat.begin(), lflat.begin() + N, params.begin() + c);
+        std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + a);
+        std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + a_words + (size_t)c * M);
+        c += (int)N, a += (int)(N * N);
+    }
+    const i64 frames = h_offs[S], nunits = unit_offs[S];
+    DeviceBuffer<double> d_params, d_logp;
+    DeviceBuffer<e2hmm::AlignLaneDev> d_lanes;
+    DeviceBuffer<e2hmm::AlignStreamDev> d_streams;
+    DeviceBuffer<int> d_info, d_comp0, d_status, d_qlast;
+    DeviceBuffer<unsigned short> d_comp_unit, d_unit, d_state;
+    DeviceBuffer<unsigned char> d_entered, d_tab;
+    DeviceBuffer<i64> d_offs, d_begin, d_end;
+    if (d_params.upload(params.data(), params.size(), st) || d_lanes.upload(ap.lanes.data(), ap.lanes.size(), st) ||
+        d_streams.upload(ap.streams.data(), ap.streams.size(), st) || d_info.upload(ap.slot_info.data(), ap.slot_info.size(), st) ||
+        d_comp0.upload(ap.unit_comp0.data(), ap.unit_comp0.size(), st) || d_comp_unit.upload(ap.comp_unit.data(), ap.comp_unit.size(), st) ||
+        d_offs.upload(h_offs, (size_t)S + 1, st) || d_logp.reserve((size_t)S) || d_status.reserve((size_t)S) || d_qlast.reserve((size_t)S) ||
+        d_unit.reserve((size_t)frames) || d_state.reserve((size_t)frames) || d_entered.reserve((size_t)frames) ||
+        d_begin.reserve((size_t)nunits) || d_end.reserve((size_t)nunits))
+        return 1;
+    if (d_tab.reserve((size_t)ap.max_bytes)) {
+        const std::string why = e2vq_last_error();
+        return e2vq_set_error("%s: no room for the back-pointer tables of %lld bytes (ECOZ2_HMM_ALIGN_TABLE_BYTES bounds them by whole "
+                              "streams): %s", who, (long long)ap.max_bytes, why.c_str());
+    }
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    // (one stream: a launch's forward pass writes the tables only after the previous launch's backtrack has read them)
+    for (const AlignPlan::Launch& g : ap.launches) {
+        const int s0 = g.s0, n = g.s1 - g.s0;
+        const e2hmm::AlignPlanDev pl{M, sumN, a_words, g.max_L, g.max_sumN, d_streams.get() + s0, d_lanes.get(), d_info.get(),
+                                     d_params.get(), d_comp_unit.get(), d_comp0.get()};
+        if (e2hmm::launch_align(pl, g.looped, g.waves, d_sym, d_offs.get() + s0, n, ln_switch, d_tab.get(), d_logp.get() + s0,
+                                d_qlast.get() + s0, d_status.get() + s0, st))
+            return e2vq_set_error("%s: %d units of sum N = %d states cannot be launched", who, g.max_L, g.max_sumN);
+        HIPCHK(hipGetLastError());
+        e2hmm::launch_align_backtrack(pl, d_offs.get() + s0, n, d_tab.get(), d_qlast.get() + s0, d_status.get() + s0, d_unit.get(),
+                                      d_state.get(), d_entered.get(), d_begin.get(), d_end.get(), st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    // the path comes to the host whatever the caller asks for: the score is replayed from it
+    const size_t nf = (size_t)std::max<i64>(frames, 1);
+    std::vector<uint16_t> h_unit(nf), h_state(nf), h_sym(nf);
+    std::vector<uint8_t> h_entered(nf);
+    std::vector<double> h_logp((size_t)S), h_score(nf);
+    std::vector<int> h_status((size_t)S);
+    if (frames > 0) {
+        HIPCHK(hipMemcpyAsync(h_unit.data(), d_unit.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_state.data(), d_state.get(), (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_entered.data(), d_entered.get(), (size_t)frames, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_sym.data(), d_sym, (size_t)frames * 2, hipMemcpyDeviceToHost, st));
+    }
+    if (nunits > 0) {
+        if (out.begin) HIPCHK(hipMemcpyAsync(out.begin, d_begin.get(), (size_t)nunits * 8, hipMemcpyDeviceToHost, st));
+        if (out.end) HIPCHK(hipMemcpyAsync(out.end, d_end.get(), (size_t)nunits * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (S > 0) {
+        HIPCHK(hipMemcpyAsync(h_logp.data(), d_logp.get(), (size_t)S * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_status.data(), d_status.get(), (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_align_kernel_ms)) return 1;
+    for (int s = 0; s < S; ++s) {
+        const i64 a = h_offs[s], T = h_offs[s + 1] - a;
+        if (T < 1) continue;
+        double* sc = h_score.data() + a;
+        if (h_status[(size_t)s] == 2) {
+            std::fill(sc, sc + T, -INFINITY);
+            sc[0] = 0.0;
+            continue;
+        }
+        align_replay(ms, lflats, h_sym.data() + a, T, units + unit_offs[s], optional ? optional + unit_offs[s] : nullptr, ln_switch,
+                     h_unit.data() + a, h_state.data() + a, h_entered.data() + a, sc);
+        if (memcmp(&sc[T - 1], &h_logp[(size_t)s], 8) != 0)
+            return e2vq_set_error("%s: internal error: stream %d: the replayed path scores %.17g, the device found %.17g", who, s, sc[T - 1],
+                                  h_logp[(size_t)s]);
+    }
+    if (frames > 0) {
+        if (out.unit) std::copy(h_unit.begin(), h_unit.begin() + frames, out.unit);
+        if (out.state) std::copy(h_state.begin(), h_state.begin() + frames, out.state);
+        if (out.entered) std::copy(h_entered.begin(), h_entered.begin() + frames, out.entered);
+        if (out.score) std::copy(h_score.begin(), h_score.begin() + frames, out.score);
+    }
+    if (out.log_prob) std::copy(h_logp.begin(), h_logp.end(), out.log_prob);
+    if (out.status) std::copy(h_status.begin(), h_status.end(), out.status);
+    return 0;
+}
+
+}  // namespace
+}  // namespace e2hmm_host
+using namespace e2hmm_host;
+
+extern "C" int e2vq_hmm_align_last_kernel_ms(float* ms)
+{
+    if (!ms) return e2vq_set_error("e2vq_hmm_align_last_kernel_ms: bad arguments");
+    *ms = g_align_kernel_ms;
+    return 0;
+}
+
+extern "C" int e2vq_hmm_align(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                              const double* const* Bs, const void* sym, const int64_t* offs, int S, const int32_t* units,
+                              const int64_t* unit_offs, const uint8_t* optional, double ln_switch, uint16_t* unit, uint16_t* state,
+                              uint8_t* entered, double* score, int64_t* begin, int64_t* end, double* log_prob, int* status,
+                              int sym_on_device)
+{
+    const char* who = "e2vq_hmm_align";
+    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
+    if (!Ns || !pis || !As || !Bs || S < 0 || !offs || !unit_offs || (S > 0 && !units) || (!sym && S > 0 && offs[S] > 0))
+        return e2vq_set_error("%s: bad arguments", who);
+    if (segment_check_shape(who, K, Ns)) return 1;
+    std::vector<Hmm> models;
+    std::vector<const Hmm*> ms;
+    std::vector<std::vector<double>> lflats((size_t)K);
+    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms)) return 1;
+    for (int k = 0; k < K; ++k)
+        if (log_model(models[(size_t)k], lflats[(size_t)k])) return 1;
+    if (check_offsets(offs, S)) return 1;
+    AlignPlan ap;
+    if (align_plan(who, K, Ns, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, ap)) return 1;
+    // ---- the device from here on --------------------------------------------------------------------------------
+    if (require_device(device)) return 1;
+    DevSeqs seqs;
+    if (seqs.symbols(sym, (size_t)offs[S], sym_on_device != 0)) return 1;
+    AlignOut out;
+    out.unit = unit, out.state = state, out.entered = entered, out.score = score, out.begin = begin, out.end = end;
+    out.log_prob = log_prob, out.status = status;
+    return align_device(who, ap, ms, lflats, seqs.sym, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, seqs.st.s, out);
+}
+
+extern "C" int e2vq_hmm_align_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms, int L,
+                                     const int32_t* units, const uint8_t* optional, const int64_t* begin, const int64_t* end,
+                                     const double* score, double log_prob, double ln_switch, const char* csv_filename)
+{
+    const char* who = "e2vq_hmm_align_report";
+    FlushStdout flush_on_return;
+    if (!name || K < 1 || !class_names || T < 0 || L < 1 || !units || !begin || !end || (T > 0 && !score)) return e2vq_set_error("%s: bad arguments", who);
+    int skipped = 0;
+    for (int l = 0; l < L; ++l) {
+        if (units[l] < 0 || units[l] >= K) return e2vq_set_error("%s: unit %d names a model outside [0, %d)", who, l, K);
+        if (begin[l] < 0) {
+            skipped += optional && optional[l] ? 1 : 0;
+            continue;
+        }
+        if (begin[l] >= end[l] || end[l] > T) return e2vq_set_error("%s: unit %d spans [%lld, %lld) of %lld frames", who, l, (long long)begin[l], (long long)end[l], (long long)T);
+    }
+    auto begin_s = [&](int64_t b) { return (double)(b * O_ms) / 1000.0; };
+    // (the end of the analysis window of the unit's last frame)
+    auto end_s = [&](int64_t e) { return (double)((e - 1) * O_ms + W_ms) / 1000.0; };
+    auto unit_score = [&](int l) { return score[end[l] - 1] - (begin[l] == 0 ? 0.0 : score[begin[l] - 1] + ln_switch); };
+    if (csv_filename && *csv_filename) {
+        std::string doc = "unit,class,begin_frame,end_frame,begin_s,end_s,score\n";
+        for (int l = 0; l < L; ++l) {
+            if (begin[l] < 0) continue;
+            doc += std::to_string(l) + "," + class_names[units[l]] + "," + std::to_string(begin[l]) + "," + std::to_string(end[l]) + "," +
+                   fmt_17g(begin_s(begin[l])) + "," + fmt_17g(end_s(end[l])) + "," + fmt_17g(unit_score(l)) + "\n";
+        }
+        if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
+    }
+    printf("%s: T=%lld  units=%d  optional units passed over=%d  log_prob=%g  (switch penalty %g)\n", name, (long long)T, L, skipped, log_prob,
+           ln_switch);
+    std::vector<int64_t> count((size_t)K, 0);
+    for (int l = 0; l < L; ++l)
+        if (begin[l] >= 0) count[(size_t)units[l]] += end[l] - begin[l];
+    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)count[(size_t)k]);
+    printf("  units:\n");
+    for (int l = 0; l < L; ++l)
+        if (begin[l] >= 0) printf("    %.3f - %.3f %s\n", begin_s(begin[l]), end_s(end[l]), class_names[units[l]]);
+    if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
+    return 0;
+}
+
+extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                    const char* const* input_filenames, const char* const* label_filenames, int num_inputs, int P,
+                                    int W_ms, int O_ms, double ln_switch, const char* filler_class, const char* csv_dir_or_file)
+{
+    const char* who = "e2vq_hmm_align_files";
+    FlushStdout flush_on_return;
+    if (!model_filenames || num_models < 1) return e2vq_set_error("%s: no models", who);
+    if (!input_filenames || !label_filenames || num_inputs < 1) return e2vq_set_error("%s: no inputs", who);
+    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms);
+    FilesModels fm;
+    if (fm.load(model_filenames, num_models)) return 1;
+    const int K = (int)num_models;
+    std::vector<int> Ns;
+    for (const Hmm& h : fm.models) Ns.push_back(h.N);
+    if (segment_check_shape(who, K, Ns.data())) return 1;
+    auto class_of = [&](const std::string& name) {
+        int k = 0;
+        while (k < K && name != fm.names[(size_t)k]) ++k;
+        return k < K ? k : -1;
+    };
+    int filler = -1;
+    if (filler_class && *filler_class && (filler = class_of(filler_class)) < 0)
+        return e2vq_set_error("%s: the filler '%s' is no model's class", who, filler_class);
+    std::vector<std::vector<double>> lflats((size_t)num_models);
+    for (unsigned k = 0; k < num_models; ++k)
+        if (log_model(fm.models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    SymInputs si;
+    if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, si)) return 1;
+    // the transcripts: the labels of file i in their order, the filler around and between them
+    std::vector<std::vector<int32_t>> units((size_t)num_inputs);
+    std::vector<std::vector<uint8_t>> optional((size_t)num_inputs);
+    for (int f = 0; f < num_inputs; ++f) {
+        const char* path = label_filenames[f];
+        if (!path) return e2vq_set_error("%s: NULL file name", who);
+        std::vector<LabelRow> rows;
+        if (read_label_file(path, rows)) return 1;
+        if (rows.empty()) return e2vq_set_error("%s: no labelled units", path);
+        std::vector<int32_t>& u = units[(size_t)f];
+        std::vector<uint8_t>& o = optional[(size_t)f];
+        auto fill = [&] {
+            if (filler >= 0) u.push_back(filler), o.push_back(1);
+        };
+        fill();
+        for (const LabelRow& r : rows) {
+            const int k = class_of(r.label);
+            if (k < 0) return e2vq_set_error("%s:%zu: '%s' is no model's class", path, r.line, r.label.c_str());
+            u.push_back(k), o.push_back(0);
+            fill();
+        }
+        // (with the frame count known so far: a .wav may still lose frames, which only shrinks the tables)
+        const i64 offs[2] = {0, si.inputs[(size_t)f].T}, uoffs[2] = {0, (i64)u.size()};
+        AlignPlan ap;
+        if (align_plan(who, K, Ns.data(), offs, 1, u.data(), uoffs, o.data(), ln_switch, ap))
+            return e2vq_set_error("%s: %s", path, std::string(e2vq_last_error()).c_str());
+    }
+    // ---- the device from here on --------------------------------------------------------------------------------
+    const int device = env_device();
+    if (require_device(device)) return 1;
+    SymStage stg;
+    Stream st;
+    if (st.create()) return 1;
+    VqSessionHolder vq;
+    if (si.need_cb) {
+        if (e2vq_session_create(device, si.cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, si.refl.data(), si.cbM))
+            return 1;
+    }
+    for (int f = 0; f < num_inputs; ++f) {
+        const SymInput& in = si.inputs[(size_t)f];
+        const std::vector<int32_t>& u = units[(size_t)f];
+        const std::vector<uint8_t>& o = optional[(size_t)f];
+        int64_t T = 0;
+        if (sym_input_to_device(in, si, stg, vq.s, device, P, W_ms, O_ms, st.s, &T)) return 1;
+        const i64 offs[2] = {0, T}, uoffs[2] = {0, (i64)u.size()};
+        AlignPlan ap;
+        if (align_plan(who, K, Ns.data(), offs, 1, u.data(), uoffs, o.data(), ln_switch, ap)) return 1;
+        std::vector<double> score((size_t)std::max<int64_t>(T, 1));
+        std::vector<int64_t> begin(u.size()), end(u.size());
+        double lp = 0.0;
+        int status = 0;
+        AlignOut out;
+        out.score = score.data(), out.begin = begin.data(), out.end = end.data(), out.log_prob = &lp, out.status = &status;
+        if (align_device(who, ap, fm.ms, lflats, stg.d_sym.get(), offs, 1, u.data(), uoffs, o.data(), ln_switch, st.s, out)) return 1;
+        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), fm.M);
+        if (status == 1)
+            return e2vq_set_error("%s: %lld frames cannot be aligned to the %zu units of %s (no path of probability > 0)", in.path.c_str(),
+                                  (long long)T, u.size(), label_filenames[f]);
+        if (e2vq_hmm_align_report(in.path.c_str(), T, K, fm.names.data(), W_ms, O_ms, (int)u.size(), u.data(), o.data(), begin.data(),
+                                  end.data(), score.data(), lp, ln_switch, in.csv.empty() ? nullptr : in.csv.c_str()))
+            return 1;
+    }
+    return 0;
+}

@@ -260,19 +260,6 @@ int scan_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, 
     return 0;
 }
 
-std::string fmt_17g(double v)
-{
-    char buf[64];
-    snprintf(buf, sizeof buf, "%.17g", v);
-    return buf;
-}
-
-bool ends_with(const std::string& s, const char* ext)
-{
-    const size_t n = strlen(ext);
-    return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
-}
-
 // ---- hmm segment: one Viterbi pass through the class loop of all models ------------------------------------
 thread_local float g_segment_kernel_ms = -1.f;  // e2vq_hmm_segment_last_kernel_ms
 
@@ -1399,6 +1386,43 @@ int transitions_from_counts(const char* who, int K, const std::vector<int64_t>& 
 
 }  // namespace
 
+// the labelled units of one file in their order (hmm_host.h): what `hmm transitions` counts and `hmm align` aligns to
+int e2hmm_host::read_label_file(const char* path, std::vector<LabelRow>& rows)
+{
+    std::vector<std::string> lines;
+    if (read_lines(path, lines)) return 1;
+    // the first line that is no '#' comment is the header: a segment CSV (column `class`) or a tab-separated selection table
+    size_t h = 0;
+    while (h < lines.size() && (lines[h].empty() || lines[h][0] == '#')) ++h;
+    if (h == lines.size()) return e2vq_set_error("%s: no header", path);
+    const bool table = lines[h].find('\t') != std::string::npos;
+    const std::vector<std::string> head = split_on(lines[h], table ? '\t' : ',');
+    auto column = [&](const char* name) { return (int)(std::find(head.begin(), head.end(), name) - head.begin()); };
+    const int ncol = (int)head.size();
+    const int c_label = column(table ? "Type" : "class"), c_time = table ? column("Begin Time (s)") : -1;
+    if (c_label == ncol || c_time == ncol)
+        return e2vq_set_error("%s:%zu: neither a segment CSV (column 'class') nor a selection table (tab-separated, 'Begin Time (s)' and 'Type')",
+                              path, h + 1);
+    std::vector<std::pair<double, LabelRow>> timed;  // (begin time or row number, label)
+    for (size_t l = h + 1; l < lines.size(); ++l) {
+        if (lines[l].empty() || lines[l][0] == '#') continue;
+        const std::vector<std::string> cells = split_on(lines[l], table ? '\t' : ',');
+        if ((int)cells.size() != ncol) return e2vq_set_error("%s:%zu: %zu fields, not %d", path, l + 1, cells.size(), ncol);
+        double at = (double)timed.size();
+        if (table) {
+            char* end = nullptr;
+            at = strtod(cells[(size_t)c_time].c_str(), &end);
+            if (cells[(size_t)c_time].empty() || *end || std::isnan(at))
+                return e2vq_set_error("%s:%zu: begin time '%s' is not a number", path, l + 1, cells[(size_t)c_time].c_str());
+        }
+        timed.emplace_back(at, LabelRow{cells[(size_t)c_label], l + 1});
+    }
+    std::stable_sort(timed.begin(), timed.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    rows.clear();
+    for (auto& r : timed) rows.push_back(std::move(r.second));
+    return 0;
+}
+
 extern "C" int e2vq_hmm_segment_trans_last_kernel_ms(float* ms)
 {
     if (!ms) return e2vq_set_error("e2vq_hmm_segment_trans_last_kernel_ms: bad arguments");
@@ -1536,39 +1560,12 @@ extern "C" int e2vq_hmm_transitions_files(const char* const* model_filenames, un
     for (int i = 0; i < num_inputs; ++i) {
         const char* path = input_filenames[i];
         if (!path) return e2vq_set_error("%s: NULL file name", who);
-        std::vector<std::string> lines;
-        if (read_lines(path, lines)) return 1;
-        // the first line that is no '#' comment is the header: a segment CSV (column `class`) or a tab-separated selection table
-        size_t h = 0;
-        while (h < lines.size() && (lines[h].empty() || lines[h][0] == '#')) ++h;
-        if (h == lines.size()) return e2vq_set_error("%s: no header", path);
-        const bool table = lines[h].find('\t') != std::string::npos;
-        const std::vector<std::string> head = split_on(lines[h], table ? '\t' : ',');
-        auto column = [&](const char* name) { return (int)(std::find(head.begin(), head.end(), name) - head.begin()); };
-        const int ncol = (int)head.size();
-        const int c_label = column(table ? "Type" : "class"), c_time = table ? column("Begin Time (s)") : -1;
-        if (c_label == ncol || c_time == ncol)
-            return e2vq_set_error("%s:%zu: neither a segment CSV (column 'class') nor a selection table (tab-separated, 'Begin Time (s)' and 'Type')",
-                                  path, h + 1);
-        std::vector<std::pair<double, std::string>> rows;  // (begin time or row number, label)
-        for (size_t l = h + 1; l < lines.size(); ++l) {
-            if (lines[l].empty() || lines[l][0] == '#') continue;
-            const std::vector<std::string> cells = split_on(lines[l], table ? '\t' : ',');
-            if ((int)cells.size() != ncol) return e2vq_set_error("%s:%zu: %zu fields, not %d", path, l + 1, cells.size(), ncol);
-            double at = (double)rows.size();
-            if (table) {
-                char* end = nullptr;
-                at = strtod(cells[(size_t)c_time].c_str(), &end);
-                if (cells[(size_t)c_time].empty() || *end || std::isnan(at))
-                    return e2vq_set_error("%s:%zu: begin time '%s' is not a number", path, l + 1, cells[(size_t)c_time].c_str());
-            }
-            rows.emplace_back(at, cells[(size_t)c_label]);
-        }
-        std::stable_sort(rows.begin(), rows.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        std::vector<LabelRow> rows;
+        if (read_label_file(path, rows)) return 1;
         int prev = -1;  // (a label that is no model's class is left out: its neighbours follow one another)
         for (const auto& r : rows) {
             int k = 0;
-            while (k < K && r.second != names[(size_t)k]) ++k;
+            while (k < K && r.label != names[(size_t)k]) ++k;
             if (k == K) {
                 ++skipped;
                 continue;

@@ -163,6 +163,55 @@ void launch_segment_trans_backtrack(const SegPlanDev& pl, const long long* offs,
                                     const int* status, unsigned short* cls, unsigned short* state, unsigned char* entered,
                                     double* exit_score, hipStream_t st);
 
+// Forced alignment to a known order of units (hmm_align.hip).  The units of one stream's transcript are
+// packed in unit order into wave-slots as the classes are above (unit l on N_{c_l} consecutive lanes of one slot; composite
+// index = the states of the units before it + j); the parameters stay per class: pl.params holds lpi (sumN of the classes) |
+// lA of every class (a_words) | lB (a row of M per class state), as launch_segment takes them.
+constexpr unsigned char ALIGN_ENTER_1 = 0xFE;  // psi: entered from the unit before
+constexpr unsigned char ALIGN_ENTER_2 = 0xFF;  // psi: entered from two units before, over an optional one
+constexpr int ALIGN_INIT = 1;   // lane flags: the unit may hold frame 0
+constexpr int ALIGN_PRED = 2;   //             the unit has a predecessor (l >= 1)
+constexpr int ALIGN_SKIP = 4;   //             the unit may be entered from l - 2 (l >= 2 and unit l - 1 is optional)
+constexpr int ALIGN_FINAL = 8;  //             the unit may hold the last frame
+struct AlignLaneDev {  // one lane of one slot; a lane without a state: unit = -1, j = N = row = a_at = flags = 0, seg = its own lane
+    int unit, j, N;
+    int seg;    // the lane of state 0 of the unit
+    int comp;   // composite index within the stream
+    int row;    // the state's row in the classes' lpi and lB
+    int a_at;   // lA of the unit's class at this many doubles into the lA area
+    int flags;
+};
+struct AlignStreamDev {  // one stream of a launch
+    long long lane_at;  // its lanes at lanes + lane_at ([slots][64]), its slot_info at slot_info + lane_at / 32
+    long long tab_at;   // its tables at tab + tab_at: psi (T x sumN bytes), then xs (T x L bytes)
+    long long unit_at;  // its units at [unit_at, unit_at + L) of begin / end / unit_comp0
+    long long comp_at;  // its states at [comp_at, comp_at + sumN) of comp_unit
+    int slots, L, sumN, pad;
+};
+struct AlignPlanDev {
+    int M, sumN_cls, a_words, max_L, max_sumN;  // max_*: the largest among the launch's streams (they size the LDS)
+    const AlignStreamDev* streams;       // [S] of the launch
+    const AlignLaneDev* lanes;
+    const int* slot_info;                // per slot: the largest N of the slot, 1 when the slot holds one unit
+    const double* params;
+    const unsigned short* comp_unit;     // composite index -> unit
+    const int* unit_comp0;               // unit -> composite index of its state 0
+};
+// dynamic LDS of k_hmm_align for such a launch
+size_t align_lds_bytes(int max_L, int max_sumN, int a_words, bool looped, bool a_lds);
+// whether a stream of L units and sumN states can be launched at all (lA left in global memory)
+inline bool align_fits_lds(int L, int sumN, bool looped) { return align_lds_bytes(L, sumN, 0, looped, false) <= SEG_LDS_BYTES; }
+// S streams (a workgroup of `waves` waves each) from offs[0] on; logp / qlast (composite index of q_{T-1}) / status at [s].
+// looped: the body that takes any number of slots; else waves >= the most slots of a stream.  Returns 1 when the shape cannot
+// be launched.
+int launch_align(const AlignPlanDev& pl, bool looped, int waves, const unsigned short* sym, const long long* offs, int S,
+                 double ln_switch, unsigned char* tab, double* logp, int* qlast, int* status, hipStream_t st);
+// unit / state / entered of each of the S streams (absolute frames) and begin / end of its units from what launch_align
+// left; a stream of status 2 gets 0xFFFF, 0xFFFF, 0, and -1 / -1 for every unit
+void launch_align_backtrack(const AlignPlanDev& pl, const long long* offs, int S, const unsigned char* tab, const int* qlast,
+                            const int* status, unsigned short* unit, unsigned short* state, unsigned char* entered,
+                            long long* begin, long long* end, hipStream_t st);
+
 // Smoothed class posteriors under the same class loop (hmm_posterior.hip), on the packing above with at
 // most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | e = sw pi (sumN) | A of every class with the leading dimension
 // N_k | 1 (lanes[].a_at and a_words count these padded words) | B (sumN rows of M).  S streams (a workgroup each) from

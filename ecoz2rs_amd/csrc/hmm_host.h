@@ -1,6 +1,6 @@
 // hmm_host.h -- what the host units of the HMM consumers share (hmm_model.cpp: models, files, sequences; hmm_train.cpp:
 // Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi, scan, segment, posteriors;
-// hmm_segment_stream.cpp: the streaming segment decoder).
+// hmm_segment_stream.cpp: the streaming segment decoder; hmm_align.cpp: forced alignment).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -234,6 +234,28 @@ struct SegPacking {
     std::vector<uint16_t> comp_cls;          // [sumN]
 };
 SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int));
+
+inline std::string fmt_17g(double v)
+{
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+inline bool ends_with(const std::string& s, const char* ext)
+{
+    const size_t n = strlen(ext);
+    return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
+}
+
+// The labelled units of one file, in their order: a segment CSV (column `class`, in row order) or a tab-separated selection
+// table (column `Type`, sorted by `Begin Time (s)`; equal times keep their row order).  The first line that is no '#'
+// comment is the header.  `hmm transitions` counts their successions, `hmm align` aligns to them.
+struct LabelRow {
+    std::string label;
+    size_t line;  // of the file, from 1
+};
+int read_label_file(const char* path, std::vector<LabelRow>& rows);
 
 // input -> device symbols: the stage `hmm scan` and `hmm segment` share
 struct SymInput {

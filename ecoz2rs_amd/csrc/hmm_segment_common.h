@@ -1,6 +1,6 @@
 // hmm_segment_common.h -- device helpers the forward kernels of `hmm segment` share (hmm_segment.hip: a closed stream;
-// hmm_segment_stream.hip: one block of an open one): the pair a wave posts per step, reads of d from another lane, and the
-// workgroup's (value, index) maximum.  Device code only.  Internal.
+// hmm_segment_stream.hip: one block of an open one) and of `hmm align` (hmm_align.hip) share: the pair a wave posts per step,
+// reads of d from another lane, and the workgroup's (value, index) maximum.  Device code only.  Internal.
 #pragma once
 #include "hmm_device.h"
 

@@ -102,6 +102,15 @@ _sig("e2vq_hmm_segment_stream_stats", C.c_int, C.c_void_p, C.POINTER(C.c_int64),
 _sig("e2vq_hmm_segment_stream_free", None, C.c_void_p)
 _sig("e2vq_hmm_segment_continuous_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_double, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_align", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_align_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_align_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_char_p)
+_sig("e2vq_hmm_align_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_double, C.c_char_p, C.c_char_p)
+
 
 def _strs(items):
     arr = (C.c_char_p * len(items))(*[str(p).encode() for p in items])
@@ -739,3 +748,87 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
     check(lib.e2vq_hmm_segment_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                      len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
                                      str(csv).encode() if csv else None))
+
+
+def units_of(units, begin, end, score, ln_switch):
+    """the unit table of one aligned stream from its outputs (host arithmetic): a list of dicts unit, cls,
+    begin, end (exclusive), score for the units the path visits -- the unit [b, e) scores
+    score[e - 1] - (0 if b == 0 else score[b - 1] + ln_switch)"""
+    out = []
+    ls = np.float64(ln_switch)
+    for l, (k, b, e) in enumerate(zip(units, begin, end)):
+        if b < 0:
+            continue
+        with np.errstate(invalid="ignore"):
+            lo = np.float64(0.0) if b == 0 else np.float64(score[b - 1]) + ls
+            out.append(dict(unit=l, cls=int(k), begin=int(b), end=int(e), score=float(np.float64(score[e - 1]) - lo)))
+    return out
+
+
+def align(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, device=0):
+    """forced alignment of whole symbol streams to the known order of their units: models = [(pi, A, B)]
+    sharing M, each of at most 64 states; sym, offs as `segment` takes them (numpy, or a device tensor); units: class indices,
+    the transcript of stream s at units[unit_offs[s]:unit_offs[s + 1]]; optional: a flag per unit (a path may pass over it);
+    ln_switch <= 0, finite: the log of the price of a unit boundary.  -> dict: per frame unit / state (uint16), entered
+    (uint8), score; per unit begin / end (int64, -1 where the path does not visit it); per stream log_prob, status; and
+    units = per stream the list `units_of` gives"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    unit_offs = np.ascontiguousarray(unit_offs, dtype=np.int64)
+    S = len(offs) - 1
+    if len(unit_offs) != S + 1:
+        raise ValueError(f"unit_offs has {len(unit_offs)} entries for {S} streams")
+    units = np.ascontiguousarray(units, dtype=np.int32)
+    if optional is not None:
+        optional = np.ascontiguousarray(np.asarray(optional) != 0, dtype=np.uint8)
+    nu = int(unit_offs[-1]) if len(unit_offs) else 0
+    if len(units) < nu or (optional is not None and len(optional) < nu):
+        raise ValueError(f"unit_offs ends at {nu}: more than the units given")
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    n = max(int(offs[-1]), 1)
+    unit, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
+    entered, score = np.zeros(n, dtype=np.uint8), np.zeros(n)
+    begin, end = np.full(max(nu, 1), -1, dtype=np.int64), np.full(max(nu, 1), -1, dtype=np.int64)
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_align(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
+                             unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None, float(ln_switch),
+                             unit.ctypes.data, state.ctypes.data, entered.ctypes.data, score.ctypes.data, begin.ctypes.data,
+                             end.ctypes.data, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    T = int(offs[-1])
+    out = dict(unit=unit[:T], state=state[:T], entered=entered[:T], score=score[:T], begin=begin[:nu], end=end[:nu], log_prob=lp[:S],
+               status=st[:S])
+    out["units"] = [units_of(units[ua:ub], begin[ua:ub], end[ua:ub], out["score"][a:b], ln_switch)
+                    for a, b, ua, ub in zip(offs[:-1], offs[1:], unit_offs[:-1], unit_offs[1:])]
+    return out
+
+
+def align_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_align_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def align_files(model_filenames, input_filenames, label_filenames, ln_switch=0.0, filler=None, codebook=None, P=36, W_ms=45, O_ms=15,
+                csv=None):
+    """`hmm align`: input i (.wav, .prd or .seq) aligned to the units label file i names (a segment CSV or a
+    selection table, as `hmm transitions` reads them); filler: the class of a model inserted as an optional unit around and
+    between them; per input a block on stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the units"""
+    if len(label_filenames) != len(input_filenames):
+        raise ValueError(f"{len(label_filenames)} label files for {len(input_filenames)} inputs")
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    l, _k3 = _strs(label_filenames)
+    check(lib.e2vq_hmm_align_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l, len(input_filenames),
+                                   int(P), int(W_ms), int(O_ms), float(ln_switch), str(filler).encode() if filler else None,
+                                   str(csv).encode() if csv else None))

@@ -460,6 +460,67 @@ int e2vq_hmm_segment_continuous_files(const char *const *model_filenames, unsign
                                       const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
                                       double ln_switch, const char *name, const char *csv_dir_or_file);
 
+/* ---- forced alignment to a known order of units ----------------------------------------------------------
+ * `hmm align`: where are the boundaries of units whose classes and order are known?  K models sharing M (the checks of
+ * e2vq_hmm_segment), S symbol streams (sym, offs), and for stream s a transcript of L_s >= 1 units: units[unit_offs[s] ..
+ * unit_offs[s + 1]) are class indices in [0, K), repeats allowed, the same class twice in a row included; optional (u8 a
+ * unit, may be NULL = none) marks units a path may pass over; ln_switch <= 0, finite, is the price of every unit boundary.
+ * The composite states of a stream are (l, j), l < L, j < N_{c_l}, in unit order.  All arithmetic is in the log domain on
+ * the logarithms e2vq_hmm_viterbi takes; every step is additions and comparisons only, values are finite or -inf, so no
+ * NaN can arise.
+ *   Frame 0.  d_0(l, j) = lpi_{c_l}[j] + lB_{c_l}[j][o_0] for l = 0, and also for l = 1 when unit 0 is optional; else -inf.
+ *   Step t > 0, in-class part: e2vq_hmm_segment's chain, best = max_i d_{t-1}(l, i) + lA[i][j], the lowest i wins ties.
+ *   Exit of a unit: E_t[l] = max_i d_{t-1}(l, i), x_t[l] the lowest state reaching it.
+ *   Entry into unit l >= 1: e = E_t[l-1], src = l - 1; when unit l - 1 is optional and l >= 2, src = l - 2 and e = E_t[l-2]
+ *   if that is strictly greater.  base = e + ln_switch; the state is entered when base + lpi[j] is strictly greater than
+ *   the in-class best (the addition order of e2vq_hmm_segment).  d_t = best + lB.
+ *   End: the maximum of d_{T-1} over the states of unit L - 1, and of unit L - 2 as well when unit L - 1 is optional; the
+ *   lowest composite index wins.
+ * Status 0; 1 with ln P* = -inf when that maximum is -inf (T smaller than the number of mandatory units is the plain
+ * case): the path is still what the back-pointers give by the same rules, and need then not start in an initial unit; 2 for
+ * a symbol >= M: ln P* = -inf, unit = state = 0xFFFF, entered = 0, score = 0.0 at frame 0 and -inf after it, every unit
+ * -1 / -1.  An empty stream: status 0, ln P* = 0.0, every unit -1 / -1.
+ * Outputs.  Per frame: unit (index into the stream's transcript), state, entered (1 at frame 0 and where the path enters a
+ * unit), score = the path's own cumulative score at that frame.  Per unit (at unit_offs): begin, end, the frame range
+ * [begin, end) relative to the stream's first frame, -1 / -1 for a unit the path does not visit.  Per stream: log_prob,
+ * status.  Any output may be NULL.
+ * score is no device table: once the path is known the host replays it, one addition per term in the device's order -- an
+ * entry is ((score[t-1] + ln_switch) + lpi) + lB, an in-class step (score[t-1] + lA) + lB, frame 0 lpi + lB (-inf where
+ * the unit of frame 0 may not hold it) -- and score[T-1] must equal the device's ln P* on the bits, else an internal error
+ * is returned.  The unit [b, e) scores score[e-1] - (b == 0 ? 0 : score[b-1] + ln_switch).
+ * With L = 1 every output is e2vq_hmm_viterbi's of that model, bit for bit.
+ * Layout: a workgroup per stream; the units are packed in unit order into wave-slots of 64 lanes (N consecutive lanes a
+ * unit, never across a slot).  Up to 16 slots each wave keeps its d in a register; beyond (or with
+ * ECOZ2_HMM_ALIGN_BODY=looped; =resident asks for the first) the waves loop over the slots with d in LDS.  Back-pointers
+ * take sum N + L bytes a frame; ECOZ2_HMM_ALIGN_TABLE_BYTES (default 4 GiB) bounds a launch, streams are launched in
+ * groups that fit.
+ * Refused before any HIP call: what e2vq_hmm_segment refuses; an empty transcript; a unit outside [0, K); two adjacent
+ * optional units; a transcript whose units are all optional; L > 65535; ln_switch > 0, NaN or -inf; a stream whose tables
+ * exceed the budget (the message names the variable and the bytes); a packing that does not fit in LDS (the message names
+ * sum N). */
+int e2vq_hmm_align(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                   const double *const *Bs, const void *sym, const int64_t *offs, int S, const int32_t *units,
+                   const int64_t *unit_offs, const uint8_t *optional, double ln_switch, uint16_t *unit, uint16_t *state,
+                   uint8_t *entered, double *score, int64_t *begin, int64_t *end, double *log_prob, int *status,
+                   int sym_on_device);
+/* HIP-event time of the kernels (forward + backtrack) of this thread's last alignment (-1: none yet) */
+int e2vq_hmm_align_last_kernel_ms(float *ms);
+/* Report of one aligned stream (host only): a block on stdout and, with csv_filename, a CSV with one row per visited unit:
+ * unit,class,begin_frame,end_frame,begin_s,end_s,score -- the time arithmetic and number formats of
+ * e2vq_hmm_segment_report, score as defined above.  units / optional / begin / end: the stream's L entries; score: its T.
+ * A unit the path passed over is left out of the CSV and counted in the block. */
+int e2vq_hmm_align_report(const char *name, int64_t T, int K, const char *const *class_names, int W_ms, int O_ms, int L,
+                          const int32_t *units, const uint8_t *optional, const int64_t *begin, const int64_t *end,
+                          const double *score, double log_prob, double ln_switch, const char *csv_filename);
+/* `hmm align`: input i (.wav, .prd or .seq, staged as e2vq_hmm_segment_files stages them) aligned to the transcript in
+ * label file i -- a segment CSV (column `class`) or a tab-separated selection table (`Type`, ordered by `Begin Time (s)`),
+ * as `hmm transitions` reads them; a label that is no model's class is refused with file and line.  filler_class (may be
+ * NULL) names a model that is inserted as an optional unit before the first unit, between every two, and after the last.
+ * csv_dir_or_file as e2vq_hmm_segment_files takes it.  Everything is checked before any HIP call. */
+int e2vq_hmm_align_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                         const char *const *input_filenames, const char *const *label_filenames, int num_inputs, int P, int W_ms,
+                         int O_ms, double ln_switch, const char *filler_class, const char *csv_dir_or_file);
+
 #ifdef __cplusplus
 }
 #endif
