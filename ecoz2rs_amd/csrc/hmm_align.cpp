@@ -1,7 +1,8 @@
 // hmm_align.cpp -- forced alignment on the GPU (`hmm align`, e2vq_hmm_align): the most likely path of a
 // symbol stream through the units of its transcript, in their order, over the kernels of hmm_align.hip.  The host checks
 // the transcripts and packs each stream's units into wave-slots (all before any HIP call), cuts the launches by the table
-// budget, replays the decoded path for its per-frame score, and writes the reports.
+// budget, replays the decoded path for its per-frame score, and writes the reports.  Shape checks, models, packing and the
+// parameter block are hmm_class_loop.cpp's, the input stage and the label files hmm_input.cpp's (hmm_host.h).
 #include "hmm_host.h"
 
 namespace e2hmm_host {
@@ -36,6 +37,7 @@ struct AlignPlan {
     };
     std::vector<Launch> launches;
     i64 max_bytes = 0;
+    SegPacking cls;  // the classes: their rows in the parameter block (comp0, a_at, sumN, a_words)
 };
 
 // may unit l hold frame 0 / the last frame (opt: the stream's flags, or null)
@@ -50,19 +52,11 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
     if (segment_check_switch(who, ln_switch)) return 1;
     if (std::isinf(ln_switch)) return e2vq_set_error("%s: ln_switch = %g: a finite price (every unit has to be entered)", who, ln_switch);
     if (unit_offs[0] != 0) return e2vq_set_error("%s: unit_offs[0] = %lld, not 0", who, (long long)unit_offs[0]);
-    const char* body = getenv("ECOZ2_HMM_ALIGN_BODY");
-    if (body && *body && strcmp(body, "resident") != 0 && strcmp(body, "looped") != 0)
-        return e2vq_set_error("ECOZ2_HMM_ALIGN_BODY=%s: resident or looped", body);
-    const bool force_looped = body && strcmp(body, "looped") == 0;
+    bool force_looped = false;
+    if (loop_body_looped("ECOZ2_HMM_ALIGN_BODY", 0, &force_looped)) return 1;
     const i64 budget = env_bytes("ECOZ2_HMM_ALIGN_TABLE_BYTES", (i64)4 << 30);
-    std::vector<int> cls_comp0((size_t)K), cls_a_at((size_t)K);
-    int a_words = 0;
-    for (int k = 0, c = 0; k < K; ++k) {
-        cls_comp0[(size_t)k] = c;
-        cls_a_at[(size_t)k] = a_words;
-        c += Ns[k];
-        a_words += Ns[k] * Ns[k];
-    }
+    ap.cls = pack_slots(std::vector<int>(Ns, Ns + K));
+    const SegPacking& cls = ap.cls;
     std::vector<bool> looped((size_t)S);
     std::vector<i64> bytes((size_t)S);
     ap.streams.resize((size_t)S);
@@ -89,7 +83,7 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
         if (!e2hmm::align_fits_lds(L, (int)sumN, false))
             return e2vq_set_error("%s: stream %d: %d units of sum N = %lld states do not fit in LDS (%zu of %zu bytes)", who, s, L,
                                   (long long)sumN, e2hmm::align_lds_bytes(L, (int)sumN, 0, false, false), e2hmm::SEG_LDS_BYTES);
-        const SegPacking pk = pack_slots(uN, [](int N) { return N; });
+        const SegPacking pk = pack_slots(uN);
         looped[(size_t)s] = force_looped || pk.slots > e2hmm::SEG_MAX_WAVES;
         if (looped[(size_t)s] && !e2hmm::align_fits_lds(L, pk.sumN, true))
             return e2vq_set_error("%s: stream %d: %d units of sum N = %d states in %d wave-slots do not fit in LDS (%zu of %zu bytes)", who,
@@ -112,7 +106,7 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
                 const int l = sl.cls, k = u[l];
                 const int flags = (unit_is_initial(l, opt) ? e2hmm::ALIGN_INIT : 0) | (l >= 1 ? e2hmm::ALIGN_PRED : 0) |
                                   (l >= 2 && opt && opt[l - 1] ? e2hmm::ALIGN_SKIP : 0) | (unit_is_final(l, L, opt) ? e2hmm::ALIGN_FINAL : 0);
-                al = e2hmm::AlignLaneDev{l, sl.j, sl.N, sl.seg, sl.comp, cls_comp0[(size_t)k] + sl.j, cls_a_at[(size_t)k], flags};
+                al = e2hmm::AlignLaneDev{l, sl.j, sl.N, sl.seg, sl.comp, cls.comp0[(size_t)k] + sl.j, cls.a_at[(size_t)k], flags};
             }
             ap.lanes.push_back(al);
         }
@@ -144,15 +138,14 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
 }
 
 // the path's own cumulative score, frame by frame, from the decoded path: one addition per term in the device's order
-void align_replay(const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats, const uint16_t* sym, i64 T,
-                  const int32_t* units, const uint8_t* opt, double ln_switch, const uint16_t* unit, const uint16_t* state,
-                  const uint8_t* entered, double* score)
+void align_replay(const LoopModels& lm, const uint16_t* sym, i64 T, const int32_t* units, const uint8_t* opt, double ln_switch,
+                  const uint16_t* unit, const uint16_t* state, const uint8_t* entered, double* score)
 {
-    const int M = ms[0]->M;
+    const int M = lm.M;
     for (i64 t = 0; t < T; ++t) {
         const int l = unit[t], j = state[t], k = units[l];
-        const size_t N = (size_t)ms[(size_t)k]->N;
-        const double* lf = lflats[(size_t)k].data();
+        const size_t N = (size_t)lm.Ns[(size_t)k];
+        const double* lf = lm.lflats[(size_t)k].data();
         const double lpi = lf[j], lB = lf[N + N * N + (size_t)j * M + sym[t]];
         if (t == 0) score[0] = unit_is_initial(l, opt) ? lpi + lB : -INFINITY;
         else if (entered[t]) score[t] = ((score[t - 1] + ln_switch) + lpi) + lB;
@@ -161,24 +154,12 @@ void align_replay(const std::vector<const Hmm*>& ms, const std::vector<std::vect
 }
 
 // The alignment of S device-resident streams (h_offs: their S + 1 offsets, on the host) to their transcripts under the
-// models (all of one M; lflats: log_model of each), as planned by align_plan, on the current device and the stream st.
-int align_device(const char* who, const AlignPlan& ap, const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats,
-                 const unsigned short* d_sym, const i64* h_offs, int S, const int32_t* units, const i64* unit_offs,
-                 const uint8_t* optional, double ln_switch, hipStream_t st, const AlignOut& out)
+// models (all of one M, with their logarithms), as planned by align_plan, on the current device and the stream st.
+int align_device(const char* who, const AlignPlan& ap, const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S,
+                 const int32_t* units, const i64* unit_offs, const uint8_t* optional, double ln_switch, hipStream_t st, const AlignOut& out)
 {
-    const int K = (int)ms.size(), M = ms[0]->M;
-    int sumN = 0, a_words = 0;
-    for (const Hmm* h : ms) sumN += h->N, a_words += h->N * h->N;
-    // logarithms: lpi of every class | lA of every class | lB of every class
-    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M);
-    for (int k = 0, c = 0, a = 0; k < K; ++k) {
-        const std::vector<double>& lflat = lflats[(size_t)k];
-        const size_t N = (size_t)ms[(size_t)k]->N;
-        std::copy(lflat.begin(), lflat.begin() + N, params.begin() + c);
-        std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + a);
-        std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + a_words + (size_t)c * M);
-        c += (int)N, a += (int)(N * N);
-    }
+    const int M = lm.M, sumN = ap.cls.sumN, a_words = ap.cls.a_words;
+    const std::vector<double> params = loop_log_params(lm, ap.cls);
     const i64 frames = h_offs[S], nunits = unit_offs[S];
     DeviceBuffer<double> d_params, d_logp;
     DeviceBuffer<e2hmm::AlignLaneDev> d_lanes;
@@ -247,7 +228,7 @@ int align_device(const char* who, const AlignPlan& ap, const std::vector<const H
             sc[0] = 0.0;
             continue;
         }
-        align_replay(ms, lflats, h_sym.data() + a, T, units + unit_offs[s], optional ? optional + unit_offs[s] : nullptr, ln_switch,
+        align_replay(lm, h_sym.data() + a, T, units + unit_offs[s], optional ? optional + unit_offs[s] : nullptr, ln_switch,
                      h_unit.data() + a, h_state.data() + a, h_entered.data() + a, sc);
         if (memcmp(&sc[T - 1], &h_logp[(size_t)s], 8) != 0)
             return e2vq_set_error("%s: internal error: stream %d: the replayed path scores %.17g, the device found %.17g", who, s, sc[T - 1],
@@ -268,12 +249,7 @@ int align_device(const char* who, const AlignPlan& ap, const std::vector<const H
 }  // namespace e2hmm_host
 using namespace e2hmm_host;
 
-extern "C" int e2vq_hmm_align_last_kernel_ms(float* ms)
-{
-    if (!ms) return e2vq_set_error("e2vq_hmm_align_last_kernel_ms: bad arguments");
-    *ms = g_align_kernel_ms;
-    return 0;
-}
+extern "C" int e2vq_hmm_align_last_kernel_ms(float* ms) { return last_kernel_ms("e2vq_hmm_align_last_kernel_ms", g_align_kernel_ms, ms); }
 
 extern "C" int e2vq_hmm_align(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
                               const double* const* Bs, const void* sym, const int64_t* offs, int S, const int32_t* units,
@@ -282,27 +258,18 @@ extern "C" int e2vq_hmm_align(int device, int K, const int* Ns, int M, const dou
                               int sym_on_device)
 {
     const char* who = "e2vq_hmm_align";
-    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
-    if (!Ns || !pis || !As || !Bs || S < 0 || !offs || !unit_offs || (S > 0 && !units) || (!sym && S > 0 && offs[S] > 0))
-        return e2vq_set_error("%s: bad arguments", who);
-    if (segment_check_shape(who, K, Ns)) return 1;
-    std::vector<Hmm> models;
-    std::vector<const Hmm*> ms;
-    std::vector<std::vector<double>> lflats((size_t)K);
-    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms)) return 1;
-    for (int k = 0; k < K; ++k)
-        if (log_model(models[(size_t)k], lflats[(size_t)k])) return 1;
-    if (check_offsets(offs, S)) return 1;
+    LoopModels lm;
+    if (loop_check_args(who, K, Ns, pis, As, Bs, offs && unit_offs && (S <= 0 || units) && syms_given(sym, offs, S)) ||
+        segment_check_shape(who, K, Ns) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs() || check_offsets(offs, S))
+        return 1;
     AlignPlan ap;
     if (align_plan(who, K, Ns, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, ap)) return 1;
     // ---- the device from here on --------------------------------------------------------------------------------
     if (require_device(device)) return 1;
     DevSeqs seqs;
     if (seqs.symbols(sym, (size_t)offs[S], sym_on_device != 0)) return 1;
-    AlignOut out;
-    out.unit = unit, out.state = state, out.entered = entered, out.score = score, out.begin = begin, out.end = end;
-    out.log_prob = log_prob, out.status = status;
-    return align_device(who, ap, ms, lflats, seqs.sym, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, seqs.st.s, out);
+    const AlignOut out{unit, state, entered, score, begin, end, log_prob, status};
+    return align_device(who, ap, lm, seqs.sym, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, seqs.st.s, out);
 }
 
 extern "C" int e2vq_hmm_align_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms, int L,
@@ -353,15 +320,12 @@ extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned
 {
     const char* who = "e2vq_hmm_align_files";
     FlushStdout flush_on_return;
-    if (!model_filenames || num_models < 1) return e2vq_set_error("%s: no models", who);
-    if (!input_filenames || !label_filenames || num_inputs < 1) return e2vq_set_error("%s: no inputs", who);
-    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms);
-    FilesModels fm;
-    if (fm.load(model_filenames, num_models)) return 1;
-    const int K = (int)num_models;
-    std::vector<int> Ns;
-    for (const Hmm& h : fm.models) Ns.push_back(h.N);
-    if (segment_check_shape(who, K, Ns.data())) return 1;
+    LoopModels fm;
+    if (files_given(who, model_filenames, num_models, input_filenames && label_filenames && num_inputs >= 1) ||
+        window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models))
+        return 1;
+    const int K = fm.K();
+    const std::vector<int>& Ns = fm.Ns;
     auto class_of = [&](const std::string& name) {
         int k = 0;
         while (k < K && name != fm.names[(size_t)k]) ++k;
@@ -370,9 +334,7 @@ extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned
     int filler = -1;
     if (filler_class && *filler_class && (filler = class_of(filler_class)) < 0)
         return e2vq_set_error("%s: the filler '%s' is no model's class", who, filler_class);
-    std::vector<std::vector<double>> lflats((size_t)num_models);
-    for (unsigned k = 0; k < num_models; ++k)
-        if (log_model(fm.models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    if (fm.logs(model_filenames)) return 1;
     SymInputs si;
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, si)) return 1;
     // the transcripts: the labels of file i in their order, the filler around and between them
@@ -404,21 +366,14 @@ extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned
     }
     // ---- the device from here on --------------------------------------------------------------------------------
     const int device = env_device();
-    if (require_device(device)) return 1;
     SymStage stg;
-    Stream st;
-    if (st.create()) return 1;
-    VqSessionHolder vq;
-    if (si.need_cb) {
-        if (e2vq_session_create(device, si.cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, si.refl.data(), si.cbM))
-            return 1;
-    }
+    if (require_device(device) || stg.open(device, si)) return 1;
     for (int f = 0; f < num_inputs; ++f) {
         const SymInput& in = si.inputs[(size_t)f];
         const std::vector<int32_t>& u = units[(size_t)f];
         const std::vector<uint8_t>& o = optional[(size_t)f];
         int64_t T = 0;
-        if (sym_input_to_device(in, si, stg, vq.s, device, P, W_ms, O_ms, st.s, &T)) return 1;
+        if (stg.input(in, si, P, W_ms, O_ms, &T)) return 1;
         const i64 offs[2] = {0, T}, uoffs[2] = {0, (i64)u.size()};
         AlignPlan ap;
         if (align_plan(who, K, Ns.data(), offs, 1, u.data(), uoffs, o.data(), ln_switch, ap)) return 1;
@@ -428,7 +383,7 @@ extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned
         int status = 0;
         AlignOut out;
         out.score = score.data(), out.begin = begin.data(), out.end = end.data(), out.log_prob = &lp, out.status = &status;
-        if (align_device(who, ap, fm.ms, lflats, stg.d_sym.get(), offs, 1, u.data(), uoffs, o.data(), ln_switch, st.s, out)) return 1;
+        if (align_device(who, ap, fm, stg.d_sym.get(), offs, 1, u.data(), uoffs, o.data(), ln_switch, stg.st.s, out)) return 1;
         if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), fm.M);
         if (status == 1)
             return e2vq_set_error("%s: %lld frames cannot be aligned to the %zu units of %s (no path of probability > 0)", in.path.c_str(),

@@ -1,6 +1,8 @@
 // hmm_host.h -- what the host units of the HMM consumers share (hmm_model.cpp: models, files, sequences; hmm_train.cpp:
-// Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi, scan, segment, posteriors;
-// hmm_segment_stream.cpp: the streaming segment decoder; hmm_align.cpp: forced alignment).
+// Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi and scan;
+// hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices; hmm_transitions.cpp: the file and the estimator
+// of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
+// decoder; hmm_align.cpp: forced alignment).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -23,6 +25,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -127,6 +130,11 @@ struct DevSeqs {
         sym = on_device ? (const unsigned short*)src : d_sym.get();
         return 0;
     }
+    // for an array-level entry point: the offsets checked and the device made current, then symbols()
+    int open(int device, const void* src, const int64_t* offs, int S, bool on_device)
+    {
+        return check_offsets(offs, S) || require_device(device) || symbols(src, (size_t)offs[S], on_device);
+    }
     // S whole sequences
     int upload(const uint16_t* src, const i64* offs, int S) { return symbols(src, (size_t)offs[S]) || d_offs.upload(offs, (size_t)S + 1, st.s); }
     // the sequences [s0, s1) of a set
@@ -218,76 +226,37 @@ struct DevModels {  // a set of models on the device
 // scores of S device-resident sequences under K models: sc[s * K + k]
 int score_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* d_offs, int S, hipStream_t st, Scores& sc);
 
-// ---- decoding (hmm_decode.cpp): what the streaming decoder (hmm_segment_stream.cpp) shares with `hmm segment` ---------
-// the shapes and the price the class loop takes (`who`: the entry point named in the message)
-int segment_check_shape(const char* who, int K, const int* Ns);
-int segment_check_switch(const char* who, double ln_switch);
+// ---- decoding: what hmm_decode.cpp, hmm_class_loop.cpp, hmm_segment_stream.cpp and hmm_align.cpp share -----------------
+// The launches of a decoder whose table takes `row` bytes a frame: whole sequences [s0, s1) up to the budget of the
+// environment variable `env` (default 256 MiB), a longer sequence alone; *max_frames: the most frames of a launch
+// (hmm_decode.cpp)
+std::vector<std::pair<int, int>> plan_chunks(const char* env, i64 row, const i64* hoffs, int S, i64* max_frames);
 
-// The packing of the classes into wave-slots of 64 lanes that `hmm segment` and its posteriors share: class after class, a
-// class that does not fit the open slot opens the next.  a_ld(N): the leading dimension of a class's A in the device block
-// (a_at / a_words count N x a_ld(N) words a class).
-struct SegPacking {
-    int sumN = 0, a_words = 0, slots = 0;
-    std::vector<int> comp0, a_at;            // [K]: composite index of state 0, offset of A
-    std::vector<int> slot_info;              // [slots][2]: the largest N of the slot, 1 when the slot holds one class
-    std::vector<e2hmm::SegLaneDev> lanes;    // [slots][64]
-    std::vector<uint16_t> comp_cls;          // [sumN]
-};
-SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int));
-
-inline std::string fmt_17g(double v)
+// the body of every e2vq_*_last_kernel_ms export
+inline int last_kernel_ms(const char* who, float value, float* ms)
 {
-    char buf[64];
-    snprintf(buf, sizeof buf, "%.17g", v);
-    return buf;
+    if (!ms) return e2vq_set_error("%s: bad arguments", who);
+    *ms = value;
+    return 0;
 }
 
-inline bool ends_with(const std::string& s, const char* ext)
+// the first refusals of an array-level entry point over K models (scan and the class loop): K >= 1, then the arrays (`rest`: the entry point's own pointers and counts)
+int loop_check_args(const char* who, int K, const int* Ns, const double* const* pis, const double* const* As, const double* const* Bs,
+                    bool rest);
+// S >= 0, and symbols wherever the offsets count any
+inline bool syms_given(const void* sym, const int64_t* offs, int S) { return S >= 0 && !(!sym && S > 0 && offs && offs[S] > 0); }
+
+// the refusals every file form opens with, and the one of its frame geometry
+inline int files_given(const char* who, const void* models, unsigned num_models, bool inputs)
 {
-    const size_t n = strlen(ext);
-    return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
+    if (!models || num_models < 1) return e2vq_set_error("%s: no models", who);
+    if (!inputs) return e2vq_set_error("%s: no inputs", who);
+    return 0;
 }
-
-// The labelled units of one file, in their order: a segment CSV (column `class`, in row order) or a tab-separated selection
-// table (column `Type`, sorted by `Begin Time (s)`; equal times keep their row order).  The first line that is no '#'
-// comment is the header.  `hmm transitions` counts their successions, `hmm align` aligns to them.
-struct LabelRow {
-    std::string label;
-    size_t line;  // of the file, from 1
-};
-int read_label_file(const char* path, std::vector<LabelRow>& rows);
-
-// input -> device symbols: the stage `hmm scan` and `hmm segment` share
-struct SymInput {
-    std::string path, csv;
-    int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
-    int sample_rate = 0;
-    int64_t samples = 0, T = 0;
-};
-struct SymInputs {
-    bool have_cb = false, need_cb = false;
-    int cbP = 0, cbM = 0;
-    std::vector<double> refl;
-    std::vector<SymInput> inputs;
-};
-struct SymStage {  // device buffers the inputs of one call reuse; symbols of the current input in d_sym
-    DeviceBuffer<double> d_frames;
-    DeviceBuffer<int32_t> d_status;
-    DeviceBuffer<unsigned short> d_sym;
-};
-struct VqSessionHolder {
-    e2vq_session* s = nullptr;
-    ~VqSessionHolder()
-    {
-        if (s) e2vq_session_destroy(s);
-    }
-};
-// the checks of the inputs against the models' M and the codebook, and the codebook itself: host only, no file written
-int sym_inputs_check(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs, int P,
-                     int W_ms, int O_ms, const char* csv_dir_or_file, SymInputs& si);
-// one input to symbols in stg.d_sym (read and uploaded once; frames and symbols stay on the device): *T_out of them
-int sym_input_to_device(const SymInput& in, const SymInputs& si, SymStage& stg, e2vq_session* vq, int device, int P, int W_ms,
-                        int O_ms, hipStream_t st, int64_t* T_out);
+inline int window_ms_ok(const char* who, int W_ms, int O_ms)
+{
+    return W_ms < 1 || O_ms < 1 ? e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms) : 0;
+}
 
 // The models of `hmm scan` / `hmm segment`: loaded, all of one M
 struct FilesModels {
@@ -307,5 +276,132 @@ struct FilesModels {
         return 0;
     }
 };
+
+// ---- the class loop (hmm_class_loop.cpp): what `hmm segment` in all its forms and `hmm align` share ---------------------
+// the shapes and the price the class loop takes (`who`: the entry point named in the message)
+int segment_check_shape(const char* who, int K, const int* Ns);
+int segment_check_switch(const char* who, double ln_switch);
+
+// The models of a class-loop call, all of one M, from the caller's arrays or from files (then with `names`): their N and,
+// once logs() has run, log_model of each.  The checks between these steps stay with the entry point, in its own order.
+struct LoopModels : FilesModels {
+    std::vector<int> Ns;
+    std::vector<std::vector<double>> lflats;
+    int K() const { return (int)ms.size(); }
+    int from_arrays(int K, const int* Ns, int M, const double* const* pis, const double* const* As, const double* const* Bs);
+    int load_checked(const char* who, const char* const* files, unsigned n);  // load(), then segment_check_shape
+    int logs(const char* const* files = nullptr);  // files: a failure is prefixed with the model's file name
+};
+
+// The packing of the classes into wave-slots of 64 lanes that the class-loop decoders share: class after class, a class
+// that does not fit the open slot opens the next.  a_ld(N): the leading dimension of a class's A in the device block
+// (a_at / a_words count N x a_ld(N) words a class).
+struct SegPacking {
+    int sumN = 0, a_words = 0, slots = 0;
+    std::vector<int> comp0, a_at;            // [K]: composite index of state 0, offset of A
+    std::vector<int> slot_info;              // [slots][2]: the largest N of the slot, 1 when the slot holds one class
+    std::vector<e2hmm::SegLaneDev> lanes;    // [slots][64]
+    std::vector<uint16_t> comp_cls;          // [sumN]
+};
+inline int a_ld_dense(int N) { return N; }  // A as N x N
+SegPacking pack_slots(const std::vector<int>& Ns, int (*a_ld)(int) = a_ld_dense);
+
+// the logarithms as the Viterbi kernels of the class loop read them: lpi of every class | lA of every class | lB of every
+// class, each class at its place in `pk` (a packing of the classes with a_ld(N) = N)
+std::vector<double> loop_log_params(const LoopModels& lm, const SegPacking& pk);
+// the body of a class-loop kernel: looped where `slots` exceed a workgroup's waves or the variable `env_name` says
+// "looped" (slots = 0: whether it says so); a value other than "resident" or "looped" is refused
+int loop_body_looped(const char* env_name, int slots, bool* looped);
+
+// A packing on the device: the parameter block, the four tables of `pk`, and the plan the kernels take.  upload() only
+// enqueues: the host vectors must outlive the stream's copies, and this struct the stream's kernels (a local is declared
+// before the DevSeqs / Stream whose stream works on it, or the function waits for that stream before it returns).
+struct ClassLoopDev {
+    DeviceBuffer<double> params;
+    DeviceBuffer<e2hmm::SegLaneDev> lanes;
+    DeviceBuffer<int> slot_info, comp0;
+    DeviceBuffer<unsigned short> comp_cls;
+    e2hmm::SegPlanDev pl{};
+    i64 bytes = 0;  // of the five buffers
+    int upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st);
+};
+
+inline std::string fmt_17g(double v)
+{
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+inline bool ends_with(const std::string& s, const char* ext)
+{
+    const size_t n = strlen(ext);
+    return s.size() >= n && s.compare(s.size() - n, n, ext) == 0;
+}
+
+// ---- the transitions file (hmm_transitions.cpp) -----------------------------------------------------------------------------
+// class names that can head its columns: K >= 1 of them, none empty or with a separator, no two equal
+int check_names(const char* who, int K, const char* const* names);
+// the file's matrix in the order of `names` (the models' classes): lt[f * K + k], each value <= 0 or -inf
+int transitions_read(const char* path, int K, const char* const* names, std::vector<double>& lt);
+
+// ---- inputs (hmm_input.cpp) -------------------------------------------------------------------------------------------------
+std::vector<std::string> split_on(const std::string& s, char sep);
+// the lines of a text file without their line ends; a last line without one counts, trailing empty lines do not
+int read_lines(const char* path, std::vector<std::string>& lines);
+
+// The labelled units of one file, in their order: a segment CSV (column `class`, in row order) or a tab-separated selection
+// table (column `Type`, sorted by `Begin Time (s)`; equal times keep their row order).  The first line that is no '#'
+// comment is the header.  `hmm transitions` counts their successions, `hmm align` aligns to them.
+struct LabelRow {
+    std::string label;
+    size_t line;  // of the file, from 1
+};
+int read_label_file(const char* path, std::vector<LabelRow>& rows);
+
+// input -> device symbols: the stage `hmm scan`, `hmm segment` and `hmm align` share
+struct SymInput {
+    std::string path, csv;
+    int kind = 0;  // 0 .wav, 1 .prd, 2 .seq
+    int sample_rate = 0;
+    int64_t samples = 0, T = 0;
+};
+struct SymInputs {
+    bool have_cb = false, need_cb = false;
+    int cbP = 0, cbM = 0;
+    std::vector<double> refl;
+    std::vector<SymInput> inputs;
+};
+// the checks of the inputs against the models' M and the codebook, and the codebook itself: host only, no file written
+int sym_inputs_check(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs, int P,
+                     int W_ms, int O_ms, const char* csv_dir_or_file, SymInputs& si);
+struct VqSessionHolder {
+    e2vq_session* s = nullptr;
+    ~VqSessionHolder()
+    {
+        if (s) e2vq_session_destroy(s);
+    }
+};
+// The device side of the inputs of one call: the buffers they reuse (the symbols of the current input in d_sym), the
+// stream, and the quantize session where an input needs the codebook.
+struct SymStage {
+    DeviceBuffer<double> d_frames;
+    DeviceBuffer<int32_t> d_status;
+    DeviceBuffer<unsigned short> d_sym;
+    int device = 0;
+    Stream st;  // (after the buffers: see Stream)
+    VqSessionHolder vq;
+    // the stream and the session on `device`, which the caller has made current (require_device)
+    int open(int device, const SymInputs& si);
+    // one input to symbols in d_sym (read and uploaded once; frames and symbols stay on the device): *T_out of them.
+    // Waits for the stream before it returns.
+    int input(const SymInput& in, const SymInputs& si, int P, int W_ms, int O_ms, int64_t* T_out);
+};
+// What the commands that work input by input do once their own checks have passed (`who`: the entry point): the check of
+// the inputs and the codebook against M, still on the host alone; then one SymStage, and for every input its symbols on
+// the device followed by the command's work on them, run(input, T, d_sym, stream).
+int run_on_files(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs, int P, int W_ms,
+                 int O_ms, const char* csv_dir_or_file,
+                 const std::function<int(const SymInput&, int64_t, const unsigned short*, hipStream_t)>& run);
 
 }  // namespace e2hmm_host

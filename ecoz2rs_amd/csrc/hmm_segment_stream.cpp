@@ -2,7 +2,8 @@
 // unknown length in feeds of any length, runs the joint Viterbi of `hmm segment` on it block by block (the kernels of
 // hmm_segment_stream.hip), keeps the back-pointers of the undecided frames alone -- in a ring on the device -- and hands the
 // frames out as soon as every surviving path agrees on them; and the file form that feeds consecutive pieces of one recording
-// to one session.  Shape checks, logarithms, packing and the input stage are hmm_decode.cpp's (hmm_host.h).
+// to one session.  Shape checks, models, packing and its device side are hmm_class_loop.cpp's, the input stage hmm_input.cpp's
+// (hmm_host.h).
 #include "hmm_host.h"
 #include "hmm_segment_stream.h"
 
@@ -18,11 +19,11 @@ struct e2vq_segment_stream {
     i64 B = 0;         // frames of a block
     i64 C = 0;         // frames the pending budget holds; the ring has C + B - 1 rows (the last B - 1: the remainder at close)
     i64 dev_bytes = 0;
-    // device: parameters and packing (as segment_device uploads them), the ring, the carried d, O(B) staging, the session's state
-    DeviceBuffer<double> d_params, d_d, d_gstage;
-    DeviceBuffer<e2hmm::SegLaneDev> d_lanes;
-    DeviceBuffer<int> d_info, d_comp0, d_gsel;
-    DeviceBuffer<unsigned short> d_comp_cls, d_psi, d_blk;
+    // device: parameters, packing and plan (as segment_device uploads them), the ring, the carried d, O(B) staging, the session's state
+    ClassLoopDev loop;
+    DeviceBuffer<double> d_d, d_gstage;
+    DeviceBuffer<int> d_gsel;
+    DeviceBuffer<unsigned short> d_psi, d_blk;
     DeviceBuffer<SegStreamState> d_state;
     // device and pinned host: cls / state / entered of one commit (5 bytes a pending frame); G of the blocks since the last wait
     DeviceBuffer<unsigned short> d_cls, d_st;
@@ -31,7 +32,6 @@ struct e2vq_segment_stream {
     PinnedBuffer<unsigned char> h_entered;
     PinnedBuffer<double> h_g;
     PinnedBuffer<SegStreamState> h_state;
-    e2hmm::SegPlanDev pl{};
     e2hmm::SegRingDev ring{};
     KernelTimer all, commit_t;
     bool timing = false;  // all.start is recorded and not yet closed by a wait
@@ -68,60 +68,44 @@ double* d_half(Session& s, int which) { return s.d_d.get() + (size_t)which * s.s
 
 // The models (checked by segment_check_shape; all of one M) on the device and an empty session.  Every refusal comes before
 // the first HIP call.
-int stream_open(const char* who, int device, const std::vector<const Hmm*>& ms, const std::vector<std::vector<double>>& lflats,
-                double ln_switch, Session** out)
+int stream_open(const char* who, int device, const LoopModels& lm, double ln_switch, Session** out)
 {
-    const int K = (int)ms.size(), M = ms[0]->M;
+    const int K = lm.K(), M = lm.M;
     const char* bv = getenv(ENV_BLOCK);
     const i64 B = bv && *bv ? atoll(bv) : 4096;
     if (B < 1 || B > ((i64)1 << 24)) return e2vq_set_error("%s: %s=%s: a block of 1 .. %d frames", who, ENV_BLOCK, bv, 1 << 24);
-    const char* body = getenv("ECOZ2_HMM_SEGMENT_BODY");
-    if (body && *body && strcmp(body, "resident") != 0 && strcmp(body, "looped") != 0)
-        return e2vq_set_error("ECOZ2_HMM_SEGMENT_BODY=%s: resident or looped", body);
-    std::vector<int> Ns;
-    for (const Hmm* h : ms) Ns.push_back(h->N);
-    const SegPacking pk = pack_slots(Ns, [](int N) { return N; });
+    const SegPacking pk = pack_slots(lm.Ns);
     const int sumN = pk.sumN;
+    bool looped = false;
+    if (loop_body_looped("ECOZ2_HMM_SEGMENT_BODY", pk.slots, &looped)) return 1;
     const i64 row = 2 * (i64)sumN + 4, budget = env_bytes(ENV_PENDING, (i64)256 << 20), C = budget / row;
     if (C < 2 * B)
         return e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states (%lld bytes a frame): fewer than two blocks of %lld", who,
                               ENV_PENDING, (long long)budget, (long long)C, sumN, (long long)row, (long long)B);
-    // logarithms: lpi of every class | lA of every class | lB of every class
-    std::vector<double> params((size_t)sumN + (size_t)pk.a_words + (size_t)sumN * M);
-    for (int k = 0; k < K; ++k) {
-        const std::vector<double>& lflat = lflats[(size_t)k];
-        const size_t N = (size_t)ms[(size_t)k]->N;
-        std::copy(lflat.begin(), lflat.begin() + N, params.begin() + pk.comp0[(size_t)k]);
-        std::copy(lflat.begin() + N, lflat.begin() + N + N * N, params.begin() + sumN + pk.a_at[(size_t)k]);
-        std::copy(lflat.begin() + N + N * N, lflat.end(), params.begin() + sumN + pk.a_words + (size_t)pk.comp0[(size_t)k] * M);
-    }
+    const std::vector<double> params = loop_log_params(lm, pk);
     // ---- the device from here on --------------------------------------------------------------------------------
     if (require_device(device)) return 1;
     std::unique_ptr<Session> sp(new Session);
     Session& s = *sp;
     s.device = device, s.K = K, s.M = M, s.sumN = sumN, s.ln_switch = ln_switch, s.B = B, s.C = C;
-    s.looped = pk.slots > e2hmm::SEG_MAX_WAVES || (body && strcmp(body, "looped") == 0);
+    s.looped = looped;
     const i64 rows = C + B - 1;
     if (s.st.create() || s.all.create() || s.commit_t.create()) return 1;
     const hipStream_t st = s.st.s;
-    if (s.d_params.upload(params.data(), params.size(), st) || s.d_lanes.upload(pk.lanes.data(), pk.lanes.size(), st) ||
-        s.d_info.upload(pk.slot_info.data(), pk.slot_info.size(), st) || s.d_comp0.upload(pk.comp0.data(), pk.comp0.size(), st) ||
-        s.d_comp_cls.upload(pk.comp_cls.data(), pk.comp_cls.size(), st) || s.d_d.reserve((size_t)2 * sumN) || s.d_gstage.reserve((size_t)B) ||
-        s.d_blk.reserve((size_t)B) || s.d_state.reserve(1) || s.h_state.reserve(1))
+    if (s.loop.upload(pk, params, K, M, st) || s.d_d.reserve((size_t)2 * sumN) || s.d_gstage.reserve((size_t)B) || s.d_blk.reserve((size_t)B) ||
+        s.d_state.reserve(1) || s.h_state.reserve(1))
         return 1;
     if (s.d_psi.reserve((size_t)rows * sumN) || s.d_gsel.reserve((size_t)rows)) {
         const std::string why = e2vq_last_error();
         return e2vq_set_error("%s: no room for the ring of %lld pending frames x %d states (%lld bytes; %s bounds it): %s", who,
                               (long long)rows, sumN, (long long)(rows * row), ENV_PENDING, why.c_str());
     }
-    s.dev_bytes = (i64)params.size() * 8 + (i64)pk.lanes.size() * (i64)sizeof(e2hmm::SegLaneDev) + (i64)pk.slot_info.size() * 4 +
-                  (i64)K * 4 + (i64)sumN * 2 + rows * row + (i64)2 * sumN * 8 + B * 10 + (i64)sizeof(SegStreamState);
+    s.dev_bytes = s.loop.bytes + rows * row + (i64)2 * sumN * 8 + B * 10 + (i64)sizeof(SegStreamState);
     SegStreamState zero{};
     zero.fstar = -1, zero.bad_frame = -1, zero.prev_a = -1, zero.reached = -1;
     *s.h_state.get() = zero;
     HIPCHK(hipMemcpyAsync(s.d_state.get(), s.h_state.get(), sizeof zero, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // (`params` and the packing are locals)
-    s.pl = e2hmm::SegPlanDev{K, M, sumN, pk.slots, pk.a_words, s.d_lanes.get(), s.d_info.get(), s.d_params.get(), s.d_comp_cls.get(), s.d_comp0.get()};
     s.ring = e2hmm::SegRingDev{s.d_psi.get(), s.d_gsel.get(), rows};
     *out = sp.release();
     return 0;
@@ -135,9 +119,9 @@ int queue_block(Session& s, const unsigned short* blk, i64 n)
         HIPCHK(hipEventRecord(s.all.start.e, st));
         s.timing = true;
     }
-    if (e2hmm::launch_segment_stream(s.pl, s.looped, blk, (int)n, s.p, s.ln_switch, d_half(s, s.dcur), d_half(s, s.dcur ^ 1), s.ring,
+    if (e2hmm::launch_segment_stream(s.loop.pl, s.looped, blk, (int)n, s.p, s.ln_switch, d_half(s, s.dcur), d_half(s, s.dcur ^ 1), s.ring,
                                      s.d_gstage.get(), s.d_state.get(), st))
-        return e2vq_set_error("hmm segment --continuous: %d wave-slots of %d states cannot be launched", s.pl.slots, s.sumN);
+        return e2vq_set_error("hmm segment --continuous: %d wave-slots of %d states cannot be launched", s.loop.pl.slots, s.sumN);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(s.h_g.get() + s.g_queued, s.d_gstage.get(), (size_t)n * 8, hipMemcpyDeviceToHost, st));
     s.g_queued += n;
@@ -167,9 +151,9 @@ int commit(Session& s, bool close)
             s.timing = true;
         }
         HIPCHK(hipEventRecord(s.commit_t.start.e, st));
-        e2hmm::launch_segment_coalesce(s.pl, d_half(s, s.dcur), s.ring, s.F, s.p - 1, close ? 1 : 0, s.d_state.get(), st);
+        e2hmm::launch_segment_coalesce(s.loop.pl, d_half(s, s.dcur), s.ring, s.F, s.p - 1, close ? 1 : 0, s.d_state.get(), st);
         HIPCHK(hipGetLastError());
-        e2hmm::launch_segment_stream_backtrack(s.pl, s.ring, s.F, s.d_state.get(), s.d_cls.get(), s.d_st.get(), s.d_entered.get(), st);
+        e2hmm::launch_segment_stream_backtrack(s.loop.pl, s.ring, s.F, s.d_state.get(), s.d_cls.get(), s.d_st.get(), s.d_entered.get(), st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(s.commit_t.stop.e, st));
     }
@@ -335,16 +319,11 @@ extern "C" int e2vq_hmm_segment_stream_open(int device, int K, const int* Ns, in
                                             const double* const* Bs, double ln_switch, e2vq_segment_stream** out)
 {
     const char* who = "e2vq_hmm_segment_stream_open";
-    if (K < 1) return e2vq_set_error("%s: %d models (at least 1)", who, K);
-    if (!Ns || !pis || !As || !Bs || !out) return e2vq_set_error("%s: bad arguments", who);
-    if (segment_check_shape(who, K, Ns) || segment_check_switch(who, ln_switch)) return 1;
-    std::vector<Hmm> models;
-    std::vector<const Hmm*> ms;
-    std::vector<std::vector<double>> lflats((size_t)K);
-    if (models_from_arrays(K, Ns, M, pis, As, Bs, models, ms)) return 1;
-    for (int k = 0; k < K; ++k)
-        if (log_model(models[(size_t)k], lflats[(size_t)k])) return 1;
-    return stream_open(who, device, ms, lflats, ln_switch, out);
+    LoopModels lm;
+    if (loop_check_args(who, K, Ns, pis, As, Bs, out != nullptr) || segment_check_shape(who, K, Ns) || segment_check_switch(who, ln_switch) ||
+        lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs())
+        return 1;
+    return stream_open(who, device, lm, ln_switch, out);
 }
 
 extern "C" int e2vq_hmm_segment_stream_feed(e2vq_segment_stream* s, const void* sym, int64_t n, int sym_on_device, int64_t* final_frames)
@@ -432,19 +411,12 @@ extern "C" int e2vq_hmm_segment_continuous_files(const char* const* model_filena
 {
     const char* who = "e2vq_hmm_segment_continuous_files";
     FlushStdout flush_on_return;
-    if (!model_filenames || num_models < 1) return e2vq_set_error("%s: no models", who);
-    if (!input_filenames || num_inputs < 1) return e2vq_set_error("%s: no inputs", who);
+    LoopModels fm;
+    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
     if (!name || !*name) return e2vq_set_error("%s: the recording needs a name", who);
-    if (segment_check_switch(who, ln_switch)) return 1;
-    if (W_ms < 1 || O_ms < 1) return e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms);
-    FilesModels fm;
-    if (fm.load(model_filenames, num_models)) return 1;
-    std::vector<int> Ns;
-    for (const Hmm& h : fm.models) Ns.push_back(h.N);
-    if (segment_check_shape(who, (int)num_models, Ns.data())) return 1;
-    std::vector<std::vector<double>> lflats((size_t)num_models);
-    for (unsigned k = 0; k < num_models; ++k)
-        if (log_model(fm.models[k], lflats[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
+    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models) ||
+        fm.logs(model_filenames))
+        return 1;
     SymInputs si;
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
     std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
@@ -454,20 +426,14 @@ extern "C" int e2vq_hmm_segment_continuous_files(const char* const* model_filena
         ~Holder() { e2vq_hmm_segment_stream_free(s); }
     } hold;
     const int device = env_device();
-    if (stream_open(who, device, fm.ms, lflats, ln_switch, &hold.s)) return 1;
+    if (stream_open(who, device, fm, ln_switch, &hold.s)) return 1;  // (makes the device current)
     Session& s = *hold.s;
     SymStage stg;
-    Stream st;
-    if (st.create()) return 1;
-    VqSessionHolder vq;
-    if (si.need_cb) {
-        if (e2vq_session_create(device, si.cbP, &vq.s) || e2vq_set_stream(vq.s, (void*)st.s) || e2vq_set_codebook(vq.s, si.refl.data(), si.cbM))
-            return 1;
-    }
+    if (stg.open(device, si)) return 1;
     for (const SymInput& in : si.inputs) {
         int64_t T = 0;
         // (the stage waits for its stream before it returns, and a feed waits for the session's: the buffer is free again)
-        if (sym_input_to_device(in, si, stg, vq.s, device, P, W_ms, O_ms, st.s, &T)) return 1;
+        if (stg.input(in, si, P, W_ms, O_ms, &T)) return 1;
         if (T > 0 && stream_feed(who, s, stg.d_sym.get(), T, true)) {
             if (s.status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d (frame %lld of %s)", in.path.c_str(), fm.M, (long long)s.bad_frame, name);
             return 1;
