@@ -53,6 +53,11 @@ static int usage()
             "                  --sequences <file.seq|dirs|tt.csv>...   (one model per class, trained together)\n"
             "  ecoz2 hmm learn --grid -N <n1,n2,...> -M <m1,m2,...> [-t 3] [-I -1] [-e 1e-05] [-a 0.3] [-s <seed>]\n"
             "                  --sequences <file.seq|dirs|tt.csv>...   (one model per N, M and class, trained together)\n"
+            "  ecoz2 hmm learn --embedded -m|--models <files|dirs>... --labels <files>... [--filler <class>] [--switch-penalty <x <= 0>]\n"
+            "                  [-e 1e-05] [-a 0.3] [-I -1] -o <dir> [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
+            "                  (--signals <.wav files>... | --predictors <.prd files>... | --sequences <.seq files>...)\n"
+            "                  (the given models re-estimated from whole recordings and the order of their units, no boundaries:\n"
+            "                  label file i is recording i's transcript, as `hmm align` reads it; the models go to <dir>/<class>.hmm)\n"
             "  ecoz2 hmm classify [-r] [-c|--c12n <out.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST> -M <M> [--class-name c]\n"
             "                  (-s|--sequences <files|dirs|tt.csv>... | --predictors <files|dirs|tt.csv>... --codebooks <files|dirs>...\n"
             "                   [--predictors-dir-template <t>])\n"
@@ -1037,10 +1042,96 @@ static int hmm_align_cmd(int argc, char** argv)
     return 0;
 }
 
+// `hmm learn --embedded`: the class models re-estimated from whole recordings and their transcripts
+static int hmm_learn_embedded_cmd(int argc, char** argv)
+{
+    int P = 36, W = 45, O = 15, max_iterations = -1;
+    double ln_switch = 0.0, epsilon = 1e-05, val_auto = 0.3;
+    std::string codebook, filler, out;
+    std::vector<std::string> models, labels, signals, predictors, sequences;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        auto num = [&](const char* name) -> long long {
+            const char* v = val(name);
+            char* end = nullptr;
+            const long long x = strtoll(v, &end, 10);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto real = [&](const char* name) -> double {
+            const char* v = val(name);
+            char* end = nullptr;
+            const double x = strtod(v, &end);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto many = [&](std::vector<std::string>& v) { while (i + 1 < argc && !is_flag(argv[i + 1])) v.push_back(argv[++i]); };
+        if (a == "--embedded") continue;
+        else if (a == "--all-classes" || a == "--grid" || a == "--class-name") {
+            fprintf(stderr, "hmm learn --embedded excludes %s (it re-estimates the models given with --models)\n", a.c_str());
+            return usage();
+        }
+        else if (a == "-m" || a == "--models") many(models);
+        else if (a == "--codebook") codebook = val("--codebook");
+        else if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
+        else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
+        else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "-I" || a == "--max-iterations") max_iterations = (int)num("-I");
+        else if (a == "-e") epsilon = real("-e");
+        else if (a == "-a") val_auto = real("-a");
+        else if (a == "--filler") filler = val("--filler");
+        else if (a == "--labels") many(labels);
+        else if (a == "--switch-penalty") ln_switch = real("--switch-penalty");
+        else if (a == "-o" || a == "--out") out = val("-o");
+        else if (a == "--signals") many(signals);
+        else if (a == "--predictors") many(predictors);
+        else if (a == "-s" || a == "--sequences") many(sequences);
+        else return usage();
+    }
+    if (models.empty()) { fprintf(stderr, "hmm learn --embedded: --models <files|dirs>... is required\n"); return usage(); }
+    if (out.empty()) { fprintf(stderr, "hmm learn --embedded: -o <dir> is required\n"); return usage(); }
+    if ((int)!signals.empty() + (int)!predictors.empty() + (int)!sequences.empty() != 1) {
+        fprintf(stderr, "hmm learn --embedded: exactly one of --signals, --predictors and --sequences is required\n");
+        return usage();
+    }
+    if (!(ln_switch <= 0.0) || std::isinf(ln_switch)) { fprintf(stderr, "hmm learn --embedded: --switch-penalty %g: finite and at most 0\n", ln_switch); return 2; }
+    if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
+    if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
+    if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm learn --embedded: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    // (the inputs are taken as given, not resolved from directories: input i goes with label file i)
+    const std::vector<std::string>& inputs = !signals.empty() ? signals : !predictors.empty() ? predictors : sequences;
+    if (labels.size() != inputs.size()) {
+        fprintf(stderr, "hmm learn --embedded: %zu label files for %zu inputs (--labels names one per input, in the inputs' order)\n", labels.size(),
+                inputs.size());
+        return 2;
+    }
+    std::vector<std::string> hmm_files;
+    e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
+    printf("val_auto = %g\n", val_auto);
+    auto pm = cptrs(hmm_files), pi = cptrs(inputs), pl = cptrs(labels);
+    if (e2vq_hmm_learn_embedded_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(), pl.data(),
+                                      (int)pi.size(), P, W, O, ln_switch, filler.empty() ? nullptr : filler.c_str(), epsilon, val_auto,
+                                      max_iterations, out.c_str(), hmm_callback)) {
+        printf("%s\n", e2vq_last_error());
+        return 1;
+    }
+    return 0;
+}
+
 static int hmm_cmd(int argc, char** argv)
 {
     if (argc < 1) return usage();
     const std::string cmd = argv[0];
+    if (cmd == "learn")
+        for (int i = 1; i < argc; ++i)
+            if (std::string(argv[i]) == "--embedded") return hmm_learn_embedded_cmd(argc - 1, argv + 1);
     if (cmd == "scan") return hmm_scan_cmd(argc - 1, argv + 1);
     if (cmd == "transitions") return hmm_transitions_cmd(argc - 1, argv + 1);
     if (cmd == "segment") return hmm_segment_cmd(argc - 1, argv + 1);

@@ -23,37 +23,21 @@ struct AlignOut {  // host arrays, any may be null; per frame: unit, state, ente
     int* status = nullptr;
 };
 
-// What the host decides about a call before the device is touched: the packing of every stream's units, the device tables
-// that describe it, and the launches (consecutive streams of one body whose tables and LDS fit together).
-struct AlignPlan {
-    std::vector<e2hmm::AlignStreamDev> streams;  // tab_at: relative to the first stream of its launch
-    std::vector<e2hmm::AlignLaneDev> lanes;
-    std::vector<int> slot_info, unit_comp0;
-    std::vector<uint16_t> comp_unit;
-    struct Launch {
-        int s0, s1, waves, max_L, max_sumN;
-        bool looped;
-        i64 bytes;
-    };
-    std::vector<Launch> launches;
-    i64 max_bytes = 0;
-    SegPacking cls;  // the classes: their rows in the parameter block (comp0, a_at, sumN, a_words)
-};
-
 // may unit l hold frame 0 / the last frame (opt: the stream's flags, or null)
 bool unit_is_initial(int l, const uint8_t* opt) { return l == 0 || (l == 1 && opt && opt[0]); }
 bool unit_is_final(int l, int L, const uint8_t* opt) { return l == L - 1 || (l == L - 2 && opt && opt[L - 1]); }
 
-// the checks of the transcripts and the price, the packing and the launches: host only (`who`: the entry point named in
-// the messages)
+}  // namespace
+
+// (declared in hmm_host.h: hmm_embed.cpp plans with it too)
 int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, AlignPlan& ap)
+               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded)
 {
     if (segment_check_switch(who, ln_switch)) return 1;
     if (std::isinf(ln_switch)) return e2vq_set_error("%s: ln_switch = %g: a finite price (every unit has to be entered)", who, ln_switch);
     if (unit_offs[0] != 0) return e2vq_set_error("%s: unit_offs[0] = %lld, not 0", who, (long long)unit_offs[0]);
     bool force_looped = false;
-    if (loop_body_looped("ECOZ2_HMM_ALIGN_BODY", 0, &force_looped)) return 1;
+    if (!embedded && loop_body_looped("ECOZ2_HMM_ALIGN_BODY", 0, &force_looped)) return 1;  // (the E-step has one body)
     const i64 budget = env_bytes("ECOZ2_HMM_ALIGN_TABLE_BYTES", (i64)4 << 30);
     ap.cls = pack_slots(std::vector<int>(Ns, Ns + K));
     const SegPacking& cls = ap.cls;
@@ -90,6 +74,10 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
                                   s, L, pk.sumN, pk.slots, e2hmm::align_lds_bytes(L, pk.sumN, 0, true, false), e2hmm::SEG_LDS_BYTES);
         const i64 T = offs[s + 1] - offs[s];
         bytes[(size_t)s] = T * ((i64)pk.sumN + L);
+        if (bytes[(size_t)s] > budget && embedded)  // (no back-pointers there: the bound alone is `hmm align`'s)
+            return e2vq_set_error("%s: stream %d: %lld frames x (%d states + %d units) = %lld exceed ECOZ2_HMM_ALIGN_TABLE_BYTES=%lld, the "
+                                  "bound on a stream that `hmm align` sets and that holds here too",
+                                  who, s, (long long)T, pk.sumN, L, (long long)bytes[(size_t)s], (long long)budget);
         if (bytes[(size_t)s] > budget)
             return e2vq_set_error("%s: stream %d: the back-pointers of %lld frames x (%d states + %d units) take %lld bytes: more than "
                                   "ECOZ2_HMM_ALIGN_TABLE_BYTES=%lld",
@@ -115,7 +103,8 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
         ap.comp_unit.insert(ap.comp_unit.end(), pk.comp_cls.begin(), pk.comp_cls.end());
     }
     // the launches: consecutive streams of one body whose tables stay within the budget and whose largest L and sum N fit LDS
-    for (int s0 = 0; s0 < S;) {
+    // (the E-step cuts its own)
+    for (int s0 = 0; s0 < S && !embedded;) {
         AlignPlan::Launch g{s0, s0, 0, 0, 0, looped[(size_t)s0], 0};
         int slots = 0;
         while (g.s1 < S) {
@@ -136,6 +125,8 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
     }
     return 0;
 }
+
+namespace {
 
 // the path's own cumulative score, frame by frame, from the decoded path: one addition per term in the device's order
 void align_replay(const LoopModels& lm, const uint16_t* sym, i64 T, const int32_t* units, const uint8_t* opt, double ln_switch,

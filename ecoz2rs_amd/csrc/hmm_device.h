@@ -212,6 +212,41 @@ void launch_align_backtrack(const AlignPlanDev& pl, const long long* offs, int S
                             const int* status, unsigned short* unit, unsigned short* state, unsigned char* entered,
                             long long* begin, long long* end, hipStream_t st);
 
+// Embedded Baum-Welch over the same chain of units (hmm_embed.hip), on k_hmm_align's packing of every
+// stream with at most SEG_MAX_WAVES slots.  The lanes carry three more flags; the parameters and the accumulators are per class.
+constexpr int EMBED_FIRST = 16;  // lane flags: the unit is the first of its class in the stream
+constexpr int EMBED_SUCC = 32;   //             the unit has a successor (l + 1 < L)
+constexpr int EMBED_SUCC2 = 64;  //             the unit may be left for l + 2 (l + 2 < L and unit l + 1 is optional)
+struct EmbedClassDev {
+    int N;
+    int a_at;            // A of the class at this many doubles into the A area (leading dimension N | 1)
+    long long acc_at;    // its acc_words(N, M) count words at acc + acc_at
+    long long param_at;  // its dense pi | A | B at this many doubles into the M-step's parameter block
+};
+struct EmbedPlanDev {
+    int K, M, sumN_cls, a_words, max_L;  // a_words: sum_k N_k (N_k | 1); max_L: the most units of a stream of the call
+    const AlignStreamDev* streams;       // [S] of the launch (tab_at unused)
+    const AlignLaneDev* lanes;
+    const int* slot_info;
+    const double* params;                // pi (sumN_cls) | e = sw pi (sumN_cls) | A (a_words) | B (sumN_cls rows of M)
+    const EmbedClassDev* classes;        // [K]
+    const unsigned short* row_cls;       // [sumN_cls]: a class state's row -> its class
+};
+// dynamic LDS of k_hmm_embed_fb: the partial sums, V / R, A (a_lds) and the AN limb table (an_lds)
+size_t embed_lds_bytes(int max_L, int a_words, bool a_lds, bool an_lds);
+// S streams (a workgroup of `waves` waves each, at least the most slots of a stream) from offs[0] on.  The scratch of a stream
+// starts at scr + (its offset - a0) * row_words and takes T (2 sumN + slots) doubles; the counts are added to acc (zeroed by the
+// caller), P(O, transcript) = mant 2^exp2 and status at [s].  Returns 1 when the shape cannot be launched.
+int launch_embed_fb(const EmbedPlanDev& pl, bool a_lds, bool an_lds, int waves, const unsigned short* sym, const long long* offs, int S,
+                    long long a0, long long row_words, double* scr, long long* acc, double* mant, long long* exp2, int* status,
+                    hipStream_t st);
+// AD of every class from its AN, once every stream's counts are in
+void launch_embed_rowsum(const EmbedClassDev* classes, int K, int max_N, long long* acc, hipStream_t st);
+// M-step of all K classes on their dense blocks (+ the floor at epsilon of B when epsilon > 0), in place; max_P / max_N: the
+// largest N + N^2 + N M and N among them
+void launch_reestimate_embedded(const EmbedClassDev* classes, int K, int M, long long max_P, int max_N, const long long* acc,
+                                double epsilon, double* params, hipStream_t st);
+
 // Smoothed class posteriors under the same class loop (hmm_posterior.hip), on the packing above with at
 // most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | e = sw pi (sumN) | A of every class with the leading dimension
 // N_k | 1 (lanes[].a_at and a_words count these padded words) | B (sumN rows of M).  S streams (a workgroup each) from

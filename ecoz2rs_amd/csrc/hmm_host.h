@@ -2,7 +2,7 @@
 // Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi and scan;
 // hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices; hmm_transitions.cpp: the file and the estimator
 // of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
-// decoder; hmm_align.cpp: forced alignment).
+// decoder; hmm_align.cpp: forced alignment; hmm_embed.cpp: embedded Baum-Welch on transcribed streams).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -325,6 +325,30 @@ struct ClassLoopDev {
     i64 bytes = 0;  // of the five buffers
     int upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st);
 };
+
+// ---- forced alignment (hmm_align.cpp): the plan `hmm align` and `hmm learn --embedded` (hmm_embed.cpp) share -----------------
+// What the host decides about a call before the device is touched: the packing of every stream's units, the device tables
+// that describe it, and the launches (consecutive streams of one body whose tables and LDS fit together).
+struct AlignPlan {
+    std::vector<e2hmm::AlignStreamDev> streams;  // tab_at: relative to the first stream of its launch
+    std::vector<e2hmm::AlignLaneDev> lanes;
+    std::vector<int> slot_info, unit_comp0;
+    std::vector<uint16_t> comp_unit;
+    struct Launch {
+        int s0, s1, waves, max_L, max_sumN;
+        bool looped;
+        i64 bytes;
+    };
+    std::vector<Launch> launches;
+    i64 max_bytes = 0;
+    SegPacking cls;  // the classes: their rows in the parameter block (comp0, a_at, sumN, a_words)
+};
+// the checks of the transcripts and the price, the packing and the launches: host only (`who`: the entry point named in
+// the messages).  embedded: the caller is the embedded E-step -- every refusal stays (the bound of
+// ECOZ2_HMM_ALIGN_TABLE_BYTES on a stream too, worded for a caller without back-pointers), but ECOZ2_HMM_ALIGN_BODY is not
+// read and no launches are cut
+int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
+               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded = false);
 
 inline std::string fmt_17g(double v)
 {

@@ -110,6 +110,14 @@ _sig("e2vq_hmm_align_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_char_p)
 _sig("e2vq_hmm_align_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_double, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_embedded_estep", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _dpp, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_train_embedded", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int,
+     C.POINTER(C.c_int), C.c_int)
+_sig("e2vq_hmm_embedded_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_learn_embedded_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, c_char_pp, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_double, C.c_char_p, C.c_double, C.c_double, C.c_int, C.c_char_p, HMM_LEARN_CALLBACK)
 
 
 def _strs(items):
@@ -832,3 +840,87 @@ def align_files(model_filenames, input_filenames, label_filenames, ln_switch=0.0
     check(lib.e2vq_hmm_align_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l, len(input_filenames),
                                    int(P), int(W_ms), int(O_ms), float(ln_switch), str(filler).encode() if filler else None,
                                    str(csv).encode() if csv else None))
+
+
+def _embedded_args(models, sym, offs, units, unit_offs, optional):
+    """the arguments `embedded_estep` and `train_embedded` share, checked as `align` checks them -> (ms, Ns, M, offs, S, units,
+    unit_offs, optional, sym (kept alive), sym_ptr, on_device)"""
+    K = len(models)
+    ms = [tuple(np.array(x, dtype=np.float64, order="C") for x in m) for m in models]  # (copies: train_embedded writes them)
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    unit_offs = np.ascontiguousarray(unit_offs, dtype=np.int64)
+    S = len(offs) - 1
+    if len(unit_offs) != S + 1:
+        raise ValueError(f"unit_offs has {len(unit_offs)} entries for {S} streams")
+    units = np.ascontiguousarray(units, dtype=np.int32)
+    if optional is not None:
+        optional = np.ascontiguousarray(np.asarray(optional) != 0, dtype=np.uint8)
+    nu = int(unit_offs[-1]) if len(unit_offs) else 0
+    if len(units) < nu or (optional is not None and len(optional) < nu):
+        raise ValueError(f"unit_offs ends at {nu}: more than the units given")
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    return ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device
+
+
+def embedded_estep(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, device=0):
+    """one E-step of embedded Baum-Welch: models, sym, offs, units, unit_offs, optional, ln_switch as `align`
+    takes them -> dict acc (per class its int64 accumulator words, the layout of `acc_words`), log_prob (ln P(O, transcript)
+    per stream, -inf where the status is not 0), status"""
+    ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device = _embedded_args(models, sym, offs, units, unit_offs, optional)
+    K = len(ms)
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    acc = [np.zeros(int(lib.e2vq_hmm_acc_words(len(m[0]), M)), dtype=np.int64) for m in ms]
+    accp = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in acc])
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_embedded_estep(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
+                                      unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None,
+                                      float(ln_switch), accp, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    return dict(acc=acc, log_prob=lp[:S], status=st[:S])
+
+
+def train_embedded(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, epsilon=1e-5, val_auto=0.3, max_iterations=-1,
+                   device=0):
+    """embedded Baum-Welch to its stop -> (the trained models [(pi, A, B)], the sum of ln P per E-step)"""
+    ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device = _embedded_args(models, sym, offs, units, unit_offs, optional)
+    K = len(ms)
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    cap = 1000
+    hist = np.zeros(cap)
+    n = C.c_int(0)
+    check(lib.e2vq_hmm_train_embedded(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
+                                      unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None,
+                                      float(ln_switch), float(epsilon), float(val_auto), int(max_iterations), hist.ctypes.data, cap,
+                                      C.byref(n), int(on_device)))
+    return ms, hist[:n.value].copy()
+
+
+def embedded_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_embedded_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def learn_embedded_files(model_filenames, input_filenames, label_filenames, out_dir, ln_switch=0.0, filler=None, hmm_epsilon=1e-5,
+                         val_auto=0.3, max_iterations=-1, codebook=None, P=36, W_ms=45, O_ms=15, callback=None):
+    """`hmm learn --embedded`: the models of the files re-estimated from input i (.wav, .prd or .seq) and the
+    transcript label file i names (as `align_files` reads it; filler as there); writes <out_dir>/<class>.hmm for every class and
+    <out_dir>/embedded.csv; callback(var: str, val: float) per E-step"""
+    if len(label_filenames) != len(input_filenames):
+        raise ValueError(f"{len(label_filenames)} label files for {len(input_filenames)} inputs")
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    l, _k3 = _strs(label_filenames)
+    cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
+    check(lib.e2vq_hmm_learn_embedded_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
+                                            len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                            str(filler).encode() if filler else None, float(hmm_epsilon), float(val_auto),
+                                            int(max_iterations), str(out_dir).encode(), cb))

@@ -521,6 +521,84 @@ int e2vq_hmm_align_files(const char *const *model_filenames, unsigned num_models
                          const char *const *input_filenames, const char *const *label_filenames, int num_inputs, int P, int W_ms,
                          int O_ms, double ln_switch, const char *filler_class, const char *csv_dir_or_file);
 
+/* ---- embedded Baum-Welch: the class models trained on transcribed streams ----------------------------------
+ * `hmm learn --embedded`: re-estimate the class models from whole streams and, per stream, the order of its units -- no
+ * boundaries.  Inputs are e2vq_hmm_align's: K models sharing M, N_k <= 64, mixed N allowed; S streams (sym, offs); per stream a
+ * transcript c_0 .. c_{L-1} of class indices (units, unit_offs), repeats and immediate repeats allowed; a flag per unit,
+ * optional (may be NULL = none); one finite ln_switch <= 0.  Everything e2vq_hmm_align refuses before a HIP call is refused
+ * here too, and one thing more: a stream whose units pack into more than 16 wave-slots (the message names the slot count) --
+ * only a resident body is built.
+ * The arithmetic is linear and scaled; nothing transcendental runs on the device.  sw = exp(ln_switch) is the C library's exp
+ * on the host; e[l][j] = sw * pi_{c_l}[j] is one host multiplication; every operation below is one IEEE double operation in
+ * the stated order, no fma.  GS is the global sum of 4.8.7 over the stream's packing: a butterfly over the 64 lanes of each
+ * slot (idle lanes 0.0), then the slots in slot order.
+ * Sets.  Start S0 = {0} + {1 if optional[0]}.  Final F = {L-1} + {L-2 if optional[L-1]}.  pred(l) = {l-1} + {l-2 if l >= 2 and
+ * optional[l-1]}; succ(l) is the mirror image: {l+1 if l+1 < L} + {l+2 if l+2 < L and optional[l+1]}.
+ * Forward.  x_0[l][j] = pi[j] * B[j][o_0] for l in S0, else 0.0.  c_t = GS(x_t); !(c_t > 0) gives status 1.  ah_t = x_t / c_t.
+ * For t >= 1 the in-class chain is 4.8.7's: acc = ah_{t-1}[l][0] * A[0][j], then acc = acc + ah_{t-1}[l][i] * A[i][j], i ascending;
+ * the unit mass is summed on the way: V_{t-1}[l] = ah_{t-1}[l][0] + ah_{t-1}[l][1] + .. in state order (normalised).  The entering
+ * mass: in = V_{t-1}[l-1], and in = in + V_{t-1}[l-2] when l-2 is in pred(l); m_t[l][j] = in * e[l][j]; x_t[l][j] = (acc +
+ * m_t[l][j]) * B[j][o_t].  Unit 0 has no m (m_t[0][j] = 0.0).  The state-0 lane of a unit posts V before a barrier of the step's
+ * own, the second next to the one of GS: no extra serial sum and no extra division.  (The other form -- the unnormalised mass
+ * posted with the slot's partial sum, in = V / c_{t-1}, one barrier a frame -- was built and measured 8 to 14 % slower.)
+ * Status.  A symbol >= M gives status 2; the symbol check of a frame comes before its arithmetic; the first event in frame
+ * order decides.  A stream without frames has status 1.
+ * End.  Z = GS(l in F ? ah_{T-1}[l][j] : 0.0); !(Z > 0) gives status 1 (T below the number of mandatory units is the plain
+ * case).  log_prob = ln((prod_t c_t) Z), accumulated as (mantissa, exponent) with scale_step in frame order, Z last; the
+ * logarithm is taken on the host as 4.8 does; -inf where the status is not 0.  This is ln P(O, transcript | models) under the
+ * weighted chain.
+ * Backward.  bh_{T-1}[l][j] = 1.0 / Z for l in F, else 0.0.  For t = T-2 .. 0: u[l][j] = (B[j][o_{t+1}] * bh_{t+1}[l][j]) /
+ * c_{t+1}; R[l] = e[l][0] * u[l][0] + e[l][1] * u[l][1] + .. in state order; acc = A[i][0] * u[l][0] + A[i][1] * u[l][1] + ..
+ * in state order; r = R[l+1], and r = r + R[l+2] when l+2 is in succ(l); bh_t[l][i] = acc + r, and acc alone for l = L-1.
+ * Counts.  Each value goes through fix2(., ACC_SHIFT) into the int64 limb pairs of class c_l's block; the block's layout is
+ * e2vq_hmm_acc_words(N, M)'s: PI[N] | AN[N][N] | AD[N] | BN[N][M] | BD[N] | used, skipped.  Every frame: g = ah_t[l][j] *
+ * bh_t[l][j] goes to BN[j][o_t] and BD[j]; at t = 0 also to PI[j].  For t < T-1: (ah_t[l][i] * A[i][j]) * u[l][j] goes to
+ * AN[i][j]; for l >= 1, m_{t+1}[l][j] * u[l][j] goes to PI[j] -- the expected number of entries through pi -- with the very bits
+ * of m the forward pass used (it is stored).  AD[i] is the integer sum of row i of AN, both limbs.  The two trailing words
+ * count the status-0 and the skipped streams whose transcript names the class, once a stream.  A stream of status != 0 adds
+ * nothing else.  All sums are integers: the split over workgroups, the order of streams and the route of an atomic change no
+ * bit.
+ * M-step (k_hmm_reestimate_embedded, one thread a parameter, all K classes in a launch).  pi[j] = unfix(PI[j]) / unfix(the
+ * integer sums of the hi and of the lo limbs of PI over j); A[i][j] = unfix(AN[i][j]) / unfix(AD[i]); B[j][k] = unfix(BN[j][k]) /
+ * unfix(BD[j]); each only where its denominator is > 0.  Then, for epsilon > 0 and a class whose `used` word is > 0, hmm_adjustb's
+ * floor of B at epsilon.  Zeros in pi and A stay zeros, so the model type survives; a class that no transcript names keeps
+ * every byte.
+ * Loop.  Per iteration one E-step over all streams, then L = the sum of log_prob over the status-0 streams in stream order, on
+ * the host.  It stops as the other trainers do: max_iterations (< 0: none), 1000 E-steps, or it > 0 and L - Lprev <= val_auto;
+ * a stopping iteration gets no M-step.  If no stream has status 0 after the first E-step the call returns 1 with a message and
+ * leaves the models as they came.
+ * Where the counts live while a stream runs: BD and PI in registers (a lane is one composite state for the whole stream), BN by
+ * global atomics, AN in an LDS table over all K classes of the call (ds_add_u64, flushed once a stream) when it fits the 160 KB
+ * next to A, else by global atomics; ECOZ2_HMM_EMBED_A / ECOZ2_HMM_EMBED_AN = lds | global force either choice (a forced layout
+ * that does not fit is refused).  Scratch: ah_t and m_t per composite state, c_t per wave; whole streams per launch under
+ * ECOZ2_HMM_EMBED_CHUNK_BYTES (default 256 MiB), a larger stream alone. */
+/* one E-step: acc[k] receives class k's e2vq_hmm_acc_words(N_k, M) words (zeroed by the call); log_prob / status per stream
+ * (either may be NULL) */
+int e2vq_hmm_embedded_estep(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                            const double *const *Bs, const void *sym, const int64_t *offs, int S, const int32_t *units,
+                            const int64_t *unit_offs, const uint8_t *optional, double ln_switch, int64_t *const *acc,
+                            double *log_prob, int *status, int sym_on_device);
+/* the whole loop, the models in place; L of E-step i at sum_log_prob[i] (i < cap), the number of E-steps at *num_esteps */
+int e2vq_hmm_train_embedded(int device, int K, const int *Ns, int M, double *const *pis, double *const *As, double *const *Bs,
+                            const void *sym, const int64_t *offs, int S, const int32_t *units, const int64_t *unit_offs,
+                            const uint8_t *optional, double ln_switch, double epsilon, double val_auto, int max_iterations,
+                            double *sum_log_prob, int cap, int *num_esteps, int sym_on_device);
+/* HIP-event time of the kernels of this thread's last embedded E-step (-1: none yet) */
+int e2vq_hmm_embedded_last_kernel_ms(float *ms);
+/* `hmm learn --embedded`: the models of the files trained on input i (.wav, .prd or .seq, staged as e2vq_hmm_align_files
+ * stages them) under the transcript in label file i (as `hmm align` reads it; filler_class, may be NULL, inserted as there).
+ * Writes <out_dir>/<class>.hmm for every class, unchanged classes included, and <out_dir>/embedded.csv:
+ * iteration,sum_log_prob,streams_used,streams_skipped.  An out_dir that would overwrite an input model, and two models of one
+ * class, are refused.  A stream of status 1 or 2 is skipped, and named on stderr
+ * with the iteration whenever its status changes (in a later iteration too); if all are skipped at first, that is an error.  Stdout: a
+ * block in the style of `hmm learn`, its it=... lines unless ECOZ2_VQ_QUIET is set; the callback gets ("sum_log_prob", L)
+ * per E-step.  Everything but the streams' statuses is checked before any HIP call. */
+int e2vq_hmm_learn_embedded_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                  const char *const *input_filenames, const char *const *label_filenames, int num_inputs, int P,
+                                  int W_ms, int O_ms, double ln_switch, const char *filler_class, double hmm_epsilon,
+                                  double val_auto, int max_iterations, const char *out_dir,
+                                  void (*callback)(char *variable, double value));
+
 #ifdef __cplusplus
 }
 #endif
