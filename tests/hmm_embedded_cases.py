@@ -13,6 +13,14 @@ planted_models = A.planted_models
 PEAKS = A.PEAKS
 PLANTED_ORDER = A.PLANTED_ORDER
 FILLER = A.FILLER
+SHAPES = A.SHAPES
+shape = A.shape
+slots_of = A.slots_of
+embed_route = A.embed_route
+event_models = A.event_models
+event_batch = A.event_batch
+unlike_streams = A.unlike_streams
+random_batch = A.random_batch
 
 
 def pack(streams, transcripts, optionals=None):

@@ -421,6 +421,76 @@ def test_report_csv_and_block(tmp_path, capfd):
     assert "e2vq_hmm_align_report: unit 1 spans [2, 9) of 8 frames" in _err()
 
 
+# ---- the shapes where classes and units part: which instantiation each row of SHAPES reaches ---------------------------------------
+def _header(name):
+    return open(os.path.join(CSRC, name)).read()
+
+
+def test_the_restated_lds_constants_are_the_headers():
+    dev = _header("hmm_device.h")
+    lds = re.search(r"constexpr\s+size_t\s+SEG_LDS_BYTES\s*=\s*(\d+)\s*\*\s*(\d+)\s*;", dev)
+    waves = re.search(r"constexpr\s+int\s+SEG_MAX_WAVES\s*=\s*(\d+)\s*;", dev)
+    assert lds and waves
+    assert cases.SEG_LDS_BYTES == int(lds.group(1)) * int(lds.group(2)) and cases.SEG_MAX_WAVES == int(waves.group(1))
+    pair = re.search(r"struct\s+Pair\s*\{[^\n]*\n(.*?)\};", _header("hmm_segment_common.h"), re.S)
+    assert pair
+    size = 0  # (a double and two ints: no padding between or behind them)
+    for typ, names in re.findall(r"\b(double|int)\s+([^;]+);", pair.group(1)):
+        size += {"double": 8, "int": 4}[typ] * len(names.split(","))
+    assert cases.PAIR_BYTES == size == 16
+    # the two sums themselves, term by term as the launchers write them
+    align = re.search(r"size_t align_lds_bytes\([^)]*\)\s*\{(.*?)\n\}", _header("hmm_align.hip"), re.S).group(1)
+    assert "SEG_MAX_WAVES * sizeof(Pair) + (size_t)2 * max_L * 8 + (a_lds ? (size_t)a_words * 8 : 0)" in align
+    assert "(looped ? (size_t)2 * max_sumN * 8 : 0)" in align
+    embed = re.search(r"size_t embed_lds_bytes\([^)]*\)\s*\{(.*?)\n\}", _header("hmm_embed.hip"), re.S).group(1)
+    assert "(size_t)2 * SEG_MAX_WAVES * sizeof(double) + (size_t)2 * max_L * 8 + (a_lds ? (size_t)a_words * 8 : 0)" in embed
+    assert "(an_lds ? (size_t)a_words * 16 : 0)" in embed
+
+
+@pytest.mark.parametrize("name", list(cases.SHAPES))
+def test_every_shape_reaches_the_instantiation_its_row_names(name):
+    Ns, units, _opt, _T, _M, _zeros, _planted = cases.SHAPES[name]
+    uN = [Ns[k] for k in units]
+    L, sumN, a_words = len(uN), sum(uN), sum(N * N for N in Ns)
+    looped, a_lds = cases.align_route(Ns, units)
+    assert looped == (cases.slots_of(uN) > cases.SEG_MAX_WAVES)
+    if name in cases.A_GLOBAL:  # lA overflows LDS under the body the row names, and the rest fits without it
+        assert looped == (cases.A_GLOBAL[name] == "looped") and not a_lds
+        assert cases.align_lds_bytes(L, sumN, a_words, looped, True) > cases.SEG_LDS_BYTES
+        assert cases.align_lds_bytes(L, sumN, a_words, looped, False) <= cases.SEG_LDS_BYTES
+        if not looped:  # (forced looped, the resident rows stay on global lA and still fit)
+            assert cases.align_route(Ns, units, looped=True) == (True, False)
+            assert cases.align_lds_bytes(L, sumN, a_words, True, False) <= cases.SEG_LDS_BYTES
+    else:
+        assert not looped and a_lds
+    if looped:
+        return  # (the E-step refuses more than 16 slots)
+    e_words = sum(N * (N | 1) for N in Ns)
+    if name in cases.A_GLOBAL:  # embed_plan chooses global A and global AN by itself
+        assert cases.embed_route(Ns, L) == (False, False)
+        assert cases.embed_lds_bytes(L, e_words, True, False) > cases.SEG_LDS_BYTES
+        assert cases.embed_lds_bytes(L, e_words, False, True) > cases.SEG_LDS_BYTES
+        assert cases.embed_lds_bytes(L, e_words, False, False) <= cases.SEG_LDS_BYTES
+    else:
+        assert cases.embed_route(Ns, L) == (True, True)
+
+
+def test_the_shapes_are_what_their_rows_say():
+    slots = {name: cases.slots_of([row[0][k] for k in row[1]]) for name, row in cases.SHAPES.items()}
+    assert slots == {"64x6c_8u": 8, "64x6c_17u": 17, "21x48c": 16, "1x3c_200u": 4, "1x3c_201u_opt": 4, "1_64_1": 5, "mixed_M1024": 3,
+                     "small_M65536": 1}
+    units17 = cases.SHAPES["64x6c_17u"][1]
+    assert len(units17) == 17 and sum(a == b for a, b in zip(units17, units17[1:])) == 1 and set(units17) == set(range(6))
+    assert 200 % 64 == 8  # the last slot of "1x3c_200u" holds 8 lanes
+    assert [m for _n, _u, _o, _t, m, _z, _p in cases.SHAPES.values()].count(8) == 6
+    _models, _units, _opt, stream = cases.shape("small_M65536")
+    assert stream[10] == stream[64] == 65535 and len(stream) == 70
+    # every optional flag the batches carry is one align_plan accepts: no two in a row, never all
+    for _models, _streams, transcripts, optionals in (cases.unlike_streams(), cases.random_batch(24, 40), cases.random_batch(24, 24, 16)):
+        for u, o in zip(transcripts, optionals):
+            assert len(u) == len(o) and not (o[1:] & o[:-1]).any() and not o.all()
+
+
 # ---- compiler metadata (read as test_hmm_segment_stream_cpu.py reads its kernels') ------------------------------------------------
 VGPR_BUDGET = 128  # 16 waves of one workgroup on a CU: four a SIMD
 
