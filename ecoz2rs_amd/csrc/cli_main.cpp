@@ -82,9 +82,12 @@ static int usage()
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
             "  ecoz2 hmm align -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  [--switch-penalty <x <= 0>] [--filler <class>] [-c <csv dir|file.csv>] --labels <files>...\n"
+            "                  [--posteriors [--frame-posteriors <dir>]]\n"
             "                  (--signals <.wav files>... | --predictors <.prd files>... | --sequences <.seq files>...)\n"
             "                  (each recording aligned to the units its label file names, in their order: a segment .csv or a\n"
-            "                  selection table; --filler: that class's model may stand before, between and after the units)\n"
+            "                  selection table; --filler: that class's model may stand before, between and after the units;\n"
+            "                  --posteriors adds how sure each unit is: the path's mean and least posterior over its frames, the\n"
+            "                  probability that the unit is there, the mean and spread of its first frame; and the per-frame table)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -978,7 +981,8 @@ static int hmm_align_cmd(int argc, char** argv)
 {
     int P = 36, W = 45, O = 15;
     double ln_switch = 0.0;
-    std::string codebook, csv, filler;
+    bool posteriors = false;
+    std::string codebook, csv, filler, frames_dir;
     std::vector<std::string> models, labels, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -1008,6 +1012,8 @@ static int hmm_align_cmd(int argc, char** argv)
             if (!*v || *end) { fprintf(stderr, "--switch-penalty: invalid value '%s'\n", v); exit(2); }
         }
         else if (a == "-c" || a == "--csv") csv = val("-c");
+        else if (a == "--posteriors") posteriors = true;
+        else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
         else if (a == "--signals") many(signals);
         else if (a == "--predictors") many(predictors);
         else if (a == "-s" || a == "--sequences") many(sequences);
@@ -1019,6 +1025,7 @@ static int hmm_align_cmd(int argc, char** argv)
         return usage();
     }
     if (!(ln_switch <= 0.0) || std::isinf(ln_switch)) { fprintf(stderr, "hmm align: --switch-penalty %g: finite and at most 0\n", ln_switch); return 2; }
+    if (!frames_dir.empty() && !posteriors) { fprintf(stderr, "hmm align: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm align: --signals and --predictors need --codebook <cbook>\n"); return 2; }
@@ -1034,8 +1041,11 @@ static int hmm_align_cmd(int argc, char** argv)
     printf("ECOZ2 C version: %s\n", ecoz2_version());
     printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
     auto pm = cptrs(hmm_files), pi = cptrs(inputs), pl = cptrs(labels);
-    if (e2vq_hmm_align_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(), pl.data(),
-                             (int)pi.size(), P, W, O, ln_switch, filler.empty() ? nullptr : filler.c_str(), csv.empty() ? nullptr : csv.c_str())) {
+    const char *cb = codebook.empty() ? nullptr : codebook.c_str(), *fl = filler.empty() ? nullptr : filler.c_str();
+    const char* out = csv.empty() ? nullptr : csv.c_str();
+    if (posteriors ? e2vq_hmm_align_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), pl.data(), (int)pi.size(), P, W, O, ln_switch,
+                                                     fl, out, frames_dir.empty() ? nullptr : frames_dir.c_str())
+                   : e2vq_hmm_align_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), pl.data(), (int)pi.size(), P, W, O, ln_switch, fl, out)) {
         printf("%s\n", e2vq_last_error());
         return 1;
     }

@@ -247,6 +247,25 @@ void launch_embed_rowsum(const EmbedClassDev* classes, int K, int max_N, long lo
 void launch_reestimate_embedded(const EmbedClassDev* classes, int K, int M, long long max_P, int max_N, const long long* acc,
                                 double epsilon, double* params, hipStream_t st);
 
+// How sure the alignment is (hmm_align_posterior.hip): the E-step's forward-backward over the same plan
+// (of pl.classes only a_at is read), with the occupancy and the entry mass kept per unit and per frame.  Every output is
+// zeroed by the caller: a stream of status != 0 writes none.
+struct AlignPostDev {
+    const unsigned short* path_unit;  // per frame (absolute), the decoded path's unit; may be null
+    const long long* ref;             // per unit (absolute), the reference frame of the moments; may be null = 0
+    const long long* occ_at;          // [S] of the launch: where the stream's T x L occupancies begin in occ
+    double* occ;                      // may be null
+    double* post_path;                // per frame (absolute)
+    double* w;                        // w0 | w1 | w2, `units` doubles each, per unit (absolute)
+    long long units;
+};
+// dynamic LDS of k_hmm_align_posteriors: the partial sums, V / R and A (a_lds)
+size_t align_post_lds_bytes(int max_L, int a_words, bool a_lds);
+// S streams from offs[0] on, as launch_embed_fb takes them (the scratch too).  Returns 1 when the shape cannot be launched.
+int launch_align_posteriors(const EmbedPlanDev& pl, bool a_lds, int waves, const unsigned short* sym, const long long* offs, int S,
+                            long long a0, long long row_words, double* scr, const AlignPostDev& out, double* mant, long long* exp2,
+                            int* status, hipStream_t st);
+
 // Smoothed class posteriors under the same class loop (hmm_posterior.hip), on the packing above with at
 // most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | e = sw pi (sumN) | A of every class with the leading dimension
 // N_k | 1 (lanes[].a_at and a_words count these padded words) | B (sumN rows of M).  S streams (a workgroup each) from

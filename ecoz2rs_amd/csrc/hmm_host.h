@@ -2,7 +2,8 @@
 // Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi and scan;
 // hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices; hmm_transitions.cpp: the file and the estimator
 // of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
-// decoder; hmm_align.cpp: forced alignment; hmm_embed.cpp: embedded Baum-Welch on transcribed streams).
+// decoder; hmm_align.cpp: forced alignment; hmm_embed.cpp: embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp:
+// the posteriors of the alignment).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).

@@ -110,6 +110,17 @@ _sig("e2vq_hmm_align_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_char_p)
 _sig("e2vq_hmm_align_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_double, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_align_posteriors", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_align_posteriors_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_align_unit_moments", C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p)
+_sig("e2vq_hmm_align_report_posteriors", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_align_files_posteriors", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, c_char_pp, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p)
 _sig("e2vq_hmm_embedded_estep", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _dpp, C.c_void_p, C.c_void_p, C.c_int)
 _sig("e2vq_hmm_train_embedded", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
@@ -828,18 +839,86 @@ def align_last_kernel_ms():
 
 
 def align_files(model_filenames, input_filenames, label_filenames, ln_switch=0.0, filler=None, codebook=None, P=36, W_ms=45, O_ms=15,
-                csv=None):
+                csv=None, posteriors=False, frame_posteriors=None):
     """`hmm align`: input i (.wav, .prd or .seq) aligned to the units label file i names (a segment CSV or a
     selection table, as `hmm transitions` reads them); filler: the class of a model inserted as an optional unit around and
-    between them; per input a block on stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the units"""
+    between them; per input a block on stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the units.
+    posteriors (4.8.12): how sure every unit is, in the block and in five more CSV columns, and with frame_posteriors (a
+    directory) a per-frame table for every input"""
     if len(label_filenames) != len(input_filenames):
         raise ValueError(f"{len(label_filenames)} label files for {len(input_filenames)} inputs")
+    if frame_posteriors is not None and not posteriors:
+        raise ValueError("frame_posteriors needs posteriors=True")
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     l, _k3 = _strs(label_filenames)
+    if posteriors:
+        check(lib.e2vq_hmm_align_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
+                                                  len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                  str(filler).encode() if filler else None, str(csv).encode() if csv else None,
+                                                  str(frame_posteriors).encode() if frame_posteriors is not None else None))
+        return
     check(lib.e2vq_hmm_align_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l, len(input_filenames),
                                    int(P), int(W_ms), int(O_ms), float(ln_switch), str(filler).encode() if filler else None,
                                    str(csv).encode() if csv else None))
+
+
+def align_unit_moments(w0, w1, w2, ref=None):
+    """the host arithmetic of DESIGN.md 4.8.12 -> (present, begin_mean, begin_sd); the latter two NaN where not w0 > 0"""
+    w0, w1, w2 = (np.ascontiguousarray(x, dtype=np.float64) for x in (w0, w1, w2))
+    n = len(w0)
+    if len(w1) != n or len(w2) != n or (ref is not None and len(ref) != n):
+        raise ValueError("w0, w1, w2 and ref differ in length")
+    ref = None if ref is None else np.ascontiguousarray(ref, dtype=np.int64)
+    out = [np.zeros(max(n, 1)) for _ in range(3)]
+    check(lib.e2vq_hmm_align_unit_moments(n, w0.ctypes.data, w1.ctypes.data, w2.ctypes.data, ref.ctypes.data if ref is not None else None,
+                                          out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data))
+    return tuple(x[:n] for x in out)
+
+
+def align_posteriors(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, path_unit=None, ref=None, occupancy=True,
+                     device=0):
+    """how sure the alignment is: models, sym, offs, units, unit_offs, optional, ln_switch as `align` takes
+    them; path_unit: `align`'s per-frame `unit` (or None); ref: a reference frame per unit for the moments (or None = 0)
+    -> dict: occ, per stream the (T_s, L_s) array of P(unit l holds frame t) (only with occupancy); post_path per frame (occ at
+    the path's unit; 0 without path_unit); per unit w0 = present (P(a path visits the unit)), w1, w2, begin_mean, begin_sd (the
+    frame the unit is entered at); per stream log_prob, status"""
+    ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device = _embedded_args(models, sym, offs, units, unit_offs, optional)
+    K = len(ms)
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    T, nu = int(offs[-1]), int(unit_offs[-1])
+    if path_unit is not None:
+        path_unit = np.ascontiguousarray(path_unit, dtype=np.uint16)
+        if len(path_unit) < T:
+            raise ValueError(f"path_unit has {len(path_unit)} entries for {T} frames")
+    if ref is not None:
+        ref = np.ascontiguousarray(ref, dtype=np.int64)
+        if len(ref) < nu:
+            raise ValueError(f"ref has {len(ref)} entries for {nu} units")
+    Ls, Ts = np.diff(unit_offs), np.diff(offs)
+    occ_at = np.concatenate([[0], np.cumsum(Ts * Ls)]).astype(np.int64)
+    occ = np.zeros(max(int(occ_at[-1]), 1)) if occupancy else None
+    post = np.zeros(max(T, 1))
+    w0, w1, w2 = (np.zeros(max(nu, 1)) for _ in range(3))
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_align_posteriors(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
+                                        unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None,
+                                        float(ln_switch), path_unit.ctypes.data if path_unit is not None else None,
+                                        ref.ctypes.data if ref is not None else None, occ.ctypes.data if occ is not None else None,
+                                        post.ctypes.data, w0.ctypes.data, w1.ctypes.data, w2.ctypes.data, lp.ctypes.data, st.ctypes.data,
+                                        int(on_device)))
+    present, begin_mean, begin_sd = align_unit_moments(w0[:nu], w1[:nu], w2[:nu], None if ref is None else ref[:nu])
+    out = dict(post_path=post[:T], w0=w0[:nu], w1=w1[:nu], w2=w2[:nu], present=present, begin_mean=begin_mean, begin_sd=begin_sd,
+               log_prob=lp[:S], status=st[:S])
+    if occupancy:
+        out["occ"] = [occ[occ_at[s]:occ_at[s + 1]].reshape(int(Ts[s]), int(Ls[s])) for s in range(S)]
+    return out
+
+
+def align_posteriors_last_kernel_ms():
+    ms = C.c_float()
+    check(lib.e2vq_hmm_align_posteriors_last_kernel_ms(C.byref(ms)))
+    return ms.value
 
 
 def _embedded_args(models, sym, offs, units, unit_offs, optional):

@@ -599,6 +599,63 @@ int e2vq_hmm_learn_embedded_files(const char *const *model_filenames, unsigned n
                                   double val_auto, int max_iterations, const char *out_dir,
                                   void (*callback)(char *variable, double value));
 
+/* ---- how sure the alignment is: posteriors over the chain of units -------------------------------------------
+ * `hmm align --posteriors`: per unit and frame the posterior that the unit holds the frame, and per unit the probability that a
+ * path visits it with the mean and the spread of the frame it is entered at.  Inputs are e2vq_hmm_embedded_estep's.  path_unit
+ * (may be NULL): one uint16 per frame at the streams' absolute offsets, e2vq_hmm_align's `unit` output.  ref (may be NULL = 0):
+ * one int64 per unit at unit_offs, a reference frame for the moments below, each in [0, T) (not read for a stream without
+ * frames).  Any output may be NULL.
+ * Sets, Forward, Status, End, Backward are 4.8.11's word for word: the same operations in the same order, with the same GS over
+ * the same packing from align_plan.  ah_t, m_t, c_t, Z, bh_t, u, log_prob and status are therefore the E-step's bits; a stream
+ * without frames has status 1, as there.
+ * Occupancy.  g_t[l][j] = ah_t[l][j] * bh_t[l][j]; G_t[l] = g_t[l][0] + g_t[l][1] + .. in state order: P(unit l holds frame t |
+ * stream, transcript).  occ receives G_t[l] at occ_base(s) + t * L_s + l, occ_base(s) = the sum of T_s' * L_s' over s' < s.
+ * Entries.  For t >= 1 and l >= 1: En_t[l] = m_t[l][0] * u_t[l][0] + m_t[l][1] * u_t[l][1] + .. in state order, u_t = (B[j][o_t] *
+ * bh_t[l][j]) / c_t -- the very products the E-step sends to PI, with the stored bits of m.  En_t[0] = 0.0 for t >= 1.  En_0[l] =
+ * G_0[l].  Every admissible path that visits unit l enters it exactly once: the sum of En_t[l] over t is P(the path visits l).
+ * Per unit.  The sums run in the order the backward pass meets the frames, t = T-1 down to 0, each term added by one
+ * addition: w0[l] += En_t[l]; w1[l] += d * En_t[l]; w2[l] += (d * d) * En_t[l]; d = (double)(t - ref[l]).  d * d is exact while
+ * |d| < 2^26.5 (94 906 265 frames) and one rounded product beyond.  The unit's state-0 lane holds the three sums in registers
+ * over the whole stream and writes them once.
+ * Per frame.  post_path[t] = G_t[path_unit[t]]; 0.0 where path_unit[t] is 0xFFFF or >= L_s, or where path_unit is NULL.  The
+ * lane that owns the unit writes it; path_unit is handed out 64 frames at a time, as the symbols are.
+ * Status != 0.  Every occ, post_path, w0, w1 and w2 entry of the stream is 0.0; log_prob is -inf.
+ * Host (e2vq_hmm_align_unit_moments, plain C++ in this order): present = w0; q = w1 / w0; begin_mean = (double)ref + q;
+ * begin_sd = sqrt(max(0, w2 / w0 - q * q)); both NaN where !(w0 > 0).
+ * Refused before any HIP call: everything e2vq_hmm_embedded_estep refuses; a packing of more than 16 wave-slots, by a message of
+ * this function's own that names the slot count and says that only a resident body exists; a ref outside [0, T).
+ * Scratch: ah_t, m_t and c_t as in the E-step; whole streams per launch under ECOZ2_HMM_EMBED_CHUNK_BYTES, a larger stream
+ * alone; ECOZ2_HMM_EMBED_A = lds | global is honoured as there.  The outputs have device mirrors for the whole call. */
+int e2vq_hmm_align_posteriors(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                              const double *const *Bs, const void *sym, const int64_t *offs, int S, const int32_t *units,
+                              const int64_t *unit_offs, const uint8_t *optional, double ln_switch, const uint16_t *path_unit,
+                              const int64_t *ref, double *occ, double *post_path, double *w0, double *w1, double *w2,
+                              double *log_prob, int *status, int sym_on_device);
+/* HIP-event time of the kernels of this thread's last e2vq_hmm_align_posteriors (-1: none yet) */
+int e2vq_hmm_align_posteriors_last_kernel_ms(float *ms);
+/* the host arithmetic above for n units (host only; ref may be NULL = 0, any output may be NULL) */
+int e2vq_hmm_align_unit_moments(int64_t n, const double *w0, const double *w1, const double *w2, const int64_t *ref,
+                                double *present, double *begin_mean, double *begin_sd);
+/* e2vq_hmm_align_report with five trailing CSV columns: posterior,min_posterior,p_present,begin_mean_frame,begin_sd_frames --
+ * posterior: the mean of post_path over the unit's [begin, end), a serial sum in frame order, then one division; min_posterior:
+ * its minimum there; the other three from e2vq_hmm_align_unit_moments(w0, w1, w2, ref); floats as %.17g.  Each stdout unit line
+ * gains " p=%.3f" (posterior); a unit the path passed over stays out of the CSV and gets a line with its p_present.  With
+ * frames_csv_filename a per-frame table frame,begin_s,unit,class,posterior is written (path_unit is needed then). */
+int e2vq_hmm_align_report_posteriors(const char *name, int64_t T, int K, const char *const *class_names, int W_ms, int O_ms,
+                                     int L, const int32_t *units, const uint8_t *optional, const int64_t *begin,
+                                     const int64_t *end, const double *score, double log_prob, double ln_switch,
+                                     const uint16_t *path_unit, const double *post_path, const double *w0, const double *w1,
+                                     const double *w2, const int64_t *ref, const char *csv_filename,
+                                     const char *frames_csv_filename);
+/* `hmm align --posteriors [--frame-posteriors <dir>]`: e2vq_hmm_align_files with the report above.  The symbols of an input are
+ * staged once; e2vq_hmm_align and the posteriors run on the same device buffer; ref is the path's begin (0 where it is -1),
+ * path_unit its unit.  frames_dir (may be NULL): <frames_dir>/<input's base name>.csv per input.  Everything e2vq_hmm_align_files
+ * and e2vq_hmm_align_posteriors refuse is refused before any HIP call. */
+int e2vq_hmm_align_files_posteriors(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                    const char *const *input_filenames, const char *const *label_filenames, int num_inputs,
+                                    int P, int W_ms, int O_ms, double ln_switch, const char *filler_class,
+                                    const char *csv_dir_or_file, const char *frames_dir);
+
 #ifdef __cplusplus
 }
 #endif
