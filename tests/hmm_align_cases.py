@@ -112,10 +112,10 @@ EVENT_PAIRS_AT = (0, 63, 64)
 DEAD = 5  # the symbol no state emits
 
 
-def event_models():
-    """three dense models whose states cannot emit DEAD"""
+def event_models(Ns=(5, 3, 4)):
+    """dense models (three by default) whose states cannot emit DEAD"""
     out = []
-    for pi, A, B in small_models(seed=3, Ns=(5, 3, 4), zeros=0.0):
+    for pi, A, B in small_models(seed=3, Ns=Ns, zeros=0.0):
         B = B.copy()
         B[:, DEAD] = 0.0
         out.append((pi, A, B / B.sum(axis=1, keepdims=True)))

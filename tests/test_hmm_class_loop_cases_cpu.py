@@ -1,0 +1,254 @@
+"""the shared inputs of test_gpu_hmm_class_loop_shapes.py (tests/hmm_class_loop_cases.py), CPU side: the restated constants and
+LDS sums against hmm_device.h and the .hip sources; the body and the placement of lA (and lt) that every row of SHAPES reaches
+in each decoder; on the restatements alone, what makes a row worth running -- its path visits many classes in many slots, the
+last one among them, and a session over it decides frames after every block --; the vectorised restatements against their
+literal forms on the event streams, and the status of each; the seeded random sets."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from . import hmm_class_loop_cases as cases
+from . import hmm_posterior_restatement as RP
+from . import hmm_segment_restatement as R
+from . import hmm_segment_trans_restatement as RT
+from . import hmm_viterbi_restatement as V
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ecoz2rs_amd", "csrc")
+NINF = float("-inf")
+
+
+def _source(name):
+    return open(os.path.join(CSRC, name)).read()
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+# ---- the restated constants and sums ---------------------------------------------------------------------------------------------
+def test_the_restated_constants_are_the_sources():
+    dev = _source("hmm_device.h")
+    lds = re.search(r"constexpr\s+size_t\s+SEG_LDS_BYTES\s*=\s*(\d+)\s*\*\s*(\d+)\s*;", dev)
+    assert cases.SEG_LDS_BYTES == int(lds.group(1)) * int(lds.group(2))
+    for name in ("SEG_MAX_WAVES", "SEG_MAX_SUM_N"):
+        assert getattr(cases, name) == int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, dev).group(1)), name
+    stream = _source("hmm_segment_stream.hip")
+    assert cases.COALESCE_THREADS == int(re.search(r"constexpr\s+int\s+COALESCE_THREADS\s*=\s*(\d+)\s*;", stream).group(1))
+    assert "constexpr int COALESCE_PER_THREAD = SEG_MAX_SUM_N / COALESCE_THREADS;" in stream
+    assert cases.COALESCE_PER_THREAD == 4
+    # the two Pair structs: a double and two ints, no padding between or behind them
+    for name in ("hmm_segment_common.h", "hmm_segment_trans.hip"):
+        pair = re.search(r"struct\s+Pair\s*\{[^\n]*\n(.*?)\};", _source(name), re.S)
+        size = sum({"double": 8, "int": 4}[typ] * len(names.split(",")) for typ, names in re.findall(r"\b(double|int)\s+([^;]+);", pair.group(1)))
+        assert cases.PAIR_BYTES == size == 16, name
+
+
+def test_the_restated_lds_sums_are_the_launchers():
+    body = lambda name, fn: re.search(r"size_t %s\([^)]*\)\s*\{(.*?)\n\s*\}" % fn, _source(name), re.S).group(1)
+    seg = "(size_t)2 * SEG_MAX_WAVES * sizeof(Pair) + (a_lds ? (size_t)pl.a_words * 8 : 0) + (looped ? (size_t)2 * pl.sumN * 8 : 0)"
+    assert seg in body("hmm_segment.hip", "segment_lds_bytes") and seg in body("hmm_segment_stream.hip", "stream_lds_bytes")
+    assert "(size_t)2 * SEG_MAX_WAVES * sizeof(double) + (a_lds ? (size_t)pl.a_words * 8 : 0)" in body("hmm_posterior.hip", "posteriors_lds_bytes")
+    trans = body("hmm_segment_trans.hip", "trans_lds_bytes")
+    assert "(size_t)SEG_MAX_WAVES * sizeof(Pair) + (size_t)2 * pl.K * 8 + (a_lds ? (size_t)pl.a_words * 8 : 0) +" in trans
+    assert "(lt_lds ? (size_t)pl.K * pl.K * 8 : 0)" in trans
+    # lA is placed first and lt takes what is left; the posteriors' A has an odd leading dimension
+    layout = _source("hmm_segment_trans.hip")
+    assert "*a_lds = trans_lds_bytes(pl, true, false) <= SEG_LDS_BYTES;" in layout
+    assert "*lt_lds = trans_lds_bytes(pl, *a_lds, true) <= SEG_LDS_BYTES;" in layout
+    assert "int posteriors_a_ld(int N) { return N | 1; }" in _source("hmm_class_loop.cpp")
+    # every launcher raises the limit of dynamic LDS above 64 KB, and the first three choose lA by the same comparison
+    for name in ("hmm_segment.hip", "hmm_segment_stream.hip", "hmm_posterior.hip", "hmm_segment_trans.hip"):
+        src = _source(name)
+        assert "if (lds > 64 * 1024 &&" in src and "hipFuncAttributeMaxDynamicSharedMemorySize" in src, name
+    assert cases.LDS_OPT_IN == 64 * 1024
+    assert "const bool a_lds = segment_lds_bytes(pl, looped, true) <= SEG_LDS_BYTES;" in _source("hmm_segment.hip")
+    assert "const bool a_lds = stream_lds_bytes(pl, looped, true) <= SEG_LDS_BYTES;" in _source("hmm_segment_stream.hip")
+    assert "return posteriors_lds_bytes(pl, true) <= SEG_LDS_BYTES;" in _source("hmm_posterior.hip")
+    assert "*looped = slots > e2hmm::SEG_MAX_WAVES || (body && strcmp(body, \"looped\") == 0);" in _source("hmm_class_loop.cpp")
+
+
+# ---- where every row goes --------------------------------------------------------------------------------------------------------
+# name: decoder: (body, lA in LDS, lt in LDS or None, more than 64 KB of dynamic LDS); only the decoders the GPU file runs the row through
+ROUTES = {
+    "64x64": {"segment": ("looped", False, None, True), "stream": ("looped", False, None, True)},
+    "1x4096": {"segment": ("looped", True, None, True)},
+    "1x1024": {"segment": ("resident", True, None, False), "posteriors": ("resident", True, None, False),
+               "trans": ("resident", True, False, False)},
+    "33x20": {"segment": ("looped", False, None, False), "stream": ("looped", False, None, False)},
+    "40_1x24_x14": {"segment": ("resident", False, None, False), "posteriors": ("resident", False, None, False)},
+}
+
+
+@pytest.mark.parametrize("name", list(cases.SHAPES))
+def test_every_row_reaches_the_body_and_the_placement_its_comment_names(name):
+    Ns = cases.SHAPES[name][0]
+    assert sum(Ns) <= cases.SEG_MAX_SUM_N
+    for decoder, (body, a_lds, lt_lds, big) in ROUTES[name].items():
+        r = cases.route(decoder, Ns)
+        assert (r["body"], r["a_lds"], r["lt_lds"], r["lds"] > cases.LDS_OPT_IN) == (body, a_lds, lt_lds, big), (decoder, r)
+        assert r["lds"] <= cases.SEG_LDS_BYTES
+    slots = cases.slots_of(Ns)
+    assert slots == {"64x64": 64, "1x4096": 64, "1x1024": 16, "33x20": 20, "40_1x24_x14": 14}[name]
+    if name in ("64x64", "1x4096"):  # the documented maximum: four turns to each of a looped workgroup's 16 waves
+        assert sum(Ns) == cases.SEG_MAX_SUM_N and slots == 4 * cases.SEG_MAX_WAVES
+        assert 2 * sum(Ns) * 8 == cases.LDS_OPT_IN  # (d of two steps alone is 64 KB: the pairs put the sum above it)
+    if name == "40_1x24_x14":  # (the row of test_gpu_hmm_segment_trans.py, where both lA and lt are read from global memory)
+        assert cases.route("trans", Ns)["a_lds"] is False and cases.route("trans", Ns)["lt_lds"] is False
+
+
+def test_the_event_models_reach_both_bodies_and_lA_in_both_places():
+    small, mid, wide = ([len(m[0]) for m in cases.event_models(name)] for name in ("5_3_4", "64x6", "64x17"))
+    assert small == [5, 3, 4] and mid == [64] * 6 and wide == [64] * 17
+    for decoder in ("segment", "stream"):  # k_hmm_segment<LOOPED, A_LDS> and k_hmm_segment_stream<LOOPED, A_LDS>
+        assert cases.route(decoder, small)["body"] == "resident" and cases.route(decoder, small)["a_lds"]      # <false, true>
+        assert cases.route(decoder, small, looped=True) == dict(body="looped", a_lds=True, lt_lds=None,
+                                                               lds=512 + 50 * 8 + 2 * 12 * 8)                  # <true, true>
+        assert cases.route(decoder, mid)["body"] == "resident" and not cases.route(decoder, mid)["a_lds"]      # <false, false>
+        assert cases.route(decoder, wide)["body"] == "looped" and not cases.route(decoder, wide)["a_lds"]      # <true, false>
+    for models in (cases.event_models(name) for name in cases.EVENT_NS):
+        assert all(not B[:, cases.DEAD].any() and (np.delete(B, cases.DEAD, axis=1) > 0).all() and (A > 0).all() and (pi > 0).all()
+                   for pi, A, B in models)
+    # the posteriors' zero fill of a failed stream, x = threadIdx.x; x < T * K; x += blockDim.x, takes 7 turns there
+    assert cases.EVENT_T * len(small) > 6 * 64 * cases.slots_of(small)
+
+
+# ---- what makes a row worth running ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(cases.SHAPES))
+def test_the_path_of_every_row_visits_many_classes_in_many_slots(name):
+    Ns, _M, T = cases.SHAPES[name]
+    want = cases.shape_reference(name)
+    v = cases.visit(Ns, want["cls"], want["entered"])
+    print(name, "segments", v["segments"], "classes", v["classes"], "slots", len(v["slots"]), "of", cases.slots_of(Ns))
+    assert want["status"] == 0 and len(want["cls"]) == T and v["segments"] >= 10 and v["last_slot"]
+    if name == "40_1x24_x14":
+        # M = 4 there, and the classes that lean to one symbol differ only in how far: one of them takes every run of it.
+        # The row is kept for its placement (lA beyond LDS with 25 classes to a slot), not for its path.
+        assert v["classes"] >= 4
+        return
+    assert 2 * len(v["slots"]) >= cases.slots_of(Ns) or len(v["slots"]) >= 16
+    # (composite indices beyond 3072 hold part of the path: the third and fourth state of a coalesce thread)
+    if sum(Ns) == cases.SEG_MAX_SUM_N:
+        comp0 = np.concatenate([[0], np.cumsum(Ns)])
+        comp = comp0[want["cls"]] + want["state"]
+        assert (comp >= 3 * cases.COALESCE_THREADS).any() and (comp >= 2 * cases.COALESCE_THREADS).sum() > T // 4
+
+
+@pytest.mark.parametrize("name", cases.SESSION_SHAPES)
+def test_a_session_over_the_row_decides_frames_after_every_block(name):
+    _Ns, _M, T = cases.SHAPES[name]
+    B = cases.SESSION_B
+    rest, finals = cases.session_reference(name, "whole_blocks")
+    print(name, "final after each block:", finals)
+    assert rest.join_failures == 0 and rest.status == 0
+    assert len(finals) == T // B + 1 and finals[0] > 0 and all(b > a for a, b in zip(finals, finals[1:T // B]))
+    assert all(f <= (i + 1) * B for i, f in enumerate(finals))
+    want = cases.shape_reference(name)
+    assert rest.cls == want["cls"].tolist() and rest.state == want["state"].tolist() and rest.entered == want["entered"].tolist()
+    assert np.array_equal(_bits(rest.gbest), _bits(want["gbest"])) and _bits(rest.log_prob)[0] == _bits(want["log_prob"])[0]
+    if name == "64x64":  # live paths at composite indices above 3072 when the walk starts: d > -inf there after every block
+        assert all((rest.ds[(i + 1) * B - 1][3 * cases.COALESCE_THREADS:] > NINF).any() for i in range(T // B))
+
+
+# ---- the event streams -----------------------------------------------------------------------------------------------------------
+def test_the_event_batch_is_the_one_the_align_tests_use():
+    streams, kinds = cases.event_batch()
+    assert len(streams) == 19 and kinds == ["clean"] + ["M"] * 6 + ["dead"] * 6 + ["dead_M", "M_dead"] * 3
+    assert all(len(s) == cases.EVENT_T == 130 for s in streams) and cases.EVENT_EDGES == (0, 1, 63, 64, 65, 129)
+    assert streams[0].max() < cases.DEAD < cases.EVENT_M == 8
+    for s, p in zip(streams[1:7], cases.EVENT_EDGES):
+        assert np.flatnonzero(s != streams[0]).tolist() == [p] and s[p] == cases.EVENT_M
+    for s, p in zip(streams[7:13], cases.EVENT_EDGES):
+        assert np.flatnonzero(s != streams[0]).tolist() == [p] and s[p] == cases.DEAD
+
+
+@pytest.mark.parametrize("name", ["5_3_4", "64x17"])
+def test_the_vectorised_restatements_are_their_literal_forms_on_the_event_streams(name):
+    looped = name == "64x17"
+    models = cases.event_models(name)
+    streams, kinds = cases.event_batch()
+    if looped:  # (the literal forms take a second a stream there: the clean one, one of each event, one pair of each order)
+        keep = [0, 3, 9, 15, 16]
+        streams, kinds = [streams[i] for i in keep], [kinds[i] for i in keep]
+    lms = [V.log_model(*m) for m in models]
+    lt = cases.event_prices(len(models))
+    ls = cases.EVENT_LN_SWITCH
+    for seq, kind in zip(streams, kinds):
+        a = R.segment_logs(lms, seq, ls)
+        c, s, e, G, lp, st = R.transcribe(models, seq, ls)
+        assert (a["cls"].tolist(), a["state"].tolist(), a["entered"].tolist(), a["status"]) == (c, s, e, st), kind
+        assert np.array_equal(_bits(a["gbest"]), _bits(G)) and _bits(a["log_prob"])[0] == _bits(lp)[0], kind
+        assert st == cases.event_status(kind, "segment")
+        a = RT.segment_trans_logs(lms, seq, lt)
+        c, s, e, ex, lp, st = RT.transcribe(models, seq, lt)
+        assert (a["cls"].tolist(), a["state"].tolist(), a["entered"].tolist(), a["status"]) == (c, s, e, st), kind
+        assert np.array_equal(_bits(a["exit_score"]), _bits(ex)) and _bits(a["log_prob"])[0] == _bits(lp)[0], kind
+        assert st == cases.event_status(kind, "trans")
+        if looped:
+            continue  # (17 slots: the posteriors refuse them)
+        a = RP.posteriors_one(models, seq, ls)
+        post, lp, st = RP.transcribe(models, seq, ls)
+        assert np.array_equal(_bits(a["post"]), _bits(np.array(post).reshape(len(seq), len(models)))), kind
+        assert _bits(a["log_prob"])[0] == _bits(lp)[0] and a["status"] == st == cases.event_status(kind, "posteriors"), kind
+        if st != 0:
+            assert not a["post"].any() and not np.signbit(a["post"]).any()
+
+
+def test_the_status_of_every_event_stream_in_every_decoder():
+    want = {"clean": (0, 0, 0, 0), "M": (2, 2, 2, 2), "dead": (1, 1, 1, 1), "M_dead": (2, 2, 2, 2), "dead_M": (2, 2, 1, 2)}
+    for kind in cases.EVENT_KINDS:
+        assert tuple(cases.event_status(kind, d) for d in ("segment", "trans", "posteriors", "stream")) == want[kind]
+    # the session, whatever the feeds: the restatement's status at close
+    lms = [V.log_model(*m) for m in cases.event_models()]
+    streams, kinds = cases.event_batch()
+    for seq, kind in zip(streams, kinds):
+        for feeds in ([130], [64, 66], [1] * 130):
+            log = cases.session_script(lms, seq, cases.EVENT_LN_SWITCH, cases.EVENT_SESSION_B, feeds)
+            assert log[-1]["status"] == cases.event_status(kind, "stream"), (kind, feeds[0])
+            assert log[-1]["final"] == log[-1]["fed"]  # (130, but for a feed that failed: what came after it was never given)
+
+
+def test_what_the_session_restatement_does_with_a_bad_symbol_at_each_edge():
+    lms = [V.log_model(*m) for m in cases.event_models()]
+    clean = cases.event_batch()[0][0]
+    B = cases.EVENT_SESSION_B
+    assert B == 100 and cases.SESSION_BAD_AT == (0, 63, 64, 99, 100, 129)
+    for p in cases.SESSION_BAD_AT:
+        seq = cases.with_symbols(clean, {p: cases.EVENT_M})
+        for feeds in ([130], [64, 66], [1] * 130):
+            log = cases.session_script(lms, seq, cases.EVENT_LN_SWITCH, B, feeds)
+            bad = [e for e in log if e.get("bad_frame") is not None]
+            if p < B:  # the feed that completes the first block fails, with the frame in the error; nothing was final before
+                assert len(bad) == 1 and bad[0]["bad_frame"] == p and bad[0]["final"] == 0, (p, feeds[0])
+                assert bad[0]["fed"] == {1: 130, 2: 130, 130: B}[len(feeds)]  # (all of the failing feed counts as fed)
+            else:  # the symbol waits in the remainder: no feed fails, and close meets it
+                assert not bad and log[-2]["final"] > 0, (p, feeds[0])
+            end = log[-1]
+            fed = B if p < B and len(feeds) == 130 else 130  # (single symbols: the 100th feed fails, the rest is never given)
+            assert (end["status"], end["log_prob"], end["final"], end["fed"]) == (2, NINF, fed, fed)
+            n = fed - log[-2]["final"]
+            assert end["out"]["cls"] == [0xFFFF] * n and end["out"]["gbest"] == [NINF] * n and end["out"]["entered"] == [0] * n
+
+
+# ---- the random sets -------------------------------------------------------------------------------------------------------------
+def test_the_random_sets_are_deterministic_and_meet_the_seed_rule():
+    seed = cases.RANDOM_SEED
+    assert cases.seed_rule(seed) and cases.first_seed(seed + 1) == seed == 4  # the first of 0, 1, 2, ... that meets the rule
+    a, b = cases.random_sets(seed), cases.random_sets(seed)
+    assert len(a) == 12
+    for x, y in zip(a, b):
+        assert x["Ns"] == y["Ns"] and x["M"] == y["M"] and _bits(x["ln_switch"])[0] == _bits(y["ln_switch"])[0]
+        assert all(np.array_equal(s, t) for s, t in zip(x["streams"], y["streams"])) and len(x["streams"]) == 6
+        assert all(np.array_equal(_bits(p), _bits(q)) for m, n in zip(x["models"], y["models"]) for p, q in zip(m, n))
+        assert 1 <= len(x["Ns"]) <= 24 and set(x["Ns"]) <= set(cases.RANDOM_NS) and x["M"] in cases.RANDOM_MS
+        assert x["ln_switch"] in cases.RANDOM_SWITCHES and all(len(s) <= 200 and (s < x["M"]).all() for s in x["streams"])
+    slots = [cases.slots_of(x["Ns"]) for x in a]
+    assert sum(s > 16 for s in slots) >= 3 and sum(cases.one_class_slot_next_to_packed(x["Ns"]) for x in a) >= 3
+    res = cases.random_sets(seed, resident_only=True)
+    assert len(res) == 12 and all(cases.slots_of(x["Ns"]) <= 16 for x in res)
+    # the sets that were resident as drawn keep their classes
+    assert all(x["Ns"] == y["Ns"] for x, y in zip(a, res) if cases.slots_of(x["Ns"]) <= 16)
+    print("slots:", slots, "resident:", [cases.slots_of(x["Ns"]) for x in res], "M:", [x["M"] for x in a],
+          "ln_switch:", [x["ln_switch"] for x in a])
