@@ -1,16 +1,14 @@
 // hmm_align.cpp -- forced alignment on the GPU (`hmm align`, e2vq_hmm_align): the most likely path of a
 // symbol stream through the units of its transcript, in their order, over the kernels of hmm_align.hip.  The host checks
-// the transcripts and packs each stream's units into wave-slots (all before any HIP call), cuts the launches by the table
-// budget, replays the decoded path for its per-frame score, and writes the reports.  Shape checks, models, packing and the
-// parameter block are hmm_class_loop.cpp's, the input stage and the label files hmm_input.cpp's (hmm_host.h).
+// runs the launches align_plan cut, replays the decoded path for its per-frame score, and writes the reports.  The checks,
+// the transcripts of the label files and align_plan are hmm_transcript.cpp's, models, packing and the parameter block
+// hmm_class_loop.cpp's, the input stage hmm_input.cpp's (hmm_host.h).
 #include "hmm_host.h"
 
 namespace e2hmm_host {
 namespace {
 
 thread_local float g_align_kernel_ms = -1.f;  // e2vq_hmm_align_last_kernel_ms
-
-constexpr int ALIGN_MAX_L = 65535;
 
 struct AlignOut {  // host arrays, any may be null; per frame: unit, state, entered, score; per unit: begin, end; per stream: the rest
     uint16_t* unit = nullptr;
@@ -22,111 +20,6 @@ struct AlignOut {  // host arrays, any may be null; per frame: unit, state, ente
     double* log_prob = nullptr;
     int* status = nullptr;
 };
-
-// may unit l hold frame 0 / the last frame (opt: the stream's flags, or null)
-bool unit_is_initial(int l, const uint8_t* opt) { return l == 0 || (l == 1 && opt && opt[0]); }
-bool unit_is_final(int l, int L, const uint8_t* opt) { return l == L - 1 || (l == L - 2 && opt && opt[L - 1]); }
-
-}  // namespace
-
-// (declared in hmm_host.h: hmm_embed.cpp plans with it too)
-int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded)
-{
-    if (segment_check_switch(who, ln_switch)) return 1;
-    if (std::isinf(ln_switch)) return e2vq_set_error("%s: ln_switch = %g: a finite price (every unit has to be entered)", who, ln_switch);
-    if (unit_offs[0] != 0) return e2vq_set_error("%s: unit_offs[0] = %lld, not 0", who, (long long)unit_offs[0]);
-    bool force_looped = false;
-    if (!embedded && loop_body_looped("ECOZ2_HMM_ALIGN_BODY", 0, &force_looped)) return 1;  // (the E-step has one body)
-    const i64 budget = env_bytes("ECOZ2_HMM_ALIGN_TABLE_BYTES", (i64)4 << 30);
-    ap.cls = pack_slots(std::vector<int>(Ns, Ns + K));
-    const SegPacking& cls = ap.cls;
-    std::vector<bool> looped((size_t)S);
-    std::vector<i64> bytes((size_t)S);
-    ap.streams.resize((size_t)S);
-    for (int s = 0; s < S; ++s) {
-        const i64 u0 = unit_offs[s], L64 = unit_offs[s + 1] - u0;
-        if (L64 < 0) return e2vq_set_error("%s: unit_offs decrease at stream %d", who, s);
-        if (L64 < 1) return e2vq_set_error("%s: stream %d has an empty transcript", who, s);
-        if (L64 > ALIGN_MAX_L) return e2vq_set_error("%s: stream %d has %lld units (at most %d)", who, s, (long long)L64, ALIGN_MAX_L);
-        const int L = (int)L64;
-        const int32_t* u = units + u0;
-        const uint8_t* opt = optional ? optional + u0 : nullptr;
-        std::vector<int> uN((size_t)L);
-        i64 sumN = 0;
-        bool mandatory = false;
-        for (int l = 0; l < L; ++l) {
-            if (u[l] < 0 || u[l] >= K) return e2vq_set_error("%s: stream %d, unit %d names the class %d outside [0, %d)", who, s, l, u[l], K);
-            if (opt && opt[l] && l > 0 && opt[l - 1])
-                return e2vq_set_error("%s: stream %d, units %d and %d are both optional (a path may pass over one unit only)", who, s, l - 1, l);
-            mandatory = mandatory || !(opt && opt[l]);
-            uN[(size_t)l] = Ns[u[l]];
-            sumN += Ns[u[l]];
-        }
-        if (!mandatory) return e2vq_set_error("%s: stream %d: every unit of the transcript is optional", who, s);
-        if (!e2hmm::align_fits_lds(L, (int)sumN, false))
-            return e2vq_set_error("%s: stream %d: %d units of sum N = %lld states do not fit in LDS (%zu of %zu bytes)", who, s, L,
-                                  (long long)sumN, e2hmm::align_lds_bytes(L, (int)sumN, 0, false, false), e2hmm::SEG_LDS_BYTES);
-        const SegPacking pk = pack_slots(uN);
-        looped[(size_t)s] = force_looped || pk.slots > e2hmm::SEG_MAX_WAVES;
-        if (looped[(size_t)s] && !e2hmm::align_fits_lds(L, pk.sumN, true))
-            return e2vq_set_error("%s: stream %d: %d units of sum N = %d states in %d wave-slots do not fit in LDS (%zu of %zu bytes)", who,
-                                  s, L, pk.sumN, pk.slots, e2hmm::align_lds_bytes(L, pk.sumN, 0, true, false), e2hmm::SEG_LDS_BYTES);
-        const i64 T = offs[s + 1] - offs[s];
-        bytes[(size_t)s] = T * ((i64)pk.sumN + L);
-        if (bytes[(size_t)s] > budget && embedded)  // (no back-pointers there: the bound alone is `hmm align`'s)
-            return e2vq_set_error("%s: stream %d: %lld frames x (%d states + %d units) = %lld exceed ECOZ2_HMM_ALIGN_TABLE_BYTES=%lld, the "
-                                  "bound on a stream that `hmm align` sets and that holds here too",
-                                  who, s, (long long)T, pk.sumN, L, (long long)bytes[(size_t)s], (long long)budget);
-        if (bytes[(size_t)s] > budget)
-            return e2vq_set_error("%s: stream %d: the back-pointers of %lld frames x (%d states + %d units) take %lld bytes: more than "
-                                  "ECOZ2_HMM_ALIGN_TABLE_BYTES=%lld",
-                                  who, s, (long long)T, pk.sumN, L, (long long)bytes[(size_t)s], (long long)budget);
-        e2hmm::AlignStreamDev& sd = ap.streams[(size_t)s];
-        sd.lane_at = (i64)ap.lanes.size();
-        sd.tab_at = 0;
-        sd.unit_at = u0;
-        sd.comp_at = (i64)ap.comp_unit.size();
-        sd.slots = pk.slots, sd.L = L, sd.sumN = pk.sumN, sd.pad = 0;
-        for (const e2hmm::SegLaneDev& sl : pk.lanes) {
-            e2hmm::AlignLaneDev al{-1, 0, 0, sl.seg, 0, 0, 0, 0};
-            if (sl.cls >= 0) {
-                const int l = sl.cls, k = u[l];
-                const int flags = (unit_is_initial(l, opt) ? e2hmm::ALIGN_INIT : 0) | (l >= 1 ? e2hmm::ALIGN_PRED : 0) |
-                                  (l >= 2 && opt && opt[l - 1] ? e2hmm::ALIGN_SKIP : 0) | (unit_is_final(l, L, opt) ? e2hmm::ALIGN_FINAL : 0);
-                al = e2hmm::AlignLaneDev{l, sl.j, sl.N, sl.seg, sl.comp, cls.comp0[(size_t)k] + sl.j, cls.a_at[(size_t)k], flags};
-            }
-            ap.lanes.push_back(al);
-        }
-        ap.slot_info.insert(ap.slot_info.end(), pk.slot_info.begin(), pk.slot_info.end());
-        ap.unit_comp0.insert(ap.unit_comp0.end(), pk.comp0.begin(), pk.comp0.end());
-        ap.comp_unit.insert(ap.comp_unit.end(), pk.comp_cls.begin(), pk.comp_cls.end());
-    }
-    // the launches: consecutive streams of one body whose tables stay within the budget and whose largest L and sum N fit LDS
-    // (the E-step cuts its own)
-    for (int s0 = 0; s0 < S && !embedded;) {
-        AlignPlan::Launch g{s0, s0, 0, 0, 0, looped[(size_t)s0], 0};
-        int slots = 0;
-        while (g.s1 < S) {
-            const e2hmm::AlignStreamDev& sd = ap.streams[(size_t)g.s1];
-            const int mL = std::max(g.max_L, sd.L), mN = std::max(g.max_sumN, sd.sumN);
-            if (g.s1 > s0 && (looped[(size_t)g.s1] != g.looped || g.bytes + bytes[(size_t)g.s1] > budget || !e2hmm::align_fits_lds(mL, mN, g.looped)))
-                break;
-            ap.streams[(size_t)g.s1].tab_at = g.bytes;
-            g.bytes += bytes[(size_t)g.s1];
-            g.max_L = mL, g.max_sumN = mN;
-            slots = std::max(slots, sd.slots);
-            ++g.s1;
-        }
-        g.waves = std::min(slots, e2hmm::SEG_MAX_WAVES);
-        ap.max_bytes = std::max(ap.max_bytes, g.bytes);
-        ap.launches.push_back(g);
-        s0 = g.s1;
-    }
-    return 0;
-}
-
-namespace {
 
 // the path's own cumulative score, frame by frame, from the decoded path: one addition per term in the device's order
 void align_replay(const LoopModels& lm, const uint16_t* sym, i64 T, const int32_t* units, const uint8_t* opt, double ln_switch,
@@ -250,9 +143,7 @@ extern "C" int e2vq_hmm_align(int device, int K, const int* Ns, int M, const dou
 {
     const char* who = "e2vq_hmm_align";
     LoopModels lm;
-    if (loop_check_args(who, K, Ns, pis, As, Bs, offs && unit_offs && (S <= 0 || units) && syms_given(sym, offs, S)) ||
-        segment_check_shape(who, K, Ns) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs() || check_offsets(offs, S))
-        return 1;
+    if (transcript_check_args(who, K, Ns, M, pis, As, Bs, sym, offs, S, units, unit_offs, lm)) return 1;
     AlignPlan ap;
     if (align_plan(who, K, Ns, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, ap)) return 1;
     // ---- the device from here on --------------------------------------------------------------------------------
@@ -269,38 +160,21 @@ extern "C" int e2vq_hmm_align_report(const char* name, int64_t T, int K, const c
 {
     const char* who = "e2vq_hmm_align_report";
     FlushStdout flush_on_return;
-    if (!name || K < 1 || !class_names || T < 0 || L < 1 || !units || !begin || !end || (T > 0 && !score)) return e2vq_set_error("%s: bad arguments", who);
-    int skipped = 0;
-    for (int l = 0; l < L; ++l) {
-        if (units[l] < 0 || units[l] >= K) return e2vq_set_error("%s: unit %d names a model outside [0, %d)", who, l, K);
-        if (begin[l] < 0) {
-            skipped += optional && optional[l] ? 1 : 0;
-            continue;
-        }
-        if (begin[l] >= end[l] || end[l] > T) return e2vq_set_error("%s: unit %d spans [%lld, %lld) of %lld frames", who, l, (long long)begin[l], (long long)end[l], (long long)T);
-    }
-    auto begin_s = [&](int64_t b) { return (double)(b * O_ms) / 1000.0; };
-    // (the end of the analysis window of the unit's last frame)
-    auto end_s = [&](int64_t e) { return (double)((e - 1) * O_ms + W_ms) / 1000.0; };
-    auto unit_score = [&](int l) { return score[end[l] - 1] - (begin[l] == 0 ? 0.0 : score[begin[l] - 1] + ln_switch); };
+    const int skipped = align_report_check(who, name, T, K, class_names, L, units, optional, begin, end, score, true);
+    if (skipped < 0) return 1;
     if (csv_filename && *csv_filename) {
         std::string doc = "unit,class,begin_frame,end_frame,begin_s,end_s,score\n";
         for (int l = 0; l < L; ++l) {
             if (begin[l] < 0) continue;
             doc += std::to_string(l) + "," + class_names[units[l]] + "," + std::to_string(begin[l]) + "," + std::to_string(end[l]) + "," +
-                   fmt_17g(begin_s(begin[l])) + "," + fmt_17g(end_s(end[l])) + "," + fmt_17g(unit_score(l)) + "\n";
+                   fmt_17g(align_time_s(begin[l], O_ms)) + "," + fmt_17g(align_time_s(end[l] - 1, O_ms, W_ms)) + "," +
+                   fmt_17g(align_unit_score(score, begin, end, l, ln_switch)) + "\n";
         }
         if (write_file(csv_filename, std::vector<unsigned char>(doc.begin(), doc.end()))) return 1;
     }
-    printf("%s: T=%lld  units=%d  optional units passed over=%d  log_prob=%g  (switch penalty %g)\n", name, (long long)T, L, skipped, log_prob,
-           ln_switch);
-    std::vector<int64_t> count((size_t)K, 0);
+    align_report_head(name, T, K, class_names, L, units, begin, end, skipped, log_prob, ln_switch);
     for (int l = 0; l < L; ++l)
-        if (begin[l] >= 0) count[(size_t)units[l]] += end[l] - begin[l];
-    for (int k = 0; k < K; ++k) printf("  '%s': %lld\n", class_names[k], (long long)count[(size_t)k]);
-    printf("  units:\n");
-    for (int l = 0; l < L; ++l)
-        if (begin[l] >= 0) printf("    %.3f - %.3f %s\n", begin_s(begin[l]), end_s(end[l]), class_names[units[l]]);
+        if (begin[l] >= 0) printf("    %.3f - %.3f %s\n", align_time_s(begin[l], O_ms), align_time_s(end[l] - 1, O_ms, W_ms), class_names[units[l]]);
     if (csv_filename && *csv_filename) printf("  %s saved\n", csv_filename);
     return 0;
 }
@@ -317,43 +191,18 @@ extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned
         return 1;
     const int K = fm.K();
     const std::vector<int>& Ns = fm.Ns;
-    auto class_of = [&](const std::string& name) {
-        int k = 0;
-        while (k < K && name != fm.names[(size_t)k]) ++k;
-        return k < K ? k : -1;
-    };
-    int filler = -1;
-    if (filler_class && *filler_class && (filler = class_of(filler_class)) < 0)
-        return e2vq_set_error("%s: the filler '%s' is no model's class", who, filler_class);
+    Transcripts tr;
+    if (tr.set_filler(who, fm, filler_class)) return 1;
     if (fm.logs(model_filenames)) return 1;
     SymInputs si;
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, si)) return 1;
-    // the transcripts: the labels of file i in their order, the filler around and between them
-    std::vector<std::vector<int32_t>> units((size_t)num_inputs);
-    std::vector<std::vector<uint8_t>> optional((size_t)num_inputs);
     for (int f = 0; f < num_inputs; ++f) {
-        const char* path = label_filenames[f];
-        if (!path) return e2vq_set_error("%s: NULL file name", who);
-        std::vector<LabelRow> rows;
-        if (read_label_file(path, rows)) return 1;
-        if (rows.empty()) return e2vq_set_error("%s: no labelled units", path);
-        std::vector<int32_t>& u = units[(size_t)f];
-        std::vector<uint8_t>& o = optional[(size_t)f];
-        auto fill = [&] {
-            if (filler >= 0) u.push_back(filler), o.push_back(1);
-        };
-        fill();
-        for (const LabelRow& r : rows) {
-            const int k = class_of(r.label);
-            if (k < 0) return e2vq_set_error("%s:%zu: '%s' is no model's class", path, r.line, r.label.c_str());
-            u.push_back(k), o.push_back(0);
-            fill();
-        }
+        if (tr.add_labels(who, fm, label_filenames[f])) return 1;
         // (with the frame count known so far: a .wav may still lose frames, which only shrinks the tables)
-        const i64 offs[2] = {0, si.inputs[(size_t)f].T}, uoffs[2] = {0, (i64)u.size()};
+        const i64 offs[2] = {0, si.inputs[(size_t)f].T}, uoffs[2] = {0, tr.L(f)};
         AlignPlan ap;
-        if (align_plan(who, K, Ns.data(), offs, 1, u.data(), uoffs, o.data(), ln_switch, ap))
-            return e2vq_set_error("%s: %s", path, std::string(e2vq_last_error()).c_str());
+        if (align_plan(who, K, Ns.data(), offs, 1, tr.u(f), uoffs, tr.o(f), ln_switch, ap))
+            return e2vq_set_error("%s: %s", label_filenames[f], std::string(e2vq_last_error()).c_str());
     }
     // ---- the device from here on --------------------------------------------------------------------------------
     const int device = env_device();
@@ -361,25 +210,26 @@ extern "C" int e2vq_hmm_align_files(const char* const* model_filenames, unsigned
     if (require_device(device) || stg.open(device, si)) return 1;
     for (int f = 0; f < num_inputs; ++f) {
         const SymInput& in = si.inputs[(size_t)f];
-        const std::vector<int32_t>& u = units[(size_t)f];
-        const std::vector<uint8_t>& o = optional[(size_t)f];
+        const int32_t* u = tr.u(f);
+        const uint8_t* o = tr.o(f);
+        const size_t L = (size_t)tr.L(f);
         int64_t T = 0;
         if (stg.input(in, si, P, W_ms, O_ms, &T)) return 1;
-        const i64 offs[2] = {0, T}, uoffs[2] = {0, (i64)u.size()};
+        const i64 offs[2] = {0, T}, uoffs[2] = {0, (i64)L};
         AlignPlan ap;
-        if (align_plan(who, K, Ns.data(), offs, 1, u.data(), uoffs, o.data(), ln_switch, ap)) return 1;
+        if (align_plan(who, K, Ns.data(), offs, 1, u, uoffs, o, ln_switch, ap)) return 1;
         std::vector<double> score((size_t)std::max<int64_t>(T, 1));
-        std::vector<int64_t> begin(u.size()), end(u.size());
+        std::vector<int64_t> begin(L), end(L);
         double lp = 0.0;
         int status = 0;
         AlignOut out;
         out.score = score.data(), out.begin = begin.data(), out.end = end.data(), out.log_prob = &lp, out.status = &status;
-        if (align_device(who, ap, fm, stg.d_sym.get(), offs, 1, u.data(), uoffs, o.data(), ln_switch, stg.st.s, out)) return 1;
+        if (align_device(who, ap, fm, stg.d_sym.get(), offs, 1, u, uoffs, o, ln_switch, stg.st.s, out)) return 1;
         if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), fm.M);
         if (status == 1)
             return e2vq_set_error("%s: %lld frames cannot be aligned to the %zu units of %s (no path of probability > 0)", in.path.c_str(),
-                                  (long long)T, u.size(), label_filenames[f]);
-        if (e2vq_hmm_align_report(in.path.c_str(), T, K, fm.names.data(), W_ms, O_ms, (int)u.size(), u.data(), o.data(), begin.data(),
+                                  (long long)T, L, label_filenames[f]);
+        if (e2vq_hmm_align_report(in.path.c_str(), T, K, fm.names.data(), W_ms, O_ms, (int)L, u, o, begin.data(),
                                   end.data(), score.data(), lp, ln_switch, in.csv.empty() ? nullptr : in.csv.c_str()))
             return 1;
     }

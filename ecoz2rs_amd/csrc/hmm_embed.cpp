@@ -1,9 +1,9 @@
 // hmm_embed.cpp -- embedded (transcript-constrained) Baum-Welch on the GPU (`hmm learn --embedded`, e2vq_hmm_embedded_estep,
 // e2vq_hmm_train_embedded): the class models re-estimated from whole streams and the order of their units,
-// over the kernels of hmm_embed.hip.  The host checks the transcripts and packs each stream's units into wave-slots with
-// hmm_align.cpp's align_plan (all before any HIP call), cuts the launches by the scratch budget, takes the logarithm of the
-// (mantissa, exponent) pairs, sums ln P over the streams in stream order, decides when to stop, and writes the models and the
-// report.  Shape checks and models are hmm_class_loop.cpp's, the input stage and the label files hmm_input.cpp's (hmm_host.h).
+// over the kernels of hmm_embed.hip.  The host adds the accumulator and M-step places and the AN table to hmm_transcript.cpp's
+// plan (all before any HIP call), takes the logarithm of the (mantissa, exponent) pairs, sums ln P over the streams in stream
+// order, decides when to stop, and writes the models and the report.  The checks, the transcripts of the label files, the plan
+// and the parameter block are hmm_transcript.cpp's, the models hmm_class_loop.cpp's, the input stage hmm_input.cpp's (hmm_host.h).
 #include "hmm_host.h"
 
 namespace e2hmm_host {
@@ -13,65 +13,23 @@ thread_local float g_embed_kernel_ms = -1.f;  // e2vq_hmm_embedded_last_kernel_m
 
 constexpr int EMBED_MAX_ESTEPS = 1000;  // the safety cap of the other trainers (hmm_train.cpp: MAX_ESTEPS)
 
-int embed_a_ld(int N) { return N | 1; }  // (odd: see hmm_embed.hip)
-
-// "lds" / "global" / unset of the variable `name` -> *forced (whether it is set) and *lds; any other value is refused
-int embed_route(const char* name, bool* forced, bool* lds)
-{
-    const char* v = getenv(name);
-    *forced = v && *v;
-    if (!*forced) return 0;
-    if (strcmp(v, "lds") != 0 && strcmp(v, "global") != 0) return e2vq_set_error("%s=%s: lds or global", name, v);
-    *lds = strcmp(v, "lds") == 0;
-    return 0;
-}
-
-// What the host decides about a call before the device is touched: align_plan's packing of every stream with the three
-// flags the E-step adds, the classes' places in the parameter, count and M-step blocks, the LDS layout and the launches.
-struct EmbedPlan {
-    AlignPlan ap;
-    SegPacking cls;  // the classes, A with the leading dimension N | 1
-    std::vector<e2hmm::EmbedClassDev> classes;
-    std::vector<uint16_t> row_cls;
+// What the host decides about a call before the device is touched: the plan of the forward-backward pass with EMBED_FIRST, the
+// classes' places in the count and M-step blocks, and the LDS layout.
+struct EmbedPlan : EStepPlan {
     std::vector<i64> acc_at;  // [K + 1]
-    i64 dense_words = 0, max_P = 0, row_words = 0, max_frames = 0;
-    int max_L = 0, max_N = 0, max_slots = 0;
-    bool a_lds = false, an_lds = false;
-    std::vector<std::pair<int, int>> chunks;
+    i64 dense_words = 0, max_P = 0;
+    int max_N = 0;
+    bool an_lds = false;
 };
 
 int embed_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
                const uint8_t* optional, double ln_switch, EmbedPlan& ep)
 {
-    if (align_plan(who, K, Ns, offs, S, units, unit_offs, optional, ln_switch, ep.ap, /*embedded=*/true)) return 1;
-    int max_sumN = 0;
-    for (int s = 0; s < S; ++s) {
-        e2hmm::AlignStreamDev& sd = ep.ap.streams[(size_t)s];
-        if (sd.slots > e2hmm::SEG_MAX_WAVES)
-            return e2vq_set_error("%s: stream %d: the units take %d wave-slots of 64 lanes (at most %d: the embedded E-step has no looped body)",
-                                  who, s, sd.slots, e2hmm::SEG_MAX_WAVES);
-        ep.max_L = std::max(ep.max_L, sd.L);
-        ep.max_slots = std::max(ep.max_slots, sd.slots);
-        max_sumN = std::max(max_sumN, sd.sumN);
-        const int32_t* u = units + unit_offs[s];
-        const uint8_t* opt = optional ? optional + unit_offs[s] : nullptr;
-        std::vector<int> first((size_t)K, -1);
-        for (int l = sd.L - 1; l >= 0; --l) first[(size_t)u[l]] = l;
-        for (int x = 0; x < sd.slots * 64; ++x) {
-            e2hmm::AlignLaneDev& al = ep.ap.lanes[(size_t)sd.lane_at + (size_t)x];
-            if (al.unit < 0) continue;
-            const int l = al.unit;
-            al.flags |= (first[(size_t)u[l]] == l ? e2hmm::EMBED_FIRST : 0) | (l + 1 < sd.L ? e2hmm::EMBED_SUCC : 0) |
-                        (l + 2 < sd.L && opt && opt[l + 1] ? e2hmm::EMBED_SUCC2 : 0);
-        }
-    }
-    ep.cls = pack_slots(std::vector<int>(Ns, Ns + K), embed_a_ld);
-    ep.classes.resize((size_t)K);
-    ep.row_cls = ep.cls.comp_cls;
+    if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the embedded E-step has no looped body", true, ep)) return 1;
     ep.acc_at.assign((size_t)K + 1, 0);
     for (int k = 0; k < K; ++k) {
         const int N = Ns[k];
-        ep.classes[(size_t)k] = e2hmm::EmbedClassDev{N, ep.cls.a_at[(size_t)k], ep.acc_at[(size_t)k], ep.dense_words};
+        ep.classes[(size_t)k].acc_at = ep.acc_at[(size_t)k], ep.classes[(size_t)k].param_at = ep.dense_words;
         ep.acc_at[(size_t)k + 1] = ep.acc_at[(size_t)k] + e2hmm::acc_words(N, M);
         const i64 P = (i64)N + (i64)N * N + (i64)N * M;
         ep.dense_words += P;
@@ -79,68 +37,31 @@ int embed_plan(const char* who, int K, const int* Ns, int M, const i64* offs, in
         ep.max_N = std::max(ep.max_N, N);
     }
     // the LDS layout: A when it fits, then the AN table when it fits as well; either route may be forced
-    bool fa = false, fan = false;
-    if (embed_route("ECOZ2_HMM_EMBED_A", &fa, &ep.a_lds) || embed_route("ECOZ2_HMM_EMBED_AN", &fan, &ep.an_lds)) return 1;
+    bool fan = false;
+    if (embed_route("ECOZ2_HMM_EMBED_AN", &fan, &ep.an_lds)) return 1;
     const int aw = ep.cls.a_words;
-    if (!fa) ep.a_lds = e2hmm::embed_lds_bytes(ep.max_L, aw, true, fan && ep.an_lds) <= e2hmm::SEG_LDS_BYTES;
+    if (!ep.a_forced) ep.a_lds = e2hmm::embed_lds_bytes(ep.max_L, aw, true, fan && ep.an_lds) <= e2hmm::SEG_LDS_BYTES;
     if (!fan) ep.an_lds = e2hmm::embed_lds_bytes(ep.max_L, aw, ep.a_lds, true) <= e2hmm::SEG_LDS_BYTES;
     const size_t lds = e2hmm::embed_lds_bytes(ep.max_L, aw, ep.a_lds, ep.an_lds);
     if (lds > e2hmm::SEG_LDS_BYTES)
         return e2vq_set_error("%s: %d units, A in %s and the AN table in %s take %zu bytes of LDS (at most %zu)", who, ep.max_L,
                               ep.a_lds ? "LDS" : "global memory", ep.an_lds ? "LDS" : "global memory", lds, e2hmm::SEG_LDS_BYTES);
-    // launches of whole streams whose scratch (ah and m: 8 sumN bytes a frame each, c: 8 bytes a frame and wave) stays within
-    // the budget; every stream's rows are counted at the widest stream's width
-    ep.row_words = 2 * (i64)max_sumN + e2hmm::SEG_MAX_WAVES;
-    ep.chunks = plan_chunks("ECOZ2_HMM_EMBED_CHUNK_BYTES", 8 * ep.row_words, offs, S, &ep.max_frames);
     return 0;
-}
-
-// pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class
-std::vector<double> embed_params(const LoopModels& lm, const SegPacking& pk, double sw)
-{
-    const int sumN = pk.sumN, M = lm.M;
-    std::vector<double> params((size_t)2 * sumN + (size_t)pk.a_words + (size_t)sumN * M, 0.0);
-    for (int k = 0; k < lm.K(); ++k) {
-        const Hmm& h = *lm.ms[(size_t)k];
-        const int N = h.N, ld = embed_a_ld(N), c0 = pk.comp0[(size_t)k];
-        for (int j = 0; j < N; ++j) {
-            params[(size_t)(c0 + j)] = h.pi[(size_t)j];
-            params[(size_t)(sumN + c0 + j)] = sw * h.pi[(size_t)j];
-            std::copy(h.A.begin() + (size_t)j * N, h.A.begin() + (size_t)(j + 1) * N,
-                      params.begin() + 2 * sumN + pk.a_at[(size_t)k] + (size_t)j * ld);
-        }
-        std::copy(h.B.begin(), h.B.end(), params.begin() + 2 * sumN + pk.a_words + (size_t)c0 * M);
-    }
-    return params;
 }
 
 // The device side of a planned call: the tables, the scratch and the accumulators, kept over the iterations of a training.
 struct EmbedDev {
-    DeviceBuffer<e2hmm::AlignLaneDev> d_lanes;
-    DeviceBuffer<e2hmm::AlignStreamDev> d_streams;
-    DeviceBuffer<int> d_info;
-    DeviceBuffer<e2hmm::EmbedClassDev> d_classes;
-    DeviceBuffer<unsigned short> d_row_cls;
-    DeviceBuffer<i64> d_offs, d_acc;
-    DeviceBuffer<double> d_params, d_dense, d_scr;
+    EStepDev pd;
+    DeviceBuffer<i64> d_acc;
+    DeviceBuffer<double> d_params, d_dense;
     Scores sc;  // P(O, transcript) of each stream
     std::vector<double> params, dense;
     KernelTimer timer;
 
     int setup(const char* who, const EmbedPlan& ep, const i64* h_offs, int S, hipStream_t st)
     {
-        const AlignPlan& ap = ep.ap;
-        if (d_lanes.upload(ap.lanes.data(), ap.lanes.size(), st) || d_streams.upload(ap.streams.data(), ap.streams.size(), st) ||
-            d_info.upload(ap.slot_info.data(), ap.slot_info.size(), st) || d_classes.upload(ep.classes.data(), ep.classes.size(), st) ||
-            d_row_cls.upload(ep.row_cls.data(), ep.row_cls.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) ||
-            d_acc.reserve((size_t)ep.acc_at.back()) || sc.reserve((size_t)S) || timer.create())
-            return 1;
-        if (d_scr.reserve((size_t)(ep.max_frames * ep.row_words))) {
-            const std::string why = e2vq_last_error();
-            return e2vq_set_error("%s: no room for the forward tables of %lld frames x %lld doubles (ECOZ2_HMM_EMBED_CHUNK_BYTES bounds "
-                                  "them by whole streams): %s", who, (long long)ep.max_frames, (long long)ep.row_words, why.c_str());
-        }
-        return 0;
+        return pd.upload(ep, h_offs, S, st) || d_acc.reserve((size_t)ep.acc_at.back()) || sc.reserve((size_t)S) || timer.create() ||
+               pd.scratch(who, ep);
     }
     // One E-step under the models: the counts of all streams in d_acc (zeroed first), P and status of every stream in sc's
     // host mirrors.  Waits for the stream.
@@ -155,14 +76,13 @@ struct EmbedDev {
         // (one stream: a chunk's forward pass writes the scratch only after the previous chunk's backward pass has read it)
         for (const auto& c : ep.chunks) {
             const int s0 = c.first, n = c.second - c.first;
-            const e2hmm::EmbedPlanDev pl{K, lm.M, ep.cls.sumN, ep.cls.a_words, ep.max_L, d_streams.get() + s0, d_lanes.get(),
-                                         d_info.get(), d_params.get(), d_classes.get(), d_row_cls.get()};
-            if (e2hmm::launch_embed_fb(pl, ep.a_lds, ep.an_lds, ep.max_slots, d_sym, d_offs.get() + s0, n, h_offs[s0], ep.row_words,
-                                       d_scr.get(), d_acc.get(), sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+            if (e2hmm::launch_embed_fb(pd.plan(ep, s0, d_params.get()), ep.a_lds, ep.an_lds, ep.max_slots, d_sym, pd.offs.get() + s0, n,
+                                       h_offs[s0], ep.row_words, pd.scr.get(), d_acc.get(), sc.d_mant.get() + s0, sc.d_exp.get() + s0,
+                                       sc.d_status.get() + s0, st))
                 return e2vq_set_error("%s: %d units in %d wave-slots cannot be launched", who, ep.max_L, ep.max_slots);
             HIPCHK(hipGetLastError());
         }
-        e2hmm::launch_embed_rowsum(d_classes.get(), K, ep.max_N, d_acc.get(), st);
+        e2hmm::launch_embed_rowsum(pd.classes.get(), K, ep.max_N, d_acc.get(), st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(timer.stop.e, st));
         if (sc.download((size_t)S, st)) return 1;
@@ -176,7 +96,7 @@ struct EmbedDev {
         dense.resize((size_t)ep.dense_words);
         for (int k = 0; k < K; ++k) lm.models[(size_t)k].pack(dense.data() + ep.classes[(size_t)k].param_at);
         if (d_dense.upload(dense.data(), dense.size(), st)) return 1;
-        e2hmm::launch_reestimate_embedded(d_classes.get(), K, lm.M, ep.max_P, ep.max_N, d_acc.get(), epsilon, d_dense.get(), st);
+        e2hmm::launch_reestimate_embedded(pd.classes.get(), K, lm.M, ep.max_P, ep.max_N, d_acc.get(), epsilon, d_dense.get(), st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(dense.data(), d_dense.get(), dense.size() * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -223,14 +143,6 @@ int embed_train(const char* who, const EmbedPlan& ep, EmbedDev& dev, LoopModels&
     return 0;
 }
 
-// the first checks of the two array-level entry points, in e2vq_hmm_align's order
-int embed_check(const char* who, int K, const int* Ns, int M, const double* const* pis, const double* const* As, const double* const* Bs,
-                const void* sym, const int64_t* offs, int S, const int32_t* units, const int64_t* unit_offs, LoopModels& lm)
-{
-    return loop_check_args(who, K, Ns, pis, As, Bs, offs && unit_offs && (S <= 0 || units) && syms_given(sym, offs, S)) ||
-           segment_check_shape(who, K, Ns) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs() || check_offsets(offs, S);
-}
-
 }  // namespace
 }  // namespace e2hmm_host
 using namespace e2hmm_host;
@@ -244,7 +156,7 @@ extern "C" int e2vq_hmm_embedded_estep(int device, int K, const int* Ns, int M, 
 {
     const char* who = "e2vq_hmm_embedded_estep";
     LoopModels lm;
-    if (embed_check(who, K, Ns, M, pis, As, Bs, sym, offs, S, units, unit_offs, lm)) return 1;
+    if (transcript_check_args(who, K, Ns, M, pis, As, Bs, sym, offs, S, units, unit_offs, lm)) return 1;
     if (!acc) return e2vq_set_error("%s: bad arguments", who);
     for (int k = 0; k < K; ++k)
         if (!acc[k]) return e2vq_set_error("%s: bad arguments", who);
@@ -272,7 +184,7 @@ extern "C" int e2vq_hmm_train_embedded(int device, int K, const int* Ns, int M, 
 {
     const char* who = "e2vq_hmm_train_embedded";
     LoopModels lm;
-    if (embed_check(who, K, Ns, M, pis, As, Bs, sym, offs, S, units, unit_offs, lm)) return 1;
+    if (transcript_check_args(who, K, Ns, M, pis, As, Bs, sym, offs, S, units, unit_offs, lm)) return 1;
     if (cap > 0 && !sum_log_prob) return e2vq_set_error("%s: bad arguments", who);
     EmbedPlan ep;
     if (embed_plan(who, K, Ns, M, (const i64*)offs, S, units, (const i64*)unit_offs, optional, ln_switch, ep)) return 1;
@@ -303,15 +215,9 @@ extern "C" int e2vq_hmm_learn_embedded_files(const char* const* model_filenames,
     if (!out_dir || !*out_dir) return e2vq_set_error("%s: no output directory", who);
     if (window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models)) return 1;
     const int K = fm.K();
-    auto class_of = [&](const std::string& name) {
-        int k = 0;
-        while (k < K && name != fm.names[(size_t)k]) ++k;
-        return k < K ? k : -1;
-    };
     if (check_names(who, K, fm.names.data())) return 1;
-    int filler = -1;
-    if (filler_class && *filler_class && (filler = class_of(filler_class)) < 0)
-        return e2vq_set_error("%s: the filler '%s' is no model's class", who, filler_class);
+    Transcripts tr;
+    if (tr.set_filler(who, fm, filler_class)) return 1;
     if (fm.logs(model_filenames)) return 1;
     // the models go to <out_dir>/<class>.hmm: none of them may be an input model
     std::vector<std::string> out_paths;
@@ -329,45 +235,26 @@ extern "C" int e2vq_hmm_learn_embedded_files(const char* const* model_filenames,
     }
     SymInputs si;
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
-    // the transcripts: the labels of file i in their order, the filler around and between them (as `hmm align`)
-    std::vector<int32_t> units;
-    std::vector<uint8_t> optional;
-    std::vector<i64> unit_offs(1, 0);
     for (int f = 0; f < num_inputs; ++f) {
-        const char* path = label_filenames[f];
-        if (!path) return e2vq_set_error("%s: NULL file name", who);
-        std::vector<LabelRow> rows;
-        if (read_label_file(path, rows)) return 1;
-        if (rows.empty()) return e2vq_set_error("%s: no labelled units", path);
-        auto fill = [&] {
-            if (filler >= 0) units.push_back(filler), optional.push_back(1);
-        };
-        fill();
-        for (const LabelRow& r : rows) {
-            const int k = class_of(r.label);
-            if (k < 0) return e2vq_set_error("%s:%zu: '%s' is no model's class", path, r.line, r.label.c_str());
-            units.push_back(k), optional.push_back(0);
-            fill();
-        }
-        unit_offs.push_back((i64)units.size());
+        if (tr.add_labels(who, fm, label_filenames[f])) return 1;
         // (with the frame count known so far: a .wav may still lose frames, which only shrinks the tables)
-        const i64 offs1[2] = {0, si.inputs[(size_t)f].T}, uoffs1[2] = {0, unit_offs[(size_t)f + 1] - unit_offs[(size_t)f]};
+        const i64 offs1[2] = {0, si.inputs[(size_t)f].T}, uoffs1[2] = {0, tr.L(f)};
         EmbedPlan ep1;
-        if (embed_plan(who, K, fm.Ns.data(), fm.M, offs1, 1, units.data() + unit_offs[(size_t)f], uoffs1, optional.data() + unit_offs[(size_t)f],
-                       ln_switch, ep1))
-            return e2vq_set_error("%s: %s", path, std::string(e2vq_last_error()).c_str());
+        if (embed_plan(who, K, fm.Ns.data(), fm.M, offs1, 1, tr.u(f), uoffs1, tr.o(f), ln_switch, ep1))
+            return e2vq_set_error("%s: %s", label_filenames[f], std::string(e2vq_last_error()).c_str());
     }
     // ---- the device from here on --------------------------------------------------------------------------------
     const int device = env_device();
     DeviceBuffer<unsigned short> d_all;
     EmbedDev dev;
+    EmbedPlan ep;  // (before the stage, as the offsets: its stream copies from them)
+    std::vector<i64> offs(1, 0);
     SymStage stg;
     if (require_device(device) || stg.open(device, si)) return 1;
     // every input to symbols, one after the other, gathered in one device buffer (the frame counts known so far bound it)
     i64 room = 0;
     for (const SymInput& in : si.inputs) room += in.T;
     if (d_all.reserve((size_t)room)) return 1;
-    std::vector<i64> offs(1, 0);
     for (int f = 0; f < num_inputs; ++f) {
         int64_t T = 0;
         if (stg.input(si.inputs[(size_t)f], si, P, W_ms, O_ms, &T)) return 1;
@@ -376,14 +263,13 @@ extern "C" int e2vq_hmm_learn_embedded_files(const char* const* model_filenames,
         if (T > 0) HIPCHK(hipMemcpyAsync(d_all.get() + offs.back(), stg.d_sym.get(), (size_t)T * 2, hipMemcpyDeviceToDevice, stg.st.s));
         offs.push_back(offs.back() + T);
     }
-    EmbedPlan ep;
-    if (embed_plan(who, K, fm.Ns.data(), fm.M, offs.data(), num_inputs, units.data(), unit_offs.data(), optional.data(), ln_switch, ep)) return 1;
+    if (embed_plan(who, K, fm.Ns.data(), fm.M, offs.data(), num_inputs, tr.units.data(), tr.unit_offs.data(), tr.optional.data(), ln_switch, ep)) return 1;
     if (dev.setup(who, ep, offs.data(), num_inputs, stg.st.s)) return 1;
     const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
     static char var[] = "sum_log_prob";
     printf("\nHMM learn --embedded: %d class(es)  M=%d  #streams = %d  #units = %lld  frames = %lld\n", K, fm.M, num_inputs,
-           (long long)unit_offs.back(), (long long)offs.back());
-    printf("  switch penalty=%g  filler=%s  epsilon=%g  val_auto=%g  max_iterations=%d\n", ln_switch, filler >= 0 ? fm.names[(size_t)filler] : "(none)",
+           (long long)tr.unit_offs.back(), (long long)offs.back());
+    printf("  switch penalty=%g  filler=%s  epsilon=%g  val_auto=%g  max_iterations=%d\n", ln_switch, tr.filler >= 0 ? fm.names[(size_t)tr.filler] : "(none)",
            hmm_epsilon, val_auto, max_iterations);
     std::vector<EmbedIteration> hist;
     std::vector<int> last_status((size_t)num_inputs, 0);

@@ -2,8 +2,8 @@
 // Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi and scan;
 // hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices; hmm_transitions.cpp: the file and the estimator
 // of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
-// decoder; hmm_align.cpp: forced alignment; hmm_embed.cpp: embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp:
-// the posteriors of the alignment).
+// decoder; hmm_transcript.cpp: what the commands that take a transcript share; hmm_align.cpp: forced alignment; hmm_embed.cpp:
+// embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp: the posteriors of the alignment).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -227,7 +227,7 @@ struct DevModels {  // a set of models on the device
 // scores of S device-resident sequences under K models: sc[s * K + k]
 int score_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, const i64* d_offs, int S, hipStream_t st, Scores& sc);
 
-// ---- decoding: what hmm_decode.cpp, hmm_class_loop.cpp, hmm_segment_stream.cpp and hmm_align.cpp share -----------------
+// ---- decoding: what hmm_decode.cpp, hmm_class_loop.cpp, hmm_segment_stream.cpp and hmm_transcript.cpp share ------------
 // The launches of a decoder whose table takes `row` bytes a frame: whole sequences [s0, s1) up to the budget of the
 // environment variable `env` (default 256 MiB), a longer sequence alone; *max_frames: the most frames of a launch
 // (hmm_decode.cpp)
@@ -327,7 +327,7 @@ struct ClassLoopDev {
     int upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st);
 };
 
-// ---- forced alignment (hmm_align.cpp): the plan `hmm align` and `hmm learn --embedded` (hmm_embed.cpp) share -----------------
+// ---- transcripts (hmm_transcript.cpp): what `hmm align`, `hmm learn --embedded` and `hmm align --posteriors` share --------
 // What the host decides about a call before the device is touched: the packing of every stream's units, the device tables
 // that describe it, and the launches (consecutive streams of one body whose tables and LDS fit together).
 struct AlignPlan {
@@ -345,11 +345,84 @@ struct AlignPlan {
     SegPacking cls;  // the classes: their rows in the parameter block (comp0, a_at, sumN, a_words)
 };
 // the checks of the transcripts and the price, the packing and the launches: host only (`who`: the entry point named in
-// the messages).  embedded: the caller is the embedded E-step -- every refusal stays (the bound of
+// the messages).  embedded: the caller is the embedded forward-backward pass -- every refusal stays (the bound of
 // ECOZ2_HMM_ALIGN_TABLE_BYTES on a stream too, worded for a caller without back-pointers), but ECOZ2_HMM_ALIGN_BODY is not
 // read and no launches are cut
 int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
                const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded = false);
+// may unit l hold frame 0 / the last frame (opt: the stream's flags, or null)
+bool unit_is_initial(int l, const uint8_t* opt);
+bool unit_is_final(int l, int L, const uint8_t* opt);
+
+// the first checks of an array-level entry point that takes transcripts: the arguments, the shapes, the models (into lm, with
+// their logarithms) and the offsets
+int transcript_check_args(const char* who, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                          const double* const* Bs, const void* sym, const int64_t* offs, int S, const int32_t* units,
+                          const int64_t* unit_offs, LoopModels& lm);
+
+// The transcripts of a file form: the labels of each file in their order, the filler (an optional unit) around and between
+// them.  File f's units are units.data() + unit_offs[f], unit_offs[f + 1] - unit_offs[f] of them.
+struct Transcripts {
+    std::vector<int32_t> units;
+    std::vector<uint8_t> optional;
+    std::vector<i64> unit_offs = std::vector<i64>(1, 0);
+    int filler = -1;  // the filler's class, or -1
+    int set_filler(const char* who, const LoopModels& fm, const char* filler_class);  // null or empty: none
+    int add_labels(const char* who, const LoopModels& fm, const char* path);          // the next file's
+    const int32_t* u(int f) const { return units.data() + unit_offs[(size_t)f]; }  // file f's
+    const uint8_t* o(int f) const { return optional.data() + unit_offs[(size_t)f]; }
+    i64 L(int f) const { return unit_offs[(size_t)f + 1] - unit_offs[(size_t)f]; }
+};
+
+// The plan of the embedded forward-backward pass (hmm_embed.hip, hmm_align_posterior.hip): align_plan's packing of every
+// stream with the successor flags, the classes' A at the leading dimension N | 1, what ECOZ2_HMM_EMBED_A says and the
+// launches.  Whether A goes to LDS is the caller's decision (a_lds; each kernel has its own LDS sum).
+struct EStepPlan {
+    AlignPlan ap;
+    SegPacking cls;                              // the classes, A with the leading dimension N | 1
+    std::vector<e2hmm::EmbedClassDev> classes;   // N and a_at; the caller's own places are 0
+    std::vector<uint16_t> row_cls;
+    i64 row_words = 0, max_frames = 0;
+    int M = 0, max_L = 0, max_slots = 0;
+    bool a_forced = false, a_lds = false;        // ECOZ2_HMM_EMBED_A is set; A in LDS
+    std::vector<std::pair<int, int>> chunks;
+};
+// `what` closes the refusal of a stream of more than 16 wave-slots; first_flags: EMBED_FIRST on a class's first unit
+int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, EStepPlan& p);
+// "lds" / "global" / unset of the variable `name` -> *forced (whether it is set) and *lds; any other value is refused
+int embed_route(const char* name, bool* forced, bool* lds);
+// pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class
+std::vector<double> embed_params(const LoopModels& lm, const SegPacking& pk, double sw);
+
+// An EStepPlan on the device: its six tables and the forward tables' scratch.  upload() only enqueues: the plan and the
+// offsets must outlive the stream's copies, and this struct the stream's kernels (a local or member declared before the
+// DevSeqs / SymStage whose stream works on it, or the function waits for that stream before it returns).
+struct EStepDev {
+    DeviceBuffer<e2hmm::AlignLaneDev> lanes;
+    DeviceBuffer<e2hmm::AlignStreamDev> streams;
+    DeviceBuffer<int> slot_info;
+    DeviceBuffer<e2hmm::EmbedClassDev> classes;
+    DeviceBuffer<unsigned short> row_cls;
+    DeviceBuffer<i64> offs;
+    DeviceBuffer<double> scr;
+    int upload(const EStepPlan& p, const i64* h_offs, int S, hipStream_t st);
+    int scratch(const char* who, const EStepPlan& p);  // room for the largest launch
+    // what a kernel takes for the launch that starts at stream s0 (offs.get() + s0 are its offsets)
+    e2hmm::EmbedPlanDev plan(const EStepPlan& p, int s0, const double* d_params) const;
+};
+
+// the reports of `hmm align`: the validation both share (`rest`: the caller's own pointers) -> the optional units passed
+// over, or -1; the time in seconds of frame * O_ms + W_ms; a visited unit's score; the header line and the per-class counts
+int align_report_check(const char* who, const char* name, int64_t T, int K, const char* const* class_names, int L, const int32_t* units,
+                       const uint8_t* optional, const int64_t* begin, const int64_t* end, const double* score, bool rest);
+inline double align_time_s(int64_t frame, int O_ms, int W_ms = 0) { return (double)(frame * O_ms + W_ms) / 1000.0; }
+inline double align_unit_score(const double* score, const int64_t* begin, const int64_t* end, int l, double ln_switch)
+{
+    return score[end[l] - 1] - (begin[l] == 0 ? 0.0 : score[begin[l] - 1] + ln_switch);
+}
+void align_report_head(const char* name, int64_t T, int K, const char* const* class_names, int L, const int32_t* units,
+                       const int64_t* begin, const int64_t* end, int skipped, double log_prob, double ln_switch);
 
 inline std::string fmt_17g(double v)
 {

@@ -5,6 +5,7 @@ arguments of the Rust functions of the same name (/root/reference/src/ecoz2_lib/
 same C symbols; the array-level functions drive the same HIP kernels without files (tests, bench).
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -134,6 +135,13 @@ _sig("e2vq_hmm_learn_embedded_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, 
 def _strs(items):
     arr = (C.c_char_p * len(items))(*[str(p).encode() for p in items])
     return C.cast(arr, c_char_pp), arr
+
+
+def _kernel_ms(fn):
+    """what an e2vq_*_last_kernel_ms export gives: the HIP-event time of the calling thread's last call, in ms"""
+    ms = C.c_float()
+    check(fn(C.byref(ms)))
+    return ms.value
 
 
 def set_random_seed(seed):
@@ -425,9 +433,7 @@ def scan(models, sym, offs, window, hop=None, device=0, matrix=True):
 
 
 def scan_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_scan_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_scan_last_kernel_ms)
 
 
 def scan_files(model_filenames, input_filenames, window, hop=None, codebook=None, P=36, W_ms=45, O_ms=15, min_margin=0.0,
@@ -490,9 +496,7 @@ def segment(models, sym, offs, ln_switch, device=0):
 
 
 def segment_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_segment_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_segment_last_kernel_ms)
 
 
 class SegmentStream:
@@ -634,9 +638,7 @@ def segment_posteriors(models, sym, offs, ln_switch, device=0):
 
 
 def segment_posteriors_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_segment_posteriors_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_segment_posteriors_last_kernel_ms)
 
 
 def segments_of_trans(cls, entered, exit_score, log_prob, ln_trans):
@@ -691,9 +693,7 @@ def segment_trans(models, sym, offs, ln_trans, device=0):
 
 
 def segment_trans_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_segment_trans_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_segment_trans_last_kernel_ms)
 
 
 def class_transitions(label_sequences, K, alpha=1.0):
@@ -791,39 +791,15 @@ def align(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, dev
     ln_switch <= 0, finite: the log of the price of a unit boundary.  -> dict: per frame unit / state (uint16), entered
     (uint8), score; per unit begin / end (int64, -1 where the path does not visit it); per stream log_prob, status; and
     units = per stream the list `units_of` gives"""
-    K = len(models)
-    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
-    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
-    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
-    M = ms[0][2].shape[1] if K else 0
-    offs = np.ascontiguousarray(offs, dtype=np.int64)
-    unit_offs = np.ascontiguousarray(unit_offs, dtype=np.int64)
-    S = len(offs) - 1
-    if len(unit_offs) != S + 1:
-        raise ValueError(f"unit_offs has {len(unit_offs)} entries for {S} streams")
-    units = np.ascontiguousarray(units, dtype=np.int32)
-    if optional is not None:
-        optional = np.ascontiguousarray(np.asarray(optional) != 0, dtype=np.uint8)
-    nu = int(unit_offs[-1]) if len(unit_offs) else 0
-    if len(units) < nu or (optional is not None and len(optional) < nu):
-        raise ValueError(f"unit_offs ends at {nu}: more than the units given")
-    on_device = hasattr(sym, "data_ptr")
-    if on_device:
-        if not sym.is_contiguous() or sym.element_size() != 2:
-            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
-        sym_ptr = sym.data_ptr()
-    else:
-        sym = np.ascontiguousarray(sym, dtype=np.uint16)
-        sym_ptr = sym.ctypes.data
+    a = _transcript_args(models, sym, offs, units, unit_offs, optional, copy=False)
+    offs, S, units, unit_offs, nu = a.offs, a.S, a.units, a.unit_offs, a.nu
     n = max(int(offs[-1]), 1)
     unit, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
     entered, score = np.zeros(n, dtype=np.uint8), np.zeros(n)
     begin, end = np.full(max(nu, 1), -1, dtype=np.int64), np.full(max(nu, 1), -1, dtype=np.int64)
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_align(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
-                             unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None, float(ln_switch),
-                             unit.ctypes.data, state.ctypes.data, entered.ctypes.data, score.ctypes.data, begin.ctypes.data,
-                             end.ctypes.data, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    check(lib.e2vq_hmm_align(device, *a.c_args, float(ln_switch), unit.ctypes.data, state.ctypes.data, entered.ctypes.data,
+                             score.ctypes.data, begin.ctypes.data, end.ctypes.data, lp.ctypes.data, st.ctypes.data, a.on_device))
     T = int(offs[-1])
     out = dict(unit=unit[:T], state=state[:T], entered=entered[:T], score=score[:T], begin=begin[:nu], end=end[:nu], log_prob=lp[:S],
                status=st[:S])
@@ -833,9 +809,7 @@ def align(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, dev
 
 
 def align_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_align_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_align_last_kernel_ms)
 
 
 def align_files(model_filenames, input_filenames, label_filenames, ln_switch=0.0, filler=None, codebook=None, P=36, W_ms=45, O_ms=15,
@@ -883,10 +857,9 @@ def align_posteriors(models, sym, offs, units, unit_offs, optional=None, ln_swit
     -> dict: occ, per stream the (T_s, L_s) array of P(unit l holds frame t) (only with occupancy); post_path per frame (occ at
     the path's unit; 0 without path_unit); per unit w0 = present (P(a path visits the unit)), w1, w2, begin_mean, begin_sd (the
     frame the unit is entered at); per stream log_prob, status"""
-    ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device = _embedded_args(models, sym, offs, units, unit_offs, optional)
-    K = len(ms)
-    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
-    T, nu = int(offs[-1]), int(unit_offs[-1])
+    a = _transcript_args(models, sym, offs, units, unit_offs, optional)
+    offs, S, unit_offs, nu = a.offs, a.S, a.unit_offs, a.nu
+    T = int(offs[-1])
     if path_unit is not None:
         path_unit = np.ascontiguousarray(path_unit, dtype=np.uint16)
         if len(path_unit) < T:
@@ -901,12 +874,10 @@ def align_posteriors(models, sym, offs, units, unit_offs, optional=None, ln_swit
     post = np.zeros(max(T, 1))
     w0, w1, w2 = (np.zeros(max(nu, 1)) for _ in range(3))
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_align_posteriors(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
-                                        unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None,
-                                        float(ln_switch), path_unit.ctypes.data if path_unit is not None else None,
+    check(lib.e2vq_hmm_align_posteriors(device, *a.c_args, float(ln_switch), path_unit.ctypes.data if path_unit is not None else None,
                                         ref.ctypes.data if ref is not None else None, occ.ctypes.data if occ is not None else None,
                                         post.ctypes.data, w0.ctypes.data, w1.ctypes.data, w2.ctypes.data, lp.ctypes.data, st.ctypes.data,
-                                        int(on_device)))
+                                        a.on_device))
     present, begin_mean, begin_sd = align_unit_moments(w0[:nu], w1[:nu], w2[:nu], None if ref is None else ref[:nu])
     out = dict(post_path=post[:T], w0=w0[:nu], w1=w1[:nu], w2=w2[:nu], present=present, begin_mean=begin_mean, begin_sd=begin_sd,
                log_prob=lp[:S], status=st[:S])
@@ -916,17 +887,19 @@ def align_posteriors(models, sym, offs, units, unit_offs, optional=None, ln_swit
 
 
 def align_posteriors_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_align_posteriors_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_align_posteriors_last_kernel_ms)
 
 
-def _embedded_args(models, sym, offs, units, unit_offs, optional):
-    """the arguments `embedded_estep` and `train_embedded` share, checked as `align` checks them -> (ms, Ns, M, offs, S, units,
-    unit_offs, optional, sym (kept alive), sym_ptr, on_device)"""
+def _transcript_args(models, sym, offs, units, unit_offs, optional, copy=True):
+    """the arguments `align`, `align_posteriors`, `embedded_estep` and `train_embedded` share, checked -> a namespace: ms (the
+    models' arrays), M, offs, S, units, unit_offs, nu (the units of all streams), on_device (0 / 1), and c_args, what the four
+    exports take between `device` and `ln_switch` (it keeps every array alive).  copy: the model arrays are copies
+    (train_embedded writes them); without it an array of the right kind is passed as it is"""
     K = len(models)
-    ms = [tuple(np.array(x, dtype=np.float64, order="C") for x in m) for m in models]  # (copies: train_embedded writes them)
+    arr = (lambda x: np.array(x, dtype=np.float64, order="C")) if copy else (lambda x: np.ascontiguousarray(x, dtype=np.float64))
+    ms = [tuple(arr(x) for x in m) for m in models]
     Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptrs = [(C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms]) for i in range(3)]
     M = ms[0][2].shape[1] if K else 0
     offs = np.ascontiguousarray(offs, dtype=np.int64)
     unit_offs = np.ascontiguousarray(unit_offs, dtype=np.int64)
@@ -947,45 +920,39 @@ def _embedded_args(models, sym, offs, units, unit_offs, optional):
     else:
         sym = np.ascontiguousarray(sym, dtype=np.uint16)
         sym_ptr = sym.ctypes.data
-    return ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device
+    c_args = (K, Ns, M, *ptrs, sym_ptr, offs.ctypes.data, S, units.ctypes.data, unit_offs.ctypes.data,
+              optional.ctypes.data if optional is not None else None)
+    return SimpleNamespace(ms=ms, M=M, offs=offs, S=S, units=units, unit_offs=unit_offs, nu=nu, on_device=int(on_device), c_args=c_args,
+                           keep=(optional, sym))
 
 
 def embedded_estep(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, device=0):
     """one E-step of embedded Baum-Welch: models, sym, offs, units, unit_offs, optional, ln_switch as `align`
     takes them -> dict acc (per class its int64 accumulator words, the layout of `acc_words`), log_prob (ln P(O, transcript)
     per stream, -inf where the status is not 0), status"""
-    ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device = _embedded_args(models, sym, offs, units, unit_offs, optional)
-    K = len(ms)
-    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
-    acc = [np.zeros(int(lib.e2vq_hmm_acc_words(len(m[0]), M)), dtype=np.int64) for m in ms]
-    accp = (C.c_void_p * max(K, 1))(*[a.ctypes.data for a in acc])
+    a = _transcript_args(models, sym, offs, units, unit_offs, optional)
+    S = a.S
+    acc = [np.zeros(int(lib.e2vq_hmm_acc_words(len(m[0]), a.M)), dtype=np.int64) for m in a.ms]
+    accp = (C.c_void_p * max(len(acc), 1))(*[x.ctypes.data for x in acc])
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_embedded_estep(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
-                                      unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None,
-                                      float(ln_switch), accp, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    check(lib.e2vq_hmm_embedded_estep(device, *a.c_args, float(ln_switch), accp, lp.ctypes.data, st.ctypes.data, a.on_device))
     return dict(acc=acc, log_prob=lp[:S], status=st[:S])
 
 
 def train_embedded(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, epsilon=1e-5, val_auto=0.3, max_iterations=-1,
                    device=0):
     """embedded Baum-Welch to its stop -> (the trained models [(pi, A, B)], the sum of ln P per E-step)"""
-    ms, Ns, M, offs, S, units, unit_offs, optional, sym, sym_ptr, on_device = _embedded_args(models, sym, offs, units, unit_offs, optional)
-    K = len(ms)
-    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    a = _transcript_args(models, sym, offs, units, unit_offs, optional)
     cap = 1000
     hist = np.zeros(cap)
     n = C.c_int(0)
-    check(lib.e2vq_hmm_train_embedded(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, units.ctypes.data,
-                                      unit_offs.ctypes.data, optional.ctypes.data if optional is not None else None,
-                                      float(ln_switch), float(epsilon), float(val_auto), int(max_iterations), hist.ctypes.data, cap,
-                                      C.byref(n), int(on_device)))
-    return ms, hist[:n.value].copy()
+    check(lib.e2vq_hmm_train_embedded(device, *a.c_args, float(ln_switch), float(epsilon), float(val_auto), int(max_iterations),
+                                      hist.ctypes.data, cap, C.byref(n), a.on_device))
+    return a.ms, hist[:n.value].copy()
 
 
 def embedded_last_kernel_ms():
-    ms = C.c_float()
-    check(lib.e2vq_hmm_embedded_last_kernel_ms(C.byref(ms)))
-    return ms.value
+    return _kernel_ms(lib.e2vq_hmm_embedded_last_kernel_ms)
 
 
 def learn_embedded_files(model_filenames, input_filenames, label_filenames, out_dir, ln_switch=0.0, filler=None, hmm_epsilon=1e-5,

@@ -403,6 +403,28 @@ def test_the_file_form_and_the_cli_refuse_before_the_device(tmp_path):
     assert "ecoz2 hmm learn --embedded -m|--models" in r.stderr + r.stdout
 
 
+def test_the_refusals_shared_with_the_other_transcript_commands_keep_every_word(tmp_path):
+    """Byte for byte, with the name of the entry point and of the label file in front: the seventeenth slot with its closing
+    words, from arrays and from files (17 units of one 64-state class), and a label file without a unit."""
+    uni = lambda N, m: (np.full(N, 1.0 / N), np.full((N, N), 1.0 / N), np.full((N, m), 1.0 / m))
+    slots = "stream 0: the units take 17 wave-slots of 64 lanes (at most 16: the embedded E-step has no looped body)"
+    for train, who in ((False, "e2vq_hmm_embedded_estep"), (True, "e2vq_hmm_train_embedded")):
+        assert _call([uni(64, M), uni(2, M)], np.zeros(8, np.uint16), [0, 8], [0] * 17, [0, 17], train=train) == 1
+        assert _err() == f"{who}: {slots}"
+    for c, N in (("a", 64), ("b", 2)):
+        hmm.save_model(tmp_path / f"{c}.hmm", c, *uni(N, 4))
+    e.formats.write_seq(str(tmp_path / "x.seq"), "_", 4, np.zeros(8, np.uint16))
+    (tmp_path / "wide.csv").write_text("class\n" + "a\n" * 17)
+    (tmp_path / "empty.csv").write_text("class\n")
+    files = [str(tmp_path / "a.hmm"), str(tmp_path / "b.hmm")]
+    for lab, msg in (("wide.csv", f"{tmp_path / 'wide.csv'}: e2vq_hmm_learn_embedded_files: {slots}"),
+                     ("empty.csv", f"{tmp_path / 'empty.csv'}: no labelled units")):
+        with pytest.raises(e.Ecoz2Error):
+            hmm.learn_embedded_files(files, [str(tmp_path / "x.seq")], [str(tmp_path / lab)], tmp_path / "o")
+        assert _err() == msg
+    assert not (tmp_path / "o").exists()
+
+
 def test_embedded_library_exports():
     for name in ("e2vq_hmm_embedded_estep", "e2vq_hmm_train_embedded", "e2vq_hmm_embedded_last_kernel_ms", "e2vq_hmm_learn_embedded_files"):
         assert hasattr(e.lib, name)
