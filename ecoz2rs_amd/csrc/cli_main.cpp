@@ -55,6 +55,7 @@ static int usage()
             "                  --sequences <file.seq|dirs|tt.csv>...   (one model per N, M and class, trained together)\n"
             "  ecoz2 hmm learn --embedded -m|--models <files|dirs>... --labels <files>... [--filler <class>] [--switch-penalty <x <= 0>]\n"
             "                  [-e 1e-05] [-a 0.3] [-I -1] -o <dir> [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
+            "                  [--body <auto|resident|looped>]\n"
             "                  (--signals <.wav files>... | --predictors <.prd files>... | --sequences <.seq files>...)\n"
             "                  (the given models re-estimated from whole recordings and the order of their units, no boundaries:\n"
             "                  label file i is recording i's transcript, as `hmm align` reads it; the models go to <dir>/<class>.hmm)\n"
@@ -1057,7 +1058,7 @@ static int hmm_learn_embedded_cmd(int argc, char** argv)
 {
     int P = 36, W = 45, O = 15, max_iterations = -1;
     double ln_switch = 0.0, epsilon = 1e-05, val_auto = 0.3;
-    std::string codebook, filler, out;
+    std::string codebook, filler, out, body;
     std::vector<std::string> models, labels, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -1096,11 +1097,19 @@ static int hmm_learn_embedded_cmd(int argc, char** argv)
         else if (a == "--filler") filler = val("--filler");
         else if (a == "--labels") many(labels);
         else if (a == "--switch-penalty") ln_switch = real("--switch-penalty");
+        else if (a == "--body") body = val("--body");
         else if (a == "-o" || a == "--out") out = val("-o");
         else if (a == "--signals") many(signals);
         else if (a == "--predictors") many(predictors);
         else if (a == "-s" || a == "--sequences") many(sequences);
         else return usage();
+    }
+    if (!body.empty()) {  // the E-step's body (ECOZ2_HMM_EMBED_BODY), set in this process before the call
+        if (body != "auto" && body != "resident" && body != "looped") {
+            fprintf(stderr, "hmm learn --embedded: --body %s: auto, resident or looped\n", body.c_str());
+            return usage();
+        }
+        setenv("ECOZ2_HMM_EMBED_BODY", body.c_str(), 1);
     }
     if (models.empty()) { fprintf(stderr, "hmm learn --embedded: --models <files|dirs>... is required\n"); return usage(); }
     if (out.empty()) { fprintf(stderr, "hmm learn --embedded: -o <dir> is required\n"); return usage(); }

@@ -20,7 +20,8 @@ struct PostPlan : EStepPlan {
 int post_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
               const uint8_t* optional, double ln_switch, PostPlan& pp)
 {
-    if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the alignment posteriors have a resident body only", false, pp))
+    if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the alignment posteriors have a resident body only", false,
+                   EMBED_BODY_RESIDENT, pp))
         return 1;
     pp.occ_at.assign((size_t)S + 1, 0);
     for (int s = 0; s < S; ++s) pp.occ_at[(size_t)s + 1] = pp.occ_at[(size_t)s] + (offs[s + 1] - offs[s]) * pp.ap.streams[(size_t)s].L;

@@ -240,6 +240,16 @@ size_t embed_lds_bytes(int max_L, int a_words, bool a_lds, bool an_lds);
 int launch_embed_fb(const EmbedPlanDev& pl, bool a_lds, bool an_lds, int waves, const unsigned short* sym, const long long* offs, int S,
                     long long a0, long long row_words, double* scr, long long* acc, double* mant, long long* exp2, int* status,
                     hipStream_t st);
+// The looped body of the same pass (hmm_embed_looped.hip): streams of any number of slots, a workgroup of min(max_slots, 16)
+// waves each; the same counts, P and status bit for bit.  pl.max_L, max_slots and max_sumN are the largest of the launch's
+// streams.  Dynamic LDS: 2 x max_slots partial sums, V / R, two per-state arrays of max_sumN doubles, A (a_lds) and the AN
+// limb table (an_lds); the first three are mandatory.
+size_t embed_looped_lds_bytes(int max_L, int max_slots, int max_sumN, int a_words, bool a_lds, bool an_lds);
+// as launch_embed_fb; the scratch of a stream takes T (2 sumN + 1) doubles of its T row_words.  Returns 1 when the shape
+// cannot be launched.
+int launch_embed_fb_looped(const EmbedPlanDev& pl, bool a_lds, bool an_lds, int max_slots, int max_sumN, const unsigned short* sym,
+                           const long long* offs, int S, long long a0, long long row_words, double* scr, long long* acc, double* mant,
+                           long long* exp2, int* status, hipStream_t st);
 // AD of every class from its AN, once every stream's counts are in
 void launch_embed_rowsum(const EmbedClassDev* classes, int K, int max_N, long long* acc, hipStream_t st);
 // M-step of all K classes on their dense blocks (+ the floor at epsilon of B when epsilon > 0), in place; max_P / max_N: the

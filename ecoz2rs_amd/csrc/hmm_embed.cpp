@@ -20,12 +20,19 @@ struct EmbedPlan : EStepPlan {
     i64 dense_words = 0, max_P = 0;
     int max_N = 0;
     bool an_lds = false;
+    struct LoopLds {  // of a launch of the looped body
+        bool a_lds = false, an_lds = false;
+    };
+    std::vector<LoopLds> loop_lds;  // per chunk
 };
 
 int embed_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
                const uint8_t* optional, double ln_switch, EmbedPlan& ep)
 {
-    if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the embedded E-step has no looped body", true, ep)) return 1;
+    int body = EMBED_BODY_RESIDENT;
+    if (embed_body(&body)) return 1;
+    if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the embedded E-step has no looped body", true, body, ep))
+        return 1;
     ep.acc_at.assign((size_t)K + 1, 0);
     for (int k = 0; k < K; ++k) {
         const int N = Ns[k];
@@ -40,10 +47,28 @@ int embed_plan(const char* who, int K, const int* Ns, int M, const i64* offs, in
     bool fan = false;
     if (embed_route("ECOZ2_HMM_EMBED_AN", &fan, &ep.an_lds)) return 1;
     const int aw = ep.cls.a_words;
+    const bool a_said = ep.a_lds, an_said = ep.an_lds;  // what the variables force
+    // the launches of the looped body: each by its own largest shapes
+    ep.loop_lds.resize(ep.chunks.size());
+    for (size_t i = 0; i < ep.chunks.size(); ++i) {
+        const EStepPlan::Shape& g = ep.shapes[i];
+        if (!g.looped) continue;
+        EmbedPlan::LoopLds& ll = ep.loop_lds[i];
+        auto bytes = [&](bool a, bool an) { return e2hmm::embed_looped_lds_bytes(g.max_L, g.max_slots, g.max_sumN, aw, a, an); };
+        ll.a_lds = ep.a_forced ? a_said : bytes(true, fan && an_said) <= e2hmm::SEG_LDS_BYTES;
+        ll.an_lds = fan ? an_said : bytes(ll.a_lds, true) <= e2hmm::SEG_LDS_BYTES;
+        if (bytes(ll.a_lds, ll.an_lds) > e2hmm::SEG_LDS_BYTES)
+            return e2vq_set_error("%s: streams %d to %d: %d units of sum N = %d states in %d wave-slots, A in %s and the AN table in %s take "
+                                  "%zu bytes of LDS (at most %zu)", who, ep.chunks[i].first, ep.chunks[i].second - 1, g.max_L, g.max_sumN,
+                                  g.max_slots, ll.a_lds ? "LDS" : "global memory", ll.an_lds ? "LDS" : "global memory",
+                                  bytes(ll.a_lds, ll.an_lds), e2hmm::SEG_LDS_BYTES);
+    }
+    // the launches of the resident body: one layout for all of them, by the most units of their streams
     if (!ep.a_forced) ep.a_lds = e2hmm::embed_lds_bytes(ep.max_L, aw, true, fan && ep.an_lds) <= e2hmm::SEG_LDS_BYTES;
     if (!fan) ep.an_lds = e2hmm::embed_lds_bytes(ep.max_L, aw, ep.a_lds, true) <= e2hmm::SEG_LDS_BYTES;
     const size_t lds = e2hmm::embed_lds_bytes(ep.max_L, aw, ep.a_lds, ep.an_lds);
-    if (lds > e2hmm::SEG_LDS_BYTES)
+    const bool resident_runs = S == 0 || std::count(ep.looped.begin(), ep.looped.end(), 0) > 0;
+    if (lds > e2hmm::SEG_LDS_BYTES && resident_runs)
         return e2vq_set_error("%s: %d units, A in %s and the AN table in %s take %zu bytes of LDS (at most %zu)", who, ep.max_L,
                               ep.a_lds ? "LDS" : "global memory", ep.an_lds ? "LDS" : "global memory", lds, e2hmm::SEG_LDS_BYTES);
     return 0;
@@ -74,12 +99,22 @@ struct EmbedDev {
         HIPCHK(hipMemsetAsync(d_acc.get(), 0, (size_t)ep.acc_at.back() * 8, st));
         HIPCHK(hipEventRecord(timer.start.e, st));
         // (one stream: a chunk's forward pass writes the scratch only after the previous chunk's backward pass has read it)
-        for (const auto& c : ep.chunks) {
-            const int s0 = c.first, n = c.second - c.first;
-            if (e2hmm::launch_embed_fb(pd.plan(ep, s0, d_params.get()), ep.a_lds, ep.an_lds, ep.max_slots, d_sym, pd.offs.get() + s0, n,
-                                       h_offs[s0], ep.row_words, pd.scr.get(), d_acc.get(), sc.d_mant.get() + s0, sc.d_exp.get() + s0,
-                                       sc.d_status.get() + s0, st))
+        for (size_t i = 0; i < ep.chunks.size(); ++i) {
+            const int s0 = ep.chunks[i].first, n = ep.chunks[i].second - s0;
+            const EStepPlan::Shape& g = ep.shapes[i];
+            if (g.looped) {
+                e2hmm::EmbedPlanDev pl = pd.plan(ep, s0, d_params.get());
+                pl.max_L = g.max_L;
+                if (e2hmm::launch_embed_fb_looped(pl, ep.loop_lds[i].a_lds, ep.loop_lds[i].an_lds, g.max_slots, g.max_sumN, d_sym,
+                                                  pd.offs.get() + s0, n, h_offs[s0], ep.row_words, pd.scr.get(), d_acc.get(),
+                                                  sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+                    return e2vq_set_error("%s: %d units of sum N = %d states in %d wave-slots cannot be launched", who, g.max_L, g.max_sumN,
+                                          g.max_slots);
+            } else if (e2hmm::launch_embed_fb(pd.plan(ep, s0, d_params.get()), ep.a_lds, ep.an_lds, ep.max_slots, d_sym, pd.offs.get() + s0,
+                                              n, h_offs[s0], ep.row_words, pd.scr.get(), d_acc.get(), sc.d_mant.get() + s0,
+                                              sc.d_exp.get() + s0, sc.d_status.get() + s0, st)) {
                 return e2vq_set_error("%s: %d units in %d wave-slots cannot be launched", who, ep.max_L, ep.max_slots);
+            }
             HIPCHK(hipGetLastError());
         }
         e2hmm::launch_embed_rowsum(pd.classes.get(), K, ep.max_N, d_acc.get(), st);

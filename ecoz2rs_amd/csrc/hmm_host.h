@@ -347,9 +347,10 @@ struct AlignPlan {
 // the checks of the transcripts and the price, the packing and the launches: host only (`who`: the entry point named in
 // the messages).  embedded: the caller is the embedded forward-backward pass -- every refusal stays (the bound of
 // ECOZ2_HMM_ALIGN_TABLE_BYTES on a stream too, worded for a caller without back-pointers), but ECOZ2_HMM_ALIGN_BODY is not
-// read and no launches are cut
+// read and no launches are cut.  own_looped_lds: the caller has a looped body of its own and holds a stream of more than 16
+// slots against that body's LDS sum, not against k_hmm_align's
 int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded = false);
+               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded = false, bool own_looped_lds = false);
 // may unit l hold frame 0 / the last frame (opt: the stream's flags, or null)
 bool unit_is_initial(int l, const uint8_t* opt);
 bool unit_is_final(int l, int L, const uint8_t* opt);
@@ -377,19 +378,33 @@ struct Transcripts {
 // The plan of the embedded forward-backward pass (hmm_embed.hip, hmm_align_posterior.hip): align_plan's packing of every
 // stream with the successor flags, the classes' A at the leading dimension N | 1, what ECOZ2_HMM_EMBED_A says and the
 // launches.  Whether A goes to LDS is the caller's decision (a_lds; each kernel has its own LDS sum).
+// The body of a stream (hmm_embed.hip / hmm_embed_looped.hip) is the caller's choice: resident for every stream (more than 16
+// wave-slots are refused), looped for every stream, or resident up to 16 slots and looped above.  A launch has one body:
+// the launches of plan_chunks are cut further where the body changes and where the looped streams' largest shapes no longer
+// fit LDS together.
+enum EmbedBody { EMBED_BODY_RESIDENT = 0, EMBED_BODY_LOOPED = 1, EMBED_BODY_AUTO = 2 };
 struct EStepPlan {
     AlignPlan ap;
     SegPacking cls;                              // the classes, A with the leading dimension N | 1
     std::vector<e2hmm::EmbedClassDev> classes;   // N and a_at; the caller's own places are 0
     std::vector<uint16_t> row_cls;
     i64 row_words = 0, max_frames = 0;
-    int M = 0, max_L = 0, max_slots = 0;
+    int M = 0, max_L = 0, max_slots = 0;         // max_*: over the streams of the resident body
     bool a_forced = false, a_lds = false;        // ECOZ2_HMM_EMBED_A is set; A in LDS
     std::vector<std::pair<int, int>> chunks;
+    std::vector<uint8_t> looped;                 // [S]: the stream's body
+    struct Shape {                               // of a launch of the looped body: the largest among its streams
+        bool looped = false;
+        int max_L = 0, max_slots = 0, max_sumN = 0;
+    };
+    std::vector<Shape> shapes;                   // per chunk
 };
-// `what` closes the refusal of a stream of more than 16 wave-slots; first_flags: EMBED_FIRST on a class's first unit
+// `what` closes the refusal of a stream of more than 16 wave-slots that would run resident; first_flags: EMBED_FIRST on a
+// class's first unit; body: an EmbedBody
 int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, EStepPlan& p);
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, int body, EStepPlan& p);
+// ECOZ2_HMM_EMBED_BODY: unset, empty or "resident" / "looped" / "auto" -> *body (an EmbedBody); any other value is refused
+int embed_body(int* body);
 // "lds" / "global" / unset of the variable `name` -> *forced (whether it is set) and *lds; any other value is refused
 int embed_route(const char* name, bool* forced, bool* lds);
 // pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class

@@ -11,13 +11,13 @@ bool unit_is_initial(int l, const uint8_t* opt) { return l == 0 || (l == 1 && op
 bool unit_is_final(int l, int L, const uint8_t* opt) { return l == L - 1 || (l == L - 2 && opt && opt[L - 1]); }
 
 int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded)
+               const uint8_t* optional, double ln_switch, AlignPlan& ap, bool embedded, bool own_looped_lds)
 {
     if (segment_check_switch(who, ln_switch)) return 1;
     if (std::isinf(ln_switch)) return e2vq_set_error("%s: ln_switch = %g: a finite price (every unit has to be entered)", who, ln_switch);
     if (unit_offs[0] != 0) return e2vq_set_error("%s: unit_offs[0] = %lld, not 0", who, (long long)unit_offs[0]);
     bool force_looped = false;
-    if (!embedded && loop_body_looped("ECOZ2_HMM_ALIGN_BODY", 0, &force_looped)) return 1;  // (the E-step has one body)
+    if (!embedded && loop_body_looped("ECOZ2_HMM_ALIGN_BODY", 0, &force_looped)) return 1;  // (the E-step's body: estep_plan)
     const i64 budget = env_bytes("ECOZ2_HMM_ALIGN_TABLE_BYTES", (i64)4 << 30);
     ap.cls = pack_slots(std::vector<int>(Ns, Ns + K));
     const SegPacking& cls = ap.cls;
@@ -49,7 +49,7 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
                                   (long long)sumN, e2hmm::align_lds_bytes(L, (int)sumN, 0, false, false), e2hmm::SEG_LDS_BYTES);
         const SegPacking pk = pack_slots(uN);
         looped[(size_t)s] = force_looped || pk.slots > e2hmm::SEG_MAX_WAVES;
-        if (looped[(size_t)s] && !e2hmm::align_fits_lds(L, pk.sumN, true))
+        if (looped[(size_t)s] && !own_looped_lds && !e2hmm::align_fits_lds(L, pk.sumN, true))
             return e2vq_set_error("%s: stream %d: %d units of sum N = %d states in %d wave-slots do not fit in LDS (%zu of %zu bytes)", who,
                                   s, L, pk.sumN, pk.slots, e2hmm::align_lds_bytes(L, pk.sumN, 0, true, false), e2hmm::SEG_LDS_BYTES);
         const i64 T = offs[s + 1] - offs[s];
@@ -160,18 +160,41 @@ int embed_route(const char* name, bool* forced, bool* lds)
     return 0;
 }
 
-int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, EStepPlan& p)
+int embed_body(int* body)
 {
-    if (align_plan(who, K, Ns, offs, S, units, unit_offs, optional, ln_switch, p.ap, /*embedded=*/true)) return 1;
+    const char* v = getenv("ECOZ2_HMM_EMBED_BODY");
+    *body = EMBED_BODY_RESIDENT;
+    if (!v || !*v || strcmp(v, "resident") == 0) return 0;
+    if (strcmp(v, "looped") == 0) *body = EMBED_BODY_LOOPED;
+    else if (strcmp(v, "auto") == 0) *body = EMBED_BODY_AUTO;
+    else return e2vq_set_error("ECOZ2_HMM_EMBED_BODY=%s: auto, resident or looped", v);
+    return 0;
+}
+
+int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, int body, EStepPlan& p)
+{
+    if (align_plan(who, K, Ns, offs, S, units, unit_offs, optional, ln_switch, p.ap, /*embedded=*/true,
+                   /*own_looped_lds=*/body != EMBED_BODY_RESIDENT))
+        return 1;
     int max_sumN = 0;
+    p.looped.assign((size_t)S, 0);
     for (int s = 0; s < S; ++s) {
         const e2hmm::AlignStreamDev& sd = p.ap.streams[(size_t)s];
-        if (sd.slots > e2hmm::SEG_MAX_WAVES)
+        const bool looped = body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && sd.slots > e2hmm::SEG_MAX_WAVES);
+        p.looped[(size_t)s] = looped ? 1 : 0;
+        if (!looped && sd.slots > e2hmm::SEG_MAX_WAVES)
             return e2vq_set_error("%s: stream %d: the units take %d wave-slots of 64 lanes (at most %d: %s)", who, s, sd.slots,
                                   e2hmm::SEG_MAX_WAVES, what);
-        p.max_L = std::max(p.max_L, sd.L);
-        p.max_slots = std::max(p.max_slots, sd.slots);
+        // (the looped body's partial sums, V / R and per-state arrays are mandatory; A and the AN table go in when they fit)
+        if (looped && e2hmm::embed_looped_lds_bytes(sd.L, sd.slots, sd.sumN, 0, false, false) > e2hmm::SEG_LDS_BYTES)
+            return e2vq_set_error("%s: stream %d: %d units of sum N = %d states in %d wave-slots do not fit in LDS (%zu of %zu bytes)", who,
+                                  s, sd.L, sd.sumN, sd.slots, e2hmm::embed_looped_lds_bytes(sd.L, sd.slots, sd.sumN, 0, false, false),
+                                  e2hmm::SEG_LDS_BYTES);
+        if (!looped) {
+            p.max_L = std::max(p.max_L, sd.L);
+            p.max_slots = std::max(p.max_slots, sd.slots);
+        }
         max_sumN = std::max(max_sumN, sd.sumN);
         const int32_t* u = units + unit_offs[s];
         const uint8_t* opt = optional ? optional + unit_offs[s] : nullptr;
@@ -193,7 +216,28 @@ int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, in
     // launches of whole streams whose scratch (ah and m: 8 sumN bytes a frame each, c: 8 bytes a frame and wave) stays within
     // the budget; every stream's rows are counted at the widest stream's width
     p.row_words = 2 * (i64)max_sumN + e2hmm::SEG_MAX_WAVES;
-    p.chunks = plan_chunks("ECOZ2_HMM_EMBED_CHUNK_BYTES", 8 * p.row_words, offs, S, &p.max_frames);
+    const auto whole = plan_chunks("ECOZ2_HMM_EMBED_CHUNK_BYTES", 8 * p.row_words, offs, S, &p.max_frames);
+    // a launch has one body, and the largest shapes of a looped launch fit LDS together (the bodies agree on every bit:
+    // where the cuts fall is a matter of cost only)
+    for (const auto& c : whole) {
+        for (int s0 = c.first; s0 < c.second;) {
+            EStepPlan::Shape g;
+            g.looped = p.looped[(size_t)s0] != 0;
+            int s1 = s0;
+            while (s1 < c.second) {
+                const e2hmm::AlignStreamDev& sd = p.ap.streams[(size_t)s1];
+                const int mL = std::max(g.max_L, sd.L), mS = std::max(g.max_slots, sd.slots), mN = std::max(g.max_sumN, sd.sumN);
+                if (s1 > s0 && ((p.looped[(size_t)s1] != 0) != g.looped ||
+                                (g.looped && e2hmm::embed_looped_lds_bytes(mL, mS, mN, 0, false, false) > e2hmm::SEG_LDS_BYTES)))
+                    break;
+                g.max_L = mL, g.max_slots = mS, g.max_sumN = mN;
+                ++s1;
+            }
+            p.chunks.emplace_back(s0, s1);
+            p.shapes.push_back(g);
+            s0 = s1;
+        }
+    }
     return 0;
 }
 

@@ -4,7 +4,9 @@
 arguments of the Rust functions of the same name (/root/reference/src/ecoz2_lib/mod.rs:188-190, 385-494) and call the
 same C symbols; the array-level functions drive the same HIP kernels without files (tests, bench).
 """
+import contextlib
 import ctypes as C
+import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -926,28 +928,50 @@ def _transcript_args(models, sym, offs, units, unit_offs, optional, copy=True):
                            keep=(optional, sym))
 
 
-def embedded_estep(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, device=0):
+@contextlib.contextmanager
+def _embed_body(body):
+    """ECOZ2_HMM_EMBED_BODY = body ("auto", "resident" or "looped") for the duration of a call; None leaves the environment alone"""
+    if body is None:
+        yield
+        return
+    name = "ECOZ2_HMM_EMBED_BODY"
+    before = os.environ.get(name)
+    os.environ[name] = str(body)
+    try:
+        yield
+    finally:
+        if before is None:
+            del os.environ[name]
+        else:
+            os.environ[name] = before
+
+
+def embedded_estep(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, device=0, body=None):
     """one E-step of embedded Baum-Welch: models, sym, offs, units, unit_offs, optional, ln_switch as `align`
     takes them -> dict acc (per class its int64 accumulator words, the layout of `acc_words`), log_prob (ln P(O, transcript)
-    per stream, -inf where the status is not 0), status"""
+    per stream, -inf where the status is not 0), status.  body: "auto", "resident" or "looped" (ECOZ2_HMM_EMBED_BODY for this
+    call: the looped body takes a stream of more than 16 wave-slots); None: what the environment says"""
     a = _transcript_args(models, sym, offs, units, unit_offs, optional)
     S = a.S
     acc = [np.zeros(int(lib.e2vq_hmm_acc_words(len(m[0]), a.M)), dtype=np.int64) for m in a.ms]
     accp = (C.c_void_p * max(len(acc), 1))(*[x.ctypes.data for x in acc])
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_embedded_estep(device, *a.c_args, float(ln_switch), accp, lp.ctypes.data, st.ctypes.data, a.on_device))
+    with _embed_body(body):
+        check(lib.e2vq_hmm_embedded_estep(device, *a.c_args, float(ln_switch), accp, lp.ctypes.data, st.ctypes.data, a.on_device))
     return dict(acc=acc, log_prob=lp[:S], status=st[:S])
 
 
 def train_embedded(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, epsilon=1e-5, val_auto=0.3, max_iterations=-1,
-                   device=0):
-    """embedded Baum-Welch to its stop -> (the trained models [(pi, A, B)], the sum of ln P per E-step)"""
+                   device=0, body=None):
+    """embedded Baum-Welch to its stop (DESIGN.md 4.8.11) -> (the trained models [(pi, A, B)], the sum of ln P per E-step);
+    body as `embedded_estep` takes it"""
     a = _transcript_args(models, sym, offs, units, unit_offs, optional)
     cap = 1000
     hist = np.zeros(cap)
     n = C.c_int(0)
-    check(lib.e2vq_hmm_train_embedded(device, *a.c_args, float(ln_switch), float(epsilon), float(val_auto), int(max_iterations),
-                                      hist.ctypes.data, cap, C.byref(n), a.on_device))
+    with _embed_body(body):
+        check(lib.e2vq_hmm_train_embedded(device, *a.c_args, float(ln_switch), float(epsilon), float(val_auto), int(max_iterations),
+                                          hist.ctypes.data, cap, C.byref(n), a.on_device))
     return a.ms, hist[:n.value].copy()
 
 
@@ -956,17 +980,18 @@ def embedded_last_kernel_ms():
 
 
 def learn_embedded_files(model_filenames, input_filenames, label_filenames, out_dir, ln_switch=0.0, filler=None, hmm_epsilon=1e-5,
-                         val_auto=0.3, max_iterations=-1, codebook=None, P=36, W_ms=45, O_ms=15, callback=None):
+                         val_auto=0.3, max_iterations=-1, codebook=None, P=36, W_ms=45, O_ms=15, callback=None, body=None):
     """`hmm learn --embedded`: the models of the files re-estimated from input i (.wav, .prd or .seq) and the
     transcript label file i names (as `align_files` reads it; filler as there); writes <out_dir>/<class>.hmm for every class and
-    <out_dir>/embedded.csv; callback(var: str, val: float) per E-step"""
+    <out_dir>/embedded.csv; callback(var: str, val: float) per E-step; body as `embedded_estep` takes it"""
     if len(label_filenames) != len(input_filenames):
         raise ValueError(f"{len(label_filenames)} label files for {len(input_filenames)} inputs")
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     l, _k3 = _strs(label_filenames)
     cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
-    check(lib.e2vq_hmm_learn_embedded_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
-                                            len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                            str(filler).encode() if filler else None, float(hmm_epsilon), float(val_auto),
-                                            int(max_iterations), str(out_dir).encode(), cb))
+    with _embed_body(body):
+        check(lib.e2vq_hmm_learn_embedded_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
+                                                len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                str(filler).encode() if filler else None, float(hmm_epsilon), float(val_auto),
+                                                int(max_iterations), str(out_dir).encode(), cb))

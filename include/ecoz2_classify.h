@@ -527,7 +527,7 @@ int e2vq_hmm_align_files(const char *const *model_filenames, unsigned num_models
  * transcript c_0 .. c_{L-1} of class indices (units, unit_offs), repeats and immediate repeats allowed; a flag per unit,
  * optional (may be NULL = none); one finite ln_switch <= 0.  Everything e2vq_hmm_align refuses before a HIP call is refused
  * here too, and one thing more: a stream whose units pack into more than 16 wave-slots (the message names the slot count) --
- * only a resident body is built.
+ * unless ECOZ2_HMM_EMBED_BODY chooses the looped body (the last paragraph).
  * The arithmetic is linear and scaled; nothing transcendental runs on the device.  sw = exp(ln_switch) is the C library's exp
  * on the host; e[l][j] = sw * pi_{c_l}[j] is one host multiplication; every operation below is one IEEE double operation in
  * the stated order, no fma.  GS is the global sum of 4.8.7 over the stream's packing: a butterfly over the 64 lanes of each
@@ -571,7 +571,17 @@ int e2vq_hmm_align_files(const char *const *model_filenames, unsigned num_models
  * global atomics, AN in an LDS table over all K classes of the call (ds_add_u64, flushed once a stream) when it fits the 160 KB
  * next to A, else by global atomics; ECOZ2_HMM_EMBED_A / ECOZ2_HMM_EMBED_AN = lds | global force either choice (a forced layout
  * that does not fit is refused).  Scratch: ah_t and m_t per composite state, c_t per wave; whole streams per launch under
- * ECOZ2_HMM_EMBED_CHUNK_BYTES (default 256 MiB), a larger stream alone. */
+ * ECOZ2_HMM_EMBED_CHUNK_BYTES (default 256 MiB), a larger stream alone.
+ * The body.  ECOZ2_HMM_EMBED_BODY chooses the kernel body of the E-step in e2vq_hmm_embedded_estep, e2vq_hmm_train_embedded and
+ * e2vq_hmm_learn_embedded_files (no other entry point reads it).  Unset, empty or "resident": as above, more than 16 wave-slots
+ * are refused.  "looped": every stream runs the looped body (hmm_embed_looped.hip), which takes any number of slots: a wave
+ * serves several slots in turn and the per-state values live in LDS.  "auto": resident up to 16 slots, looped above; a launch
+ * has one body, so the launches are cut where it changes.  Any other value is refused before a HIP call:
+ * "ECOZ2_HMM_EMBED_BODY=<v>: auto, resident or looped".  The contract above never depended on the body -- GS is defined for any
+ * number of slots -- so both bodies give the same limbs, the same bits of log_prob and the same status.  A looped stream needs
+ * 16 (slots + L + sum N) bytes of LDS; one that does not fit in 160 KB is refused before a HIP call ("stream %d: %d units of sum
+ * N = %d states in %d wave-slots do not fit in LDS").  A and the AN table go to LDS when they fit next to that, and the two
+ * variables above force either choice here too.  BD and PI go by global atomics per frame under the looped body. */
 /* one E-step: acc[k] receives class k's e2vq_hmm_acc_words(N_k, M) words (zeroed by the call); log_prob / status per stream
  * (either may be NULL) */
 int e2vq_hmm_embedded_estep(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
