@@ -302,10 +302,14 @@ __device__ unsigned long long g_sweep_stamps[16];
 // experiments on the stamped build only (tools/probe/sweep_stamps.py; results are WRONG under them, timing is the point):
 // 1 = stage 1 does not reload its codeword tiles, 2 = stage 2 runs the home tile only, 4 = no rows request,
 // 8 = the cell sums' atomics are skipped, 16 = no codeword-row gathers in the evaluation, 32 = rows request of even frames
-// only (16-byte aligned pieces), 64 = rows request without the frame-number shuffle
+// only (16-byte aligned pieces), 64 = rows request without the frame-number shuffle, 128 = only waves 0..3 of a workgroup
+// take turns (one wave per SIMD where the hardware places them round robin: stage 1 at the one-wave rate; slots 13 / 14 of
+// the table tell whether they did share)
+// Slots 13 / 14 / 15 (fused two-stage kernel): turns that found a SIMD partner in stage 1 when they entered theirs / when
+// they left it, and the token's polls that slept.
 __device__ int g_sweep_exp;
 #define SW_EXP(bit) ((sw_exp & (bit)) != 0)
-#define SW_STAMP_DECL unsigned long long sw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sw_conv = 0, sw_t = __builtin_amdgcn_s_memtime(), sw_n = 0; \
+#define SW_STAMP_DECL unsigned long long sw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sw_conv = 0, sw_t = __builtin_amdgcn_s_memtime(), sw_n = 0, sw_in = 0, sw_out = 0, sw_polls = 0; \
     const int sw_exp = __builtin_amdgcn_readfirstlane(g_sweep_exp);
 #define SW_STAMP(i)                                                                          \
     {                                                                                        \
@@ -319,6 +323,21 @@ __device__ int g_sweep_exp;
 #define SW_STAMP(i)
 #define SW_EXP(bit) false
 #endif
+
+// ---- the stage-1 token of the fused two-stage kernel ---------------------------------------------------------
+// The waves of a workgroup that share a SIMD (read from the hardware ID register, not assumed from the wave index) take
+// their stage 1 in turns where they can, and a wave in its tail issues ahead of its partner's stage 1 (s_setprio).  One LDS
+// word per SIMD behind the waves' regions; bit w = "wave w of this workgroup is in stage 1", written by wave w alone (LDS
+// atomics on its own bit).  A wave about to enter looks at the other bits of its SIMD's word and, while one is set, sleeps --
+// at most E2VQ_SWEEP_TOKEN_POLLS times, then it enters whatever the word says.  ADVISORY ONLY: the word is read into that
+// loop's exit condition and nowhere else, so no computed value depends on it; no barrier, no wait on another workgroup, no
+// loop without a constant bound; a wave without turns never sets its bit; with every `TOKEN` statement deleted the kernel
+// is the one it was.  The cap is the longest a partner can hold the word for a reason (one stage 1 at M = 1024: 76 k cycles):
+// caps of 12 and 64 polls measured no or half the gain (docs/HISTORY.md).
+#ifndef E2VQ_SWEEP_TOKEN_POLLS  // (A/B switch of the probes: 0 = the bits are kept, nobody waits)
+#define E2VQ_SWEEP_TOKEN_POLLS 256  // x (s_sleep 4 = 256 cycles + one LDS read)
+#endif
+constexpr int SWEEP_TOKEN_BYTES = 16;  // four SIMDs per CU
 
 struct SweepCounters {
     unsigned long long flagged;  // (tile, column block) jobs that ran stage 2
@@ -412,6 +431,33 @@ __global__ __launch_bounds__((FUSE ? SweepLds<NC>::WAVES_FUSE : 8) * 64, 2) void
     const int col = lane & 31, h = lane >> 5;
     unsigned long long nflag = 0, njobs = 0;
     SW_STAMP_DECL
+    // the stage-1 token (above): this wave's bit, the word of its SIMD.  A workgroup of fewer than eight waves never waits.
+    constexpr bool TOKEN = TWO && FUSE && WAVES == 8;
+    const unsigned tok_me = 1u << wib;
+    unsigned* tok_w = nullptr;
+    if constexpr (TOKEN) {
+        unsigned* const tok = (unsigned*)(smem + (size_t)WAVES * WAVE_LDS);
+        // (the words hold whatever the CU's last workgroup left there: every wave clears ITS bit in all four before it can
+        // set it -- a stale bit of a partner that has not got this far yet costs one bounded wait)
+        if (lane < 4) __hip_atomic_fetch_and(&tok[lane], ~tok_me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        tok_w = tok + (__builtin_amdgcn_s_getreg((2 - 1) << 11 | 4 << 6 | 4) & 3u);  // HW_ID[5:4]: the SIMD
+    }
+    auto tok_others = [&]() {  // is another wave of this SIMD in stage 1? (wave-uniform)
+        const unsigned w = __hip_atomic_load(tok_w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return (__builtin_amdgcn_readfirstlane((int)w) & 0xff & ~(int)tok_me) != 0;
+    };
+    // (the bit as an operand made afresh at every use: as a loop invariant it is a vector register alive across stage 1,
+    // whose budget has none left)
+    auto tok_set = [&](bool on) {
+        unsigned me = tok_me;
+        asm volatile("" : "+s"(me));
+        if (lane == 0) {
+            if (on)
+                __hip_atomic_fetch_or(tok_w, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else
+                __hip_atomic_fetch_and(tok_w, ~me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
 
     // A turn of the loop = NB blocks of 64 slots = NCB column blocks of 32.  The fused two-stage kernel takes TWO blocks per
     // turn: what bounds its stage 1 is not the matrix pipe but what the codeword tiles' operand loads cost the CU's
@@ -472,12 +518,13 @@ __global__ __launch_bounds__((FUSE ? SweepLds<NC>::WAVES_FUSE : 8) * 64, 2) void
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) load_pairs(B[cb], g[cb], fn[cb], NB == 2 ? 5 : 7);
     };
-    if (wave < nturns) {
+    const long turn0 = SW_EXP(128) && wib >= 4 ? nturns : wave;  // (the product: `wave`)
+    if (turn0 < nturns) {
         next_frames(wave);
         home_n = home_of(fn[0]);
         request_B();
     }
-    for (long turn = wave; turn < nturns; turn += nwaves) {
+    for (long turn = turn0; turn < nturns; turn += nwaves) {
         unsigned f[NCB];
         float gc[NCB];
 #pragma unroll
@@ -538,6 +585,26 @@ __global__ __launch_bounds__((FUSE ? SweepLds<NC>::WAVES_FUSE : 8) * 64, 2) void
                 return home + i < MT ? home + i : home + i - MT;
             };
             constexpr int ND = 2;  // register sets
+            if constexpr (TOKEN) {
+                __builtin_amdgcn_s_setprio(0);
+                // (the block's rows and the turn's B operands are under way: the wait costs the wave nothing it could issue)
+#pragma unroll 1
+                for (int p = 0; p < E2VQ_SWEEP_TOKEN_POLLS && tok_others(); ++p) {
+                    __builtin_amdgcn_s_sleep(4);
+#ifdef E2VQ_SWEEP_STAMP
+                    sw_polls += 1;
+#endif
+                }
+#ifdef E2VQ_SWEEP_STAMP
+                sw_in += tok_others() ? 1 : 0;
+                {   // (the token's wait is booked with the wait for B: stage 1's stamp is its MFMA loop)
+                    const unsigned long long sw_now = __builtin_amdgcn_s_memtime();
+                    sw_acc[0] += sw_now - sw_t;
+                    sw_t = sw_now;
+                }
+#endif
+                tok_set(true);
+            }
             h8 A[ND][NU];
 #pragma unroll
             for (int k = 0; k < ND - 1; ++k) sweep_load_tile<NC>(A[k], cimg, tile_at(k), lane, true);
@@ -605,6 +672,15 @@ __global__ __launch_bounds__((FUSE ? SweepLds<NC>::WAVES_FUSE : 8) * 64, 2) void
                 tlist[0] = (unsigned short)((unsigned)home | ((1u << NCB) - 1u) << 8);
             }
             SW_STAMP(1)  // stage 1
+            if constexpr (TOKEN) {
+                // the tail's instructions -- few, and most of them waited for -- go ahead of the partner's stage 1, which
+                // always has the next MFMA to offer (the issue priority decides nothing but the order of issue)
+                __builtin_amdgcn_s_setprio(1);
+#ifdef E2VQ_SWEEP_STAMP
+                sw_out += tok_others() ? 1 : 0;
+#endif
+                tok_set(false);
+            }
             next_frames(tn);
         }
 #pragma unroll
@@ -769,7 +845,9 @@ __global__ __launch_bounds__((FUSE ? SweepLds<NC>::WAVES_FUSE : 8) * 64, 2) void
                 } else {
                     if (fz.sym) fz.sym[fr] = (unsigned short)idx;
                     if (fz.dmin) fz.dmin[fr] = best;
-                    fz.cells[fr] = (unsigned short)idx;
+                    // (an incremental pass finds most frames in the cell they had: `oldraw` is that cell, already in a
+                    // register -- 64 scattered 2-byte stores per block go only where the cell changed)
+                    if (fz.incr != 1 || (int)oldraw != idx) fz.cells[fr] = (unsigned short)idx;
                     const double e = best - 1.0;
                     int h0, l0, h1, l1;
                     if (fast_d) {  // (kernel-uniform; same limbs as fix2: vq_fixed.h)
@@ -887,6 +965,9 @@ __global__ __launch_bounds__((FUSE ? SweepLds<NC>::WAVES_FUSE : 8) * 64, 2) void
         atomicAdd(&g_sweep_stamps[10], nflag);
         atomicAdd(&g_sweep_stamps[11], njobs);
         atomicAdd(&g_sweep_stamps[12], sw_conv);
+        atomicAdd(&g_sweep_stamps[13], sw_in);
+        atomicAdd(&g_sweep_stamps[14], sw_out);
+        atomicAdd(&g_sweep_stamps[15], sw_polls);
     }
 #endif
     if (counters && lane == 0 && njobs) {
@@ -1270,7 +1351,7 @@ static int launch_pass_sorted_t(bool two_stage, bool one_block, const void* fimg
         constexpr int W = SweepLds<NC>::WAVES_FUSE;
         long g = (nblocks + W - 1) / W;
         const int grid = (int)(g < 1 ? 1 : (g > 256 ? 256 : g));
-        const size_t lds = (size_t)W * SweepLds<NC>::WAVE_BYTES_FUSE;
+        const size_t lds = (size_t)W * SweepLds<NC>::WAVE_BYTES_FUSE + SWEEP_TOKEN_BYTES;  // (FIT leaves 256 bytes)
         auto go = [&](auto kernel) {
             (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, E2VQ_LDS_BYTES);
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(W * 64), lds, s, (const unsigned char*)fimg, perm, T, nblocks, (const h8*)cimg,

@@ -1,6 +1,8 @@
 """Timing experiments on the stamped fused sorted pass (round 5): what a wave's stage 1 / tail cost without one of their
 ingredients.  Needs a -DE2VQ_SWEEP_STAMP=2 library (tools/probe/ab/build_variant.sh); results under an experiment are WRONG
-by construction -- the level's state is restored before each run.  EXP_M = codebook size(s) to look at."""
+by construction -- the level's state is restored before each run.  EXP_M = codebook size(s) to look at.
+EXP_MODES=0,128,0 gives stage 1's rate with one wave per SIMD (bit 128) beside the product's; the last three columns tell how
+often the two waves of a SIMD are in stage 1 together (the stage-1 token)."""
 import ctypes as C
 import os
 import sys
@@ -48,5 +50,11 @@ for M in want:
             fx(0)
             n = max(1, buf[8])
             per = [buf[k] / n for k in range(7)]
-            print(f"M {M:5d} exp {mode:2d} {what:40s}: kernel {ms:.3f} ms; " + ", ".join(f"{nm} {v:7.0f}" for nm, v in zip(names, per)) +
-                  f", conversion {buf[12] / n:6.0f}; total {sum(per) + buf[12] / n:7.0f}; flagged {buf[10] / max(1, buf[11]):.3f}; kind {s.last_pass_sweep()}", flush=True)
+            # stage 1 issues 16 MFMAs per tile and block (two column blocks x 8 k-steps); a turn = two blocks where the shard has
+            # 4096 blocks or more (vq_pass.cpp).  Slots 13 / 14: turns that found a SIMD partner in stage 1 when they entered
+            # theirs (behind the token's wait) / when they left it; slot 15: the token's polls that slept.
+            turns = max(1, buf[8] // (2 if S // 64 >= 4096 else 1))
+            print(f"M {M:5d} exp {mode:3d} {what:40s}: kernel {ms:.3f} ms; " + ", ".join(f"{nm} {v:7.0f}" for nm, v in zip(names, per)) +
+                  f", conversion {buf[12] / n:6.0f}; total {sum(per) + buf[12] / n:7.0f}; flagged {buf[10] / max(1, buf[11]):.3f}; kind {s.last_pass_sweep()}; "
+                  f"stage 1 cycles per MFMA {per[1] / (M // 32 * 16):.1f}; partner in stage 1 at entry {buf[13] / turns:.3f}, at exit {buf[14] / turns:.3f}; "
+                  f"polls per turn {buf[15] / turns:.2f}", flush=True)
