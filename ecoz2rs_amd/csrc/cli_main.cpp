@@ -72,11 +72,14 @@ static int usage()
             "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  --switch-penalty <x <= 0 | -inf> [-c <csv dir|file.csv>]\n"
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
+            "                  [--body <auto|resident|looped>]\n"
             "                  [--class-transitions <file.csv>]\n"
             "                  [--continuous <name>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
             "                  --posteriors adds each segment's mean and least class posterior, and the per-frame table)\n"
+            "                  (--body, with --posteriors: the kernel body of the posteriors -- resident takes at most 16 wave-slots\n"
+            "                  of classes, looped any number, auto the looped one above 16; the figures are the same bit for bit)\n"
             "                  (--class-transitions adds the file's price of every class-to-class succession to the penalty)\n"
             "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
@@ -854,7 +857,7 @@ static int hmm_segment_cmd(int argc, char** argv)
     bool have_switch = false;
     bool posteriors = false;
     bool continuous = false;
-    std::string codebook, csv, frames_dir, transitions, rec_name;
+    std::string codebook, csv, frames_dir, transitions, rec_name, body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -876,6 +879,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
         else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
         else if (a == "--posteriors") posteriors = true;
+        else if (a == "--body") body = val("--body");
         else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
         else if (a == "--class-transitions") transitions = val("--class-transitions");
@@ -903,6 +907,14 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
     if (!frames_dir.empty() && !posteriors) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
+    if (!body.empty()) {  // the body of the posteriors (ECOZ2_HMM_POSTERIOR_BODY), set in this process before the call
+        if (!posteriors) { fprintf(stderr, "hmm segment: --body <auto|resident|looped> needs --posteriors\n"); return 2; }
+        if (body != "auto" && body != "resident" && body != "looped") {
+            fprintf(stderr, "hmm segment --posteriors: --body %s: auto, resident or looped\n", body.c_str());
+            return usage();
+        }
+        setenv("ECOZ2_HMM_POSTERIOR_BODY", body.c_str(), 1);
+    }
     if (!transitions.empty() && posteriors) {
         fprintf(stderr, "hmm segment: --class-transitions and --posteriors exclude one another (the posteriors know one price only)\n");
         return 2;

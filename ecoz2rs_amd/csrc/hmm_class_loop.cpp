@@ -119,6 +119,17 @@ int loop_body_looped(const char* env_name, int slots, bool* looped)
     return 0;
 }
 
+int opt_in_body(const char* env_name, int* body)
+{
+    const char* v = getenv(env_name);
+    *body = EMBED_BODY_RESIDENT;
+    if (!v || !*v || strcmp(v, "resident") == 0) return 0;
+    if (strcmp(v, "looped") == 0) *body = EMBED_BODY_LOOPED;
+    else if (strcmp(v, "auto") == 0) *body = EMBED_BODY_AUTO;
+    else return e2vq_set_error("%s=%s: auto, resident or looped", env_name, v);
+    return 0;
+}
+
 int ClassLoopDev::upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st)
 {
     if (params.upload(host_params.data(), host_params.size(), st) || lanes.upload(pk.lanes.data(), pk.lanes.size(), st) ||
@@ -239,9 +250,27 @@ int segment_device(const LoopModels& lm, const unsigned short* d_sym, const i64*
 // ---- hmm segment --posteriors: forward-backward through the same class loop -------------------------------
 int posteriors_a_ld(int N) { return N | 1; }  // (odd: see hmm_posterior.hip)
 
-int posteriors_check_slots(const char* who, int K, const int* Ns)
+// the body of the pass (ECOZ2_HMM_POSTERIOR_BODY): resident (at most 16 slots) unless the caller opts into the looped one
+int posteriors_body(int* body) { return opt_in_body("ECOZ2_HMM_POSTERIOR_BODY", body); }
+
+bool posteriors_looped(int body, int slots)
 {
-    return check_resident(who, pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld).slots, "the posteriors have");
+    return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
+}
+
+// (host only) resident: at most 16 slots.  looped: the mandatory LDS of hmm_posterior_looped.hip must fit -- with
+// segment_check_shape's caps it always does; the check stands for the day a cap moves.
+int posteriors_check_slots(const char* who, int K, const int* Ns, int body)
+{
+    const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld);
+    if (!posteriors_looped(body, pk.slots)) return check_resident(who, pk.slots, "the posteriors have");
+    e2hmm::SegPlanDev shape{};
+    shape.slots = pk.slots, shape.sumN = pk.sumN;
+    const size_t need = e2hmm::posteriors_looped_lds_bytes(shape, false);
+    if (need > e2hmm::SEG_LDS_BYTES)
+        return e2vq_set_error("%s: %d wave-slots and %d states take %zu bytes of LDS in the looped body of the posteriors (at most %zu)",
+                              who, pk.slots, pk.sumN, need, (size_t)e2hmm::SEG_LDS_BYTES);
+    return 0;
 }
 
 // log_model's refusal, without the logarithms: a negative, NaN or infinite parameter (then no NaN can arise on the device)
@@ -266,14 +295,16 @@ struct PostOut {  // host arrays, any may be null; post: K doubles a frame; per 
 
 // The smoothed class posteriors of S device-resident streams (h_offs: their S + 1 offsets, on the host) under the class
 // loop of the models (already checked by segment_check_shape and posteriors_check_slots; all of one M), on the current
-// device and the stream st.
+// device and the stream st, by the body that posteriors_body gave.
 int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, double ln_switch, hipStream_t st,
-                      const PostOut& out)
+                      const PostOut& out, int body)
 {
     const int K = lm.K(), M = lm.M;
     const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);
     const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
     const double sw = exp(ln_switch);  // (-inf: 0.0)
+    const bool looped = posteriors_looped(body, slots);
+    const int waves = looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots;  // each stores its copy of c_t
     // pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class
     std::vector<double> params((size_t)2 * sumN + (size_t)a_words + (size_t)sumN * M, 0.0);
     for (int k = 0; k < K; ++k) {
@@ -297,10 +328,10 @@ int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i
         return 1;
     const e2hmm::SegPlanDev& pl = loop.pl;
     // launches of whole streams whose ah (8 sumN bytes a frame) and c (8 bytes a frame and wave) stay within the budget
-    const i64 row = 8 * ((i64)sumN + slots);
+    const i64 row = 8 * ((i64)sumN + waves);
     i64 max_frames = 0;
     const auto chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * slots)) {
+    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves)) {
         const std::string why = e2vq_last_error();
         return e2vq_set_error("hmm segment --posteriors: no room for the forward table of %lld frames x %d states (%lld bytes; "
                               "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
@@ -312,8 +343,9 @@ int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i
     // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
     for (const auto& c : chunks) {
         const int s0 = c.first, n = c.second - c.first;
-        if (e2hmm::launch_loop_posteriors(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], sw, d_ah.get(), d_c.get(), d_post.get(),
-                                          sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+        const auto launch = looped ? e2hmm::launch_loop_posteriors_looped : e2hmm::launch_loop_posteriors;
+        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], sw, d_ah.get(), d_c.get(), d_post.get(), sc.d_mant.get() + s0,
+                   sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
             return e2vq_set_error("hmm segment --posteriors: %d wave-slots of %d states cannot be launched", slots, sumN);
         HIPCHK(hipGetLastError());
     }
@@ -490,7 +522,8 @@ int segment_files(const char* who, const char* const* model_filenames, unsigned 
         window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models))
         return 1;
     const int K = lm.K();
-    if (posteriors && posteriors_check_slots(who, K, lm.Ns.data())) return 1;
+    int body = EMBED_BODY_RESIDENT;
+    if (posteriors && (posteriors_body(&body) || posteriors_check_slots(who, K, lm.Ns.data(), body))) return 1;
     if (lm.logs(model_filenames)) return 1;
     const std::string fdir = posteriors && frames_dir ? frames_dir : "";
     auto frames_csv = [&](const char* path) { return fdir + "/" + e2vq_io::basename_noext(path) + ".csv"; };
@@ -514,7 +547,7 @@ int segment_files(const char* who, const char* const* model_filenames, unsigned 
             post.resize(n * (size_t)K);
             PostOut po;
             po.post = post.data();
-            if (posteriors_device(lm, d_sym, offs, 1, ln_switch, st, po)) return 1;
+            if (posteriors_device(lm, d_sym, offs, 1, ln_switch, st, po, body)) return 1;
         }
         const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
         return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), gbest.data(), lp,
@@ -583,14 +616,16 @@ extern "C" int e2vq_hmm_segment_posteriors(int device, int K, const int* Ns, int
     const char* who = "e2vq_hmm_segment_posteriors";
     LoopModels lm;
     DevSeqs seqs;
+    int body = EMBED_BODY_RESIDENT;
     if (loop_check_args(who, K, Ns, pis, As, Bs, syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
-        segment_check_switch(who, ln_switch) || posteriors_check_slots(who, K, Ns) || lm.from_arrays(K, Ns, M, pis, As, Bs))
+        segment_check_switch(who, ln_switch) || posteriors_body(&body) || posteriors_check_slots(who, K, Ns, body) ||
+        lm.from_arrays(K, Ns, M, pis, As, Bs))
         return 1;
     for (const Hmm& h : lm.models)
         if (posteriors_check_params(h)) return 1;
     if (seqs.open(device, sym, offs, S, sym_on_device != 0)) return 1;
     const PostOut out{post, log_prob, status};
-    return posteriors_device(lm, seqs.sym, (const i64*)offs, S, ln_switch, seqs.st.s, out);
+    return posteriors_device(lm, seqs.sym, (const i64*)offs, S, ln_switch, seqs.st.s, out, body);
 }
 
 extern "C" int e2vq_hmm_segment_report_posteriors(const char* name, int64_t T, int K, const char* const* class_names, int W_ms,

@@ -285,5 +285,13 @@ int launch_align_posteriors(const EmbedPlanDev& pl, bool a_lds, int waves, const
 bool posteriors_a_in_lds(const SegPlanDev& pl);
 int launch_loop_posteriors(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0, double sw,
                            double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status, hipStream_t st);
+// The looped body of the same pass (hmm_posterior_looped.hip): any number of slots, a workgroup of min(slots, 16) waves per
+// stream; the same post, P and status bit for bit.  The same plan, parameter block and tables, except that cs takes
+// (frames of the launch) x min(slots, 16) doubles: a copy of c_t per wave.  Dynamic LDS: 8 (2 slots + sumN) bytes are mandatory
+// (the partial sums of GS in both parities, and one double per composite state); A, 8 a_words bytes, goes behind them when
+// the sum stays within SEG_LDS_BYTES (a_lds).  Returns 1 when the shape cannot be launched.
+size_t posteriors_looped_lds_bytes(const SegPlanDev& pl, bool a_lds);
+int launch_loop_posteriors_looped(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0, double sw,
+                                  double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status, hipStream_t st);
 
 }  // namespace e2hmm

@@ -313,6 +313,10 @@ std::vector<double> loop_log_params(const LoopModels& lm, const SegPacking& pk);
 // the body of a class-loop kernel: looped where `slots` exceed a workgroup's waves or the variable `env_name` says
 // "looped" (slots = 0: whether it says so); a value other than "resident" or "looped" is refused
 int loop_body_looped(const char* env_name, int slots, bool* looped);
+// the body of a pass whose looped kernel is opt-in (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY): unset, empty or
+// "resident" / "looped" / "auto" of the variable `env_name` -> *body (an EmbedBody, below); any other value is refused with
+// "<env_name>=<v>: auto, resident or looped"
+int opt_in_body(const char* env_name, int* body);
 
 // A packing on the device: the parameter block, the four tables of `pk`, and the plan the kernels take.  upload() only
 // enqueues: the host vectors must outlive the stream's copies, and this struct the stream's kernels (a local is declared

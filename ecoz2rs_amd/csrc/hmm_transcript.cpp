@@ -160,16 +160,7 @@ int embed_route(const char* name, bool* forced, bool* lds)
     return 0;
 }
 
-int embed_body(int* body)
-{
-    const char* v = getenv("ECOZ2_HMM_EMBED_BODY");
-    *body = EMBED_BODY_RESIDENT;
-    if (!v || !*v || strcmp(v, "resident") == 0) return 0;
-    if (strcmp(v, "looped") == 0) *body = EMBED_BODY_LOOPED;
-    else if (strcmp(v, "auto") == 0) *body = EMBED_BODY_AUTO;
-    else return e2vq_set_error("ECOZ2_HMM_EMBED_BODY=%s: auto, resident or looped", v);
-    return 0;
-}
+int embed_body(int* body) { return opt_in_body("ECOZ2_HMM_EMBED_BODY", body); }
 
 int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
                const uint8_t* optional, double ln_switch, const char* what, bool first_flags, int body, EStepPlan& p)

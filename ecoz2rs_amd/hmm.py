@@ -146,6 +146,24 @@ def _kernel_ms(fn):
     return ms.value
 
 
+@contextlib.contextmanager
+def _body_env(name, body):
+    """the variable `name` (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY) = body ("auto", "resident" or "looped") for the
+    duration of a call; None leaves the environment alone"""
+    if body is None:
+        yield
+        return
+    before = os.environ.get(name)
+    os.environ[name] = str(body)
+    try:
+        yield
+    finally:
+        if before is None:
+            del os.environ[name]
+        else:
+            os.environ[name] = before
+
+
 def set_random_seed(seed):
     """ecoz2_lib::set_random_seed (src/ecoz2_lib/mod.rs:188-190)"""
     return lib.ecoz2_set_random_seed(int(seed))
@@ -611,9 +629,11 @@ class SegmentStream:
         return dict(peak_pending=pk.value, device_bytes=by.value, commit_ms=ms.value)
 
 
-def segment_posteriors(models, sym, offs, ln_switch, device=0):
+def segment_posteriors(models, sym, offs, ln_switch, device=0, body=None):
     """P(class at frame t | the whole stream) under the class loop `segment` decodes: arguments as
-    `segment` takes them (sym a numpy array or a device tensor); the classes must pack into at most 16 wave-slots.
+    `segment` takes them (sym a numpy array or a device tensor); the classes must pack into at most 16 wave-slots unless
+    the looped body is chosen.  body: "auto", "resident" or "looped" (ECOZ2_HMM_POSTERIOR_BODY for this call: the looped
+    body takes any number of wave-slots, "auto" uses it above 16; the same bits either way); None: what the environment says.
     -> dict: post (sum T_s, K), row offs[s] + t; per stream log_prob = ln P(O | loop) and status (0 ok, 1 the loop cannot
     emit the stream, 2 a symbol >= M; then the stream's rows are 0.0 and log_prob is -inf)"""
     K = len(models)
@@ -634,8 +654,9 @@ def segment_posteriors(models, sym, offs, ln_switch, device=0):
     T = int(offs[-1])
     post = np.zeros((max(T, 1), max(K, 1)))
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_segment_posteriors(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, float(ln_switch),
-                                          post.ctypes.data, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    with _body_env("ECOZ2_HMM_POSTERIOR_BODY", body):
+        check(lib.e2vq_hmm_segment_posteriors(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, float(ln_switch),
+                                              post.ctypes.data, lp.ctypes.data, st.ctypes.data, int(on_device)))
     return dict(post=post[:T], log_prob=lp[:S], status=st[:S])
 
 
@@ -735,11 +756,11 @@ def class_transitions_files(model_filenames, input_filenames, out_csv, alpha=1.0
 
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
-                  frame_posteriors=None, class_transitions=None, continuous=None):
+                  frame_posteriors=None, class_transitions=None, continuous=None, body=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
-    table for every input.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch.  continuous
+    table for every input; body as `segment_posteriors` takes it.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch.  continuous
     (4.8.9): the name of the one recording whose consecutive pieces the inputs are -- one block, and with `csv` (a directory
     or a .csv file) one CSV, <csv>/<name>.csv"""
     m, _k1 = _strs(model_filenames)
@@ -753,6 +774,8 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
         return
     if frame_posteriors is not None and not posteriors:
         raise ValueError("frame_posteriors needs posteriors=True")
+    if body is not None and not posteriors:
+        raise ValueError("body needs posteriors=True")
     if class_transitions is not None:
         if posteriors:
             raise ValueError("class_transitions and posteriors exclude one another")
@@ -761,10 +784,11 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
                                                str(class_transitions).encode(), str(csv).encode() if csv else None))
         return
     if posteriors:
-        check(lib.e2vq_hmm_segment_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
-                                                    len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                                    str(csv).encode() if csv else None,
-                                                    str(frame_posteriors).encode() if frame_posteriors is not None else None))
+        with _body_env("ECOZ2_HMM_POSTERIOR_BODY", body):
+            check(lib.e2vq_hmm_segment_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                        len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                        str(csv).encode() if csv else None,
+                                                        str(frame_posteriors).encode() if frame_posteriors is not None else None))
         return
     check(lib.e2vq_hmm_segment_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                      len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
@@ -928,24 +952,6 @@ def _transcript_args(models, sym, offs, units, unit_offs, optional, copy=True):
                            keep=(optional, sym))
 
 
-@contextlib.contextmanager
-def _embed_body(body):
-    """ECOZ2_HMM_EMBED_BODY = body ("auto", "resident" or "looped") for the duration of a call; None leaves the environment alone"""
-    if body is None:
-        yield
-        return
-    name = "ECOZ2_HMM_EMBED_BODY"
-    before = os.environ.get(name)
-    os.environ[name] = str(body)
-    try:
-        yield
-    finally:
-        if before is None:
-            del os.environ[name]
-        else:
-            os.environ[name] = before
-
-
 def embedded_estep(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, device=0, body=None):
     """one E-step of embedded Baum-Welch: models, sym, offs, units, unit_offs, optional, ln_switch as `align`
     takes them -> dict acc (per class its int64 accumulator words, the layout of `acc_words`), log_prob (ln P(O, transcript)
@@ -956,7 +962,7 @@ def embedded_estep(models, sym, offs, units, unit_offs, optional=None, ln_switch
     acc = [np.zeros(int(lib.e2vq_hmm_acc_words(len(m[0]), a.M)), dtype=np.int64) for m in a.ms]
     accp = (C.c_void_p * max(len(acc), 1))(*[x.ctypes.data for x in acc])
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    with _embed_body(body):
+    with _body_env("ECOZ2_HMM_EMBED_BODY", body):
         check(lib.e2vq_hmm_embedded_estep(device, *a.c_args, float(ln_switch), accp, lp.ctypes.data, st.ctypes.data, a.on_device))
     return dict(acc=acc, log_prob=lp[:S], status=st[:S])
 
@@ -969,7 +975,7 @@ def train_embedded(models, sym, offs, units, unit_offs, optional=None, ln_switch
     cap = 1000
     hist = np.zeros(cap)
     n = C.c_int(0)
-    with _embed_body(body):
+    with _body_env("ECOZ2_HMM_EMBED_BODY", body):
         check(lib.e2vq_hmm_train_embedded(device, *a.c_args, float(ln_switch), float(epsilon), float(val_auto), int(max_iterations),
                                           hist.ctypes.data, cap, C.byref(n), a.on_device))
     return a.ms, hist[:n.value].copy()
@@ -990,7 +996,7 @@ def learn_embedded_files(model_filenames, input_filenames, label_filenames, out_
     f, _k2 = _strs(input_filenames)
     l, _k3 = _strs(label_filenames)
     cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
-    with _embed_body(body):
+    with _body_env("ECOZ2_HMM_EMBED_BODY", body):
         check(lib.e2vq_hmm_learn_embedded_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
                                                 len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
                                                 str(filler).encode() if filler else None, float(hmm_epsilon), float(val_auto),

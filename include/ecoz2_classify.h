@@ -326,7 +326,8 @@ int e2vq_hmm_segment_files(const char *const *model_filenames, unsigned num_mode
  * decodes -- the forward-backward companion of its joint Viterbi: at every frame the whole mass may leave its class and
  * enter any class through that class's pi at the price sw = exp(ln_switch) (the C library's exp on the host; -inf gives 0).
  * Inputs and refusals are e2vq_hmm_segment's; in addition a packing of more than 16 wave-slots is refused (classes are
- * packed in class order into slots of 64 lanes, a class that does not fit the open slot opens the next).  The arithmetic is
+ * packed in class order into slots of 64 lanes, a class that does not fit the open slot opens the next) unless
+ * ECOZ2_HMM_POSTERIOR_BODY chooses the looped body (the last paragraph).  The arithmetic is
  * scaled and linear, every operation one IEEE double operation in a fixed order, no fma (DESIGN.md 4.8.7 states it;
  * tests/hmm_posterior_restatement.py restates it; the GPU matches it bit for bit):
  *   x_0[k][j] = pi_k[j] B_k[j][o_0];  x_t[k][j] = (sum_i ah_{t-1}[k][i] A_k[i][j] + sw pi_k[j]) B_k[j][o_t];
@@ -338,7 +339,17 @@ int e2vq_hmm_segment_files(const char *const *model_filenames, unsigned num_mode
  * order decides.  Status != 0: every post entry of the stream is 0.0 and log_prob is -inf.  An empty stream: status 0,
  * log_prob 0.0, no rows.  One device.  sym_on_device as in e2vq_hmm_segment.
  * ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds the per-launch forward table (default 256 MiB, whole streams; a table that cannot
- * be allocated is an error). */
+ * be allocated is an error).
+ * The body.  ECOZ2_HMM_POSTERIOR_BODY chooses the kernel body in e2vq_hmm_segment_posteriors and
+ * e2vq_hmm_segment_files_posteriors (no other entry point reads it).  Unset, empty or "resident": as above, more than 16
+ * wave-slots are refused with "the classes take %d wave-slots of 64 lanes (at most 16: the posteriors have no looped body)".
+ * "looped": the looped body for every packing, in which a wave serves several slots in turn.  "auto": resident up to 16
+ * slots, looped above.  Any other value is refused before any HIP call: "ECOZ2_HMM_POSTERIOR_BODY=<v>: auto, resident or looped".
+ * The contract above never depended on the body -- the global sum is defined for any number of slots: a butterfly per slot,
+ * then the slot results added in slot order from slot 0 -- so post, log_prob and status are the same bits under either body.
+ * The looped body keeps 8 (2 slots + sum N) bytes in LDS (its partial sums and one double per state); a packing whose bytes
+ * exceeded the 160 KB would be refused before any HIP call ("%d wave-slots and %d states take %zu bytes of LDS in the looped
+ * body of the posteriors"), which the limits on N_k and on the number of states (at most 34 832 bytes) keep out of reach. */
 int e2vq_hmm_segment_posteriors(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
                                 const double *const *Bs, const void *sym, const int64_t *offs, int S, double ln_switch,
                                 double *post, double *log_prob, int *status, int sym_on_device);

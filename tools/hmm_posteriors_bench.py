@@ -10,6 +10,9 @@ refused, with the library's message):
               how many segmentations a posterior pass costs.
 --warmup + --reps of each.  Kernel times come from one `rocprofv3 --kernel-trace` run of this script (--run) per N; each
 call's own HIP-event time is recorded next to it.  median and min .. max over the repetitions.
+--bodies (a list of auto, resident, looped: ECOZ2_HMM_POSTERIOR_BODY of the posteriors calls): a run per N and body, by_N[N][body],
+and looped_over_resident where both ran -- the price of the looped body where the resident one runs.  Without it, one run
+per N with the environment's body, by_N[N], as before.
 """
 import argparse
 import csv
@@ -52,12 +55,12 @@ def run(args):
     models, sym = workload(args.n, args.m, args.k, args.t)
     offs = np.array([0, len(sym)], dtype=np.int64)
     try:
-        e.hmm.segment_posteriors(models, sym[:8], [0, 8], args.ln_switch)
+        e.hmm.segment_posteriors(models, sym[:8], [0, 8], args.ln_switch, body=args.body)
     except e.Ecoz2Error as err:
         print(json.dumps(dict(refused=str(err))))
         return
     out = {}
-    calls = (("posteriors", lambda: e.hmm.segment_posteriors(models, sym, offs, args.ln_switch), e.hmm.segment_posteriors_last_kernel_ms),
+    calls = (("posteriors", lambda: e.hmm.segment_posteriors(models, sym, offs, args.ln_switch, body=args.body), e.hmm.segment_posteriors_last_kernel_ms),
              ("comparator", lambda: e.hmm.segment(models, sym, offs, args.ln_switch), e.hmm.segment_last_kernel_ms))
     for kind, call, event in calls:
         ts, ev = [], []
@@ -100,37 +103,51 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=600)
+    ap.add_argument("--body", help="(internal) the body of the run")
+    ap.add_argument("--bodies", help="auto, resident and / or looped, comma-separated: a run per N and body")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.run:
         return run(args)
     rec = dict(tool="tools/hmm_posteriors_bench.py", M=args.m, K=args.k, T=args.t, ln_switch=args.ln_switch, reps=args.reps,
                warmup=args.warmup, by_N={})
+    bodies = args.bodies.split(",") if args.bodies else [None]
+    if args.bodies:
+        rec["bodies"] = bodies
     for N in [int(x) for x in args.ns.split(",")]:
-        with tempfile.TemporaryDirectory() as d:
-            cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-                   sys.executable, os.path.abspath(__file__), "--run", "--n", str(N), "--m", str(args.m), "--k", str(args.k),
-                   "--t", str(args.t), "--ln-switch", str(args.ln_switch), "--reps", str(args.reps), "--warmup", str(args.warmup)]
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
-            if r.returncode != 0:
-                sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-                raise SystemExit(f"N = {N}: rocprofv3 run failed with status {r.returncode}")
-            host = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-            if "refused" in host:
-                ent = host
-            else:
-                traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-                if len(traces) != 1:
-                    raise SystemExit(f"N = {N}: expected one kernel trace, found {traces}")
-                k = kernel_ms(traces[0], args.warmup + args.reps, args.warmup, {"posteriors": 1})
-                for kind in k:
-                    k[kind].update(host[kind])
-                ent = dict(kinds=k)
-                if "kernel_ms" in k["posteriors"] and "kernel_ms" in k["comparator"]:
-                    ent["ratio"] = k["posteriors"]["kernel_ms"] / k["comparator"]["kernel_ms"]
-                    ent["ratio_wall"] = k["posteriors"]["call_wall_ms"] / k["comparator"]["call_wall_ms"]
-        rec["by_N"][str(N)] = ent
-        print(json.dumps({str(N): ent}), flush=True)
+        ents = {}
+        for body in bodies:
+            with tempfile.TemporaryDirectory() as d:
+                cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--",
+                       sys.executable, os.path.abspath(__file__), "--run", "--n", str(N), "--m", str(args.m), "--k", str(args.k),
+                       "--t", str(args.t), "--ln-switch", str(args.ln_switch), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+                if body:
+                    cmd += ["--body", body]
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
+                if r.returncode != 0:
+                    sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+                    raise SystemExit(f"N = {N}: rocprofv3 run failed with status {r.returncode}")
+                host = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+                if "refused" in host:
+                    ent = host
+                else:
+                    traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+                    if len(traces) != 1:
+                        raise SystemExit(f"N = {N}: expected one kernel trace, found {traces}")
+                    k = kernel_ms(traces[0], args.warmup + args.reps, args.warmup, {"posteriors": 1})
+                    for kind in k:
+                        k[kind].update(host[kind])
+                    ent = dict(kinds=k)
+                    if "kernel_ms" in k["posteriors"] and "kernel_ms" in k["comparator"]:
+                        ent["ratio"] = k["posteriors"]["kernel_ms"] / k["comparator"]["kernel_ms"]
+                        ent["ratio_wall"] = k["posteriors"]["call_wall_ms"] / k["comparator"]["call_wall_ms"]
+            ents[body] = ent
+        if args.bodies:
+            ms = {b: x["kinds"]["posteriors"].get("kernel_ms") for b, x in ents.items() if "kinds" in x}
+            if ms.get("looped") and ms.get("resident"):
+                ents["looped_over_resident"] = ms["looped"] / ms["resident"]
+        rec["by_N"][str(N)] = ents if args.bodies else ents[None]
+        print(json.dumps({str(N): rec["by_N"][str(N)]}), flush=True)
     line = json.dumps(rec)
     print(line)
     if args.out:
