@@ -74,6 +74,7 @@ static int usage()
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
             "                  [--body <auto|resident|looped>]\n"
             "                  [--class-transitions <file.csv>]\n"
+            "                  [--grammar-posteriors [--frame-posteriors <dir>]]\n"
             "                  [--continuous <name>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
@@ -81,6 +82,8 @@ static int usage()
             "                  (--body, with --posteriors: the kernel body of the posteriors -- resident takes at most 16 wave-slots\n"
             "                  of classes, looped any number, auto the looped one above 16; the figures are the same bit for bit)\n"
             "                  (--class-transitions adds the file's price of every class-to-class succession to the penalty)\n"
+            "                  (--grammar-posteriors, with --class-transitions: the posteriors under those prices, reported as\n"
+            "                  --posteriors reports them)\n"
             "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
@@ -857,6 +860,7 @@ static int hmm_segment_cmd(int argc, char** argv)
     bool have_switch = false;
     bool posteriors = false;
     bool continuous = false;
+    bool grammar = false;  // --grammar-posteriors
     std::string codebook, csv, frames_dir, transitions, rec_name, body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
@@ -879,6 +883,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
         else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
         else if (a == "--posteriors") posteriors = true;
+        else if (a == "--grammar-posteriors") grammar = true;
         else if (a == "--body") body = val("--body");
         else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
@@ -906,7 +911,11 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
-    if (!frames_dir.empty() && !posteriors) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
+    if (!frames_dir.empty() && !posteriors && !grammar) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
+    if (grammar && (continuous || !body.empty())) {
+        fprintf(stderr, "hmm segment: --grammar-posteriors has the resident body and whole recordings only: not with --continuous or --body\n");
+        return 2;
+    }
     if (!body.empty()) {  // the body of the posteriors (ECOZ2_HMM_POSTERIOR_BODY), set in this process before the call
         if (!posteriors) { fprintf(stderr, "hmm segment: --body <auto|resident|looped> needs --posteriors\n"); return 2; }
         if (body != "auto" && body != "resident" && body != "looped") {
@@ -917,6 +926,10 @@ static int hmm_segment_cmd(int argc, char** argv)
     }
     if (!transitions.empty() && posteriors) {
         fprintf(stderr, "hmm segment: --class-transitions and --posteriors exclude one another (the posteriors know one price only)\n");
+        return 2;
+    }
+    if (grammar && transitions.empty()) {
+        fprintf(stderr, "hmm segment: --grammar-posteriors needs --class-transitions <file.csv> (the posteriors under its prices)\n");
         return 2;
     }
     if (continuous && (posteriors || !transitions.empty())) {
@@ -939,6 +952,9 @@ static int hmm_segment_cmd(int argc, char** argv)
     const char* out = csv.empty() ? nullptr : csv.c_str();
     const int failed = continuous ? e2vq_hmm_segment_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                       ln_switch, rec_name.c_str(), out)
+                       : grammar ? e2vq_hmm_segment_trans_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+                                                                           ln_switch, transitions.c_str(), out,
+                                                                           frames_dir.empty() ? nullptr : frames_dir.c_str())
                        : !transitions.empty() ? e2vq_hmm_segment_trans_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                            ln_switch, transitions.c_str(), out)
                        : posteriors ? e2vq_hmm_segment_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,

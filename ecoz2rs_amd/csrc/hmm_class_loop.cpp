@@ -1,6 +1,7 @@
 // hmm_class_loop.cpp -- the class loop of all models on the GPU: the joint Viterbi through it (`hmm segment`, DESIGN.md
 // 4.8.6, hmm_segment.hip), the class posteriors under it (`--posteriors`, 4.8.7, hmm_posterior.hip) and the same loop under
-// a matrix of class-to-class prices (`--class-transitions`, 4.8.8, hmm_segment_trans.hip), with their reports and their
+// a matrix of class-to-class prices (`--class-transitions`, 4.8.8, hmm_segment_trans.hip) with the posteriors under that
+// matrix (`--grammar-posteriors`, 4.8.13, hmm_posterior_trans.hip), with their reports and their
 // array and file entry points; and what every class-loop decoder shares (hmm_host.h): the shape checks, the packing into
 // wave-slots, the models with their logarithms, the parameter block and the device side of a packing.
 #include "hmm_host.h"
@@ -147,6 +148,7 @@ namespace {
 thread_local float g_segment_kernel_ms = -1.f;        // e2vq_hmm_segment_last_kernel_ms
 thread_local float g_posteriors_kernel_ms = -1.f;     // e2vq_hmm_segment_posteriors_last_kernel_ms
 thread_local float g_segment_trans_kernel_ms = -1.f;  // e2vq_hmm_segment_trans_last_kernel_ms
+thread_local float g_trans_posteriors_kernel_ms = -1.f;  // e2vq_hmm_segment_trans_posteriors_last_kernel_ms
 
 struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered, gbest; per stream: log_prob, status
     uint16_t* cls = nullptr;
@@ -430,6 +432,77 @@ int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, cons
     return timer.elapsed_ms(&g_segment_trans_kernel_ms);
 }
 
+// ---- hmm segment --class-transitions --grammar-posteriors --------------------------------------------------
+int trans_posteriors_check_slots(const char* who, int K, const int* Ns)
+{
+    return check_resident(who, pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld).slots,
+                          "the posteriors under class-to-class prices have");
+}
+
+// posteriors_device under the K x K prices lt (row: the class left).  Already checked: segment_check_shape,
+// trans_posteriors_check_slots, trans_check_lt (and the models' parameters: finite and non-negative).
+int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, const double* lt, hipStream_t st,
+                            const PostOut& out)
+{
+    const int K = lm.K(), M = lm.M;
+    const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);
+    const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
+    // w[f][k] = exp(lt[f][k]) (-inf: 0.0), then its transpose: each walk of the kernel reads consecutive words
+    std::vector<double> w((size_t)2 * K * K);
+    for (int f = 0; f < K; ++f)
+        for (int k = 0; k < K; ++k) w[(size_t)f * K + k] = w[(size_t)K * K + (size_t)k * K + f] = exp(lt[(size_t)f * K + k]);
+    // pi of every class | A of every class, row i at i (N | 1) | B of every class
+    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = *lm.ms[(size_t)k];
+        const int N = h.N, ld = posteriors_a_ld(N), c0 = pk.comp0[(size_t)k];
+        for (int j = 0; j < N; ++j) {
+            params[(size_t)(c0 + j)] = h.pi[(size_t)j];
+            std::copy(h.A.begin() + (size_t)j * N, h.A.begin() + (size_t)(j + 1) * N,
+                      params.begin() + sumN + pk.a_at[(size_t)k] + (size_t)j * ld);
+        }
+        std::copy(h.B.begin(), h.B.end(), params.begin() + sumN + a_words + (size_t)c0 * M);
+    }
+    ClassLoopDev loop;
+    Scores sc;  // P(O) of each stream
+    DeviceBuffer<double> d_post, d_ah, d_c, d_w;
+    DeviceBuffer<i64> d_offs;
+    const i64 frames = h_offs[S];
+    if (loop.upload(pk, params, K, M, st) || d_w.upload(w.data(), w.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) ||
+        sc.reserve((size_t)S) || d_post.reserve((size_t)frames * K))
+        return 1;
+    const e2hmm::SegPlanDev& pl = loop.pl;
+    // launches of whole streams whose ah (8 sumN bytes a frame) and c (8 bytes a frame and wave) stay within the budget (the
+    // class masses live in LDS only: the kernel stores nothing more per frame than 4.8.7's)
+    const i64 row = 8 * ((i64)sumN + slots);
+    i64 max_frames = 0;
+    const auto chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
+    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * slots)) {
+        const std::string why = e2vq_last_error();
+        return e2vq_set_error("hmm segment --grammar-posteriors: no room for the forward table of %lld frames x %d states (%lld bytes; "
+                              "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
+                              (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
+    }
+    KernelTimer timer;
+    if (timer.create()) return 1;
+    HIPCHK(hipEventRecord(timer.start.e, st));
+    // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
+    for (const auto& c : chunks) {
+        const int s0 = c.first, n = c.second - c.first;
+        if (e2hmm::launch_loop_posteriors_trans(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), d_ah.get(), d_c.get(), d_post.get(),
+                                                sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+            return e2vq_set_error("hmm segment --grammar-posteriors: %d wave-slots of %d states cannot be launched", slots, sumN);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(timer.stop.e, st));
+    if (frames > 0 && out.post) HIPCHK(hipMemcpyAsync(out.post, d_post.get(), (size_t)frames * K * 8, hipMemcpyDeviceToHost, st));
+    if (sc.download((size_t)S, st)) return 1;
+    HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
+    if (timer.elapsed_ms(&g_trans_posteriors_kernel_ms)) return 1;
+    for (int s = 0; s < S; ++s) sc.get((size_t)s, nullptr, nullptr, out.status ? out.status + s : nullptr, out.log_prob ? out.log_prob + s : nullptr);
+    return 0;
+}
+
 // CSV and stdout block of one segmented input from the per-frame outputs (host only).  post (T rows of K; may be null: every
 // byte as without it): two more CSV columns and a p= field per segment, and with frames_csv the per-frame table.  lt (K x K;
 // may be null: ln_switch for every pair): the price of the succession that starts a segment (4.8.8; gbest is then exit_score).
@@ -553,6 +626,57 @@ int segment_files(const char* who, const char* const* model_filenames, unsigned 
         return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), gbest.data(), lp,
                               ln_switch, posteriors ? post.data() : nullptr, in.csv.empty() ? nullptr : in.csv.c_str(),
                               fcsv.empty() ? nullptr : fcsv.c_str());
+    };
+    return run_on_files(who, lm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+}
+
+// `hmm segment --class-transitions` with and without --grammar-posteriors: segment_files under the transitions file.  The
+// symbols of an input are staged once; the posteriors run on the same device buffer under the same effective prices.
+int segment_trans_files(const char* who, const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                        const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                        const char* transitions_csv, const char* csv_dir_or_file, bool posteriors, const char* frames_dir)
+{
+    FlushStdout flush_on_return;
+    LoopModels lm;
+    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
+    if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
+    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models)) return 1;
+    const int K = lm.K();
+    if (trans_check_slots(who, K, lm.Ns.data()) || (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data())) ||
+        check_names(who, K, lm.names.data()))
+        return 1;
+    std::vector<double> lt;
+    if (transitions_read(transitions_csv, K, lm.names.data(), lt)) return 1;
+    for (double& v : lt) v = v + ln_switch;  // the effective price
+    if (lm.logs(model_filenames)) return 1;
+    const std::string fdir = posteriors && frames_dir ? frames_dir : "";
+    auto frames_csv = [&](const char* path) { return fdir + "/" + e2vq_io::basename_noext(path) + ".csv"; };
+    for (int f = 0; f < num_inputs && !fdir.empty(); ++f)
+        for (int g = 0; g < f; ++g)
+            if (input_filenames[f] && input_filenames[g] && frames_csv(input_filenames[g]) == frames_csv(input_filenames[f]))
+                return e2vq_set_error("%s and %s would both write %s", input_filenames[g], input_filenames[f], frames_csv(input_filenames[f]).c_str());
+    auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
+        const i64 offs[2] = {0, T};
+        const size_t n = (size_t)std::max<int64_t>(T, 1);
+        std::vector<uint16_t> cls(n);
+        std::vector<uint8_t> entered(n);
+        std::vector<double> exit_score(n), post;
+        double lp = 0.0;
+        int status = 0;
+        SegOut out;
+        out.cls = cls.data(), out.entered = entered.data(), out.gbest = exit_score.data(), out.log_prob = &lp, out.status = &status;
+        if (segment_trans_device(lm, d_sym, offs, 1, lt.data(), st, out)) return 1;
+        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), lm.M);
+        if (posteriors) {  // the same staged symbols, the same effective prices
+            post.resize(n * (size_t)K);
+            PostOut po;
+            po.post = post.data();
+            if (trans_posteriors_device(lm, d_sym, offs, 1, lt.data(), st, po)) return 1;
+        }
+        const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
+        return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), exit_score.data(), lp,
+                              ln_switch, posteriors ? post.data() : nullptr, in.csv.empty() ? nullptr : in.csv.c_str(),
+                              fcsv.empty() ? nullptr : fcsv.c_str(), lt.data());
     };
     return run_on_files(who, lm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
 }
@@ -682,32 +806,40 @@ extern "C" int e2vq_hmm_segment_trans_files(const char* const* model_filenames, 
                                             const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
                                             double ln_switch, const char* transitions_csv, const char* csv_dir_or_file)
 {
-    const char* who = "e2vq_hmm_segment_trans_files";
-    FlushStdout flush_on_return;
+    return segment_trans_files("e2vq_hmm_segment_trans_files", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P,
+                               W_ms, O_ms, ln_switch, transitions_csv, csv_dir_or_file, false, nullptr);
+}
+
+// ---- hmm segment --class-transitions --grammar-posteriors --------------------------------------------------
+extern "C" int e2vq_hmm_segment_trans_posteriors_last_kernel_ms(float* ms)
+{
+    return last_kernel_ms("e2vq_hmm_segment_trans_posteriors_last_kernel_ms", g_trans_posteriors_kernel_ms, ms);
+}
+
+// P(class at frame t | the whole stream) of each of S streams under the class loop of K models and the K x K prices lt
+extern "C" int e2vq_hmm_segment_trans_posteriors(int device, int K, const int* Ns, int M, const double* const* pis,
+                                                 const double* const* As, const double* const* Bs, const void* sym, const int64_t* offs,
+                                                 int S, const double* lt, double* post, double* log_prob, int* status, int sym_on_device)
+{
+    const char* who = "e2vq_hmm_segment_trans_posteriors";
     LoopModels lm;
-    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
-    if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
-    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models)) return 1;
-    const int K = lm.K();
-    if (trans_check_slots(who, K, lm.Ns.data()) || check_names(who, K, lm.names.data())) return 1;
-    std::vector<double> lt;
-    if (transitions_read(transitions_csv, K, lm.names.data(), lt)) return 1;
-    for (double& v : lt) v = v + ln_switch;  // the effective price
-    if (lm.logs(model_filenames)) return 1;
-    auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
-        const i64 offs[2] = {0, T};
-        const size_t n = (size_t)std::max<int64_t>(T, 1);
-        std::vector<uint16_t> cls(n);
-        std::vector<uint8_t> entered(n);
-        std::vector<double> exit_score(n);
-        double lp = 0.0;
-        int status = 0;
-        SegOut out;
-        out.cls = cls.data(), out.entered = entered.data(), out.gbest = exit_score.data(), out.log_prob = &lp, out.status = &status;
-        if (segment_trans_device(lm, d_sym, offs, 1, lt.data(), st, out)) return 1;
-        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), lm.M);
-        return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), exit_score.data(), lp,
-                              ln_switch, nullptr, in.csv.empty() ? nullptr : in.csv.c_str(), nullptr, lt.data());
-    };
-    return run_on_files(who, lm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
+    DevSeqs seqs;
+    if (loop_check_args(who, K, Ns, pis, As, Bs, lt && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
+        trans_check_lt(who, K, lt) || trans_posteriors_check_slots(who, K, Ns) || lm.from_arrays(K, Ns, M, pis, As, Bs))
+        return 1;
+    for (const Hmm& h : lm.models)
+        if (posteriors_check_params(h)) return 1;
+    if (seqs.open(device, sym, offs, S, sym_on_device != 0)) return 1;
+    const PostOut out{post, log_prob, status};
+    return trans_posteriors_device(lm, seqs.sym, (const i64*)offs, S, lt, seqs.st.s, out);
+}
+
+extern "C" int e2vq_hmm_segment_trans_files_posteriors(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                                       const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                                       double ln_switch, const char* transitions_csv, const char* csv_dir_or_file,
+                                                       const char* frames_dir)
+{
+    return segment_trans_files("e2vq_hmm_segment_trans_files_posteriors", model_filenames, num_models, cb_filename, input_filenames,
+                               num_inputs, P, W_ms, O_ms, ln_switch, transitions_csv, csv_dir_or_file, true,
+                               frames_dir && *frames_dir ? frames_dir : nullptr);
 }

@@ -294,4 +294,15 @@ size_t posteriors_looped_lds_bytes(const SegPlanDev& pl, bool a_lds);
 int launch_loop_posteriors_looped(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0, double sw,
                                   double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status, hipStream_t st);
 
+// The same posteriors under a K x K matrix of class-to-class prices (hmm_posterior_trans.hip), on the
+// packing above with at most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | A with the leading dimension N_k | 1 | B.
+// w: 2 K^2 doubles, w[f * K + k] = exp(lt[f][k]) followed by its transpose.  The tables and outputs are
+// launch_loop_posteriors'.  Dynamic LDS: 8 (32 + 2 K + sumN) bytes are mandatory (the partial sums, the class masses of two
+// steps, pi); A, and then both matrices, go behind them while the sum stays within SEG_LDS_BYTES (posteriors_trans_layout:
+// the instantiation).  Returns 1 when the shape cannot be launched.
+void posteriors_trans_layout(const SegPlanDev& pl, bool* a_lds, bool* w_lds);
+int launch_loop_posteriors_trans(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0,
+                                 const double* w, double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status,
+                                 hipStream_t st);
+
 }  // namespace e2hmm

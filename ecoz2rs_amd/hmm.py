@@ -88,6 +88,11 @@ _sig("e2vq_hmm_segment_trans_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c
      C.c_double, C.c_char_p, C.c_char_p)
 _sig("e2vq_hmm_segment_trans_report", C.c_int, C.c_char_p, C.c_int64, C.c_int, c_char_pp, C.c_int, C.c_int, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_char_p)
+_sig("e2vq_hmm_segment_trans_posteriors", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p,
+     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_segment_trans_posteriors_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_segment_trans_files_posteriors", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p)
 _sig("e2vq_hmm_transitions_read", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_void_p)
 _sig("e2vq_hmm_transitions_write", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_void_p)
 _sig("e2vq_hmm_class_transitions", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p)
@@ -719,6 +724,41 @@ def segment_trans_last_kernel_ms():
     return _kernel_ms(lib.e2vq_hmm_segment_trans_last_kernel_ms)
 
 
+def segment_trans_posteriors(models, sym, offs, ln_trans, device=0):
+    """`segment_posteriors` under the K x K prices of `segment_trans`: P(class at frame t | the whole
+    stream) under the loop `segment_trans` decodes; ln_trans[f][k] <= 0 (or -inf) as there; the classes must pack into at
+    most 16 wave-slots (there is no looped body).  sym: a numpy array or a device tensor.  -> the dict of
+    `segment_posteriors`: post (sum T_s, K), per stream log_prob and status"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+    M = ms[0][2].shape[1] if K else 0
+    lt = np.ascontiguousarray(ln_trans, dtype=np.float64)
+    if lt.shape != (K, K):
+        raise ValueError(f"ln_trans has the shape {lt.shape}, not ({K}, {K})")
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    S = len(offs) - 1
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    T = int(offs[-1])
+    post = np.zeros((max(T, 1), max(K, 1)))
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_segment_trans_posteriors(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, lt.ctypes.data,
+                                                post.ctypes.data, lp.ctypes.data, st.ctypes.data, int(on_device)))
+    return dict(post=post[:T], log_prob=lp[:S], status=st[:S])
+
+
+def segment_trans_posteriors_last_kernel_ms():
+    return _kernel_ms(lib.e2vq_hmm_segment_trans_posteriors_last_kernel_ms)
+
+
 def class_transitions(label_sequences, K, alpha=1.0):
     """the K x K prices of `segment_trans` from sequences of class labels in [0, K) (host only): bigrams
     are counted within each sequence; ln((c[f][k] + alpha) / (sum_k' c[f][k'] + alpha K)), -inf for an unseen pair at alpha = 0"""
@@ -756,29 +796,39 @@ def class_transitions_files(model_filenames, input_filenames, out_csv, alpha=1.0
 
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
-                  frame_posteriors=None, class_transitions=None, continuous=None, body=None):
+                  frame_posteriors=None, class_transitions=None, continuous=None, body=None, grammar_posteriors=False):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
-    table for every input; body as `segment_posteriors` takes it.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch.  continuous
+    table for every input; body as `segment_posteriors` takes it.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch;
+    grammar_posteriors (4.8.13): with class_transitions, the posteriors under those prices, reported as posteriors reports
+    them (frame_posteriors is then taken too; there is one body).  continuous
     (4.8.9): the name of the one recording whose consecutive pieces the inputs are -- one block, and with `csv` (a directory
     or a .csv file) one CSV, <csv>/<name>.csv"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     if continuous is not None:
-        if posteriors or class_transitions is not None:
+        if posteriors or class_transitions is not None or grammar_posteriors:
             raise ValueError("continuous excludes posteriors and class_transitions")
         check(lib.e2vq_hmm_segment_continuous_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                                     len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
                                                     str(continuous).encode(), str(csv).encode() if csv else None))
         return
-    if frame_posteriors is not None and not posteriors:
+    if frame_posteriors is not None and not posteriors and not grammar_posteriors:
         raise ValueError("frame_posteriors needs posteriors=True")
     if body is not None and not posteriors:
         raise ValueError("body needs posteriors=True")
+    if grammar_posteriors and class_transitions is None:
+        raise ValueError("grammar_posteriors needs class_transitions")
     if class_transitions is not None:
         if posteriors:
             raise ValueError("class_transitions and posteriors exclude one another")
+        if grammar_posteriors:
+            check(lib.e2vq_hmm_segment_trans_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                              len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                              str(class_transitions).encode(), str(csv).encode() if csv else None,
+                                                              str(frame_posteriors).encode() if frame_posteriors is not None else None))
+            return
         check(lib.e2vq_hmm_segment_trans_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
                                                len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
                                                str(class_transitions).encode(), str(csv).encode() if csv else None))

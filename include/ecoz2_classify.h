@@ -417,6 +417,41 @@ int e2vq_hmm_class_transitions(const int32_t *labels, const int64_t *offs, int S
 int e2vq_hmm_transitions_files(const char *const *model_filenames, unsigned num_models, const char *const *input_filenames,
                                int num_inputs, double alpha, const char *out_csv);
 
+/* ---- smoothed class posteriors under class-to-class prices ---------------------------------------------
+ * `hmm segment --class-transitions <file> --grammar-posteriors`: e2vq_hmm_segment_posteriors with the one price replaced by
+ * the matrix lt of e2vq_hmm_segment_trans -- post[t][k] = P(class k at frame t | the whole stream) under the loop that
+ * e2vq_hmm_segment_trans decodes.  One step from state (f, i) to state (k, j) weighs [f = k] A_f[i][j] + w[f][k] pi_k[j]
+ * with w[f][k] = exp(lt[f][k]) (the C library's exp on the host; -inf gives 0).  Refused before any HIP call: what
+ * e2vq_hmm_segment_posteriors refuses for the models (a negative, NaN or infinite parameter included), what
+ * e2vq_hmm_segment_trans refuses for lt (NaN or > 0), and a packing of more than 16 wave-slots ("the classes take %d
+ * wave-slots of 64 lanes (at most 16: the posteriors under class-to-class prices have no looped body)"; only the resident
+ * layout exists, and ECOZ2_HMM_POSTERIOR_BODY is not read).  The arithmetic is scaled and linear, every operation one IEEE
+ * double operation in a fixed order, no fma (DESIGN.md 4.8.13 states it; tests/hmm_trans_posterior_restatement.py restates
+ * it; the GPU matches it bit for bit).  With CS_k the sum over the states of class k in state order:
+ *   x_0[k][j] = pi_k[j] B_k[j][o_0];  S[f] = CS_f(ah_{t-1});  m[k] = sum_f S[f] w[f][k] (f in class order);
+ *   x_t[k][j] = (sum_i ah_{t-1}[k][i] A_k[i][j] + m[k] pi_k[j]) B_k[j][o_t];  c_t, ah_t and P(O | loop) as in 4.8.7;
+ *   bh_{T-1} = 1;  u = B_k[j][o_{t+1}] bh_{t+1}[k][j] / c_{t+1};  R[k] = sum_j pi_k[j] u[k][j];
+ *   r[f] = sum_k w[f][k] R[k] (k in class order);  bh_t[f][i] = sum_j A_f[i][j] u[f][j] + r[f];
+ *   post[t][k] = sum_j ah_t[k][j] bh_t[k][j].
+ * Outputs, status and the empty stream are e2vq_hmm_segment_posteriors'.  With every price -inf the figures are those of
+ * e2vq_hmm_segment_posteriors at ln_switch = -inf bit for bit; with every price one finite value they agree within rounding
+ * (4.8.7 replaces the sum of S by 1).  ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds the per-launch forward table as in 4.8.7.
+ * One device.  sym_on_device as in e2vq_hmm_segment. */
+int e2vq_hmm_segment_trans_posteriors(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                                      const double *const *Bs, const void *sym, const int64_t *offs, int S, const double *lt,
+                                      double *post, double *log_prob, int *status, int sym_on_device);
+/* HIP-event time of the kernels of this thread's last such call (-1: none yet) */
+int e2vq_hmm_segment_trans_posteriors_last_kernel_ms(float *ms);
+/* e2vq_hmm_segment_trans_files with these posteriors: the symbols of an input are staged once, the segmentation and the
+ * posteriors run on the same device buffer under the same effective prices, and the report gains what
+ * e2vq_hmm_segment_report_posteriors adds (the CSV columns posterior,min_posterior, " p=%.3f", and with frames_dir -- may be
+ * NULL -- the per-frame table <frames_dir>/<input's base name>.csv); the first eight CSV columns are
+ * e2vq_hmm_segment_trans_files' byte for byte. */
+int e2vq_hmm_segment_trans_files_posteriors(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                            const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                            double ln_switch, const char *transitions_csv, const char *csv_dir_or_file,
+                                            const char *frames_dir);
+
 /* ---- the same decode on a stream that arrives piece by piece -------------------------------------------
  * `hmm segment --continuous`: a session decodes ONE symbol stream of unknown length under the contract of e2vq_hmm_segment
  * (K models sharing M, one ln_switch; same recursion, ties, G_t, g_t, psi and ENTER) and gives the bits of e2vq_hmm_segment
