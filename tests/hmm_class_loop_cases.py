@@ -1,8 +1,10 @@
-"""inputs that test_hmm_class_loop_cases_cpu.py and test_gpu_hmm_class_loop_shapes.py share (TEST INFRASTRUCTURE): what the four
-class-loop decoders of DESIGN.md 4.8.6 - 4.8.9 (`hmm segment`, --posteriors, --class-transitions, --continuous) are run at
-beyond the tables of class sets of their own files -- streams with a bad or a dead symbol at the edges of the 64-symbol
-hand-out, class sets near the 4096 states the decoders admit whose models lean so that the path visits many classes, and
-seeded random sets -- and the LDS arithmetic of the four launchers, restated."""
+"""inputs that test_hmm_class_loop_cases_cpu.py, test_gpu_hmm_class_loop_shapes.py and test_gpu_hmm_trans_posteriors_shapes.py
+share (TEST INFRASTRUCTURE): what the five class-loop decoders of DESIGN.md 4.8.6 - 4.8.9 and 4.8.13 (`hmm segment`,
+--posteriors, --class-transitions, --continuous, --grammar-posteriors) are run at beyond the tables of class sets of their
+own files -- streams with a bad or a dead symbol at the edges of the 64-symbol hand-out, class sets near the 4096 states the
+decoders admit whose models lean so that the path visits many classes, the class sets that take --grammar-posteriors to each
+of its four LDS layouts and above 64 KB of dynamic LDS, and seeded random sets -- and the LDS arithmetic of the five
+launchers, restated."""
 import functools
 
 import numpy as np
@@ -10,6 +12,7 @@ import numpy as np
 from . import hmm_align_cases as align_cases
 from . import hmm_segment_restatement as R
 from . import hmm_segment_stream_restatement as RS
+from . import hmm_trans_posterior_restatement as RTP
 from .hmm_align_cases import DEAD, EVENT_EDGES, EVENT_PAIRS_AT, EVENT_T, RANDOM_NS, slots_of  # noqa: F401  (for the tests as well)
 from .hmm_segment_trans_cases import random_model, random_prices
 from .hmm_viterbi_restatement import log_model
@@ -19,7 +22,13 @@ EVENT_M = align_cases.M
 EVENT_KINDS = ("clean", "M", "dead", "dead_M", "M_dead")
 # the class sets the event streams are decoded under: one slot; six one-class slots, resident, whose lA (192 KB) stays in
 # global memory; 17 slots, the first packing that is looped by itself (lA global as well)
-EVENT_NS = {"5_3_4": (5, 3, 4), "64x6": (64,) * 6, "64x17": (64,) * 17}
+EVENT_NS = {"5_3_4": (5, 3, 4), "64x6": (64,) * 6, "64x17": (64,) * 17,
+            # --grammar-posteriors alone: pi, A and both price matrices above 64 KB of LDS; 14 slots of 25 classes, A and
+            # the matrices in global memory, and 130 x 350 rows to zero behind an event
+            "64x3": (64,) * 3, "40_1x24_x14": ((40,) + (1,) * 24) * 14}
+# the event class sets of --grammar-posteriors, one per instantiation of k_hmm_loop_posteriors_trans<A_LDS, W_LDS>:
+# <true, true>, <false, true>, <true, true> above 64 KB, <false, false>
+TRANS_POSTERIORS_EVENT_SETS = ("5_3_4", "64x6", "64x3", "40_1x24_x14")
 EVENT_LN_SWITCH = -0.5
 EVENT_SESSION_B = 100  # frame 99 ends the block, 100 opens the remainder, 129 reaches the kernel only at close
 SESSION_BAD_AT = (0, 63, 64, 99, 100, 129)
@@ -43,7 +52,7 @@ def event_status(kind, decoder):
     """the status of an event stream: any symbol >= M is 2 wherever it stands and a stream no path emits is 1 -- but the
     posteriors stop at the first event in frame order, so (DEAD, M) is 1 there"""
     if kind == "dead_M":
-        return 1 if decoder == "posteriors" else 2
+        return 1 if decoder in ("posteriors", "trans_posteriors") else 2
     return {"clean": 0, "M": 2, "dead": 1, "M_dead": 2}[kind]
 
 
@@ -245,7 +254,7 @@ def first_seed(limit):
 RANDOM_SEED = 4
 
 
-# ---- the LDS arithmetic of the four launchers, restated; test_hmm_class_loop_cases_cpu.py holds it against the sources -----------
+# ---- the LDS arithmetic of the five launchers, restated; test_hmm_class_loop_cases_cpu.py holds it against the sources -----------
 SEG_LDS_BYTES = align_cases.SEG_LDS_BYTES
 SEG_MAX_WAVES = align_cases.SEG_MAX_WAVES
 SEG_MAX_SUM_N = 4096
@@ -270,9 +279,14 @@ def trans_lds_bytes(K, a_words, a_lds, lt_lds):
     return SEG_MAX_WAVES * PAIR_BYTES + 2 * K * 8 + (a_words * 8 if a_lds else 0) + (K * K * 8 if lt_lds else 0)
 
 
+def trans_posteriors_lds_bytes(K, sumN, a_words, a_lds, w_lds):
+    return (2 * SEG_MAX_WAVES + 2 * K + sumN + (a_words if a_lds else 0) + (2 * K * K if w_lds else 0)) * 8
+
+
 def route(decoder, Ns, looped=None):
     """-> dict body ("resident" / "looped"), a_lds, lt_lds (trans alone; else None), lds: what the launcher of `decoder`
-    ("segment", "stream", "posteriors" or "trans") decides for the class set; looped: ECOZ2_HMM_SEGMENT_BODY=looped"""
+    ("segment", "stream", "posteriors", "trans" or "trans_posteriors") decides for the class set; looped:
+    ECOZ2_HMM_SEGMENT_BODY=looped.  "trans_posteriors" adds w_lds: both price matrices of 4.8.13, placed after A"""
     slots, sumN, K = slots_of(Ns), sum(Ns), len(Ns)
     if decoder in ("segment", "stream"):
         if looped is None:
@@ -287,8 +301,56 @@ def route(decoder, Ns, looped=None):
         a_words = sum(N * (N | 1) for N in Ns)  # (the leading dimension is odd there)
         a_lds = posteriors_lds_bytes(a_words, True) <= SEG_LDS_BYTES
         return dict(body="resident", a_lds=a_lds, lt_lds=None, lds=posteriors_lds_bytes(a_words, a_lds))
+    if decoder == "trans_posteriors":
+        a_words = sum(N * (N | 1) for N in Ns)  # (posteriors_a_ld)
+        a_lds = trans_posteriors_lds_bytes(K, sumN, a_words, True, False) <= SEG_LDS_BYTES
+        w_lds = trans_posteriors_lds_bytes(K, sumN, a_words, a_lds, True) <= SEG_LDS_BYTES
+        return dict(body="resident", a_lds=a_lds, lt_lds=None, w_lds=w_lds,
+                    lds=trans_posteriors_lds_bytes(K, sumN, a_words, a_lds, w_lds))
     assert decoder == "trans"
     a_words = sum(N * N for N in Ns)
     a_lds = trans_lds_bytes(K, a_words, True, False) <= SEG_LDS_BYTES
     lt_lds = trans_lds_bytes(K, a_words, a_lds, True) <= SEG_LDS_BYTES
     return dict(body="resident", a_lds=a_lds, lt_lds=lt_lds, lds=trans_lds_bytes(K, a_words, a_lds, lt_lds))
+
+
+# ---- --grammar-posteriors (4.8.13) at every LDS layout ---------------------------------------------------------------------------
+TRANS_POSTERIORS_T = 130
+TRANS_POSTERIORS_PRICE_SEED = 3
+# name: (N of every class, M): leaning models, a dwelling stream of TRANS_POSTERIORS_T frames, forbidding_prices(3, K).
+# Behind each row: the instantiation of k_hmm_loop_posteriors_trans<A_LDS, W_LDS> and the dynamic LDS it is launched with
+# (test_hmm_class_loop_cases_cpu.py asserts both through route()).
+TRANS_POSTERIORS_SHAPES = {
+    "64x3": ([64] * 3, 64),                           # <true, true>, 101,824 B: the opt-in above 64 KB
+    "64x6_1x84": ([64] * 6 + [1] * 84, 64),           # <false, true>, 135,040 B: the opt-in; K = 90 in 8 slots
+    "40_1x24_x6": (([40] + [1] * 24) * 6, 4),         # <true, false>, 85,600 B: the opt-in; K = 150 in 6 slots
+    "64x4_1x768": ([64] * 4 + [1] * 768, 64),         # <true, false>, 160,064 B: 3,776 B under the cap; K = 772 in 16 slots
+    "1x1024": ([1] * 1024, 64),                       # <true, false>, 33,024 B: the most classes admitted, 16 full slots
+    "40_1x24_x14": (([40] + [1] * 24) * 14, 4),       # <false, false>, 13,024 B: K = 350, 25 classes to a slot
+    "64x8_1x512": ([64] * 8 + [1] * 512, 64),         # <false, false>, 16,768 B: eight one-class slots (the readlane chains)
+}
+
+
+def trans_posteriors_shape(name):
+    """-> (models, stream, lt) of a row of TRANS_POSTERIORS_SHAPES"""
+    Ns, M = TRANS_POSTERIORS_SHAPES[name]
+    K = len(Ns)
+    return (leaning_models(MODEL_SEED, Ns, M), run_stream(STREAM_SEED, K, M, TRANS_POSTERIORS_T),
+            forbidding_prices(TRANS_POSTERIORS_PRICE_SEED, K))
+
+
+@functools.lru_cache(maxsize=None)
+def trans_posteriors_reference(name):
+    """hmm_trans_posterior_restatement.posteriors of the row, computed once (read only: the tests share it)"""
+    models, stream, lt = trans_posteriors_shape(name)
+    return RTP.posteriors(models, stream, [0, len(stream)], lt)
+
+
+@functools.lru_cache(maxsize=None)
+def trans_posteriors_event_reference(name):
+    """the restatement of the event batch under event_models(name) and event_prices(K), computed once (read only)"""
+    streams, _kinds = event_batch()
+    models = event_models(name)
+    sym = np.concatenate(streams)
+    offs = np.arange(len(streams) + 1, dtype=np.int64) * EVENT_T
+    return RTP.posteriors(models, sym, offs, event_prices(len(models)))

@@ -1,6 +1,8 @@
-"""the shared inputs of test_gpu_hmm_class_loop_shapes.py (tests/hmm_class_loop_cases.py), CPU side: the restated constants and
-LDS sums against hmm_device.h and the .hip sources; the body and the placement of lA (and lt) that every row of SHAPES reaches
-in each decoder; on the restatements alone, what makes a row worth running -- its path visits many classes in many slots, the
+"""the shared inputs of test_gpu_hmm_class_loop_shapes.py and test_gpu_hmm_trans_posteriors_shapes.py
+(tests/hmm_class_loop_cases.py), CPU side: the restated constants and the LDS sums of the five launchers against hmm_device.h
+and the .hip sources; the body and the placement of lA (and lt) that every row of SHAPES reaches in each decoder; the
+instantiation and the bytes of dynamic LDS that every row, event set and random set of --grammar-posteriors (4.8.13) reaches
+(the restatement at those rows is held against extended precision in test_hmm_trans_posteriors_cpu.py); on the restatements alone, what makes a row worth running -- its path visits many classes in many slots, the
 last one among them, and a session over it decides frames after every block --; the vectorised restatements against their
 literal forms on the event streams, and the status of each; the seeded random sets."""
 import os
@@ -68,6 +70,20 @@ def test_the_restated_lds_sums_are_the_launchers():
     assert "const bool a_lds = stream_lds_bytes(pl, looped, true) <= SEG_LDS_BYTES;" in _source("hmm_segment_stream.hip")
     assert "return posteriors_lds_bytes(pl, true) <= SEG_LDS_BYTES;" in _source("hmm_posterior.hip")
     assert "*looped = slots > e2hmm::SEG_MAX_WAVES || (body && strcmp(body, \"looped\") == 0);" in _source("hmm_class_loop.cpp")
+    # the fifth: --grammar-posteriors counts doubles (partials of two parities, S / R of two steps, pi, A, w and wT); A goes
+    # in first, then both matrices; the packing is the posteriors' (odd leading dimension)
+    src = _source("hmm_posterior_trans.hip")
+    post_trans = body("hmm_posterior_trans.hip", "post_trans_lds_bytes")
+    assert "return ((size_t)2 * SEG_MAX_WAVES + (size_t)2 * pl.K + (size_t)pl.sumN + (a_lds ? (size_t)pl.a_words : 0) +" in post_trans
+    assert "(w_lds ? (size_t)2 * pl.K * pl.K : 0)) * sizeof(double);" in post_trans
+    assert "*a_lds = post_trans_lds_bytes(pl, true, false) <= SEG_LDS_BYTES;" in src
+    assert "*w_lds = post_trans_lds_bytes(pl, *a_lds, true) <= SEG_LDS_BYTES;" in src
+    assert "if (lds > 64 * 1024 &&" in src and "hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEG_LDS_BYTES) != hipSuccess)" in src
+    assert "if (lds > SEG_LDS_BYTES) return 1;" in src
+    device = _source("hmm_class_loop.cpp")
+    at = device.index("int trans_posteriors_device(")
+    assert "const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);" in device[at:at + 600]
+    assert cases.trans_posteriors_lds_bytes(3, 12, 68, True, True) == (32 + 6 + 12 + 68 + 18) * 8
 
 
 # ---- where every row goes --------------------------------------------------------------------------------------------------------
@@ -113,6 +129,74 @@ def test_the_event_models_reach_both_bodies_and_lA_in_both_places():
                    for pi, A, B in models)
     # the posteriors' zero fill of a failed stream, x = threadIdx.x; x < T * K; x += blockDim.x, takes 7 turns there
     assert cases.EVENT_T * len(small) > 6 * 64 * cases.slots_of(small)
+
+
+# ---- --grammar-posteriors: the instantiation and the dynamic LDS of every row --------------------------------------------------
+# name: (K, slots, A in LDS, w and wT in LDS, bytes of dynamic LDS) -- k_hmm_loop_posteriors_trans<A_LDS, W_LDS>
+TRANS_POSTERIORS_ROUTES = {
+    "64x3": (3, 3, True, True, 101824),
+    "64x6_1x84": (90, 8, False, True, 135040),
+    "40_1x24_x6": (150, 6, True, False, 85600),
+    "64x4_1x768": (772, 16, True, False, 160064),
+    "1x1024": (1024, 16, True, False, 33024),
+    "40_1x24_x14": (350, 14, False, False, 13024),
+    "64x8_1x512": (520, 16, False, False, 16768),
+}
+
+
+def test_the_rows_of_the_grammar_posteriors_reach_every_instantiation_and_the_opt_in_of_three():
+    assert list(cases.TRANS_POSTERIORS_SHAPES) == list(TRANS_POSTERIORS_ROUTES) and cases.TRANS_POSTERIORS_T == 130
+    seen, opted = set(), set()
+    for name, (K, slots, a_lds, w_lds, lds) in TRANS_POSTERIORS_ROUTES.items():
+        Ns = cases.TRANS_POSTERIORS_SHAPES[name][0]
+        r = cases.route("trans_posteriors", Ns)
+        assert (len(Ns), cases.slots_of(Ns), r["a_lds"], r["w_lds"], r["lds"]) == (K, slots, a_lds, w_lds, lds), (name, r)
+        assert r["body"] == "resident" and lds <= cases.SEG_LDS_BYTES and sum(Ns) <= cases.SEG_MAX_SUM_N
+        seen.add((a_lds, w_lds))
+        if lds > cases.LDS_OPT_IN:
+            opted.add((a_lds, w_lds))
+    assert seen == {(True, True), (False, True), (True, False), (False, False)}
+    # <false, false> holds the partials, S / R and pi alone: at most (32 + 2 * 1024 + 4096) * 8 bytes, below the opt-in
+    assert opted == {(True, True), (False, True), (True, False)}
+    assert cases.trans_posteriors_lds_bytes(1024, cases.SEG_MAX_SUM_N, 0, False, False) < cases.LDS_OPT_IN
+    assert cases.SEG_LDS_BYTES - TRANS_POSTERIORS_ROUTES["64x4_1x768"][4] == 3776
+    # the one-class slots of "64x8_1x512" read their chains by readlane, next to eight packed slots of 64 classes each
+    assert cases.one_class_slot_next_to_packed(cases.TRANS_POSTERIORS_SHAPES["64x8_1x512"][0])
+    # (the largest launch of the kernel's own GPU file, "21_22_64", stays below the opt-in)
+    assert cases.route("trans_posteriors", [21, 22, 64])["lds"] == 42160
+
+
+def test_the_event_sets_of_the_grammar_posteriors_reach_every_instantiation():
+    want = {"5_3_4": (True, True, False), "64x6": (False, True, False), "64x3": (True, True, True),
+            "40_1x24_x14": (False, False, False)}
+    assert cases.TRANS_POSTERIORS_EVENT_SETS == tuple(want)
+    for name, (a_lds, w_lds, big) in want.items():
+        Ns = [len(m[0]) for m in cases.event_models(name)]
+        assert Ns == list(cases.EVENT_NS[name])
+        r = cases.route("trans_posteriors", Ns)
+        assert (r["a_lds"], r["w_lds"], r["lds"] > cases.LDS_OPT_IN) == (a_lds, w_lds, big), (name, r)
+    assert cases.route("trans_posteriors", cases.EVENT_NS["64x6"])["lds"] == 4000
+    # the zero fill of a failed stream, x = threadIdx.x; x < T * K; x += blockDim.x: 130 x 350 entries by 896 threads
+    Ns = cases.EVENT_NS["40_1x24_x14"]
+    assert (cases.EVENT_T * len(Ns), 64 * cases.slots_of(Ns)) == (45500, 896)
+    assert [cases.event_status(k, "trans_posteriors") for k in cases.EVENT_KINDS] == [0, 2, 1, 1, 2]
+
+
+def test_the_random_sets_take_the_grammar_posteriors_above_64_kb_in_two_instantiations():
+    routes = [cases.route("trans_posteriors", row["Ns"]) for row in cases.random_shapes(cases.RANDOM_SEED, resident_only=True)]
+    assert len(routes) == 12
+    for i in (1, 8, 11):
+        assert routes[i]["a_lds"] and routes[i]["w_lds"] and routes[i]["lds"] > cases.LDS_OPT_IN, (i, routes[i])
+    assert (routes[0]["a_lds"], routes[0]["w_lds"], routes[0]["lds"]) == (True, False, 161120)
+    print([(r["a_lds"], r["w_lds"], r["lds"]) for r in routes])
+
+
+def test_the_neighbour_row_takes_segment_trans_above_64_kb_with_lA_global():
+    r = cases.route("trans", cases.TRANS_POSTERIORS_SHAPES["64x6_1x84"][0])
+    assert (r["a_lds"], r["lt_lds"], r["lds"]) == (False, True, 66496) and r["lds"] > cases.LDS_OPT_IN
+    models, stream, lt = cases.trans_posteriors_shape("64x6_1x84")
+    want = RT.segment_trans(models, stream, [0, len(stream)], lt)
+    assert want["status"].tolist() == [0] and want["entered"].sum() >= 10  # (a path of one segment would read little of lt)
 
 
 # ---- what makes a row worth running ----------------------------------------------------------------------------------------------

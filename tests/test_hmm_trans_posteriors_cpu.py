@@ -1,6 +1,8 @@
 """`hmm segment --class-transitions --grammar-posteriors`, CPU side: the numpy restatement against the
 contract transcribed in plain loops, against an exact Fraction sum over every composite path and against an np.longdouble
-forward-backward over the one composite matrix; the rows of post summing to 1; the two consequences of the contract (all
+forward-backward over the one composite matrix -- at small class sets and at the rows of hmm_class_loop_cases.py that reach every
+LDS layout of the kernel (K up to 1024), where the argmax also has to visit many classes --; the statuses and zero rows of the
+event batch under every event set; the rows of post summing to 1; the two consequences of the contract (all
 prices -inf: 4.8.7's bits at -inf; one finite price: 4.8.7's figures within the tolerance); the argument checks of
 e2vq_hmm_segment_trans_posteriors and of the file form, which run before any HIP call; the CLI's new flag with its refusals;
 the exports and the usage text; the kernel's compiler metadata.  The GPU parity tests are in
@@ -20,6 +22,7 @@ import pytest
 import ecoz2rs_amd as e
 from ecoz2rs_amd import hmm
 
+from . import hmm_class_loop_cases as cases
 from . import hmm_posterior_restatement as R7
 from . import hmm_trans_posterior_restatement as R
 from .hmm_segment_trans_cases import UNIFORM_PRICE, random_model, random_prices, uniform_cases
@@ -258,6 +261,51 @@ def test_rows_sum_to_one(name):
     print(f"{name}: rows sum to 1 within {err:.3e}")
     assert err <= tolerance(T, max(Ns), len(Ns))
     assert r["post"].min() >= 0.0
+
+
+# ---- the rows, event sets and -inf rows that test_gpu_hmm_trans_posteriors_shapes.py runs (hmm_class_loop_cases.py) ---------
+@pytest.mark.parametrize("name", list(cases.TRANS_POSTERIORS_SHAPES))
+def test_the_restatement_at_the_layout_rows_against_extended_precision(name):
+    """K up to 1024 and sum N up to 1024, where the restatement had been compared with nothing above K = 20"""
+    models, stream, lt = cases.trans_posteriors_shape(name)
+    Ns, T, K = cases.TRANS_POSTERIORS_SHAPES[name][0], len(stream), len(models)
+    r = cases.trans_posteriors_reference(name)
+    assert r["status"].tolist() == [0] and r["post"].shape == (T, K) and T == 130
+    want, lnP = _longdouble(models, stream, lt)
+    err = float(np.max(np.abs(r["post"].astype(LD) - want)))
+    tol = tolerance(T, max(Ns), K)
+    dlp = abs(float(r["log_prob"][0]) - float(lnP))
+    visited = len(np.unique(r["post"].argmax(axis=1)))
+    print(f"{name}: worst error {err:.3e}, tolerance {tol:.3e}, share {err / tol:.2e}, |ln P| differs by {dlp:.2e}, "
+          f"the argmax visits {visited} classes")
+    assert err <= tol
+    assert dlp <= tol + 4 * U * abs(float(lnP))
+    assert float(np.max(np.abs(r["post"].sum(axis=1) - 1.0))) <= tol and r["post"].min() >= 0.0
+    if K >= 90:  # a wide row whose posterior sat on a few classes would not show a wrong walk over the others
+        assert visited >= 10
+
+
+@pytest.mark.parametrize("name", cases.TRANS_POSTERIORS_EVENT_SETS)
+def test_the_restatement_on_the_event_batch_under_every_event_set(name):
+    streams, kinds = cases.event_batch()
+    T, S = cases.EVENT_T, len(streams)
+    r = cases.trans_posteriors_event_reference(name)
+    # (the first event in frame order decides: (DEAD, M) is 1, (M, DEAD) is 2)
+    assert r["status"].tolist() == [0] + [2] * 6 + [1] * 6 + [1, 2] * 3 == [cases.event_status(k, "trans_posteriors") for k in kinds]
+    assert np.isfinite(r["log_prob"][0]) and (r["log_prob"][1:] == NINF).all()
+    failed = r["post"][T:]
+    assert failed.shape == ((S - 1) * T, len(cases.EVENT_NS[name])) and not failed.any() and not np.signbit(failed).any()
+    assert float(np.max(np.abs(r["post"][:T].sum(axis=1) - 1.0))) <= tolerance(T, max(cases.EVENT_NS[name]), failed.shape[1])
+
+
+@pytest.mark.parametrize("name", ["64x3", "64x6_1x84"])
+def test_all_prices_minus_infinity_are_the_single_price_bits_above_64_kb(name):
+    models, stream, _lt = cases.trans_posteriors_shape(name)
+    K, T = len(models), len(stream)
+    got = R.posteriors(models, stream, [0, T], np.full((K, K), NINF))
+    want = R7.posteriors(models, stream, [0, T], NINF)
+    assert got["status"].tolist() == want["status"].tolist() == [0]
+    assert np.array_equal(_bits(got["post"]), _bits(want["post"])) and np.array_equal(_bits(got["log_prob"]), _bits(want["log_prob"]))
 
 
 # ---- the two consequences of the contract ---------------------------------------------------------------------------------
