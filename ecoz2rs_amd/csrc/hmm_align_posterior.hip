@@ -14,69 +14,9 @@
 // [2 * T * sumN + t * slots + wave] by each wave's lane 0; the backward pass loads only what the same lane stored, so no
 // visibility between waves is needed.  The outputs are zeroed by the host: a stream of status != 0 writes none of them, and a
 // frame whose path_unit names no unit keeps its 0.0.
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
-
-namespace {
-
-// (small helpers copied from hmm_embed.hip rather than shared: see docs/HISTORY.md on spills)
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once) -- k_hmm_score's
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-// the sum of v over every lane of the workgroup: the same bits in every lane on return (k_hmm_loop_posteriors')
-__device__ __forceinline__ double block_sum(double v, double* slot, int wib, int lane, int nw)
-{
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m);
-    if (lane == 0) slot[wib] = v;
-    __syncthreads();
-    v = slot[0];
-    for (int w = 1; w < nw; ++w) v = v + slot[w];
-    return v;
-}
-
-// the sum of x over the states of the lane's unit, in state order (`single`: the slot holds one unit)
-__device__ __forceinline__ double unit_sum(double x, bool single, int seg, int N, int maxN)
-{
-    double s;
-    if (single) {
-        s = bcast(x, 0);
-        for (int i = 1; i < maxN; ++i) s = s + bcast(x, i);
-    } else {
-        s = lane_read(x, seg);
-        for (int i = 1; i < maxN; ++i) {
-            const int ii = i < N ? i : 0;
-            const double v = lane_read(x, seg + ii);
-            if (i < N) s = s + v;
-        }
-    }
-    return s;
-}
-
-}  // namespace
 
 // grid: the streams of the launch, block: 64 x waves (at least the most slots of a stream).
 // Dynamic LDS: 2 x SEG_MAX_WAVES partials | Vn / R of two consecutive steps, 2 x max_L doubles | A of every class (A_LDS).
@@ -159,28 +99,8 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_align_posteriors(Emb
                 x = (flags & ALIGN_INIT) ? pij * bq : 0.0;
             } else {
                 // the in-unit chain, and on the way the unit's mass Vn = ah_{t-1}[l][0] + ah_{t-1}[l][1] + ..
-                double a, Vn;
-                if (single) {  // the slot holds one unit: wave-uniform reads
-                    Vn = bcast(ah, 0);
-                    a = Vn * Acol[0];
-                    for (int i = 1; i < maxN; ++i) {
-                        const double h = bcast(ah, i);
-                        a = a + h * Acol[i * ld];
-                        Vn = Vn + h;
-                    }
-                } else {  // units of any N side by side: every lane runs to the slot's largest N, and counts to its own
-                    Vn = lane_read(ah, seg);
-                    a = Vn * Acol[0];
-                    for (int i = 1; i < maxN; ++i) {
-                        const int ii = i < N ? i : 0;
-                        const double h = lane_read(ah, seg + ii);
-                        const double v = h * Acol[ii * ld];
-                        if (i < N) {
-                            a = a + v;
-                            Vn = Vn + h;
-                        }
-                    }
-                }
+                const ChainPair cv = chain_col_mass(ah, Acol, ld, N, seg, maxN, single);
+                const double a = cv.acc, Vn = cv.sum;
                 // the mass of step t - 1 lives in Vb[t & 1]: a wave writes that half again at t + 2, past the barriers of t and
                 // t + 1, which every wave reaches only after its reads of step t
                 double* Vp = Vb + (size_t)(t & 1) * pl.max_L;
@@ -251,7 +171,7 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_align_posteriors(Emb
             }
             const int pu = __builtin_amdgcn_readlane(mypu, q);
             const double g = a_cur * bh;
-            const double G = unit_sum(g, single, seg, N, maxN);
+            const double G = chain_sum(g, N, seg, maxN, single);
             if (head) {
                 if (occ) occ[(size_t)t * sd.L + l] = G;
                 if (pu == l) out.post_path[base + t] = G;
@@ -260,7 +180,7 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_align_posteriors(Emb
             if (t > 0) {
                 const double ct = bcast(cq, 0);
                 u = act ? (bq * bh) / ct : 0.0;
-                En = unit_sum(mq * u, single, seg, N, maxN);  // the expected entries through pi
+                En = chain_sum(mq * u, N, seg, maxN, single);  // the expected entries through pi
                 if (!(flags & ALIGN_PRED)) En = 0.0;          // (unit 0 is entered at frame 0 only)
             }
             const double d = (double)(t - rf);
@@ -268,22 +188,11 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_align_posteriors(Emb
             w1 = w1 + d * En;
             w2 = w2 + (d * d) * En;
             if (t == 0) break;
-            const double R = unit_sum(ej * u, single, seg, N, maxN);
+            const double R = chain_sum(ej * u, N, seg, maxN, single);
             double* Rt = Vb + (size_t)(t & 1) * pl.max_L;  // (the halves alternate as in the forward pass)
             if (head) Rt[l] = R;
             // the in-unit chain over a row of A
-            double a;
-            if (single) {
-                a = Arow[0] * bcast(u, 0);
-                for (int i = 1; i < maxN; ++i) a = a + Arow[i] * bcast(u, i);
-            } else {
-                a = Arow[0] * lane_read(u, seg);
-                for (int i = 1; i < maxN; ++i) {
-                    const int ii = i < N ? i : 0;
-                    const double v = Arow[ii] * lane_read(u, seg + ii);
-                    if (i < N) a = a + v;
-                }
-            }
+            const double a = chain_row(u, Arow, N, seg, maxN, single);
             __syncthreads();
             if (flags & EMBED_SUCC) {
                 double r = Rt[l + 1];

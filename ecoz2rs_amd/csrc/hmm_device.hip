@@ -25,30 +25,10 @@
 // read from global memory, and the xi sums of a workgroup live in a global scratch table whose column j only thread j
 // ever touches (no atomics until the final flush).  Same arithmetic, same order, same bits as the wave kernels; built to
 // work, not to be fast.
-#include "hmm_device.h"
+#include "hmm_lane.h"
 #include "vq_fixed.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    // `lane` is wave-uniform: two v_readlane_b32
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once)
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
 
 constexpr int SCORE_WAVES = 4;
 
@@ -121,14 +101,6 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_hmm_score(const ModelDev* 
         exp2[idx] = st == 0 ? E : 0;
         status[idx] = st;
     }
-}
-
-// the value of x in lane `src` (its own for every lane: ds_bpermute_b32, two dwords per double)
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
 }
 
 // Grid scoring (hmm classify --grid): a PACK is up to G = floor(64 / N) models of one N, M and sequence
@@ -244,6 +216,8 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void k_hmm_score_grid(const Score
     }
 }
 
+// (this unit's own pair, by the fix2 route and with every limb added; the embedded E-step's, in hmm_limbs.h, take fix2_mul and
+// skip a zero limb -- the limbs are the same, the instructions are not)
 __device__ __forceinline__ void acc_add(i64* cell, double x)
 {
     int hi, lo;

@@ -24,105 +24,9 @@
 //   gamma -> BN[j][o_t] : global atomics (N x M words per class: spread out)
 //   xi -> AN : a workgroup-wide LDS table over all classes (ds_add_u64), flushed with global atomics at the end; where the
 //              table does not fit, global atomics straight away
-#include "hmm_device.h"
-#include "vq_fixed.h"
+#include "hmm_limbs.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned long long u64;
-typedef unsigned short u16;
-
-namespace {
-
-// (small helpers copied from hmm_posterior.hip / hmm_device.hip rather than shared: see docs/HISTORY.md on spills)
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once) -- k_hmm_score's
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-// the sum of v over every lane of the workgroup: the same bits in every lane on return (k_hmm_loop_posteriors')
-__device__ __forceinline__ double block_sum(double v, double* slot, int wib, int lane, int nw)
-{
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m);
-    if (lane == 0) slot[wib] = v;
-    __syncthreads();
-    v = slot[0];
-    for (int w = 1; w < nw; ++w) v = v + slot[w];
-    return v;
-}
-
-// the sum of x over the states of the lane's unit, in state order (`single`: the slot holds one unit)
-__device__ __forceinline__ double unit_sum(double x, bool single, int seg, int N, int maxN)
-{
-    double s;
-    if (single) {
-        s = bcast(x, 0);
-        for (int i = 1; i < maxN; ++i) s = s + bcast(x, i);
-    } else {
-        s = lane_read(x, seg);
-        for (int i = 1; i < maxN; ++i) {
-            const int ii = i < N ? i : 0;
-            const double v = lane_read(x, seg + ii);
-            if (i < N) s = s + v;
-        }
-    }
-    return s;
-}
-
-// (fix2_mul: fix2's limbs for every input, by full-rate operations -- vq_fixed.h)
-constexpr double ACC_SCALE = (double)(1 << ACC_SHIFT);
-
-__device__ __forceinline__ void acc_local(i64 (&cell)[2], double x)
-{
-    int hi, lo;
-    e2vq::fix2_mul(x, ACC_SCALE, hi, lo);
-    cell[0] += (i64)hi;
-    cell[1] += (i64)lo;
-}
-
-// (a zero limb adds nothing: no atomic for it)
-__device__ __forceinline__ void acc_add(i64* cell, double x)
-{
-    int hi, lo;
-    e2vq::fix2_mul(x, ACC_SCALE, hi, lo);
-    if (hi) atomicAdd((u64*)&cell[0], (u64)(i64)hi);
-    if (lo) atomicAdd((u64*)&cell[1], (u64)(i64)lo);
-}
-
-// one xi into its AN cell: the workgroup's LDS table (ds_add_u64) or the class's block in global memory
-__device__ __forceinline__ void an_add(bool an_lds, i64* lds_cell, i64* g_cell, double x)
-{
-    int hi, lo;
-    e2vq::fix2_mul(x, ACC_SCALE, hi, lo);
-    if (an_lds) {
-        if (hi) atomicAdd((u64*)&lds_cell[0], (u64)(i64)hi);
-        if (lo) atomicAdd((u64*)&lds_cell[1], (u64)(i64)lo);
-    } else {
-        if (hi) atomicAdd((u64*)&g_cell[0], (u64)(i64)hi);
-        if (lo) atomicAdd((u64*)&g_cell[1], (u64)(i64)lo);
-    }
-}
-
-}  // namespace
 
 // grid: the streams of the launch, block: 64 x waves (at least the most slots of a stream).
 // Dynamic LDS: 2 x SEG_MAX_WAVES partials | Vn / R of two consecutive steps, 2 x max_L doubles | A of every class (A_LDS) |
@@ -216,6 +120,8 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_embed_fb(EmbedPlanDe
                 x = (flags & ALIGN_INIT) ? pij * bq : 0.0;
             } else {
                 // the in-unit chain, and on the way the unit's mass Vn = ah_{t-1}[l][0] + ah_{t-1}[l][1] + ..
+                // (hmm_lane.h's chain_col_mass, written out: with the call this kernel's registers were allocated otherwise --
+                // docs/HISTORY.md; a change to that chain is made in both places)
                 double a, Vn;
                 if (single) {  // the slot holds one unit: wave-uniform reads
                     Vn = bcast(ah, 0);
@@ -316,7 +222,7 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_embed_fb(EmbedPlanDe
             const double ct = bcast(cq, 0);
             const double u = act ? (bq * bh) / ct : 0.0;
             if (flags & ALIGN_PRED) acc_local(pic, mq * u);  // the expected entries through pi
-            const double R = unit_sum(ej * u, single, seg, N, maxN);
+            const double R = chain_sum(ej * u, N, seg, maxN, single);
             double* Rt = Vb + (size_t)(t & 1) * pl.max_L;  // (the halves alternate as in the forward pass)
             if (head) Rt[l] = R;
             // the in-unit chain over a row of A, and xi_{t-1}(i, j) = (ah_{t-1}(i) A_ij) u_j for this lane's j

@@ -17,64 +17,17 @@
 // Where the counts go (exact integer limb sums, so the routes are interchangeable bit for bit): gamma -> BN, BD and PI, and
 // m u -> PI by global atomics per frame (a lane serves several states, so no register can hold a state's sum over the
 // stream); xi -> AN as in the resident body (the workgroup's LDS table where it fits, else global atomics).
-#include "hmm_device.h"
-#include "vq_fixed.h"
+#include "hmm_limbs.h"
 
 namespace e2hmm {
 
-typedef long long i64;
-typedef unsigned long long u64;
-typedef unsigned short u16;
-
 namespace {
-
-// (small helpers copied from hmm_embed.hip rather than shared: see docs/HISTORY.md on spills)
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once) -- k_hmm_score's
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-constexpr double ACC_SCALE = (double)(1 << ACC_SHIFT);
-
-// (a zero limb adds nothing: no atomic for it)
-__device__ __forceinline__ void acc_add(i64* cell, double x)
-{
-    int hi, lo;
-    e2vq::fix2_mul(x, ACC_SCALE, hi, lo);
-    if (hi) atomicAdd((u64*)&cell[0], (u64)(i64)hi);
-    if (lo) atomicAdd((u64*)&cell[1], (u64)(i64)lo);
-}
-
-// one xi into its AN cell: the workgroup's LDS table (ds_add_u64) or the class's block in global memory
-__device__ __forceinline__ void an_add(bool an_lds, i64* lds_cell, i64* g_cell, double x)
-{
-    int hi, lo;
-    e2vq::fix2_mul(x, ACC_SCALE, hi, lo);
-    if (an_lds) {
-        if (hi) atomicAdd((u64*)&lds_cell[0], (u64)(i64)hi);
-        if (lo) atomicAdd((u64*)&lds_cell[1], (u64)(i64)lo);
-    } else {
-        if (hi) atomicAdd((u64*)&g_cell[0], (u64)(i64)hi);
-        if (lo) atomicAdd((u64*)&g_cell[1], (u64)(i64)lo);
-    }
-}
 
 // what a wave wrote to LDS is read by other lanes of the same wave: the accesses keep their order
 __device__ __forceinline__ void wave_order()
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-}
-
-// the slot's part of the global sum: a butterfly over its 64 lanes (the same bits in every lane)
-__device__ __forceinline__ double slot_sum(double v)
-{
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m);
-    return v;
 }
 
 }  // namespace

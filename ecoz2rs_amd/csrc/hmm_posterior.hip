@@ -3,62 +3,18 @@
 // frame the whole mass may leave its class and enter any class through that class's pi at the price sw = exp(ln_switch) --
 // by a scaled forward-backward in the linear domain, bit-exact against the restatement.
 //   k_hmm_loop_posteriors   one workgroup per stream, a wave per slot of k_hmm_segment's packing (resident only: at most 16
-//                           slots).  Lane (k, j) is state j of class k.  The in-class sums are chains in state order (the
-//                           values of the other states through ds_bpermute_b32, or v_readlane where the slot holds one
-//                           class); the forward pass reads a column of A, the backward pass a row.  The coupling between
+//                           slots).  Lane (k, j) is state j of class k.  The in-class sums are hmm_lane.h's chains in state
+//                           order (the values of the other states through ds_bpermute_b32, or v_readlane where the slot holds
+//                           one class); the forward pass reads a column of A, the backward pass a row.  The coupling between
 //                           the classes is one sum per step over all states: a butterfly over the wave's 64 lanes, lane 0
 //                           posting to a double-buffered LDS slot, one barrier, every wave adding the partials in slot order.
 // Nothing transcendental runs here: sw and e = sw * pi come from the host.  Every operation is one IEEE double operation in
 // the contract's order (the unit is compiled with -ffp-contract=off).  All terms are >= 0 and idle lanes carry +0.0.
 // Scratch: ah_t to ahs[(frame - a0) * sumN + composite index] by its state's lane, c_t to cs[(frame - a0) * waves + wave] by
 // each wave's lane 0; the backward pass loads only what the same lane stored, so no visibility between waves is needed.
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
-
-namespace {
-
-// (small helpers copied from hmm_segment.hip / hmm_device.hip rather than shared: see docs/HISTORY.md on spills)
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once) -- k_hmm_score's
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-// the sum of v over every lane of the workgroup: the same bits in every lane on return.  slot: the nw partials of this
-// call's parity -- two calls apart a wave writes the same slot again, and between them lies a barrier every wave passes only
-// after its reads (block_argmax's pattern).
-__device__ __forceinline__ double block_sum(double v, double* slot, int wib, int lane, int nw)
-{
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m);
-    if (lane == 0) slot[wib] = v;
-    __syncthreads();
-    v = slot[0];
-    for (int w = 1; w < nw; ++w) v = v + slot[w];
-    return v;
-}
-
-}  // namespace
 
 // grid: the streams of the launch, block: 64 x slots.  Dynamic LDS: 2 x SEG_MAX_WAVES partials | A of every class (A_LDS).
 // pl.params: pi (sumN) | e = sw * pi (sumN) | A (a_words; class k from lanes[].a_at, leading dimension ld = N_k | 1: odd,
@@ -130,18 +86,7 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_loop_posteriors(SegP
             if (t == 0) {
                 x = pij * bq;
             } else {
-                double acc;
-                if (single) {  // the slot holds one class: wave-uniform reads
-                    acc = bcast(ah, 0) * Acol[0];
-                    for (int i = 1; i < maxN; ++i) acc = acc + bcast(ah, i) * Acol[i * ld];
-                } else {  // classes of any N_k side by side: every lane runs to the slot's largest N, and counts to its own
-                    acc = lane_read(ah, seg) * Acol[0];
-                    for (int i = 1; i < maxN; ++i) {
-                        const int ii = i < N ? i : 0;
-                        const double v = lane_read(ah, seg + ii) * Acol[ii * ld];
-                        if (i < N) acc = acc + v;
-                    }
-                }
+                const double acc = chain_col(ah, Acol, ld, N, seg, maxN, single);
                 x = (acc + ej) * bq;
             }
             if (!act) x = 0.0;
@@ -186,36 +131,14 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_loop_posteriors(SegP
             }
             const i64 t = t0 + q;
             const double g = aq * bh;
-            double sum;
-            if (single) {
-                sum = bcast(g, 0);
-                for (int j = 1; j < maxN; ++j) sum = sum + bcast(g, j);
-            } else {
-                sum = lane_read(g, seg);
-                for (int j = 1; j < maxN; ++j) {
-                    const int jj = j < N ? j : 0;
-                    const double v = lane_read(g, seg + jj);
-                    if (j < N) sum = sum + v;
-                }
-            }
+            const double sum = chain_sum(g, N, seg, maxN, single);
             if (act && L.j == 0) prow[(size_t)t * K + L.cls] = sum;
             if (t == 0) break;
             const double ct = bcast(cq, 0);
             const double u = act ? (bq * bh) / ct : 0.0;
             const double R = block_sum(pij * u, parts + (calls++ & 1) * SEG_MAX_WAVES, wib, lane, nw);
             const double r = sw * R;
-            double acc;
-            if (single) {
-                acc = Arow[0] * bcast(u, 0);
-                for (int j = 1; j < maxN; ++j) acc = acc + Arow[j] * bcast(u, j);
-            } else {
-                acc = Arow[0] * lane_read(u, seg);
-                for (int j = 1; j < maxN; ++j) {
-                    const int jj = j < N ? j : 0;
-                    const double v = Arow[jj] * lane_read(u, seg + jj);
-                    if (j < N) acc = acc + v;
-                }
-            }
+            const double acc = chain_row(u, Arow, N, seg, maxN, single);
             bh = act ? acc + r : 0.0;
         }
     }

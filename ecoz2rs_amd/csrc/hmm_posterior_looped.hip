@@ -28,109 +28,9 @@
 //                 stream's post rows and skips the backward pass.
 //   A             in LDS behind the mandatory arrays when it fits (A_LDS), else read in place: two instantiations.
 // One barrier per frame and pass.  Nothing transcendental runs here; the unit is compiled with -ffp-contract=off.
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
-
-namespace {
-
-// (small helpers copied from hmm_posterior.hip rather than shared: see docs/HISTORY.md on spills)
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once) -- k_hmm_score's
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-// the slot's part of GS: a butterfly over its 64 lanes (the same bits in every lane)
-__device__ __forceinline__ double slot_sum(double v)
-{
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m);
-    return v;
-}
-
-// GS once every slot has posted: the partials in slot order from slot 0
-__device__ __forceinline__ double slots_sum(const double* pt, int slots)
-{
-    double v = pt[0];
-    for (int w = 1; w < slots; ++w) v = v + pt[w];
-    return v;
-}
-
-// sum_i v_i * Acol[i * ld] over the states of the lane's class, in state order (the forward chain: a column of A)
-__device__ __forceinline__ double chain_col(double v, const double* Acol, int ld, int N, int seg, int maxN, bool single)
-{
-    double acc;
-    if (single) {  // the slot holds one class: wave-uniform reads
-        acc = bcast(v, 0) * Acol[0];
-        for (int i = 1; i < maxN; ++i) acc = acc + bcast(v, i) * Acol[i * ld];
-    } else {  // classes of any N_k side by side: every lane runs to the slot's largest N, and counts to its own
-        acc = lane_read(v, seg) * Acol[0];
-        for (int i = 1; i < maxN; ++i) {
-            const int ii = i < N ? i : 0;
-            const double w = lane_read(v, seg + ii) * Acol[ii * ld];
-            if (i < N) acc = acc + w;
-        }
-    }
-    return acc;
-}
-
-// sum_j Arow[j] * v_j (the backward chain: a row of A)
-__device__ __forceinline__ double chain_row(double v, const double* Arow, int N, int seg, int maxN, bool single)
-{
-    double acc;
-    if (single) {
-        acc = Arow[0] * bcast(v, 0);
-        for (int j = 1; j < maxN; ++j) acc = acc + Arow[j] * bcast(v, j);
-    } else {
-        acc = Arow[0] * lane_read(v, seg);
-        for (int j = 1; j < maxN; ++j) {
-            const int jj = j < N ? j : 0;
-            const double w = Arow[jj] * lane_read(v, seg + jj);
-            if (j < N) acc = acc + w;
-        }
-    }
-    return acc;
-}
-
-// sum_j v_j (the posterior of the class)
-__device__ __forceinline__ double chain_sum(double v, int N, int seg, int maxN, bool single)
-{
-    double sum;
-    if (single) {
-        sum = bcast(v, 0);
-        for (int j = 1; j < maxN; ++j) sum = sum + bcast(v, j);
-    } else {
-        sum = lane_read(v, seg);
-        for (int j = 1; j < maxN; ++j) {
-            const int jj = j < N ? j : 0;
-            const double w = lane_read(v, seg + jj);
-            if (j < N) sum = sum + w;
-        }
-    }
-    return sum;
-}
-
-}  // namespace
 
 // grid: the streams of the launch, block: 64 x min(slots, 16).  Dynamic LDS: 2 x slots partials | sv, sumN doubles | A of
 // every class (A_LDS).  pl.params as k_hmm_loop_posteriors takes them: pi (sumN) | e = sw * pi (sumN) | A (a_words; class k from

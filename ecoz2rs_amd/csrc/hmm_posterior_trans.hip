@@ -4,7 +4,7 @@
 // hmm_posterior.hip's scaled forward-backward with the one price sw replaced by a K x K matrix -- bit-exact against the
 // restatement.
 //   k_hmm_loop_posteriors_trans  one workgroup per stream, a wave per slot of k_hmm_segment's packing (resident only: at most
-//                                16 slots).  Lane (k, j) is state j of class k.  The in-class chains are hmm_posterior.hip's.
+//                                16 slots).  Lane (k, j) is state j of class k.  The in-class chains are hmm_lane.h's.
 //                                Forward: the chain reads ah_{t-1} of every state of its class anyway, so the class mass
 //                                S[k] rides on it, one add a state; the class's state-0 lane posts S[k] to a double-buffered
 //                                LDS array of 2 x K doubles, one barrier, then every lane of class k walks the K sources along
@@ -16,53 +16,9 @@
 // -ffp-contract=off).  All terms are >= 0 and idle lanes carry +0.0.
 // Scratch, as in hmm_posterior.hip: ah_t to ahs[(frame - a0) * sumN + composite index] by its state's lane, c_t to
 // cs[(frame - a0) * waves + wave] by each wave's lane 0; the backward pass loads only what the same lane stored.
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
-
-namespace {
-
-// (small helpers copied from hmm_posterior.hip rather than shared: see docs/HISTORY.md on spills)
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// P = p * 2^E with p in [0.5, 1): one more factor c (frexp is exact; the product rounds once) -- k_hmm_score's
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-// the sum of v over every lane of the workgroup: the same bits in every lane on return.  slot: the nw partials of this
-// call's parity -- two calls apart a wave writes the same slot again, and between them lie barriers every wave passes only
-// after its reads.
-__device__ __forceinline__ double block_sum(double v, double* slot, int wib, int lane, int nw)
-{
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m);
-    if (lane == 0) slot[wib] = v;
-    __syncthreads();
-    v = slot[0];
-    for (int w = 1; w < nw; ++w) v = v + slot[w];
-    return v;
-}
-
-}  // namespace
 
 // grid: the streams of the launch, block: 64 x slots.  Dynamic LDS: 2 x SEG_MAX_WAVES partials | the class masses of two
 // consecutive steps, 2 x K doubles (S forward, R backward) | pi (sumN) | A of every class (A_LDS) | w and wT (W_LDS).
@@ -145,28 +101,8 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_loop_posteriors_tran
                 x = pij * bq;
             } else {
                 // the in-class chain, and on the way the class's mass S = CS(ah_{t-1})
-                double acc, S;
-                if (single) {  // the slot holds one class: wave-uniform reads
-                    S = bcast(ah, 0);
-                    acc = S * Acol[0];
-                    for (int i = 1; i < maxN; ++i) {
-                        const double ai = bcast(ah, i);
-                        acc = acc + ai * Acol[i * ld];
-                        S = S + ai;
-                    }
-                } else {  // classes of any N_k side by side: every lane runs to the slot's largest N, and counts to its own
-                    S = lane_read(ah, seg);
-                    acc = S * Acol[0];
-                    for (int i = 1; i < maxN; ++i) {
-                        const int ii = i < N ? i : 0;
-                        const double ai = lane_read(ah, seg + ii);
-                        const double v = ai * Acol[ii * ld];
-                        if (i < N) {
-                            acc = acc + v;
-                            S = S + ai;
-                        }
-                    }
-                }
+                const ChainPair cf = chain_col_mass(ah, Acol, ld, N, seg, maxN, single);
+                const double acc = cf.acc, S = cf.sum;
                 // S of step t lives in Xb[t & 1]: a wave writes that half again at t + 2, past the barriers of t + 1
                 double* St = Xb + (size_t)(t & 1) * K;
                 if (head) St[k] = S;
@@ -220,48 +156,14 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void k_hmm_loop_posteriors_tran
             }
             const i64 t = t0 + q;
             const double g = aq * bh;
-            double sum;
-            if (single) {
-                sum = bcast(g, 0);
-                for (int j = 1; j < maxN; ++j) sum = sum + bcast(g, j);
-            } else {
-                sum = lane_read(g, seg);
-                for (int j = 1; j < maxN; ++j) {
-                    const int jj = j < N ? j : 0;
-                    const double v = lane_read(g, seg + jj);
-                    if (j < N) sum = sum + v;
-                }
-            }
+            const double sum = chain_sum(g, N, seg, maxN, single);
             if (head) prow[(size_t)t * K + k] = sum;
             if (t == 0) break;
             const double ct = bcast(cq, 0);
             const double u = act ? (bq * bh) / ct : 0.0;
             // the in-class chain, and on the way what leaves through the class's pi: R = sum_j pi[j] u[j]
-            double acc, R;
-            if (single) {
-                const double u0 = bcast(u, 0);
-                acc = Arow[0] * u0;
-                R = pik[0] * u0;
-                for (int j = 1; j < maxN; ++j) {
-                    const double uj = bcast(u, j);
-                    acc = acc + Arow[j] * uj;
-                    R = R + pik[j] * uj;
-                }
-            } else {
-                const double u0 = lane_read(u, seg);
-                acc = Arow[0] * u0;
-                R = pik[0] * u0;
-                for (int j = 1; j < maxN; ++j) {
-                    const int jj = j < N ? j : 0;
-                    const double uj = lane_read(u, seg + jj);
-                    const double v = Arow[jj] * uj;
-                    const double pv = pik[jj] * uj;
-                    if (j < N) {
-                        acc = acc + v;
-                        R = R + pv;
-                    }
-                }
-            }
+            const ChainPair cr = chain_row_pi(u, Arow, pik, N, seg, maxN, single);
+            const double acc = cr.acc, R = cr.sum;
             // R of this step lives in Xb[steps & 1]: a wave writes that half again two steps on, past the barrier of the
             // step between, which every wave reaches only after its walk of this step
             double* Rt = Xb + (size_t)(steps++ & 1) * K;

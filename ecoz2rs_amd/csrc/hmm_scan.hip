@@ -13,37 +13,9 @@
 // Every lane performs k_hmm_score's operations in k_hmm_score's order: each result is, bit for bit, what e2vq_hmm_score
 // returns for the window's symbols passed as a sequence of their own.  The step body is a copy of k_hmm_score_grid's, not
 // a shared __device__ function: sharing it would move the register allocation of the existing kernels (docs/HISTORY.md).
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-
-namespace {
-
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ void scale_step(double c, double& p, i64& E)
-{
-    int e, e2;
-    const double m = frexp(c, &e);
-    p = frexp(p * m, &e2);
-    E += (i64)e + (i64)e2;
-}
-
-}  // namespace
 
 constexpr int SCAN_WAVES = 4;
 

@@ -1,13 +1,11 @@
-// hmm_segment_common.h -- device helpers the forward kernels of `hmm segment` share (hmm_segment.hip: a closed stream;
-// hmm_segment_stream.hip: one block of an open one) and of `hmm align` (hmm_align.hip) share: the pair a wave posts per step,
-// reads of d from another lane, and the workgroup's (value, index) maximum.  Device code only.  Internal.
+// hmm_segment_common.h -- what the max-sum decoders share on the device (hmm_segment.hip: a closed stream;
+// hmm_segment_stream.hip: one block of an open one; hmm_segment_trans.hip: class-to-class prices; hmm_align.hip: a known class
+// order): the marks of the psi tables, the pair a wave posts per step, and the workgroup's (value, index) maximum.  Reads of d
+// from another lane are hmm_lane.h's.  Device code only.  Internal.
 #pragma once
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
 
 namespace {
 
@@ -18,20 +16,6 @@ struct Pair {  // what a wave posts per step
     double v;
     int idx, pad;
 };
-
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
 
 // greater value, then lower index: a total order on the pairs of distinct indices, so the result does not depend on the tree
 __device__ __forceinline__ bool beats(double v2, int i2, double v, int i) { return v2 > v || (v2 == v && i2 < i); }

@@ -14,70 +14,10 @@
 // The model and lt arrive as logarithms (log 0 = -inf): the device adds and compares, nothing else.  Every term is finite
 // or -inf and lt <= 0, so no NaN can arise.  Tables, rows relative to psi0: psi (u16, ENTER = 0xFFFF) at
 // psi[row * sumN + composite index]; src[row * K + k], xs[row * K + f] (u16) and Es[row * K + f].
-// The small helpers are copies of hmm_segment.hip's (sharing device bodies has cost spills before: docs/HISTORY.md).
-#include "hmm_device.h"
+// The lane helpers, Pair and block_argmax (called once here, after the last step) are hmm_segment_common.h's.
+#include "hmm_segment_common.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
-
-namespace {
-
-constexpr u16 ENTER = 0xFFFF;
-constexpr int NO_INDEX = 0x7fffffff;
-
-struct Pair {  // what a wave posts to the final maximum
-    double v;
-    int idx, pad;
-};
-
-__device__ __forceinline__ double bcast(double x, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double lane_read(double x, int src)
-{
-    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-    return __hiloint2double(hi, lo);
-}
-
-// greater value, then lower index: a total order on the pairs of distinct indices, so the result does not depend on the tree
-__device__ __forceinline__ bool beats(double v2, int i2, double v, int i) { return v2 > v || (v2 == v && i2 < i); }
-
-// the workgroup's maximum of (v, idx): in every lane on return (called once, after the last step)
-__device__ __forceinline__ void block_argmax(double& v, int& idx, Pair* slot, int wib, int lane, int nw)
-{
-    for (int m = 32; m > 0; m >>= 1) {
-        const double v2 = __shfl_xor(v, m);
-        const int i2 = __shfl_xor(idx, m);
-        if (beats(v2, i2, v, idx)) {
-            v = v2;
-            idx = i2;
-        }
-    }
-    if (lane == 0) {
-        slot[wib].v = v;
-        slot[wib].idx = idx;
-    }
-    __syncthreads();
-    v = slot[0].v;
-    idx = slot[0].idx;
-    for (int w = 1; w < nw; ++w) {
-        const double v2 = slot[w].v;
-        const int i2 = slot[w].idx;
-        if (beats(v2, i2, v, idx)) {
-            v = v2;
-            idx = i2;
-        }
-    }
-}
-
-}  // namespace
 
 // grid: the streams of the launch, block: 64 x slots (<= SEG_MAX_WAVES).
 // Dynamic LDS: SEG_MAX_WAVES pairs | E of two consecutive steps, 2 x K doubles | lA of every class (A_LDS) | ltT (LT_LDS).

@@ -8,20 +8,9 @@
 // (best, arg) = (v, i);  d'[j] = best + lB[j][o_t], psi_t[j] = arg.  The strict > gives ties to the lowest index.
 // psi is written as u16 at psi[(offs[s] - psi0 + t) * N + j] by the forward kernels and read back by the backtrack in
 // a launch of its own (the kernel boundary orders the stores before the loads).  PATH = false: no psi, no backtrack.
-#include "hmm_device.h"
+#include "hmm_lane.h"
 
 namespace e2hmm {
-
-typedef long long i64;
-typedef unsigned short u16;
-
-static __device__ __forceinline__ double bcast(double x, int lane)
-{
-    // `lane` is wave-uniform: two v_readlane_b32
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
 
 static constexpr int VIT_WAVES = 4;
 

@@ -41,11 +41,27 @@ def test_the_restated_constants_are_the_sources():
     assert cases.COALESCE_THREADS == int(re.search(r"constexpr\s+int\s+COALESCE_THREADS\s*=\s*(\d+)\s*;", stream).group(1))
     assert "constexpr int COALESCE_PER_THREAD = SEG_MAX_SUM_N / COALESCE_THREADS;" in stream
     assert cases.COALESCE_PER_THREAD == 4
-    # the two Pair structs: a double and two ints, no padding between or behind them
-    for name in ("hmm_segment_common.h", "hmm_segment_trans.hip"):
+    # the one Pair struct (hmm_segment_trans.hip takes it from the header too): a double and two ints, no padding between or behind them
+    for name in ("hmm_segment_common.h",):
         pair = re.search(r"struct\s+Pair\s*\{[^\n]*\n(.*?)\};", _source(name), re.S)
         size = sum({"double": 8, "int": 4}[typ] * len(names.split(",")) for typ, names in re.findall(r"\b(double|int)\s+([^;]+);", pair.group(1)))
         assert cases.PAIR_BYTES == size == 16, name
+    assert '#include "hmm_segment_common.h"' in _source("hmm_segment_trans.hip")
+
+
+def test_no_hmm_unit_defines_the_shared_lane_helpers_again():
+    # hmm_lane.h holds them once (the chains are the bit-exactness contract); a new unit includes the header
+    shared = ("bcast", "lane_read", "scale_step", "block_sum", "slot_sum", "slots_sum", "chain_sum", "unit_sum", "chain_col",
+              "chain_row", "chain_col_mass", "chain_row_pi")
+    define = re.compile(r"__device__[^;{}()]*?\b(?:double|void|ChainPair)\s+(%s)\s*\(" % "|".join(shared))
+    assert sorted(set(define.findall(_source("hmm_lane.h")))) == sorted(set(shared) - {"unit_sum"})
+    units = sorted(n for n in os.listdir(CSRC) if re.fullmatch(r"hmm_\w+\.hip", n))
+    assert len(units) >= 13
+    for name in units:
+        src = _source(name)
+        assert not define.findall(src), (name, define.findall(src))
+        assert not re.search(r"\bstruct\s+Pair\b", src), name
+    assert len(re.findall(r"\bstruct\s+Pair\s*\{", _source("hmm_segment_common.h"))) == 1
 
 
 def test_the_restated_lds_sums_are_the_launchers():
