@@ -87,6 +87,10 @@ static int usage()
             "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
+            "  ecoz2 hmm transitions --em -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15] --switch-penalty <x>\n"
+            "                  [--init <file.csv>] [--alpha 1] [-a val_auto] [-I max_iterations] -o <file.csv>\n"
+            "                  --sequences <.seq>... | --predictors <.prd>... | --signals <.wav>...\n"
+            "                  (the same prices by Baum-Welch from unlabelled recordings under the models; <file.csv>.em.csv: the iterations)\n"
             "  ecoz2 hmm align -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  [--switch-penalty <x <= 0>] [--filler <class>] [-c <csv dir|file.csv>] --labels <files>...\n"
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
@@ -967,9 +971,89 @@ static int hmm_segment_cmd(int argc, char** argv)
     return 0;
 }
 
+// `hmm transitions --em`: the same matrix by Baum-Welch from unlabelled recordings under the trained models
+static int hmm_transitions_em_cmd(int argc, char** argv)
+{
+    int P = 36, W = 45, O = 15, max_iterations = -1;
+    double ln_switch = 0.0, alpha = 1.0, val_auto = 0.3;
+    bool have_switch = false;
+    std::string codebook, init, out;
+    std::vector<std::string> models, signals, predictors, sequences;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        auto num = [&](const char* name) -> long long {
+            const char* v = val(name);
+            char* end = nullptr;
+            const long long x = strtoll(v, &end, 10);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto real = [&](const char* name) -> double {
+            const char* v = val(name);
+            char* end = nullptr;
+            const double x = strtod(v, &end);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto many = [&](std::vector<std::string>& v) { while (i + 1 < argc && !is_flag(argv[i + 1])) v.push_back(argv[++i]); };
+        if (a == "--em") continue;
+        else if (a == "-m" || a == "--models") many(models);
+        else if (a == "--codebook") codebook = val("--codebook");
+        else if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
+        else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
+        else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "--switch-penalty") { ln_switch = real("--switch-penalty"); have_switch = true; }
+        else if (a == "--init") init = val("--init");
+        else if (a == "--alpha") alpha = real("--alpha");
+        else if (a == "-a") val_auto = real("-a");
+        else if (a == "-I") max_iterations = (int)num("-I");
+        else if (a == "-o" || a == "--output") out = val("-o");
+        else if (a == "--signals") many(signals);
+        else if (a == "--predictors") many(predictors);
+        else if (a == "--sequences") many(sequences);
+        else return usage();
+    }
+    if (models.empty()) { fprintf(stderr, "hmm transitions --em: --models <files|dirs>... is required\n"); return usage(); }
+    if ((int)!signals.empty() + (int)!predictors.empty() + (int)!sequences.empty() != 1) {
+        fprintf(stderr, "hmm transitions --em: exactly one of --signals, --predictors and --sequences is required\n");
+        return usage();
+    }
+    if (!have_switch) { fprintf(stderr, "hmm transitions --em: --switch-penalty <x <= 0 | -inf> is required\n"); return 2; }
+    if (!(ln_switch <= 0.0)) { fprintf(stderr, "hmm transitions --em: --switch-penalty %g: at most 0\n", ln_switch); return 2; }
+    if (out.empty()) { fprintf(stderr, "hmm transitions --em: -o <file.csv> is required\n"); return 2; }
+    if (!(alpha >= 0.0)) { fprintf(stderr, "hmm transitions --em: --alpha %g: at least 0\n", alpha); return 2; }
+    if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
+    if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
+    if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm transitions --em: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    std::vector<std::string> hmm_files, inputs;
+    e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    const int rc = !signals.empty() ? e2vq_io::resolve_filenames(signals, ".wav", inputs)
+                   : !predictors.empty() ? e2vq_io::resolve_filenames(predictors, ".prd", inputs)
+                                         : e2vq_io::resolve_filenames(sequences, ".seq", inputs);
+    if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+    if (inputs.empty()) { printf("No inputs given\n"); return 0; }
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
+    auto pm = cptrs(hmm_files), pi = cptrs(inputs);
+    if (e2vq_hmm_learn_transitions_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(),
+                                         (int)pi.size(), P, W, O, ln_switch, init.empty() ? nullptr : init.c_str(), alpha, val_auto,
+                                         max_iterations, out.c_str())) {
+        printf("%s\n", e2vq_last_error());
+        return 1;
+    }
+    return 0;
+}
+
 // `hmm transitions`: the class-to-class prices of `hmm segment --class-transitions` from labelled successions
 static int hmm_transitions_cmd(int argc, char** argv)
 {
+    for (int i = 0; i < argc; ++i)
+        if (strcmp(argv[i], "--em") == 0) return hmm_transitions_em_cmd(argc, argv);
     double alpha = 1.0;
     std::string out;
     std::vector<std::string> models, inputs;
@@ -987,6 +1071,10 @@ static int hmm_transitions_cmd(int argc, char** argv)
             if (!*v || *end) { fprintf(stderr, "--alpha: invalid value '%s'\n", v); exit(2); }
         }
         else if (a == "-o" || a == "--output") out = val("-o");
+        else if (a == "--init" || a == "-a" || a == "-I" || a == "--sequences" || a == "--predictors" || a == "--signals") {
+            fprintf(stderr, "hmm transitions: %s needs --em (the matrix from unlabelled recordings)\n", a.c_str());
+            return 2;
+        }
         else if (is_flag(argv[i])) return usage();
         else inputs.push_back(a);
     }

@@ -143,6 +143,71 @@ int ClassLoopDev::upload(const SegPacking& pk, const std::vector<double>& host_p
     return 0;
 }
 
+// ---- what hmm_trans_train.cpp shares with the passes below (hmm_host.h) ---------------------------------------------------------
+// where only the resident layout exists: a packing of more than SEG_MAX_WAVES slots is refused (host only)
+int check_resident(const char* who, int slots, const char* what_has)
+{
+    if (slots > e2hmm::SEG_MAX_WAVES)
+        return e2vq_set_error("%s: the classes take %d wave-slots of 64 lanes (at most %d: %s no looped body)", who, slots,
+                              e2hmm::SEG_MAX_WAVES, what_has);
+    return 0;
+}
+
+// log_model's refusal, without the logarithms: a negative, NaN or infinite parameter (then no NaN can arise on the device)
+int posteriors_check_params(const Hmm& h)
+{
+    const std::vector<double>* parts[3] = {&h.pi, &h.A, &h.B};
+    const char* names[3] = {"pi", "A", "B"};
+    for (int k = 0; k < 3; ++k)
+        for (size_t i = 0; i < parts[k]->size(); ++i) {
+            const double x = (*parts[k])[i];
+            if (!(x >= 0.0) || !std::isfinite(x))
+                return e2vq_set_error("HMM parameter %s[%zu] = %g: not a finite non-negative number", names[k], i, x);
+        }
+    return 0;
+}
+
+// the leading dimension of a class's A in the sum-product passes
+int posteriors_a_ld(int N) { return N | 1; }  // (odd: see hmm_posterior.hip)
+
+int trans_check_lt(const char* who, int K, const double* lt)
+{
+    for (int f = 0; f < K; ++f)
+        for (int k = 0; k < K; ++k) {
+            const double v = lt[(size_t)f * K + k];
+            if (std::isnan(v) || v > 0.0)
+                return e2vq_set_error("%s: lt[%d][%d] = %g: the logarithm of a price, at most 0 (-inf forbids the succession)", who, f, k, v);
+        }
+    return 0;
+}
+
+// w[f][k] = exp(lt[f][k]) (-inf: 0.0), then its transpose: each walk of the sum-product kernels reads consecutive words
+std::vector<double> trans_prices(int K, const double* lt)
+{
+    std::vector<double> w((size_t)2 * K * K);
+    for (int f = 0; f < K; ++f)
+        for (int k = 0; k < K; ++k) w[(size_t)f * K + k] = w[(size_t)K * K + (size_t)k * K + f] = exp(lt[(size_t)f * K + k]);
+    return w;
+}
+
+// pi of every class | A of every class, row i at i (N | 1) | B of every class (pk: the packing with posteriors_a_ld)
+std::vector<double> trans_params(const LoopModels& lm, const SegPacking& pk)
+{
+    const int K = lm.K(), M = lm.M, sumN = pk.sumN, a_words = pk.a_words;
+    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const Hmm& h = *lm.ms[(size_t)k];
+        const int N = h.N, ld = posteriors_a_ld(N), c0 = pk.comp0[(size_t)k];
+        for (int j = 0; j < N; ++j) {
+            params[(size_t)(c0 + j)] = h.pi[(size_t)j];
+            std::copy(h.A.begin() + (size_t)j * N, h.A.begin() + (size_t)(j + 1) * N,
+                      params.begin() + sumN + pk.a_at[(size_t)k] + (size_t)j * ld);
+        }
+        std::copy(h.B.begin(), h.B.end(), params.begin() + sumN + a_words + (size_t)c0 * M);
+    }
+    return params;
+}
+
 namespace {
 
 thread_local float g_segment_kernel_ms = -1.f;        // e2vq_hmm_segment_last_kernel_ms
@@ -158,15 +223,6 @@ struct SegOut {  // host arrays, any may be null; per frame: cls, state, entered
     double* log_prob = nullptr;
     int* status = nullptr;
 };
-
-// where only the resident layout exists: a packing of more than SEG_MAX_WAVES slots is refused (host only)
-int check_resident(const char* who, int slots, const char* what_has)
-{
-    if (slots > e2hmm::SEG_MAX_WAVES)
-        return e2vq_set_error("%s: the classes take %d wave-slots of 64 lanes (at most %d: %s no looped body)", who, slots,
-                              e2hmm::SEG_MAX_WAVES, what_has);
-    return 0;
-}
 
 // What the two Viterbi decoders of the class loop leave on the device: per frame cls / state / entered / score (gbest, or
 // exit_score under class-to-class prices); per stream logp / status / qlast.
@@ -250,8 +306,6 @@ int segment_device(const LoopModels& lm, const unsigned short* d_sym, const i64*
 }
 
 // ---- hmm segment --posteriors: forward-backward through the same class loop -------------------------------
-int posteriors_a_ld(int N) { return N | 1; }  // (odd: see hmm_posterior.hip)
-
 // the body of the pass (ECOZ2_HMM_POSTERIOR_BODY): resident (at most 16 slots) unless the caller opts into the looped one
 int posteriors_body(int* body) { return opt_in_body("ECOZ2_HMM_POSTERIOR_BODY", body); }
 
@@ -272,20 +326,6 @@ int posteriors_check_slots(const char* who, int K, const int* Ns, int body)
     if (need > e2hmm::SEG_LDS_BYTES)
         return e2vq_set_error("%s: %d wave-slots and %d states take %zu bytes of LDS in the looped body of the posteriors (at most %zu)",
                               who, pk.slots, pk.sumN, need, (size_t)e2hmm::SEG_LDS_BYTES);
-    return 0;
-}
-
-// log_model's refusal, without the logarithms: a negative, NaN or infinite parameter (then no NaN can arise on the device)
-int posteriors_check_params(const Hmm& h)
-{
-    const std::vector<double>* parts[3] = {&h.pi, &h.A, &h.B};
-    const char* names[3] = {"pi", "A", "B"};
-    for (int k = 0; k < 3; ++k)
-        for (size_t i = 0; i < parts[k]->size(); ++i) {
-            const double x = (*parts[k])[i];
-            if (!(x >= 0.0) || !std::isfinite(x))
-                return e2vq_set_error("HMM parameter %s[%zu] = %g: not a finite non-negative number", names[k], i, x);
-        }
     return 0;
 }
 
@@ -361,17 +401,6 @@ int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i
 }
 
 // ---- hmm segment --class-transitions ----------------------------------------------------------------------
-int trans_check_lt(const char* who, int K, const double* lt)
-{
-    for (int f = 0; f < K; ++f)
-        for (int k = 0; k < K; ++k) {
-            const double v = lt[(size_t)f * K + k];
-            if (std::isnan(v) || v > 0.0)
-                return e2vq_set_error("%s: lt[%d][%d] = %g: the logarithm of a price, at most 0 (-inf forbids the succession)", who, f, k, v);
-        }
-    return 0;
-}
-
 int trans_check_slots(const char* who, int K, const int* Ns)
 {
     return check_resident(who, pack_slots(std::vector<int>(Ns, Ns + K)).slots, "the class-transition decoder has");
@@ -446,23 +475,8 @@ int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, c
 {
     const int K = lm.K(), M = lm.M;
     const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);
-    const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
-    // w[f][k] = exp(lt[f][k]) (-inf: 0.0), then its transpose: each walk of the kernel reads consecutive words
-    std::vector<double> w((size_t)2 * K * K);
-    for (int f = 0; f < K; ++f)
-        for (int k = 0; k < K; ++k) w[(size_t)f * K + k] = w[(size_t)K * K + (size_t)k * K + f] = exp(lt[(size_t)f * K + k]);
-    // pi of every class | A of every class, row i at i (N | 1) | B of every class
-    std::vector<double> params((size_t)sumN + (size_t)a_words + (size_t)sumN * M, 0.0);
-    for (int k = 0; k < K; ++k) {
-        const Hmm& h = *lm.ms[(size_t)k];
-        const int N = h.N, ld = posteriors_a_ld(N), c0 = pk.comp0[(size_t)k];
-        for (int j = 0; j < N; ++j) {
-            params[(size_t)(c0 + j)] = h.pi[(size_t)j];
-            std::copy(h.A.begin() + (size_t)j * N, h.A.begin() + (size_t)(j + 1) * N,
-                      params.begin() + sumN + pk.a_at[(size_t)k] + (size_t)j * ld);
-        }
-        std::copy(h.B.begin(), h.B.end(), params.begin() + sumN + a_words + (size_t)c0 * M);
-    }
+    const int sumN = pk.sumN, slots = pk.slots;
+    const std::vector<double> w = trans_prices(K, lt), params = trans_params(lm, pk);
     ClassLoopDev loop;
     Scores sc;  // P(O) of each stream
     DeviceBuffer<double> d_post, d_ah, d_c, d_w;

@@ -305,4 +305,16 @@ int launch_loop_posteriors_trans(const SegPlanDev& pl, const unsigned short* sym
                                  const double* w, double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status,
                                  hipStream_t st);
 
+// The expected class-to-class counts under the same loop and prices (hmm_trans_estep.hip): the E-step of
+// `hmm transitions --em`.  pl, w, the scratch tables and mant / exp2 / status are launch_loop_posteriors_trans'.  acc:
+// 2 K^2 + 2 int64, added to: the limb pair of C[f][k] at 2 (f K + k), then the status-0 streams and the others.  Dynamic LDS:
+// the mandatory terms of 4.8.13; behind them the C table (16 K^2 bytes) when it fits -- or as c_forced says: *c_lds is then
+// the caller's -- then A, then both matrices, while the sum stays within SEG_LDS_BYTES (trans_estep_layout).  Returns 1 when
+// the shape cannot be launched.
+size_t trans_estep_lds_bytes(const SegPlanDev& pl, bool c_lds, bool a_lds, bool w_lds);
+void trans_estep_layout(const SegPlanDev& pl, bool c_forced, bool* c_lds, bool* a_lds, bool* w_lds);
+int launch_trans_estep(const SegPlanDev& pl, bool c_lds, bool a_lds, bool w_lds, const unsigned short* sym, const long long* offs,
+                       int S, long long a0, const double* w, double* ahs, double* cs, long long* acc, double* mant, long long* exp2,
+                       int* status, hipStream_t st);
+
 }  // namespace e2hmm

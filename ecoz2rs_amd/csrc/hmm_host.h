@@ -3,7 +3,8 @@
 // hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices; hmm_transitions.cpp: the file and the estimator
 // of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
 // decoder; hmm_transcript.cpp: what the commands that take a transcript share; hmm_align.cpp: forced alignment; hmm_embed.cpp:
-// embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp: the posteriors of the alignment).
+// embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp: the posteriors of the alignment; hmm_trans_train.cpp:
+// Baum-Welch for the class-to-class prices).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -330,6 +331,18 @@ struct ClassLoopDev {
     i64 bytes = 0;  // of the five buffers
     int upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st);
 };
+
+// What the sum-product passes under class-to-class prices share (hmm_class_loop.cpp: --grammar-posteriors;
+// hmm_trans_train.cpp: transitions --em).  check_resident: where only the resident layout exists, a packing of more than 16
+// slots is refused (`what_has` closes the message).  posteriors_a_ld: the leading dimension N | 1 of a class's A.
+// posteriors_check_params: a negative, NaN or infinite parameter is refused.  trans_check_lt: every price <= 0 or -inf.
+// trans_prices: w = exp(lt) and its transpose.  trans_params: pi | A (N | 1) | B at the places of `pk`.
+int check_resident(const char* who, int slots, const char* what_has);
+int posteriors_a_ld(int N);
+int posteriors_check_params(const Hmm& h);
+int trans_check_lt(const char* who, int K, const double* lt);
+std::vector<double> trans_prices(int K, const double* lt);
+std::vector<double> trans_params(const LoopModels& lm, const SegPacking& pk);
 
 // ---- transcripts (hmm_transcript.cpp): what `hmm align`, `hmm learn --embedded` and `hmm align --posteriors` share --------
 // What the host decides about a call before the device is touched: the packing of every stream's units, the device tables

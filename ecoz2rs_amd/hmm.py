@@ -6,6 +6,7 @@ same C symbols; the array-level functions drive the same HIP kernels without fil
 """
 import contextlib
 import ctypes as C
+import math
 import os
 from types import SimpleNamespace
 
@@ -97,6 +98,15 @@ _sig("e2vq_hmm_transitions_read", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_v
 _sig("e2vq_hmm_transitions_write", C.c_int, C.c_char_p, C.c_int, c_char_pp, C.c_void_p)
 _sig("e2vq_hmm_class_transitions", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p)
 _sig("e2vq_hmm_transitions_files", C.c_int, c_char_pp, C.c_uint, c_char_pp, C.c_int, C.c_double, C.c_char_p)
+_sig("e2vq_hmm_transitions_acc_words", C.c_int64, C.c_int)
+_sig("e2vq_hmm_transitions_estep", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_transitions_estep_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_train_transitions", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), HMM_LEARN_CALLBACK,
+     C.c_int)
+_sig("e2vq_hmm_learn_transitions_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_double, C.c_char_p, C.c_double, C.c_double, C.c_int, C.c_char_p)
 
 _sig("e2vq_hmm_segment_stream_open", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_double,
      C.POINTER(C.c_void_p))
@@ -793,6 +803,82 @@ def class_transitions_files(model_filenames, input_filenames, out_csv, alpha=1.0
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     check(lib.e2vq_hmm_transitions_files(m, len(model_filenames), f, len(input_filenames), float(alpha), str(out_csv).encode()))
+
+
+def _trans_args(models, sym, offs, ln_trans):
+    """the arguments `transitions_estep` and `train_transitions` share -> (the C arguments up to S, a copy of ln_trans (K, K),
+    on_device, S, what must stay alive)"""
+    K = len(models)
+    ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+    Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+    ptrs = [(C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms]) for i in range(3)]
+    M = ms[0][2].shape[1] if K else 0
+    lt = np.array(ln_trans, dtype=np.float64, order="C")
+    if lt.shape != (K, K):
+        raise ValueError(f"ln_trans has the shape {lt.shape}, not ({K}, {K})")
+    offs = np.ascontiguousarray(offs, dtype=np.int64)
+    on_device = hasattr(sym, "data_ptr")
+    if on_device:
+        if not sym.is_contiguous() or sym.element_size() != 2:
+            raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+        sym_ptr = sym.data_ptr()
+    else:
+        sym = np.ascontiguousarray(sym, dtype=np.uint16)
+        sym_ptr = sym.ctypes.data
+    S = len(offs) - 1
+    return (K, Ns, M, *ptrs, sym_ptr, offs.ctypes.data, S), lt, int(on_device), S, (ms, sym, offs)
+
+
+def transitions_acc_words(K):
+    return int(lib.e2vq_hmm_transitions_acc_words(int(K)))
+
+
+def transitions_estep(models, sym, offs, ln_trans, acc=None, device=0):
+    """one E-step of Baum-Welch for the class-to-class prices: models, sym (a numpy array or a device tensor),
+    offs and ln_trans as `segment_trans_posteriors` takes them -> dict acc (int64, 2 K^2 + 2: the limb pairs of the expected
+    counts C[f][k], then the streams used and skipped; added to `acc` where one is given), per stream log_prob and status"""
+    c_args, lt, on_device, S, _keep = _trans_args(models, sym, offs, ln_trans)
+    words = transitions_acc_words(len(models))
+    if acc is None:
+        acc = np.zeros(max(words, 2), dtype=np.int64)
+    elif not (isinstance(acc, np.ndarray) and acc.dtype == np.int64 and acc.flags.c_contiguous and acc.size == words):
+        raise ValueError(f"acc must be a contiguous int64 array of {words} words")
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_transitions_estep(device, *c_args, lt.ctypes.data, acc.ctypes.data, lp.ctypes.data, st.ctypes.data, on_device))
+    return dict(acc=acc, log_prob=lp[:S], status=st[:S])
+
+
+def transitions_estep_last_kernel_ms():
+    return _kernel_ms(lib.e2vq_hmm_transitions_estep_last_kernel_ms)
+
+
+def train_transitions(models, sym, offs, ln_p=None, ln_switch=0.0, alpha=1.0, val_auto=0.3, max_iterations=-1, callback=None, device=0):
+    """Baum-Welch for the class-to-class prices to its stop: ln_p is the matrix as a transitions file holds it
+    (None: every entry log(1 / K)), the effective price of an E-step ln_p + ln_switch -> (the trained ln_p (K, K), the sum of
+    ln P per E-step); callback(var: str, val: float) per E-step"""
+    K = len(models)
+    if ln_p is None:
+        ln_p = np.full((K, K), math.log(1.0 / K)) if K else np.zeros((0, 0))
+    c_args, lt, on_device, _S, _keep = _trans_args(models, sym, offs, ln_p)
+    cap = 1000
+    hist = np.zeros(cap)
+    n = C.c_int(0)
+    cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
+    check(lib.e2vq_hmm_train_transitions(device, *c_args, lt.ctypes.data, float(ln_switch), float(alpha), float(val_auto),
+                                         int(max_iterations), hist.ctypes.data, cap, C.byref(n), cb, on_device))
+    return lt, hist[:n.value].copy()
+
+
+def learn_transitions_files(model_filenames, input_filenames, out_csv, ln_switch, init=None, alpha=1.0, val_auto=0.3, max_iterations=-1,
+                            codebook=None, P=36, W_ms=45, O_ms=15):
+    """`hmm transitions --em`: the transitions file of the models' classes by Baum-Welch from the inputs (.wav,
+    .prd or .seq), from the file `init` or the uniform matrix; writes out_csv and <out_csv>.em.csv"""
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    check(lib.e2vq_hmm_learn_transitions_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                               len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                               str(init).encode() if init else None, float(alpha), float(val_auto), int(max_iterations),
+                                               str(out_csv).encode()))
 
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,

@@ -452,6 +452,57 @@ int e2vq_hmm_segment_trans_files_posteriors(const char *const *model_filenames, 
                                             double ln_switch, const char *transitions_csv, const char *csv_dir_or_file,
                                             const char *frames_dir);
 
+/* ---- Baum-Welch for the class-to-class prices ----------------------------------------------------------
+ * `hmm transitions --em`: the matrix of e2vq_hmm_segment_trans re-estimated from whole unlabelled streams.  The model, the
+ * inputs and the refusals are e2vq_hmm_segment_trans_posteriors': K models sharing M, N_k <= 64, S streams in sym / offs, lt
+ * (row-major K x K, each entry <= 0 or -inf) with w[f][k] = exp(lt[f][k]) taken by the C library on the host.  Only the
+ * resident layout exists: a packing of more than 16 wave-slots is refused before any HIP call ("the classes take %d
+ * wave-slots of 64 lanes (at most 16: the E-step of the class transitions has no looped body)").  Nothing transcendental runs
+ * on the device; every operation is one IEEE double operation in a fixed order, no fma (DESIGN.md 4.8.14 states it;
+ * tests/hmm_transitions_em_restatement.py restates it; the GPU matches it bit for bit).
+ * E-step.  Forward, scaling, status, log_prob and backward are 4.8.13's word for word (S, m, x, c_t, ah, u, R, r, bh, the same
+ * CS and GS): for a given input log_prob and status are the bits of e2vq_hmm_segment_trans_posteriors.  New are the counts.
+ * For every stream of status 0, every t = 1 .. T - 1 and every pair (f, k):
+ *   xi_t[f][k] = S_t[f] * (w[f][k] * R_t[k])
+ * with S_t[f] = CS_f(ah_{t-1}) in the bits the forward pass used, R_t[k] the backward entry sum formed from
+ * u = (B[.][o_t] * bh_t) / c_t, and w[f][k] * R_t[k] the very term the backward walk adds into r[f].  Each xi goes through
+ * fix2(., 29) into the int64 limb pair of cell C[f][k]: acc[2 (f K + k)] and acc[2 (f K + k) + 1]; a zero limb adds nothing.
+ * A stream of status != 0 adds nothing to C.  acc[2 K^2] counts the status-0 streams of the call, acc[2 K^2 + 1] the others.
+ * acc (e2vq_hmm_transitions_acc_words(K) = 2 K^2 + 2 words) is added to and never cleared.  All sums are integers: the split
+ * over workgroups, the order of the streams and the route of an atomic (the workgroup's LDS table, used when its 16 K^2
+ * bytes fit next to the mandatory LDS terms, or global memory; ECOZ2_HMM_TRANS_EM_C=lds|global forces either, and a forced
+ * table that does not fit is refused) change no bit.  ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds the per-launch forward table as
+ * in 4.8.13.  One device.  sym_on_device as in e2vq_hmm_segment. */
+int64_t e2vq_hmm_transitions_acc_words(int K);
+int e2vq_hmm_transitions_estep(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                               const double *const *Bs, const void *sym, const int64_t *offs, int S, const double *lt, int64_t *acc,
+                               double *log_prob, int *status, int sym_on_device);
+/* HIP-event time of the kernels of this thread's last E-step (-1: none yet) */
+int e2vq_hmm_transitions_estep_last_kernel_ms(float *ms);
+/* The training.  ln_p (K x K, in and out) is the matrix as the transitions file holds it; the effective price of an E-step is
+ * ln_p[f][k] + ln_switch (one host addition, exactly how e2vq_hmm_segment_trans_files forms it; ln_switch <= 0 is not
+ * trained).  Per iteration one E-step over all streams (acc from zero), then L = the sum of log_prob over the status-0
+ * streams in stream order (reported through callback("sum_log_prob", L) and sum_log_prob[it] while it < cap).  The loop
+ * stops at max_iterations (< 0: none), at 1000 E-steps, or when it > 0 and L - Lprev <= val_auto; a stopping iteration gets no
+ * M-step.  If no stream has status 0 after the first E-step the call returns 1 and ln_p is as it came.
+ * M-step (host, K^2 values; unfix as everywhere): D[f] = the integer sum of row f of C, both limbs, unfixed once; n_f = the
+ * finite entries of the current row f; a finite entry becomes log((unfix(C[f][k]) + alpha) / (D[f] + alpha n_f)) with the C
+ * library's log; a -inf entry stays -inf whatever alpha (a forbidden succession is the user's statement: smoothing does not
+ * revive it); a row with D[f] + alpha n_f not > 0 keeps every byte.  alpha: finite, >= 0.  *num_esteps: the E-steps run. */
+int e2vq_hmm_train_transitions(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                               const double *const *Bs, const void *sym, const int64_t *offs, int S, double *ln_p, double ln_switch,
+                               double alpha, double val_auto, int max_iterations, double *sum_log_prob, int cap, int *num_esteps,
+                               void (*callback)(char *variable, double value), int sym_on_device);
+/* `hmm transitions --em`: the same from files.  Models, codebook and inputs (.wav / .prd / .seq) are
+ * e2vq_hmm_segment_trans_files'; all streams are gathered in one device buffer, so an E-step is one call.  The start is
+ * init_csv (a transitions file) or, when NULL or empty, every entry log(1.0 / K).  The result is written with
+ * e2vq_hmm_transitions_write to out_csv; next to it <out_csv>.em.csv holds iteration,sum_log_prob,streams_used,streams_skipped
+ * (%.17g).  A stream whose status changes is named on stderr with the iteration. */
+int e2vq_hmm_learn_transitions_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                     const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                     double ln_switch, const char *init_csv, double alpha, double val_auto, int max_iterations,
+                                     const char *out_csv);
+
 /* ---- the same decode on a stream that arrives piece by piece -------------------------------------------
  * `hmm segment --continuous`: a session decodes ONE symbol stream of unknown length under the contract of e2vq_hmm_segment
  * (K models sharing M, one ln_switch; same recursion, ties, G_t, g_t, psi and ENTER) and gives the bits of e2vq_hmm_segment
