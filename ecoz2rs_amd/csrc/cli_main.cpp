@@ -85,6 +85,12 @@ static int usage()
             "                  (--grammar-posteriors, with --class-transitions: the posteriors under those prices, reported as\n"
             "                  --posteriors reports them)\n"
             "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
+            "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
+            "                  --switch-penalty <x <= 0 | -inf> --class-transitions <file.csv> --grammar-continuous <name>\n"
+            "                  [-c <csv dir|file.csv>]\n"
+            "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
+            "                  (--grammar-continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream\n"
+            "                  under the prices of --class-transitions)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
             "  ecoz2 hmm transitions --em -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15] --switch-penalty <x>\n"
@@ -865,7 +871,8 @@ static int hmm_segment_cmd(int argc, char** argv)
     bool posteriors = false;
     bool continuous = false;
     bool grammar = false;  // --grammar-posteriors
-    std::string codebook, csv, frames_dir, transitions, rec_name, body;
+    bool grammar_continuous = false;
+    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -890,6 +897,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "--grammar-posteriors") grammar = true;
         else if (a == "--body") body = val("--body");
         else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
+        else if (a == "--grammar-continuous") { grammar_name = val("--grammar-continuous"); grammar_continuous = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
         else if (a == "--class-transitions") transitions = val("--class-transitions");
         else if (a == "--switch-penalty") {
@@ -915,6 +923,18 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    if (grammar_continuous) {  // (its own refusals first: the ones below speak of the other modes)
+        if (continuous || posteriors || grammar || !frames_dir.empty() || !body.empty()) {
+            fprintf(stderr, "hmm segment: --grammar-continuous decodes one stream under the prices of --class-transitions: not with "
+                            "--continuous, --posteriors, --grammar-posteriors, --frame-posteriors or --body\n");
+            return 2;
+        }
+        if (transitions.empty()) {
+            fprintf(stderr, "hmm segment: --grammar-continuous needs --class-transitions <file.csv> (the stream is decoded under its prices)\n");
+            return 2;
+        }
+        if (grammar_name.empty()) { fprintf(stderr, "hmm segment: --grammar-continuous <name>: the recording needs a name\n"); return 2; }
+    }
     if (!frames_dir.empty() && !posteriors && !grammar) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
     if (grammar && (continuous || !body.empty())) {
         fprintf(stderr, "hmm segment: --grammar-posteriors has the resident body and whole recordings only: not with --continuous or --body\n");
@@ -954,7 +974,10 @@ static int hmm_segment_cmd(int argc, char** argv)
     auto pm = cptrs(hmm_files), pi = cptrs(inputs);
     const char* cb = codebook.empty() ? nullptr : codebook.c_str();
     const char* out = csv.empty() ? nullptr : csv.c_str();
-    const int failed = continuous ? e2vq_hmm_segment_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+    const int failed = grammar_continuous
+                           ? e2vq_hmm_segment_trans_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O, ln_switch,
+                                                                     transitions.c_str(), grammar_name.c_str(), out)
+                       : continuous ? e2vq_hmm_segment_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                       ln_switch, rec_name.c_str(), out)
                        : grammar ? e2vq_hmm_segment_trans_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
                                                                            ln_switch, transitions.c_str(), out,

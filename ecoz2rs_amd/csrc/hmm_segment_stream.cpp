@@ -4,8 +4,11 @@
 // frames out as soon as every surviving path agrees on them; and the file form that feeds consecutive pieces of one recording
 // to one session.  Shape checks, models, packing and its device side are hmm_class_loop.cpp's, the input stage hmm_input.cpp's
 // (hmm_host.h).
+// A session has two modes, and one schedule serves both: under the one switch penalty, or -- `matrix` --
+// under a K x K matrix of class-to-class prices (`--class-transitions --grammar-continuous`, hmm_segment_trans_stream.hip).
+// Only the launches, the ring's allocations and the results of a commit differ.
 #include "hmm_host.h"
-#include "hmm_segment_stream.h"
+#include "hmm_segment_trans_stream.h"
 
 #include <memory>
 
@@ -15,6 +18,7 @@ using e2hmm::SegStreamState;
 struct e2vq_segment_stream {
     int device = 0, K = 0, M = 0, sumN = 0;
     bool looped = false;
+    bool matrix = false;  // class-to-class prices: the ring holds psi, src, x and E, a commit yields exit_score
     double ln_switch = 0.0;
     i64 B = 0;         // frames of a block
     i64 C = 0;         // frames the pending budget holds; the ring has C + B - 1 rows (the last B - 1: the remainder at close)
@@ -25,6 +29,11 @@ struct e2vq_segment_stream {
     DeviceBuffer<int> d_gsel;
     DeviceBuffer<unsigned short> d_psi, d_blk;
     DeviceBuffer<SegStreamState> d_state;
+    // matrix: the prices transposed, the ring's src / x / E, and exit_score of one commit (8 bytes more a pending frame)
+    DeviceBuffer<double> d_ltT, d_Es, d_score;
+    DeviceBuffer<unsigned short> d_src, d_xs;
+    PinnedBuffer<double> h_score;
+    e2hmm::SegTransRingDev tring{};
     // device and pinned host: cls / state / entered of one commit (5 bytes a pending frame); G of the blocks since the last wait
     DeviceBuffer<unsigned short> d_cls, d_st;
     DeviceBuffer<unsigned char> d_entered;
@@ -53,6 +62,7 @@ struct e2vq_segment_stream {
     // final frames not yet taken, [taken, F); G of the pending frames, [F, p)
     std::vector<uint16_t> f_cls, f_st;
     std::vector<uint8_t> f_entered;
+    // (matrix: f_g holds exit_score, which the backtrack writes; pend_g stays empty)
     std::vector<double> f_g, pend_g;
     Stream st;  // (after the buffers: see Stream)
 };
@@ -66,9 +76,11 @@ const char* const ENV_PENDING = "ECOZ2_HMM_SEGMENT_STREAM_PENDING_BYTES";
 
 double* d_half(Session& s, int which) { return s.d_d.get() + (size_t)which * s.sumN; }
 
-// The models (checked by segment_check_shape; all of one M) on the device and an empty session.  Every refusal comes before
-// the first HIP call.
-int stream_open(const char* who, int device, const LoopModels& lm, double ln_switch, Session** out)
+const char* flag_of(const Session& s) { return s.matrix ? "--grammar-continuous" : "--continuous"; }
+
+// The models (checked by segment_check_shape; all of one M) on the device and an empty session.  lt: the K x K prices of a
+// matrix session (checked by trans_check_lt), or null under the one ln_switch.  Every refusal comes before the first HIP call.
+int stream_open(const char* who, int device, const LoopModels& lm, double ln_switch, const double* lt, Session** out)
 {
     const int K = lm.K(), M = lm.M;
     const char* bv = getenv(ENV_BLOCK);
@@ -77,41 +89,56 @@ int stream_open(const char* who, int device, const LoopModels& lm, double ln_swi
     const SegPacking pk = pack_slots(lm.Ns);
     const int sumN = pk.sumN;
     bool looped = false;
-    if (loop_body_looped("ECOZ2_HMM_SEGMENT_BODY", pk.slots, &looped)) return 1;
-    const i64 row = 2 * (i64)sumN + 4, budget = env_bytes(ENV_PENDING, (i64)256 << 20), C = budget / row;
+    if (lt ? check_resident(who, pk.slots, "the class-transition decoder has") : loop_body_looped("ECOZ2_HMM_SEGMENT_BODY", pk.slots, &looped))
+        return 1;
+    const i64 row = 2 * (i64)sumN + (lt ? 12 * (i64)K : 4), budget = env_bytes(ENV_PENDING, (i64)256 << 20), C = budget / row;
     if (C < 2 * B)
-        return e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states (%lld bytes a frame): fewer than two blocks of %lld", who,
-                              ENV_PENDING, (long long)budget, (long long)C, sumN, (long long)row, (long long)B);
+        return lt ? e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states and %d classes (%lld bytes a frame): fewer than "
+                                   "two blocks of %lld", who, ENV_PENDING, (long long)budget, (long long)C, sumN, K, (long long)row, (long long)B)
+                  : e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states (%lld bytes a frame): fewer than two blocks of %lld", who,
+                                   ENV_PENDING, (long long)budget, (long long)C, sumN, (long long)row, (long long)B);
     const std::vector<double> params = loop_log_params(lm, pk);
+    std::vector<double> ltT;  // a lane of class k walks its sources along consecutive words
+    if (lt) {
+        ltT.resize((size_t)K * K);
+        for (int f = 0; f < K; ++f)
+            for (int k = 0; k < K; ++k) ltT[(size_t)k * K + f] = lt[(size_t)f * K + k];
+    }
     // ---- the device from here on --------------------------------------------------------------------------------
     if (require_device(device)) return 1;
     std::unique_ptr<Session> sp(new Session);
     Session& s = *sp;
     s.device = device, s.K = K, s.M = M, s.sumN = sumN, s.ln_switch = ln_switch, s.B = B, s.C = C;
     s.looped = looped;
+    s.matrix = lt != nullptr;
     const i64 rows = C + B - 1;
     if (s.st.create() || s.all.create() || s.commit_t.create()) return 1;
     const hipStream_t st = s.st.s;
-    if (s.loop.upload(pk, params, K, M, st) || s.d_d.reserve((size_t)2 * sumN) || s.d_gstage.reserve((size_t)B) || s.d_blk.reserve((size_t)B) ||
-        s.d_state.reserve(1) || s.h_state.reserve(1))
+    if (s.loop.upload(pk, params, K, M, st) || s.d_d.reserve((size_t)2 * sumN) || s.d_blk.reserve((size_t)B) || s.d_state.reserve(1) ||
+        s.h_state.reserve(1) || (s.matrix ? s.d_ltT.upload(ltT.data(), ltT.size(), st) : s.d_gstage.reserve((size_t)B)))
         return 1;
-    if (s.d_psi.reserve((size_t)rows * sumN) || s.d_gsel.reserve((size_t)rows)) {
+    if (s.d_psi.reserve((size_t)rows * sumN) ||
+        (s.matrix ? s.d_src.reserve((size_t)rows * K) || s.d_xs.reserve((size_t)rows * K) || s.d_Es.reserve((size_t)rows * K)
+                  : s.d_gsel.reserve((size_t)rows))) {
         const std::string why = e2vq_last_error();
         return e2vq_set_error("%s: no room for the ring of %lld pending frames x %d states (%lld bytes; %s bounds it): %s", who,
                               (long long)rows, sumN, (long long)(rows * row), ENV_PENDING, why.c_str());
     }
-    s.dev_bytes = s.loop.bytes + rows * row + (i64)2 * sumN * 8 + B * 10 + (i64)sizeof(SegStreamState);
+    // (besides the ring: the carried d, the block's symbols, and G of a block or the K x K prices)
+    s.dev_bytes = s.loop.bytes + rows * row + (i64)2 * sumN * 8 + (s.matrix ? B * 2 + (i64)K * K * 8 : B * 10) + (i64)sizeof(SegStreamState);
     SegStreamState zero{};
     zero.fstar = -1, zero.bad_frame = -1, zero.prev_a = -1, zero.reached = -1;
     *s.h_state.get() = zero;
     HIPCHK(hipMemcpyAsync(s.d_state.get(), s.h_state.get(), sizeof zero, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));  // (`params` and the packing are locals)
     s.ring = e2hmm::SegRingDev{s.d_psi.get(), s.d_gsel.get(), rows};
+    s.tring = e2hmm::SegTransRingDev{s.d_psi.get(), s.d_src.get(), s.d_xs.get(), s.d_Es.get(), rows};
     *out = sp.release();
     return 0;
 }
 
-// queues the forward pass of n symbols at `blk` (device) as the frames p .. p + n - 1, and the copy of their G
+// queues the forward pass of n symbols at `blk` (device) as the frames p .. p + n - 1, and under the one price the copy of
+// their G
 int queue_block(Session& s, const unsigned short* blk, i64 n)
 {
     const hipStream_t st = s.st.s;
@@ -119,12 +146,16 @@ int queue_block(Session& s, const unsigned short* blk, i64 n)
         HIPCHK(hipEventRecord(s.all.start.e, st));
         s.timing = true;
     }
-    if (e2hmm::launch_segment_stream(s.loop.pl, s.looped, blk, (int)n, s.p, s.ln_switch, d_half(s, s.dcur), d_half(s, s.dcur ^ 1), s.ring,
-                                     s.d_gstage.get(), s.d_state.get(), st))
-        return e2vq_set_error("hmm segment --continuous: %d wave-slots of %d states cannot be launched", s.loop.pl.slots, s.sumN);
+    if (s.matrix ? e2hmm::launch_segment_trans_stream(s.loop.pl, blk, (int)n, s.p, s.d_ltT.get(), d_half(s, s.dcur), d_half(s, s.dcur ^ 1),
+                                                      s.tring, s.d_state.get(), st)
+                 : e2hmm::launch_segment_stream(s.loop.pl, s.looped, blk, (int)n, s.p, s.ln_switch, d_half(s, s.dcur), d_half(s, s.dcur ^ 1),
+                                                s.ring, s.d_gstage.get(), s.d_state.get(), st))
+        return e2vq_set_error("hmm segment %s: %d wave-slots of %d states cannot be launched", flag_of(s), s.loop.pl.slots, s.sumN);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s.h_g.get() + s.g_queued, s.d_gstage.get(), (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    s.g_queued += n;
+    if (!s.matrix) {
+        HIPCHK(hipMemcpyAsync(s.h_g.get() + s.g_queued, s.d_gstage.get(), (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        s.g_queued += n;
+    }
     s.dcur ^= 1;
     s.p += n;
     s.dirty = true;
@@ -144,16 +175,21 @@ int commit(Session& s, bool close)
         size_t cap = 1024;
         while ((i64)cap < pend) cap *= 2;
         if (s.d_cls.reserve(cap) || s.d_st.reserve(cap) || s.d_entered.reserve(cap) || s.h_cls.reserve(cap) || s.h_st.reserve(cap) ||
-            s.h_entered.reserve(cap))
+            s.h_entered.reserve(cap) || (s.matrix && (s.d_score.reserve(cap) || s.h_score.reserve(cap))))
             return 1;
         if (!s.timing) {
             HIPCHK(hipEventRecord(s.all.start.e, st));
             s.timing = true;
         }
         HIPCHK(hipEventRecord(s.commit_t.start.e, st));
-        e2hmm::launch_segment_coalesce(s.loop.pl, d_half(s, s.dcur), s.ring, s.F, s.p - 1, close ? 1 : 0, s.d_state.get(), st);
+        if (s.matrix) e2hmm::launch_segment_trans_coalesce(s.loop.pl, d_half(s, s.dcur), s.tring, s.F, s.p - 1, close ? 1 : 0, s.d_state.get(), st);
+        else e2hmm::launch_segment_coalesce(s.loop.pl, d_half(s, s.dcur), s.ring, s.F, s.p - 1, close ? 1 : 0, s.d_state.get(), st);
         HIPCHK(hipGetLastError());
-        e2hmm::launch_segment_stream_backtrack(s.loop.pl, s.ring, s.F, s.d_state.get(), s.d_cls.get(), s.d_st.get(), s.d_entered.get(), st);
+        if (s.matrix)
+            e2hmm::launch_segment_trans_stream_backtrack(s.loop.pl, s.tring, s.F, s.d_state.get(), s.d_cls.get(), s.d_st.get(),
+                                                         s.d_entered.get(), s.d_score.get(), st);
+        else
+            e2hmm::launch_segment_stream_backtrack(s.loop.pl, s.ring, s.F, s.d_state.get(), s.d_cls.get(), s.d_st.get(), s.d_entered.get(), st);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(s.commit_t.stop.e, st));
     }
@@ -164,6 +200,7 @@ int commit(Session& s, bool close)
             HIPCHK(hipMemcpyAsync(s.h_cls.get(), s.d_cls.get(), (size_t)pend * 2, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(s.h_st.get(), s.d_st.get(), (size_t)pend * 2, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(s.h_entered.get(), s.d_entered.get(), (size_t)pend, hipMemcpyDeviceToHost, st));
+            if (s.matrix) HIPCHK(hipMemcpyAsync(s.h_score.get(), s.d_score.get(), (size_t)pend * 8, hipMemcpyDeviceToHost, st));
         }
     }
     HIPCHK(hipStreamSynchronize(st));
@@ -188,15 +225,19 @@ int commit(Session& s, bool close)
         return 2;
     }
     if (hs.join_bad)
-        return e2vq_set_error("hmm segment --continuous: internal error: the frames decided from %lld on reach state %d at frame %lld, where "
-                              "the previous commit ended in another", (long long)s.F, hs.reached, (long long)(s.F - 1));
+        return e2vq_set_error("hmm segment %s: internal error: the frames decided from %lld on reach state %d at frame %lld, where "
+                              "the previous commit ended in another", flag_of(s), (long long)s.F, hs.reached, (long long)(s.F - 1));
     if (hs.fstar >= s.F) {
         const size_t c = (size_t)(hs.fstar - s.F + 1);
         s.f_cls.insert(s.f_cls.end(), s.h_cls.get(), s.h_cls.get() + c);
         s.f_st.insert(s.f_st.end(), s.h_st.get(), s.h_st.get() + c);
         s.f_entered.insert(s.f_entered.end(), s.h_entered.get(), s.h_entered.get() + c);
-        s.f_g.insert(s.f_g.end(), s.pend_g.begin(), s.pend_g.begin() + (std::ptrdiff_t)c);
-        s.pend_g.erase(s.pend_g.begin(), s.pend_g.begin() + (std::ptrdiff_t)c);
+        if (s.matrix) {
+            s.f_g.insert(s.f_g.end(), s.h_score.get(), s.h_score.get() + c);
+        } else {
+            s.f_g.insert(s.f_g.end(), s.pend_g.begin(), s.pend_g.begin() + (std::ptrdiff_t)c);
+            s.pend_g.erase(s.pend_g.begin(), s.pend_g.begin() + (std::ptrdiff_t)c);
+        }
         s.F += (i64)c;
     }
     if (close) {
@@ -208,6 +249,11 @@ int commit(Session& s, bool close)
 
 int ring_full(const char* who, const Session& s, i64 n)
 {
+    if (s.matrix)
+        return e2vq_set_error("%s: %lld frames are pending and %lld more do not fit the %lld that %s holds (where every price is -inf, or "
+                              "the finite ones do not connect the classes, paths of different classes never meet, and nothing is decided "
+                              "before close); the session can still be closed",
+                              who, (long long)(s.p - s.F), (long long)n, (long long)s.C, ENV_PENDING);
     return e2vq_set_error("%s: %lld frames are pending and %lld more do not fit the %lld that %s holds (with ln_switch = -inf paths of "
                           "different classes never meet, and nothing is decided before close); the session can still be closed",
                           who, (long long)(s.p - s.F), (long long)n, (long long)s.C, ENV_PENDING);
@@ -244,7 +290,7 @@ int stream_feed(const char* who, Session& s, const void* sym, i64 n, bool on_dev
     const unsigned short* src = (const unsigned short*)sym;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const i64 B = s.B, nblk = (s.r + n) / B;
-    if (s.h_g.reserve((size_t)(nblk * B))) return 1;  // (empty: every feed ends with a wait)
+    if (!s.matrix && s.h_g.reserve((size_t)(nblk * B))) return 1;  // (empty: every feed ends with a wait)
     i64 o = 0;  // symbols of the feed taken
     int rc = 0;
     while (s.r + (n - o) >= B) {
@@ -281,7 +327,7 @@ int stream_flush(const char* who, Session& s)
     int rc = make_room(who, s, s.r);
     if (rc == 1) return 1;
     if (rc == 0) {
-        if (s.h_g.reserve((size_t)s.r)) return 1;
+        if (!s.matrix && s.h_g.reserve((size_t)s.r)) return 1;
         if (queue_block(s, s.d_blk.get(), s.r)) return 1;
         s.r = 0;
         rc = commit(s, false);
@@ -293,7 +339,7 @@ int stream_close(Session& s)
 {
     if (s.status != 2) {
         if (s.r > 0) {  // (the ring's last B - 1 rows are kept for this)
-            if (s.h_g.reserve((size_t)s.r)) return 1;
+            if (!s.matrix && s.h_g.reserve((size_t)s.r)) return 1;
             if (queue_block(s, s.d_blk.get(), s.r)) return 1;
             s.r = 0;
         }
@@ -305,6 +351,7 @@ int stream_close(Session& s)
         s.f_st.insert(s.f_st.end(), c, (uint16_t)0xFFFF);
         s.f_entered.insert(s.f_entered.end(), c, (uint8_t)0);
         s.f_g.insert(s.f_g.end(), c, -INFINITY);
+        if (s.matrix && s.F == 0 && c > 0) s.f_g[s.f_g.size() - c] = 0.0;  // (exit_score of the absolute frame 0, as the closed decode fills it)
         s.pend_g.clear();
         s.F = s.fed;
         s.log_prob = -INFINITY;
@@ -323,7 +370,20 @@ extern "C" int e2vq_hmm_segment_stream_open(int device, int K, const int* Ns, in
     if (loop_check_args(who, K, Ns, pis, As, Bs, out != nullptr) || segment_check_shape(who, K, Ns) || segment_check_switch(who, ln_switch) ||
         lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs())
         return 1;
-    return stream_open(who, device, lm, ln_switch, out);
+    return stream_open(who, device, lm, ln_switch, nullptr, out);
+}
+
+// the same session under a K x K matrix of class-to-class prices; feed, flush, close, take, kernel_ms,
+// stats and free above serve it
+extern "C" int e2vq_hmm_segment_trans_stream_open(int device, int K, const int* Ns, int M, const double* const* pis, const double* const* As,
+                                                  const double* const* Bs, const double* lt, e2vq_segment_stream** out)
+{
+    const char* who = "e2vq_hmm_segment_trans_stream_open";
+    LoopModels lm;
+    if (loop_check_args(who, K, Ns, pis, As, Bs, lt != nullptr && out != nullptr) || segment_check_shape(who, K, Ns) ||
+        trans_check_lt(who, K, lt) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs())
+        return 1;
+    return stream_open(who, device, lm, 0.0, lt, out);
 }
 
 extern "C" int e2vq_hmm_segment_stream_feed(e2vq_segment_stream* s, const void* sym, int64_t n, int sym_on_device, int64_t* final_frames)
@@ -391,7 +451,7 @@ extern "C" int e2vq_hmm_segment_stream_stats(e2vq_segment_stream* s, int64_t* pe
 {
     if (!s) return e2vq_set_error("e2vq_hmm_segment_stream_stats: NULL session");
     if (peak_pending) *peak_pending = s->peak_pending;
-    if (device_bytes) *device_bytes = s->dev_bytes + std::max<i64>(s->peak_pending, 1024) * 5;
+    if (device_bytes) *device_bytes = s->dev_bytes + std::max<i64>(s->peak_pending, 1024) * (s->matrix ? 13 : 5);
     if (commit_ms) *commit_ms = s->commit_ms;
     return 0;
 }
@@ -403,30 +463,20 @@ extern "C" void e2vq_hmm_segment_stream_free(e2vq_segment_stream* s)
     delete s;
 }
 
-// `hmm segment --continuous`: the inputs are consecutive pieces of one recording.  Each piece is turned into symbols on its own
-// (a .wav is analysed by itself: no LPC window straddles two files) and fed to one session; the report is that of the whole run.
-extern "C" int e2vq_hmm_segment_continuous_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
-                                                 const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
-                                                 double ln_switch, const char* name, const char* csv_dir_or_file)
+namespace {
+
+// The file forms: the inputs are consecutive pieces of one recording.  Each piece is turned into symbols on its own (a .wav is
+// analysed by itself: no LPC window straddles two files) and fed to one session, which is then closed.  lt: as stream_open.
+struct Holder {
+    Session* s = nullptr;
+    ~Holder() { e2vq_hmm_segment_stream_free(s); }
+};
+
+int decode_pieces(const char* who, const LoopModels& fm, const SymInputs& si, int P, int W_ms, int O_ms, double ln_switch, const double* lt,
+                  const char* name, Holder& hold)
 {
-    const char* who = "e2vq_hmm_segment_continuous_files";
-    FlushStdout flush_on_return;
-    LoopModels fm;
-    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
-    if (!name || !*name) return e2vq_set_error("%s: the recording needs a name", who);
-    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models) ||
-        fm.logs(model_filenames))
-        return 1;
-    SymInputs si;
-    if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
-    std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
-    if (!csv.empty() && !(csv.size() >= 4 && csv.compare(csv.size() - 4, 4, ".csv") == 0)) csv += std::string("/") + name + ".csv";
-    struct Holder {
-        Session* s = nullptr;
-        ~Holder() { e2vq_hmm_segment_stream_free(s); }
-    } hold;
     const int device = env_device();
-    if (stream_open(who, device, fm, ln_switch, &hold.s)) return 1;  // (makes the device current)
+    if (stream_open(who, device, fm, ln_switch, lt, &hold.s)) return 1;  // (makes the device current)
     Session& s = *hold.s;
     SymStage stg;
     if (stg.open(device, si)) return 1;
@@ -441,6 +491,67 @@ extern "C" int e2vq_hmm_segment_continuous_files(const char* const* model_filena
     }
     if (stream_close(s)) return 1;
     if (s.status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d (frame %lld)", name, fm.M, (long long)s.bad_frame);
+    return 0;
+}
+
+std::string csv_of(const char* csv_dir_or_file, const char* name)
+{
+    std::string csv = csv_dir_or_file ? csv_dir_or_file : "";
+    if (!csv.empty() && !(csv.size() >= 4 && csv.compare(csv.size() - 4, 4, ".csv") == 0)) csv += std::string("/") + name + ".csv";
+    return csv;
+}
+
+}  // namespace
+
+// `hmm segment --continuous`: the report is that of the whole run.
+extern "C" int e2vq_hmm_segment_continuous_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                                 const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                                 double ln_switch, const char* name, const char* csv_dir_or_file)
+{
+    const char* who = "e2vq_hmm_segment_continuous_files";
+    FlushStdout flush_on_return;
+    LoopModels fm;
+    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
+    if (!name || !*name) return e2vq_set_error("%s: the recording needs a name", who);
+    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models) ||
+        fm.logs(model_filenames))
+        return 1;
+    SymInputs si;
+    if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
+    const std::string csv = csv_of(csv_dir_or_file, name);
+    Holder hold;
+    if (decode_pieces(who, fm, si, P, W_ms, O_ms, ln_switch, nullptr, name, hold)) return 1;
+    const Session& s = *hold.s;
     return e2vq_hmm_segment_report(name, s.F, (int)num_models, fm.names.data(), W_ms, O_ms, s.f_cls.data(), s.f_entered.data(), s.f_g.data(),
                                    s.log_prob, ln_switch, csv.empty() ? nullptr : csv.c_str());
+}
+
+// `hmm segment --class-transitions --grammar-continuous`: the same under the transitions file, read and permuted as
+// e2vq_hmm_segment_trans_files reads it; the effective price is the file's plus ln_switch.
+extern "C" int e2vq_hmm_segment_trans_continuous_files(const char* const* model_filenames, unsigned num_models, const char* cb_filename,
+                                                       const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                                       double ln_switch, const char* transitions_csv, const char* name,
+                                                       const char* csv_dir_or_file)
+{
+    const char* who = "e2vq_hmm_segment_trans_continuous_files";
+    FlushStdout flush_on_return;
+    LoopModels fm;
+    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
+    if (!name || !*name) return e2vq_set_error("%s: the recording needs a name", who);
+    if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
+    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models)) return 1;
+    const int K = fm.K();
+    if (check_resident(who, pack_slots(fm.Ns).slots, "the class-transition decoder has") || check_names(who, K, fm.names.data())) return 1;
+    std::vector<double> lt;
+    if (transitions_read(transitions_csv, K, fm.names.data(), lt)) return 1;
+    for (double& v : lt) v = v + ln_switch;  // the effective price
+    if (fm.logs(model_filenames)) return 1;
+    SymInputs si;
+    if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
+    const std::string csv = csv_of(csv_dir_or_file, name);
+    Holder hold;
+    if (decode_pieces(who, fm, si, P, W_ms, O_ms, ln_switch, lt.data(), name, hold)) return 1;
+    const Session& s = *hold.s;
+    return e2vq_hmm_segment_trans_report(name, s.F, K, fm.names.data(), W_ms, O_ms, s.f_cls.data(), s.f_entered.data(), s.f_g.data(),
+                                         s.log_prob, ln_switch, lt.data(), csv.empty() ? nullptr : csv.c_str());
 }

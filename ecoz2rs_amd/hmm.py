@@ -120,6 +120,10 @@ _sig("e2vq_hmm_segment_stream_stats", C.c_int, C.c_void_p, C.POINTER(C.c_int64),
 _sig("e2vq_hmm_segment_stream_free", None, C.c_void_p)
 _sig("e2vq_hmm_segment_continuous_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_double, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_segment_trans_stream_open", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p,
+     C.POINTER(C.c_void_p))
+_sig("e2vq_hmm_segment_trans_continuous_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p)
 _sig("e2vq_hmm_align", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p, C.c_int,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_int)
@@ -734,6 +738,64 @@ def segment_trans_last_kernel_ms():
     return _kernel_ms(lib.e2vq_hmm_segment_trans_last_kernel_ms)
 
 
+class SegmentTransStream(SegmentStream):
+    """`segment_trans` on one stream that arrives piece by piece: `SegmentStream` under the K x K prices
+    ln_trans of `segment_trans` (the classes must pack into at most 16 wave-slots).  feed / flush / close / take return the
+    dict of `SegmentStream` with exit_score in the place of gbest; segments follow `segments_of_trans` with absolute frames
+    (the class of the last final frame is kept across calls: the segment that starts at b paid
+    ln_trans[cls[b - 1]][cls[b]])."""
+
+    def __init__(self, models, ln_trans, device=0):
+        K = len(models)
+        ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+        Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+        ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+        M = ms[0][2].shape[1] if K else 0
+        lt = np.ascontiguousarray(ln_trans, dtype=np.float64)
+        self._h = C.c_void_p()
+        if lt.shape != (K, K):
+            raise ValueError(f"ln_trans has the shape {lt.shape}, not ({K}, {K})")
+        self.ln_trans = lt
+        self.final_frames_ = 0
+        self.log_prob = None
+        self.status = None
+        self._open = None  # the segment that is not complete yet: (begin, cls, lo)
+        self._last_cls = None  # the class of the last frame handed out
+        check(lib.e2vq_hmm_segment_trans_stream_open(device, K, Ns, M, ptr(0), ptr(1), ptr(2), lt.ctypes.data, C.byref(self._h)))
+
+    def _take(self, end_log_prob=None):
+        n = max(self.final_frames_, 1)
+        cls, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
+        entered, ex = np.zeros(n, dtype=np.uint8), np.zeros(n)
+        first, count = C.c_int64(), C.c_int64()
+        check(lib.e2vq_hmm_segment_stream_take(self._h, n, cls.ctypes.data, state.ctypes.data, entered.ctypes.data, ex.ctypes.data,
+                                               C.byref(first), C.byref(count)))
+        c, f0 = count.value, first.value
+        out = dict(first=f0, cls=cls[:c], state=state[:c], entered=entered[:c], exit_score=ex[:c], segments=[])
+
+        def complete(end, hi):
+            b, k, lo = self._open
+            with np.errstate(invalid="ignore"):
+                out["segments"].append(dict(begin=b, end=end, cls=k, log_prob=float(np.float64(hi) - np.float64(lo))))
+
+        for i in np.flatnonzero(out["entered"]):
+            t = f0 + int(i)
+            if self._open is not None:
+                complete(t, float(ex[i]))
+            lo = np.float64(0.0)
+            if t > 0:
+                before = int(cls[i - 1]) if i > 0 else self._last_cls
+                with np.errstate(invalid="ignore"):
+                    lo = np.float64(ex[i]) + self.ln_trans[before, int(cls[i])]
+            self._open = (t, int(cls[i]), lo)
+        if c > 0:
+            self._last_cls = int(cls[c - 1])
+        if end_log_prob is not None and self._open is not None:
+            complete(f0 + c, end_log_prob)
+            self._open = None
+        return out
+
+
 def segment_trans_posteriors(models, sym, offs, ln_trans, device=0):
     """`segment_posteriors` under the K x K prices of `segment_trans`: P(class at frame t | the whole
     stream) under the loop `segment_trans` decodes; ln_trans[f][k] <= 0 (or -inf) as there; the classes must pack into at
@@ -882,7 +944,8 @@ def learn_transitions_files(model_filenames, input_filenames, out_csv, ln_switch
 
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
-                  frame_posteriors=None, class_transitions=None, continuous=None, body=None, grammar_posteriors=False):
+                  frame_posteriors=None, class_transitions=None, continuous=None, body=None, grammar_posteriors=False,
+                  grammar_continuous=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
@@ -890,9 +953,20 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
     grammar_posteriors (4.8.13): with class_transitions, the posteriors under those prices, reported as posteriors reports
     them (frame_posteriors is then taken too; there is one body).  continuous
     (4.8.9): the name of the one recording whose consecutive pieces the inputs are -- one block, and with `csv` (a directory
-    or a .csv file) one CSV, <csv>/<name>.csv"""
+    or a .csv file) one CSV, <csv>/<name>.csv.  grammar_continuous (4.8.15): with class_transitions, the same under the
+    file's prices; it excludes continuous, the posteriors, frame_posteriors and body"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
+    if grammar_continuous is not None:
+        if continuous is not None or posteriors or grammar_posteriors or frame_posteriors is not None or body is not None:
+            raise ValueError("grammar_continuous excludes continuous, posteriors, grammar_posteriors, frame_posteriors and body")
+        if class_transitions is None:
+            raise ValueError("grammar_continuous needs class_transitions")
+        check(lib.e2vq_hmm_segment_trans_continuous_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                          len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                          str(class_transitions).encode(), str(grammar_continuous).encode(),
+                                                          str(csv).encode() if csv else None))
+        return
     if continuous is not None:
         if posteriors or class_transitions is not None or grammar_posteriors:
             raise ValueError("continuous excludes posteriors and class_transitions")

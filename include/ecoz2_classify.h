@@ -557,6 +557,38 @@ int e2vq_hmm_segment_continuous_files(const char *const *model_filenames, unsign
                                       const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
                                       double ln_switch, const char *name, const char *csv_dir_or_file);
 
+/* ---- the streaming decode under class-to-class prices ----------------------------------------------------
+ * `hmm segment --class-transitions --grammar-continuous`: a session of the kind above under the contract of
+ * e2vq_hmm_segment_trans (K models sharing M, the K x K prices lt; same recursion, ties, E_t, x_t, base_t, src_t, psi, ENTER
+ * and exit_score), which gives the bits of e2vq_hmm_segment_trans on the concatenation of everything fed, whatever the
+ * feeds' lengths and the block length.  e2vq_hmm_segment_trans_stream_open returns the session type above; feed, flush,
+ * close, take, kernel_ms, stats and free serve it unchanged, and take's gbest array receives exit_score (exit_score[t] =
+ * E_t of the class of frame t - 1; 0.0 at the absolute frame 0).  Blocks, carry, buffering, flush and close are those of the
+ * one-price session.
+ * Finality: the same rule with the matrix's back step -- state (k, j) at frame t goes to (k, psi), or on ENTER to
+ * (src_t[k], x_t[src_t[k]]).  The join with the previous commit is checked as above.  close takes the lowest composite index
+ * reaching max d.
+ * Status.  As above, with exit_score in the place of gbest: after a symbol >= M every frame that was not final is delivered
+ * as cls = state = 0xFFFF, entered 0, exit_score -inf (0.0 at the absolute frame 0, as e2vq_hmm_segment_trans fills it).
+ * The equality is claimed for a stream whose status there is 0; for a stream that died (status 1) it is not, for the reason
+ * given above.
+ * Memory.  A pending frame keeps psi (2 sum N bytes), src and x (2 K each) and E (8 K): 2 sum N + 12 K bytes, bounded by
+ * ECOZ2_HMM_SEGMENT_STREAM_PENDING_BYTES as above (a budget below two blocks is refused at open, with the row size in the
+ * message; B - 1 rows more are kept for the remainder at close).  Where every price is -inf, or the finite ones do not
+ * connect the classes, nothing becomes final before close, and the ring-full message says so.  The results of a commit take
+ * 13 bytes a pending frame.  Nothing grows with the stream.
+ * Refused before any HIP call: what e2vq_hmm_segment_trans refuses (a NaN or positive price; a packing of more than 16
+ * wave-slots, the message names their number: the layout is resident only), a bad block length, a budget below two blocks. */
+int e2vq_hmm_segment_trans_stream_open(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                                       const double *const *Bs, const double *lt, e2vq_segment_stream **out);
+/* The file form of e2vq_hmm_segment_continuous_files under a transitions file: inputs and stages as there; the file is read
+ * and permuted as e2vq_hmm_segment_trans_files reads it, the effective price is the file's plus ln_switch, and the report
+ * goes through e2vq_hmm_segment_trans_report under `name`. */
+int e2vq_hmm_segment_trans_continuous_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                            const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                            double ln_switch, const char *transitions_csv, const char *name,
+                                            const char *csv_dir_or_file);
+
 /* ---- forced alignment to a known order of units ----------------------------------------------------------
  * `hmm align`: where are the boundaries of units whose classes and order are known?  K models sharing M (the checks of
  * e2vq_hmm_segment), S symbol streams (sym, offs), and for stream s a transcript of L_s >= 1 units: units[unit_offs[s] ..
