@@ -59,6 +59,12 @@ static int usage()
             "                  (--signals <.wav files>... | --predictors <.prd files>... | --sequences <.seq files>...)\n"
             "                  (the given models re-estimated from whole recordings and the order of their units, no boundaries:\n"
             "                  label file i is recording i's transcript, as `hmm align` reads it; the models go to <dir>/<class>.hmm)\n"
+            "  ecoz2 hmm learn --loop -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15] --switch-penalty <x <= 0 | -inf>\n"
+            "                  [--class-transitions <file.csv>] [--train-transitions [--alpha 1]] [--freeze <class>]... [-e 1e-05] [-a 0.3]\n"
+            "                  [-I -1] -o <dir> --sequences <.seq>... | --predictors <.prd>... | --signals <.wav>...\n"
+            "                  (the given models re-estimated from whole unlabelled recordings under the class loop `hmm segment\n"
+            "                  --class-transitions` decodes, with --train-transitions the matrix too; --freeze: that class's model stays;\n"
+            "                  the models go to <dir>/<class>.hmm, the matrix to <dir>/transitions.csv, the history to <dir>/loop.csv)\n"
             "  ecoz2 hmm classify [-r] [-c|--c12n <out.csv>] -m|--models <files|dirs>... --tt <TRAIN|TEST> -M <M> [--class-name c]\n"
             "                  (-s|--sequences <files|dirs|tt.csv>... | --predictors <files|dirs|tt.csv>... --codebooks <files|dirs>...\n"
             "                   [--predictors-dir-template <t>])\n"
@@ -1283,10 +1289,108 @@ static int hmm_learn_embedded_cmd(int argc, char** argv)
     return 0;
 }
 
+// `hmm learn --loop`: the class models re-estimated from whole unlabelled recordings under the class loop
+static int hmm_learn_loop_cmd(int argc, char** argv)
+{
+    int P = 36, W = 45, O = 15, max_iterations = -1;
+    double ln_switch = 0.0, alpha = 1.0, epsilon = 1e-05, val_auto = 0.3;
+    bool have_switch = false, have_alpha = false, train_transitions = false;
+    std::string codebook, transitions, out;
+    std::vector<std::string> models, frozen, signals, predictors, sequences;
+    for (int i = 0; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto val = [&](const char* name) -> const char* {
+            if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", name); exit(2); }
+            return argv[++i];
+        };
+        auto num = [&](const char* name) -> long long {
+            const char* v = val(name);
+            char* end = nullptr;
+            const long long x = strtoll(v, &end, 10);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto real = [&](const char* name) -> double {
+            const char* v = val(name);
+            char* end = nullptr;
+            const double x = strtod(v, &end);
+            if (!*v || *end) { fprintf(stderr, "%s: invalid value '%s'\n", name, v); exit(2); }
+            return x;
+        };
+        auto many = [&](std::vector<std::string>& v) { while (i + 1 < argc && !is_flag(argv[i + 1])) v.push_back(argv[++i]); };
+        if (a == "--loop") continue;
+        else if (a == "--embedded" || a == "--labels" || a == "--filler" || a == "--all-classes" || a == "--grid" || a == "--class-name") {
+            fprintf(stderr, "hmm learn --loop excludes %s (it re-estimates the models given with --models from unlabelled recordings)\n", a.c_str());
+            return usage();
+        }
+        else if (a == "-m" || a == "--models") many(models);
+        else if (a == "--codebook") codebook = val("--codebook");
+        else if (a == "-P" || a == "--prediction-order") P = (int)num("-P");
+        else if (a == "-W" || a == "--window-length-ms") W = (int)num("-W");
+        else if (a == "-O" || a == "--offset-length-ms") O = (int)num("-O");
+        else if (a == "-I" || a == "--max-iterations") max_iterations = (int)num("-I");
+        else if (a == "-e") epsilon = real("-e");
+        else if (a == "-a") val_auto = real("-a");
+        else if (a == "--switch-penalty") { ln_switch = real("--switch-penalty"); have_switch = true; }
+        else if (a == "--class-transitions") transitions = val("--class-transitions");
+        else if (a == "--train-transitions") train_transitions = true;
+        else if (a == "--alpha") { alpha = real("--alpha"); have_alpha = true; }
+        else if (a == "--freeze") frozen.push_back(val("--freeze"));
+        else if (a == "-o" || a == "--out") out = val("-o");
+        else if (a == "--signals") many(signals);
+        else if (a == "--predictors") many(predictors);
+        else if (a == "-s" || a == "--sequences") many(sequences);
+        else return usage();
+    }
+    if (models.empty()) { fprintf(stderr, "hmm learn --loop: --models <files|dirs>... is required\n"); return usage(); }
+    if ((int)!signals.empty() + (int)!predictors.empty() + (int)!sequences.empty() != 1) {
+        fprintf(stderr, "hmm learn --loop: exactly one of --signals, --predictors and --sequences is required\n");
+        return usage();
+    }
+    if (!have_switch) { fprintf(stderr, "hmm learn --loop: --switch-penalty <x <= 0 | -inf> is required\n"); return 2; }
+    if (!(ln_switch <= 0.0)) { fprintf(stderr, "hmm learn --loop: --switch-penalty %g: at most 0\n", ln_switch); return 2; }
+    if (out.empty()) { fprintf(stderr, "hmm learn --loop: -o <dir> is required\n"); return 2; }
+    if (have_alpha && !train_transitions) { fprintf(stderr, "hmm learn --loop: --alpha needs --train-transitions\n"); return 2; }
+    if (!(alpha >= 0.0)) { fprintf(stderr, "hmm learn --loop: --alpha %g: at least 0\n", alpha); return 2; }
+    if (!(epsilon >= 0.0)) { fprintf(stderr, "hmm learn --loop: -e %g: at least 0\n", epsilon); return 2; }
+    if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
+    if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
+    if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm learn --loop: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    std::vector<std::string> hmm_files, inputs;
+    e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
+    if (hmm_files.empty()) { printf("No models given\n"); return 0; }
+    const int rc = !signals.empty() ? e2vq_io::resolve_filenames(signals, ".wav", inputs)
+                   : !predictors.empty() ? e2vq_io::resolve_filenames(predictors, ".prd", inputs)
+                                         : e2vq_io::resolve_filenames(sequences, ".seq", inputs);
+    if (rc) { printf("%s\n", e2vq_last_error()); return 0; }
+    if (inputs.empty()) { printf("No inputs given\n"); return 0; }
+    printf("ECOZ2 C version: %s\n", ecoz2_version());
+    printf("number of HMM models: %zu  number of inputs: %zu\n", hmm_files.size(), inputs.size());
+    printf("val_auto = %g\n", val_auto);
+    auto pm = cptrs(hmm_files), pi = cptrs(inputs), pf = cptrs(frozen);
+    if (e2vq_hmm_learn_loop_files(pm.data(), (unsigned)pm.size(), codebook.empty() ? nullptr : codebook.c_str(), pi.data(), (int)pi.size(), P, W,
+                                  O, ln_switch, transitions.empty() ? nullptr : transitions.c_str(), train_transitions ? 1 : 0,
+                                  pf.empty() ? nullptr : pf.data(), (int)pf.size(), alpha, epsilon, val_auto, max_iterations, out.c_str(),
+                                  hmm_callback)) {
+        printf("%s\n", e2vq_last_error());
+        return 1;
+    }
+    return 0;
+}
+
 static int hmm_cmd(int argc, char** argv)
 {
     if (argc < 1) return usage();
     const std::string cmd = argv[0];
+    if (cmd == "learn") {
+        for (int i = 1; i < argc; ++i)
+            if (std::string(argv[i]) == "--loop") return hmm_learn_loop_cmd(argc - 1, argv + 1);
+        for (int i = 1; i < argc; ++i)
+            if (std::string(argv[i]) == "--train-transitions" || std::string(argv[i]) == "--freeze") {
+                fprintf(stderr, "hmm learn: %s needs --loop (the models re-estimated under the class loop)\n", argv[i]);
+                return 2;
+            }
+    }
     if (cmd == "learn")
         for (int i = 1; i < argc; ++i)
             if (std::string(argv[i]) == "--embedded") return hmm_learn_embedded_cmd(argc - 1, argv + 1);

@@ -89,6 +89,26 @@ int LoopModels::logs(const char* const* files)
     return 0;
 }
 
+// the models go to <out_dir>/<class>.hmm: none of them may be an input model
+int model_out_paths(const char* who, const char* out_dir, const LoopModels& fm, const char* const* model_filenames, unsigned num_models,
+                    std::vector<std::string>& out_paths)
+{
+    out_paths.clear();
+    for (int k = 0; k < fm.K(); ++k) {
+        out_paths.push_back(std::string(out_dir) + "/" + fm.names[(size_t)k] + ".hmm");
+        char *a = realpath(out_paths.back().c_str(), nullptr);
+        bool same = false;
+        for (unsigned m = 0; a && m < num_models && !same; ++m) {
+            char* b = realpath(model_filenames[m], nullptr);
+            same = b && strcmp(a, b) == 0;
+            free(b);
+        }
+        free(a);
+        if (same) return e2vq_set_error("%s: %s would overwrite an input model (choose another output directory)", who, out_paths.back().c_str());
+    }
+    return 0;
+}
+
 int loop_check_args(const char* who, int K, const int* Ns, const double* const* pis, const double* const* As, const double* const* Bs,
                     bool rest)
 {

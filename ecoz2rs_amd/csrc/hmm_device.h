@@ -317,4 +317,19 @@ int launch_trans_estep(const SegPlanDev& pl, bool c_lds, bool a_lds, bool w_lds,
                        int S, long long a0, const double* w, double* ahs, double* cs, long long* acc, double* mant, long long* exp2,
                        int* status, hipStream_t st);
 
+// The expected state-level counts of every class under the same loop and prices (hmm_loop_estep.hip): the
+// E-step of `hmm learn --loop`.  pl, w, ahs / cs and mant / exp2 / status are launch_loop_posteriors_trans'; ms: K doubles a
+// frame more, the mass that entered each class (indexed as ahs).  classes: N, a_at (leading dimension N | 1) and acc_at of every
+// class; acc: their acc_words(N, M) blocks, added to (AD is launch_embed_rowsum's).  acc_trans: null, or launch_trans_estep's
+// 2 K^2 + 2 words, added to.  Dynamic LDS: the mandatory terms of 4.8.13; behind them, in this order and while the sum stays
+// within SEG_LDS_BYTES, the AN table of all classes (16 a_words bytes), the C table (16 K^2 bytes; with acc_trans only), A, then
+// both matrices (loop_estep_layout; an_forced / c_forced: *an_lds / *c_lds are the caller's).  Returns 1 when the shape cannot
+// be launched.
+size_t loop_estep_lds_bytes(const SegPlanDev& pl, bool an_lds, bool c_lds, bool a_lds, bool w_lds);
+void loop_estep_layout(const SegPlanDev& pl, bool gram, bool an_forced, bool c_forced, bool* an_lds, bool* c_lds, bool* a_lds,
+                       bool* w_lds);
+int launch_loop_estep(const SegPlanDev& pl, const EmbedClassDev* classes, bool an_lds, bool c_lds, bool a_lds, bool w_lds,
+                      const unsigned short* sym, const long long* offs, int S, long long a0, const double* w, double* ahs, double* cs,
+                      double* ms, long long* acc, long long* acc_trans, double* mant, long long* exp2, int* status, hipStream_t st);
+
 }  // namespace e2hmm

@@ -254,20 +254,8 @@ extern "C" int e2vq_hmm_learn_embedded_files(const char* const* model_filenames,
     Transcripts tr;
     if (tr.set_filler(who, fm, filler_class)) return 1;
     if (fm.logs(model_filenames)) return 1;
-    // the models go to <out_dir>/<class>.hmm: none of them may be an input model
     std::vector<std::string> out_paths;
-    for (int k = 0; k < K; ++k) {
-        out_paths.push_back(std::string(out_dir) + "/" + fm.names[(size_t)k] + ".hmm");
-        char *a = realpath(out_paths.back().c_str(), nullptr);
-        bool same = false;
-        for (unsigned m = 0; a && m < num_models && !same; ++m) {
-            char* b = realpath(model_filenames[m], nullptr);
-            same = b && strcmp(a, b) == 0;
-            free(b);
-        }
-        free(a);
-        if (same) return e2vq_set_error("%s: %s would overwrite an input model (choose another output directory)", who, out_paths.back().c_str());
-    }
+    if (model_out_paths(who, out_dir, fm, model_filenames, num_models, out_paths)) return 1;
     SymInputs si;
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
     for (int f = 0; f < num_inputs; ++f) {
@@ -286,18 +274,7 @@ extern "C" int e2vq_hmm_learn_embedded_files(const char* const* model_filenames,
     std::vector<i64> offs(1, 0);
     SymStage stg;
     if (require_device(device) || stg.open(device, si)) return 1;
-    // every input to symbols, one after the other, gathered in one device buffer (the frame counts known so far bound it)
-    i64 room = 0;
-    for (const SymInput& in : si.inputs) room += in.T;
-    if (d_all.reserve((size_t)room)) return 1;
-    for (int f = 0; f < num_inputs; ++f) {
-        int64_t T = 0;
-        if (stg.input(si.inputs[(size_t)f], si, P, W_ms, O_ms, &T)) return 1;
-        if (offs.back() + T > room) return e2vq_set_error("%s: internal error: %s gave more frames than its header counts", who, si.inputs[(size_t)f].path.c_str());
-        // (on the stage's stream: the next input overwrites d_sym only behind this copy)
-        if (T > 0) HIPCHK(hipMemcpyAsync(d_all.get() + offs.back(), stg.d_sym.get(), (size_t)T * 2, hipMemcpyDeviceToDevice, stg.st.s));
-        offs.push_back(offs.back() + T);
-    }
+    if (stg.gather(who, si, P, W_ms, O_ms, d_all, offs)) return 1;
     if (embed_plan(who, K, fm.Ns.data(), fm.M, offs.data(), num_inputs, tr.units.data(), tr.unit_offs.data(), tr.optional.data(), ln_switch, ep)) return 1;
     if (dev.setup(who, ep, offs.data(), num_inputs, stg.st.s)) return 1;
     const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;

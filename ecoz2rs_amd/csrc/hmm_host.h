@@ -4,7 +4,7 @@
 // of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
 // decoder; hmm_transcript.cpp: what the commands that take a transcript share; hmm_align.cpp: forced alignment; hmm_embed.cpp:
 // embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp: the posteriors of the alignment; hmm_trans_train.cpp:
-// Baum-Welch for the class-to-class prices).
+// Baum-Welch for the class-to-class prices; hmm_loop_train.cpp: Baum-Welch for the class models under the class loop).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -295,6 +295,11 @@ struct LoopModels : FilesModels {
     int logs(const char* const* files = nullptr);  // files: a failure is prefixed with the model's file name
 };
 
+// where the trainers that re-estimate given models write them: <out_dir>/<class>.hmm for every class of fm, in class order; a
+// path that names an input model's file is refused ("%s would overwrite an input model")
+int model_out_paths(const char* who, const char* out_dir, const LoopModels& fm, const char* const* model_filenames, unsigned num_models,
+                    std::vector<std::string>& out_paths);
+
 // The packing of the classes into wave-slots of 64 lanes that the class-loop decoders share: class after class, a class
 // that does not fit the open slot opens the next.  a_ld(N): the leading dimension of a class's A in the device block
 // (a_at / a_words count N x a_ld(N) words a class).
@@ -343,6 +348,10 @@ int posteriors_check_params(const Hmm& h);
 int trans_check_lt(const char* who, int K, const double* lt);
 std::vector<double> trans_prices(int K, const double* lt);
 std::vector<double> trans_params(const LoopModels& lm, const SegPacking& pk);
+// (hmm_trans_train.cpp) alpha: finite and at least 0.  trans_mstep: the M-step of 4.8.14 on the host -- row f of ln_p (K x K) from
+// the 2 K^2 limb words of acc; a -inf entry stays, a row without mass keeps its bytes.
+int trans_check_alpha(const char* who, double alpha);
+void trans_mstep(int K, const i64* acc, double alpha, double* ln_p);
 
 // ---- transcripts (hmm_transcript.cpp): what `hmm align`, `hmm learn --embedded` and `hmm align --posteriors` share --------
 // What the host decides about a call before the device is touched: the packing of every stream's units, the device tables
@@ -526,6 +535,9 @@ struct SymStage {
     // one input to symbols in d_sym (read and uploaded once; frames and symbols stay on the device): *T_out of them.
     // Waits for the stream before it returns.
     int input(const SymInput& in, const SymInputs& si, int P, int W_ms, int O_ms, int64_t* T_out);
+    // every input to symbols, one after the other, gathered in one device buffer: d_all holds them all, offs their
+    // num_inputs + 1 offsets from 0 (the trainers over whole streams: an E-step is then one call)
+    int gather(const char* who, const SymInputs& si, int P, int W_ms, int O_ms, DeviceBuffer<unsigned short>& d_all, std::vector<i64>& offs);
 };
 // What the commands that work input by input do once their own checks have passed (`who`: the entry point): the check of
 // the inputs and the codebook against M, still on the host alone; then one SymStage, and for every input its symbols on

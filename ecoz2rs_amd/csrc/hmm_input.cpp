@@ -180,6 +180,25 @@ int SymStage::input(const SymInput& in, const SymInputs& si, int P, int W_ms, in
     return 0;
 }
 
+int SymStage::gather(const char* who, const SymInputs& si, int P, int W_ms, int O_ms, DeviceBuffer<unsigned short>& d_all,
+                     std::vector<i64>& offs)
+{
+    // (the frame counts known so far bound the buffer: a .wav may still lose frames)
+    i64 room = 0;
+    for (const SymInput& in : si.inputs) room += in.T;
+    if (d_all.reserve((size_t)room)) return 1;
+    offs.assign(1, 0);
+    for (const SymInput& in : si.inputs) {
+        int64_t T = 0;
+        if (input(in, si, P, W_ms, O_ms, &T)) return 1;
+        if (offs.back() + T > room) return e2vq_set_error("%s: internal error: %s gave more frames than its header counts", who, in.path.c_str());
+        // (on the stage's stream: the next input overwrites d_sym only behind this copy)
+        if (T > 0) HIPCHK(hipMemcpyAsync(d_all.get() + offs.back(), d_sym.get(), (size_t)T * 2, hipMemcpyDeviceToDevice, st.s));
+        offs.push_back(offs.back() + T);
+    }
+    return 0;
+}
+
 int run_on_files(const char* who, int M, const char* cb_filename, const char* const* input_filenames, int num_inputs, int P, int W_ms,
                  int O_ms, const char* csv_dir_or_file,
                  const std::function<int(const SymInput&, int64_t, const unsigned short*, hipStream_t)>& run)

@@ -1,4 +1,4 @@
-// hmm_limbs.h -- the limb accumulators of the E-steps (hmm_embed.hip, hmm_embed_looped.hip, hmm_trans_estep.hip), written once: an expected
+// hmm_limbs.h -- the limb accumulators of the E-steps (hmm_embed.hip, hmm_embed_looped.hip, hmm_trans_estep.hip, hmm_loop_estep.hip), written once: an expected
 // count becomes two int32 limbs by the fix2_mul route (fix2's limbs for every input, by full-rate operations -- vq_fixed.h) and
 // is added to int64 cells; a zero limb adds nothing, so no atomic is issued for it.  (hmm_device.hip's acc_add / acc_local are
 // other functions: the fix2 route, every limb added.  This header does not reach that unit.)  Device code only.  Internal.

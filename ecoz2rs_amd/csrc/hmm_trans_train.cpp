@@ -9,6 +9,34 @@
 #include "vq_fixed.h"
 
 namespace e2hmm_host {
+
+// ---- what hmm_loop_train.cpp shares (hmm_host.h) ----------------------------------------------------------------------------
+int trans_check_alpha(const char* who, double alpha)
+{
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return e2vq_set_error("%s: alpha = %g: a finite number, at least 0", who, alpha);
+    return 0;
+}
+
+// The M-step of 4.8.14 (host; K^2 values): row f of ln_p from the counts.  A -inf entry stays; a row without mass keeps its bytes.
+void trans_mstep(int K, const i64* acc, double alpha, double* ln_p)
+{
+    for (int f = 0; f < K; ++f) {
+        const i64* row = acc + (size_t)f * K * 2;
+        double* lp = ln_p + (size_t)f * K;
+        i64 hi = 0, lo = 0;
+        int n = 0;
+        for (int k = 0; k < K; ++k) {
+            hi += row[2 * k];
+            lo += row[2 * k + 1];
+            n += lp[k] != -INFINITY;
+        }
+        const double den = e2vq::unfix(hi, lo, e2hmm::ACC_SHIFT) + alpha * (double)n;
+        if (!(den > 0.0)) continue;
+        for (int k = 0; k < K; ++k)
+            if (lp[k] != -INFINITY) lp[k] = log((e2vq::unfix(row[2 * k], row[2 * k + 1], e2hmm::ACC_SHIFT) + alpha) / den);
+    }
+}
+
 namespace {
 
 thread_local float g_trans_estep_kernel_ms = -1.f;  // e2vq_hmm_transitions_estep_last_kernel_ms
@@ -99,32 +127,6 @@ struct TransDev {
         return timer.elapsed_ms(&g_trans_estep_kernel_ms);
     }
 };
-
-int check_alpha(const char* who, double alpha)
-{
-    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return e2vq_set_error("%s: alpha = %g: a finite number, at least 0", who, alpha);
-    return 0;
-}
-
-// The M-step of 4.8.14 (host; K^2 values): row f of ln_p from the counts.  A -inf entry stays; a row without mass keeps its bytes.
-void trans_mstep(int K, const i64* acc, double alpha, double* ln_p)
-{
-    for (int f = 0; f < K; ++f) {
-        const i64* row = acc + (size_t)f * K * 2;
-        double* lp = ln_p + (size_t)f * K;
-        i64 hi = 0, lo = 0;
-        int n = 0;
-        for (int k = 0; k < K; ++k) {
-            hi += row[2 * k];
-            lo += row[2 * k + 1];
-            n += lp[k] != -INFINITY;
-        }
-        const double den = e2vq::unfix(hi, lo, e2hmm::ACC_SHIFT) + alpha * (double)n;
-        if (!(den > 0.0)) continue;
-        for (int k = 0; k < K; ++k)
-            if (lp[k] != -INFINITY) lp[k] = log((e2vq::unfix(row[2 * k], row[2 * k + 1], e2hmm::ACC_SHIFT) + alpha) / den);
-    }
-}
 
 struct TransIteration {
     double L;
@@ -219,7 +221,7 @@ extern "C" int e2vq_hmm_train_transitions(int device, int K, const int* Ns, int 
     LoopModels lm;
     TransPlan tp;
     if (trans_check_args(who, K, Ns, M, pis, As, Bs, sym, offs, S, ln_p, !(cap > 0 && !sum_log_prob), lm, tp) ||
-        segment_check_switch(who, ln_switch) || check_alpha(who, alpha))
+        segment_check_switch(who, ln_switch) || trans_check_alpha(who, alpha))
         return 1;
     // ---- the device from here on --------------------------------------------------------------------------------
     if (require_device(device)) return 1;
@@ -252,7 +254,7 @@ extern "C" int e2vq_hmm_learn_transitions_files(const char* const* model_filenam
     TransPlan tp;
     if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
     if (!out_csv || !*out_csv) return e2vq_set_error("%s: no output file", who);
-    if (segment_check_switch(who, ln_switch) || check_alpha(who, alpha) || window_ms_ok(who, W_ms, O_ms) ||
+    if (segment_check_switch(who, ln_switch) || trans_check_alpha(who, alpha) || window_ms_ok(who, W_ms, O_ms) ||
         lm.load_checked(who, model_filenames, num_models))
         return 1;
     const int K = lm.K();
@@ -271,18 +273,7 @@ extern "C" int e2vq_hmm_learn_transitions_files(const char* const* model_filenam
     std::vector<i64> offs(1, 0);  // (before the stage: its stream copies from them)
     SymStage stg;
     if (require_device(device) || stg.open(device, si)) return 1;
-    // every input to symbols, one after the other, gathered in one device buffer (the frame counts known so far bound it)
-    i64 room = 0;
-    for (const SymInput& in : si.inputs) room += in.T;
-    if (d_all.reserve((size_t)room)) return 1;
-    for (int f = 0; f < num_inputs; ++f) {
-        int64_t T = 0;
-        if (stg.input(si.inputs[(size_t)f], si, P, W_ms, O_ms, &T)) return 1;
-        if (offs.back() + T > room) return e2vq_set_error("%s: internal error: %s gave more frames than its header counts", who, si.inputs[(size_t)f].path.c_str());
-        // (on the stage's stream: the next input overwrites d_sym only behind this copy)
-        if (T > 0) HIPCHK(hipMemcpyAsync(d_all.get() + offs.back(), stg.d_sym.get(), (size_t)T * 2, hipMemcpyDeviceToDevice, stg.st.s));
-        offs.push_back(offs.back() + T);
-    }
+    if (stg.gather(who, si, P, W_ms, O_ms, d_all, offs)) return 1;
     if (dev.setup(who, tp, lm, offs.data(), num_inputs, stg.st.s)) return 1;
     const bool verbose = getenv("ECOZ2_VQ_QUIET") == nullptr;
     printf("\nHMM transitions --em: %d class(es)  M=%d  #streams = %d  frames = %lld\n", K, lm.M, num_inputs, (long long)offs.back());

@@ -107,6 +107,14 @@ _sig("e2vq_hmm_train_transitions", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)
      C.c_int)
 _sig("e2vq_hmm_learn_transitions_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_double, C.c_char_p, C.c_double, C.c_double, C.c_int, C.c_char_p)
+_sig("e2vq_hmm_loop_estep", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("e2vq_hmm_loop_estep_last_kernel_ms", C.c_int, C.POINTER(C.c_float))
+_sig("e2vq_hmm_train_loop", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p,
+     C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int,
+     C.POINTER(C.c_int), HMM_LEARN_CALLBACK, C.c_int)
+_sig("e2vq_hmm_learn_loop_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_double, C.c_char_p, C.c_int, c_char_pp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_char_p, HMM_LEARN_CALLBACK)
 
 _sig("e2vq_hmm_segment_stream_open", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_double,
      C.POINTER(C.c_void_p))
@@ -941,6 +949,77 @@ def learn_transitions_files(model_filenames, input_filenames, out_csv, ln_switch
                                                len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
                                                str(init).encode() if init else None, float(alpha), float(val_auto), int(max_iterations),
                                                str(out_csv).encode()))
+
+
+def loop_estep(models, sym, offs, ln_trans, acc_trans=None, device=0):
+    """one E-step of Baum-Welch for the class models under the class loop: models, sym (a numpy array or a
+    device tensor), offs and ln_trans as `transitions_estep` takes them -> dict acc (per class its int64 accumulator words, the
+    layout of `acc_words`), per stream log_prob and status.  acc_trans: None, True (a new table) or an int64 array of
+    `transitions_acc_words(K)` words to add into -> also acc_trans, the grammar counts of `transitions_estep`"""
+    c_args, lt, on_device, S, keep = _trans_args(models, sym, offs, ln_trans)
+    ms, M = keep[0], c_args[2]
+    acc = [np.zeros(int(lib.e2vq_hmm_acc_words(len(m[0]), M)), dtype=np.int64) for m in ms]
+    accp = (C.c_void_p * max(len(acc), 1))(*[x.ctypes.data for x in acc])
+    words = transitions_acc_words(len(models))
+    if acc_trans is True:
+        acc_trans = np.zeros(max(words, 2), dtype=np.int64)
+    elif acc_trans is not None and not (isinstance(acc_trans, np.ndarray) and acc_trans.dtype == np.int64 and
+                                        acc_trans.flags.c_contiguous and acc_trans.size == words):
+        raise ValueError(f"acc_trans must be a contiguous int64 array of {words} words")
+    lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
+    check(lib.e2vq_hmm_loop_estep(device, *c_args, lt.ctypes.data, accp, acc_trans.ctypes.data if acc_trans is not None else None,
+                                  lp.ctypes.data, st.ctypes.data, on_device))
+    out = dict(acc=acc, log_prob=lp[:S], status=st[:S])
+    if acc_trans is not None:
+        out["acc_trans"] = acc_trans
+    return out
+
+
+def loop_estep_last_kernel_ms():
+    return _kernel_ms(lib.e2vq_hmm_loop_estep_last_kernel_ms)
+
+
+def train_loop(models, sym, offs, ln_p=None, ln_switch=0.0, train_transitions=False, frozen=None, alpha=1.0, epsilon=1e-5, val_auto=0.3,
+               max_iterations=-1, callback=None, device=0):
+    """Baum-Welch for the class models under the class loop to its stop: ln_p is the matrix as a transitions
+    file holds it (None: zeros), the effective price of an E-step ln_p + ln_switch; train_transitions: the matrix is
+    re-estimated with the models (alpha as `train_transitions` takes it); frozen: per class a flag, a class whose flag is set
+    keeps its model -> (the trained models [(pi, A, B)], ln_p (K, K), the sum of ln P per E-step); callback(var: str,
+    val: float) per E-step"""
+    K = len(models)
+    if ln_p is None:
+        ln_p = np.zeros((K, K))
+    models = [tuple(np.array(x, dtype=np.float64, order="C") for x in m) for m in models]  # (copies: the call writes them)
+    c_args, lt, on_device, _S, _keep = _trans_args(models, sym, offs, ln_p)
+    fz = None
+    if frozen is not None:
+        fz = np.ascontiguousarray(np.asarray(frozen) != 0, dtype=np.uint8)
+        if fz.shape != (K,):
+            raise ValueError(f"frozen has the shape {fz.shape}, not ({K},)")
+    cap = 1000
+    hist = np.zeros(cap)
+    n = C.c_int(0)
+    cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
+    check(lib.e2vq_hmm_train_loop(device, *c_args, lt.ctypes.data, float(ln_switch), int(bool(train_transitions)),
+                                  fz.ctypes.data if fz is not None else None, float(alpha), float(epsilon), float(val_auto),
+                                  int(max_iterations), hist.ctypes.data, cap, C.byref(n), cb, on_device))
+    return _keep[0], lt, hist[:n.value].copy()
+
+
+def learn_loop_files(model_filenames, input_filenames, out_dir, ln_switch, class_transitions=None, train_transitions=False, freeze=(),
+                     alpha=1.0, hmm_epsilon=1e-5, val_auto=0.3, max_iterations=-1, codebook=None, P=36, W_ms=45, O_ms=15, callback=None):
+    """`hmm learn --loop`: the models of the files re-estimated from the inputs (.wav, .prd or .seq) under the
+    class loop, from the transitions file class_transitions or a matrix of zeros; freeze: class names whose models stay; writes
+    <out_dir>/<class>.hmm for every class, <out_dir>/loop.csv and, with train_transitions, <out_dir>/transitions.csv"""
+    m, _k1 = _strs(model_filenames)
+    f, _k2 = _strs(input_filenames)
+    z, _k3 = _strs(list(freeze))
+    cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
+    check(lib.e2vq_hmm_learn_loop_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, len(input_filenames),
+                                        int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                        str(class_transitions).encode() if class_transitions else None, int(bool(train_transitions)),
+                                        z, len(freeze), float(alpha), float(hmm_epsilon), float(val_auto), int(max_iterations),
+                                        str(out_dir).encode(), cb))
 
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,

@@ -503,6 +503,70 @@ int e2vq_hmm_learn_transitions_files(const char *const *model_filenames, unsigne
                                      double ln_switch, const char *init_csv, double alpha, double val_auto, int max_iterations,
                                      const char *out_csv);
 
+/* ---- Baum-Welch for the class models under the class loop ----------------------------------------------
+ * `hmm learn --loop`: pi, A and B of every class re-estimated from whole unlabelled streams under the very loop that
+ * e2vq_hmm_segment_trans decodes, and on request the matrix with them, from one forward-backward pass.  The model, the inputs
+ * and the refusals are e2vq_hmm_transitions_estep's: K models sharing M, N_k <= 64 (mixed N), S streams in sym / offs, lt
+ * (row-major K x K, each entry <= 0 or -inf) with w[f][k] = exp(lt[f][k]) taken by the C library on the host.  Only the
+ * resident layout exists: a packing of more than 16 wave-slots is refused before any HIP call ("the classes take %d
+ * wave-slots of 64 lanes (at most 16: the E-step of the class models under the loop has no looped body)").  Nothing
+ * transcendental runs on the device; every operation is one IEEE double operation in a fixed order, no fma (DESIGN.md 4.8.16
+ * states it; tests/hmm_loop_em_restatement.py restates it; the GPU matches it bit for bit).
+ * E-step.  Forward, scaling, status, log_prob and backward are 4.8.13's word for word (S, m, x, c_t, ah, u, R, r, bh with
+ * bh_{T-1} = 1, the same CS and GS): for a given input log_prob and status are the bits of e2vq_hmm_segment_trans_posteriors.
+ * An empty stream has status 0, log_prob 0.0 and adds nothing but its mark.  New are the state counts, for every stream of
+ * status 0, each through fix2(., 29) into class k's block acc[k] of e2vq_hmm_acc_words(N_k, M) words (PI | AN | AD | BN | BD |
+ * used, skipped; a zero limb adds nothing):
+ *   every t:        g = ah_t[k][j] * bh_t[k][j]                      to BN[j][o_t] and BD[j]; at t = 0 also to PI[j]
+ *   t < T - 1:      (ah_t[k][i] * A_k[i][j]) * u_{t+1}[k][j]         to AN[i][j]    (u_{t+1} = (B_k[j][o_{t+1}] * bh_{t+1}[k][j]) / c_{t+1})
+ *   t < T - 1:      (m_{t+1}[k] * pi_k[j]) * u_{t+1}[k][j]           to PI[j]       (the entry through pi; the inner product has the
+ *                                                                                    bits the forward step added to the chain)
+ * AD[i] is the integer sum of row i of AN, both limbs.  used counts the status-0 streams of the call and skipped the others,
+ * once a stream, in every class's block (every class is in the loop); a stream of status != 0 adds nothing else.  acc[k] is
+ * overwritten, as e2vq_hmm_embedded_estep does.  acc_trans (may be NULL; e2vq_hmm_transitions_acc_words(K) words, added to):
+ * 4.8.14's xi_t[f][k] = S_t[f] * (w[f][k] * R_t[k]), limb for limb the result of e2vq_hmm_transitions_estep on the same input;
+ * without it the grammar products are not formed.  All sums are integers: the split over workgroups, the order of the streams
+ * and the route of an atomic change no bit.  Routes: BD and PI are summed per lane and flushed once a stream, BN goes by
+ * global atomics; the AN table of all classes (16 sum_k N_k (N_k | 1) bytes) and the C table (16 K^2 bytes) live in the
+ * workgroup's LDS when they fit, in this order, behind the mandatory terms and ahead of A and the two price matrices;
+ * ECOZ2_HMM_LOOP_EM_AN=lds|global and ECOZ2_HMM_LOOP_EM_C=lds|global force either, and a forced table that does not fit is
+ * refused.  ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds the per-launch forward table, 8 (sum N + slots + K) bytes a frame (4.8.13's
+ * row and m_t of every class), by whole streams.  One device.  sym_on_device as in e2vq_hmm_segment. */
+int e2vq_hmm_loop_estep(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                        const double *const *Bs, const void *sym, const int64_t *offs, int S, const double *lt, int64_t *const *acc,
+                        int64_t *acc_trans, double *log_prob, int *status, int sym_on_device);
+/* HIP-event time of the kernels of this thread's last E-step (-1: none yet) */
+int e2vq_hmm_loop_estep_last_kernel_ms(float *ms);
+/* The training.  pis / As / Bs are re-estimated in place; ln_p (K x K, in and, with train_transitions, out) is the matrix as
+ * the transitions file holds it; the effective price of an E-step is ln_p[f][k] + ln_switch (one host addition; ln_switch <= 0
+ * is not trained).  Per iteration one E-step over all streams, then L = the sum of log_prob over the status-0 streams in
+ * stream order (callback("sum_log_prob", L); sum_log_prob[it] while it < cap).  The loop stops at max_iterations (< 0: none),
+ * at 1000 E-steps, or when it > 0 and L - Lprev <= val_auto; a stopping iteration gets no M-step.  If no stream has status 0
+ * after the first E-step the call returns 1 and models and matrix are as they came.
+ * M-step.  e2vq_hmm_train_embedded's, all K classes in one launch: pi by the sum of its own counts, A by AD, B by BD, each
+ * quotient only where its denominator is > 0 (zeros in pi and A stay zeros), then the floor of B at epsilon (> 0) for the
+ * classes whose used > 0.  frozen (may be NULL): K flags; the block of a class whose flag is not 0 is zeroed before the
+ * M-step, so the class keeps every byte of its model.  With train_transitions (not 0) e2vq_hmm_train_transitions' M-step is
+ * applied to ln_p from the counts of the same E-step (alpha: finite, >= 0; -inf stays -inf); without it ln_p is not written. */
+int e2vq_hmm_train_loop(int device, int K, const int *Ns, int M, double *const *pis, double *const *As, double *const *Bs,
+                        const void *sym, const int64_t *offs, int S, double *ln_p, double ln_switch, int train_transitions,
+                        const uint8_t *frozen, double alpha, double epsilon, double val_auto, int max_iterations,
+                        double *sum_log_prob, int cap, int *num_esteps, void (*callback)(char *variable, double value),
+                        int sym_on_device);
+/* `hmm learn --loop`: the same from files.  Models, codebook and inputs (.wav / .prd / .seq) are
+ * e2vq_hmm_learn_transitions_files'; all streams are gathered in one device buffer.  The start of the matrix is
+ * transitions_csv or, when NULL or empty, a matrix of zeros (the effective prices are then the one ln_switch, as
+ * e2vq_hmm_segment_trans_files treats a file of zeros).  frozen_classes: num_frozen class names, each some model's class.
+ * Written: <out_dir>/<class>.hmm for every class, <out_dir>/loop.csv with iteration,sum_log_prob,streams_used,streams_skipped
+ * (%.17g) and, with train_transitions, <out_dir>/transitions.csv through e2vq_hmm_transitions_write.  Refused: an out_dir
+ * that would overwrite an input model, two models of one class, a frozen name that is no model's class.  A stream whose
+ * status changes is named on stderr with the iteration. */
+int e2vq_hmm_learn_loop_files(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                              const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
+                              const char *transitions_csv, int train_transitions, const char *const *frozen_classes, int num_frozen,
+                              double alpha, double epsilon, double val_auto, int max_iterations, const char *out_dir,
+                              void (*callback)(char *variable, double value));
+
 /* ---- the same decode on a stream that arrives piece by piece -------------------------------------------
  * `hmm segment --continuous`: a session decodes ONE symbol stream of unknown length under the contract of e2vq_hmm_segment
  * (K models sharing M, one ln_switch; same recursion, ties, G_t, g_t, psi and ENTER) and gives the bits of e2vq_hmm_segment
