@@ -1,18 +1,22 @@
-"""inputs that test_hmm_class_loop_cases_cpu.py, test_gpu_hmm_class_loop_shapes.py and test_gpu_hmm_trans_posteriors_shapes.py
-share (TEST INFRASTRUCTURE): what the five class-loop decoders of DESIGN.md 4.8.6 - 4.8.9 and 4.8.13 (`hmm segment`,
---posteriors, --class-transitions, --continuous, --grammar-posteriors) are run at beyond the tables of class sets of their
-own files -- streams with a bad or a dead symbol at the edges of the 64-symbol hand-out, class sets near the 4096 states the
+"""inputs that test_hmm_class_loop_cases_cpu.py, test_gpu_hmm_class_loop_shapes.py, test_gpu_hmm_trans_posteriors_shapes.py and
+test_gpu_hmm_grammar_shapes.py share (TEST INFRASTRUCTURE): what the five class-loop decoders of DESIGN.md 4.8.6 - 4.8.9 and
+4.8.13 (`hmm segment`, --posteriors, --class-transitions, --continuous, --grammar-posteriors), the two grammar trainers of
+4.8.14 and 4.8.16 (`hmm transitions --em`, `hmm learn --loop`) and the grammar session of 4.8.15 (--grammar-continuous) are
+run at beyond the tables of class sets of their own files -- streams with a bad or a dead symbol at the edges of the 64-symbol hand-out, class sets near the 4096 states the
 decoders admit whose models lean so that the path visits many classes, the class sets that take --grammar-posteriors to each
-of its four LDS layouts and above 64 KB of dynamic LDS, and seeded random sets -- and the LDS arithmetic of the five
-launchers, restated."""
+of its four LDS layouts and above 64 KB of dynamic LDS, the class sets that take the trainers and the grammar session to each of theirs (GRAMMAR_SHAPES), and
+seeded random sets -- and the LDS arithmetic of the eight launchers, restated."""
 import functools
 
 import numpy as np
 
 from . import hmm_align_cases as align_cases
 from . import hmm_segment_restatement as R
+from . import hmm_loop_em_restatement as RLE
 from . import hmm_segment_stream_restatement as RS
+from . import hmm_segment_trans_stream_restatement as RTS
 from . import hmm_trans_posterior_restatement as RTP
+from . import hmm_transitions_em_restatement as RTE
 from .hmm_align_cases import DEAD, EVENT_EDGES, EVENT_PAIRS_AT, EVENT_T, RANDOM_NS, slots_of  # noqa: F401  (for the tests as well)
 from .hmm_segment_trans_cases import random_model, random_prices
 from .hmm_viterbi_restatement import log_model
@@ -254,7 +258,7 @@ def first_seed(limit):
 RANDOM_SEED = 4
 
 
-# ---- the LDS arithmetic of the five launchers, restated; test_hmm_class_loop_cases_cpu.py holds it against the sources -----------
+# ---- the LDS arithmetic of the eight launchers, restated; test_hmm_class_loop_cases_cpu.py holds it against the sources ----------
 SEG_LDS_BYTES = align_cases.SEG_LDS_BYTES
 SEG_MAX_WAVES = align_cases.SEG_MAX_WAVES
 SEG_MAX_SUM_N = 4096
@@ -283,10 +287,27 @@ def trans_posteriors_lds_bytes(K, sumN, a_words, a_lds, w_lds):
     return (2 * SEG_MAX_WAVES + 2 * K + sumN + (a_words if a_lds else 0) + (2 * K * K if w_lds else 0)) * 8
 
 
-def route(decoder, Ns, looped=None):
-    """-> dict body ("resident" / "looped"), a_lds, lt_lds (trans alone; else None), lds: what the launcher of `decoder`
-    ("segment", "stream", "posteriors", "trans" or "trans_posteriors") decides for the class set; looped:
-    ECOZ2_HMM_SEGMENT_BODY=looped.  "trans_posteriors" adds w_lds: both price matrices of 4.8.13, placed after A"""
+def trans_estep_lds_bytes(K, sumN, a_words, c_lds, a_lds, w_lds):
+    return (2 * SEG_MAX_WAVES + 2 * K + sumN + (2 * K * K if c_lds else 0) + (a_words if a_lds else 0) + (2 * K * K if w_lds else 0)) * 8
+
+
+def loop_estep_lds_bytes(K, sumN, a_words, an_lds, c_lds, a_lds, w_lds):
+    return (2 * SEG_MAX_WAVES + 2 * K + sumN + (2 * a_words if an_lds else 0) + (2 * K * K if c_lds else 0) +
+            (a_words if a_lds else 0) + (2 * K * K if w_lds else 0)) * 8
+
+
+def trans_stream_lds_bytes(K, a_words, a_lds, lt_lds):
+    return 2 * K * 8 + (a_words * 8 if a_lds else 0) + (K * K * 8 if lt_lds else 0)
+
+
+def route(decoder, Ns, looped=None, gram=True, an=None, c=None):
+    """-> dict body ("resident" / "looped"), a_lds, lt_lds (trans and trans_stream alone; else None), lds: what the launcher of
+    `decoder` ("segment", "stream", "posteriors", "trans", "trans_posteriors", "trans_estep", "loop_estep" or "trans_stream")
+    decides for the class set; looped: ECOZ2_HMM_SEGMENT_BODY=looped.  "trans_posteriors" adds w_lds: both price matrices of
+    4.8.13, placed after A.  The two trainers (4.8.14, 4.8.16) add c_lds, the count table of the grammar, and "loop_estep"
+    an_lds, the AN table over all classes, before it; gram: the call forms the grammar counts (else c_lds is None); an / c:
+    the route ECOZ2_HMM_LOOP_EM_AN / ECOZ2_HMM_LOOP_EM_C (for "trans_estep" ECOZ2_HMM_TRANS_EM_C) forces, True for lds, False
+    for global.  A forced route may ask for more than SEG_LDS_BYTES: the host refuses that call."""
     slots, sumN, K = slots_of(Ns), sum(Ns), len(Ns)
     if decoder in ("segment", "stream"):
         if looped is None:
@@ -307,10 +328,31 @@ def route(decoder, Ns, looped=None):
         w_lds = trans_posteriors_lds_bytes(K, sumN, a_words, a_lds, True) <= SEG_LDS_BYTES
         return dict(body="resident", a_lds=a_lds, lt_lds=None, w_lds=w_lds,
                     lds=trans_posteriors_lds_bytes(K, sumN, a_words, a_lds, w_lds))
-    assert decoder == "trans"
+    if decoder == "trans_estep":  # the decision order: c, a, w
+        a_words = sum(N * (N | 1) for N in Ns)  # (posteriors_a_ld)
+        lds = lambda *where: trans_estep_lds_bytes(K, sumN, a_words, *where)
+        c_lds = lds(True, False, False) <= SEG_LDS_BYTES if c is None else c
+        a_lds = lds(c_lds, True, False) <= SEG_LDS_BYTES
+        w_lds = lds(c_lds, a_lds, True) <= SEG_LDS_BYTES
+        return dict(body="resident", c_lds=c_lds, a_lds=a_lds, lt_lds=None, w_lds=w_lds, lds=lds(c_lds, a_lds, w_lds))
+    if decoder == "loop_estep":  # the decision order: an, c (with the grammar table alone), a, w
+        a_words = sum(N * (N | 1) for N in Ns)  # (posteriors_a_ld)
+        lds = lambda *where: loop_estep_lds_bytes(K, sumN, a_words, *where)
+        an_lds = lds(True, False, False, False) <= SEG_LDS_BYTES if an is None else an
+        if not gram:
+            c_lds = False
+        else:
+            c_lds = lds(an_lds, True, False, False) <= SEG_LDS_BYTES if c is None else c
+        a_lds = lds(an_lds, c_lds, True, False) <= SEG_LDS_BYTES
+        w_lds = lds(an_lds, c_lds, a_lds, True) <= SEG_LDS_BYTES
+        return dict(body="resident", an_lds=an_lds, c_lds=c_lds if gram else None, a_lds=a_lds, lt_lds=None, w_lds=w_lds,
+                    lds=lds(an_lds, c_lds, a_lds, w_lds))
+    assert decoder in ("trans", "trans_stream")
     a_words = sum(N * N for N in Ns)
     a_lds = trans_lds_bytes(K, a_words, True, False) <= SEG_LDS_BYTES
     lt_lds = trans_lds_bytes(K, a_words, a_lds, True) <= SEG_LDS_BYTES
+    if decoder == "trans_stream":  # segment_trans_layout's decision; the session's kernel is launched without the pairs
+        return dict(body="resident", a_lds=a_lds, lt_lds=lt_lds, lds=trans_stream_lds_bytes(K, a_words, a_lds, lt_lds))
     return dict(body="resident", a_lds=a_lds, lt_lds=lt_lds, lds=trans_lds_bytes(K, a_words, a_lds, lt_lds))
 
 
@@ -354,3 +396,70 @@ def trans_posteriors_event_reference(name):
     sym = np.concatenate(streams)
     offs = np.arange(len(streams) + 1, dtype=np.int64) * EVENT_T
     return RTP.posteriors(models, sym, offs, event_prices(len(models)))
+
+
+# ---- the grammar trainers and the grammar session (4.8.14 - 4.8.16) at every LDS layout ------------------------------------------
+# name: (N of every class, M, T): the rows of TRANS_POSTERIORS_SHAPES and six more, built as those are -- leaning models, a
+# dwelling stream of T frames, forbidding_prices(3, K).  Behind each row what the three launchers make of it (asserted through
+# route() in test_hmm_class_loop_cases_cpu.py): k_hmm_trans_estep's (c, a, w) and bytes | k_hmm_loop_estep's (an, c, a, w) and
+# bytes with the grammar table | k_hmm_segment_trans_stream's (a, lt) and bytes.  T / F: in LDS / in global memory.
+GRAMMAR_SHAPES = {
+    "64x3": ([64] * 3, 64, 130),                          # TTT 101,968 | FTTT 101,968 | TT 98,424
+    "64x6_1x84": ([64] * 6 + [1] * 84, 64, 130),          # TFF 135,040 | FTFF 135,040; without the table F-FT | FT 66,240
+    "40_1x24_x6": (([40] + [1] * 24) * 6, 4, 130),        # FTF 85,600 | FFTF 85,600 | TF 80,352
+    "64x4_1x768": ([64] * 4 + [1] * 768, 64, 130),        # FTF 160,064 | FFTF 160,064 | TF 149,568
+    # (the C table in global memory at K = 1024, about 10^6 limb pairs a frame: 605 ms and 599 ms of kernel time for the 130
+    # frames in the two trainers on one MI355X, so T stays 130)
+    "1x1024": ([1] * 1024, 64, 130),                      # FTF 33,024 | TFTF 49,408 | TF 24,576
+    "40_1x24_x14": (([40] + [1] * 24) * 14, 4, 130),      # FFF 13,024 | FFFF 13,024 | FF 5,600
+    "64x8_1x512": ([64] * 8 + [1] * 512, 64, 130),        # FFF 16,768 | FFFF 16,768 | FF 8,320
+    "64x2": ([64] * 2, 64, 130),                          # TTT 68,000 | TTFT 134,560: AN in LDS, A global | TT 65,600
+    "1x71": ([1] * 71, 64, 130),                          # TTT 163,840: the cap exactly | TTTF 84,320 | TT 42,032
+    "1x80": ([1] * 80, 64, 130),                          # TTF 105,216 | TTTF 106,496 | TT 53,120
+    "64_1x64": ([64] + [1] * 64, 64, 130),                # TTF 103,712 | TTFF 137,504 | TT 68,120
+    "64x2_1x60": ([64] * 2 + [1] * 60, 64, 130),          # TTF 131,296 | TFFF 136,832 | TT 97,760
+    "64x3_1x64": ([64] * 3 + [1] * 64, 64, 130),          # TFT 147,024 | FTFT 147,024; without the table F-TF 103,728 | TT 135,800
+}
+GRAMMAR_EVENT_SETS = TRANS_POSTERIORS_EVENT_SETS + ("64x2",)  # (AN in LDS next to A in global memory, an event behind it)
+EVENT_NS["64x2"] = (64,) * 2
+
+
+def grammar_shape(name):
+    """-> (models, stream, lt) of a row of GRAMMAR_SHAPES"""
+    Ns, M, T = GRAMMAR_SHAPES[name]
+    K = len(Ns)
+    return leaning_models(MODEL_SEED, Ns, M), run_stream(STREAM_SEED, K, M, T), forbidding_prices(TRANS_POSTERIORS_PRICE_SEED, K)
+
+
+@functools.lru_cache(maxsize=None)
+def trans_estep_reference(name):
+    """hmm_transitions_em_restatement.estep of the row, computed once (read only: the tests share it)"""
+    models, stream, lt = grammar_shape(name)
+    return RTE.estep(models, stream, [0, len(stream)], lt)
+
+
+@functools.lru_cache(maxsize=None)
+def loop_estep_reference(name):
+    """hmm_loop_em_restatement.estep of the row with the grammar table, computed once (read only)"""
+    models, stream, lt = grammar_shape(name)
+    return RLE.estep(models, stream, [0, len(stream)], lt, acc_trans=True)
+
+
+@functools.lru_cache(maxsize=None)
+def trans_stream_reference(name):
+    """-> (the closed Stream of hmm_segment_trans_stream_restatement at SESSION_B, fed whole; final_after(p) at every multiple p
+    of SESSION_B: the frames a session has delivered once it has processed p of them, whatever the feeds), computed once"""
+    models, stream, lt = grammar_shape(name)
+    rest, _finals = RTS.decode([log_model(*m) for m in models], stream, lt, SESSION_B, [len(stream)])
+    return rest, {p: rest.final_after(p) for p in range(0, len(stream) + 1, SESSION_B)}
+
+
+@functools.lru_cache(maxsize=None)
+def grammar_event_reference(name):
+    """-> (hmm_transitions_em_restatement.estep, hmm_loop_em_restatement.estep with the grammar table) of the clean stream of the
+    event batch alone, under event_models(name) and event_prices(K), computed once (read only): a failed stream adds nothing
+    but its mark, so these are the limbs of the whole batch"""
+    streams, _kinds = event_batch()
+    models = event_models(name)
+    lt = event_prices(len(models))
+    return RTE.estep(models, streams[0], [0, EVENT_T], lt), RLE.estep(models, streams[0], [0, EVENT_T], lt, acc_trans=True)

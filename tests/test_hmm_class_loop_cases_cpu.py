@@ -4,7 +4,11 @@ and the .hip sources; the body and the placement of lA (and lt) that every row o
 instantiation and the bytes of dynamic LDS that every row, event set and random set of --grammar-posteriors (4.8.13) reaches
 (the restatement at those rows is held against extended precision in test_hmm_trans_posteriors_cpu.py); on the restatements alone, what makes a row worth running -- its path visits many classes in many slots, the
 last one among them, and a session over it decides frames after every block --; the vectorised restatements against their
-literal forms on the event streams, and the status of each; the seeded random sets."""
+literal forms on the event streams, and the status of each; the seeded random sets.  For test_gpu_hmm_grammar_shapes.py: the LDS
+sums and decision orders of the two grammar trainers (4.8.14, 4.8.16) and of the grammar session (4.8.15) against their
+launchers, the layout and bytes of every row of GRAMMAR_SHAPES in each of the three kernels, every instantiation and count-table
+route reached (above 64 KB where one can be), the status of the event streams under the trainers' restatements, and that the
+session's restatement delivers frames before close at every row."""
 import os
 import re
 
@@ -12,9 +16,11 @@ import numpy as np
 import pytest
 
 from . import hmm_class_loop_cases as cases
+from . import hmm_loop_em_restatement as RLE
 from . import hmm_posterior_restatement as RP
 from . import hmm_segment_restatement as R
 from . import hmm_segment_trans_restatement as RT
+from . import hmm_transitions_em_restatement as RTE
 from . import hmm_viterbi_restatement as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -213,6 +219,188 @@ def test_the_neighbour_row_takes_segment_trans_above_64_kb_with_lA_global():
     models, stream, lt = cases.trans_posteriors_shape("64x6_1x84")
     want = RT.segment_trans(models, stream, [0, len(stream)], lt)
     assert want["status"].tolist() == [0] and want["entered"].sum() >= 10  # (a path of one segment would read little of lt)
+
+
+# ---- the grammar trainers and the grammar session: the sums, and the layout and bytes of every row ----------------------------
+def test_the_restated_lds_sums_of_the_grammar_kernels_are_the_launchers():
+    body = lambda name, fn: re.search(r"size_t %s\([^)]*\)\s*\{(.*?)\n\s*\}" % fn, _source(name), re.S).group(1)
+    # 4.8.14: doubles (partials of two parities, S / R of two steps, pi, the C table, A, w and wT); the order c, a, w
+    src = _source("hmm_trans_estep.hip")
+    te = body("hmm_trans_estep.hip", "trans_estep_lds_bytes")
+    assert "return ((size_t)2 * SEG_MAX_WAVES + (size_t)2 * pl.K + (size_t)pl.sumN + (c_lds ? (size_t)2 * pl.K * pl.K : 0) +" in te
+    assert "(a_lds ? (size_t)pl.a_words : 0) + (w_lds ? (size_t)2 * pl.K * pl.K : 0)) * sizeof(double);" in te
+    assert "if (!c_forced) *c_lds = trans_estep_lds_bytes(pl, true, false, false) <= SEG_LDS_BYTES;" in src
+    assert "*a_lds = trans_estep_lds_bytes(pl, *c_lds, true, false) <= SEG_LDS_BYTES;" in src
+    assert "*w_lds = trans_estep_lds_bytes(pl, *c_lds, *a_lds, true) <= SEG_LDS_BYTES;" in src
+    assert src.index("*c_lds = trans_estep_lds_bytes") < src.index("*a_lds = trans_estep_lds_bytes") < src.index("*w_lds = trans_estep_lds_bytes")
+    # 4.8.16: the AN table (two words a cell of A) before the C table; the order an, c (with the grammar table alone), a, w
+    loop = _source("hmm_loop_estep.hip")
+    le = body("hmm_loop_estep.hip", "loop_estep_lds_bytes")
+    assert "return ((size_t)2 * SEG_MAX_WAVES + (size_t)2 * pl.K + (size_t)pl.sumN + (an_lds ? (size_t)2 * pl.a_words : 0) +" in le
+    assert "(c_lds ? (size_t)2 * pl.K * pl.K : 0) + (a_lds ? (size_t)pl.a_words : 0) + (w_lds ? (size_t)2 * pl.K * pl.K : 0)) *" in le
+    assert "sizeof(double);" in le
+    order = ["if (!an_forced) *an_lds = loop_estep_lds_bytes(pl, true, false, false, false) <= SEG_LDS_BYTES;",
+             "if (!gram) *c_lds = false;",
+             "else if (!c_forced) *c_lds = loop_estep_lds_bytes(pl, *an_lds, true, false, false) <= SEG_LDS_BYTES;",
+             "*a_lds = loop_estep_lds_bytes(pl, *an_lds, *c_lds, true, false) <= SEG_LDS_BYTES;",
+             "*w_lds = loop_estep_lds_bytes(pl, *an_lds, *c_lds, *a_lds, true) <= SEG_LDS_BYTES;"]
+    at = [loop.index(line) for line in order]
+    assert at == sorted(at)
+    assert "if (!gram) c_lds = false;" in loop  # (the launcher's own: a call without the table has no C table in LDS)
+    # 4.8.15: segment_trans_layout decides (its sum holds the pairs), the launch is without them
+    stream = _source("hmm_segment_trans_stream.hip")
+    assert "segment_trans_layout(pl, &a_lds, &lt_lds);" in stream
+    assert ("const size_t lds = (size_t)2 * pl.K * 8 + (a_lds ? (size_t)pl.a_words * 8 : 0) + (lt_lds ? (size_t)pl.K * pl.K * 8 : 0);"
+            in stream)
+    for name, text in (("hmm_trans_estep.hip", src), ("hmm_loop_estep.hip", loop), ("hmm_segment_trans_stream.hip", stream)):
+        assert "if (lds > 64 * 1024 &&" in text and "hipFuncAttributeMaxDynamicSharedMemorySize" in text, name
+        assert "(int)SEG_LDS_BYTES) != hipSuccess)" in text and "if (lds > SEG_LDS_BYTES) return 1;" in text, name
+    # both trainers pack with the posteriors' odd leading dimension, the session with the decoder's N x N
+    assert "tp.pk = pack_slots(Ns, posteriors_a_ld);" in _source("hmm_trans_train.cpp")
+    assert "lp.pk = pack_slots(Ns, posteriors_a_ld);" in _source("hmm_loop_train.cpp")
+    assert cases.trans_estep_lds_bytes(3, 12, 68, True, True, True) == (32 + 6 + 12 + 18 + 68 + 18) * 8
+    assert cases.loop_estep_lds_bytes(3, 12, 68, True, True, True, True) == (32 + 6 + 12 + 136 + 18 + 68 + 18) * 8
+    assert cases.trans_stream_lds_bytes(3, 50, True, True) == (6 + 50 + 9) * 8
+
+
+# name: k_hmm_trans_estep (c, a, w, bytes), k_hmm_loop_estep with the table (an, c, a, w, bytes) and without it (an, a, w,
+# bytes), k_hmm_segment_trans_stream (a, lt, bytes)
+T_, F_ = True, False
+GRAMMAR_ROUTES = {
+    "64x3": ((T_, T_, T_, 101968), (F_, T_, T_, T_, 101968), (F_, T_, T_, 101824), (T_, T_, 98424)),
+    "64x6_1x84": ((T_, F_, F_, 135040), (F_, T_, F_, F_, 135040), (F_, F_, T_, 135040), (F_, T_, 66240)),
+    "40_1x24_x6": ((F_, T_, F_, 85600), (F_, F_, T_, F_, 85600), (F_, T_, F_, 85600), (T_, F_, 80352)),
+    "64x4_1x768": ((F_, T_, F_, 160064), (F_, F_, T_, F_, 160064), (F_, T_, F_, 160064), (T_, F_, 149568)),
+    "1x1024": ((F_, T_, F_, 33024), (T_, F_, T_, F_, 49408), (T_, T_, F_, 49408), (T_, F_, 24576)),
+    "40_1x24_x14": ((F_, F_, F_, 13024), (F_, F_, F_, F_, 13024), (F_, F_, F_, 13024), (F_, F_, 5600)),
+    "64x8_1x512": ((F_, F_, F_, 16768), (F_, F_, F_, F_, 16768), (F_, F_, F_, 16768), (F_, F_, 8320)),
+    "64x2": ((T_, T_, T_, 68000), (T_, T_, F_, T_, 134560), (T_, F_, T_, 134496), (T_, T_, 65600)),
+    "1x71": ((T_, T_, T_, 163840), (T_, T_, T_, F_, 84320), (T_, T_, T_, 84320), (T_, T_, 42032)),
+    "1x80": ((T_, T_, F_, 105216), (T_, T_, T_, F_, 106496), (T_, T_, T_, 106496), (T_, T_, 53120)),
+    "64_1x64": ((T_, T_, F_, 103712), (T_, T_, F_, F_, 137504), (T_, T_, F_, 103696), (T_, T_, 68120)),
+    "64x2_1x60": ((T_, T_, F_, 131296), (T_, F_, F_, F_, 136832), (T_, F_, F_, 136832), (T_, T_, 97760)),
+    "64x3_1x64": ((T_, F_, T_, 147024), (F_, T_, F_, T_, 147024), (F_, T_, F_, 103728), (T_, T_, 135800)),
+}
+
+
+def _grammar_routes(name):
+    Ns = cases.GRAMMAR_SHAPES[name][0]
+    te, le, lp, ts = (cases.route("trans_estep", Ns), cases.route("loop_estep", Ns), cases.route("loop_estep", Ns, gram=False),
+                      cases.route("trans_stream", Ns))
+    return ((te["c_lds"], te["a_lds"], te["w_lds"], te["lds"]), (le["an_lds"], le["c_lds"], le["a_lds"], le["w_lds"], le["lds"]),
+            (lp["an_lds"], lp["a_lds"], lp["w_lds"], lp["lds"]), (ts["a_lds"], ts["lt_lds"], ts["lds"]))
+
+
+def test_every_row_of_the_grammar_shapes_reaches_the_layouts_and_bytes_its_comment_names():
+    assert list(cases.GRAMMAR_SHAPES) == list(GRAMMAR_ROUTES)
+    assert list(cases.GRAMMAR_SHAPES)[:7] == list(cases.TRANS_POSTERIORS_SHAPES)
+    for name, (Ns, M, T) in cases.GRAMMAR_SHAPES.items():
+        assert _grammar_routes(name) == GRAMMAR_ROUTES[name], (name, _grammar_routes(name))
+        assert max(r[-1] for r in GRAMMAR_ROUTES[name]) <= cases.SEG_LDS_BYTES
+        assert cases.slots_of(Ns) <= cases.SEG_MAX_WAVES and sum(Ns) <= cases.SEG_MAX_SUM_N and 66 <= T <= cases.TRANS_POSTERIORS_T
+        if name in cases.TRANS_POSTERIORS_SHAPES:  # the same models, stream and prices as the posteriors' row
+            assert (Ns, M) == cases.TRANS_POSTERIORS_SHAPES[name] and T == cases.TRANS_POSTERIORS_T
+        else:
+            assert M == 64
+        assert cases.route("loop_estep", Ns, gram=False)["c_lds"] is None
+    # the cap exactly: no launch of the project asks for more dynamic LDS than "1x71" in k_hmm_trans_estep<true, true>
+    assert GRAMMAR_ROUTES["1x71"][0][3] == cases.SEG_LDS_BYTES == 160 * 1024
+    assert cases.trans_estep_lds_bytes(72, 72, 72, True, True, True) > cases.SEG_LDS_BYTES  # (one class more and w leaves LDS)
+    # (the largest launches of the kernels' own GPU files, at "21_22_64", stay below the opt-in)
+    assert cases.route("trans_estep", [21, 22, 64])["lds"] == 42304 and cases.route("trans_stream", [21, 22, 64])["lds"] == 40288
+    assert cases.route("loop_estep", [21, 22, 64])["lds"] > cases.LDS_OPT_IN and cases.route("loop_estep", [21, 22, 64])["a_lds"]
+
+
+def test_the_grammar_shapes_reach_every_instantiation_route_and_the_opt_in_where_one_can_be():
+    big = lambda lds: lds > cases.LDS_OPT_IN
+    te = {(r[0][1], r[0][2], r[0][0], big(r[0][3])) for r in GRAMMAR_ROUTES.values()}  # (A_LDS, W_LDS, c_lds, above 64 KB)
+    # k_hmm_trans_estep<A_LDS, W_LDS>: all four, each with the C table in LDS above 64 KB ...
+    assert {(a, w, True, True) for a in (T_, F_) for w in (T_, F_)} <= te
+    # ... and with the table in global memory: <true, false> above 64 KB, <false, false> below it (partials, S / R and pi
+    # alone stay below the opt-in); W in LDS next to a global table the rule cannot produce (C goes in first and is as large)
+    assert (T_, F_, F_, True) in te and (F_, F_, F_, False) in te and not any(w and not c for _a, w, c, _b in te)
+    assert cases.trans_estep_lds_bytes(1024, cases.SEG_MAX_SUM_N, 0, False, False, False) < cases.LDS_OPT_IN
+    # (the forced route the GPU file adds at "64x3" and "1x80": <true, true> with the table in global memory, at "1x80" w
+    # takes the room the table leaves)
+    for name, want in (("64x3", (F_, T_, T_, 101824)), ("1x80", (F_, T_, T_, 105216))):
+        r = cases.route("trans_estep", cases.GRAMMAR_SHAPES[name][0], c=False)
+        assert (r["c_lds"], r["a_lds"], r["w_lds"], r["lds"]) == want, (name, r)
+    r = cases.route("trans_estep", cases.GRAMMAR_SHAPES["40_1x24_x6"][0], c=True)  # forced into LDS: refused by the host
+    assert r["lds"] == 365728 > cases.SEG_LDS_BYTES
+    # k_hmm_loop_estep<A_LDS, W_LDS, GRAM>: all eight, and every (an, c) the rule can produce, each above 64 KB but <f, f, *>
+    # without a table in LDS
+    le = {(r[1][2], r[1][3], True, big(r[1][4])) for r in GRAMMAR_ROUTES.values()}
+    le |= {(r[2][1], r[2][2], False, big(r[2][3])) for r in GRAMMAR_ROUTES.values()}
+    assert {(a, w, g, True) for a in (T_, F_) for w in (T_, F_) for g in (T_, F_)} <= le
+    anc = {(r[1][0], r[1][1], big(r[1][4])) for r in GRAMMAR_ROUTES.values()}
+    assert {(an, c, True) for an in (T_, F_) for c in (T_, F_)} <= anc
+    assert GRAMMAR_ROUTES["64x2"][1][:4] == (T_, T_, F_, T_)  # the AN table in LDS (leading dimension N | 1) while A is global
+    assert {(r[1][0], r[1][2]) for r in GRAMMAR_ROUTES.values()} == {(a, b) for a in (T_, F_) for b in (T_, F_)}
+    # C in LDS with w global, and C global with w global, in both trainers
+    assert any(r[0][0] and not r[0][2] for r in GRAMMAR_ROUTES.values()) and any(r[1][1] and not r[1][3] for r in GRAMMAR_ROUTES.values())
+    # k_hmm_segment_trans_stream<A_LDS, LT_LDS>: all four, three of them above 64 KB (<false, false> holds E of two steps alone)
+    ts = {(r[3][0], r[3][1], big(r[3][2])) for r in GRAMMAR_ROUTES.values()}
+    assert {(T_, T_, True), (F_, T_, True), (T_, F_, True), (F_, F_, False)} <= ts
+    assert cases.trans_stream_lds_bytes(4096, 0, False, False) == cases.LDS_OPT_IN  # (not above it)
+    # the forced routes of the loop E-step at "64x2": each changes the layout
+    Ns = cases.GRAMMAR_SHAPES["64x2"][0]
+    free, an_g, c_g = cases.route("loop_estep", Ns), cases.route("loop_estep", Ns, an=False), cases.route("loop_estep", Ns, c=False)
+    pick = lambda r: (r["an_lds"], r["c_lds"], r["a_lds"], r["w_lds"], r["lds"])
+    assert pick(free) == (T_, T_, F_, T_, 134560) and pick(an_g) == (F_, T_, T_, T_, 68000) and pick(c_g) == (T_, F_, F_, T_, 134496)
+
+
+def test_the_event_sets_of_the_grammar_trainers_and_the_status_of_every_event_stream():
+    assert cases.GRAMMAR_EVENT_SETS == cases.TRANS_POSTERIORS_EVENT_SETS + ("64x2",)
+    want = {"5_3_4": ((T_, T_, T_), (T_, T_, T_, T_)), "64x6": ((T_, F_, T_), (F_, T_, F_, T_)), "64x3": ((T_, T_, T_), (F_, T_, T_, T_)),
+            "40_1x24_x14": ((F_, F_, F_), (F_, F_, F_, F_)), "64x2": ((T_, T_, T_), (T_, T_, F_, T_))}
+    for name in cases.GRAMMAR_EVENT_SETS:
+        Ns = [len(m[0]) for m in cases.event_models(name)]
+        assert Ns == list(cases.EVENT_NS[name])
+        te, le = cases.route("trans_estep", Ns), cases.route("loop_estep", Ns)
+        assert ((te["c_lds"], te["a_lds"], te["w_lds"]), (le["an_lds"], le["c_lds"], le["a_lds"], le["w_lds"])) == want[name], (name, te, le)
+    # the first event in frame order decides, as for the posteriors: from the restatements, on the smallest set
+    streams, kinds = cases.event_batch()
+    models = cases.event_models("5_3_4")
+    lt = cases.event_prices(len(models))
+    sym = np.concatenate(streams)
+    offs = np.arange(len(streams) + 1, dtype=np.int64) * cases.EVENT_T
+    status = [cases.event_status(k, "trans_posteriors") for k in kinds]
+    assert status == [0] + [2] * 6 + [1] * 6 + [1, 2] * 3
+    te = RTE.estep(models, sym, offs, lt)
+    le = RLE.estep(models, sym, offs, lt, acc_trans=True)
+    S = len(streams)
+    for got in (te, le):
+        assert got["status"].tolist() == status
+        assert np.isfinite(got["log_prob"][0]) and (got["log_prob"][1:] == NINF).all()
+    assert te["acc"][-2:].tolist() == [1, S - 1] == le["acc_trans"][-2:].tolist() and np.array_equal(te["acc"], le["acc_trans"])
+    for (pi, _A, B), acc in zip(models, le["acc"]):
+        lay = RLE.layout(len(pi), B.shape[1])
+        assert (acc[lay["used"]], acc[lay["skipped"]]) == (1, S - 1)
+    # a failed stream adds nothing: the limbs are the clean stream's alone
+    alone = RLE.estep(models, streams[0], [0, cases.EVENT_T], lt, acc_trans=True)
+    assert np.array_equal(alone["acc_trans"][:-2], le["acc_trans"][:-2]) and alone["acc_trans"][:-2].any()
+    for (pi, _A, B), a, b in zip(models, alone["acc"], le["acc"]):
+        used = RLE.layout(len(pi), B.shape[1])["used"]
+        assert np.array_equal(a[:used], b[:used]) and a[:used].any()
+
+
+@pytest.mark.parametrize("name", list(cases.GRAMMAR_SHAPES))
+def test_the_grammar_session_restatement_delivers_frames_before_close_at_every_row(name):
+    # (a GPU session test would else pass with every frame decided at close, the coalescence never having found a frame)
+    _Ns, _M, T = cases.GRAMMAR_SHAPES[name]
+    B = cases.SESSION_B
+    rest, final_after = cases.trans_stream_reference(name)
+    blocks = [final_after[p] for p in range(B, T + 1, B)]
+    print(name, "final after each whole block:", blocks, "segments", sum(rest.entered), "classes", len(set(rest.cls)))
+    assert rest.status == 0 and rest.join_failures == 0 and len(rest.cls) == T and len(blocks) == T // B >= 1
+    assert 2 * sum(f > 0 for f in blocks) >= len(blocks)
+    assert all(f <= p for f, p in zip(blocks, range(B, T + 1, B))) and blocks == sorted(blocks) and blocks[-1] > 0
+    # the session is the one-shot decode of the restatement
+    models, stream, lt = cases.grammar_shape(name)
+    want = RT.segment_trans(models, stream, [0, T], lt)
+    assert rest.cls == want["cls"].tolist() and rest.state == want["state"].tolist() and rest.entered == want["entered"].tolist()
+    assert np.array_equal(_bits(np.array(rest.exit_score)), _bits(want["exit_score"]))
+    assert _bits(rest.log_prob)[0] == _bits(want["log_prob"])[0] and want["entered"].sum() >= 8
 
 
 # ---- what makes a row worth running ----------------------------------------------------------------------------------------------
