@@ -178,7 +178,11 @@ int scan_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, 
         i64 cap = (i64)e2hmm::scan_waves() * G * rounds;
         // (a window longer than the staging area is read from global memory; shorter ones: as many as fit)
         if (window <= e2hmm::SCAN_SPAN_CAP) cap = std::min<i64>(cap, (e2hmm::SCAN_SPAN_CAP - window) / hop + 1);
-        const i64 span = (std::min<i64>(cap, W) - 1) * hop + window;
+        // the longest span among the runs this launch makes: a run lies in one stream, so (count - 1) hop + window is at most
+        // that stream's length, whatever the hop
+        i64 span = 0;
+        for (int s = 0; s < S; ++s)
+            if (const i64 n = win_offs[(size_t)s + 1] - win_offs[(size_t)s]) span = std::max(span, (std::min(cap, n) - 1) * hop + window);
         Launch l{N, G, (int)(span <= e2hmm::SCAN_SPAN_CAP ? span : 0), (int)ks.size(), (int)kv.second.size(), (int)runs.size(), 0};
         ks.insert(ks.end(), kv.second.begin(), kv.second.end());
         make_runs(cap, runs);
@@ -205,13 +209,16 @@ int scan_device(const std::vector<const Hmm*>& ms, const unsigned short* d_sym, 
     if (timer.create()) return 1;
     HIPCHK(hipEventRecord(timer.start.e, st));
     for (const Launch& l : launches) {
-        e2hmm::launch_scan(dm.table.get(), d_ks.get() + l.ks_at, l.nk, K, l.N, l.G, d_wins.get(), d_runs.get() + l.runs_at, l.nruns,
-                           l.span_lds, d_sym, d_offs.get(), sc.d_mant.get(), sc.d_exp.get(), sc.d_status.get(), st);
+        if (e2hmm::launch_scan(dm.table.get(), d_ks.get() + l.ks_at, l.nk, K, l.N, l.G, d_wins.get(), d_runs.get() + l.runs_at, l.nruns,
+                               l.span_lds, d_sym, d_offs.get(), sc.d_mant.get(), sc.d_exp.get(), sc.d_status.get(), st))
+            return e2vq_set_error("hmm scan: %d runs of N=%d, G=%d over a staged span of %d symbols cannot be launched", l.nruns, l.N,
+                                  l.G, l.span_lds);
         HIPCHK(hipGetLastError());
     }
     if (!big.empty()) {
-        e2hmm::launch_scan_wg(dm.table.get(), d_ks.get() + big_at, (int)big.size(), K, big_N, d_wins.get(), W, d_sym, d_offs.get(),
-                              sc.d_mant.get(), sc.d_exp.get(), sc.d_status.get(), st);
+        if (e2hmm::launch_scan_wg(dm.table.get(), d_ks.get() + big_at, (int)big.size(), K, big_N, d_wins.get(), W, d_sym, d_offs.get(),
+                                  sc.d_mant.get(), sc.d_exp.get(), sc.d_status.get(), st))
+            return e2vq_set_error("hmm scan: %lld windows under models of up to %d states cannot be launched", (long long)W, big_N);
         HIPCHK(hipGetLastError());
     }
     e2hmm::launch_scan_top2(sc.d_mant.get(), sc.d_exp.get(), sc.d_status.get(), W, K, d_top.get(), d_tmant.get(), d_texp.get(), st);

@@ -59,12 +59,13 @@ int scan_waves();                    // waves of a k_hmm_scan workgroup: each ta
 // Scores every window of the runs under the nk models models[ks[0 .. nk)] of ONE N <= WAVE_N, G windows to a wave
 // (1 <= G <= floor(64 / N)); results at [w * K + k] as launch_score's.  span_lds <= SCAN_SPAN_CAP: the longest span among the
 // runs, all of which are staged; 0: none is (the symbols are read from global memory).  offs: the streams' S + 1 symbol offsets.
-void launch_scan(const ModelDev* models, const int* ks, int nk, int K, int N, int G, const ScanWin* wins, const ScanRun* runs,
-                 int nruns, int span_lds, const unsigned short* sym, const long long* offs, double* mant, long long* exp2,
-                 int* status, hipStream_t st);
+// Returns 1, having launched nothing, when the arguments are outside these bounds.
+int launch_scan(const ModelDev* models, const int* ks, int nk, int K, int N, int G, const ScanWin* wins, const ScanRun* runs,
+                int nruns, int span_lds, const unsigned short* sym, const long long* offs, double* mant, long long* exp2,
+                int* status, hipStream_t st);
 // the same for models of more than WAVE_N states (maxN: the largest among them): a workgroup per (window, model)
-void launch_scan_wg(const ModelDev* models, const int* ks, int nk, int K, int maxN, const ScanWin* wins, long long W,
-                    const unsigned short* sym, const long long* offs, double* mant, long long* exp2, int* status, hipStream_t st);
+int launch_scan_wg(const ModelDev* models, const int* ks, int nk, int K, int maxN, const ScanWin* wins, long long W,
+                   const unsigned short* sym, const long long* offs, double* mant, long long* exp2, int* status, hipStream_t st);
 // best and second-best model of each of the W windows from the W x K results: top[2 w], top[2 w + 1] (second -1 when K = 1),
 // their P at tmant / texp[2 w], [2 w + 1] (0, 0 where the status is not 0); ties as `hmm classify` ranks them
 void launch_scan_top2(const double* mant, const long long* exp2, const int* status, long long W, int K, int* top, double* tmant,

@@ -228,11 +228,12 @@ __global__ void k_scan_top2(const double* __restrict__ mant, const i64* __restri
 // ---- launchers ------------------------------------------------------------------------------------------------
 int scan_waves() { return SCAN_WAVES; }
 
-void launch_scan(const ModelDev* models, const int* ks, int nk, int K, int N, int G, const ScanWin* wins, const ScanRun* runs,
-                 int nruns, int span_lds, const unsigned short* sym, const i64* offs, double* mant, i64* exp2, int* status,
-                 hipStream_t st)
+// (1: the arguments name no launch this file can make, and nothing was launched)
+int launch_scan(const ModelDev* models, const int* ks, int nk, int K, int N, int G, const ScanWin* wins, const ScanRun* runs,
+                int nruns, int span_lds, const unsigned short* sym, const i64* offs, double* mant, i64* exp2, int* status,
+                hipStream_t st)
 {
-    if (nruns < 1 || nk < 1 || N < 1 || N > WAVE_N || G < 1 || G * N > WAVE_N || span_lds < 0 || span_lds > SCAN_SPAN_CAP) return;
+    if (nruns < 1 || nk < 1 || N < 1 || N > WAVE_N || G < 1 || G * N > WAVE_N || span_lds < 0 || span_lds > SCAN_SPAN_CAP) return 1;
     const size_t lds = (size_t)N * G * N * 8 + (size_t)span_lds * 2;
     // grid.y carries the models: at most 65535 per launch, more in further launches
     for (int k0 = 0; k0 < nk; k0 += 65535) {
@@ -244,12 +245,13 @@ void launch_scan(const ModelDev* models, const int* ks, int nk, int K, int N, in
             hipLaunchKernelGGL(k_hmm_scan<false>, dim3((unsigned)nruns, (unsigned)kn), dim3(64 * SCAN_WAVES), lds, st, models, ks + k0, K,
                                N, G, wins, runs, sym, offs, span_lds, mant, exp2, status);
     }
+    return 0;
 }
 
-void launch_scan_wg(const ModelDev* models, const int* ks, int nk, int K, int maxN, const ScanWin* wins, long long W,
-                    const unsigned short* sym, const i64* offs, double* mant, i64* exp2, int* status, hipStream_t st)
+int launch_scan_wg(const ModelDev* models, const int* ks, int nk, int K, int maxN, const ScanWin* wins, long long W,
+                   const unsigned short* sym, const i64* offs, double* mant, i64* exp2, int* status, hipStream_t st)
 {
-    if (W < 1 || nk < 1 || maxN < 1 || maxN > MAX_N) return;
+    if (W < 1 || nk < 1 || maxN < 1 || maxN > MAX_N) return 1;
     for (int k0 = 0; k0 < nk; k0 += 65535) {
         const int kn = nk - k0 < 65535 ? nk - k0 : 65535;
         for (i64 w0 = 0; w0 < W; w0 += 1 << 20) {
@@ -258,6 +260,7 @@ void launch_scan_wg(const ModelDev* models, const int* ks, int nk, int K, int ma
                                (size_t)2 * maxN * 8, st, models, ks + k0, K, wins, (int)w0, sym, offs, mant, exp2, status);
         }
     }
+    return 0;
 }
 
 void launch_scan_top2(const double* mant, const i64* exp2, const int* status, long long W, int K, int* top, double* tmant,

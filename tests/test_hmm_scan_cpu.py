@@ -2,7 +2,10 @@
 before any HIP call (so they answer the same with or without a device) and write no file; the window arithmetic; the CSV
 and stdout block of e2vq_hmm_scan_report on a hand-made result; the usage text names the command; k_hmm_scan,
 k_hmm_scan_wg and k_scan_top2 are in the gfx950 build without scratch or spilled registers.  The GPU parity tests are in
-test_gpu_hmm_scan.py."""
+test_gpu_hmm_scan.py.  For test_gpu_hmm_scan_shapes.py: the restated plan of scan_device (tests/hmm_scan_cases.py) against
+the sources, the cap, span, runs and bytes of every row of SCAN_SHAPES, that every launch stages all its longest run covers
+(which the earlier span formula does not at hops near 2^63), and on the oracle alone which windows of the event cases get
+which status."""
 import ctypes as C
 import os
 import re
@@ -14,7 +17,9 @@ import pytest
 import ecoz2rs_amd as e
 from ecoz2rs_amd import hmm
 
+from . import hmm_scan_cases as cases
 from . import lpc_wavs
+from . import oracle_lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ecoz2rs_amd", "csrc")
@@ -289,3 +294,186 @@ def test_scan_kernel_reads_across_lanes_and_from_lds(asm):
 def test_scan_library_exports():
     for name in ("e2vq_hmm_scan", "e2vq_hmm_scan_files", "e2vq_hmm_scan_windows", "e2vq_hmm_scan_report", "e2vq_hmm_scan_last_kernel_ms"):
         assert hasattr(e.lib, name)
+
+
+# ---- the plan of scan_device, restated (tests/hmm_scan_cases.py), against the sources ----------------------------------------
+def _source(name):
+    return open(os.path.join(CSRC, name)).read()
+
+
+def test_the_restated_constants_and_formulas_are_the_sources():
+    dev, hip, host = _source("hmm_device.h"), _source("hmm_scan.hip"), _source("hmm_decode.cpp")
+    const = lambda text, name: int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text).group(1))
+    assert cases.SCAN_SPAN_CAP == const(dev, "SCAN_SPAN_CAP") and cases.SCAN_WAVES == const(hip, "SCAN_WAVES")
+    assert cases.SCAN_PACK_MAX_N == const(host, "SCAN_PACK_MAX_N") and cases.WAVE_N == 64
+    assert "int scan_waves() { return SCAN_WAVES; }" in hip and "__launch_bounds__(64 * SCAN_WAVES)" in hip
+    # the pack width and the rounds, default and clamp
+    assert 'if (v && *v) return atoi(v) == 0 || N > 32 ? 1 : e2hmm::WAVE_N / N;' in host
+    assert "return N <= SCAN_PACK_MAX_N ? e2hmm::WAVE_N / N : 1;" in host
+    assert 'const int r = e2vq_env_int("ECOZ2_HMM_SCAN_ROUNDS", %d);' % cases.SCAN_ROUNDS_DEFAULT in host
+    assert "return r < 1 ? 1 : (r > %d ? %d : r);" % (cases.SCAN_ROUNDS_MAX, cases.SCAN_ROUNDS_MAX) in host
+    assert [cases.scan_rounds(r) for r in (None, "0", "1", "3", "64", "1000", "-5")] == [4, 1, 1, 3, 64, 64, 1]
+    assert [cases.scan_pack_width_in_use(N) for N in (1, 3, 21, 22, 32, 33, 64)] == [64, 21, 3, 1, 1, 1, 1]
+    assert [cases.scan_pack_width_in_use(N, "1") for N in (1, 3, 21, 22, 32, 33, 64)] == [64, 21, 3, 2, 2, 1, 1]
+    assert [cases.scan_pack_width_in_use(N, "0") for N in (1, 21, 22, 64)] == [1, 1, 1, 1] and cases.scan_pack_width_in_use(22, "") == 1
+    # the cap, the runs, and the span of a launch from the runs it makes (no product of the hop with a count across streams)
+    assert "i64 cap = (i64)e2hmm::scan_waves() * G * rounds;" in host
+    assert "if (window <= e2hmm::SCAN_SPAN_CAP) cap = std::min<i64>(cap, (e2hmm::SCAN_SPAN_CAP - window) / hop + 1);" in host
+    assert "runs.push_back(e2hmm::ScanRun{(int)w, (int)std::min<i64>(cap, win_offs[(size_t)s + 1] - w)});" in host
+    assert "for (i64 w = win_offs[(size_t)s]; w < win_offs[(size_t)s + 1]; w += cap)" in host
+    assert "span = std::max(span, (std::min(cap, n) - 1) * hop + window);" in host
+    assert "(int)(span <= e2hmm::SCAN_SPAN_CAP ? span : 0)" in host
+    assert "std::min<i64>(cap, W)" not in host
+    # the launchers: the bytes, the limits of a launch, and a refusal the caller sees
+    assert "const size_t lds = (size_t)N * G * N * 8 + (size_t)span_lds * 2;" in hip
+    assert "span_lds < 0 || span_lds > SCAN_SPAN_CAP) return 1;" in hip
+    assert hip.count("k0 += %d)" % cases.MODELS_PER_LAUNCH) == 2 and cases.WG_WINDOWS_PER_LAUNCH == 1 << 20
+    assert "for (i64 w0 = 0; w0 < W; w0 += 1 << 20) {" in hip and "W - w0 < (1 << 20) ? W - w0 : (1 << 20)" in hip
+    for text in (dev, hip):
+        assert re.search(r"\bint launch_scan\(", text) and re.search(r"\bint launch_scan_wg\(", text)
+        assert not re.search(r"\bvoid launch_scan(_wg)?\(", text)
+    assert "if (e2hmm::launch_scan(" in host and "if (e2hmm::launch_scan_wg(" in host
+
+
+def _plan(name, hop=None, **kw):
+    Ns, _M, lens, L, hops = cases.SCAN_SHAPES[name]
+    return cases.scan_plan(Ns, lens, L, hops[0] if hop is None else hop, **kw)
+
+
+def test_every_row_of_the_scan_shapes_shows_the_plan_its_comment_names():
+    assert list(cases.SCAN_SHAPES) == ["L8192", "L8191", "L8193", "L4000_H1000", "rounds_N1", "rounds_N21_N64", "many_windows",
+                                       "huge_hop_long", "huge_hop_short"]
+    pick = lambda p, N, *keys: tuple(p["launches"][N][k] for k in keys)
+    # a window of exactly the staging area: one window a run, and the kernel's largest launch at N = 64
+    p = _plan("L8192")
+    assert p["counts"] == [0, 1, 0, 2]
+    for N in (5, 64):
+        assert pick(p, N, "cap", "span_lds", "runs") == (1, 8192, [[1], [1, 1]])
+    assert p["launches"][64]["lds"] == 49152 == 64 * 64 * 8 + 2 * 8192
+    # two windows whose span is exactly 8192, then the one left over
+    p = _plan("L8191")
+    for N in (21, 64):
+        assert pick(p, N, "cap", "span_lds", "runs") == (2, 8192, [[2, 1]])
+    assert (2 - 1) * 1 + 8191 == cases.SCAN_SPAN_CAP
+    # one symbol more than the staging area holds: k_hmm_scan<false>, 8 + 1 windows behind a non-zero stream base
+    for pack, G22 in ((None, 1), ("0", 1), ("1", 2)):
+        p = _plan("L8193", pack=pack)
+        assert p["counts"] == [0, 8, 1] and p["launches"][22]["G"] == G22 and p["launches"][64]["G"] == 1
+        assert all(not l["staged"] and l["span_lds"] == 0 and l["runs"] == [[8], [1]] for l in p["launches"].values())
+    # the span rule, not waves x G x rounds, cuts the runs at every N
+    for pack in cases.PACKS:
+        p = _plan("L4000_H1000", pack=pack)
+        assert p["counts"] == [0, 13, 6]
+        for N in (5, 16, 64):
+            assert pick(p, N, "cap", "span_lds", "runs") == (5, 8000, [[5, 5, 3], [5, 1]])
+            assert cases.SCAN_WAVES * p["launches"][N]["G"] * 4 > 5
+    # the rounds
+    l = _plan("rounds_N1", rounds=64)["launches"][1]
+    assert (l["G"], l["cap"], l["runs"], l["span_lds"]) == (64, 8156, [[8156, 808]], 8192) and 4 * 64 * 64 == 16384 > 8156
+    l = _plan("rounds_N1", rounds=1)["launches"][1]
+    assert (l["cap"], len(l["runs"][0]), l["runs"][0][-1]) == (256, 36, 4)
+    assert _plan("rounds_N1", rounds=1000) == _plan("rounds_N1", rounds=64) and _plan("rounds_N1", rounds=0) == _plan("rounds_N1", rounds=1)
+    p = _plan("rounds_N21_N64", rounds=64)
+    assert pick(p, 21, "G", "cap", "runs") == (3, 768, [[768, 696]]) and pick(p, 64, "G", "cap", "runs") == (1, 256, [[256] * 5 + [184]])
+    assert 768 // (cases.SCAN_WAVES * 3) == 64 == 256 // cases.SCAN_WAVES  # a wave takes 64 turns
+    # a second launch of k_hmm_scan_wg, of 4 windows
+    p = _plan("many_windows")
+    assert p["W"] == (1 << 20) + 4 and p["big"] == [1] and p["wg_launches"] == 2 and p["W"] - cases.WG_WINDOWS_PER_LAUNCH == 4
+    assert pick(p, 3, "G", "cap") == (21, 336) and len(p["launches"][3]["runs"][0]) == 3121
+    # (the other figures of DESIGN.md 4.8.5's table, at the default pack width and rounds)
+    assert _plan("L8192")["launches"][5]["lds"] == 18784 and pick(_plan("L8191"), 21, "G", "lds") == (3, 26968)
+    assert [_plan("L8193")["launches"][N]["cap"] for N in (64, 22, 5)] == [16, 16, 192] and _plan("L8193", pack="1")["launches"][22]["cap"] == 32
+    l = _plan("rounds_N1")["launches"][1]
+    assert (l["cap"], len(l["runs"][0]), l["span_lds"]) == (1024, 9, 1060)
+    assert [_plan("rounds_N21_N64")["launches"][N]["cap"] for N in (21, 64)] == [48, 16]
+    # one window a stream at every huge hop, whatever the hop.  (At hop 8 the 150-symbol stream of huge_hop_short has seven
+    # windows, not one: nine in all, a staged span of 148; windows 0, 1 and 8 of them are the three of the larger hops.)
+    for hop in cases.HUGE_HOPS:
+        for pack in cases.PACKS:
+            p = _plan("huge_hop_long", hop, pack=pack)
+            assert p["counts"] == [1, 1, 1] and all(l["span_lds"] == 0 and l["runs"] == [[1]] * 3 for l in p["launches"].values())
+            p = _plan("huge_hop_short", hop, pack=pack)
+            want = ([1, 7, 1], 148, [[1], [7], [1]]) if hop == 8 else ([1, 1, 1], 100, [[1]] * 3)
+            assert p["counts"] == want[0] and all((l["span_lds"], l["runs"]) == want[1:] for l in p["launches"].values())
+
+
+def _span_faults(formula):
+    """(row, hop, pack, N) at which a launch is refused, or stages fewer symbols than its longest run covers"""
+    bad = []
+    for name, (Ns, _M, lens, L, hops) in cases.SCAN_SHAPES.items():
+        for hop in hops:
+            for pack in cases.PACKS:
+                p = cases.scan_plan(Ns, lens, L, hop, pack=pack, formula=formula)
+                true = cases.longest_true_span(p, L, hop)
+                for N, l in p["launches"].items():
+                    ok = 0 <= l["span_lds"] <= cases.SCAN_SPAN_CAP and not l["refused"]
+                    if not ok or (l["span_lds"] != 0 and l["span_lds"] < true[N]):
+                        bad.append((name, hop, pack, N))
+                    if ok and l["span_lds"] == 0:  # read from global memory only where the longest run cannot be staged
+                        assert true[N] > cases.SCAN_SPAN_CAP or formula == "parent", (name, hop, pack, N)
+                    assert not ok or l["lds"] <= 49152
+    return bad
+
+
+def test_every_launch_stages_all_its_longest_run_covers():
+    assert _span_faults("runs") == []
+    # the record of the defect: (min(cap, W) - 1) hop + window wraps where W counts windows of several streams
+    bad = _span_faults("parent")
+    assert sorted(set((name, hop) for name, hop, _pack, _N in bad)) == [("huge_hop_long", 1 << 62), ("huge_hop_long", (1 << 63) - 1)]
+    Ns, _M, lens, L, _hops = cases.SCAN_SHAPES["huge_hop_long"]
+    l = cases.scan_plan(Ns, lens, L, 1 << 62, formula="parent")["launches"][64]
+    assert l["span_lds"] == 8193 and l["refused"]                       # launch_scan returned without a launch
+    l = cases.scan_plan(Ns, lens, L, (1 << 63) - 1, formula="parent")["launches"][64]
+    assert l["span_lds"] == 8191 < L and l["staged"] and not l["refused"]  # staged, two symbols short of the window
+    l = cases.scan_plan([5], [9000, 9000], 9000, (1 << 63) - 1, formula="parent")["launches"][5]
+    assert l["span_lds"] == 8999 and l["refused"]
+    assert not cases.scan_plan([5], [9000, 9000], 9000, (1 << 63) - 1)["launches"][5]["refused"]
+
+
+# ---- the reference and the event cases, on the oracle alone ------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def H():
+    return oracle_lib.load_hmm()
+
+
+def test_many_windows_has_all_16_pairs_and_costs_16_oracle_calls_a_model(H):
+    models, streams, L, _hops = cases.scan_shape("many_windows")
+    s = streams[0]
+    assert (L, len(s)) == (2, (1 << 20) + 5) and s[:5].tolist() == [3, 3, 1, 0, 2] and s[-5:].tolist() == [0, 1, 3, 2, 0]
+    pairs = lambda x: set(zip(x[:-1].tolist(), x[1:].tolist()))
+    assert len(pairs(s[:5]) | pairs(s[-5:])) == 8 and len(pairs(s)) == 16
+    ref = cases.shape_reference(H, "many_windows", 1)
+    assert ref["oracle_calls"] == 16 * len(models) and ref["mant"].shape == (len(s) - 1, 2) and (ref["status"] == 0).all()
+    for w in (0, 1, 2, 3, len(s) - 5, len(s) - 2, 77777):  # the expansion by keys puts each window's own result in its row
+        for k, (pi, A, B) in enumerate(models):
+            assert (ref["status"][w, k], ref["mant"][w, k], ref["exp2"][w, k]) == H.forward(pi, A, B, s[w:w + 2])
+
+
+def test_the_rank_of_the_reference_is_the_top2_contract():
+    st = np.array([[0, 0, 0], [0, 1, 0], [2, 1, 1], [0, 0, 0], [1, 0, 2]], np.int32)
+    ex = np.array([[-3, -3, -4], [-9, 7, -9], [5, 6, 7], [-3, -2, -3], [0, -50, 0]], np.int64)
+    ma = np.array([[.5, .5, .9], [.75, .9, .75], [.6, .7, .8], [.9, .5, .95], [.0, .5, .0]])
+    best, second = cases.rank(st, ex, ma)
+    # equal P: the later model first; P = 0 (any status but 0) below every P > 0, and equal among themselves
+    assert best.tolist() == [1, 2, 2, 1, 1] and second.tolist() == [0, 0, 1, 2, 2]
+    assert cases.rank(st[:, :1], ex[:, :1], ma[:, :1])[1].tolist() == [-1] * 5
+
+
+@pytest.mark.parametrize("kind", cases.EVENT_KINDS)
+@pytest.mark.parametrize("staged", [True, False])
+def test_the_event_cases_put_each_status_at_both_ends_of_a_window(H, kind, staged):
+    models, clean, dirty, L, hop = cases.events_case(kind) if staged else cases.unstaged_events_case(kind)
+    at = cases.EVENT_AT if staged else cases.UNSTAGED_EVENT_AT
+    assert all((s < cases.EVENT_M).all() for s in clean)
+    assert kind == "outside" or all((s != cases.EVENT_DEAD).all() for s in clean)  # (no symbol but the planted ones is dead)
+    assert [np.flatnonzero(d != c).tolist() for c, d in zip(clean, dirty)][1] == list(at)
+    hit = cases.hits([len(s) for s in dirty], L, hop, 1, at)
+    ts = {t for h in hit for t in h}
+    assert {0, L - 1} <= ts and (ts == set(range(L)) if staged else ts == {0, 1, 2, 3, L - 1})
+    ref = cases.reference(H, models, dirty, L, hop)
+    want = np.array([cases.EVENT_STATUS[kind] if h else 0 for h in hit])
+    assert (ref["status"] == want[:, None]).all() and (want == 0).sum() >= 4 and (want != 0).sum() >= 5
+    assert np.isneginf(ref["log_prob"][want != 0]).all() and np.isfinite(ref["log_prob"][want == 0]).all()
+    assert not ref["mant"][want != 0].any() and not ref["exp2"][want != 0].any()
+    plan = cases.scan_plan([len(m[0]) for m in models], [len(s) for s in dirty], L, hop)
+    assert all(l["staged"] == staged for l in plan["launches"].values()) and (plan["big"] == [3]) == staged
