@@ -82,6 +82,7 @@ static int usage()
             "                  [--class-transitions <file.csv>]\n"
             "                  [--grammar-posteriors [--frame-posteriors <dir>]]\n"
             "                  [--continuous <name>]\n"
+            "                  [--grammar-body <auto|resident|looped>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
             "                  --posteriors adds each segment's mean and least class posterior, and the per-frame table)\n"
@@ -91,9 +92,13 @@ static int usage()
             "                  (--grammar-posteriors, with --class-transitions: the posteriors under those prices, reported as\n"
             "                  --posteriors reports them)\n"
             "                  (--continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream)\n"
+            "                  (--grammar-body, with --class-transitions: the kernel body of the decoder under the prices -- resident\n"
+            "                  takes at most 16 wave-slots of classes, looped any number, auto the looped one above 16; the same path\n"
+            "                  bit for bit; not with --grammar-posteriors)\n"
             "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  --switch-penalty <x <= 0 | -inf> --class-transitions <file.csv> --grammar-continuous <name>\n"
             "                  [-c <csv dir|file.csv>]\n"
+            "                  [--grammar-body <auto|resident|looped>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (--grammar-continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream\n"
             "                  under the prices of --class-transitions)\n"
@@ -878,7 +883,8 @@ static int hmm_segment_cmd(int argc, char** argv)
     bool continuous = false;
     bool grammar = false;  // --grammar-posteriors
     bool grammar_continuous = false;
-    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, body;
+    bool have_grammar_body = false;
+    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, body, grammar_body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -902,6 +908,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "--posteriors") posteriors = true;
         else if (a == "--grammar-posteriors") grammar = true;
         else if (a == "--body") body = val("--body");
+        else if (a == "--grammar-body") { grammar_body = val("--grammar-body"); have_grammar_body = true; }
         else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
         else if (a == "--grammar-continuous") { grammar_name = val("--grammar-continuous"); grammar_continuous = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
@@ -929,6 +936,22 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    if (have_grammar_body) {  // the body of the decoder under the prices (ECOZ2_HMM_SEGMENT_TRANS_BODY), set in this process before the call
+        if (transitions.empty()) {
+            fprintf(stderr, "hmm segment: --grammar-body <auto|resident|looped> needs --class-transitions <file.csv> (it chooses the body of "
+                            "the decoder under its prices)\n");
+            return 2;
+        }
+        if (grammar) {
+            fprintf(stderr, "hmm segment: --grammar-posteriors has the resident body only: not with --grammar-body\n");
+            return 2;
+        }
+        if (grammar_body != "auto" && grammar_body != "resident" && grammar_body != "looped") {
+            fprintf(stderr, "hmm segment --class-transitions: --grammar-body %s: auto, resident or looped\n", grammar_body.c_str());
+            return 2;
+        }
+        setenv("ECOZ2_HMM_SEGMENT_TRANS_BODY", grammar_body.c_str(), 1);
+    }
     if (grammar_continuous) {  // (its own refusals first: the ones below speak of the other modes)
         if (continuous || posteriors || grammar || !frames_dir.empty() || !body.empty()) {
             fprintf(stderr, "hmm segment: --grammar-continuous decodes one stream under the prices of --class-transitions: not with "

@@ -1,6 +1,7 @@
 // hmm_class_loop.cpp -- the class loop of all models on the GPU: the joint Viterbi through it (`hmm segment`, DESIGN.md
 // 4.8.6, hmm_segment.hip), the class posteriors under it (`--posteriors`, 4.8.7, hmm_posterior.hip) and the same loop under
-// a matrix of class-to-class prices (`--class-transitions`, 4.8.8, hmm_segment_trans.hip) with the posteriors under that
+// a matrix of class-to-class prices (`--class-transitions`, 4.8.8, hmm_segment_trans.hip and, above 16 wave-slots or on
+// request, hmm_segment_trans_looped.hip: ECOZ2_HMM_SEGMENT_TRANS_BODY) with the posteriors under that
 // matrix (`--grammar-posteriors`, 4.8.13, hmm_posterior_trans.hip), with their reports and their
 // array and file entry points; and what every class-loop decoder shares (hmm_host.h): the shape checks, the packing into
 // wave-slots, the models with their logarithms, the parameter block and the device side of a packing.
@@ -170,6 +171,31 @@ int check_resident(const char* who, int slots, const char* what_has)
     if (slots > e2hmm::SEG_MAX_WAVES)
         return e2vq_set_error("%s: the classes take %d wave-slots of 64 lanes (at most %d: %s no looped body)", who, slots,
                               e2hmm::SEG_MAX_WAVES, what_has);
+    return 0;
+}
+
+// the body of the decoder under class-to-class prices (ECOZ2_HMM_SEGMENT_TRANS_BODY): resident (at most 16 slots) unless the
+// caller opts into the looped one
+int segment_trans_body(int* body) { return opt_in_body("ECOZ2_HMM_SEGMENT_TRANS_BODY", body); }
+
+bool segment_trans_looped(int body, int slots)
+{
+    return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
+}
+
+// (host only) resident: at most 16 slots.  looped: the mandatory LDS of hmm_segment_trans_looped.hip must fit -- with
+// segment_check_shape's caps it always does (147 712 bytes at K = sum N = 4096); the check stands for the day
+// a cap moves.
+int trans_check_slots(const char* who, int K, const int* Ns, int body)
+{
+    const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K));
+    if (!segment_trans_looped(body, pk.slots)) return check_resident(who, pk.slots, "the class-transition decoder has");
+    e2hmm::SegPlanDev shape{};
+    shape.K = K, shape.slots = pk.slots, shape.sumN = pk.sumN;
+    const size_t need = e2hmm::segment_trans_looped_lds_bytes(shape, false, false);
+    if (need > e2hmm::SEG_LDS_BYTES)
+        return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of the "
+                              "class-transition decoder (at most %zu)", who, pk.slots, pk.sumN, K, need, (size_t)e2hmm::SEG_LDS_BYTES);
     return 0;
 }
 
@@ -421,15 +447,10 @@ int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i
 }
 
 // ---- hmm segment --class-transitions ----------------------------------------------------------------------
-int trans_check_slots(const char* who, int K, const int* Ns)
-{
-    return check_resident(who, pack_slots(std::vector<int>(Ns, Ns + K)).slots, "the class-transition decoder has");
-}
-
 // segment_device under the K x K prices lt (row: the class left); out.gbest receives exit_score.  Already checked:
-// segment_check_shape, trans_check_slots, trans_check_lt.
+// segment_check_shape, trans_check_slots (with the body that segment_trans_body gave), trans_check_lt.
 int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, const double* lt, hipStream_t st,
-                         const SegOut& out)
+                         const SegOut& out, int body)
 {
     const int K = lm.K();
     const SegPacking pk = pack_slots(lm.Ns);
@@ -460,14 +481,16 @@ int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, cons
                               "classes) (%lld bytes; ECOZ2_HMM_SEGMENT_CHUNK_BYTES bounds them by whole streams): %s",
                               (long long)max_frames, sumN, K, (long long)(max_frames * row), why.c_str());
     }
+    // (both bodies write the same tables: the backtrack below serves either)
+    const auto launch = segment_trans_looped(body, slots) ? e2hmm::launch_segment_trans_looped : e2hmm::launch_segment_trans;
     KernelTimer timer;
     if (timer.create()) return 1;
     HIPCHK(hipEventRecord(timer.start.e, st));
     // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backtrack has read them)
     for (const auto& c : chunks) {
         const int s0 = c.first, n = c.second - c.first;
-        if (e2hmm::launch_segment_trans(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_ltT.get(), d_psi.get(), d_src.get(), d_xs.get(),
-                                        d_Es.get(), res.logp.get() + s0, res.qlast.get() + s0, res.status.get() + s0, st))
+        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_ltT.get(), d_psi.get(), d_src.get(), d_xs.get(), d_Es.get(),
+                   res.logp.get() + s0, res.qlast.get() + s0, res.status.get() + s0, st))
             return e2vq_set_error("hmm segment --class-transitions: %d wave-slots of %d states cannot be launched", slots, sumN);
         HIPCHK(hipGetLastError());
         e2hmm::launch_segment_trans_backtrack(pl, d_offs.get() + s0, n, h_offs[s0], d_psi.get(), d_src.get(), d_xs.get(), d_Es.get(),
@@ -676,8 +699,10 @@ int segment_trans_files(const char* who, const char* const* model_filenames, uns
     if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
     if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models)) return 1;
     const int K = lm.K();
-    if (trans_check_slots(who, K, lm.Ns.data()) || (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data())) ||
-        check_names(who, K, lm.names.data()))
+    // (--grammar-posteriors has the resident layout only and does not read the variable: its decode stays resident too)
+    int body = EMBED_BODY_RESIDENT;
+    if ((!posteriors && segment_trans_body(&body)) || trans_check_slots(who, K, lm.Ns.data(), body) ||
+        (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data())) || check_names(who, K, lm.names.data()))
         return 1;
     std::vector<double> lt;
     if (transitions_read(transitions_csv, K, lm.names.data(), lt)) return 1;
@@ -699,7 +724,7 @@ int segment_trans_files(const char* who, const char* const* model_filenames, uns
         int status = 0;
         SegOut out;
         out.cls = cls.data(), out.entered = entered.data(), out.gbest = exit_score.data(), out.log_prob = &lp, out.status = &status;
-        if (segment_trans_device(lm, d_sym, offs, 1, lt.data(), st, out)) return 1;
+        if (segment_trans_device(lm, d_sym, offs, 1, lt.data(), st, out, body)) return 1;
         if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), lm.M);
         if (posteriors) {  // the same staged symbols, the same effective prices
             post.resize(n * (size_t)K);
@@ -819,12 +844,13 @@ extern "C" int e2vq_hmm_segment_trans(int device, int K, const int* Ns, int M, c
     const char* who = "e2vq_hmm_segment_trans";
     LoopModels lm;
     DevSeqs seqs;
+    int body = EMBED_BODY_RESIDENT;
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
-        trans_check_lt(who, K, lt) || trans_check_slots(who, K, Ns))
+        trans_check_lt(who, K, lt) || segment_trans_body(&body) || trans_check_slots(who, K, Ns, body))
         return 1;
     if (lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs() || seqs.open(device, sym, offs, S, sym_on_device != 0)) return 1;
     const SegOut out{cls, state, entered, exit_score, log_prob, status};
-    return segment_trans_device(lm, seqs.sym, (const i64*)offs, S, lt, seqs.st.s, out);
+    return segment_trans_device(lm, seqs.sym, (const i64*)offs, S, lt, seqs.st.s, out, body);
 }
 
 extern "C" int e2vq_hmm_segment_trans_report(const char* name, int64_t T, int K, const char* const* class_names, int W_ms, int O_ms,

@@ -163,6 +163,16 @@ void launch_segment_trans_backtrack(const SegPlanDev& pl, const long long* offs,
                                     const unsigned short* src, const unsigned short* xs, const double* Es, const int* qlast,
                                     const int* status, unsigned short* cls, unsigned short* state, unsigned char* entered,
                                     double* exit_score, hipStream_t st);
+// The looped body of the same decode (hmm_segment_trans_looped.hip): min(slots, SEG_MAX_WAVES) waves, a wave
+// serves the slots w, w + waves, .. in turn; any number of slots.  Arguments, tables and results are launch_segment_trans's,
+// bit for bit, and launch_segment_trans_backtrack reads them.  Dynamic LDS: 16 SEG_MAX_WAVES + 16 K + 20 sumN bytes are
+// mandatory (the pairs, E of two frames, d / best / arg per state); lA, and then ltT, go behind them while the sum stays
+// within SEG_LDS_BYTES (segment_trans_looped_layout: the instantiation).  Returns 1 when the shape cannot be launched.
+size_t segment_trans_looped_lds_bytes(const SegPlanDev& pl, bool a_lds, bool lt_lds);
+void segment_trans_looped_layout(const SegPlanDev& pl, bool* a_lds, bool* lt_lds);
+int launch_segment_trans_looped(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long psi0,
+                                const double* ltT, unsigned short* psi, unsigned short* src, unsigned short* xs, double* Es,
+                                double* logp, int* qlast, int* status, hipStream_t st);
 
 // Forced alignment to a known order of units (hmm_align.hip).  The units of one stream's transcript are
 // packed in unit order into wave-slots as the classes are above (unit l on N_{c_l} consecutive lanes of one slot; composite

@@ -324,6 +324,14 @@ int loop_body_looped(const char* env_name, int slots, bool* looped);
 // "<env_name>=<v>: auto, resident or looped"
 int opt_in_body(const char* env_name, int* body);
 
+// The decoder under class-to-class prices (`hmm segment --class-transitions` and its session):
+// segment_trans_body: ECOZ2_HMM_SEGMENT_TRANS_BODY through opt_in_body -> *body (an EmbedBody).  segment_trans_looped: whether
+// a packing of `slots` runs the looped kernels under that body.  trans_check_slots (host only): resident -- more than 16 slots
+// are refused, word for word as before the looped body existed; looped -- its mandatory LDS must fit.
+int segment_trans_body(int* body);
+bool segment_trans_looped(int body, int slots);
+int trans_check_slots(const char* who, int K, const int* Ns, int body);
+
 // A packing on the device: the parameter block, the four tables of `pk`, and the plan the kernels take.  upload() only
 // enqueues: the host vectors must outlive the stream's copies, and this struct the stream's kernels (a local is declared
 // before the DevSeqs / Stream whose stream works on it, or the function waits for that stream before it returns).

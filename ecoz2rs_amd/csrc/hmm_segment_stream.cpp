@@ -5,7 +5,8 @@
 // to one session.  Shape checks, models, packing and its device side are hmm_class_loop.cpp's, the input stage hmm_input.cpp's
 // (hmm_host.h).
 // A session has two modes, and one schedule serves both: under the one switch penalty, or -- `matrix` --
-// under a K x K matrix of class-to-class prices (`--class-transitions --grammar-continuous`, hmm_segment_trans_stream.hip).
+// under a K x K matrix of class-to-class prices (`--class-transitions --grammar-continuous`, hmm_segment_trans_stream.hip, or
+// the looped block step of hmm_segment_trans_looped.hip where ECOZ2_HMM_SEGMENT_TRANS_BODY chose it when the session opened).
 // Only the launches, the ring's allocations and the results of a commit differ.
 #include "hmm_host.h"
 #include "hmm_segment_trans_stream.h"
@@ -17,7 +18,7 @@ using e2hmm::SegStreamState;
 
 struct e2vq_segment_stream {
     int device = 0, K = 0, M = 0, sumN = 0;
-    bool looped = false;
+    bool looped = false;  // the body of the block step, fixed at open (under a matrix: ECOZ2_HMM_SEGMENT_TRANS_BODY)
     bool matrix = false;  // class-to-class prices: the ring holds psi, src, x and E, a commit yields exit_score
     double ln_switch = 0.0;
     i64 B = 0;         // frames of a block
@@ -80,7 +81,9 @@ const char* flag_of(const Session& s) { return s.matrix ? "--grammar-continuous"
 
 // The models (checked by segment_check_shape; all of one M) on the device and an empty session.  lt: the K x K prices of a
 // matrix session (checked by trans_check_lt), or null under the one ln_switch.  Every refusal comes before the first HIP call.
-int stream_open(const char* who, int device, const LoopModels& lm, double ln_switch, const double* lt, Session** out)
+// trans_body: the EmbedBody of a matrix session (segment_trans_body's).
+int stream_open(const char* who, int device, const LoopModels& lm, double ln_switch, const double* lt, Session** out,
+                int trans_body = EMBED_BODY_RESIDENT)
 {
     const int K = lm.K(), M = lm.M;
     const char* bv = getenv(ENV_BLOCK);
@@ -89,8 +92,9 @@ int stream_open(const char* who, int device, const LoopModels& lm, double ln_swi
     const SegPacking pk = pack_slots(lm.Ns);
     const int sumN = pk.sumN;
     bool looped = false;
-    if (lt ? check_resident(who, pk.slots, "the class-transition decoder has") : loop_body_looped("ECOZ2_HMM_SEGMENT_BODY", pk.slots, &looped))
+    if (lt ? trans_check_slots(who, K, lm.Ns.data(), trans_body) : loop_body_looped("ECOZ2_HMM_SEGMENT_BODY", pk.slots, &looped))
         return 1;
+    if (lt) looped = segment_trans_looped(trans_body, pk.slots);
     const i64 row = 2 * (i64)sumN + (lt ? 12 * (i64)K : 4), budget = env_bytes(ENV_PENDING, (i64)256 << 20), C = budget / row;
     if (C < 2 * B)
         return lt ? e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states and %d classes (%lld bytes a frame): fewer than "
@@ -146,8 +150,9 @@ int queue_block(Session& s, const unsigned short* blk, i64 n)
         HIPCHK(hipEventRecord(s.all.start.e, st));
         s.timing = true;
     }
-    if (s.matrix ? e2hmm::launch_segment_trans_stream(s.loop.pl, blk, (int)n, s.p, s.d_ltT.get(), d_half(s, s.dcur), d_half(s, s.dcur ^ 1),
-                                                      s.tring, s.d_state.get(), st)
+    const auto trans_launch = s.looped ? e2hmm::launch_segment_trans_stream_looped : e2hmm::launch_segment_trans_stream;
+    if (s.matrix ? trans_launch(s.loop.pl, blk, (int)n, s.p, s.d_ltT.get(), d_half(s, s.dcur), d_half(s, s.dcur ^ 1), s.tring,
+                                s.d_state.get(), st)
                  : e2hmm::launch_segment_stream(s.loop.pl, s.looped, blk, (int)n, s.p, s.ln_switch, d_half(s, s.dcur), d_half(s, s.dcur ^ 1),
                                                 s.ring, s.d_gstage.get(), s.d_state.get(), st))
         return e2vq_set_error("hmm segment %s: %d wave-slots of %d states cannot be launched", flag_of(s), s.loop.pl.slots, s.sumN);
@@ -380,10 +385,11 @@ extern "C" int e2vq_hmm_segment_trans_stream_open(int device, int K, const int* 
 {
     const char* who = "e2vq_hmm_segment_trans_stream_open";
     LoopModels lm;
+    int body = EMBED_BODY_RESIDENT;
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt != nullptr && out != nullptr) || segment_check_shape(who, K, Ns) ||
-        trans_check_lt(who, K, lt) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs())
+        trans_check_lt(who, K, lt) || segment_trans_body(&body) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs())
         return 1;
-    return stream_open(who, device, lm, 0.0, lt, out);
+    return stream_open(who, device, lm, 0.0, lt, out, body);
 }
 
 extern "C" int e2vq_hmm_segment_stream_feed(e2vq_segment_stream* s, const void* sym, int64_t n, int sym_on_device, int64_t* final_frames)
@@ -473,10 +479,10 @@ struct Holder {
 };
 
 int decode_pieces(const char* who, const LoopModels& fm, const SymInputs& si, int P, int W_ms, int O_ms, double ln_switch, const double* lt,
-                  const char* name, Holder& hold)
+                  const char* name, Holder& hold, int trans_body = EMBED_BODY_RESIDENT)
 {
     const int device = env_device();
-    if (stream_open(who, device, fm, ln_switch, lt, &hold.s)) return 1;  // (makes the device current)
+    if (stream_open(who, device, fm, ln_switch, lt, &hold.s, trans_body)) return 1;  // (makes the device current)
     Session& s = *hold.s;
     SymStage stg;
     if (stg.open(device, si)) return 1;
@@ -541,7 +547,8 @@ extern "C" int e2vq_hmm_segment_trans_continuous_files(const char* const* model_
     if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
     if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models)) return 1;
     const int K = fm.K();
-    if (check_resident(who, pack_slots(fm.Ns).slots, "the class-transition decoder has") || check_names(who, K, fm.names.data())) return 1;
+    int body = EMBED_BODY_RESIDENT;
+    if (segment_trans_body(&body) || trans_check_slots(who, K, fm.Ns.data(), body) || check_names(who, K, fm.names.data())) return 1;
     std::vector<double> lt;
     if (transitions_read(transitions_csv, K, fm.names.data(), lt)) return 1;
     for (double& v : lt) v = v + ln_switch;  // the effective price
@@ -550,7 +557,7 @@ extern "C" int e2vq_hmm_segment_trans_continuous_files(const char* const* model_
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, nullptr, si)) return 1;
     const std::string csv = csv_of(csv_dir_or_file, name);
     Holder hold;
-    if (decode_pieces(who, fm, si, P, W_ms, O_ms, ln_switch, lt.data(), name, hold)) return 1;
+    if (decode_pieces(who, fm, si, P, W_ms, O_ms, ln_switch, lt.data(), name, hold, body)) return 1;
     const Session& s = *hold.s;
     return e2vq_hmm_segment_trans_report(name, s.F, K, fm.names.data(), W_ms, O_ms, s.f_cls.data(), s.f_entered.data(), s.f_g.data(),
                                          s.log_prob, ln_switch, lt.data(), csv.empty() ? nullptr : csv.c_str());

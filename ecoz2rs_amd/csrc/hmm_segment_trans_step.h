@@ -1,7 +1,7 @@
 // hmm_segment_trans_step.h -- the two halves of a step of the joint Viterbi under class-to-class prices,
 // written once: the in-class chain that also yields the class's exit, and the walk over the K sources of a destination class.
 // Each is the same IEEE additions and comparisons in the same order as the restatement (`transcribe`), so a change to that
-// contract is made here.  hmm_segment_trans_stream.hip uses them; k_hmm_segment_trans (hmm_segment_trans.hip) still carries
+// contract is made here.  hmm_segment_trans_stream.hip and the looped bodies (hmm_segment_trans_looped_step.h) use them; k_hmm_segment_trans (hmm_segment_trans.hip) still carries
 // its own copies -- moving it here is a change with a measurement of its own.  Both are __forceinline__ leaves.
 // Device code only.  Internal.
 #pragma once

@@ -21,6 +21,10 @@ struct SegTransRingDev {
 // SEG_MAX_WAVES slots.  Returns 1 when the shape cannot be launched.
 int launch_segment_trans_stream(const SegPlanDev& pl, const unsigned short* sym, int n, long long frame0, const double* ltT,
                                 const double* d_in, double* d_out, SegTransRingDev ring, SegStreamState* state, hipStream_t st);
+// The looped body of the same block step (hmm_segment_trans_looped.hip; LDS as launch_segment_trans_looped): any number of
+// slots, the same d_out and the same ring rows bit for bit
+int launch_segment_trans_stream_looped(const SegPlanDev& pl, const unsigned short* sym, int n, long long frame0, const double* ltT,
+                                       const double* d_in, double* d_out, SegTransRingDev ring, SegStreamState* state, hipStream_t st);
 // launch_segment_coalesce with the back step of the matrix: (k, psi), or on ENTER (src[k], x[src[k]])
 void launch_segment_trans_coalesce(const SegPlanDev& pl, const double* d, SegTransRingDev ring, long long F, long long e, int close,
                                    SegStreamState* state, hipStream_t st);

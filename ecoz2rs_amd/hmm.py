@@ -175,7 +175,7 @@ def _kernel_ms(fn):
 
 @contextlib.contextmanager
 def _body_env(name, body):
-    """the variable `name` (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY) = body ("auto", "resident" or "looped") for the
+    """the variable `name` (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY, ECOZ2_HMM_SEGMENT_TRANS_BODY) = body ("auto", "resident" or "looped") for the
     duration of a call; None leaves the environment alone"""
     if body is None:
         yield
@@ -706,10 +706,13 @@ def segments_of_trans(cls, entered, exit_score, log_prob, ln_trans):
     return out
 
 
-def segment_trans(models, sym, offs, ln_trans, device=0):
+def segment_trans(models, sym, offs, ln_trans, device=0, body=None):
     """`segment` under a K x K matrix of class-to-class prices: ln_trans[f][k] <= 0 (or -inf) is the log of
-    the price of leaving class f and entering class k; the classes must pack into at most 16 wave-slots.  -> the dict of
-    `segment` with exit_score in the place of gbest: exit_score[t] = the best score in the class of frame t - 1 at t - 1"""
+    the price of leaving class f and entering class k; the classes must pack into at most 16 wave-slots unless the looped body
+    is chosen.  body: "auto", "resident" or "looped" (ECOZ2_HMM_SEGMENT_TRANS_BODY for this call: the looped body takes any
+    number of slots, auto picks it above 16; the path is the same bit for bit); None leaves the environment alone.  -> the
+    dict of `segment` with exit_score in the place of gbest: exit_score[t] = the best score in the class of frame t - 1 at
+    t - 1"""
     K = len(models)
     ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
     Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
@@ -732,9 +735,10 @@ def segment_trans(models, sym, offs, ln_trans, device=0):
     cls, state = np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
     entered, ex = np.zeros(n, dtype=np.uint8), np.zeros(n)
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_segment_trans(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, lt.ctypes.data,
-                                     cls.ctypes.data, state.ctypes.data, entered.ctypes.data, ex.ctypes.data, lp.ctypes.data,
-                                     st.ctypes.data, int(on_device)))
+    with _body_env("ECOZ2_HMM_SEGMENT_TRANS_BODY", body):
+        check(lib.e2vq_hmm_segment_trans(device, K, Ns, M, ptr(0), ptr(1), ptr(2), sym_ptr, offs.ctypes.data, S, lt.ctypes.data,
+                                         cls.ctypes.data, state.ctypes.data, entered.ctypes.data, ex.ctypes.data, lp.ctypes.data,
+                                         st.ctypes.data, int(on_device)))
     T = int(offs[-1])
     out = dict(cls=cls[:T], state=state[:T], entered=entered[:T], exit_score=ex[:T], log_prob=lp[:S], status=st[:S])
     out["segments"] = [segments_of_trans(out["cls"][a:b], out["entered"][a:b], out["exit_score"][a:b], lp[s], lt)
@@ -748,12 +752,14 @@ def segment_trans_last_kernel_ms():
 
 class SegmentTransStream(SegmentStream):
     """`segment_trans` on one stream that arrives piece by piece: `SegmentStream` under the K x K prices
-    ln_trans of `segment_trans` (the classes must pack into at most 16 wave-slots).  feed / flush / close / take return the
+    ln_trans of `segment_trans` (the classes must pack into at most 16 wave-slots unless body -- "auto", "resident" or
+    "looped", ECOZ2_HMM_SEGMENT_TRANS_BODY while the session opens, which fixes its body -- chooses the looped one).  feed /
+    flush / close / take return the
     dict of `SegmentStream` with exit_score in the place of gbest; segments follow `segments_of_trans` with absolute frames
     (the class of the last final frame is kept across calls: the segment that starts at b paid
     ln_trans[cls[b - 1]][cls[b]])."""
 
-    def __init__(self, models, ln_trans, device=0):
+    def __init__(self, models, ln_trans, device=0, body=None):
         K = len(models)
         ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
         Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
@@ -769,7 +775,8 @@ class SegmentTransStream(SegmentStream):
         self.status = None
         self._open = None  # the segment that is not complete yet: (begin, cls, lo)
         self._last_cls = None  # the class of the last frame handed out
-        check(lib.e2vq_hmm_segment_trans_stream_open(device, K, Ns, M, ptr(0), ptr(1), ptr(2), lt.ctypes.data, C.byref(self._h)))
+        with _body_env("ECOZ2_HMM_SEGMENT_TRANS_BODY", body):
+            check(lib.e2vq_hmm_segment_trans_stream_open(device, K, Ns, M, ptr(0), ptr(1), ptr(2), lt.ctypes.data, C.byref(self._h)))
 
     def _take(self, end_log_prob=None):
         n = max(self.final_frames_, 1)
@@ -1024,7 +1031,7 @@ def learn_loop_files(model_filenames, input_filenames, out_dir, ln_switch, class
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
                   frame_posteriors=None, class_transitions=None, continuous=None, body=None, grammar_posteriors=False,
-                  grammar_continuous=None):
+                  grammar_continuous=None, grammar_body=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
@@ -1033,18 +1040,26 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
     them (frame_posteriors is then taken too; there is one body).  continuous
     (4.8.9): the name of the one recording whose consecutive pieces the inputs are -- one block, and with `csv` (a directory
     or a .csv file) one CSV, <csv>/<name>.csv.  grammar_continuous (4.8.15): with class_transitions, the same under the
-    file's prices; it excludes continuous, the posteriors, frame_posteriors and body"""
+    file's prices; it excludes continuous, the posteriors, frame_posteriors and body.  grammar_body ("auto", "resident" or
+    "looped", as `segment_trans` takes body): the kernel body of the decoder under class_transitions, with or without
+    grammar_continuous; it needs class_transitions and excludes grammar_posteriors, which has the resident body only"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
+    if grammar_body is not None:
+        if class_transitions is None:
+            raise ValueError("grammar_body needs class_transitions")
+        if grammar_posteriors:
+            raise ValueError("grammar_body excludes grammar_posteriors (there is one body)")
     if grammar_continuous is not None:
         if continuous is not None or posteriors or grammar_posteriors or frame_posteriors is not None or body is not None:
             raise ValueError("grammar_continuous excludes continuous, posteriors, grammar_posteriors, frame_posteriors and body")
         if class_transitions is None:
             raise ValueError("grammar_continuous needs class_transitions")
-        check(lib.e2vq_hmm_segment_trans_continuous_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
-                                                          len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                                          str(class_transitions).encode(), str(grammar_continuous).encode(),
-                                                          str(csv).encode() if csv else None))
+        with _body_env("ECOZ2_HMM_SEGMENT_TRANS_BODY", grammar_body):
+            check(lib.e2vq_hmm_segment_trans_continuous_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                              len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                              str(class_transitions).encode(), str(grammar_continuous).encode(),
+                                                              str(csv).encode() if csv else None))
         return
     if continuous is not None:
         if posteriors or class_transitions is not None or grammar_posteriors:
@@ -1068,9 +1083,10 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
                                                               str(class_transitions).encode(), str(csv).encode() if csv else None,
                                                               str(frame_posteriors).encode() if frame_posteriors is not None else None))
             return
-        check(lib.e2vq_hmm_segment_trans_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
-                                               len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                               str(class_transitions).encode(), str(csv).encode() if csv else None))
+        with _body_env("ECOZ2_HMM_SEGMENT_TRANS_BODY", grammar_body):
+            check(lib.e2vq_hmm_segment_trans_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                   len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                   str(class_transitions).encode(), str(csv).encode() if csv else None))
         return
     if posteriors:
         with _body_env("ECOZ2_HMM_POSTERIOR_BODY", body):

@@ -376,14 +376,28 @@ int e2vq_hmm_segment_files_posteriors(const char *const *model_filenames, unsign
  * array: lt[f * K + k] is the logarithm of the price of leaving class f and entering class k through pi_k (f = k: a
  * boundary between two segments of one class).  Every entry is <= 0 or -inf.  Refused before any HIP call: what
  * e2vq_hmm_segment refuses, an entry that is NaN or > 0, and a packing of more than 16 wave-slots (classes are packed in
- * class order into slots of 64 lanes, N_k consecutive lanes each, never across a slot; only the resident layout exists).
+ * class order into slots of 64 lanes, N_k consecutive lanes each, never across a slot) unless
+ * ECOZ2_HMM_SEGMENT_TRANS_BODY chooses the looped body (the last paragraph).
  * Per step: E_t[f] = max_i d_{t-1}[f][i] with x_t[f] the lowest state reaching it; base_t[k] = max_f (E_t[f] + lt[f][k])
  * with src_t[k] the lowest class reaching it; a state (k, j) is entered when base_t[k] + lpi_k[j] is strictly greater
  * than the best in-class predecessor.  Backwards an ENTER at frame t + 1 in class k gives q_t = (src_{t+1}[k], x_{t+1}[.]).
  * Outputs as e2vq_hmm_segment's with exit_score in the place of gbest: exit_score[t] = E_t[cls[t-1]] (0.0 at frame 0);
  * on an entered frame it is the path's own cumulative score at t - 1.  The segment [b, e) scores
  *   (e == T ? ln P* : exit_score[e]) - (b == 0 ? 0.0 : exit_score[b] + lt[cls[b-1]][cls[b]]).
- * With every entry equal to ln_switch, d, ln P* and exit_score on entered frames are e2vq_hmm_segment's bit for bit. */
+ * With every entry equal to ln_switch, d, ln P* and exit_score on entered frames are e2vq_hmm_segment's bit for bit.
+ * The body.  ECOZ2_HMM_SEGMENT_TRANS_BODY chooses the kernel body in e2vq_hmm_segment_trans, e2vq_hmm_segment_trans_files,
+ * e2vq_hmm_segment_trans_stream_open (a session fixes its body at open) and e2vq_hmm_segment_trans_continuous_files; no other
+ * entry point reads it -- e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors (whose decode stays
+ * resident too), e2vq_hmm_transitions_estep and e2vq_hmm_loop_estep keep their refusals of more than 16 wave-slots.  Unset, empty
+ * or "resident": as above, more than 16 wave-slots are refused with "the classes take %d wave-slots of 64 lanes (at most 16:
+ * the class-transition decoder has no looped body)".  "looped": the looped body for every packing, in which a wave serves
+ * several slots in turn.  "auto": resident up to 16 slots, looped above.  Any other value is refused before any HIP call:
+ * "ECOZ2_HMM_SEGMENT_TRANS_BODY=<v>: auto, resident or looped".  The decode is a max-sum whose contract never depended on the
+ * body: cls, state, entered, exit_score, log_prob and status are the same bits under either.  The looped body keeps
+ * 256 + 16 K + 20 sum N bytes in LDS (E of two frames; d, the in-class maximum and its state per state); a packing whose bytes
+ * exceeded the 160 KB would be refused before any HIP call ("%d wave-slots, %d states and %d classes take %zu bytes of LDS in
+ * the looped body of the class-transition decoder"), which the limits on the number of states (at most 147 712 bytes, at
+ * K = sum N = 4096) keep out of reach. */
 int e2vq_hmm_segment_trans(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
                            const double *const *Bs, const void *sym, const int64_t *offs, int S, const double *lt,
                            uint16_t *cls, uint16_t *state, uint8_t *entered, double *exit_score, double *log_prob, int *status,
