@@ -83,6 +83,7 @@ static int usage()
             "                  [--grammar-posteriors [--frame-posteriors <dir>]]\n"
             "                  [--continuous <name>]\n"
             "                  [--grammar-body <auto|resident|looped>]\n"
+            "                  [--grammar-posteriors-body <auto|resident|looped>]\n"
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (each recording decoded once under all models: segment boundaries to the frame, a class per segment;\n"
             "                  --posteriors adds each segment's mean and least class posterior, and the per-frame table)\n"
@@ -95,6 +96,9 @@ static int usage()
             "                  (--grammar-body, with --class-transitions: the kernel body of the decoder under the prices -- resident\n"
             "                  takes at most 16 wave-slots of classes, looped any number, auto the looped one above 16; the same path\n"
             "                  bit for bit; not with --grammar-posteriors)\n"
+            "                  (--grammar-posteriors-body, with --grammar-posteriors: the kernel body of the posteriors under the prices,\n"
+            "                  which the decode of the same recording follows -- resident takes at most 16 wave-slots of classes, looped\n"
+            "                  any number, auto the looped one above 16; the figures are the same bit for bit)\n"
             "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  --switch-penalty <x <= 0 | -inf> --class-transitions <file.csv> --grammar-continuous <name>\n"
             "                  [-c <csv dir|file.csv>]\n"
@@ -107,7 +111,10 @@ static int usage()
             "  ecoz2 hmm transitions --em -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15] --switch-penalty <x>\n"
             "                  [--init <file.csv>] [--alpha 1] [-a val_auto] [-I max_iterations] -o <file.csv>\n"
             "                  --sequences <.seq>... | --predictors <.prd>... | --signals <.wav>...\n"
+            "                  [--body <auto|resident|looped>]\n"
             "                  (the same prices by Baum-Welch from unlabelled recordings under the models; <file.csv>.em.csv: the iterations)\n"
+            "                  (--body: the kernel body of the E-step -- resident takes at most 16 wave-slots of classes, looped any\n"
+            "                  number, auto the looped one above 16; the same matrix bit for bit)\n"
             "  ecoz2 hmm align -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  [--switch-penalty <x <= 0>] [--filler <class>] [-c <csv dir|file.csv>] --labels <files>...\n"
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
@@ -883,8 +890,8 @@ static int hmm_segment_cmd(int argc, char** argv)
     bool continuous = false;
     bool grammar = false;  // --grammar-posteriors
     bool grammar_continuous = false;
-    bool have_grammar_body = false;
-    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, body, grammar_body;
+    bool have_grammar_body = false, have_post_body = false;
+    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, body, grammar_body, post_body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -909,6 +916,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "--grammar-posteriors") grammar = true;
         else if (a == "--body") body = val("--body");
         else if (a == "--grammar-body") { grammar_body = val("--grammar-body"); have_grammar_body = true; }
+        else if (a == "--grammar-posteriors-body") { post_body = val("--grammar-posteriors-body"); have_post_body = true; }
         else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
         else if (a == "--grammar-continuous") { grammar_name = val("--grammar-continuous"); grammar_continuous = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
@@ -952,6 +960,17 @@ static int hmm_segment_cmd(int argc, char** argv)
         }
         setenv("ECOZ2_HMM_SEGMENT_TRANS_BODY", grammar_body.c_str(), 1);
     }
+    if (have_post_body) {  // the body of the posteriors under the prices (ECOZ2_HMM_TRANS_FB_BODY), set in this process before the call
+        if (!grammar) {
+            fprintf(stderr, "hmm segment: --grammar-posteriors-body <auto|resident|looped> needs --grammar-posteriors (it chooses the body "
+                            "of the posteriors under the prices)\n");
+            return 2;
+        }
+        if (post_body != "auto" && post_body != "resident" && post_body != "looped") {
+            fprintf(stderr, "hmm segment --grammar-posteriors: --grammar-posteriors-body %s: auto, resident or looped\n", post_body.c_str());
+            return 2;
+        }
+    }
     if (grammar_continuous) {  // (its own refusals first: the ones below speak of the other modes)
         if (continuous || posteriors || grammar || !frames_dir.empty() || !body.empty()) {
             fprintf(stderr, "hmm segment: --grammar-continuous decodes one stream under the prices of --class-transitions: not with "
@@ -990,6 +1009,7 @@ static int hmm_segment_cmd(int argc, char** argv)
         return 2;
     }
     if (continuous && rec_name.empty()) { fprintf(stderr, "hmm segment: --continuous <name>: the recording needs a name\n"); return 2; }
+    if (have_post_body) setenv("ECOZ2_HMM_TRANS_FB_BODY", post_body.c_str(), 1);
     std::vector<std::string> hmm_files, inputs;
     e2vq_io::resolve_filenames(models, ".hmm", hmm_files);
     if (hmm_files.empty()) { printf("No models given\n"); return 0; }
@@ -1028,8 +1048,8 @@ static int hmm_transitions_em_cmd(int argc, char** argv)
 {
     int P = 36, W = 45, O = 15, max_iterations = -1;
     double ln_switch = 0.0, alpha = 1.0, val_auto = 0.3;
-    bool have_switch = false;
-    std::string codebook, init, out;
+    bool have_switch = false, have_body = false;
+    std::string codebook, init, out, body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -1064,10 +1084,18 @@ static int hmm_transitions_em_cmd(int argc, char** argv)
         else if (a == "-a") val_auto = real("-a");
         else if (a == "-I") max_iterations = (int)num("-I");
         else if (a == "-o" || a == "--output") out = val("-o");
+        else if (a == "--body") { body = val("--body"); have_body = true; }
         else if (a == "--signals") many(signals);
         else if (a == "--predictors") many(predictors);
         else if (a == "--sequences") many(sequences);
         else return usage();
+    }
+    if (have_body) {  // the E-step's body (ECOZ2_HMM_TRANS_FB_BODY), set in this process before the call
+        if (body != "auto" && body != "resident" && body != "looped") {
+            fprintf(stderr, "hmm transitions --em: --body %s: auto, resident or looped\n", body.c_str());
+            return 2;
+        }
+        setenv("ECOZ2_HMM_TRANS_FB_BODY", body.c_str(), 1);
     }
     if (models.empty()) { fprintf(stderr, "hmm transitions --em: --models <files|dirs>... is required\n"); return usage(); }
     if ((int)!signals.empty() + (int)!predictors.empty() + (int)!sequences.empty() != 1) {
@@ -1123,7 +1151,7 @@ static int hmm_transitions_cmd(int argc, char** argv)
             if (!*v || *end) { fprintf(stderr, "--alpha: invalid value '%s'\n", v); exit(2); }
         }
         else if (a == "-o" || a == "--output") out = val("-o");
-        else if (a == "--init" || a == "-a" || a == "-I" || a == "--sequences" || a == "--predictors" || a == "--signals") {
+        else if (a == "--init" || a == "-a" || a == "-I" || a == "--body" || a == "--sequences" || a == "--predictors" || a == "--signals") {
             fprintf(stderr, "hmm transitions: %s needs --em (the matrix from unlabelled recordings)\n", a.c_str());
             return 2;
         }

@@ -2,7 +2,8 @@
 // 4.8.6, hmm_segment.hip), the class posteriors under it (`--posteriors`, 4.8.7, hmm_posterior.hip) and the same loop under
 // a matrix of class-to-class prices (`--class-transitions`, 4.8.8, hmm_segment_trans.hip and, above 16 wave-slots or on
 // request, hmm_segment_trans_looped.hip: ECOZ2_HMM_SEGMENT_TRANS_BODY) with the posteriors under that
-// matrix (`--grammar-posteriors`, 4.8.13, hmm_posterior_trans.hip), with their reports and their
+// matrix (`--grammar-posteriors`, 4.8.13, hmm_posterior_trans.hip and, above 16 wave-slots or on request,
+// hmm_posterior_trans_looped.hip: ECOZ2_HMM_TRANS_FB_BODY), with their reports and their
 // array and file entry points; and what every class-loop decoder shares (hmm_host.h): the shape checks, the packing into
 // wave-slots, the models with their logarithms, the parameter block and the device side of a packing.
 #include "hmm_host.h"
@@ -179,6 +180,15 @@ int check_resident(const char* who, int slots, const char* what_has)
 int segment_trans_body(int* body) { return opt_in_body("ECOZ2_HMM_SEGMENT_TRANS_BODY", body); }
 
 bool segment_trans_looped(int body, int slots)
+{
+    return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
+}
+
+// the body of the forward-backward passes under class-to-class prices (ECOZ2_HMM_TRANS_FB_BODY): resident (at most 16 slots)
+// unless the caller opts into the looped one
+int trans_fb_body(int* body) { return opt_in_body("ECOZ2_HMM_TRANS_FB_BODY", body); }
+
+bool trans_fb_looped(int body, int slots)
 {
     return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
 }
@@ -505,20 +515,34 @@ int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, cons
 }
 
 // ---- hmm segment --class-transitions --grammar-posteriors --------------------------------------------------
-int trans_posteriors_check_slots(const char* who, int K, const int* Ns)
+// (host only) resident: at most 16 slots.  looped: the mandatory LDS of hmm_posterior_trans_looped.hip must fit -- with
+// segment_check_shape's caps it always does (99 328 bytes at K = sum N = 4096); the check stands for the day
+// a cap moves.
+int trans_posteriors_check_slots(const char* who, int K, const int* Ns, int body)
 {
-    return check_resident(who, pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld).slots,
-                          "the posteriors under class-to-class prices have");
+    const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld);
+    if (!trans_fb_looped(body, pk.slots)) return check_resident(who, pk.slots, "the posteriors under class-to-class prices have");
+    e2hmm::SegPlanDev shape{};
+    shape.K = K, shape.slots = pk.slots, shape.sumN = pk.sumN;
+    const size_t need = e2hmm::posteriors_trans_looped_lds_bytes(shape, false, false);
+    if (need > e2hmm::SEG_LDS_BYTES)
+        return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of the "
+                              "posteriors under class-to-class prices (at most %zu)", who, pk.slots, pk.sumN, K, need,
+                              (size_t)e2hmm::SEG_LDS_BYTES);
+    return 0;
 }
 
 // posteriors_device under the K x K prices lt (row: the class left).  Already checked: segment_check_shape,
-// trans_posteriors_check_slots, trans_check_lt (and the models' parameters: finite and non-negative).
+// trans_posteriors_check_slots (with the body that trans_fb_body gave), trans_check_lt (and the models' parameters: finite and
+// non-negative).
 int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, const double* lt, hipStream_t st,
-                            const PostOut& out)
+                            const PostOut& out, int body)
 {
     const int K = lm.K(), M = lm.M;
     const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);
     const int sumN = pk.sumN, slots = pk.slots;
+    const bool looped = trans_fb_looped(body, slots);
+    const int waves = looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots;  // each stores its copy of c_t
     const std::vector<double> w = trans_prices(K, lt), params = trans_params(lm, pk);
     ClassLoopDev loop;
     Scores sc;  // P(O) of each stream
@@ -531,10 +555,10 @@ int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, c
     const e2hmm::SegPlanDev& pl = loop.pl;
     // launches of whole streams whose ah (8 sumN bytes a frame) and c (8 bytes a frame and wave) stay within the budget (the
     // class masses live in LDS only: the kernel stores nothing more per frame than 4.8.7's)
-    const i64 row = 8 * ((i64)sumN + slots);
+    const i64 row = 8 * ((i64)sumN + waves);
     i64 max_frames = 0;
     const auto chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * slots)) {
+    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves)) {
         const std::string why = e2vq_last_error();
         return e2vq_set_error("hmm segment --grammar-posteriors: no room for the forward table of %lld frames x %d states (%lld bytes; "
                               "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
@@ -546,8 +570,9 @@ int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, c
     // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
     for (const auto& c : chunks) {
         const int s0 = c.first, n = c.second - c.first;
-        if (e2hmm::launch_loop_posteriors_trans(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), d_ah.get(), d_c.get(), d_post.get(),
-                                                sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+        const auto launch = looped ? e2hmm::launch_loop_posteriors_trans_looped : e2hmm::launch_loop_posteriors_trans;
+        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), d_ah.get(), d_c.get(), d_post.get(), sc.d_mant.get() + s0,
+                   sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
             return e2vq_set_error("hmm segment --grammar-posteriors: %d wave-slots of %d states cannot be launched", slots, sumN);
         HIPCHK(hipGetLastError());
     }
@@ -699,10 +724,11 @@ int segment_trans_files(const char* who, const char* const* model_filenames, uns
     if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
     if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models)) return 1;
     const int K = lm.K();
-    // (--grammar-posteriors has the resident layout only and does not read the variable: its decode stays resident too)
+    // (--grammar-posteriors reads its own variable, never the decoder's: the decode of the same input follows that one choice,
+    // segment_trans_looped with its value, so that what the posteriors take the decoder takes too)
     int body = EMBED_BODY_RESIDENT;
-    if ((!posteriors && segment_trans_body(&body)) || trans_check_slots(who, K, lm.Ns.data(), body) ||
-        (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data())) || check_names(who, K, lm.names.data()))
+    if ((posteriors ? trans_fb_body(&body) : segment_trans_body(&body)) || trans_check_slots(who, K, lm.Ns.data(), body) ||
+        (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data(), body)) || check_names(who, K, lm.names.data()))
         return 1;
     std::vector<double> lt;
     if (transitions_read(transitions_csv, K, lm.names.data(), lt)) return 1;
@@ -730,7 +756,7 @@ int segment_trans_files(const char* who, const char* const* model_filenames, uns
             post.resize(n * (size_t)K);
             PostOut po;
             po.post = post.data();
-            if (trans_posteriors_device(lm, d_sym, offs, 1, lt.data(), st, po)) return 1;
+            if (trans_posteriors_device(lm, d_sym, offs, 1, lt.data(), st, po, body)) return 1;
         }
         const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
         return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), exit_score.data(), lp,
@@ -884,14 +910,16 @@ extern "C" int e2vq_hmm_segment_trans_posteriors(int device, int K, const int* N
     const char* who = "e2vq_hmm_segment_trans_posteriors";
     LoopModels lm;
     DevSeqs seqs;
+    int body = EMBED_BODY_RESIDENT;
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
-        trans_check_lt(who, K, lt) || trans_posteriors_check_slots(who, K, Ns) || lm.from_arrays(K, Ns, M, pis, As, Bs))
+        trans_check_lt(who, K, lt) || trans_fb_body(&body) || trans_posteriors_check_slots(who, K, Ns, body) ||
+        lm.from_arrays(K, Ns, M, pis, As, Bs))
         return 1;
     for (const Hmm& h : lm.models)
         if (posteriors_check_params(h)) return 1;
     if (seqs.open(device, sym, offs, S, sym_on_device != 0)) return 1;
     const PostOut out{post, log_prob, status};
-    return trans_posteriors_device(lm, seqs.sym, (const i64*)offs, S, lt, seqs.st.s, out);
+    return trans_posteriors_device(lm, seqs.sym, (const i64*)offs, S, lt, seqs.st.s, out, body);
 }
 
 extern "C" int e2vq_hmm_segment_trans_files_posteriors(const char* const* model_filenames, unsigned num_models, const char* cb_filename,

@@ -315,6 +315,18 @@ void posteriors_trans_layout(const SegPlanDev& pl, bool* a_lds, bool* w_lds);
 int launch_loop_posteriors_trans(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0,
                                  const double* w, double* ahs, double* cs, double* post, double* mant, long long* exp2, int* status,
                                  hipStream_t st);
+// The looped body of the same pass (hmm_posterior_trans_looped.hip, the frames in hmm_trans_fb_looped_step.h): any number of
+// slots, a workgroup of min(slots, SEG_MAX_WAVES) waves per stream in which a wave serves the slots w, w + waves, .. in turn;
+// the same post, P and status bit for bit.  The same plan, parameter block, w and tables, except that cs takes (frames of the
+// launch) x min(slots, 16) doubles: a copy of c_t per wave.  Dynamic LDS: 8 (2 slots + 2 K + sumN) bytes are mandatory (the
+// partial sums in both parities, the class masses of two steps, one double per composite state; pi is read in place); A, and
+// then both matrices, go behind them while the sum stays within SEG_LDS_BYTES (posteriors_trans_looped_layout: the
+// instantiation).  Returns 1 when the shape cannot be launched.
+size_t posteriors_trans_looped_lds_bytes(const SegPlanDev& pl, bool a_lds, bool w_lds);
+void posteriors_trans_looped_layout(const SegPlanDev& pl, bool* a_lds, bool* w_lds);
+int launch_loop_posteriors_trans_looped(const SegPlanDev& pl, const unsigned short* sym, const long long* offs, int S, long long a0,
+                                        const double* w, double* ahs, double* cs, double* post, double* mant, long long* exp2,
+                                        int* status, hipStream_t st);
 
 // The expected class-to-class counts under the same loop and prices (hmm_trans_estep.hip): the E-step of
 // `hmm transitions --em`.  pl, w, the scratch tables and mant / exp2 / status are launch_loop_posteriors_trans'.  acc:
@@ -327,6 +339,16 @@ void trans_estep_layout(const SegPlanDev& pl, bool c_forced, bool* c_lds, bool* 
 int launch_trans_estep(const SegPlanDev& pl, bool c_lds, bool a_lds, bool w_lds, const unsigned short* sym, const long long* offs,
                        int S, long long a0, const double* w, double* ahs, double* cs, long long* acc, double* mant, long long* exp2,
                        int* status, hipStream_t st);
+// The looped body of the same E-step (hmm_trans_estep_looped.hip): any number of slots, the workgroup and the cs table of
+// launch_loop_posteriors_trans_looped; the same acc (every limb and both counters), P and status bit for bit.  Dynamic LDS:
+// 8 (2 slots + 2 K + 2 sumN) bytes are mandatory (the looped posteriors' terms and S_t per composite state); behind them, in
+// trans_estep_layout's order and with its c_forced, the C table, A, then both matrices (trans_estep_looped_layout).  Returns 1
+// when the shape cannot be launched.
+size_t trans_estep_looped_lds_bytes(const SegPlanDev& pl, bool c_lds, bool a_lds, bool w_lds);
+void trans_estep_looped_layout(const SegPlanDev& pl, bool c_forced, bool* c_lds, bool* a_lds, bool* w_lds);
+int launch_trans_estep_looped(const SegPlanDev& pl, bool c_lds, bool a_lds, bool w_lds, const unsigned short* sym,
+                              const long long* offs, int S, long long a0, const double* w, double* ahs, double* cs, long long* acc,
+                              double* mant, long long* exp2, int* status, hipStream_t st);
 
 // The expected state-level counts of every class under the same loop and prices (hmm_loop_estep.hip): the
 // E-step of `hmm learn --loop`.  pl, w, ahs / cs and mant / exp2 / status are launch_loop_posteriors_trans'; ms: K doubles a

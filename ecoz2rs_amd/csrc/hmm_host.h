@@ -332,6 +332,14 @@ int segment_trans_body(int* body);
 bool segment_trans_looped(int body, int slots);
 int trans_check_slots(const char* who, int K, const int* Ns, int body);
 
+// The two forward-backward passes under class-to-class prices (`hmm segment --grammar-posteriors`, DESIGN.md 4.8.13, and the
+// E-step of `hmm transitions --em`, 4.8.14): trans_fb_body: ECOZ2_HMM_TRANS_FB_BODY through opt_in_body -> *body (an
+// EmbedBody); e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors (whose decode follows the same
+// choice), e2vq_hmm_transitions_estep, e2vq_hmm_train_transitions and e2vq_hmm_learn_transitions_files read it, once a call,
+// and nothing else does.  trans_fb_looped: whether a packing of `slots` runs the looped kernels under that body.
+int trans_fb_body(int* body);
+bool trans_fb_looped(int body, int slots);
+
 // A packing on the device: the parameter block, the four tables of `pk`, and the plan the kernels take.  upload() only
 // enqueues: the host vectors must outlive the stream's copies, and this struct the stream's kernels (a local is declared
 // before the DevSeqs / Stream whose stream works on it, or the function waits for that stream before it returns).

@@ -1,6 +1,7 @@
 // hmm_trans_train.cpp -- Baum-Welch for the matrix of class-to-class prices (`hmm transitions --em`,
 // e2vq_hmm_transitions_estep, e2vq_hmm_train_transitions): the grammar of the class loop re-estimated from
-// whole unlabelled streams, over the kernel of hmm_trans_estep.hip.  The host takes exp of the prices, chooses the LDS layout
+// whole unlabelled streams, over the kernel of hmm_trans_estep.hip or, above 16 wave-slots or on request
+// (ECOZ2_HMM_TRANS_FB_BODY), its looped body hmm_trans_estep_looped.hip.  The host takes exp of the prices, chooses the LDS layout
 // and the route of the count table (all before any HIP call), takes the logarithm of the (mantissa, exponent) pairs, sums
 // ln P over the streams in stream order, forms the M-step (K^2 values) and decides when to stop.  The checks, the packing, the
 // parameter block and the prices are hmm_class_loop.cpp's, the file of the matrix hmm_transitions.cpp's, the input stage
@@ -49,20 +50,34 @@ inline i64 trans_acc_words(int K) { return 2 * (i64)K * K + 2; }
 // (ECOZ2_HMM_TRANS_EM_C: lds or global; unset: LDS when the table fits next to the mandatory terms).
 struct TransPlan {
     SegPacking pk;
+    bool looped = false;  // the body of every E-step of the call (ECOZ2_HMM_TRANS_FB_BODY, read once)
+    int waves = 0;        // of a workgroup: each stores its copy of c_t
     bool c_lds = false, a_lds = false, w_lds = false;
 };
 
-int trans_plan(const char* who, const std::vector<int>& Ns, int M, TransPlan& tp)
+// body: what trans_fb_body gave.  resident: more than 16 slots are refused, word for word as before the looped body existed.
+// looped: its mandatory LDS must fit -- with segment_check_shape's caps it always does (132 096 bytes at
+// K = sum N = 4096); the check stands for the day a cap moves.
+int trans_plan(const char* who, const std::vector<int>& Ns, int M, int body, TransPlan& tp)
 {
     const int K = (int)Ns.size();
     tp.pk = pack_slots(Ns, posteriors_a_ld);
-    if (check_resident(who, tp.pk.slots, "the E-step of the class transitions has")) return 1;
-    bool forced = false;
-    if (embed_route("ECOZ2_HMM_TRANS_EM_C", &forced, &tp.c_lds)) return 1;
+    tp.looped = trans_fb_looped(body, tp.pk.slots);
+    tp.waves = tp.looped ? std::min(tp.pk.slots, (int)e2hmm::SEG_MAX_WAVES) : tp.pk.slots;
+    if (!tp.looped && check_resident(who, tp.pk.slots, "the E-step of the class transitions has")) return 1;
     e2hmm::SegPlanDev shape{};
     shape.K = K, shape.M = M, shape.sumN = tp.pk.sumN, shape.slots = tp.pk.slots, shape.a_words = tp.pk.a_words;
-    e2hmm::trans_estep_layout(shape, forced, &tp.c_lds, &tp.a_lds, &tp.w_lds);
-    const size_t lds = e2hmm::trans_estep_lds_bytes(shape, tp.c_lds, tp.a_lds, tp.w_lds);
+    // (the two bodies' formulas and decision orders have one signature)
+    const auto lds_bytes = tp.looped ? e2hmm::trans_estep_looped_lds_bytes : e2hmm::trans_estep_lds_bytes;
+    const auto layout = tp.looped ? e2hmm::trans_estep_looped_layout : e2hmm::trans_estep_layout;
+    if (tp.looped && lds_bytes(shape, false, false, false) > e2hmm::SEG_LDS_BYTES)
+        return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of the "
+                              "E-step of the class transitions (at most %zu)", who, tp.pk.slots, tp.pk.sumN, K,
+                              lds_bytes(shape, false, false, false), (size_t)e2hmm::SEG_LDS_BYTES);
+    bool forced = false;
+    if (embed_route("ECOZ2_HMM_TRANS_EM_C", &forced, &tp.c_lds)) return 1;
+    layout(shape, forced, &tp.c_lds, &tp.a_lds, &tp.w_lds);
+    const size_t lds = lds_bytes(shape, tp.c_lds, tp.a_lds, tp.w_lds);
     if (lds > e2hmm::SEG_LDS_BYTES)
         return e2vq_set_error("%s: %d classes of %d states with the count table in LDS take %zu bytes of LDS (at most %zu)", who, K,
                               tp.pk.sumN, lds, (size_t)e2hmm::SEG_LDS_BYTES);
@@ -82,16 +97,16 @@ struct TransDev {
 
     int setup(const char* who, const TransPlan& tp, const LoopModels& lm, const i64* h_offs, int S, hipStream_t st)
     {
-        const int K = lm.K(), sumN = tp.pk.sumN, slots = tp.pk.slots;
+        const int K = lm.K(), sumN = tp.pk.sumN, waves = tp.waves;
         params = trans_params(lm, tp.pk);
         if (loop.upload(tp.pk, params, K, lm.M, st) || d_offs.upload(h_offs, (size_t)S + 1, st) || sc.reserve((size_t)S) ||
             d_acc.reserve((size_t)trans_acc_words(K)) || d_w.reserve((size_t)2 * K * K) || timer.create())
             return 1;
         // the forward table of 4.8.13, bounded by whole streams in the same way
-        const i64 row = 8 * ((i64)sumN + slots);
+        const i64 row = 8 * ((i64)sumN + waves);
         i64 max_frames = 0;
         chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-        if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * slots)) {
+        if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves)) {
             const std::string why = e2vq_last_error();
             return e2vq_set_error("%s: no room for the forward table of %lld frames x %d states (%lld bytes; "
                                   "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
@@ -113,9 +128,9 @@ struct TransDev {
         // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
         for (const auto& c : chunks) {
             const int s0 = c.first, n = c.second - c.first;
-            if (e2hmm::launch_trans_estep(loop.pl, tp.c_lds, tp.a_lds, tp.w_lds, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(),
-                                          d_ah.get(), d_c.get(), d_acc.get(), sc.d_mant.get() + s0, sc.d_exp.get() + s0,
-                                          sc.d_status.get() + s0, st))
+            const auto launch = tp.looped ? e2hmm::launch_trans_estep_looped : e2hmm::launch_trans_estep;
+            if (launch(loop.pl, tp.c_lds, tp.a_lds, tp.w_lds, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), d_ah.get(), d_c.get(),
+                       d_acc.get(), sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
                 return e2vq_set_error("%s: %d wave-slots of %d states cannot be launched", who, tp.pk.slots, tp.pk.sumN);
             HIPCHK(hipGetLastError());
         }
@@ -173,8 +188,10 @@ int trans_check_args(const char* who, int K, const int* Ns, int M, const double*
                      const double* const* Bs, const void* sym, const int64_t* offs, int S, const double* lt, bool rest, LoopModels& lm,
                      TransPlan& tp)
 {
+    int body = EMBED_BODY_RESIDENT;  // (read once a call: a training keeps it over its E-steps)
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt && rest && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
-        trans_check_lt(who, K, lt) || trans_plan(who, std::vector<int>(Ns, Ns + K), M, tp) || lm.from_arrays(K, Ns, M, pis, As, Bs))
+        trans_check_lt(who, K, lt) || trans_fb_body(&body) || trans_plan(who, std::vector<int>(Ns, Ns + K), M, body, tp) ||
+        lm.from_arrays(K, Ns, M, pis, As, Bs))
         return 1;
     for (const Hmm& h : lm.models)
         if (posteriors_check_params(h)) return 1;
@@ -258,7 +275,8 @@ extern "C" int e2vq_hmm_learn_transitions_files(const char* const* model_filenam
         lm.load_checked(who, model_filenames, num_models))
         return 1;
     const int K = lm.K();
-    if (trans_plan(who, lm.Ns, lm.M, tp) || check_names(who, K, lm.names.data())) return 1;
+    int body = EMBED_BODY_RESIDENT;  // (read once, before the first E-step)
+    if (trans_fb_body(&body) || trans_plan(who, lm.Ns, lm.M, body, tp) || check_names(who, K, lm.names.data())) return 1;
     for (unsigned k = 0; k < num_models; ++k)
         if (posteriors_check_params(lm.models[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());
     // the start: the file's matrix, or every succession as likely as any other

@@ -175,7 +175,8 @@ def _kernel_ms(fn):
 
 @contextlib.contextmanager
 def _body_env(name, body):
-    """the variable `name` (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY, ECOZ2_HMM_SEGMENT_TRANS_BODY) = body ("auto", "resident" or "looped") for the
+    """the variable `name` (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY, ECOZ2_HMM_SEGMENT_TRANS_BODY,
+    ECOZ2_HMM_TRANS_FB_BODY) = body ("auto", "resident" or "looped") for the
     duration of a call; None leaves the environment alone"""
     if body is None:
         yield
@@ -189,6 +190,16 @@ def _body_env(name, body):
             del os.environ[name]
         else:
             os.environ[name] = before
+
+
+def trans_fb_body(body):
+    """a context in which ECOZ2_HMM_TRANS_FB_BODY = body ("auto", "resident" or "looped"; None leaves the environment alone):
+    the kernel body of the forward-backward passes under class-to-class prices -- the looped one
+    takes any number of wave-slots, auto picks it above 16, and the results are the same bit for bit.  It is what body= of
+    `transitions_estep`, `train_transitions` and `learn_transitions_files` and grammar_posteriors_body= of `segment_files`
+    enter; `segment_trans_posteriors` keeps its parameters and is called inside it:
+        with hmm.trans_fb_body("auto"): hmm.segment_trans_posteriors(...)"""
+    return _body_env("ECOZ2_HMM_TRANS_FB_BODY", body)
 
 
 def set_random_seed(seed):
@@ -814,7 +825,9 @@ class SegmentTransStream(SegmentStream):
 def segment_trans_posteriors(models, sym, offs, ln_trans, device=0):
     """`segment_posteriors` under the K x K prices of `segment_trans`: P(class at frame t | the whole
     stream) under the loop `segment_trans` decodes; ln_trans[f][k] <= 0 (or -inf) as there; the classes must pack into at
-    most 16 wave-slots (there is no looped body).  sym: a numpy array or a device tensor.  -> the dict of
+    most 16 wave-slots unless the looped body is chosen (ECOZ2_HMM_TRANS_FB_BODY; `trans_fb_body` sets it for a call: the looped
+    body takes any number of slots, auto picks it above 16, the posteriors are the same bit for bit).  sym: a numpy array or a
+    device tensor.  -> the dict of
     `segment_posteriors`: post (sum T_s, K), per stream log_prob and status"""
     K = len(models)
     ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
@@ -910,10 +923,13 @@ def transitions_acc_words(K):
     return int(lib.e2vq_hmm_transitions_acc_words(int(K)))
 
 
-def transitions_estep(models, sym, offs, ln_trans, acc=None, device=0):
+def transitions_estep(models, sym, offs, ln_trans, acc=None, device=0, body=None):
     """one E-step of Baum-Welch for the class-to-class prices: models, sym (a numpy array or a device tensor),
     offs and ln_trans as `segment_trans_posteriors` takes them -> dict acc (int64, 2 K^2 + 2: the limb pairs of the expected
-    counts C[f][k], then the streams used and skipped; added to `acc` where one is given), per stream log_prob and status"""
+    counts C[f][k], then the streams used and skipped; added to `acc` where one is given), per stream log_prob and status.
+    body: "auto", "resident" or "looped" (ECOZ2_HMM_TRANS_FB_BODY for this call, as `trans_fb_body` sets it: resident takes at
+    most 16 wave-slots of classes, looped any number, auto the looped one above 16; the same counts bit for bit); None leaves
+    the environment alone"""
     c_args, lt, on_device, S, _keep = _trans_args(models, sym, offs, ln_trans)
     words = transitions_acc_words(len(models))
     if acc is None:
@@ -921,7 +937,8 @@ def transitions_estep(models, sym, offs, ln_trans, acc=None, device=0):
     elif not (isinstance(acc, np.ndarray) and acc.dtype == np.int64 and acc.flags.c_contiguous and acc.size == words):
         raise ValueError(f"acc must be a contiguous int64 array of {words} words")
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_transitions_estep(device, *c_args, lt.ctypes.data, acc.ctypes.data, lp.ctypes.data, st.ctypes.data, on_device))
+    with trans_fb_body(body):
+        check(lib.e2vq_hmm_transitions_estep(device, *c_args, lt.ctypes.data, acc.ctypes.data, lp.ctypes.data, st.ctypes.data, on_device))
     return dict(acc=acc, log_prob=lp[:S], status=st[:S])
 
 
@@ -929,10 +946,12 @@ def transitions_estep_last_kernel_ms():
     return _kernel_ms(lib.e2vq_hmm_transitions_estep_last_kernel_ms)
 
 
-def train_transitions(models, sym, offs, ln_p=None, ln_switch=0.0, alpha=1.0, val_auto=0.3, max_iterations=-1, callback=None, device=0):
+def train_transitions(models, sym, offs, ln_p=None, ln_switch=0.0, alpha=1.0, val_auto=0.3, max_iterations=-1, callback=None, device=0,
+                      body=None):
     """Baum-Welch for the class-to-class prices to its stop: ln_p is the matrix as a transitions file holds it
     (None: every entry log(1 / K)), the effective price of an E-step ln_p + ln_switch -> (the trained ln_p (K, K), the sum of
-    ln P per E-step); callback(var: str, val: float) per E-step"""
+    ln P per E-step); callback(var: str, val: float) per E-step; body as `transitions_estep` takes it (read once, before the first
+    E-step)"""
     K = len(models)
     if ln_p is None:
         ln_p = np.full((K, K), math.log(1.0 / K)) if K else np.zeros((0, 0))
@@ -941,21 +960,23 @@ def train_transitions(models, sym, offs, ln_p=None, ln_switch=0.0, alpha=1.0, va
     hist = np.zeros(cap)
     n = C.c_int(0)
     cb = HMM_LEARN_CALLBACK((lambda v, x: callback(v.decode(), x)) if callback else (lambda _v, _x: None))
-    check(lib.e2vq_hmm_train_transitions(device, *c_args, lt.ctypes.data, float(ln_switch), float(alpha), float(val_auto),
-                                         int(max_iterations), hist.ctypes.data, cap, C.byref(n), cb, on_device))
+    with trans_fb_body(body):
+        check(lib.e2vq_hmm_train_transitions(device, *c_args, lt.ctypes.data, float(ln_switch), float(alpha), float(val_auto),
+                                             int(max_iterations), hist.ctypes.data, cap, C.byref(n), cb, on_device))
     return lt, hist[:n.value].copy()
 
 
 def learn_transitions_files(model_filenames, input_filenames, out_csv, ln_switch, init=None, alpha=1.0, val_auto=0.3, max_iterations=-1,
-                            codebook=None, P=36, W_ms=45, O_ms=15):
+                            codebook=None, P=36, W_ms=45, O_ms=15, body=None):
     """`hmm transitions --em`: the transitions file of the models' classes by Baum-Welch from the inputs (.wav,
-    .prd or .seq), from the file `init` or the uniform matrix; writes out_csv and <out_csv>.em.csv"""
+    .prd or .seq), from the file `init` or the uniform matrix; writes out_csv and <out_csv>.em.csv; body as `transitions_estep` takes it"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
-    check(lib.e2vq_hmm_learn_transitions_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
-                                               len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                               str(init).encode() if init else None, float(alpha), float(val_auto), int(max_iterations),
-                                               str(out_csv).encode()))
+    with trans_fb_body(body):
+        check(lib.e2vq_hmm_learn_transitions_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                   len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                   str(init).encode() if init else None, float(alpha), float(val_auto),
+                                                   int(max_iterations), str(out_csv).encode()))
 
 
 def loop_estep(models, sym, offs, ln_trans, acc_trans=None, device=0):
@@ -1031,18 +1052,20 @@ def learn_loop_files(model_filenames, input_filenames, out_dir, ln_switch, class
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
                   frame_posteriors=None, class_transitions=None, continuous=None, body=None, grammar_posteriors=False,
-                  grammar_continuous=None, grammar_body=None):
+                  grammar_continuous=None, grammar_body=None, grammar_posteriors_body=None):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
     table for every input; body as `segment_posteriors` takes it.  class_transitions (4.8.8): a transitions file whose prices are added to ln_switch;
     grammar_posteriors (4.8.13): with class_transitions, the posteriors under those prices, reported as posteriors reports
-    them (frame_posteriors is then taken too; there is one body).  continuous
+    them (frame_posteriors is then taken too); grammar_posteriors_body ("auto", "resident" or "looped", as `transitions_estep`
+    takes body) chooses their kernel body, and the decode of the same input follows it; it needs grammar_posteriors.  continuous
     (4.8.9): the name of the one recording whose consecutive pieces the inputs are -- one block, and with `csv` (a directory
     or a .csv file) one CSV, <csv>/<name>.csv.  grammar_continuous (4.8.15): with class_transitions, the same under the
     file's prices; it excludes continuous, the posteriors, frame_posteriors and body.  grammar_body ("auto", "resident" or
     "looped", as `segment_trans` takes body): the kernel body of the decoder under class_transitions, with or without
-    grammar_continuous; it needs class_transitions and excludes grammar_posteriors, which has the resident body only"""
+    grammar_continuous; it needs class_transitions and excludes grammar_posteriors, whose one choice is
+    grammar_posteriors_body"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     if grammar_body is not None:
@@ -1050,6 +1073,8 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
             raise ValueError("grammar_body needs class_transitions")
         if grammar_posteriors:
             raise ValueError("grammar_body excludes grammar_posteriors (there is one body)")
+    if grammar_posteriors_body is not None and not grammar_posteriors:
+        raise ValueError("grammar_posteriors_body needs grammar_posteriors=True")
     if grammar_continuous is not None:
         if continuous is not None or posteriors or grammar_posteriors or frame_posteriors is not None or body is not None:
             raise ValueError("grammar_continuous excludes continuous, posteriors, grammar_posteriors, frame_posteriors and body")
@@ -1078,10 +1103,11 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
         if posteriors:
             raise ValueError("class_transitions and posteriors exclude one another")
         if grammar_posteriors:
-            check(lib.e2vq_hmm_segment_trans_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
-                                                              len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                                              str(class_transitions).encode(), str(csv).encode() if csv else None,
-                                                              str(frame_posteriors).encode() if frame_posteriors is not None else None))
+            with trans_fb_body(grammar_posteriors_body):
+                check(lib.e2vq_hmm_segment_trans_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f,
+                                                                  len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                                  str(class_transitions).encode(), str(csv).encode() if csv else None,
+                                                                  str(frame_posteriors).encode() if frame_posteriors is not None else None))
             return
         with _body_env("ECOZ2_HMM_SEGMENT_TRANS_BODY", grammar_body):
             check(lib.e2vq_hmm_segment_trans_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f,

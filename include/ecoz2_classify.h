@@ -387,8 +387,9 @@ int e2vq_hmm_segment_files_posteriors(const char *const *model_filenames, unsign
  * With every entry equal to ln_switch, d, ln P* and exit_score on entered frames are e2vq_hmm_segment's bit for bit.
  * The body.  ECOZ2_HMM_SEGMENT_TRANS_BODY chooses the kernel body in e2vq_hmm_segment_trans, e2vq_hmm_segment_trans_files,
  * e2vq_hmm_segment_trans_stream_open (a session fixes its body at open) and e2vq_hmm_segment_trans_continuous_files; no other
- * entry point reads it -- e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors (whose decode stays
- * resident too), e2vq_hmm_transitions_estep and e2vq_hmm_loop_estep keep their refusals of more than 16 wave-slots.  Unset, empty
+ * entry point reads it -- e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors (whose decode follows
+ * their own variable) and e2vq_hmm_transitions_estep read ECOZ2_HMM_TRANS_FB_BODY instead (4.8.13 below), and
+ * e2vq_hmm_loop_estep keeps its refusal of more than 16 wave-slots.  Unset, empty
  * or "resident": as above, more than 16 wave-slots are refused with "the classes take %d wave-slots of 64 lanes (at most 16:
  * the class-transition decoder has no looped body)".  "looped": the looped body for every packing, in which a wave serves
  * several slots in turn.  "auto": resident up to 16 slots, looped above.  Any other value is refused before any HIP call:
@@ -438,8 +439,9 @@ int e2vq_hmm_transitions_files(const char *const *model_filenames, unsigned num_
  * with w[f][k] = exp(lt[f][k]) (the C library's exp on the host; -inf gives 0).  Refused before any HIP call: what
  * e2vq_hmm_segment_posteriors refuses for the models (a negative, NaN or infinite parameter included), what
  * e2vq_hmm_segment_trans refuses for lt (NaN or > 0), and a packing of more than 16 wave-slots ("the classes take %d
- * wave-slots of 64 lanes (at most 16: the posteriors under class-to-class prices have no looped body)"; only the resident
- * layout exists, and ECOZ2_HMM_POSTERIOR_BODY is not read).  The arithmetic is scaled and linear, every operation one IEEE
+ * wave-slots of 64 lanes (at most 16: the posteriors under class-to-class prices have no looped body)") unless
+ * ECOZ2_HMM_TRANS_FB_BODY chooses the looped body (the last paragraph; ECOZ2_HMM_POSTERIOR_BODY and
+ * ECOZ2_HMM_SEGMENT_TRANS_BODY are not read).  The arithmetic is scaled and linear, every operation one IEEE
  * double operation in a fixed order, no fma (DESIGN.md 4.8.13 states it; tests/hmm_trans_posterior_restatement.py restates
  * it; the GPU matches it bit for bit).  With CS_k the sum over the states of class k in state order:
  *   x_0[k][j] = pi_k[j] B_k[j][o_0];  S[f] = CS_f(ah_{t-1});  m[k] = sum_f S[f] w[f][k] (f in class order);
@@ -450,7 +452,20 @@ int e2vq_hmm_transitions_files(const char *const *model_filenames, unsigned num_
  * Outputs, status and the empty stream are e2vq_hmm_segment_posteriors'.  With every price -inf the figures are those of
  * e2vq_hmm_segment_posteriors at ln_switch = -inf bit for bit; with every price one finite value they agree within rounding
  * (4.8.7 replaces the sum of S by 1).  ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds the per-launch forward table as in 4.8.7.
- * One device.  sym_on_device as in e2vq_hmm_segment. */
+ * One device.  sym_on_device as in e2vq_hmm_segment.
+ * The body.  ECOZ2_HMM_TRANS_FB_BODY chooses the kernel body of the two forward-backward passes under the prices, these
+ * posteriors and the E-step of 4.8.14, in e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors,
+ * e2vq_hmm_transitions_estep, e2vq_hmm_train_transitions and e2vq_hmm_learn_transitions_files (a training reads it once,
+ * before its first E-step); no other entry point reads it.  Unset, empty or "resident": as above, more than 16 wave-slots are
+ * refused with the words above (4.8.14: "... the E-step of the class transitions has no looped body").  "looped": the looped
+ * body for every packing, min(slots, 16) waves of which each serves several slots in turn.  "auto": resident up to 16 slots,
+ * looped above.  Any other value is refused before any HIP call: "ECOZ2_HMM_TRANS_FB_BODY=<v>: auto, resident or looped".  The
+ * looped body is the same operations in the same order: post, acc, log_prob and status are the same bits under either.  It keeps
+ * 8 (2 slots + 2 K + sum N) bytes in LDS for the posteriors and 8 (2 slots + 2 K + 2 sum N) for the E-step; a packing whose bytes
+ * exceeded the 160 KB would be refused before any HIP call ("%d wave-slots, %d states and %d classes take %zu bytes of LDS in
+ * the looped body of the posteriors under class-to-class prices" / "... of the E-step of the class transitions"), which the
+ * limits on the number of states (at most 99 328 and 132 096 bytes, at K = sum N = 4096) keep out of reach.  The forward table's
+ * c_t takes one double per frame and wave, not per slot, under the looped body. */
 int e2vq_hmm_segment_trans_posteriors(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
                                       const double *const *Bs, const void *sym, const int64_t *offs, int S, const double *lt,
                                       double *post, double *log_prob, int *status, int sym_on_device);
@@ -460,7 +475,8 @@ int e2vq_hmm_segment_trans_posteriors_last_kernel_ms(float *ms);
  * posteriors run on the same device buffer under the same effective prices, and the report gains what
  * e2vq_hmm_segment_report_posteriors adds (the CSV columns posterior,min_posterior, " p=%.3f", and with frames_dir -- may be
  * NULL -- the per-frame table <frames_dir>/<input's base name>.csv); the first eight CSV columns are
- * e2vq_hmm_segment_trans_files' byte for byte. */
+ * e2vq_hmm_segment_trans_files' byte for byte.  ECOZ2_HMM_TRANS_FB_BODY is the one choice of body here: where it picks the
+ * looped posteriors the decode runs its looped body too (ECOZ2_HMM_SEGMENT_TRANS_BODY is not read). */
 int e2vq_hmm_segment_trans_files_posteriors(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
                                             const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
                                             double ln_switch, const char *transitions_csv, const char *csv_dir_or_file,
@@ -469,9 +485,10 @@ int e2vq_hmm_segment_trans_files_posteriors(const char *const *model_filenames, 
 /* ---- Baum-Welch for the class-to-class prices ----------------------------------------------------------
  * `hmm transitions --em`: the matrix of e2vq_hmm_segment_trans re-estimated from whole unlabelled streams.  The model, the
  * inputs and the refusals are e2vq_hmm_segment_trans_posteriors': K models sharing M, N_k <= 64, S streams in sym / offs, lt
- * (row-major K x K, each entry <= 0 or -inf) with w[f][k] = exp(lt[f][k]) taken by the C library on the host.  Only the
- * resident layout exists: a packing of more than 16 wave-slots is refused before any HIP call ("the classes take %d
- * wave-slots of 64 lanes (at most 16: the E-step of the class transitions has no looped body)").  Nothing transcendental runs
+ * (row-major K x K, each entry <= 0 or -inf) with w[f][k] = exp(lt[f][k]) taken by the C library on the host.  A packing
+ * of more than 16 wave-slots is refused before any HIP call ("the classes take %d
+ * wave-slots of 64 lanes (at most 16: the E-step of the class transitions has no looped body)") unless ECOZ2_HMM_TRANS_FB_BODY
+ * chooses the looped body (4.8.13 above: "The body").  Nothing transcendental runs
  * on the device; every operation is one IEEE double operation in a fixed order, no fma (DESIGN.md 4.8.14 states it;
  * tests/hmm_transitions_em_restatement.py restates it; the GPU matches it bit for bit).
  * E-step.  Forward, scaling, status, log_prob and backward are 4.8.13's word for word (S, m, x, c_t, ah, u, R, r, bh, the same

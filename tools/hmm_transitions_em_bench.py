@@ -9,6 +9,10 @@ random models of N states each, the planted matrix of 4.8.8 plus --ln-switch (de
 The comparator is code this feature does not touch; the commit before it cannot compute the counts, so no speed-up is
 claimed.  --warmup + --reps of each.  Kernel times come from one `rocprofv3 --kernel-trace` run of this script (--run) per N,
 without counters; each call's own HIP-event time is recorded next to it.  median and min .. max over the repetitions.
+--bodies (a list of auto, resident, looped: ECOZ2_HMM_TRANS_FB_BODY of both calls): a run per N and body, by_N[N][body], and
+looped_over_resident where both ran -- the price of the looped body where the resident one runs.  A packing the body refuses
+(more than 16 wave-slots under resident: N = 64 at K = 20) is recorded as refused, with the library's message.  Without
+--bodies, one run per N with the environment's body, by_N[N], as before.
 """
 import argparse
 import csv
@@ -43,9 +47,19 @@ def run(args):
     models, sym, lt = workload(args.n, args.m, args.k, args.t, args.ln_switch)
     offs = np.array([0, len(sym)], dtype=np.int64)
     out = {}
-    calls = (("estep", lambda: e.hmm.transitions_estep(models, sym, offs, lt), e.hmm.transitions_estep_last_kernel_ms),
-             ("trans_posteriors", lambda: e.hmm.segment_trans_posteriors(models, sym, offs, lt),
-              e.hmm.segment_trans_posteriors_last_kernel_ms))
+
+    def trans_posteriors():
+        with e.hmm.trans_fb_body(args.body):
+            return e.hmm.segment_trans_posteriors(models, sym, offs, lt)
+
+    if args.body:
+        try:
+            e.hmm.transitions_estep(models, sym[:8], [0, 8], lt, body=args.body)
+        except e.Ecoz2Error as err:
+            print(json.dumps(dict(refused=str(err))))
+            return
+    calls = (("estep", lambda: e.hmm.transitions_estep(models, sym, offs, lt, body=args.body), e.hmm.transitions_estep_last_kernel_ms),
+             ("trans_posteriors", trans_posteriors, e.hmm.segment_trans_posteriors_last_kernel_ms))
     for kind, call, event in calls:
         ts, ev = [], []
         for _ in range(args.warmup + args.reps):
@@ -58,12 +72,13 @@ def run(args):
     print(json.dumps(out))
 
 
-def kernel_ms(trace, calls, warmup):
-    """per kind the kernel time of each call"""
+def kernel_ms(trace, calls, warmup, skip=None):
+    """per kind the kernel time of each call; skip[kind]: launches before the measured calls (the probe of `run`)"""
     rows = list(csv.DictReader(open(trace)))
     out = {}
     for kind, rx in KINDS.items():
         sel = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in rows if rx.search(r["Kernel_Name"]))
+        sel = sel[(skip or {}).get(kind, 0):]
         if not sel or len(sel) % calls:
             out[kind] = dict(error=f"{len(sel)} launches for {calls} calls")
             continue
@@ -86,34 +101,51 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=600)
+    ap.add_argument("--body", help="(internal) the body of the run")
+    ap.add_argument("--bodies", help="auto, resident and / or looped, comma-separated: a run per N and body")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.run:
         return run(args)
     rec = dict(tool="tools/hmm_transitions_em_bench.py", M=args.m, K=args.k, T=args.t, ln_switch=args.ln_switch, reps=args.reps,
                warmup=args.warmup, by_N={})
+    bodies = args.bodies.split(",") if args.bodies else [None]
+    if args.bodies:
+        rec["bodies"] = bodies
     for N in [int(x) for x in args.ns.split(",")]:
-        with tempfile.TemporaryDirectory() as d:
-            cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--",
-                   sys.executable, os.path.abspath(__file__), "--run", "--n", str(N), "--m", str(args.m), "--k", str(args.k),
-                   "--t", str(args.t), "--ln-switch", str(args.ln_switch), "--reps", str(args.reps), "--warmup", str(args.warmup)]
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
-            if r.returncode != 0:
-                sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-                raise SystemExit(f"N = {N}: rocprofv3 run failed with status {r.returncode}")
-            host = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-            traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-            if len(traces) != 1:
-                raise SystemExit(f"N = {N}: expected one kernel trace, found {traces}")
-            k = kernel_ms(traces[0], args.warmup + args.reps, args.warmup)
-            for kind in k:
-                k[kind].update(host[kind])
-            ent = dict(kinds=k)
-            if all("kernel_ms" in k[kind] for kind in KINDS):
-                ent["over_posteriors"] = k["estep"]["kernel_ms"] / k["trans_posteriors"]["kernel_ms"]
-                ent["over_posteriors_event"] = k["estep"]["event_ms"] / k["trans_posteriors"]["event_ms"]
-        rec["by_N"][str(N)] = ent
-        print(json.dumps({str(N): ent}), flush=True)
+        ents = {}
+        for body in bodies:
+            with tempfile.TemporaryDirectory() as d:
+                cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--",
+                       sys.executable, os.path.abspath(__file__), "--run", "--n", str(N), "--m", str(args.m), "--k", str(args.k),
+                       "--t", str(args.t), "--ln-switch", str(args.ln_switch), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+                if body:
+                    cmd += ["--body", body]
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout, cwd=ROOT)
+                if r.returncode != 0:
+                    sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+                    raise SystemExit(f"N = {N}: rocprofv3 run failed with status {r.returncode}")
+                host = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+                if "refused" in host:
+                    ents[body] = host
+                    continue
+                traces = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+                if len(traces) != 1:
+                    raise SystemExit(f"N = {N}: expected one kernel trace, found {traces}")
+                k = kernel_ms(traces[0], args.warmup + args.reps, args.warmup, {"estep": 1} if body else None)  # (the probe)
+                for kind in k:
+                    k[kind].update(host[kind])
+                ent = dict(kinds=k)
+                if all("kernel_ms" in k[kind] for kind in KINDS):
+                    ent["over_posteriors"] = k["estep"]["kernel_ms"] / k["trans_posteriors"]["kernel_ms"]
+                    ent["over_posteriors_event"] = k["estep"]["event_ms"] / k["trans_posteriors"]["event_ms"]
+                ents[body] = ent
+        if args.bodies:
+            ms = {b: x["kinds"]["estep"].get("kernel_ms") for b, x in ents.items() if "kinds" in x}
+            if ms.get("looped") and ms.get("resident"):
+                ents["looped_over_resident"] = ms["looped"] / ms["resident"]
+        rec["by_N"][str(N)] = ents if args.bodies else ents[None]
+        print(json.dumps({str(N): rec["by_N"][str(N)]}), flush=True)
     line = json.dumps(rec)
     print(line)
     if args.out:
