@@ -815,6 +815,14 @@ static int hmm_classify_grid(const std::string& m_arg, const std::string& cls, c
 }
 
 // `hmm scan`: the trained models over sliding windows of whole recordings
+// the value of a flag that chooses a kernel body: auto, resident or looped; anything else is named on stderr under `prefix`
+static bool body_value_ok(const char* prefix, const char* flag, const std::string& v)
+{
+    if (v == "auto" || v == "resident" || v == "looped") return true;
+    fprintf(stderr, "%s: %s %s: auto, resident or looped\n", prefix, flag, v.c_str());
+    return false;
+}
+
 static int hmm_scan_cmd(int argc, char** argv)
 {
     int P = 36, W = 45, O = 15;
@@ -954,10 +962,7 @@ static int hmm_segment_cmd(int argc, char** argv)
             fprintf(stderr, "hmm segment: --grammar-posteriors has the resident body only: not with --grammar-body\n");
             return 2;
         }
-        if (grammar_body != "auto" && grammar_body != "resident" && grammar_body != "looped") {
-            fprintf(stderr, "hmm segment --class-transitions: --grammar-body %s: auto, resident or looped\n", grammar_body.c_str());
-            return 2;
-        }
+        if (!body_value_ok("hmm segment --class-transitions", "--grammar-body", grammar_body)) return 2;
         setenv("ECOZ2_HMM_SEGMENT_TRANS_BODY", grammar_body.c_str(), 1);
     }
     if (have_post_body) {  // the body of the posteriors under the prices (ECOZ2_HMM_TRANS_FB_BODY), set in this process before the call
@@ -966,10 +971,7 @@ static int hmm_segment_cmd(int argc, char** argv)
                             "of the posteriors under the prices)\n");
             return 2;
         }
-        if (post_body != "auto" && post_body != "resident" && post_body != "looped") {
-            fprintf(stderr, "hmm segment --grammar-posteriors: --grammar-posteriors-body %s: auto, resident or looped\n", post_body.c_str());
-            return 2;
-        }
+        if (!body_value_ok("hmm segment --grammar-posteriors", "--grammar-posteriors-body", post_body)) return 2;
     }
     if (grammar_continuous) {  // (its own refusals first: the ones below speak of the other modes)
         if (continuous || posteriors || grammar || !frames_dir.empty() || !body.empty()) {
@@ -990,10 +992,7 @@ static int hmm_segment_cmd(int argc, char** argv)
     }
     if (!body.empty()) {  // the body of the posteriors (ECOZ2_HMM_POSTERIOR_BODY), set in this process before the call
         if (!posteriors) { fprintf(stderr, "hmm segment: --body <auto|resident|looped> needs --posteriors\n"); return 2; }
-        if (body != "auto" && body != "resident" && body != "looped") {
-            fprintf(stderr, "hmm segment --posteriors: --body %s: auto, resident or looped\n", body.c_str());
-            return usage();
-        }
+        if (!body_value_ok("hmm segment --posteriors", "--body", body)) return usage();
         setenv("ECOZ2_HMM_POSTERIOR_BODY", body.c_str(), 1);
     }
     if (!transitions.empty() && posteriors) {
@@ -1091,10 +1090,7 @@ static int hmm_transitions_em_cmd(int argc, char** argv)
         else return usage();
     }
     if (have_body) {  // the E-step's body (ECOZ2_HMM_TRANS_FB_BODY), set in this process before the call
-        if (body != "auto" && body != "resident" && body != "looped") {
-            fprintf(stderr, "hmm transitions --em: --body %s: auto, resident or looped\n", body.c_str());
-            return 2;
-        }
+        if (!body_value_ok("hmm transitions --em", "--body", body)) return 2;
         setenv("ECOZ2_HMM_TRANS_FB_BODY", body.c_str(), 1);
     }
     if (models.empty()) { fprintf(stderr, "hmm transitions --em: --models <files|dirs>... is required\n"); return usage(); }
@@ -1301,10 +1297,7 @@ static int hmm_learn_embedded_cmd(int argc, char** argv)
         else return usage();
     }
     if (!body.empty()) {  // the E-step's body (ECOZ2_HMM_EMBED_BODY), set in this process before the call
-        if (body != "auto" && body != "resident" && body != "looped") {
-            fprintf(stderr, "hmm learn --embedded: --body %s: auto, resident or looped\n", body.c_str());
-            return usage();
-        }
+        if (!body_value_ok("hmm learn --embedded", "--body", body)) return usage();
         setenv("ECOZ2_HMM_EMBED_BODY", body.c_str(), 1);
     }
     if (models.empty()) { fprintf(stderr, "hmm learn --embedded: --models <files|dirs>... is required\n"); return usage(); }

@@ -21,7 +21,7 @@ int post_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int
               const uint8_t* optional, double ln_switch, PostPlan& pp)
 {
     if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the alignment posteriors have a resident body only", false,
-                   EMBED_BODY_RESIDENT, pp))
+                   LoopBody::Resident, pp))
         return 1;
     pp.occ_at.assign((size_t)S + 1, 0);
     for (int s = 0; s < S; ++s) pp.occ_at[(size_t)s + 1] = pp.occ_at[(size_t)s] + (offs[s + 1] - offs[s]) * pp.ap.streams[(size_t)s].L;
@@ -101,7 +101,7 @@ int post_device(const char* who, const PostPlan& pp, const LoopModels& lm, const
         if (w[i] && nunits > 0) HIPCHK(hipMemcpyAsync(w[i], d_w.get() + (size_t)i * nunits, (size_t)nunits * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (timer.elapsed_ms(&g_align_post_kernel_ms)) return 1;
-    for (int s = 0; s < S; ++s) sc.get((size_t)s, nullptr, nullptr, out.status ? out.status + s : nullptr, out.log_prob ? out.log_prob + s : nullptr);
+    sc.get_all((size_t)S, out.status, out.log_prob);
     return 0;
 }
 
@@ -232,11 +232,7 @@ extern "C" int e2vq_hmm_align_files_posteriors(const char* const* model_filename
     if (tr.set_filler(who, fm, filler_class)) return 1;
     if (fm.logs(model_filenames)) return 1;
     const std::string fdir = frames_dir && *frames_dir ? frames_dir : "";
-    auto frames_csv = [&](const char* path) { return fdir + "/" + e2vq_io::basename_noext(path) + ".csv"; };
-    for (int f = 0; f < num_inputs && !fdir.empty(); ++f)
-        for (int g = 0; g < f; ++g)
-            if (input_filenames[f] && input_filenames[g] && frames_csv(input_filenames[g]) == frames_csv(input_filenames[f]))
-                return e2vq_set_error("%s and %s would both write %s", input_filenames[g], input_filenames[f], frames_csv(input_filenames[f]).c_str());
+    if (frames_csv_distinct(fdir, input_filenames, num_inputs)) return 1;
     SymInputs si;
     if (sym_inputs_check(who, fm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, si)) return 1;
     for (int f = 0; f < num_inputs; ++f) {
@@ -285,7 +281,7 @@ extern "C" int e2vq_hmm_align_files_posteriors(const char* const* model_filename
             return 1;
         // (a path of log-probability > -inf whose linear products underflow to 0 leaves status 1 here: every posterior is 0.0)
         if (pstatus != 0) fprintf(stderr, "%s: the posteriors are all 0: the scaled forward pass found no mass (status %d)\n", in.path.c_str(), pstatus);
-        const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
+        const std::string fcsv = fdir.empty() ? "" : frames_csv_path(fdir, in.path.c_str());
         if (e2vq_hmm_align_report_posteriors(in.path.c_str(), T, K, fm.names.data(), W_ms, O_ms, L, u, o, begin.data(), end.data(),
                                              score.data(), lp, ln_switch, path.data(), post.data(), w0.data(), w1.data(), w2.data(),
                                              ref.data(), in.csv.empty() ? nullptr : in.csv.c_str(), fcsv.empty() ? nullptr : fcsv.c_str()))

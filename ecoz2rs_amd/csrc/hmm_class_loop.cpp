@@ -4,8 +4,10 @@
 // request, hmm_segment_trans_looped.hip: ECOZ2_HMM_SEGMENT_TRANS_BODY) with the posteriors under that
 // matrix (`--grammar-posteriors`, 4.8.13, hmm_posterior_trans.hip and, above 16 wave-slots or on request,
 // hmm_posterior_trans_looped.hip: ECOZ2_HMM_TRANS_FB_BODY), with their reports and their
-// array and file entry points; and what every class-loop decoder shares (hmm_host.h): the shape checks, the packing into
-// wave-slots, the models with their logarithms, the parameter block and the device side of a packing.
+// array and file entry points (one file form, segment_files, for all four of them); and what every class-loop pass shares
+// (hmm_host.h): the shape checks, the packing into wave-slots, the models with their logarithms, the parameter block, the
+// device side of a packing, and for the passes with a looped body the choice of the body (LoopBody, opt_in_body, runs_looped,
+// body_waves), the slot check (check_body_slots) and the forward table (ForwardTable).
 #include "hmm_host.h"
 
 namespace e2hmm_host {
@@ -142,15 +144,33 @@ int loop_body_looped(const char* env_name, int slots, bool* looped)
     return 0;
 }
 
-int opt_in_body(const char* env_name, int* body)
+int opt_in_body(const char* env_name, LoopBody* body)
 {
     const char* v = getenv(env_name);
-    *body = EMBED_BODY_RESIDENT;
+    *body = LoopBody::Resident;
     if (!v || !*v || strcmp(v, "resident") == 0) return 0;
-    if (strcmp(v, "looped") == 0) *body = EMBED_BODY_LOOPED;
-    else if (strcmp(v, "auto") == 0) *body = EMBED_BODY_AUTO;
+    if (strcmp(v, "looped") == 0) *body = LoopBody::Looped;
+    else if (strcmp(v, "auto") == 0) *body = LoopBody::Auto;
     else return e2vq_set_error("%s=%s: auto, resident or looped", env_name, v);
     return 0;
+}
+
+int posteriors_body(LoopBody* body) { return opt_in_body("ECOZ2_HMM_POSTERIOR_BODY", body); }
+int segment_trans_body(LoopBody* body) { return opt_in_body("ECOZ2_HMM_SEGMENT_TRANS_BODY", body); }
+int trans_fb_body(LoopBody* body) { return opt_in_body("ECOZ2_HMM_TRANS_FB_BODY", body); }
+
+bool runs_looped(LoopBody body, int slots)
+{
+    return body == LoopBody::Looped || (body == LoopBody::Auto && slots > e2hmm::SEG_MAX_WAVES);
+}
+
+int body_waves(bool looped, int slots) { return looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots; }
+
+e2hmm::SegPlanDev loop_shape(const SegPacking& pk, int K, int M)
+{
+    e2hmm::SegPlanDev shape{};
+    shape.K = K, shape.M = M, shape.sumN = pk.sumN, shape.slots = pk.slots, shape.a_words = pk.a_words;
+    return shape;
 }
 
 int ClassLoopDev::upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st)
@@ -175,37 +195,60 @@ int check_resident(const char* who, int slots, const char* what_has)
     return 0;
 }
 
-// the body of the decoder under class-to-class prices (ECOZ2_HMM_SEGMENT_TRANS_BODY): resident (at most 16 slots) unless the
-// caller opts into the looped one
-int segment_trans_body(int* body) { return opt_in_body("ECOZ2_HMM_SEGMENT_TRANS_BODY", body); }
-
-bool segment_trans_looped(int body, int slots)
+int check_body_slots(const char* who, const SegPacking& pk, int K, LoopBody body, const char* resident_has, const char* looped_of,
+                     size_t looped_lds, bool classes)
 {
-    return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
+    if (!runs_looped(body, pk.slots)) return check_resident(who, pk.slots, resident_has);
+    if (looped_lds <= e2hmm::SEG_LDS_BYTES) return 0;
+    if (!classes)
+        return e2vq_set_error("%s: %d wave-slots and %d states take %zu bytes of LDS in the looped body of %s (at most %zu)", who,
+                              pk.slots, pk.sumN, looped_lds, looped_of, (size_t)e2hmm::SEG_LDS_BYTES);
+    return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of %s (at most %zu)",
+                          who, pk.slots, pk.sumN, K, looped_lds, looped_of, (size_t)e2hmm::SEG_LDS_BYTES);
 }
 
-// the body of the forward-backward passes under class-to-class prices (ECOZ2_HMM_TRANS_FB_BODY): resident (at most 16 slots)
-// unless the caller opts into the looped one
-int trans_fb_body(int* body) { return opt_in_body("ECOZ2_HMM_TRANS_FB_BODY", body); }
-
-bool trans_fb_looped(int body, int slots)
-{
-    return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
-}
-
-// (host only) resident: at most 16 slots.  looped: the mandatory LDS of hmm_segment_trans_looped.hip must fit -- with
-// segment_check_shape's caps it always does (147 712 bytes at K = sum N = 4096); the check stands for the day
-// a cap moves.
-int trans_check_slots(const char* who, int K, const int* Ns, int body)
+// the mandatory LDS of hmm_segment_trans_looped.hip (147 712 bytes at K = sum N = 4096)
+int trans_check_slots(const char* who, int K, const int* Ns, LoopBody body)
 {
     const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K));
-    if (!segment_trans_looped(body, pk.slots)) return check_resident(who, pk.slots, "the class-transition decoder has");
-    e2hmm::SegPlanDev shape{};
-    shape.K = K, shape.slots = pk.slots, shape.sumN = pk.sumN;
-    const size_t need = e2hmm::segment_trans_looped_lds_bytes(shape, false, false);
-    if (need > e2hmm::SEG_LDS_BYTES)
-        return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of the "
-                              "class-transition decoder (at most %zu)", who, pk.slots, pk.sumN, K, need, (size_t)e2hmm::SEG_LDS_BYTES);
+    const e2hmm::SegPlanDev shape = loop_shape(pk, K);
+    return check_body_slots(who, pk, K, body, "the class-transition decoder has", "the class-transition decoder",
+                            e2hmm::segment_trans_looped_lds_bytes(shape, false, false));
+}
+
+std::vector<double> trans_transposed(int K, const double* lt)
+{
+    std::vector<double> ltT((size_t)K * K);
+    for (int f = 0; f < K; ++f)
+        for (int k = 0; k < K; ++k) ltT[(size_t)k * K + f] = lt[(size_t)f * K + k];
+    return ltT;
+}
+
+int ForwardTable::reserve(const char* prefix, int sumN, int waves, int extra, const i64* h_offs, int S)
+{
+    const i64 row = 8 * ((i64)sumN + waves + extra);
+    chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
+    if (!(d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves) ||
+          (extra && d_x.reserve((size_t)max_frames * extra))))
+        return 0;
+    const std::string why = e2vq_last_error();
+    return e2vq_set_error("%s: no room for the forward table of %lld frames x %d states (%lld bytes; "
+                          "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
+                          prefix, (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
+}
+
+std::string frames_csv_path(const std::string& dir, const char* input_filename)
+{
+    return dir + "/" + e2vq_io::basename_noext(input_filename) + ".csv";
+}
+
+int frames_csv_distinct(const std::string& dir, const char* const* input_filenames, int num_inputs)
+{
+    for (int f = 0; f < num_inputs && !dir.empty(); ++f)
+        for (int g = 0; g < f; ++g)
+            if (input_filenames[f] && input_filenames[g] && frames_csv_path(dir, input_filenames[g]) == frames_csv_path(dir, input_filenames[f]))
+                return e2vq_set_error("%s and %s would both write %s", input_filenames[g], input_filenames[f],
+                                      frames_csv_path(dir, input_filenames[f]).c_str());
     return 0;
 }
 
@@ -362,27 +405,13 @@ int segment_device(const LoopModels& lm, const unsigned short* d_sym, const i64*
 }
 
 // ---- hmm segment --posteriors: forward-backward through the same class loop -------------------------------
-// the body of the pass (ECOZ2_HMM_POSTERIOR_BODY): resident (at most 16 slots) unless the caller opts into the looped one
-int posteriors_body(int* body) { return opt_in_body("ECOZ2_HMM_POSTERIOR_BODY", body); }
-
-bool posteriors_looped(int body, int slots)
-{
-    return body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && slots > e2hmm::SEG_MAX_WAVES);
-}
-
-// (host only) resident: at most 16 slots.  looped: the mandatory LDS of hmm_posterior_looped.hip must fit -- with
-// segment_check_shape's caps it always does; the check stands for the day a cap moves.
-int posteriors_check_slots(const char* who, int K, const int* Ns, int body)
+// the slot check of the pass (body: what posteriors_body gave): the mandatory LDS of hmm_posterior_looped.hip
+int posteriors_check_slots(const char* who, int K, const int* Ns, LoopBody body)
 {
     const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld);
-    if (!posteriors_looped(body, pk.slots)) return check_resident(who, pk.slots, "the posteriors have");
-    e2hmm::SegPlanDev shape{};
-    shape.slots = pk.slots, shape.sumN = pk.sumN;
-    const size_t need = e2hmm::posteriors_looped_lds_bytes(shape, false);
-    if (need > e2hmm::SEG_LDS_BYTES)
-        return e2vq_set_error("%s: %d wave-slots and %d states take %zu bytes of LDS in the looped body of the posteriors (at most %zu)",
-                              who, pk.slots, pk.sumN, need, (size_t)e2hmm::SEG_LDS_BYTES);
-    return 0;
+    const e2hmm::SegPlanDev shape = loop_shape(pk, K);
+    return check_body_slots(who, pk, K, body, "the posteriors have", "the posteriors", e2hmm::posteriors_looped_lds_bytes(shape, false),
+                            /*classes=*/false);
 }
 
 struct PostOut {  // host arrays, any may be null; post: K doubles a frame; per stream: log_prob, status
@@ -395,14 +424,13 @@ struct PostOut {  // host arrays, any may be null; post: K doubles a frame; per 
 // loop of the models (already checked by segment_check_shape and posteriors_check_slots; all of one M), on the current
 // device and the stream st, by the body that posteriors_body gave.
 int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, double ln_switch, hipStream_t st,
-                      const PostOut& out, int body)
+                      const PostOut& out, LoopBody body)
 {
     const int K = lm.K(), M = lm.M;
     const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);
     const int sumN = pk.sumN, a_words = pk.a_words, slots = pk.slots;
     const double sw = exp(ln_switch);  // (-inf: 0.0)
-    const bool looped = posteriors_looped(body, slots);
-    const int waves = looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots;  // each stores its copy of c_t
+    const bool looped = runs_looped(body, slots);
     // pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class
     std::vector<double> params((size_t)2 * sumN + (size_t)a_words + (size_t)sumN * M, 0.0);
     for (int k = 0; k < K; ++k) {
@@ -418,31 +446,22 @@ int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i
     }
     ClassLoopDev loop;
     Scores sc;  // P(O) of each stream
-    DeviceBuffer<double> d_post, d_ah, d_c;
+    DeviceBuffer<double> d_post;
+    ForwardTable ft;
     DeviceBuffer<i64> d_offs;
     const i64 frames = h_offs[S];
     if (loop.upload(pk, params, K, M, st) || d_offs.upload(h_offs, (size_t)S + 1, st) || sc.reserve((size_t)S) ||
-        d_post.reserve((size_t)frames * K))
+        d_post.reserve((size_t)frames * K) || ft.reserve("hmm segment --posteriors", sumN, body_waves(looped, slots), 0, h_offs, S))
         return 1;
     const e2hmm::SegPlanDev& pl = loop.pl;
-    // launches of whole streams whose ah (8 sumN bytes a frame) and c (8 bytes a frame and wave) stay within the budget
-    const i64 row = 8 * ((i64)sumN + waves);
-    i64 max_frames = 0;
-    const auto chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves)) {
-        const std::string why = e2vq_last_error();
-        return e2vq_set_error("hmm segment --posteriors: no room for the forward table of %lld frames x %d states (%lld bytes; "
-                              "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
-                              (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
-    }
     KernelTimer timer;
     if (timer.create()) return 1;
     HIPCHK(hipEventRecord(timer.start.e, st));
     // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
-    for (const auto& c : chunks) {
+    for (const auto& c : ft.chunks) {
         const int s0 = c.first, n = c.second - c.first;
         const auto launch = looped ? e2hmm::launch_loop_posteriors_looped : e2hmm::launch_loop_posteriors;
-        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], sw, d_ah.get(), d_c.get(), d_post.get(), sc.d_mant.get() + s0,
+        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], sw, ft.d_ah.get(), ft.d_c.get(), d_post.get(), sc.d_mant.get() + s0,
                    sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
             return e2vq_set_error("hmm segment --posteriors: %d wave-slots of %d states cannot be launched", slots, sumN);
         HIPCHK(hipGetLastError());
@@ -452,23 +471,20 @@ int posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i
     if (sc.download((size_t)S, st)) return 1;
     HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
     if (timer.elapsed_ms(&g_posteriors_kernel_ms)) return 1;
-    for (int s = 0; s < S; ++s) sc.get((size_t)s, nullptr, nullptr, out.status ? out.status + s : nullptr, out.log_prob ? out.log_prob + s : nullptr);
+    sc.get_all((size_t)S, out.status, out.log_prob);
     return 0;
 }
 
 // ---- hmm segment --class-transitions ----------------------------------------------------------------------
 // segment_device under the K x K prices lt (row: the class left); out.gbest receives exit_score.  Already checked:
-// segment_check_shape, trans_check_slots (with the body that segment_trans_body gave), trans_check_lt.
+// segment_check_shape, trans_check_slots (with the same body), trans_check_lt.
 int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, const double* lt, hipStream_t st,
-                         const SegOut& out, int body)
+                         const SegOut& out, LoopBody body)
 {
     const int K = lm.K();
     const SegPacking pk = pack_slots(lm.Ns);
     const int sumN = pk.sumN, slots = pk.slots;
-    const std::vector<double> params = loop_log_params(lm, pk);
-    std::vector<double> ltT((size_t)K * K);  // a lane of class k walks its sources along consecutive words
-    for (int f = 0; f < K; ++f)
-        for (int k = 0; k < K; ++k) ltT[(size_t)k * K + f] = lt[(size_t)f * K + k];
+    const std::vector<double> params = loop_log_params(lm, pk), ltT = trans_transposed(K, lt);
 
     ClassLoopDev loop;
     SegResultsDev res;
@@ -492,7 +508,7 @@ int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, cons
                               (long long)max_frames, sumN, K, (long long)(max_frames * row), why.c_str());
     }
     // (both bodies write the same tables: the backtrack below serves either)
-    const auto launch = segment_trans_looped(body, slots) ? e2hmm::launch_segment_trans_looped : e2hmm::launch_segment_trans;
+    const auto launch = runs_looped(body, slots) ? e2hmm::launch_segment_trans_looped : e2hmm::launch_segment_trans;
     KernelTimer timer;
     if (timer.create()) return 1;
     HIPCHK(hipEventRecord(timer.start.e, st));
@@ -515,63 +531,45 @@ int segment_trans_device(const LoopModels& lm, const unsigned short* d_sym, cons
 }
 
 // ---- hmm segment --class-transitions --grammar-posteriors --------------------------------------------------
-// (host only) resident: at most 16 slots.  looped: the mandatory LDS of hmm_posterior_trans_looped.hip must fit -- with
-// segment_check_shape's caps it always does (99 328 bytes at K = sum N = 4096); the check stands for the day
-// a cap moves.
-int trans_posteriors_check_slots(const char* who, int K, const int* Ns, int body)
+// the slot check of the pass (body: what trans_fb_body gave): the mandatory LDS of hmm_posterior_trans_looped.hip
+// (99 328 bytes at K = sum N = 4096)
+int trans_posteriors_check_slots(const char* who, int K, const int* Ns, LoopBody body)
 {
     const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld);
-    if (!trans_fb_looped(body, pk.slots)) return check_resident(who, pk.slots, "the posteriors under class-to-class prices have");
-    e2hmm::SegPlanDev shape{};
-    shape.K = K, shape.slots = pk.slots, shape.sumN = pk.sumN;
-    const size_t need = e2hmm::posteriors_trans_looped_lds_bytes(shape, false, false);
-    if (need > e2hmm::SEG_LDS_BYTES)
-        return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of the "
-                              "posteriors under class-to-class prices (at most %zu)", who, pk.slots, pk.sumN, K, need,
-                              (size_t)e2hmm::SEG_LDS_BYTES);
-    return 0;
+    const e2hmm::SegPlanDev shape = loop_shape(pk, K);
+    return check_body_slots(who, pk, K, body, "the posteriors under class-to-class prices have", "the posteriors under class-to-class prices",
+                            e2hmm::posteriors_trans_looped_lds_bytes(shape, false, false));
 }
 
 // posteriors_device under the K x K prices lt (row: the class left).  Already checked: segment_check_shape,
-// trans_posteriors_check_slots (with the body that trans_fb_body gave), trans_check_lt (and the models' parameters: finite and
-// non-negative).
+// trans_posteriors_check_slots (with the same body), trans_check_lt (and the models' parameters: finite and non-negative).
 int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, const i64* h_offs, int S, const double* lt, hipStream_t st,
-                            const PostOut& out, int body)
+                            const PostOut& out, LoopBody body)
 {
     const int K = lm.K(), M = lm.M;
     const SegPacking pk = pack_slots(lm.Ns, posteriors_a_ld);
     const int sumN = pk.sumN, slots = pk.slots;
-    const bool looped = trans_fb_looped(body, slots);
-    const int waves = looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots;  // each stores its copy of c_t
+    const bool looped = runs_looped(body, slots);
     const std::vector<double> w = trans_prices(K, lt), params = trans_params(lm, pk);
     ClassLoopDev loop;
     Scores sc;  // P(O) of each stream
-    DeviceBuffer<double> d_post, d_ah, d_c, d_w;
+    DeviceBuffer<double> d_post, d_w;
+    ForwardTable ft;  // (the class masses live in LDS only: the kernel stores nothing more per frame than 4.8.7's)
     DeviceBuffer<i64> d_offs;
     const i64 frames = h_offs[S];
     if (loop.upload(pk, params, K, M, st) || d_w.upload(w.data(), w.size(), st) || d_offs.upload(h_offs, (size_t)S + 1, st) ||
-        sc.reserve((size_t)S) || d_post.reserve((size_t)frames * K))
+        sc.reserve((size_t)S) || d_post.reserve((size_t)frames * K) ||
+        ft.reserve("hmm segment --grammar-posteriors", sumN, body_waves(looped, slots), 0, h_offs, S))
         return 1;
     const e2hmm::SegPlanDev& pl = loop.pl;
-    // launches of whole streams whose ah (8 sumN bytes a frame) and c (8 bytes a frame and wave) stay within the budget (the
-    // class masses live in LDS only: the kernel stores nothing more per frame than 4.8.7's)
-    const i64 row = 8 * ((i64)sumN + waves);
-    i64 max_frames = 0;
-    const auto chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-    if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves)) {
-        const std::string why = e2vq_last_error();
-        return e2vq_set_error("hmm segment --grammar-posteriors: no room for the forward table of %lld frames x %d states (%lld bytes; "
-                              "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
-                              (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
-    }
     KernelTimer timer;
     if (timer.create()) return 1;
     HIPCHK(hipEventRecord(timer.start.e, st));
     // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
-    for (const auto& c : chunks) {
+    for (const auto& c : ft.chunks) {
         const int s0 = c.first, n = c.second - c.first;
         const auto launch = looped ? e2hmm::launch_loop_posteriors_trans_looped : e2hmm::launch_loop_posteriors_trans;
-        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), d_ah.get(), d_c.get(), d_post.get(), sc.d_mant.get() + s0,
+        if (launch(pl, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), ft.d_ah.get(), ft.d_c.get(), d_post.get(), sc.d_mant.get() + s0,
                    sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
             return e2vq_set_error("hmm segment --grammar-posteriors: %d wave-slots of %d states cannot be launched", slots, sumN);
         HIPCHK(hipGetLastError());
@@ -581,7 +579,7 @@ int trans_posteriors_device(const LoopModels& lm, const unsigned short* d_sym, c
     if (sc.download((size_t)S, st)) return 1;
     HIPCHK(hipStreamSynchronize(st));  // (the one synchronisation; the host tables above are locals)
     if (timer.elapsed_ms(&g_trans_posteriors_kernel_ms)) return 1;
-    for (int s = 0; s < S; ++s) sc.get((size_t)s, nullptr, nullptr, out.status ? out.status + s : nullptr, out.log_prob ? out.log_prob + s : nullptr);
+    sc.get_all((size_t)S, out.status, out.log_prob);
     return 0;
 }
 
@@ -665,103 +663,63 @@ int segment_report(const char* who, const char* name, int64_t T, int K, const ch
     return 0;
 }
 
-// `hmm segment` with and without --posteriors: every input (.wav: lpc -> quantize -> segment; .prd: quantize -> segment;
-// .seq: segment) under the models.  The symbols of an input are staged once; the posteriors run on the same device buffer.
+// `hmm segment` over whole recordings, in its four forms: every input (.wav: lpc -> quantize -> segment; .prd: quantize ->
+// segment; .seq: segment) under the models.  transitions_csv: null under the one ln_switch; else the file of the class-to-class
+// prices of `--class-transitions` (empty: refused), whose values plus ln_switch are the effective prices.  posteriors:
+// `--posteriors`, or under a transitions file `--grammar-posteriors`.  read_body: the reader of the variable that chooses the
+// body of the form (null: the form has none).  The symbols of an input are staged once; the posteriors run on the same device
+// buffer, under the same effective prices.
 int segment_files(const char* who, const char* const* model_filenames, unsigned num_models, const char* cb_filename,
                   const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
-                  const char* csv_dir_or_file, bool posteriors, const char* frames_dir)
+                  const char* transitions_csv, int (*read_body)(LoopBody*), const char* csv_dir_or_file, bool posteriors,
+                  const char* frames_dir)
 {
     FlushStdout flush_on_return;
     LoopModels lm;
-    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1) || segment_check_switch(who, ln_switch) ||
-        window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models))
-        return 1;
+    const bool trans = transitions_csv != nullptr;
+    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
+    if (trans && !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
+    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models)) return 1;
     const int K = lm.K();
-    int body = EMBED_BODY_RESIDENT;
-    if (posteriors && (posteriors_body(&body) || posteriors_check_slots(who, K, lm.Ns.data(), body))) return 1;
+    // (--grammar-posteriors reads its own variable, never the decoder's: the decode of the same input follows that one choice,
+    // runs_looped with its value, so that what the posteriors take the decoder takes too)
+    LoopBody body = LoopBody::Resident;
+    if (read_body && read_body(&body)) return 1;
+    if (trans ? trans_check_slots(who, K, lm.Ns.data(), body) || (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data(), body)) ||
+                    check_names(who, K, lm.names.data())
+              : posteriors && posteriors_check_slots(who, K, lm.Ns.data(), body))
+        return 1;
+    std::vector<double> lt;
+    if (trans && transitions_read(transitions_csv, K, lm.names.data(), lt)) return 1;
+    for (double& v : lt) v = v + ln_switch;  // the effective price
     if (lm.logs(model_filenames)) return 1;
     const std::string fdir = posteriors && frames_dir ? frames_dir : "";
-    auto frames_csv = [&](const char* path) { return fdir + "/" + e2vq_io::basename_noext(path) + ".csv"; };
-    for (int f = 0; f < num_inputs && !fdir.empty(); ++f)
-        for (int g = 0; g < f; ++g)
-            if (input_filenames[f] && input_filenames[g] && frames_csv(input_filenames[g]) == frames_csv(input_filenames[f]))
-                return e2vq_set_error("%s and %s would both write %s", input_filenames[g], input_filenames[f], frames_csv(input_filenames[f]).c_str());
+    if (frames_csv_distinct(fdir, input_filenames, num_inputs)) return 1;
     auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
         const i64 offs[2] = {0, T};
         const size_t n = (size_t)std::max<int64_t>(T, 1);
         std::vector<uint16_t> cls(n);
         std::vector<uint8_t> entered(n);
-        std::vector<double> gbest(n), post;
+        std::vector<double> gbest(n), post;  // (gbest: exit_score under a transitions file)
         double lp = 0.0;
         int status = 0;
         SegOut out;
         out.cls = cls.data(), out.entered = entered.data(), out.gbest = gbest.data(), out.log_prob = &lp, out.status = &status;
-        if (segment_device(lm, d_sym, offs, 1, ln_switch, st, out)) return 1;
+        if (trans ? segment_trans_device(lm, d_sym, offs, 1, lt.data(), st, out, body) : segment_device(lm, d_sym, offs, 1, ln_switch, st, out))
+            return 1;
         if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), lm.M);
         if (posteriors) {
             post.resize(n * (size_t)K);
             PostOut po;
             po.post = post.data();
-            if (posteriors_device(lm, d_sym, offs, 1, ln_switch, st, po, body)) return 1;
+            if (trans ? trans_posteriors_device(lm, d_sym, offs, 1, lt.data(), st, po, body)
+                      : posteriors_device(lm, d_sym, offs, 1, ln_switch, st, po, body))
+                return 1;
         }
-        const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
+        const std::string fcsv = fdir.empty() ? "" : frames_csv_path(fdir, in.path.c_str());
         return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), gbest.data(), lp,
                               ln_switch, posteriors ? post.data() : nullptr, in.csv.empty() ? nullptr : in.csv.c_str(),
-                              fcsv.empty() ? nullptr : fcsv.c_str());
-    };
-    return run_on_files(who, lm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
-}
-
-// `hmm segment --class-transitions` with and without --grammar-posteriors: segment_files under the transitions file.  The
-// symbols of an input are staged once; the posteriors run on the same device buffer under the same effective prices.
-int segment_trans_files(const char* who, const char* const* model_filenames, unsigned num_models, const char* cb_filename,
-                        const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms, double ln_switch,
-                        const char* transitions_csv, const char* csv_dir_or_file, bool posteriors, const char* frames_dir)
-{
-    FlushStdout flush_on_return;
-    LoopModels lm;
-    if (files_given(who, model_filenames, num_models, input_filenames && num_inputs >= 1)) return 1;
-    if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
-    if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || lm.load_checked(who, model_filenames, num_models)) return 1;
-    const int K = lm.K();
-    // (--grammar-posteriors reads its own variable, never the decoder's: the decode of the same input follows that one choice,
-    // segment_trans_looped with its value, so that what the posteriors take the decoder takes too)
-    int body = EMBED_BODY_RESIDENT;
-    if ((posteriors ? trans_fb_body(&body) : segment_trans_body(&body)) || trans_check_slots(who, K, lm.Ns.data(), body) ||
-        (posteriors && trans_posteriors_check_slots(who, K, lm.Ns.data(), body)) || check_names(who, K, lm.names.data()))
-        return 1;
-    std::vector<double> lt;
-    if (transitions_read(transitions_csv, K, lm.names.data(), lt)) return 1;
-    for (double& v : lt) v = v + ln_switch;  // the effective price
-    if (lm.logs(model_filenames)) return 1;
-    const std::string fdir = posteriors && frames_dir ? frames_dir : "";
-    auto frames_csv = [&](const char* path) { return fdir + "/" + e2vq_io::basename_noext(path) + ".csv"; };
-    for (int f = 0; f < num_inputs && !fdir.empty(); ++f)
-        for (int g = 0; g < f; ++g)
-            if (input_filenames[f] && input_filenames[g] && frames_csv(input_filenames[g]) == frames_csv(input_filenames[f]))
-                return e2vq_set_error("%s and %s would both write %s", input_filenames[g], input_filenames[f], frames_csv(input_filenames[f]).c_str());
-    auto run = [&](const SymInput& in, int64_t T, const unsigned short* d_sym, hipStream_t st) -> int {
-        const i64 offs[2] = {0, T};
-        const size_t n = (size_t)std::max<int64_t>(T, 1);
-        std::vector<uint16_t> cls(n);
-        std::vector<uint8_t> entered(n);
-        std::vector<double> exit_score(n), post;
-        double lp = 0.0;
-        int status = 0;
-        SegOut out;
-        out.cls = cls.data(), out.entered = entered.data(), out.gbest = exit_score.data(), out.log_prob = &lp, out.status = &status;
-        if (segment_trans_device(lm, d_sym, offs, 1, lt.data(), st, out, body)) return 1;
-        if (status == 2) return e2vq_set_error("%s: a symbol outside the models' alphabet of %d", in.path.c_str(), lm.M);
-        if (posteriors) {  // the same staged symbols, the same effective prices
-            post.resize(n * (size_t)K);
-            PostOut po;
-            po.post = post.data();
-            if (trans_posteriors_device(lm, d_sym, offs, 1, lt.data(), st, po, body)) return 1;
-        }
-        const std::string fcsv = fdir.empty() ? "" : frames_csv(in.path.c_str());
-        return segment_report(who, in.path.c_str(), T, K, lm.names.data(), W_ms, O_ms, cls.data(), entered.data(), exit_score.data(), lp,
-                              ln_switch, posteriors ? post.data() : nullptr, in.csv.empty() ? nullptr : in.csv.c_str(),
-                              fcsv.empty() ? nullptr : fcsv.c_str(), lt.data());
+                              fcsv.empty() ? nullptr : fcsv.c_str(), trans ? lt.data() : nullptr);
     };
     return run_on_files(who, lm.M, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms, csv_dir_or_file, run);
 }
@@ -807,7 +765,7 @@ extern "C" int e2vq_hmm_segment_files(const char* const* model_filenames, unsign
                                       const char* csv_dir_or_file)
 {
     return segment_files("e2vq_hmm_segment_files", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P, W_ms, O_ms,
-                         ln_switch, csv_dir_or_file, false, nullptr);
+                         ln_switch, nullptr, nullptr, csv_dir_or_file, false, nullptr);
 }
 
 
@@ -825,7 +783,7 @@ extern "C" int e2vq_hmm_segment_posteriors(int device, int K, const int* Ns, int
     const char* who = "e2vq_hmm_segment_posteriors";
     LoopModels lm;
     DevSeqs seqs;
-    int body = EMBED_BODY_RESIDENT;
+    LoopBody body = LoopBody::Resident;
     if (loop_check_args(who, K, Ns, pis, As, Bs, syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
         segment_check_switch(who, ln_switch) || posteriors_body(&body) || posteriors_check_slots(who, K, Ns, body) ||
         lm.from_arrays(K, Ns, M, pis, As, Bs))
@@ -853,7 +811,8 @@ extern "C" int e2vq_hmm_segment_files_posteriors(const char* const* model_filena
                                                  double ln_switch, const char* csv_dir_or_file, const char* frames_dir)
 {
     return segment_files("e2vq_hmm_segment_files_posteriors", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P,
-                         W_ms, O_ms, ln_switch, csv_dir_or_file, true, frames_dir && *frames_dir ? frames_dir : nullptr);
+                         W_ms, O_ms, ln_switch, nullptr, posteriors_body, csv_dir_or_file, true,
+                         frames_dir && *frames_dir ? frames_dir : nullptr);
 }
 
 // ---- hmm segment --class-transitions ----------------------------------------------------------------------
@@ -870,7 +829,7 @@ extern "C" int e2vq_hmm_segment_trans(int device, int K, const int* Ns, int M, c
     const char* who = "e2vq_hmm_segment_trans";
     LoopModels lm;
     DevSeqs seqs;
-    int body = EMBED_BODY_RESIDENT;
+    LoopBody body = LoopBody::Resident;
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
         trans_check_lt(who, K, lt) || segment_trans_body(&body) || trans_check_slots(who, K, Ns, body))
         return 1;
@@ -892,8 +851,8 @@ extern "C" int e2vq_hmm_segment_trans_files(const char* const* model_filenames, 
                                             const char* const* input_filenames, int num_inputs, int P, int W_ms, int O_ms,
                                             double ln_switch, const char* transitions_csv, const char* csv_dir_or_file)
 {
-    return segment_trans_files("e2vq_hmm_segment_trans_files", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P,
-                               W_ms, O_ms, ln_switch, transitions_csv, csv_dir_or_file, false, nullptr);
+    return segment_files("e2vq_hmm_segment_trans_files", model_filenames, num_models, cb_filename, input_filenames, num_inputs, P, W_ms,
+                         O_ms, ln_switch, transitions_csv ? transitions_csv : "", segment_trans_body, csv_dir_or_file, false, nullptr);
 }
 
 // ---- hmm segment --class-transitions --grammar-posteriors --------------------------------------------------
@@ -910,7 +869,7 @@ extern "C" int e2vq_hmm_segment_trans_posteriors(int device, int K, const int* N
     const char* who = "e2vq_hmm_segment_trans_posteriors";
     LoopModels lm;
     DevSeqs seqs;
-    int body = EMBED_BODY_RESIDENT;
+    LoopBody body = LoopBody::Resident;
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
         trans_check_lt(who, K, lt) || trans_fb_body(&body) || trans_posteriors_check_slots(who, K, Ns, body) ||
         lm.from_arrays(K, Ns, M, pis, As, Bs))
@@ -927,7 +886,7 @@ extern "C" int e2vq_hmm_segment_trans_files_posteriors(const char* const* model_
                                                        double ln_switch, const char* transitions_csv, const char* csv_dir_or_file,
                                                        const char* frames_dir)
 {
-    return segment_trans_files("e2vq_hmm_segment_trans_files_posteriors", model_filenames, num_models, cb_filename, input_filenames,
-                               num_inputs, P, W_ms, O_ms, ln_switch, transitions_csv, csv_dir_or_file, true,
-                               frames_dir && *frames_dir ? frames_dir : nullptr);
+    return segment_files("e2vq_hmm_segment_trans_files_posteriors", model_filenames, num_models, cb_filename, input_filenames, num_inputs,
+                         P, W_ms, O_ms, ln_switch, transitions_csv ? transitions_csv : "", trans_fb_body, csv_dir_or_file, true,
+                         frames_dir && *frames_dir ? frames_dir : nullptr);
 }

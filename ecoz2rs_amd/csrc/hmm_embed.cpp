@@ -29,7 +29,7 @@ struct EmbedPlan : EStepPlan {
 int embed_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
                const uint8_t* optional, double ln_switch, EmbedPlan& ep)
 {
-    int body = EMBED_BODY_RESIDENT;
+    LoopBody body = LoopBody::Resident;
     if (embed_body(&body)) return 1;
     if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the embedded E-step has no looped body", true, body, ep))
         return 1;

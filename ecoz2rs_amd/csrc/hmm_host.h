@@ -1,8 +1,9 @@
 // hmm_host.h -- what the host units of the HMM consumers share (hmm_model.cpp: models, files, sequences; hmm_train.cpp:
 // Baum-Welch; hmm_classify.cpp: forward scoring and the classification reports; hmm_decode.cpp: Viterbi and scan;
-// hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices; hmm_transitions.cpp: the file and the estimator
-// of those prices; hmm_input.cpp: inputs to device symbols, label files; hmm_segment_stream.cpp: the streaming segment
-// decoder; hmm_transcript.cpp: what the commands that take a transcript share; hmm_align.cpp: forced alignment; hmm_embed.cpp:
+// hmm_class_loop.cpp: segment, its posteriors and its class-to-class prices, the body choice, slot check and forward table of
+// every pass with a looped body; hmm_transitions.cpp: the file and the estimator of those prices; hmm_input.cpp: inputs to
+// device symbols, label files; hmm_segment_stream.cpp: the streaming segment decoder; hmm_transcript.cpp: what the commands
+// that take a transcript share; hmm_align.cpp: forced alignment; hmm_embed.cpp:
 // embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp: the posteriors of the alignment; hmm_trans_train.cpp:
 // Baum-Welch for the class-to-class prices; hmm_loop_train.cpp: Baum-Welch for the class models under the class loop).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
@@ -214,6 +215,11 @@ struct ScoresT {
         if (s) *s = status.get()[i];
         if (lp) *lp = log_prob(i);
     }
+    // status and natural log of the first n results into the caller's arrays (either may be null)
+    void get_all(size_t n, int* s, double* lp) const
+    {
+        for (size_t i = 0; i < n; ++i) get(i, nullptr, nullptr, s ? s + i : nullptr, lp ? lp + i : nullptr);
+    }
 };
 typedef ScoresT<HostVec> Scores;
 
@@ -259,6 +265,11 @@ inline int window_ms_ok(const char* who, int W_ms, int O_ms)
 {
     return W_ms < 1 || O_ms < 1 ? e2vq_set_error("%s: window %d ms / offset %d ms", who, W_ms, O_ms) : 0;
 }
+
+// the per-frame table of an input in `dir`: <dir>/<the input's name without directory and extension>.csv; frames_csv_distinct:
+// no two inputs may share one ("%s and %s would both write %s"; dir empty: no table is written, nothing is refused)
+std::string frames_csv_path(const std::string& dir, const char* input_filename);
+int frames_csv_distinct(const std::string& dir, const char* const* input_filenames, int num_inputs);
 
 // The models of `hmm scan` / `hmm segment`: loaded, all of one M
 struct FilesModels {
@@ -319,26 +330,38 @@ std::vector<double> loop_log_params(const LoopModels& lm, const SegPacking& pk);
 // the body of a class-loop kernel: looped where `slots` exceed a workgroup's waves or the variable `env_name` says
 // "looped" (slots = 0: whether it says so); a value other than "resident" or "looped" is refused
 int loop_body_looped(const char* env_name, int slots, bool* looped);
-// the body of a pass whose looped kernel is opt-in (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY): unset, empty or
-// "resident" / "looped" / "auto" of the variable `env_name` -> *body (an EmbedBody, below); any other value is refused with
-// "<env_name>=<v>: auto, resident or looped"
-int opt_in_body(const char* env_name, int* body);
 
-// The decoder under class-to-class prices (`hmm segment --class-transitions` and its session):
-// segment_trans_body: ECOZ2_HMM_SEGMENT_TRANS_BODY through opt_in_body -> *body (an EmbedBody).  segment_trans_looped: whether
-// a packing of `slots` runs the looped kernels under that body.  trans_check_slots (host only): resident -- more than 16 slots
-// are refused, word for word as before the looped body existed; looped -- its mandatory LDS must fit.
-int segment_trans_body(int* body);
-bool segment_trans_looped(int body, int slots);
-int trans_check_slots(const char* who, int K, const int* Ns, int body);
+// The body of a pass whose looped kernel is opt-in: resident (more than 16 wave-slots are refused), looped, or resident up to
+// 16 slots and looped above.  opt_in_body is the one reader of the variables: unset, empty or "resident" / "looped" / "auto" of
+// `env_name` -> *body; any other value is refused with "<env_name>=<v>: auto, resident or looped".  The four readers below name
+// their variable; each entry point calls its reader once.  runs_looped: whether a packing (or a transcript) of `slots` runs the
+// looped kernels under `body`.  body_waves: the waves of a workgroup, each of which stores its copy of c_t.
+enum class LoopBody { Resident, Looped, Auto };
+int opt_in_body(const char* env_name, LoopBody* body);
+bool runs_looped(LoopBody body, int slots);
+int body_waves(bool looped, int slots);
+int embed_body(LoopBody* body);          // ECOZ2_HMM_EMBED_BODY: the E-step of `hmm learn --embedded`
+int posteriors_body(LoopBody* body);     // ECOZ2_HMM_POSTERIOR_BODY: `hmm segment --posteriors` (4.8.7)
+int segment_trans_body(LoopBody* body);  // ECOZ2_HMM_SEGMENT_TRANS_BODY: `--class-transitions` and its session (4.8.8 / 4.8.15)
+// ECOZ2_HMM_TRANS_FB_BODY: `--grammar-posteriors` (4.8.13) and the E-step of `hmm transitions --em` (4.8.14);
+// e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors (whose decode follows the same choice),
+// e2vq_hmm_transitions_estep, e2vq_hmm_train_transitions and e2vq_hmm_learn_transitions_files read it, and nothing else does
+int trans_fb_body(LoopBody* body);
 
-// The two forward-backward passes under class-to-class prices (`hmm segment --grammar-posteriors`, DESIGN.md 4.8.13, and the
-// E-step of `hmm transitions --em`, 4.8.14): trans_fb_body: ECOZ2_HMM_TRANS_FB_BODY through opt_in_body -> *body (an
-// EmbedBody); e2vq_hmm_segment_trans_posteriors, e2vq_hmm_segment_trans_files_posteriors (whose decode follows the same
-// choice), e2vq_hmm_transitions_estep, e2vq_hmm_train_transitions and e2vq_hmm_learn_transitions_files read it, once a call,
-// and nothing else does.  trans_fb_looped: whether a packing of `slots` runs the looped kernels under that body.
-int trans_fb_body(int* body);
-bool trans_fb_looped(int body, int slots);
+// the shape of a packing as the *_lds_bytes and *_layout functions of hmm_device.h read it (no table, no device pointer)
+e2hmm::SegPlanDev loop_shape(const SegPacking& pk, int K, int M = 0);
+// The slot check of a pass that has a looped body (host only).  Resident: more than 16 slots are refused, word for word as
+// before the looped body existed (`resident_has` closes that message).  Looped: `looped_lds`, the mandatory LDS bytes of the
+// looped body for this shape, must fit -- with segment_check_shape's caps they always do; the check stands for the day a cap
+// moves.  `looped_of` names the looped body in that refusal; classes: the pass runs under class-to-class prices and the refusal
+// counts the K classes too.
+int check_body_slots(const char* who, const SegPacking& pk, int K, LoopBody body, const char* resident_has, const char* looped_of,
+                     size_t looped_lds, bool classes = true);
+// that check for the decoder under class-to-class prices (`hmm segment --class-transitions` and its session, DESIGN.md 4.8.8 /
+// 4.8.15; body: what segment_trans_body gave, or trans_fb_body where the decode follows the posteriors)
+int trans_check_slots(const char* who, int K, const int* Ns, LoopBody body);
+// the K x K prices transposed, ltT[k * K + f] = lt[f * K + k]: a lane of class k walks its sources along consecutive words
+std::vector<double> trans_transposed(int K, const double* lt);
 
 // A packing on the device: the parameter block, the four tables of `pk`, and the plan the kernels take.  upload() only
 // enqueues: the host vectors must outlive the stream's copies, and this struct the stream's kernels (a local is declared
@@ -353,9 +376,22 @@ struct ClassLoopDev {
     int upload(const SegPacking& pk, const std::vector<double>& host_params, int K, int M, hipStream_t st);
 };
 
+// The forward table of a sum-product pass through the class loop (hmm_class_loop.cpp: --posteriors, --grammar-posteriors;
+// hmm_trans_train.cpp; hmm_loop_train.cpp): per frame ah (sumN doubles), c (one double a wave) and, where the pass keeps one,
+// a third array of `extra` doubles (the loop trainer's m_t, K a frame).  reserve() cuts the S streams of h_offs into launches
+// of whole streams whose rows of 8 (sumN + waves + extra) bytes stay within ECOZ2_HMM_POSTERIOR_CHUNK_BYTES (plan_chunks) and
+// makes room for the largest; a failure is refused as "<prefix>: no room for the forward table of ...".
+struct ForwardTable {
+    DeviceBuffer<double> d_ah, d_c, d_x;
+    std::vector<std::pair<int, int>> chunks;
+    i64 max_frames = 0;
+    int reserve(const char* prefix, int sumN, int waves, int extra, const i64* h_offs, int S);
+};
+
 // What the sum-product passes under class-to-class prices share (hmm_class_loop.cpp: --grammar-posteriors;
-// hmm_trans_train.cpp: transitions --em).  check_resident: where only the resident layout exists, a packing of more than 16
-// slots is refused (`what_has` closes the message).  posteriors_a_ld: the leading dimension N | 1 of a class's A.
+// hmm_trans_train.cpp: transitions --em; hmm_loop_train.cpp: learn --loop).  check_resident: where only the resident layout
+// exists, a packing of more than 16 slots is refused (`what_has` closes the message).  posteriors_a_ld: the leading dimension
+// N | 1 of a class's A.
 // posteriors_check_params: a negative, NaN or infinite parameter is refused.  trans_check_lt: every price <= 0 or -inf.
 // trans_prices: w = exp(lt) and its transpose.  trans_params: pi | A (N | 1) | B at the places of `pk`.
 int check_resident(const char* who, int slots, const char* what_has);
@@ -424,7 +460,6 @@ struct Transcripts {
 // wave-slots are refused), looped for every stream, or resident up to 16 slots and looped above.  A launch has one body:
 // the launches of plan_chunks are cut further where the body changes and where the looped streams' largest shapes no longer
 // fit LDS together.
-enum EmbedBody { EMBED_BODY_RESIDENT = 0, EMBED_BODY_LOOPED = 1, EMBED_BODY_AUTO = 2 };
 struct EStepPlan {
     AlignPlan ap;
     SegPacking cls;                              // the classes, A with the leading dimension N | 1
@@ -442,11 +477,9 @@ struct EStepPlan {
     std::vector<Shape> shapes;                   // per chunk
 };
 // `what` closes the refusal of a stream of more than 16 wave-slots that would run resident; first_flags: EMBED_FIRST on a
-// class's first unit; body: an EmbedBody
+// class's first unit; body: the caller's choice (the embedded E-step: what embed_body gave), held against each stream's slots
 int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, int body, EStepPlan& p);
-// ECOZ2_HMM_EMBED_BODY: unset, empty or "resident" / "looped" / "auto" -> *body (an EmbedBody); any other value is refused
-int embed_body(int* body);
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, LoopBody body, EStepPlan& p);
 // "lds" / "global" / unset of the variable `name` -> *forced (whether it is set) and *lds; any other value is refused
 int embed_route(const char* name, bool* forced, bool* lds);
 // pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class

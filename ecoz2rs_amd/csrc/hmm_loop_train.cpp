@@ -4,7 +4,7 @@
 // hmm_loop_estep.hip.  The host takes exp of the prices, chooses the LDS layout and the routes of the two count tables (all
 // before any HIP call), keeps the device state over the iterations, takes the logarithm of the (mantissa, exponent) pairs, sums
 // ln P over the streams in stream order, zeroes the blocks of the frozen classes, runs the M-steps and decides when to stop.
-// The checks, the packing, the parameter block and the prices are hmm_class_loop.cpp's, the M-step of the models
+// The checks, the packing, the parameter block, the prices and the forward table are hmm_class_loop.cpp's, the M-step of the models
 // hmm_embed.hip's, that of the matrix hmm_trans_train.cpp's, the file of the matrix hmm_transitions.cpp's, the input stage
 // hmm_input.cpp's (hmm_host.h).
 #include "hmm_host.h"
@@ -48,8 +48,7 @@ int loop_em_plan(const char* who, const std::vector<int>& Ns, int M, bool gram, 
     }
     bool an_forced = false, c_forced = false;
     if (embed_route("ECOZ2_HMM_LOOP_EM_AN", &an_forced, &lp.an_lds) || embed_route("ECOZ2_HMM_LOOP_EM_C", &c_forced, &lp.c_lds)) return 1;
-    e2hmm::SegPlanDev shape{};
-    shape.K = K, shape.M = M, shape.sumN = lp.pk.sumN, shape.slots = lp.pk.slots, shape.a_words = lp.pk.a_words;
+    const e2hmm::SegPlanDev shape = loop_shape(lp.pk, K, M);
     e2hmm::loop_estep_layout(shape, gram, an_forced, c_forced, &lp.an_lds, &lp.c_lds, &lp.a_lds, &lp.w_lds);
     const size_t lds = e2hmm::loop_estep_lds_bytes(shape, lp.an_lds, lp.c_lds, lp.a_lds, lp.w_lds);
     if (lds > e2hmm::SEG_LDS_BYTES)
@@ -63,33 +62,22 @@ int loop_em_plan(const char* who, const std::vector<int>& Ns, int M, bool gram, 
 struct LoopEmDev {
     ClassLoopDev loop;
     Scores sc;  // P(O | loop) of each stream
-    DeviceBuffer<double> d_ah, d_c, d_m, d_w, d_dense;
+    ForwardTable ft;  // 4.8.13's row and m_t of every class (ft.d_x, K doubles a frame), bounded by whole streams in the same way
+    DeviceBuffer<double> d_w, d_dense;
     DeviceBuffer<i64> d_offs, d_acc, d_acc_t;
     DeviceBuffer<e2hmm::EmbedClassDev> d_classes;
     std::vector<double> params, w, dense;
     std::vector<i64> acc_t;  // the grammar counts of the last E-step: 2 K^2 + 2 words (gram)
-    std::vector<std::pair<int, int>> chunks;
     KernelTimer timer;
 
     int setup(const char* who, const LoopEmPlan& lp, const LoopModels& lm, const i64* h_offs, int S, hipStream_t st)
     {
-        const int K = lm.K(), sumN = lp.pk.sumN, slots = lp.pk.slots;
+        const int K = lm.K();
         params = trans_params(lm, lp.pk);
-        if (loop.upload(lp.pk, params, K, lm.M, st) || d_classes.upload(lp.classes.data(), lp.classes.size(), st) ||
-            d_offs.upload(h_offs, (size_t)S + 1, st) || sc.reserve((size_t)S) || d_acc.reserve((size_t)lp.acc_at.back()) ||
-            d_acc_t.reserve((size_t)trans_acc_words(K)) || d_w.reserve((size_t)2 * K * K) || timer.create())
-            return 1;
-        // the forward table: 4.8.13's row and m_t of every class, bounded by whole streams in the same way
-        const i64 row = 8 * ((i64)sumN + slots + K);
-        i64 max_frames = 0;
-        chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-        if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * slots) || d_m.reserve((size_t)max_frames * K)) {
-            const std::string why = e2vq_last_error();
-            return e2vq_set_error("%s: no room for the forward table of %lld frames x %d states (%lld bytes; "
-                                  "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
-                                  who, (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
-        }
-        return 0;
+        return loop.upload(lp.pk, params, K, lm.M, st) || d_classes.upload(lp.classes.data(), lp.classes.size(), st) ||
+               d_offs.upload(h_offs, (size_t)S + 1, st) || sc.reserve((size_t)S) || d_acc.reserve((size_t)lp.acc_at.back()) ||
+               d_acc_t.reserve((size_t)trans_acc_words(K)) || d_w.reserve((size_t)2 * K * K) || timer.create() ||
+               ft.reserve(who, lp.pk.sumN, lp.pk.slots, K, h_offs, S);
     }
     // One E-step under the models lm and the effective prices lt: the counts of all streams in d_acc (from zero, AD summed),
     // with lp.gram the grammar counts in acc_t (from zero), P and status of every stream in sc's host mirrors.  Waits for the
@@ -107,10 +95,10 @@ struct LoopEmDev {
         if (lp.gram) HIPCHK(hipMemsetAsync(d_acc_t.get(), 0, words_t * 8, st));
         HIPCHK(hipEventRecord(timer.start.e, st));
         // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
-        for (const auto& c : chunks) {
+        for (const auto& c : ft.chunks) {
             const int s0 = c.first, n = c.second - c.first;
             if (e2hmm::launch_loop_estep(loop.pl, d_classes.get(), lp.an_lds, lp.c_lds, lp.a_lds, lp.w_lds, d_sym, d_offs.get() + s0, n,
-                                         h_offs[s0], d_w.get(), d_ah.get(), d_c.get(), d_m.get(), d_acc.get(),
+                                         h_offs[s0], d_w.get(), ft.d_ah.get(), ft.d_c.get(), ft.d_x.get(), d_acc.get(),
                                          lp.gram ? d_acc_t.get() : nullptr, sc.d_mant.get() + s0, sc.d_exp.get() + s0,
                                          sc.d_status.get() + s0, st))
                 return e2vq_set_error("%s: %d wave-slots of %d states cannot be launched", who, lp.pk.slots, lp.pk.sumN);
@@ -242,7 +230,7 @@ extern "C" int e2vq_hmm_loop_estep(int device, int K, const int* Ns, int M, cons
     HIPCHK(hipStreamSynchronize(seqs.st.s));
     if (acc_trans)
         for (size_t i = 0; i < dev.acc_t.size(); ++i) acc_trans[i] += dev.acc_t[i];
-    for (int s = 0; s < S; ++s) dev.sc.get((size_t)s, nullptr, nullptr, status ? status + s : nullptr, log_prob ? log_prob + s : nullptr);
+    dev.sc.get_all((size_t)S, status, log_prob);
     return 0;
 }
 

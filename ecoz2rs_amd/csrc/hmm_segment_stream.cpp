@@ -81,9 +81,9 @@ const char* flag_of(const Session& s) { return s.matrix ? "--grammar-continuous"
 
 // The models (checked by segment_check_shape; all of one M) on the device and an empty session.  lt: the K x K prices of a
 // matrix session (checked by trans_check_lt), or null under the one ln_switch.  Every refusal comes before the first HIP call.
-// trans_body: the EmbedBody of a matrix session (segment_trans_body's).
+// trans_body: the body of a matrix session (what segment_trans_body gave).
 int stream_open(const char* who, int device, const LoopModels& lm, double ln_switch, const double* lt, Session** out,
-                int trans_body = EMBED_BODY_RESIDENT)
+                LoopBody trans_body = LoopBody::Resident)
 {
     const int K = lm.K(), M = lm.M;
     const char* bv = getenv(ENV_BLOCK);
@@ -94,7 +94,7 @@ int stream_open(const char* who, int device, const LoopModels& lm, double ln_swi
     bool looped = false;
     if (lt ? trans_check_slots(who, K, lm.Ns.data(), trans_body) : loop_body_looped("ECOZ2_HMM_SEGMENT_BODY", pk.slots, &looped))
         return 1;
-    if (lt) looped = segment_trans_looped(trans_body, pk.slots);
+    if (lt) looped = runs_looped(trans_body, pk.slots);
     const i64 row = 2 * (i64)sumN + (lt ? 12 * (i64)K : 4), budget = env_bytes(ENV_PENDING, (i64)256 << 20), C = budget / row;
     if (C < 2 * B)
         return lt ? e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states and %d classes (%lld bytes a frame): fewer than "
@@ -102,12 +102,7 @@ int stream_open(const char* who, int device, const LoopModels& lm, double ln_swi
                   : e2vq_set_error("%s: %s=%lld holds %lld pending frames of %d states (%lld bytes a frame): fewer than two blocks of %lld", who,
                                    ENV_PENDING, (long long)budget, (long long)C, sumN, (long long)row, (long long)B);
     const std::vector<double> params = loop_log_params(lm, pk);
-    std::vector<double> ltT;  // a lane of class k walks its sources along consecutive words
-    if (lt) {
-        ltT.resize((size_t)K * K);
-        for (int f = 0; f < K; ++f)
-            for (int k = 0; k < K; ++k) ltT[(size_t)k * K + f] = lt[(size_t)f * K + k];
-    }
+    const std::vector<double> ltT = lt ? trans_transposed(K, lt) : std::vector<double>();
     // ---- the device from here on --------------------------------------------------------------------------------
     if (require_device(device)) return 1;
     std::unique_ptr<Session> sp(new Session);
@@ -385,7 +380,7 @@ extern "C" int e2vq_hmm_segment_trans_stream_open(int device, int K, const int* 
 {
     const char* who = "e2vq_hmm_segment_trans_stream_open";
     LoopModels lm;
-    int body = EMBED_BODY_RESIDENT;
+    LoopBody body = LoopBody::Resident;
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt != nullptr && out != nullptr) || segment_check_shape(who, K, Ns) ||
         trans_check_lt(who, K, lt) || segment_trans_body(&body) || lm.from_arrays(K, Ns, M, pis, As, Bs) || lm.logs())
         return 1;
@@ -479,7 +474,7 @@ struct Holder {
 };
 
 int decode_pieces(const char* who, const LoopModels& fm, const SymInputs& si, int P, int W_ms, int O_ms, double ln_switch, const double* lt,
-                  const char* name, Holder& hold, int trans_body = EMBED_BODY_RESIDENT)
+                  const char* name, Holder& hold, LoopBody trans_body = LoopBody::Resident)
 {
     const int device = env_device();
     if (stream_open(who, device, fm, ln_switch, lt, &hold.s, trans_body)) return 1;  // (makes the device current)
@@ -547,7 +542,7 @@ extern "C" int e2vq_hmm_segment_trans_continuous_files(const char* const* model_
     if (!transitions_csv || !*transitions_csv) return e2vq_set_error("%s: no class-transitions file", who);
     if (segment_check_switch(who, ln_switch) || window_ms_ok(who, W_ms, O_ms) || fm.load_checked(who, model_filenames, num_models)) return 1;
     const int K = fm.K();
-    int body = EMBED_BODY_RESIDENT;
+    LoopBody body = LoopBody::Resident;
     if (segment_trans_body(&body) || trans_check_slots(who, K, fm.Ns.data(), body) || check_names(who, K, fm.names.data())) return 1;
     std::vector<double> lt;
     if (transitions_read(transitions_csv, K, fm.names.data(), lt)) return 1;

@@ -4,8 +4,8 @@
 // (ECOZ2_HMM_TRANS_FB_BODY), its looped body hmm_trans_estep_looped.hip.  The host takes exp of the prices, chooses the LDS layout
 // and the route of the count table (all before any HIP call), takes the logarithm of the (mantissa, exponent) pairs, sums
 // ln P over the streams in stream order, forms the M-step (K^2 values) and decides when to stop.  The checks, the packing, the
-// parameter block and the prices are hmm_class_loop.cpp's, the file of the matrix hmm_transitions.cpp's, the input stage
-// hmm_input.cpp's (hmm_host.h).
+// parameter block, the prices, the choice of the body with its slot check and the forward table are hmm_class_loop.cpp's, the
+// file of the matrix hmm_transitions.cpp's, the input stage hmm_input.cpp's (hmm_host.h).
 #include "hmm_host.h"
 #include "vq_fixed.h"
 
@@ -55,25 +55,21 @@ struct TransPlan {
     bool c_lds = false, a_lds = false, w_lds = false;
 };
 
-// body: what trans_fb_body gave.  resident: more than 16 slots are refused, word for word as before the looped body existed.
-// looped: its mandatory LDS must fit -- with segment_check_shape's caps it always does (132 096 bytes at
-// K = sum N = 4096); the check stands for the day a cap moves.
-int trans_plan(const char* who, const std::vector<int>& Ns, int M, int body, TransPlan& tp)
+// body: what trans_fb_body gave; the slot check holds it against the mandatory LDS of hmm_trans_estep_looped.hip (DESIGN.md
+// 4.8.14: 132 096 bytes at K = sum N = 4096).
+int trans_plan(const char* who, const std::vector<int>& Ns, int M, LoopBody body, TransPlan& tp)
 {
     const int K = (int)Ns.size();
     tp.pk = pack_slots(Ns, posteriors_a_ld);
-    tp.looped = trans_fb_looped(body, tp.pk.slots);
-    tp.waves = tp.looped ? std::min(tp.pk.slots, (int)e2hmm::SEG_MAX_WAVES) : tp.pk.slots;
-    if (!tp.looped && check_resident(who, tp.pk.slots, "the E-step of the class transitions has")) return 1;
-    e2hmm::SegPlanDev shape{};
-    shape.K = K, shape.M = M, shape.sumN = tp.pk.sumN, shape.slots = tp.pk.slots, shape.a_words = tp.pk.a_words;
+    tp.looped = runs_looped(body, tp.pk.slots);
+    tp.waves = body_waves(tp.looped, tp.pk.slots);
+    const e2hmm::SegPlanDev shape = loop_shape(tp.pk, K, M);
+    if (check_body_slots(who, tp.pk, K, body, "the E-step of the class transitions has", "the E-step of the class transitions",
+                         e2hmm::trans_estep_looped_lds_bytes(shape, false, false, false)))
+        return 1;
     // (the two bodies' formulas and decision orders have one signature)
     const auto lds_bytes = tp.looped ? e2hmm::trans_estep_looped_lds_bytes : e2hmm::trans_estep_lds_bytes;
     const auto layout = tp.looped ? e2hmm::trans_estep_looped_layout : e2hmm::trans_estep_layout;
-    if (tp.looped && lds_bytes(shape, false, false, false) > e2hmm::SEG_LDS_BYTES)
-        return e2vq_set_error("%s: %d wave-slots, %d states and %d classes take %zu bytes of LDS in the looped body of the "
-                              "E-step of the class transitions (at most %zu)", who, tp.pk.slots, tp.pk.sumN, K,
-                              lds_bytes(shape, false, false, false), (size_t)e2hmm::SEG_LDS_BYTES);
     bool forced = false;
     if (embed_route("ECOZ2_HMM_TRANS_EM_C", &forced, &tp.c_lds)) return 1;
     layout(shape, forced, &tp.c_lds, &tp.a_lds, &tp.w_lds);
@@ -88,31 +84,20 @@ int trans_plan(const char* who, const std::vector<int>& Ns, int M, int body, Tra
 struct TransDev {
     ClassLoopDev loop;
     Scores sc;  // P(O | loop) of each stream
-    DeviceBuffer<double> d_ah, d_c, d_w;
+    ForwardTable ft;  // 4.8.13's, bounded by whole streams in the same way
+    DeviceBuffer<double> d_w;
     DeviceBuffer<i64> d_offs, d_acc;
     std::vector<double> params, w;
     std::vector<i64> acc;  // the counts of the last E-step: 2 K^2 + 2 words
-    std::vector<std::pair<int, int>> chunks;
     KernelTimer timer;
 
     int setup(const char* who, const TransPlan& tp, const LoopModels& lm, const i64* h_offs, int S, hipStream_t st)
     {
-        const int K = lm.K(), sumN = tp.pk.sumN, waves = tp.waves;
+        const int K = lm.K();
         params = trans_params(lm, tp.pk);
-        if (loop.upload(tp.pk, params, K, lm.M, st) || d_offs.upload(h_offs, (size_t)S + 1, st) || sc.reserve((size_t)S) ||
-            d_acc.reserve((size_t)trans_acc_words(K)) || d_w.reserve((size_t)2 * K * K) || timer.create())
-            return 1;
-        // the forward table of 4.8.13, bounded by whole streams in the same way
-        const i64 row = 8 * ((i64)sumN + waves);
-        i64 max_frames = 0;
-        chunks = plan_chunks("ECOZ2_HMM_POSTERIOR_CHUNK_BYTES", row, h_offs, S, &max_frames);
-        if (d_ah.reserve((size_t)max_frames * sumN) || d_c.reserve((size_t)max_frames * waves)) {
-            const std::string why = e2vq_last_error();
-            return e2vq_set_error("%s: no room for the forward table of %lld frames x %d states (%lld bytes; "
-                                  "ECOZ2_HMM_POSTERIOR_CHUNK_BYTES bounds it by whole streams): %s",
-                                  who, (long long)max_frames, sumN, (long long)(max_frames * row), why.c_str());
-        }
-        return 0;
+        return loop.upload(tp.pk, params, K, lm.M, st) || d_offs.upload(h_offs, (size_t)S + 1, st) || sc.reserve((size_t)S) ||
+               d_acc.reserve((size_t)trans_acc_words(K)) || d_w.reserve((size_t)2 * K * K) || timer.create() ||
+               ft.reserve(who, tp.pk.sumN, tp.waves, 0, h_offs, S);
     }
     // One E-step under the effective prices lt: the counts of all streams in `acc` (from zero), P and status of every stream
     // in sc's host mirrors.  Waits for the stream.
@@ -126,10 +111,10 @@ struct TransDev {
         HIPCHK(hipMemsetAsync(d_acc.get(), 0, words * 8, st));
         HIPCHK(hipEventRecord(timer.start.e, st));
         // (one stream: a chunk's forward pass writes the tables only after the previous chunk's backward pass has read them)
-        for (const auto& c : chunks) {
+        for (const auto& c : ft.chunks) {
             const int s0 = c.first, n = c.second - c.first;
             const auto launch = tp.looped ? e2hmm::launch_trans_estep_looped : e2hmm::launch_trans_estep;
-            if (launch(loop.pl, tp.c_lds, tp.a_lds, tp.w_lds, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), d_ah.get(), d_c.get(),
+            if (launch(loop.pl, tp.c_lds, tp.a_lds, tp.w_lds, d_sym, d_offs.get() + s0, n, h_offs[s0], d_w.get(), ft.d_ah.get(), ft.d_c.get(),
                        d_acc.get(), sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
                 return e2vq_set_error("%s: %d wave-slots of %d states cannot be launched", who, tp.pk.slots, tp.pk.sumN);
             HIPCHK(hipGetLastError());
@@ -188,7 +173,7 @@ int trans_check_args(const char* who, int K, const int* Ns, int M, const double*
                      const double* const* Bs, const void* sym, const int64_t* offs, int S, const double* lt, bool rest, LoopModels& lm,
                      TransPlan& tp)
 {
-    int body = EMBED_BODY_RESIDENT;  // (read once a call: a training keeps it over its E-steps)
+    LoopBody body = LoopBody::Resident;  // (read once a call: a training keeps it over its E-steps)
     if (loop_check_args(who, K, Ns, pis, As, Bs, lt && rest && syms_given(sym, offs, S)) || segment_check_shape(who, K, Ns) ||
         trans_check_lt(who, K, lt) || trans_fb_body(&body) || trans_plan(who, std::vector<int>(Ns, Ns + K), M, body, tp) ||
         lm.from_arrays(K, Ns, M, pis, As, Bs))
@@ -225,7 +210,7 @@ extern "C" int e2vq_hmm_transitions_estep(int device, int K, const int* Ns, int 
         dev.estep(who, tp, lt, seqs.sym, (const i64*)offs, S, seqs.st.s))
         return 1;
     for (size_t i = 0; i < dev.acc.size(); ++i) acc[i] += dev.acc[i];
-    for (int s = 0; s < S; ++s) dev.sc.get((size_t)s, nullptr, nullptr, status ? status + s : nullptr, log_prob ? log_prob + s : nullptr);
+    dev.sc.get_all((size_t)S, status, log_prob);
     return 0;
 }
 
@@ -275,7 +260,7 @@ extern "C" int e2vq_hmm_learn_transitions_files(const char* const* model_filenam
         lm.load_checked(who, model_filenames, num_models))
         return 1;
     const int K = lm.K();
-    int body = EMBED_BODY_RESIDENT;  // (read once, before the first E-step)
+    LoopBody body = LoopBody::Resident;  // (read once, before the first E-step)
     if (trans_fb_body(&body) || trans_plan(who, lm.Ns, lm.M, body, tp) || check_names(who, K, lm.names.data())) return 1;
     for (unsigned k = 0; k < num_models; ++k)
         if (posteriors_check_params(lm.models[k])) return e2vq_set_error("%s: %s", model_filenames[k], std::string(e2vq_last_error()).c_str());

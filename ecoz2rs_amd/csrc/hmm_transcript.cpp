@@ -98,7 +98,7 @@ int align_plan(const char* who, int K, const int* Ns, const i64* offs, int S, co
             slots = std::max(slots, sd.slots);
             ++g.s1;
         }
-        g.waves = std::min(slots, e2hmm::SEG_MAX_WAVES);
+        g.waves = body_waves(g.looped, slots);
         ap.max_bytes = std::max(ap.max_bytes, g.bytes);
         ap.launches.push_back(g);
         s0 = g.s1;
@@ -160,19 +160,19 @@ int embed_route(const char* name, bool* forced, bool* lds)
     return 0;
 }
 
-int embed_body(int* body) { return opt_in_body("ECOZ2_HMM_EMBED_BODY", body); }
+int embed_body(LoopBody* body) { return opt_in_body("ECOZ2_HMM_EMBED_BODY", body); }
 
 int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, int body, EStepPlan& p)
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, LoopBody body, EStepPlan& p)
 {
     if (align_plan(who, K, Ns, offs, S, units, unit_offs, optional, ln_switch, p.ap, /*embedded=*/true,
-                   /*own_looped_lds=*/body != EMBED_BODY_RESIDENT))
+                   /*own_looped_lds=*/body != LoopBody::Resident))
         return 1;
     int max_sumN = 0;
     p.looped.assign((size_t)S, 0);
     for (int s = 0; s < S; ++s) {
         const e2hmm::AlignStreamDev& sd = p.ap.streams[(size_t)s];
-        const bool looped = body == EMBED_BODY_LOOPED || (body == EMBED_BODY_AUTO && sd.slots > e2hmm::SEG_MAX_WAVES);
+        const bool looped = runs_looped(body, sd.slots);
         p.looped[(size_t)s] = looped ? 1 : 0;
         if (!looped && sd.slots > e2hmm::SEG_MAX_WAVES)
             return e2vq_set_error("%s: stream %d: the units take %d wave-slots of 64 lanes (at most %d: %s)", who, s, sd.slots,

@@ -184,10 +184,12 @@ def test_the_restated_lds_formula_is_the_sources():
     assert LC.looped_route([5] * 3) == dict(waves=1, a_lds=True, lds=16 + 120 + 600, c_copies=1)
     # no class set the shape check admits comes near the limit: the host's LDS refusal cannot be reached
     assert LC.most_mandatory_lds() == 8 * (2 * 129 + 4096) < LC.SEG_LDS_BYTES // 4
-    # the host sizes the scratch row by the copies of c_t that the kernel stores: one per wave
+    # the host sizes the scratch row by the copies of c_t that the kernel stores: one per wave (body_waves and ForwardTable,
+    # written once for every pass with a looped body)
     host = open(os.path.join(CSRC, "hmm_class_loop.cpp")).read()
-    assert "const int waves = looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots;" in host
-    assert "const i64 row = 8 * ((i64)sumN + waves);" in host and "d_c.reserve((size_t)max_frames * waves)" in host
+    assert "int body_waves(bool looped, int slots) { return looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots; }" in host
+    assert 'ft.reserve("hmm segment --posteriors", sumN, body_waves(looped, slots), 0, h_offs, S)' in host
+    assert "const i64 row = 8 * ((i64)sumN + waves + extra);" in host and "d_c.reserve((size_t)max_frames * waves)" in host
 
 
 VGPR_BUDGET = 128  # 16 waves of one workgroup on a CU: four a SIMD
@@ -225,7 +227,7 @@ def test_the_new_symbols_are_exported_and_no_declared_one_is_lost():
         assert any(part in n for n in names), part
     # the resident body's launcher and kernels are still there, under their own names
     for part in ("22launch_loop_posteriorsERK", "19posteriors_a_in_ldsERK", "k_hmm_loop_posteriorsILb0EE", "k_hmm_loop_posteriorsILb1EE",
-                 "10embed_bodyEPi"):
+                 "10embed_bodyEPNS_8LoopBodyE"):
         assert any(part in n for n in names), part
     # every function the two public headers declare is exported, the signatures of the posteriors unchanged
     declared = set()

@@ -160,9 +160,13 @@ def test_the_restated_lds_formulas_are_the_sources():
     assert "e2hmm::posteriors_trans_looped_lds_bytes(shape, false, false)" in host
     train = open(os.path.join(CSRC, "hmm_trans_train.cpp")).read()
     assert "lds_bytes = tp.looped ? e2hmm::trans_estep_looped_lds_bytes : e2hmm::trans_estep_lds_bytes;" in train
-    assert "if (tp.looped && lds_bytes(shape, false, false, false) > e2hmm::SEG_LDS_BYTES)" in train
-    assert "const i64 row = 8 * ((i64)sumN + waves);" in host and "const i64 row = 8 * ((i64)sumN + waves);" in train
-    assert "d_c.reserve((size_t)max_frames * waves)" in train
+    assert "e2hmm::trans_estep_looped_lds_bytes(shape, false, false, false)" in train  # (what check_body_slots holds against the limit)
+    assert "if (looped_lds <= e2hmm::SEG_LDS_BYTES) return 0;" in host
+    # (body_waves and ForwardTable: written once in hmm_class_loop.cpp for every pass with a looped body)
+    assert "int body_waves(bool looped, int slots) { return looped ? std::min(slots, (int)e2hmm::SEG_MAX_WAVES) : slots; }" in host
+    assert "const i64 row = 8 * ((i64)sumN + waves + extra);" in host and "d_c.reserve((size_t)max_frames * waves)" in host
+    assert 'ft.reserve("hmm segment --grammar-posteriors", sumN, body_waves(looped, slots), 0, h_offs, S)' in host
+    assert "tp.waves = body_waves(tp.looped, tp.pk.slots);" in train and "ft.reserve(who, tp.pk.sumN, tp.waves, 0, h_offs, S)" in train
     # the frame is written once, and the units are compiled like their siblings
     for src in (post, est):
         assert '#include "hmm_trans_fb_looped_step.h"' in src and "fb_forward_frame(" in src and "fb_post_R(" in src
@@ -421,7 +425,7 @@ def test_the_new_symbols_are_exported_and_the_headers_name_the_variable():
     names = set(line.split()[-1] for line in r.stdout.splitlines() if line.strip())
     for part in ("launch_loop_posteriors_trans_looped", "launch_trans_estep_looped", "posteriors_trans_looped_lds_bytes",
                  "trans_estep_looped_lds_bytes", "posteriors_trans_looped_layout", "trans_estep_looped_layout", "trans_fb_body",
-                 "trans_fb_looped",
+                 "runs_looped",
                  *[f"{k}ILb{a}ELb{w}EE" for k in ("k_hmm_loop_posteriors_trans_looped", "k_hmm_trans_estep_looped") for a in (0, 1) for w in (0, 1)]):
         assert any(part in n for n in names), part
     # the resident bodies are still there, under their own names
