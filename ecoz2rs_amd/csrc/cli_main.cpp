@@ -118,11 +118,14 @@ static int usage()
             "  ecoz2 hmm align -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
             "                  [--switch-penalty <x <= 0>] [--filler <class>] [-c <csv dir|file.csv>] --labels <files>...\n"
             "                  [--posteriors [--frame-posteriors <dir>]]\n"
+            "                  [--body <auto|resident|looped>]\n"
             "                  (--signals <.wav files>... | --predictors <.prd files>... | --sequences <.seq files>...)\n"
             "                  (each recording aligned to the units its label file names, in their order: a segment .csv or a\n"
             "                  selection table; --filler: that class's model may stand before, between and after the units;\n"
             "                  --posteriors adds how sure each unit is: the path's mean and least posterior over its frames, the\n"
-            "                  probability that the unit is there, the mean and spread of its first frame; and the per-frame table)\n"
+            "                  probability that the unit is there, the mean and spread of its first frame; and the per-frame table;\n"
+            "                  --body, with --posteriors: the kernel body of the posteriors -- resident takes a transcript of at most\n"
+            "                  16 wave-slots, looped any number, auto the looped one above 16; the same posteriors bit for bit)\n"
             "  ecoz2 hmm show --hmm <file> [-f|--format \"%%Lg \"]\n"
             "  ecoz2 lpc [-P 36] [-W 45] [-O 15] [-m 0] [-s 0] [-X 5] [--verbose] --signals <files|dirs|tt.csv>...\n"
             "            [--signals-dir-template data/signals] [--tt <TRAIN|TEST>] [--class <class>]\n"
@@ -1174,8 +1177,8 @@ static int hmm_align_cmd(int argc, char** argv)
 {
     int P = 36, W = 45, O = 15;
     double ln_switch = 0.0;
-    bool posteriors = false;
-    std::string codebook, csv, filler, frames_dir;
+    bool posteriors = false, have_body = false;
+    std::string codebook, csv, filler, frames_dir, body;
     std::vector<std::string> models, labels, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -1207,6 +1210,7 @@ static int hmm_align_cmd(int argc, char** argv)
         else if (a == "-c" || a == "--csv") csv = val("-c");
         else if (a == "--posteriors") posteriors = true;
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
+        else if (a == "--body") { body = val("--body"); have_body = true; }
         else if (a == "--signals") many(signals);
         else if (a == "--predictors") many(predictors);
         else if (a == "-s" || a == "--sequences") many(sequences);
@@ -1219,6 +1223,15 @@ static int hmm_align_cmd(int argc, char** argv)
     }
     if (!(ln_switch <= 0.0) || std::isinf(ln_switch)) { fprintf(stderr, "hmm align: --switch-penalty %g: finite and at most 0\n", ln_switch); return 2; }
     if (!frames_dir.empty() && !posteriors) { fprintf(stderr, "hmm align: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
+    if (have_body) {  // the body of the posteriors (ECOZ2_HMM_ALIGN_POSTERIOR_BODY), set in this process before the call
+        if (!posteriors) {
+            fprintf(stderr, "hmm align: --body <auto|resident|looped> needs --posteriors (it chooses the body of the posteriors; the "
+                            "alignment picks its own)\n");
+            return 2;
+        }
+        if (!body_value_ok("hmm align --posteriors", "--body", body)) return 2;
+        setenv("ECOZ2_HMM_ALIGN_POSTERIOR_BODY", body.c_str(), 1);
+    }
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm align: --signals and --predictors need --codebook <cbook>\n"); return 2; }

@@ -1,9 +1,11 @@
 // hmm_align_posterior.cpp -- how sure the alignment is (`hmm align --posteriors`, e2vq_hmm_align_posteriors):
 // per unit and frame the posterior that the unit holds the frame, per unit the probability that a path visits it and the mean
-// and spread of the frame it is entered at, over the kernel of hmm_align_posterior.hip.  The host adds the places of the
-// occupancies to hmm_transcript.cpp's plan of the embedded forward-backward pass (all before any HIP call), takes the logarithm
-// of the (mantissa, exponent) pairs and the unit moments, and writes the reports.  The checks, the transcripts of the label
-// files, the plan, the parameter block and the reports' common parts are hmm_transcript.cpp's (hmm_host.h).
+// and spread of the frame it is entered at, over the kernels of hmm_align_posterior.hip (the resident body) and
+// hmm_align_posterior_looped.hip (the looped body, which ECOZ2_HMM_ALIGN_POSTERIOR_BODY opts into).  The host adds the body, the
+// places of the occupancies and each launch's LDS layout to hmm_transcript.cpp's plan of the embedded forward-backward pass (all
+// before any HIP call), takes the logarithm of the (mantissa, exponent) pairs and the unit moments, and writes the reports.
+// The checks, the transcripts of the label files, the plan, the parameter block and the reports' common parts are
+// hmm_transcript.cpp's (hmm_host.h).
 #include "hmm_host.h"
 
 namespace e2hmm_host {
@@ -12,24 +14,45 @@ namespace {
 thread_local float g_align_post_kernel_ms = -1.f;  // e2vq_hmm_align_posteriors_last_kernel_ms
 
 // What the host decides about a call before the device is touched: the plan of the forward-backward pass, whether A goes to
-// LDS, and where each stream's occupancies begin.
+// LDS (the resident launches share one layout, a launch of the looped body has its own), and where each stream's occupancies
+// begin.
 struct PostPlan : EStepPlan {
-    std::vector<i64> occ_at;  // [S + 1]
+    std::vector<i64> occ_at;        // [S + 1]
+    std::vector<uint8_t> loop_a_lds;  // per chunk: A in LDS, of a launch of the looped body
 };
 
 int post_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
               const uint8_t* optional, double ln_switch, PostPlan& pp)
 {
+    // ECOZ2_HMM_ALIGN_POSTERIOR_BODY: unset or "resident" keeps every stream resident and every refusal as it was
+    LoopBody body = LoopBody::Resident;
+    if (align_post_body(&body)) return 1;
     if (estep_plan(who, K, Ns, M, offs, S, units, unit_offs, optional, ln_switch, "the alignment posteriors have a resident body only", false,
-                   LoopBody::Resident, pp))
+                   body, pp, /*looped_unit_bytes=*/3 * sizeof(double)))
         return 1;
     pp.occ_at.assign((size_t)S + 1, 0);
     for (int s = 0; s < S; ++s) pp.occ_at[(size_t)s + 1] = pp.occ_at[(size_t)s] + (offs[s + 1] - offs[s]) * pp.ap.streams[(size_t)s].L;
     // A in LDS when it fits; ECOZ2_HMM_EMBED_A = lds | global forces either, as in the E-step
     const int aw = pp.cls.a_words;
+    // the launches of the looped body: each by its own largest shapes
+    const bool a_said = pp.a_lds;  // what the variable forces
+    pp.loop_a_lds.assign(pp.chunks.size(), 0);
+    for (size_t i = 0; i < pp.chunks.size(); ++i) {
+        const EStepPlan::Shape& g = pp.shapes[i];
+        if (!g.looped) continue;
+        auto bytes = [&](bool a) { return e2hmm::align_post_looped_lds_bytes(g.max_L, g.max_slots, g.max_sumN, aw, a); };
+        const bool a = pp.a_forced ? a_said : bytes(true) <= e2hmm::SEG_LDS_BYTES;
+        pp.loop_a_lds[i] = a ? 1 : 0;
+        if (bytes(a) > e2hmm::SEG_LDS_BYTES)
+            return e2vq_set_error("%s: streams %d to %d: %d units of sum N = %d states in %d wave-slots and A in %s take %zu bytes of LDS "
+                                  "(at most %zu)", who, pp.chunks[i].first, pp.chunks[i].second - 1, g.max_L, g.max_sumN, g.max_slots,
+                                  a ? "LDS" : "global memory", bytes(a), e2hmm::SEG_LDS_BYTES);
+    }
+    // the launches of the resident body: one layout for all of them, by the most units of their streams
     if (!pp.a_forced) pp.a_lds = e2hmm::align_post_lds_bytes(pp.max_L, aw, true) <= e2hmm::SEG_LDS_BYTES;
     const size_t lds = e2hmm::align_post_lds_bytes(pp.max_L, aw, pp.a_lds);
-    if (lds > e2hmm::SEG_LDS_BYTES)
+    const bool resident_runs = S == 0 || std::count(pp.looped.begin(), pp.looped.end(), 0) > 0;
+    if (lds > e2hmm::SEG_LDS_BYTES && resident_runs)
         return e2vq_set_error("%s: %d units and A in %s take %zu bytes of LDS (at most %zu)", who, pp.max_L, pp.a_lds ? "LDS" : "global memory",
                               lds, e2hmm::SEG_LDS_BYTES);
     return 0;
@@ -83,13 +106,24 @@ int post_device(const char* who, const PostPlan& pp, const LoopModels& lm, const
     if (nocc > 0) HIPCHK(hipMemsetAsync(d_occ.get(), 0, (size_t)nocc * 8, st));
     HIPCHK(hipEventRecord(timer.start.e, st));
     // (one stream: a chunk's forward pass writes the scratch only after the previous chunk's backward pass has read it)
-    for (const auto& c : pp.chunks) {
-        const int s0 = c.first, n = c.second - c.first;
+    for (size_t i = 0; i < pp.chunks.size(); ++i) {
+        const int s0 = pp.chunks[i].first, n = pp.chunks[i].second - s0;
+        const EStepPlan::Shape& g = pp.shapes[i];
         const e2hmm::AlignPostDev po{path_unit && frames > 0 ? d_path.get() : nullptr, ref && nunits > 0 ? d_ref.get() : nullptr,
                                      d_occ_at.get() + s0, nocc > 0 ? d_occ.get() : nullptr, d_post.get(), d_w.get(), nunits};
-        if (e2hmm::launch_align_posteriors(pd.plan(pp, s0, d_params.get()), pp.a_lds, pp.max_slots, d_sym, pd.offs.get() + s0, n, h_offs[s0],
-                                           pp.row_words, pd.scr.get(), po, sc.d_mant.get() + s0, sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+        if (g.looped) {
+            e2hmm::EmbedPlanDev pl = pd.plan(pp, s0, d_params.get());
+            pl.max_L = g.max_L;
+            if (e2hmm::launch_align_posteriors_looped(pl, pp.loop_a_lds[i] != 0, g.max_slots, g.max_sumN, d_sym, pd.offs.get() + s0, n,
+                                                      h_offs[s0], pp.row_words, pd.scr.get(), po, sc.d_mant.get() + s0,
+                                                      sc.d_exp.get() + s0, sc.d_status.get() + s0, st))
+                return e2vq_set_error("%s: %d units of sum N = %d states in %d wave-slots cannot be launched", who, g.max_L, g.max_sumN,
+                                      g.max_slots);
+        } else if (e2hmm::launch_align_posteriors(pd.plan(pp, s0, d_params.get()), pp.a_lds, pp.max_slots, d_sym, pd.offs.get() + s0, n,
+                                                  h_offs[s0], pp.row_words, pd.scr.get(), po, sc.d_mant.get() + s0, sc.d_exp.get() + s0,
+                                                  sc.d_status.get() + s0, st)) {
             return e2vq_set_error("%s: %d units in %d wave-slots cannot be launched", who, pp.max_L, pp.max_slots);
+        }
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(timer.stop.e, st));

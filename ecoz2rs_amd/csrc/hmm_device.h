@@ -286,6 +286,15 @@ size_t align_post_lds_bytes(int max_L, int a_words, bool a_lds);
 int launch_align_posteriors(const EmbedPlanDev& pl, bool a_lds, int waves, const unsigned short* sym, const long long* offs, int S,
                             long long a0, long long row_words, double* scr, const AlignPostDev& out, double* mant, long long* exp2,
                             int* status, hipStream_t st);
+// The looped body of the same pass (hmm_align_posterior_looped.hip): streams of any number of slots, a workgroup of
+// min(max_slots, 16) waves each; the same outputs, P and status bit for bit.  pl.max_L, max_slots and max_sumN are the largest
+// of the launch's streams.  Dynamic LDS: embed_looped_lds_bytes' mandatory part (the partial sums, V / R, two per-state arrays
+// of max_sumN doubles), the three per-unit sums (3 x max_L doubles, mandatory too) and A (a_lds).
+size_t align_post_looped_lds_bytes(int max_L, int max_slots, int max_sumN, int a_words, bool a_lds);
+// as launch_embed_fb_looped takes them (the scratch too).  Returns 1 when the shape cannot be launched.
+int launch_align_posteriors_looped(const EmbedPlanDev& pl, bool a_lds, int max_slots, int max_sumN, const unsigned short* sym,
+                                   const long long* offs, int S, long long a0, long long row_words, double* scr,
+                                   const AlignPostDev& out, double* mant, long long* exp2, int* status, hipStream_t st);
 
 // Smoothed class posteriors under the same class loop (hmm_posterior.hip), on the packing above with at
 // most SEG_MAX_WAVES slots.  pl.params here: pi (sumN) | e = sw pi (sumN) | A of every class with the leading dimension

@@ -333,7 +333,7 @@ int loop_body_looped(const char* env_name, int slots, bool* looped);
 
 // The body of a pass whose looped kernel is opt-in: resident (more than 16 wave-slots are refused), looped, or resident up to
 // 16 slots and looped above.  opt_in_body is the one reader of the variables: unset, empty or "resident" / "looped" / "auto" of
-// `env_name` -> *body; any other value is refused with "<env_name>=<v>: auto, resident or looped".  The four readers below name
+// `env_name` -> *body; any other value is refused with "<env_name>=<v>: auto, resident or looped".  The five readers below name
 // their variable; each entry point calls its reader once.  runs_looped: whether a packing (or a transcript) of `slots` runs the
 // looped kernels under `body`.  body_waves: the waves of a workgroup, each of which stores its copy of c_t.
 enum class LoopBody { Resident, Looped, Auto };
@@ -341,6 +341,7 @@ int opt_in_body(const char* env_name, LoopBody* body);
 bool runs_looped(LoopBody body, int slots);
 int body_waves(bool looped, int slots);
 int embed_body(LoopBody* body);          // ECOZ2_HMM_EMBED_BODY: the E-step of `hmm learn --embedded`
+int align_post_body(LoopBody* body);     // ECOZ2_HMM_ALIGN_POSTERIOR_BODY: `hmm align --posteriors` (4.8.12)
 int posteriors_body(LoopBody* body);     // ECOZ2_HMM_POSTERIOR_BODY: `hmm segment --posteriors` (4.8.7)
 int segment_trans_body(LoopBody* body);  // ECOZ2_HMM_SEGMENT_TRANS_BODY: `--class-transitions` and its session (4.8.8 / 4.8.15)
 // ECOZ2_HMM_TRANS_FB_BODY: `--grammar-posteriors` (4.8.13) and the E-step of `hmm transitions --em` (4.8.14);
@@ -477,9 +478,13 @@ struct EStepPlan {
     std::vector<Shape> shapes;                   // per chunk
 };
 // `what` closes the refusal of a stream of more than 16 wave-slots that would run resident; first_flags: EMBED_FIRST on a
-// class's first unit; body: the caller's choice (the embedded E-step: what embed_body gave), held against each stream's slots
+// class's first unit; body: the caller's choice (the embedded E-step: what embed_body gave; the alignment posteriors: what
+// align_post_body gave), held against each stream's slots; looped_unit_bytes: what the caller's looped body keeps in LDS per unit
+// on top of embed_looped_lds_bytes' mandatory part (the alignment posteriors: the three per-unit sums), counted wherever a looped
+// stream or launch is held against LDS
 int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, LoopBody body, EStepPlan& p);
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, LoopBody body, EStepPlan& p,
+               size_t looped_unit_bytes = 0);
 // "lds" / "global" / unset of the variable `name` -> *forced (whether it is set) and *lds; any other value is refused
 int embed_route(const char* name, bool* forced, bool* lds);
 // pi of every class | e = sw pi | A of every class, row i at i (N | 1) | B of every class

@@ -161,10 +161,17 @@ int embed_route(const char* name, bool* forced, bool* lds)
 }
 
 int embed_body(LoopBody* body) { return opt_in_body("ECOZ2_HMM_EMBED_BODY", body); }
+int align_post_body(LoopBody* body) { return opt_in_body("ECOZ2_HMM_ALIGN_POSTERIOR_BODY", body); }
 
 int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, int S, const int32_t* units, const i64* unit_offs,
-               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, LoopBody body, EStepPlan& p)
+               const uint8_t* optional, double ln_switch, const char* what, bool first_flags, LoopBody body, EStepPlan& p,
+               size_t looped_unit_bytes)
 {
+    // the mandatory LDS of the looped body: the E-step's partial sums, V / R and per-state arrays, and what the caller's pass
+    // keeps per unit on top of them
+    auto looped_lds = [&](int L, int slots, int sumN) {
+        return e2hmm::embed_looped_lds_bytes(L, slots, sumN, 0, false, false) + looped_unit_bytes * (size_t)L;
+    };
     if (align_plan(who, K, Ns, offs, S, units, unit_offs, optional, ln_switch, p.ap, /*embedded=*/true,
                    /*own_looped_lds=*/body != LoopBody::Resident))
         return 1;
@@ -178,10 +185,9 @@ int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, in
             return e2vq_set_error("%s: stream %d: the units take %d wave-slots of 64 lanes (at most %d: %s)", who, s, sd.slots,
                                   e2hmm::SEG_MAX_WAVES, what);
         // (the looped body's partial sums, V / R and per-state arrays are mandatory; A and the AN table go in when they fit)
-        if (looped && e2hmm::embed_looped_lds_bytes(sd.L, sd.slots, sd.sumN, 0, false, false) > e2hmm::SEG_LDS_BYTES)
+        if (looped && looped_lds(sd.L, sd.slots, sd.sumN) > e2hmm::SEG_LDS_BYTES)
             return e2vq_set_error("%s: stream %d: %d units of sum N = %d states in %d wave-slots do not fit in LDS (%zu of %zu bytes)", who,
-                                  s, sd.L, sd.sumN, sd.slots, e2hmm::embed_looped_lds_bytes(sd.L, sd.slots, sd.sumN, 0, false, false),
-                                  e2hmm::SEG_LDS_BYTES);
+                                  s, sd.L, sd.sumN, sd.slots, looped_lds(sd.L, sd.slots, sd.sumN), e2hmm::SEG_LDS_BYTES);
         if (!looped) {
             p.max_L = std::max(p.max_L, sd.L);
             p.max_slots = std::max(p.max_slots, sd.slots);
@@ -219,7 +225,7 @@ int estep_plan(const char* who, int K, const int* Ns, int M, const i64* offs, in
                 const e2hmm::AlignStreamDev& sd = p.ap.streams[(size_t)s1];
                 const int mL = std::max(g.max_L, sd.L), mS = std::max(g.max_slots, sd.slots), mN = std::max(g.max_sumN, sd.sumN);
                 if (s1 > s0 && ((p.looped[(size_t)s1] != 0) != g.looped ||
-                                (g.looped && e2hmm::embed_looped_lds_bytes(mL, mS, mN, 0, false, false) > e2hmm::SEG_LDS_BYTES)))
+                                (g.looped && looped_lds(mL, mS, mN) > e2hmm::SEG_LDS_BYTES)))
                     break;
                 g.max_L = mL, g.max_slots = mS, g.max_sumN = mN;
                 ++s1;

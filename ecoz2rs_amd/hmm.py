@@ -176,7 +176,7 @@ def _kernel_ms(fn):
 @contextlib.contextmanager
 def _body_env(name, body):
     """the variable `name` (ECOZ2_HMM_EMBED_BODY, ECOZ2_HMM_POSTERIOR_BODY, ECOZ2_HMM_SEGMENT_TRANS_BODY,
-    ECOZ2_HMM_TRANS_FB_BODY) = body ("auto", "resident" or "looped") for the
+    ECOZ2_HMM_TRANS_FB_BODY, ECOZ2_HMM_ALIGN_POSTERIOR_BODY) = body ("auto", "resident" or "looped") for the
     duration of a call; None leaves the environment alone"""
     if body is None:
         yield
@@ -1170,24 +1170,27 @@ def align_last_kernel_ms():
 
 
 def align_files(model_filenames, input_filenames, label_filenames, ln_switch=0.0, filler=None, codebook=None, P=36, W_ms=45, O_ms=15,
-                csv=None, posteriors=False, frame_posteriors=None):
+                csv=None, posteriors=False, frame_posteriors=None, body=None):
     """`hmm align`: input i (.wav, .prd or .seq) aligned to the units label file i names (a segment CSV or a
     selection table, as `hmm transitions` reads them); filler: the class of a model inserted as an optional unit around and
     between them; per input a block on stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the units.
     posteriors (4.8.12): how sure every unit is, in the block and in five more CSV columns, and with frame_posteriors (a
-    directory) a per-frame table for every input"""
+    directory) a per-frame table for every input; body as `align_posteriors` takes it (it needs posteriors)"""
     if len(label_filenames) != len(input_filenames):
         raise ValueError(f"{len(label_filenames)} label files for {len(input_filenames)} inputs")
     if frame_posteriors is not None and not posteriors:
         raise ValueError("frame_posteriors needs posteriors=True")
+    if body is not None and not posteriors:
+        raise ValueError("body needs posteriors=True")
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
     l, _k3 = _strs(label_filenames)
     if posteriors:
-        check(lib.e2vq_hmm_align_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
-                                                  len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
-                                                  str(filler).encode() if filler else None, str(csv).encode() if csv else None,
-                                                  str(frame_posteriors).encode() if frame_posteriors is not None else None))
+        with _body_env("ECOZ2_HMM_ALIGN_POSTERIOR_BODY", body):
+            check(lib.e2vq_hmm_align_files_posteriors(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l,
+                                                      len(input_filenames), int(P), int(W_ms), int(O_ms), float(ln_switch),
+                                                      str(filler).encode() if filler else None, str(csv).encode() if csv else None,
+                                                      str(frame_posteriors).encode() if frame_posteriors is not None else None))
         return
     check(lib.e2vq_hmm_align_files(m, len(model_filenames), str(codebook).encode() if codebook else None, f, l, len(input_filenames),
                                    int(P), int(W_ms), int(O_ms), float(ln_switch), str(filler).encode() if filler else None,
@@ -1208,12 +1211,14 @@ def align_unit_moments(w0, w1, w2, ref=None):
 
 
 def align_posteriors(models, sym, offs, units, unit_offs, optional=None, ln_switch=0.0, path_unit=None, ref=None, occupancy=True,
-                     device=0):
+                     device=0, body=None):
     """how sure the alignment is: models, sym, offs, units, unit_offs, optional, ln_switch as `align` takes
     them; path_unit: `align`'s per-frame `unit` (or None); ref: a reference frame per unit for the moments (or None = 0)
     -> dict: occ, per stream the (T_s, L_s) array of P(unit l holds frame t) (only with occupancy); post_path per frame (occ at
     the path's unit; 0 without path_unit); per unit w0 = present (P(a path visits the unit)), w1, w2, begin_mean, begin_sd (the
-    frame the unit is entered at); per stream log_prob, status"""
+    frame the unit is entered at); per stream log_prob, status.  body: "auto", "resident" or "looped"
+    (ECOZ2_HMM_ALIGN_POSTERIOR_BODY for this call: the looped body takes a stream of more than 16 wave-slots, "auto" uses it
+    above 16; the same bits either way); None: what the environment says"""
     a = _transcript_args(models, sym, offs, units, unit_offs, optional)
     offs, S, unit_offs, nu = a.offs, a.S, a.unit_offs, a.nu
     T = int(offs[-1])
@@ -1231,10 +1236,11 @@ def align_posteriors(models, sym, offs, units, unit_offs, optional=None, ln_swit
     post = np.zeros(max(T, 1))
     w0, w1, w2 = (np.zeros(max(nu, 1)) for _ in range(3))
     lp, st = np.zeros(max(S, 1)), np.zeros(max(S, 1), dtype=np.int32)
-    check(lib.e2vq_hmm_align_posteriors(device, *a.c_args, float(ln_switch), path_unit.ctypes.data if path_unit is not None else None,
-                                        ref.ctypes.data if ref is not None else None, occ.ctypes.data if occ is not None else None,
-                                        post.ctypes.data, w0.ctypes.data, w1.ctypes.data, w2.ctypes.data, lp.ctypes.data, st.ctypes.data,
-                                        a.on_device))
+    with _body_env("ECOZ2_HMM_ALIGN_POSTERIOR_BODY", body):
+        check(lib.e2vq_hmm_align_posteriors(device, *a.c_args, float(ln_switch), path_unit.ctypes.data if path_unit is not None else None,
+                                            ref.ctypes.data if ref is not None else None, occ.ctypes.data if occ is not None else None,
+                                            post.ctypes.data, w0.ctypes.data, w1.ctypes.data, w2.ctypes.data, lp.ctypes.data,
+                                            st.ctypes.data, a.on_device))
     present, begin_mean, begin_sd = align_unit_moments(w0[:nu], w1[:nu], w2[:nu], None if ref is None else ref[:nu])
     out = dict(post_path=post[:T], w0=w0[:nu], w1=w1[:nu], w2=w2[:nu], present=present, begin_mean=begin_mean, begin_sd=begin_sd,
                log_prob=lp[:S], status=st[:S])

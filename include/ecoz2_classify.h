@@ -849,17 +849,28 @@ int e2vq_hmm_learn_embedded_files(const char *const *model_filenames, unsigned n
  * G_0[l].  Every admissible path that visits unit l enters it exactly once: the sum of En_t[l] over t is P(the path visits l).
  * Per unit.  The sums run in the order the backward pass meets the frames, t = T-1 down to 0, each term added by one
  * addition: w0[l] += En_t[l]; w1[l] += d * En_t[l]; w2[l] += (d * d) * En_t[l]; d = (double)(t - ref[l]).  d * d is exact while
- * |d| < 2^26.5 (94 906 265 frames) and one rounded product beyond.  The unit's state-0 lane holds the three sums in registers
- * over the whole stream and writes them once.
+ * |d| < 2^26.5 (94 906 265 frames) and one rounded product beyond.  The unit's state-0 lane holds the three sums over the whole
+ * stream (the resident body in registers, the looped body in LDS words of its own) and writes them once.
  * Per frame.  post_path[t] = G_t[path_unit[t]]; 0.0 where path_unit[t] is 0xFFFF or >= L_s, or where path_unit is NULL.  The
  * lane that owns the unit writes it; path_unit is handed out 64 frames at a time, as the symbols are.
  * Status != 0.  Every occ, post_path, w0, w1 and w2 entry of the stream is 0.0; log_prob is -inf.
  * Host (e2vq_hmm_align_unit_moments, plain C++ in this order): present = w0; q = w1 / w0; begin_mean = (double)ref + q;
  * begin_sd = sqrt(max(0, w2 / w0 - q * q)); both NaN where !(w0 > 0).
  * Refused before any HIP call: everything e2vq_hmm_embedded_estep refuses; a packing of more than 16 wave-slots, by a message of
- * this function's own that names the slot count and says that only a resident body exists; a ref outside [0, T).
+ * this function's own that names the slot count and says that only a resident body exists (unless the looped body is chosen:
+ * the last paragraph); a ref outside [0, T).
  * Scratch: ah_t, m_t and c_t as in the E-step; whole streams per launch under ECOZ2_HMM_EMBED_CHUNK_BYTES, a larger stream
- * alone; ECOZ2_HMM_EMBED_A = lds | global is honoured as there.  The outputs have device mirrors for the whole call. */
+ * alone; ECOZ2_HMM_EMBED_A = lds | global is honoured as there.  The outputs have device mirrors for the whole call.
+ * The body.  ECOZ2_HMM_ALIGN_POSTERIOR_BODY chooses the kernel body in e2vq_hmm_align_posteriors and
+ * e2vq_hmm_align_files_posteriors (no other entry point reads it).  Unset, empty or "resident": as above, more than 16
+ * wave-slots are refused.  "looped": every stream runs the looped body (hmm_align_posterior_looped.hip), which takes any number
+ * of slots as the E-step's looped body does.  "auto": resident up to 16 slots, looped above; a launch has one body, so the
+ * launches are cut where it changes.  Any other value is refused before a HIP call:
+ * "ECOZ2_HMM_ALIGN_POSTERIOR_BODY=<v>: auto, resident or looped".  Nothing above depends on the body: both give the same bits
+ * of every output, of log_prob and the same status.  A looped stream needs 16 (slots + sum N) + 40 L bytes of LDS; one that
+ * does not fit in 160 KB is refused before a HIP call ("stream %d: %d units of sum N = %d states in %d wave-slots do not fit in
+ * LDS").  A goes to LDS when it fits next to that, per launch; ECOZ2_HMM_EMBED_A forces either choice here too, and a forced
+ * layout that does not fit is refused. */
 int e2vq_hmm_align_posteriors(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
                               const double *const *Bs, const void *sym, const int64_t *offs, int S, const int32_t *units,
                               const int64_t *unit_offs, const uint8_t *optional, double ln_switch, const uint16_t *path_unit,
@@ -884,7 +895,9 @@ int e2vq_hmm_align_report_posteriors(const char *name, int64_t T, int K, const c
 /* `hmm align --posteriors [--frame-posteriors <dir>]`: e2vq_hmm_align_files with the report above.  The symbols of an input are
  * staged once; e2vq_hmm_align and the posteriors run on the same device buffer; ref is the path's begin (0 where it is -1),
  * path_unit its unit.  frames_dir (may be NULL): <frames_dir>/<input's base name>.csv per input.  Everything e2vq_hmm_align_files
- * and e2vq_hmm_align_posteriors refuse is refused before any HIP call. */
+ * and e2vq_hmm_align_posteriors refuse is refused before any HIP call, under the body that ECOZ2_HMM_ALIGN_POSTERIOR_BODY chooses
+ * for the posteriors: with "auto" or "looped" a transcript of more than 16 wave-slots is decoded by e2vq_hmm_align, which picks
+ * its looped body by itself, and then scored; without it such a transcript is refused. */
 int e2vq_hmm_align_files_posteriors(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
                                     const char *const *input_filenames, const char *const *label_filenames, int num_inputs,
                                     int P, int W_ms, int O_ms, double ln_switch, const char *filler_class,

@@ -10,6 +10,15 @@ method of tools/probe/hmm_embedded_bench.py).  Every time is the HIP-event pair 
 with the path and the begin frames of the alignment, once with the occupancy table (T x L doubles) and once without.  `warmup`
 calls discarded, then the median, least and greatest of `reps`.
 
+Two more tables for the looped body (ECOZ2_HMM_ALIGN_POSTERIOR_BODY, hmm_align_posterior_looped.hip):
+
+  forced   the looped body forced at the four shapes above, against the resident body in the same process (the two alternate
+           call by call): the price of LDS-resident state and of the extra pass over the slots, which `auto` avoids
+  above    the long-transcript rows of 4.8.10 (more than 16 slots, which only the looped body takes): the looped posteriors
+           against the looped E-step (k_hmm_embed_fb_looped) and the alignment of the same stream to the same transcript, the
+           three alternating call by call.  The posteriors do a subset of the E-step's work, so over_estep should not exceed 1
+           beyond the spread of the runs; over_estep_min / _max are the least and greatest ratio of a pair of neighbouring calls.
+
     python tools/probe/hmm_align_posteriors_bench.py [--out profiles/hmm_align_posteriors_bench.json] [--T 38265] [--reps 7]
                                                      [--warmup 2]
 """
@@ -27,6 +36,7 @@ from ecoz2rs_amd import hmm  # noqa: E402
 
 M, K, LN_SWITCH = 1024, 5, -1.0
 SHAPES = ((5, 20), (16, 20), (32, 20), (5, 100))
+ABOVE = ((5, 500), (16, 500), (16, 100), (32, 100))
 
 
 def slots_of(Ns):
@@ -48,6 +58,23 @@ def timed(call, last_ms, reps, warmup):
     return dict(kernel_ms=statistics.median(ms), kernel_ms_min=min(ms), kernel_ms_max=max(ms))
 
 
+def alternating(calls, reps, warmup):
+    """calls: {key: (call, last_ms)}, run one after the other `warmup` + `reps` times -> ({key: the summary of `timed`}, {key: [ms]})"""
+    ms = {k: [] for k in calls}
+    for r in range(warmup + reps):
+        for k, (call, last_ms) in calls.items():
+            call()
+            if r >= warmup:
+                ms[k].append(last_ms())
+    return {k: dict(kernel_ms=statistics.median(v), kernel_ms_min=min(v), kernel_ms_max=max(v)) for k, v in ms.items()}, ms
+
+
+def ratio(ms, a, b):
+    """a over b: of the medians, and the least and greatest over the pairs of neighbouring calls"""
+    pairs = [x / y for x, y in zip(ms[a], ms[b])]
+    return statistics.median(ms[a]) / statistics.median(ms[b]), min(pairs), max(pairs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="profiles/hmm_align_posteriors_bench.json")
@@ -59,7 +86,19 @@ def main():
     sym = rng.integers(0, M, a.T).astype(np.uint16)
     offs = np.array([0, a.T], dtype=np.int64)
     doc = dict(tool="tools/probe/hmm_align_posteriors_bench.py", M=M, K=K, T=a.T, ln_switch=LN_SWITCH, reps=a.reps, warmup=a.warmup,
-               shapes=[])
+               shapes=[], forced=[], above=[])
+
+    def setup(N, L):
+        e.hmm.set_random_seed(N)
+        models = [hmm.init_model(N, M, 0) for _ in range(K)]
+        units = (np.arange(L) % K).astype(np.int32)
+        return models, units, dict(N=N, L=L, slots=slots_of([N] * L), sum_N=N * L)
+
+    def post(models, units, L, path, ref, body, occupancy, into):
+        return lambda: into.update(hmm.align_posteriors(models, sym, offs, units, [0, L], None, LN_SWITCH, path_unit=path, ref=ref,
+                                                        occupancy=occupancy, body=body))
+
+    same = lambda x, y, keys: bool(all(np.array_equal(np.asarray(x[k]).view(np.uint64), np.asarray(y[k]).view(np.uint64)) for k in keys))
     for N, L in SHAPES:
         e.hmm.set_random_seed(N)
         models = [hmm.init_model(N, M, 0) for _ in range(K)]
@@ -85,6 +124,45 @@ def main():
         row["between"] = bool(row["align"]["kernel_ms"] <= row["posteriors_occ"]["kernel_ms"] <= row["estep"]["kernel_ms"])
         print(json.dumps(row), flush=True)
         doc["shapes"].append(row)
+    ms_of = hmm.align_posteriors_last_kernel_ms
+    for N, L in SHAPES:
+        models, units, row = setup(N, L)
+        al = hmm.align(models, sym, offs, units, [0, L], None, LN_SWITCH)
+        path, ref = al["unit"], np.where(al["begin"] < 0, 0, al["begin"])
+        lo, re = {}, {}
+        t, ms = alternating(dict(looped=(post(models, units, L, path, ref, "looped", True, lo), ms_of),
+                                 resident=(post(models, units, L, path, ref, "resident", True, re), ms_of)), a.reps, a.warmup)
+        row.update(t)
+        row["looped_over_resident"], row["looped_over_resident_min"], row["looped_over_resident_max"] = ratio(ms, "looped", "resident")
+        row["same_words"] = same(lo, re, ("post_path", "w0", "w1", "w2", "log_prob")) and same(lo["occ"], re["occ"], (0,))
+        print(json.dumps(row), flush=True)
+        doc["forced"].append(row)
+    for N, L in ABOVE:
+        models, units, row = setup(N, L)
+        al, es, po, pn = {}, {}, {}, {}
+        al.update(hmm.align(models, sym, offs, units, [0, L], None, LN_SWITCH))
+        path, ref = al["unit"], np.where(al["begin"] < 0, 0, al["begin"])
+        t, ms = alternating(dict(
+            estep=(lambda: es.update(hmm.embedded_estep(models, sym, offs, units, [0, L], None, LN_SWITCH, body="auto")),
+                   hmm.embedded_last_kernel_ms),
+            posteriors_occ=(post(models, units, L, path, ref, "auto", True, po), ms_of),
+            posteriors=(post(models, units, L, path, ref, "auto", False, pn), ms_of),
+            align=(lambda: al.update(hmm.align(models, sym, offs, units, [0, L], None, LN_SWITCH)), hmm.align_last_kernel_ms)),
+            a.reps, a.warmup)
+        row.update(t)
+        for key in ("posteriors", "posteriors_occ"):
+            row[key]["us_per_frame"] = 1e3 * row[key]["kernel_ms"] / a.T
+            row[key]["over_estep"], row[key]["over_estep_min"], row[key]["over_estep_max"] = ratio(ms, key, "estep")
+            row[key]["over_align"], row[key]["over_align_min"], row[key]["over_align_max"] = ratio(ms, key, "align")
+        row["status"] = [int(al["status"][0]), int(es["status"][0]), int(po["status"][0])]
+        row["same_log_prob_bits"] = same(es, po, ("log_prob",))
+        # (a random stream does not fit a transcript of hundreds of units: where bh overflows the contract's products are inf or
+        # 0 x inf; the time of the arithmetic is what is measured, the frames are counted)
+        finite = np.isfinite(po["post_path"])
+        row["post_path_not_finite"] = int((~finite).sum())
+        row["mean_post_path"] = float(po["post_path"][finite].mean()) if finite.any() else None
+        print(json.dumps(row), flush=True)
+        doc["above"].append(row)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
