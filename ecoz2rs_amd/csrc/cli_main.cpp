@@ -106,6 +106,14 @@ static int usage()
             "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
             "                  (--grammar-continuous <name>: the inputs are consecutive pieces of one recording, decoded as one stream\n"
             "                  under the prices of --class-transitions)\n"
+            "  ecoz2 hmm segment -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15]\n"
+            "                  --switch-penalty <x <= 0 | -inf> --continuous-posteriors <name> [--block 4096] [--lookahead 4096]\n"
+            "                  [--frame-posteriors <dir>] [--body <auto|resident|looped>] [-c <csv dir|file.csv>]\n"
+            "                  (--signals <.wav files|dirs>... | --predictors <.prd files|dirs>... | --sequences <.seq files|dirs>...)\n"
+            "                  (--continuous-posteriors <name>: the inputs are consecutive pieces of one recording, decoded as one stream\n"
+            "                  and reported as --posteriors reports a recording; the posteriors of a block of --block frames are\n"
+            "                  computed once --lookahead frames behind it are known, and are conditioned on the recording up to there:\n"
+            "                  a look-ahead of at least the recording's length gives the figures of --posteriors bit for bit)\n"
             "  ecoz2 hmm transitions -m|--models <files|dirs>... [--alpha 1] -o <file.csv> <segment .csv | selection table>...\n"
             "                  (the class-to-class prices for --class-transitions, from the successions of labelled segments)\n"
             "  ecoz2 hmm transitions --em -m|--models <files|dirs>... [--codebook <cbook>] [-P 36] [-W 45] [-O 15] --switch-penalty <x>\n"
@@ -901,8 +909,10 @@ static int hmm_segment_cmd(int argc, char** argv)
     bool continuous = false;
     bool grammar = false;  // --grammar-posteriors
     bool grammar_continuous = false;
+    bool cont_post = false, have_block = false;  // --continuous-posteriors; --block or --lookahead
+    long long block = 4096, lookahead = 4096;
     bool have_grammar_body = false, have_post_body = false;
-    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, body, grammar_body, post_body;
+    std::string codebook, csv, frames_dir, transitions, rec_name, grammar_name, post_name, body, grammar_body, post_body;
     std::vector<std::string> models, signals, predictors, sequences;
     for (int i = 0; i < argc; ++i) {
         const std::string a = argv[i];
@@ -930,6 +940,9 @@ static int hmm_segment_cmd(int argc, char** argv)
         else if (a == "--grammar-posteriors-body") { post_body = val("--grammar-posteriors-body"); have_post_body = true; }
         else if (a == "--continuous") { rec_name = val("--continuous"); continuous = true; }
         else if (a == "--grammar-continuous") { grammar_name = val("--grammar-continuous"); grammar_continuous = true; }
+        else if (a == "--continuous-posteriors") { post_name = val("--continuous-posteriors"); cont_post = true; }
+        else if (a == "--block") { block = num("--block"); have_block = true; }
+        else if (a == "--lookahead") { lookahead = num("--lookahead"); have_block = true; }
         else if (a == "--frame-posteriors") frames_dir = val("--frame-posteriors");
         else if (a == "--class-transitions") transitions = val("--class-transitions");
         else if (a == "--switch-penalty") {
@@ -955,6 +968,20 @@ static int hmm_segment_cmd(int argc, char** argv)
     if (P < 1 || P > 80) { fprintf(stderr, "-P %d: prediction order out of range [1, 80]\n", P); return 2; }
     if (O < 1 || W < 1) { fprintf(stderr, "-W and -O must be positive\n"); return 2; }
     if (sequences.empty() && codebook.empty()) { fprintf(stderr, "hmm segment: --signals and --predictors need --codebook <cbook>\n"); return 2; }
+    if (cont_post) {  // (its own refusals first: the ones below speak of the other modes)
+        if (continuous || posteriors || !transitions.empty() || grammar || grammar_continuous || have_grammar_body || have_post_body) {
+            fprintf(stderr, "hmm segment: --continuous-posteriors gives the posteriors of one stream under the one switch penalty: not with "
+                            "--continuous, --posteriors, --class-transitions, --grammar-posteriors, --grammar-continuous, --grammar-body or "
+                            "--grammar-posteriors-body\n");
+            return 2;
+        }
+        if (post_name.empty()) { fprintf(stderr, "hmm segment: --continuous-posteriors <name>: the recording needs a name\n"); return 2; }
+        if (block < 1) { fprintf(stderr, "hmm segment: --block %lld: at least 1 frame\n", block); return 2; }
+        if (lookahead < 0) { fprintf(stderr, "hmm segment: --lookahead %lld: at least 0 frames\n", lookahead); return 2; }
+    } else if (have_block) {
+        fprintf(stderr, "hmm segment: --block and --lookahead need --continuous-posteriors <name> (they are its block and its look-ahead)\n");
+        return 2;
+    }
     if (have_grammar_body) {  // the body of the decoder under the prices (ECOZ2_HMM_SEGMENT_TRANS_BODY), set in this process before the call
         if (transitions.empty()) {
             fprintf(stderr, "hmm segment: --grammar-body <auto|resident|looped> needs --class-transitions <file.csv> (it chooses the body of "
@@ -988,14 +1015,14 @@ static int hmm_segment_cmd(int argc, char** argv)
         }
         if (grammar_name.empty()) { fprintf(stderr, "hmm segment: --grammar-continuous <name>: the recording needs a name\n"); return 2; }
     }
-    if (!frames_dir.empty() && !posteriors && !grammar) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
+    if (!frames_dir.empty() && !posteriors && !grammar && !cont_post) { fprintf(stderr, "hmm segment: --frame-posteriors <dir> needs --posteriors\n"); return 2; }
     if (grammar && (continuous || !body.empty())) {
         fprintf(stderr, "hmm segment: --grammar-posteriors has the resident body and whole recordings only: not with --continuous or --body\n");
         return 2;
     }
     if (!body.empty()) {  // the body of the posteriors (ECOZ2_HMM_POSTERIOR_BODY), set in this process before the call
-        if (!posteriors) { fprintf(stderr, "hmm segment: --body <auto|resident|looped> needs --posteriors\n"); return 2; }
-        if (!body_value_ok("hmm segment --posteriors", "--body", body)) return usage();
+        if (!posteriors && !cont_post) { fprintf(stderr, "hmm segment: --body <auto|resident|looped> needs --posteriors\n"); return 2; }
+        if (!body_value_ok(cont_post ? "hmm segment --continuous-posteriors" : "hmm segment --posteriors", "--body", body)) return usage();
         setenv("ECOZ2_HMM_POSTERIOR_BODY", body.c_str(), 1);
     }
     if (!transitions.empty() && posteriors) {
@@ -1025,7 +1052,11 @@ static int hmm_segment_cmd(int argc, char** argv)
     auto pm = cptrs(hmm_files), pi = cptrs(inputs);
     const char* cb = codebook.empty() ? nullptr : codebook.c_str();
     const char* out = csv.empty() ? nullptr : csv.c_str();
-    const int failed = grammar_continuous
+    const int failed = cont_post
+                           ? e2vq_hmm_segment_continuous_files_posteriors(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,
+                                                                          ln_switch, post_name.c_str(), out,
+                                                                          frames_dir.empty() ? nullptr : frames_dir.c_str(), block, lookahead)
+                       : grammar_continuous
                            ? e2vq_hmm_segment_trans_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O, ln_switch,
                                                                      transitions.c_str(), grammar_name.c_str(), out)
                        : continuous ? e2vq_hmm_segment_continuous_files(pm.data(), (unsigned)pm.size(), cb, pi.data(), (int)pi.size(), P, W, O,

@@ -307,6 +307,16 @@ std::vector<double> trans_params(const LoopModels& lm, const SegPacking& pk)
     return params;
 }
 
+// the slot check of `hmm segment --posteriors` and of its streamed form (hmm_host.h; body: what posteriors_body gave): the
+// mandatory LDS of hmm_posterior_looped.hip
+int posteriors_check_slots(const char* who, int K, const int* Ns, LoopBody body)
+{
+    const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld);
+    const e2hmm::SegPlanDev shape = loop_shape(pk, K);
+    return check_body_slots(who, pk, K, body, "the posteriors have", "the posteriors", e2hmm::posteriors_looped_lds_bytes(shape, false),
+                            /*classes=*/false);
+}
+
 namespace {
 
 thread_local float g_segment_kernel_ms = -1.f;        // e2vq_hmm_segment_last_kernel_ms
@@ -405,15 +415,6 @@ int segment_device(const LoopModels& lm, const unsigned short* d_sym, const i64*
 }
 
 // ---- hmm segment --posteriors: forward-backward through the same class loop -------------------------------
-// the slot check of the pass (body: what posteriors_body gave): the mandatory LDS of hmm_posterior_looped.hip
-int posteriors_check_slots(const char* who, int K, const int* Ns, LoopBody body)
-{
-    const SegPacking pk = pack_slots(std::vector<int>(Ns, Ns + K), posteriors_a_ld);
-    const e2hmm::SegPlanDev shape = loop_shape(pk, K);
-    return check_body_slots(who, pk, K, body, "the posteriors have", "the posteriors", e2hmm::posteriors_looped_lds_bytes(shape, false),
-                            /*classes=*/false);
-}
-
 struct PostOut {  // host arrays, any may be null; post: K doubles a frame; per stream: log_prob, status
     double* post = nullptr;
     double* log_prob = nullptr;

@@ -5,7 +5,8 @@
 // device symbols, label files; hmm_segment_stream.cpp: the streaming segment decoder; hmm_transcript.cpp: what the commands
 // that take a transcript share; hmm_align.cpp: forced alignment; hmm_embed.cpp:
 // embedded Baum-Welch on transcribed streams; hmm_align_posterior.cpp: the posteriors of the alignment; hmm_trans_train.cpp:
-// Baum-Welch for the class-to-class prices; hmm_loop_train.cpp: Baum-Welch for the class models under the class loop).
+// Baum-Welch for the class-to-class prices; hmm_loop_train.cpp: Baum-Welch for the class models under the class loop;
+// hmm_posterior_stream.cpp: the streamed class posteriors).
 // The host loads files, draws the initial model, sequences the launches, takes the logarithm of the (mantissa, exponent)
 // pairs the kernels return and the stopping decision, and prints the reports; every sum over states, time or sequences
 // that defines a model or a score runs on the GPU (no CPU fallback: without a HIP device the entry points fail).
@@ -361,6 +362,9 @@ int check_body_slots(const char* who, const SegPacking& pk, int K, LoopBody body
 // that check for the decoder under class-to-class prices (`hmm segment --class-transitions` and its session, DESIGN.md 4.8.8 /
 // 4.8.15; body: what segment_trans_body gave, or trans_fb_body where the decode follows the posteriors)
 int trans_check_slots(const char* who, int K, const int* Ns, LoopBody body);
+// and for the sum-product pass under the one price (`hmm segment --posteriors`, DESIGN.md 4.8.7, and the posterior session of
+// hmm_posterior_stream.cpp, 4.8.17; body: what posteriors_body gave)
+int posteriors_check_slots(const char* who, int K, const int* Ns, LoopBody body);
 // the K x K prices transposed, ltT[k * K + f] = lt[f * K + k]: a lane of class k walks its sources along consecutive words
 std::vector<double> trans_transposed(int K, const double* lt);
 

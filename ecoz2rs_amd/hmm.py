@@ -132,6 +132,17 @@ _sig("e2vq_hmm_segment_trans_stream_open", C.c_int, C.c_int, C.c_int, C.POINTER(
      C.POINTER(C.c_void_p))
 _sig("e2vq_hmm_segment_trans_continuous_files", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int,
      C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p)
+_sig("e2vq_hmm_posterior_stream_open", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_double,
+     C.c_int64, C.c_int64, C.POINTER(C.c_void_p))
+_sig("e2vq_hmm_posterior_stream_feed", C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int64))
+_sig("e2vq_hmm_posterior_stream_close", C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int64))
+_sig("e2vq_hmm_posterior_stream_take", C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_sig("e2vq_hmm_posterior_stream_kernel_ms", C.c_int, C.c_void_p, C.POINTER(C.c_float))
+_sig("e2vq_hmm_posterior_stream_stats", C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+     C.POINTER(C.c_int64))
+_sig("e2vq_hmm_posterior_stream_free", None, C.c_void_p)
+_sig("e2vq_hmm_segment_continuous_files_posteriors", C.c_int, c_char_pp, C.c_uint, C.c_char_p, c_char_pp, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_int64)
 _sig("e2vq_hmm_align", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dpp, _dpp, _dpp, C.c_void_p, C.c_void_p, C.c_int,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_int)
@@ -702,6 +713,95 @@ def segment_posteriors_last_kernel_ms():
     return _kernel_ms(lib.e2vq_hmm_segment_posteriors_last_kernel_ms)
 
 
+class PosteriorStream:
+    """`segment_posteriors` on one stream that arrives piece by piece: a context manager around a posterior
+    session.  models, ln_switch and body as `segment_posteriors` takes them (body: ECOZ2_HMM_POSTERIOR_BODY while the session
+    opens, which fixes its body).  block B >= 1 and lookahead L >= 0, in frames: the rows of block b = the frames
+    [b B, (b + 1) B) are ready once (b + 1) B + L symbols were fed, and are P(class at t | those symbols) -- the bits of
+    `segment_posteriors` on that prefix; `close()` delivers the rest, conditioned on the whole stream.  `feed(sym)` (numpy, or
+    a device tensor), `close()` and `take()` return (first, post): the absolute frame of the first row that became ready with
+    the call, and the rows (count, K).  After `close`, log_prob and status are set (a stream of status 1 or 2: the rows that
+    were not delivered before the event come as 0.0 with close, log_prob is -inf; the feed or close that meets a symbol >= M
+    raises, and `take()` then hands out what is ready)."""
+
+    def __init__(self, models, ln_switch, block=4096, lookahead=4096, device=0, body=None):
+        self._h = C.c_void_p()  # (first: free, which __del__ calls, reads it whatever fails below)
+        K = len(models)
+        ms = [tuple(np.ascontiguousarray(x, dtype=np.float64) for x in m) for m in models]
+        Ns = (C.c_int * max(K, 1))(*[len(m[0]) for m in ms])
+        ptr = lambda i: (C.c_void_p * max(K, 1))(*[m[i].ctypes.data for m in ms])
+        M = ms[0][2].shape[1] if K else 0
+        self.K = K
+        self.ready_frames_ = 0
+        self._taken = 0  # rows handed out so far
+        self.log_prob = None
+        self.status = None
+        with _body_env("ECOZ2_HMM_POSTERIOR_BODY", body):
+            check(lib.e2vq_hmm_posterior_stream_open(device, K, Ns, M, ptr(0), ptr(1), ptr(2), float(ln_switch), int(block),
+                                                     int(lookahead), C.byref(self._h)))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def free(self):
+        if self._h:
+            lib.e2vq_hmm_posterior_stream_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = free
+
+    @property
+    def ready_frames(self):
+        """frames delivered so far"""
+        return self.ready_frames_
+
+    def take(self):
+        """(first, post): the rows that are ready and were not handed out yet"""
+        n = max(self.ready_frames_ - self._taken, 0)  # (what waits in the session, not the stream so far)
+        post = np.zeros((max(n, 1), max(self.K, 1)))
+        first, count = C.c_int64(), C.c_int64()
+        check(lib.e2vq_hmm_posterior_stream_take(self._h, n, post.ctypes.data, C.byref(first), C.byref(count)))
+        self._taken = first.value + count.value
+        return first.value, post[:count.value]
+
+    def feed(self, sym):
+        on_device = hasattr(sym, "data_ptr")
+        if on_device:
+            if not sym.is_contiguous() or sym.element_size() != 2:
+                raise ValueError("a device symbol tensor must be contiguous with 2-byte elements")
+            sym_ptr, n = sym.data_ptr(), sym.numel()
+        else:
+            sym = np.ascontiguousarray(sym, dtype=np.uint16)
+            sym_ptr, n = sym.ctypes.data, sym.size
+        ready = C.c_int64()
+        rc = lib.e2vq_hmm_posterior_stream_feed(self._h, sym_ptr, n, int(on_device), C.byref(ready))
+        self.ready_frames_ = max(self.ready_frames_, ready.value)  # (a feed that fails may have delivered blocks before it did)
+        check(rc)
+        return self.take()
+
+    def close(self):
+        lp, st, ready = C.c_double(), C.c_int(-1), C.c_int64(-1)
+        rc = lib.e2vq_hmm_posterior_stream_close(self._h, C.byref(lp), C.byref(st), C.byref(ready))
+        if ready.value >= 0:  # (a close that meets a symbol >= M fails after it has set its outputs)
+            self.ready_frames_, self.log_prob, self.status = ready.value, lp.value, st.value
+        check(rc)
+        return self.take()
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        check(lib.e2vq_hmm_posterior_stream_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def stats(self):
+        """dict device_bytes, ring_rows, launches, backward_frames (the frames the backward passes walked)"""
+        by, rows, ln, bw = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib.e2vq_hmm_posterior_stream_stats(self._h, C.byref(by), C.byref(rows), C.byref(ln), C.byref(bw)))
+        return dict(device_bytes=by.value, ring_rows=rows.value, launches=ln.value, backward_frames=bw.value)
+
+
 def segments_of_trans(cls, entered, exit_score, log_prob, ln_trans):
     """`segments_of` under the K x K prices ln_trans: the segment that starts at b > 0 paid
     ln_trans[cls[b - 1]][cls[b]]"""
@@ -1052,7 +1152,8 @@ def learn_loop_files(model_filenames, input_filenames, out_dir, ln_switch, class
 
 def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=36, W_ms=45, O_ms=15, csv=None, posteriors=False,
                   frame_posteriors=None, class_transitions=None, continuous=None, body=None, grammar_posteriors=False,
-                  grammar_continuous=None, grammar_body=None, grammar_posteriors_body=None):
+                  grammar_continuous=None, grammar_body=None, grammar_posteriors_body=None, continuous_posteriors=None, block=4096,
+                  lookahead=4096):
     """`hmm segment`: every input (.wav, .prd or .seq) decoded once under the models; per input a block on
     stdout and, with `csv` (a directory, or a .csv file for one input), a CSV of the segments.  posteriors (4.8.7): each
     segment's mean and least class posterior in the block and the CSV, and with frame_posteriors (a directory) a per-frame
@@ -1065,9 +1166,23 @@ def segment_files(model_filenames, input_filenames, ln_switch, codebook=None, P=
     file's prices; it excludes continuous, the posteriors, frame_posteriors and body.  grammar_body ("auto", "resident" or
     "looped", as `segment_trans` takes body): the kernel body of the decoder under class_transitions, with or without
     grammar_continuous; it needs class_transitions and excludes grammar_posteriors, whose one choice is
-    grammar_posteriors_body"""
+    grammar_posteriors_body.  continuous_posteriors (4.8.17): the name of the one recording whose consecutive pieces the inputs
+    are, decoded as by continuous and reported as by posteriors (one block, one CSV, and with frame_posteriors
+    <frame_posteriors>/<name>.csv), the posteriors of a block of `block` frames conditioned on the recording up to `lookahead`
+    frames behind it; it takes body and frame_posteriors and excludes every other mode"""
     m, _k1 = _strs(model_filenames)
     f, _k2 = _strs(input_filenames)
+    if continuous_posteriors is not None:
+        if (continuous is not None or posteriors or class_transitions is not None or grammar_posteriors or grammar_continuous is not None
+                or grammar_body is not None or grammar_posteriors_body is not None):
+            raise ValueError("continuous_posteriors excludes continuous, posteriors, class_transitions, grammar_posteriors, "
+                             "grammar_continuous, grammar_body and grammar_posteriors_body")
+        with _body_env("ECOZ2_HMM_POSTERIOR_BODY", body):
+            check(lib.e2vq_hmm_segment_continuous_files_posteriors(
+                m, len(model_filenames), str(codebook).encode() if codebook else None, f, len(input_filenames), int(P), int(W_ms),
+                int(O_ms), float(ln_switch), str(continuous_posteriors).encode(), str(csv).encode() if csv else None,
+                str(frame_posteriors).encode() if frame_posteriors is not None else None, int(block), int(lookahead)))
+        return
     if grammar_body is not None:
         if class_transitions is None:
             raise ValueError("grammar_body needs class_transitions")

@@ -684,6 +684,61 @@ int e2vq_hmm_segment_trans_continuous_files(const char *const *model_filenames, 
                                             double ln_switch, const char *transitions_csv, const char *name,
                                             const char *csv_dir_or_file);
 
+/* ---- the class posteriors on a stream that arrives piece by piece -------------------------------------
+ * `hmm segment --continuous-posteriors`: a session over ONE symbol stream of unknown length under the contract of
+ * e2vq_hmm_segment_posteriors (K models sharing M, one ln_switch; the same sw, e, forward pass, GS, scaling, backward pass,
+ * posterior and scale_step, each one IEEE double operation in that order).  Two integers are fixed at open: a block length
+ * B >= 1 and a look-ahead L >= 0, in frames.  Block b is the absolute frames [b B, (b + 1) B); its window end is
+ * w_b = (b + 1) B + L while the stream is open, and T, the number of symbols fed, at close.
+ * The result.  The K posteriors delivered for frame t of block b are, bit for bit, row t of e2vq_hmm_segment_posteriors run
+ * on the prefix o[0 : w_b) of everything fed: P(class at t | the first w_b symbols).  Hence every block with
+ * (b + 1) B + L >= T gets the closed pass's bits on the whole stream, and a session with L >= T is
+ * e2vq_hmm_segment_posteriors bit for bit; log_prob at close is the closed pass's bit for bit (the (mantissa, exponent) pair
+ * is carried in the session).  The rows, and the number of rows ready after p symbols -- the blocks with (b + 1) B + L <= p --
+ * depend on (B, L) and the first p symbols alone, however they were fed; close delivers the rest.  Nothing fed: status 0,
+ * log_prob 0.0, no rows.  Delivered rows wait in host memory (8 K bytes a frame) until e2vq_hmm_posterior_stream_take hands
+ * them out, in order.
+ * Status.  The first event in frame order decides, as there: a symbol >= M gives 2, !(c_t > 0) gives 1, and the symbol check
+ * of a frame comes before its arithmetic.  The launch whose forward pass meets the event delivers no rows; rows delivered
+ * earlier stay; every other row of everything fed is delivered as +0.0, by close.  2: the feed (or close) that meets it
+ * fails with a message naming the absolute frame, and further feeds are refused.  1: further feeds are accepted, are counted
+ * and do nothing.  In both cases close reports the status and log_prob = -inf (a close that itself meets status 2 fails
+ * with the message after it has set its outputs and closed the session).  The equality with the closed pass is not claimed
+ * for such a stream: the closed pass zeroes every row.
+ * Memory.  ah_t, c_t and the symbol of the last B + L frames stay on the device in a ring of exactly B + L rows (frame t in
+ * row t mod (B + L)), next to the parameters and the rows of one launch: nothing on the device grows with a feed or with
+ * the stream.  The forward pass runs over every frame once; the backward pass of window b walks from w_b - 1 down to b B.
+ * Refused before any HIP call: what e2vq_hmm_segment_posteriors refuses (more than 16 wave-slots word for word, unless
+ * ECOZ2_HMM_POSTERIOR_BODY, read at open, is auto or looped), B < 1, L < 0.  A ring that cannot be allocated fails with a
+ * message that gives its bytes.  A NULL session, a feed after close or after status 2, and a second close are refused.
+ * One thread at a time uses a session. */
+typedef struct e2vq_posterior_stream e2vq_posterior_stream;
+int e2vq_hmm_posterior_stream_open(int device, int K, const int *Ns, int M, const double *const *pis, const double *const *As,
+                                   const double *const *Bs, double ln_switch, int64_t block, int64_t lookahead,
+                                   e2vq_posterior_stream **out);
+/* n >= 0 symbols (u16; sym_on_device: a device pointer on the session's device); *ready_frames: all frames delivered so far.
+ * The launches of a feed are queued on the session's stream with one synchronisation at the end. */
+int e2vq_hmm_posterior_stream_feed(e2vq_posterior_stream *s, const void *sym, int64_t n, int sym_on_device, int64_t *ready_frames);
+int e2vq_hmm_posterior_stream_close(e2vq_posterior_stream *s, double *log_prob, int *status, int64_t *ready_frames);
+/* up to max_frames delivered rows (K doubles each; post may be NULL) from the absolute frame *first_frame on */
+int e2vq_hmm_posterior_stream_take(e2vq_posterior_stream *s, int64_t max_frames, double *post, int64_t *first_frame, int64_t *count);
+/* HIP-event time of all launches of the session so far (per feed: first launch to last, the copies between them included) */
+int e2vq_hmm_posterior_stream_kernel_ms(e2vq_posterior_stream *s, float *ms);
+/* the device bytes of the session; the rows of its ring; the launches so far; the frames their backward passes walked.
+ * Each may be NULL. */
+int e2vq_hmm_posterior_stream_stats(e2vq_posterior_stream *s, int64_t *device_bytes, int64_t *ring_rows, int64_t *launches,
+                                    int64_t *backward_frames);
+void e2vq_hmm_posterior_stream_free(e2vq_posterior_stream *s);
+/* The file form: the inputs, in the order given, are consecutive pieces of ONE recording called `name`, as
+ * e2vq_hmm_segment_continuous_files takes them.  Each piece is staged once and fed, on the device, to a session of
+ * e2vq_hmm_segment_stream_open and to a posterior session (block, lookahead); e2vq_hmm_segment_report_posteriors(name, ...)
+ * then writes the block, the CSV with posterior,min_posterior and, with frames_dir (may be NULL), <frames_dir>/<name>.csv.
+ * The host keeps the T K doubles of the posteriors for that report. */
+int e2vq_hmm_segment_continuous_files_posteriors(const char *const *model_filenames, unsigned num_models, const char *cb_filename,
+                                                 const char *const *input_filenames, int num_inputs, int P, int W_ms, int O_ms,
+                                                 double ln_switch, const char *name, const char *csv_dir_or_file,
+                                                 const char *frames_dir, int64_t block, int64_t lookahead);
+
 /* ---- forced alignment to a known order of units ----------------------------------------------------------
  * `hmm align`: where are the boundaries of units whose classes and order are known?  K models sharing M (the checks of
  * e2vq_hmm_segment), S symbol streams (sym, offs), and for stream s a transcript of L_s >= 1 units: units[unit_offs[s] ..
